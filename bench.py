@@ -272,6 +272,33 @@ def exact_halo_mode(lib, devices, shape, psf_edge, n_views, steps, warmup, check
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE = 2 << 20  # voxels of the seeded sample of a volume too large to be written whole
+DUMP_SEED = 20261015
+
+
+def dump_outputs(out_dir, psi):
+    """--dump-outputs: psi after the last timed step (what a caller of the engine receives) as float32 .npy files in
+    `out_dir`, at most DUMP_MAX_BYTES in all.  A volume of up to half that size is written whole (psi.npy); a larger
+    one as a fixed, seeded sample of its voxels (psi_sample.npy, their flat indices in psi_sample_index.npy, float64)
+    and, where it fits, its middle dim0 plane (psi_mid_plane.npy).  Returns the names and sizes written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    psi = np.ascontiguousarray(psi, dtype=np.float32)
+    if psi.nbytes <= DUMP_MAX_BYTES // 2:
+        arrays = {"psi": psi}
+    else:
+        idx = np.random.default_rng(DUMP_SEED).integers(0, psi.size, DUMP_SAMPLE, dtype=np.int64)
+        arrays = {"psi_sample": psi.reshape(-1)[idx], "psi_sample_index": idx.astype(np.float64)}
+        plane = psi[psi.shape[0] // 2]
+        if sum(a.nbytes for a in arrays.values()) + plane.nbytes <= DUMP_MAX_BYTES:
+            arrays["psi_mid_plane"] = plane
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "psi_shape": list(psi.shape),
+            "files": {name + ".npy": {"shape": list(a.shape), "dtype": str(a.dtype)} for name, a in arrays.items()}}
+
+
 def measured_traffic(kind, shape):
     """HBM bytes per launch of the dominant kernel from the PMC counters, collected NOW: two rocprofv3 passes
     (FETCH_SIZE; WRITE_SIZE) of child processes that run tools/pmc_probe.py on this GPU, corrected as
@@ -336,6 +363,9 @@ def main():
     ap.add_argument("--check-parity", action="store_true",
                     help="N > 1: rank 0 still runs the one-view parity check / CPU sample (default: N = 1 only)")
     ap.add_argument("--dump-psi", default=None, help="rank 0 saves the final psi here (.npy)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the timed path computed (psi after the last timed step) as DIR/<name>.npy, "
+                         "float32, at most 64 MB in all (a fixed, seeded sample of a larger volume)")
     ap.add_argument("--exact-halo-child", default=None, metavar="DEVICES",
                     help="internal: run only the exact_halo_mode measurement on these devices (comma separated) and "
                          "print its JSON block (the N > 1 lines start it as a child process with a time limit)")
@@ -462,6 +492,7 @@ def run_rank(args, world_env):
         psi_ok = bool(np.isfinite(psi).all() and (psi > 0).all())
         if args.dump_psi:
             np.save(args.dump_psi, psi)
+        dumped = dump_outputs(args.dump_outputs, psi) if args.dump_outputs else None
         ms_per_step = elapsed / args.steps * 1e3
         value = args.steps / elapsed  # iterations/s of the WHOLE problem, at every N
         d0, d1, d2 = shape
@@ -543,6 +574,8 @@ def run_rank(args, world_env):
             "psi_finite_positive": psi_ok,
             "roofline": roofline,
         }
+        if dumped:
+            out["dump_outputs"] = dumped
         if driver is None:
             # what the 8-pass pipeline actually moves per (view, iteration), DESIGN.md section 4: 22 volumes
             # with the fused FFT dim0 pass, 20 + 2 K / d0 with the direct dim0 leg (K PSF planes)

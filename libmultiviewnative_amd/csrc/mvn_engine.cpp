@@ -713,7 +713,7 @@ Engine::Engine(int device, const shape_t& dims, int num_views) : device_(device)
   be::dzero(psi_, mb, stream_);
   be::dzero(work_, mb, stream_);
   if (plan_->nyq_bytes()) work_nyq_ = (cfloat*)be::dmalloc(plan_->nyq_bytes());
-  poison_own_ = (unsigned*)be::dmalloc(256);  // the word, and at byte 64 the table of the peers' words
+  poison_own_ = (unsigned*)be::dmalloc(256);  // the words, and at bytes 64 / 128 the tables of the peers' words
   be::dzero(poison_own_, 256, stream_);
   poison_ = poison_own_;
   views_.resize((size_t)num_views);
@@ -1016,14 +1016,14 @@ void Engine::dim0_conv(const ViewSlot& s, int i, const cfloat* in, const cfloat*
   // non-finite inputs are reported under this leg's epoch (never 0, never a value the word may still hold); the
   // launches of one leg (a slab's interior planes, then those next to its halos) share it
   if (first && ++epoch_ == 0x7fffffffu) {
-    be::dzero(poison_, sizeof(unsigned), stream_);
+    be::dzero(poison_, poison_bytes(), stream_);
     epoch_ = 1;
   }
   armed_epoch_ = epoch_;
-  p.poison = poison_;
+  p.poison = poison_word(epoch_);
   p.poison_epoch = epoch_;
   p.n_peers = (int)poison_peers_.size();
-  p.poison_peers = (unsigned* const*)(poison_own_ + 16);
+  p.poison_peers = poison_table(epoch_);
   if (packed_) {
     p.packed = 1;
     p.taps2 = s.taps_nyq[i];
@@ -1048,12 +1048,14 @@ void Engine::dim0_conv(const ViewSlot& s, int i, const cfloat* in, const cfloat*
 }
 
 void Engine::arm(EpilogueParams& e) {
-  e.poison = armed_epoch_ ? poison_ : nullptr;
+  e.poison = armed_epoch_ ? poison_word(armed_epoch_) : nullptr;
   e.poison_epoch = armed_epoch_;
   armed_epoch_ = 0;
 }
 
 void Engine::bind_poison(unsigned* external) {
+  // (an engine with peers keeps two words of its own, poison_word: a caller-bound word of 4 bytes cannot be one)
+  if (external && !poison_peers_.empty()) throw std::logic_error("mvn: bind_poison on an engine with poison peers");
   be::set_device(device_);
   be::stream_sync(stream_);
   be::graph_destroy(sweep_graph_);  // a captured sweep holds the word's address
@@ -1065,16 +1067,16 @@ void Engine::bind_poison(unsigned* external) {
 
 unsigned Engine::poison_get() {
   be::set_device(device_);
-  unsigned v = 0;
-  be::d2h(&v, poison_, sizeof(v), stream_);
+  unsigned v[2] = {0, 0};
+  be::d2h(v, poison_, poison_bytes(), stream_);
   be::stream_sync(stream_);
-  return v;
+  return v[0] > v[1] ? v[0] : v[1];  // (with peers: the later report of the two words)
 }
 
 // word = max(word, value): epochs only grow, so the larger one is the later report
 void Engine::poison_merge(unsigned value) {
   if (value > poison_get()) {
-    be::h2d(poison_, &value, sizeof(value), stream_);
+    be::h2d(poison_word(value), &value, sizeof(value), stream_);
     be::stream_sync(stream_);  // (`value` is a stack variable)
   }
 }
@@ -1082,10 +1084,14 @@ void Engine::poison_merge(unsigned value) {
 void Engine::add_poison_peer(unsigned* word) {
   if (!word) throw std::invalid_argument("mvn: null poison word");
   if ((int)poison_peers_.size() >= MVN_D0_MAX_PEERS) throw std::invalid_argument("mvn: too many poison peers");
+  if (poison_ != poison_own_) throw std::logic_error("mvn: poison peers on an engine with a caller-bound word");
   be::set_device(device_);
   be::stream_sync(stream_);
   poison_peers_.push_back(word);
+  std::vector<unsigned*> odd(poison_peers_);  // the peers' words of the odd epochs (poison_word)
+  for (size_t i = 0; i < odd.size(); ++i) ++odd[i];
   be::h2d(poison_own_ + 16, poison_peers_.data(), poison_peers_.size() * sizeof(unsigned*), stream_);
+  be::h2d(poison_own_ + 32, odd.data(), odd.size() * sizeof(unsigned*), stream_);
   be::stream_sync(stream_);
 }
 
@@ -1146,12 +1152,13 @@ void Engine::mid_fused_conv(const ViewSlot& s, int i, Profiler* prof, int zbeg, 
   if (!s.taps_l_ok[i] || !s.tap_k[i]) throw std::logic_error("mvn: fused middle pass with a kernel that is not in its form");
   ensure_work2();
   if (++epoch_ == 0x7fffffffu) {
-    be::dzero(poison_, sizeof(unsigned), stream_);
+    be::dzero(poison_, poison_bytes(), stream_);
     epoch_ = 1;
   }
   armed_epoch_ = epoch_;
-  plan_->mid_fused((const cfloat*)work_, (cfloat*)work2_, (const cfloat*)s.taps_l[i], s.tap_k[i], s.tap_kd[i], poison_,
-                   epoch_, stream_, prof, zbeg, zcount, (int)poison_peers_.size(), (unsigned* const*)(poison_own_ + 16));
+  plan_->mid_fused((const cfloat*)work_, (cfloat*)work2_, (const cfloat*)s.taps_l[i], s.tap_k[i], s.tap_kd[i],
+                   poison_word(epoch_), epoch_, stream_, prof, zbeg, zcount, (int)poison_peers_.size(),
+                   poison_table(epoch_));
   std::swap(work_, work2_);
   std::swap(work_nyq_, work2_nyq_);
 }
@@ -1599,7 +1606,7 @@ void Engine::iterate(int iterations, double lambda, float min_value) {
         be::capture_begin(stream_);
         try {
           // (a replay reports under the epochs of the capture: the word must not still hold one of them)
-          be::dzero(poison_, sizeof(unsigned), stream_);
+          be::dzero(poison_, poison_bytes(), stream_);
           for (int v = 0; v < V; ++v) conv_pair(v, lambda, min_value, MVN_EPI_UPDATE, 0, true);
         } catch (...) {
           try {
@@ -1804,12 +1811,12 @@ void Engine::compute_delta_head(double lambda, float min_value) {
       // line layout: psi's last-axis spectrum -> ONE middle pass -> fused divide -> ONE middle pass -> correction
       if (!s.taps_l_ok[0] || !s.tap_k[0]) throw std::logic_error("mvn: fused middle pass with a kernel that is not in its form");
       if (++epoch_ == 0x7fffffffu) {
-        be::dzero(poison_, sizeof(unsigned), stream_);
+        be::dzero(poison_, poison_bytes(), stream_);
         epoch_ = 1;
       }
       armed_epoch_ = epoch_;
-      P.mid_fused((const cfloat*)psi_spec_, (cfloat*)work_, (const cfloat*)s.taps_l[0], s.tap_k[0], s.tap_kd[0], poison_,
-                  epoch_, stream_, prof);
+      P.mid_fused((const cfloat*)psi_spec_, (cfloat*)work_, (const cfloat*)s.taps_l[0], s.tap_k[0], s.tap_kd[0],
+                  poison_word(epoch_), epoch_, stream_, prof);
       arm(e1);
       P.rows_c2r_r2c((cfloat*)work_, nullptr, e1, stream_, prof, 0, -1, true);
       mid_fused_conv(s, 1, prof);

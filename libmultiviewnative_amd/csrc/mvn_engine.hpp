@@ -437,8 +437,17 @@ class Engine {
   int halo_planes_ = 0;
   bool halo_ranged() const;
   unsigned* poison_ = nullptr;      // the word in use: poison_own_, or caller-owned memory (bind_poison)
-  unsigned* poison_own_ = nullptr;  // 256 bytes: [0] the engine's own word, byte 64: table of the peers' words
+  unsigned* poison_own_ = nullptr;  // 256 bytes: [0] / [1] the engine's own words, bytes 64 / 128: tables of the peers'
   std::vector<unsigned*> poison_peers_;
+  // The word a leg of `epoch` reports to (and the last-axis pass that ends its convolution reads), and the table of
+  // the peers' words it reports to as well.  With peers (the slabs of one volume, mvn_multi.cpp) the words alternate
+  // with the epoch's parity: another slab's NEXT leg may already report while this slab's last-axis pass still has
+  // to read the current epoch (boundary-first order: the interior planes of that pass run after the exchange has
+  // begun), so it must not overwrite that word; a leg two epochs on follows the peers' next leg, and with it their
+  // last-axis pass (HaloGroup::behind_leg).
+  unsigned* poison_word(unsigned epoch) const { return poison_peers_.empty() ? poison_ : poison_own_ + (epoch & 1u); }
+  unsigned* const* poison_table(unsigned epoch) const { return (unsigned* const*)(poison_own_ + 16 + 16 * (epoch & 1u)); }
+  size_t poison_bytes() const { return (poison_peers_.empty() ? 1 : 2) * sizeof(unsigned); }
   unsigned epoch_ = 0;        // direct dim0 legs enqueued so far = the epoch of the latest
   unsigned armed_epoch_ = 0;  // != 0: the convolution in flight ran a direct leg with this epoch
   // hands the report of the convolution's direct leg (if it had one) to the last-axis pass that ends it
