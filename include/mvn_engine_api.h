@@ -53,7 +53,7 @@ MVN_API const char* mvn_get_pad_mode(void);
  * process start. */
 MVN_API int mvn_psf_cache_counters(long out[2]);
 /* passes launched through the long-line (16-column, split-window) kernels since process start
- * (test / diagnostics; MVN_NO_SPLIT=1 keeps the 8-column kernels) */
+ * (test / diagnostics) */
 MVN_API long mvn_split_launch_count(void);
 /* launches of the fused middle pass (dim1 forward + direct dim0 leg + dim1 inverse in one pass over the line layout;
    csrc/mvn_mid_fused.hpp) since process start: tests check that the shapes that have it take it */

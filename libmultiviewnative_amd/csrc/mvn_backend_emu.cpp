@@ -151,11 +151,9 @@ void graph_destroy(graph_exec_t) {}
 // same knobs as the HIP backend, but read at every launch and with every pass enabled by default
 // (the emulation exists to test them)
 static bool emu_wave_rows(const RowsParams& p, int kind_bit) {
-  const char* e = std::getenv("MVN_NO_WAVE_ROWS");
   const char* m = std::getenv("MVN_WAVE_ROWS_MASK");
   const int mask = m && *m ? std::atoi(m) : 31;
-  return !(e && *e && std::strcmp(e, "0") != 0) && (mask & kind_bit) && p.fixed && !p.lines && p.h == WrCfg::H &&
-         p.C == WrCfg::H;
+  return (mask & kind_bit) && p.fixed && !p.lines && p.h == WrCfg::H && p.C == WrCfg::H;
 }
 
 template <int MODE, int EPI>
@@ -365,9 +363,7 @@ template <int N>
 static bool emu_try_split(int mode, const StridedParams& p, long nblocks) {
   if constexpr (FxSplitCfg<N>::USE) {
     typedef FxSplitCfg<N> C;
-    const char* e = std::getenv("MVN_NO_SPLIT");
-    if ((e && *e && std::strcmp(e, "0") != 0) || mode == MVN_ST_FWD_MUL_INV || p.cstride != 1 ||
-        p.ncols % C::T != 0 || p.tiles_per_outer < 1)
+    if (mode == MVN_ST_FWD_MUL_INV || p.cstride != 1 || p.ncols % C::T != 0 || p.tiles_per_outer < 1)
       return false;
     StridedParams q = p;
     const long outer = nblocks / p.tiles_per_outer;

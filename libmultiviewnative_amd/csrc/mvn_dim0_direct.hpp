@@ -14,8 +14,8 @@
 // FFT - and, what counts on MI355X (profiles/r03_mem_counters.md: a pass costs 0.16 ms per READ
 // volume at 512^3, its writes ride along), it reads the volume plus K / d0 of a volume of taps (6 %)
 // where the fused FFT pass reads the volume plus a whole PSF spectrum: 0.20 - 0.22 ms instead of
-// 0.32 ms at K = 31 (tools/dim0_direct_probe.hip), and the PSF costs 2 K / d0 volumes of HBM per
-// view instead of 2.
+// 0.32 ms at K = 31 (`tools/dim0_direct_probe.hip` (removed; see git history before this change)),
+// and the PSF costs 2 K / d0 volumes of HBM per view instead of 2.
 //
 // A work item owns ONE bin and walks along dim0 with its K taps and the K + PF most recent / next
 // input values in registers (PF planes are requested ahead of their first use).  The walk is
@@ -76,13 +76,8 @@ struct Dim0DirectParams {
   int zbeg, zcount;
 };
 
-#ifndef MVN_D0_PF
-#define MVN_D0_PF 4         // planes requested ahead
-#endif
-#ifndef MVN_D0_CHAINS
-#define MVN_D0_CHAINS 2     // independent pairs of multiply-add chains per output (1 or 2)
-#endif
-#define MVN_D0_MAX_TAPS 33  // largest instantiated K
+constexpr int MVN_D0_PF = 4;  // planes requested ahead
+#define MVN_D0_MAX_TAPS 33     // largest instantiated K
 
 // K the direct kernel is instantiated for: k itself if odd, else k + 1 (one zero tap)
 inline int mvn_dim0_taps_template(int k) { return k | 1; }
@@ -380,12 +375,6 @@ MVN_HD void mvn_dim0_step(Dim0Window<K, PF>& r, Dim0Walk& w, unsigned b, int nou
   constexpr int KW = K + PF;
   if (nn + U >= nout) return;  // nout outputs in all, the walk is cyclic
   cfloat s1, s2;
-#if defined(MVN_EXPERIMENTS) && defined(MVN_D0_EXP_TAPS)
-  s1 = s2 = cmake(0.f, 0.f);
-  // timing experiment (variant builds only, WRONG results): the walk with only the first few multiply-adds
-#pragma unroll
-  for (int j = 0; j < (K < MVN_D0_EXP_TAPS ? K : MVN_D0_EXP_TAPS); ++j) mvn_cmac2(s1, s2, r.w[(j + PF - U + KW) % KW], r.tap[j]);
-#elif MVN_D0_CHAINS == 2
   // even and odd taps in chains of their own: four instructions between a multiply-add and the next one of its
   // chain - the compiler asks for two between inline instructions and fills what is missing with wait states
   mvn_cmul2(s1, s2, r.w[(PF - U + KW) % KW], r.tap[0]);
@@ -401,11 +390,6 @@ MVN_HD void mvn_dim0_step(Dim0Window<K, PF>& r, Dim0Walk& w, unsigned b, int nou
     s1 = cadd(s1, t1);
     s2 = cadd(s2, t2);
   }
-#else
-  mvn_cmul2(s1, s2, r.w[(PF - U + KW) % KW], r.tap[0]);
-#pragma unroll
-  for (int j = 1; j < K; ++j) mvn_cmac2(s1, s2, r.w[(j + PF - U + KW) % KW], r.tap[j]);
-#endif
   mvn_dim0_st(w.pout, b, w.bytes, cadd_i<+1>(s1, s2));  // (s1.x - s2.y, s1.y + s2.x)
   // x_0 = in[z + h] runs over every plane of the column once: tracked HERE, where it has long arrived
   // (at its load the check would stall on the request that was just issued)

@@ -16,6 +16,7 @@ namespace mvn {
 
 static const size_t kLdsSoftBudget = 80 * 1024;   // two workgroups per CU (160 KiB LDS)
 static const size_t kLdsHardBudget = 160 * 1024;  // one workgroup may own the whole CU
+static const size_t kSideMinBytes = 16u << 20;    // volumes above this use the side stream (see Engine::conv_pair)
 
 const char* kernel_kind_name(int k) {
   static const char* names[KK_COUNT] = {"rows_r2c",    "rows_c2r",  "rows_fused_div",
@@ -120,8 +121,6 @@ DevAxis::~DevAxis() {
   be::dfree(bhat);
 }
 
-// tuning knobs for experiments (not part of the ABI): MVN_T_ROWS / MVN_T_AXIS / MVN_T_FUSED cap
-// the tile width of the three pass families, MVN_THREADS fixes the workgroup size
 static int env_int(const char* name, int dflt) {
   const char* v = std::getenv(name);
   return (v && *v) ? std::atoi(v) : dflt;
@@ -132,8 +131,7 @@ PassGeom Plan3D::pick_geom(int n, bool generic, bool rows, int max_t) {
   PassGeom g;
   bool found = false;
   for (int pass = 0; pass < 2 && !found; ++pass) {
-    size_t budget = pass == 0 ? kLdsSoftBudget : kLdsHardBudget;
-    if (pass == 0 && env_int("MVN_LDS_SOFT_KB", 0) > 0) budget = (size_t)env_int("MVN_LDS_SOFT_KB", 0) * 1024;
+    const size_t budget = pass == 0 ? kLdsSoftBudget : kLdsHardBudget;
     for (int i = 0; i < 5; ++i) {
       const int T = cand[i];
       if (T > max_t) continue;
@@ -170,8 +168,6 @@ PassGeom Plan3D::pick_geom(int n, bool generic, bool rows, int max_t) {
   // one radix-8 butterfly per thread and stage when the tile is big enough
   const long work = (long)n * g.T / 8;
   g.threads = work >= 512 ? 512 : (work >= 256 ? 256 : (work >= 128 ? 128 : 64));
-  const int forced = env_int("MVN_THREADS", 0);
-  if (forced >= 64 && forced <= 512 && forced % 64 == 0) g.threads = forced;
   return g;
 }
 
@@ -213,12 +209,10 @@ Plan3D::Plan3D(int dev, int d0, int d1, int d2)
     be::stream_sync(nullptr);
   }
   // LDS rows per tile = length of the radix transform (the chirp-z length for bluestein axes)
-  g_rows = pick_geom(ax2.host.nfft, ax2.host.generic, true, env_int("MVN_T_ROWS", 16));
-  g_ax1 = pick_geom(ax1.host.nfft, ax1.host.generic, false, env_int("MVN_T_AXIS", 16));
-  g_ax0 = pick_geom(ax0.host.nfft, ax0.host.generic, false, env_int("MVN_T_AXIS", 16));
-  // the fused pass has its own geometry so that it can be tuned apart (measured on MI355X at
-  // 512^3: T=16 0.46 ms, T=8 0.63 ms)
-  g_ax0f = pick_geom(ax0.host.nfft, ax0.host.generic, false, env_int("MVN_T_FUSED", 16));
+  // widest tile 16 for all three pass families (the fused pass on MI355X at 512^3: T=16 0.46 ms, T=8 0.63 ms)
+  g_rows = pick_geom(ax2.host.nfft, ax2.host.generic, true, 16);
+  g_ax1 = pick_geom(ax1.host.nfft, ax1.host.generic, false, 16);
+  g_ax0 = pick_geom(ax0.host.nfft, ax0.host.generic, false, 16);
   g_nyq1 = g_ax1;
   g_nyq0 = g_ax0;
   g_nyq1_line = pick_geom(ax1.host.nfft, ax1.host.generic, false, 1);  // one line per workgroup (riders)
@@ -538,18 +532,6 @@ void Plan3D::axis1(int mode, cfloat* data, cfloat* nyq, be::stream_t s, Profiler
   }
 }
 
-// The Nyquist plane's dim1 transforms ride in the main array's launches where those are the fixed-length walking
-// kernels (MVN_NYQ_RIDE=0: launches of their own, on the stream the caller names, as in rounds 1 - 3)
-bool Plan3D::nyq_rides() const {
-  static const bool off = env_int("MVN_NYQ_RIDE", 1) == 0;  // A/B knob
-  return fx_ax1 && !off;
-}
-
-bool Plan3D::tiles_spectra() const {
-  static const bool off = env_int("MVN_NO_TILED_SPECTRA", 0) != 0;  // A/B knob
-  return fx_ax0 && !off;
-}
-
 void Plan3D::retile_spectrum(const cfloat* natural, cfloat* tiled, be::stream_t s) const {
   const long cols = (long)L.d1 * L.C;
   const int T = gx_ax0.T;
@@ -568,7 +550,7 @@ void Plan3D::axis0(int mode, cfloat* data, cfloat* nyq, const cfloat* spec,
     // main array viewed as [d0][d1*C]: lines along d0, all (d1, bin) columns are contiguous
     const long cols = (long)L.d1 * L.C;
     if (cols > 0x7fffffffL) throw std::invalid_argument("mvn: d1*d2 too large");
-    const PassGeom& g = fx_ax0 ? gx_ax0 : (mode == MVN_ST_FWD_MUL_INV ? g_ax0f : g_ax0);
+    const PassGeom& g = fx_ax0 ? gx_ax0 : g_ax0;
     StridedParams p = make_strided(ax0, g, data, spec, 0, cols, 1, (int)cols);
     p.fixed = fx_ax0 ? 1 : 0;
     p.src = src;
@@ -718,7 +700,7 @@ Engine::Engine(int device, const shape_t& dims, int num_views) : device_(device)
   poison_ = poison_own_;
   views_.resize((size_t)num_views);
   spec_tiled_ = plan_->tiles_spectra();
-  // read per engine (A/B runs, tests).  MVN_DIM0_DIRECT_MAX: most PSF planes the direct dim0 leg takes on
+  // read per engine (tests).  MVN_DIM0_DIRECT_MAX: most PSF planes the direct dim0 leg takes on
   // (MVN_D0_MAX_TAPS = 33 are instantiated); measured at 512^3 x 6 views on MI355X (profiles/r03_dim0_direct.md)
   // the whole iteration is 6.7 / 4.1 % faster than with the fused FFT pass at 15 / 31 planes
   direct_enabled_ = env_int("MVN_DIM0_DIRECT", 1) != 0;
@@ -734,15 +716,14 @@ Engine::Engine(int device, const shape_t& dims, int num_views) : device_(device)
 }
 
 // Packed Nyquist layout (mvn_dim0_direct.hpp): MVN_NYQ_PACKED = 1 always / 0 never / unset: for volumes up to
-// MVN_NYQ_PACKED_MAX_MB (default 256).  Small volumes are bound by launches and latency and the layout's single
+// 256 MB.  Small volumes are bound by launches and latency and the layout's single
 // launch chain wins (one view update, round 4, against the split layout with its Nyquist lines riding in the dim1
 // launches: 64^3 0.055 / 0.062 ms, 128^3 0.082 / 0.089, 256^3 0.246 / 0.262; 320^3 and 384^3 even).  At 512^3 it
 // is 6 % SLOWER (2.24 / 2.11 ms): the DC column's 2 x 257 dim0 columns are 8-byte accesses one row apart in every
 // plane, and the leg takes 0.27 instead of 0.23 ms (profiles/r04_layouts.md).
 bool Engine::packed_layout_for(size_t volume_bytes) {
   const int sw = env_int("MVN_NYQ_PACKED", -1);
-  const size_t max_bytes = (size_t)env_int("MVN_NYQ_PACKED_MAX_MB", 256) << 20;
-  return sw > 0 || (sw < 0 && volume_bytes <= max_bytes);
+  return sw > 0 || (sw < 0 && volume_bytes <= ((size_t)256 << 20));
 }
 
 Engine::~Engine() {
@@ -981,20 +962,15 @@ void Engine::prepare_psf(ViewSlot& s, int i, const float* d_kernel, const int* k
 
 void Engine::ensure_work2() {
   if (work2_) return;
-  size_t skew = 0;
-#ifdef MVN_EXPERIMENTS  // variant builds only: the second work volume displaced against the first (DRAM bank / channel phase)
-  skew = (size_t)env_int("MVN_WORK2_SKEW_KB", 0) * 1024;
-#endif
-  work2_alloc_ = (float*)be::dmalloc(plan_->main_bytes() + skew);
-  work2_ = work2_alloc_ + skew / sizeof(float);
+  work2_ = work2_alloc_ = (float*)be::dmalloc(plan_->main_bytes());
   if (plan_->nyq_bytes()) work2_nyq_ = (cfloat*)be::dmalloc(plan_->nyq_bytes());
 }
 
 // the dim0 leg with the direct form of kernel i: in -> out (never in place).  Packed layout: one launch, the
-// DC + i Nyquist column separated inside it.  Split layout: sn == stream_: main array and Nyquist plane in ONE
-// launch on the engine's stream; otherwise the Nyquist plane as a launch of its own on sn
+// DC + i Nyquist column separated inside it.  Split layout: main array and Nyquist plane in ONE launch on the
+// engine's stream
 void Engine::dim0_conv(const ViewSlot& s, int i, const cfloat* in, const cfloat* in_nyq, cfloat* out,
-                       cfloat* out_nyq, Profiler* prof, be::stream_t sn, int zbeg, int zcount, bool first) {
+                       cfloat* out_nyq, Profiler* prof, int zbeg, int zcount, bool first) {
   const Layout& L = plan_->L;
   if (zcount < 0 || zbeg < 0 || zbeg + zcount > L.d0) throw std::out_of_range("mvn: plane range of a dim0 leg");
   Dim0DirectParams p;
@@ -1037,12 +1013,6 @@ void Engine::dim0_conv(const ViewSlot& s, int i, const cfloat* in, const cfloat*
   p.taps2 = L.even ? s.taps_nyq[i] : nullptr;
   p.plane2 = L.even ? L.d1 : 0;
   p.seg2 = 16;
-  if (sn != stream_ && L.even) {
-    Dim0DirectParams q = p;
-    q.plane = 0;  // the Nyquist plane alone, in pieces of 16 output planes
-    be::launch_dim0_direct(q, sn);
-    p.plane2 = 0;
-  }
   ProfScope ps(prof, KK_AXIS0_DIRECT, stream_);
   be::launch_dim0_direct(p, stream_);
 }
@@ -1263,19 +1233,19 @@ void Engine::middle(const ViewSlot& s, int i, Profiler* prof, SideStream* side, 
         if (halo_drain_) be::stream_sync(stream_);
         halo_fn_(halo_user_, work_, view, i + 4);
       }
-      dim0_conv(s, i, in, in_n, out, out_n, prof, stream_);
+      dim0_conv(s, i, in, in_n, out, out_n, prof);
     } else if (halo_split_ && own > 2 * H) {
-      dim0_conv(s, i, in, in_n, out, out_n, prof, stream_, 2 * H, own - 2 * H, true);
+      dim0_conv(s, i, in, in_n, out, out_n, prof, 2 * H, own - 2 * H, true);
       if (halo_drain_) be::stream_sync(stream_);
       halo_fn_(halo_user_, work_, view, i + 4);  // the halo planes must be in place behind this call
-      dim0_conv(s, i, in, in_n, out, out_n, nullptr, stream_, H, H, false);
-      dim0_conv(s, i, in, in_n, out, out_n, nullptr, stream_, own, H, false);
+      dim0_conv(s, i, in, in_n, out, out_n, nullptr, H, H, false);
+      dim0_conv(s, i, in, in_n, out, out_n, nullptr, own, H, false);
     } else {
       if (halo_split_) {
         if (halo_drain_) be::stream_sync(stream_);
         halo_fn_(halo_user_, work_, view, i + 4);
       }
-      dim0_conv(s, i, in, in_n, out, out_n, prof, stream_, H, own, true);
+      dim0_conv(s, i, in, in_n, out, out_n, prof, H, own, true);
     }
     std::swap(work_, work2_);
     std::swap(work_nyq_, work2_nyq_);
@@ -1296,25 +1266,18 @@ void Engine::middle(const ViewSlot& s, int i, Profiler* prof, SideStream* side, 
     return;
   }
   // The folded dim0 leg needs two fork / join pairs per convolution (17 - 20 us of cross-queue latency each):
-  // below MVN_D0_SIDE_MIN_MB (default 256) the Nyquist plane's two dim1 launches cost less in line
+  // below 256 MB the Nyquist plane's two dim1 launches cost less in line
   // (256^3 per view update: 0.329 ms with the side stream, 0.312 with the fused FFT pass)
-  static const size_t d0_side_min = (size_t)env_int("MVN_D0_SIDE_MIN_MB", 256) << 20;
-  const bool use_side = side && side->s && P.L.even && P.main_bytes() > d0_side_min && !P.nyq_rides();
+  const bool use_side = side && side->s && P.L.even && P.main_bytes() > ((size_t)256 << 20) && !P.nyq_rides();
   be::stream_t sn = use_side ? side->s : stream_;
-  // MVN_D0_NYQ_SIDE=1: the Nyquist plane's whole chain (dim1, dim0 leg, dim1) on the side stream, one fork
-  // and one join per convolution; default: its dim0 leg rides in the main launch, the side stream joins
-  // before it and forks again behind it
-  static const bool nyq_side = env_int("MVN_D0_NYQ_SIDE", 0) != 0;
+  // the Nyquist plane's dim1 launches go on the side stream; its dim0 leg rides in the main launch, so the side
+  // stream joins before that launch and forks again behind it
   if (use_side) side->fork_from(stream_);  // the plane was written by the last-axis pass just enqueued on stream_
   P.axis1(MVN_ST_FWD, (cfloat*)work_, work_nyq_, stream_, prof, sn);
   ensure_work2();
-  if (use_side && nyq_side) {
-    dim0_conv(s, i, (const cfloat*)work_, work_nyq_, (cfloat*)work2_, work2_nyq_, prof, sn);
-  } else {
-    if (use_side) side->join_into(stream_);
-    dim0_conv(s, i, (const cfloat*)work_, work_nyq_, (cfloat*)work2_, work2_nyq_, prof, stream_);
-    if (use_side) side->fork_from(stream_);
-  }
+  if (use_side) side->join_into(stream_);
+  dim0_conv(s, i, (const cfloat*)work_, work_nyq_, (cfloat*)work2_, work2_nyq_, prof);
+  if (use_side) side->fork_from(stream_);
   std::swap(work_, work2_);
   std::swap(work_nyq_, work2_nyq_);
   P.axis1(MVN_ST_INV, (cfloat*)work_, work_nyq_, stream_, prof, sn);
@@ -1463,8 +1426,7 @@ void Engine::conv_pair(int v, double lambda, float min_value, int final_mode, in
   if (prof_.enabled && (pair_counter_++ % (prof_.sample_every > 0 ? prof_.sample_every : 1)) == 0)
     prof = &prof_;
   const Plan3D& P = *plan_;
-  static const bool no_fuse = env_int("MVN_NO_FUSE", 0) != 0;  // A/B knob for experiments
-  const bool fuse = P.can_fuse_rows() && !no_fuse;
+  const bool fuse = P.can_fuse_rows();
 
   EpilogueParams e1;
   std::memset(&e1, 0, sizeof(e1));
@@ -1490,9 +1452,7 @@ void Engine::conv_pair(int v, double lambda, float min_value, int final_mode, in
   // small volumes, where the two event waits per convolution cost more than three more 4 us
   // launches in line (measured per view update: 64^3 0.095 -> 0.074 ms, 96^3 0.124 -> 0.105 ms,
   // 128^3 0.143 -> 0.134 ms in line; 256^3 0.308 -> 0.340 ms, so the switch sits in between).
-  static const bool no_side = env_int("MVN_NO_SIDE_STREAM", 0) != 0;  // A/B knob
-  static const size_t side_min_bytes = (size_t)env_int("MVN_SIDE_MIN_MB", 16) << 20;
-  SideStream* side = (no_side || P.main_bytes() <= side_min_bytes) ? nullptr : &side_;
+  SideStream* side = P.main_bytes() <= kSideMinBytes ? nullptr : &side_;
   // The last-axis pass that PRODUCES a convolution's input is handed to middle() as a function of a row range: in
   // halo mode with a split leg the planes next to the halos are produced (and dim1-transformed) FIRST, so that the
   // neighbours can pull them while this slab still works on its interior (middle()); otherwise it is called once.
@@ -1568,10 +1528,11 @@ bool Engine::boundary_first() const {
 // Sweeps 2 .. n-1 of a call are identical launch sequences (every view update starts from the
 // last-axis transform the previous one left and leaves one itself).  Where a sweep is
 // launch-bound -- a 64^3 view update is 14 launches of ~6 us kernels -- it can be captured once
-// as a graph and replayed.  Measured on MI355X (tools/graph_probe.py): 64^3 0.091 -> 0.081 ms,
-// 128^3 0.132 -> 0.120 ms, 256^3 0.308 -> 0.305 ms per view update, against ~11 ms for capture
-// and instantiation, which only a long-lived engine (thousands of small view updates) earns
-// back.  Hence opt-in: MVN_GRAPH=1 enables it, MVN_GRAPH_MAX_MB (default 160) bounds the volume.
+// as a graph and replayed.  Measured on MI355X (`tools/graph_probe.py`
+// (removed; see git history before this change)): 64^3 0.091 -> 0.081 ms, 128^3 0.132 -> 0.120 ms,
+// 256^3 0.308 -> 0.305 ms per view update, against ~11 ms for capture and instantiation, which only
+// a long-lived engine (thousands of small view updates) earns back.  Hence opt-in: MVN_GRAPH=1
+// enables it, MVN_GRAPH_MAX_MB (default 160) bounds the volume.
 void Engine::iterate(int iterations, double lambda, float min_value) {
   be::set_device(device_);
   work_has_psi_spectrum_ = false;  // psi may have been replaced since the last call
@@ -1582,11 +1543,10 @@ void Engine::iterate(int iterations, double lambda, float min_value) {
   const int V = (int)views_.size();
   static const bool graphs_on = env_int("MVN_GRAPH", 0) != 0 && be::graphs_supported();
   static const size_t graph_max_bytes = (size_t)env_int("MVN_GRAPH_MAX_MB", 160) << 20;
-  static const bool no_fuse = env_int("MVN_NO_FUSE", 0) != 0;
   // (a captured sweep holds buffer addresses: the two work volumes must be back in their roles after it,
   // i.e. the sweep must contain an even number of direct dim0 legs)
   bool use_graph = graphs_on && !halo_fn_ && iterations >= 3 && !prof_.enabled && plan_->can_fuse_rows() &&
-                   !no_fuse && plan_->main_bytes() <= graph_max_bytes;
+                   plan_->main_bytes() <= graph_max_bytes;
   for (int it = 0; it < iterations; ++it) {
     if (use_graph && it == 1) {  // every view has been staged by now: its PSF forms are known
       int swaps = 0;
@@ -1769,11 +1729,8 @@ void Engine::compute_delta_head(double lambda, float min_value) {
     if (P.nyq_bytes()) psi_spec_nyq_ = (cfloat*)be::dmalloc(P.nyq_bytes());
     psi_spec_valid_ = false;
   }
-  static const bool no_fuse = env_int("MVN_NO_FUSE", 0) != 0;
-  const bool fuse = P.can_fuse_rows() && !no_fuse;
-  static const bool no_side = env_int("MVN_NO_SIDE_STREAM", 0) != 0;
-  static const size_t side_min_bytes = (size_t)env_int("MVN_SIDE_MIN_MB", 16) << 20;
-  const bool use_side = !no_side && side_.s && P.L.even && P.main_bytes() > side_min_bytes && !packed_ && !P.nyq_rides();
+  const bool fuse = P.can_fuse_rows();
+  const bool use_side = side_.s && P.L.even && P.main_bytes() > kSideMinBytes && !packed_ && !P.nyq_rides();
   be::stream_t sn = use_side ? side_.s : stream_;
   if (!psi_spec_valid_) {  // else: left there chunk by chunk by apply_delta_chunk(.., feed_next)
     if (lines_) {  // line layout: the fused middle pass transforms along dim1 itself
@@ -1836,7 +1793,7 @@ void Engine::compute_delta_head(double lambda, float min_value) {
     if (s.tap_k[0]) {
       // (the shared spectrum of psi may still be in the making on the side stream: v == 0)
       if (use_side && v == 0) side_.join_into(stream_);
-      dim0_conv(s, 0, (const cfloat*)psi_spec_, pn(), (cfloat*)work_, wn(), prof, stream_);
+      dim0_conv(s, 0, (const cfloat*)psi_spec_, pn(), (cfloat*)work_, wn(), prof);
       if (use_side) side_.fork_from(stream_);
     } else {
       if (use_side) side_.fork_from(stream_);

@@ -107,10 +107,12 @@ class Plan3D {
   DevAxis ax2, ax1, ax0;
   cfloat* twr = nullptr;  // d2-th roots of unity (even d2)
   unsigned* no_poison = nullptr;  // a zero word: what EpilogueParams::poison points to after an FFT dim0 leg
-  PassGeom g_rows, g_ax1, g_ax0, g_ax0f, g_nyq1, g_nyq0, g_nyq1_line;
-  bool nyq_rides() const;
+  PassGeom g_rows, g_ax1, g_ax0, g_nyq1, g_nyq0, g_nyq1_line;
   // compile-time specialised kernels (mvn_fixed.hpp) are used where the shape allows
   bool fx_rows = false, fx_ax1 = false, fx_ax0 = false;
+  // the Nyquist plane's dim1 transforms ride in the main array's launches where those are the fixed-length
+  // walking kernels
+  bool nyq_rides() const { return fx_ax1; }
   PassGeom gx_rows, gx_ax1, gx_ax0;
 
   Plan3D(int device, int d0, int d1, int d2);
@@ -166,7 +168,7 @@ class Plan3D {
   // pass runs the fixed-length kernels: [tile][row][T columns] instead of [row][d1 * C columns], so
   // that the operand fetch of a tile is one stream of d0 * T * 8 bytes (64 KB at 512^3) instead of d0
   // row segments of 128 bytes, each on another 1 MB-strided page.
-  bool tiles_spectra() const;
+  bool tiles_spectra() const { return fx_ax0; }
   void retile_spectrum(const cfloat* natural, cfloat* tiled, be::stream_t s) const;
 
   // whole transforms, un-normalised, in place on (vol, nyq)
@@ -411,7 +413,7 @@ class Engine {
   bool boundary_first() const;
   // zcount > 0: only the output planes [zbeg, zbeg + zcount); first = false: a further launch of the same leg
   void dim0_conv(const ViewSlot& s, int i, const cfloat* in, const cfloat* in_nyq, cfloat* out, cfloat* out_nyq,
-                 Profiler* prof, be::stream_t sn, int zbeg = 0, int zcount = 0, bool first = true);
+                 Profiler* prof, int zbeg = 0, int zcount = 0, bool first = true);
   void ensure_work2();
   // Nyquist layout of the spectra between the last-axis passes of one call (mvn_dim0_direct.hpp, RowsParams::
   // nyq_packed): packed into the DC column when every kernel of every view is in the direct form, else the

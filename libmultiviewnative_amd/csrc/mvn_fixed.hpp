@@ -280,12 +280,8 @@ constexpr int fx_pick_nt(int cap, int full, int a, int b, int c) {
 //   sequence.
 // That leaves ns-1 LDS round trips per transform (2 for N = 512; the fused pass 4 instead of 8).
 // ---------------------------------------------------------------------------------------------
-#ifndef MVN_FX_ST_NT_TARGET
-#define MVN_FX_ST_NT_TARGET 512
-#endif
-#ifndef MVN_FX_ST_MAX_WAVES
-#define MVN_FX_ST_MAX_WAVES 4
-#endif
+constexpr int kFxStNtTarget = 512;  // most threads of a strided workgroup (see FxStridedCfg::IT0)
+constexpr int kFxStMaxWaves = 4;    // most waves per SIMD the register allocation leaves room for
 // stage-0 butterflies per thread: the fewest that bring the workgroup to <= target threads
 constexpr int fx_st_it0(int nt1, int target) {
   for (int it = 1; it <= 8; ++it)
@@ -305,12 +301,12 @@ struct FxStridedCfg {
   static constexpr int R0 = fx_radix(N, 0), M0 = fx_M(N, 0);
   static constexpr int RL = fx_radix(N, NS - 1);  // radix of the last stage (M = 1)
   // threads: NT1 = M0 * CH would give every thread one stage-0 butterfly (on two columns); IT0 of
-  // them per thread keep the workgroup at or below MVN_FX_ST_NT_TARGET threads, which leaves the
+  // them per thread keep the workgroup at or below kFxStNtTarget threads, which leaves the
   // registers for the tile fetched ahead (see fx_strided_body)
   // Lengths whose stage-0 work items do not fill whole waves (96, 160, 288: the padded extents of 64-,
   // 128- and 256-blocks) round the workgroup up; the idle threads of stage 0 are guarded (RAGGED).
   static constexpr int NT1 = M0 * CH;
-  static constexpr int IT0 = fx_st_it0(NT1, MVN_FX_ST_NT_TARGET);
+  static constexpr int IT0 = fx_st_it0(NT1, kFxStNtTarget);
   static constexpr int NT = ((NT1 / IT0 + 63) / 64) * 64;
   static constexpr bool RAGGED = NT * IT0 != NT1;
   static constexpr int NWL = (N / RL) * CH;  // work items of the last stage
@@ -319,7 +315,7 @@ struct FxStridedCfg {
   // waves per SIMD the register allocation should leave room for: what the LDS admits, at most 4
   static constexpr int WG_PER_CU = (160 * 1024) / (int)(sizeof(cfloat) * lds_cfloats) > 0 ? (160 * 1024) / (int)(sizeof(cfloat) * lds_cfloats) : 1;
   static constexpr int WAVES_WANTED = (WG_PER_CU * (NT / 64) + 3) / 4;
-  static constexpr int WAVES = WAVES_WANTED > MVN_FX_ST_MAX_WAVES ? MVN_FX_ST_MAX_WAVES : WAVES_WANTED;
+  static constexpr int WAVES = WAVES_WANTED > kFxStMaxWaves ? kFxStMaxWaves : WAVES_WANTED;
   static_assert(fx_smooth(N) && N >= 64 && N <= 2048 && N % 32 == 0, "unsupported fixed length");
   static_assert(R0 == 8 && NS >= 2 && M0 > 1 && fx_M(N, NS - 1) == 1, "unexpected radix plan");
   static_assert(NT % 64 == 0 && NT <= 1024 && (!RAGGED || IT0 == 1), "workgroup size");
@@ -429,12 +425,8 @@ struct FxStagesQ {
 // the first inverse stage has been written to the LDS -- so they are in flight during the LDS
 // stages and the stores of the current tile (fused pass: see fx_st_first).
 
-#ifndef MVN_PROBE_BLOCK
-#define MVN_PROBE_BLOCK(b) (b)  // timing probes only (mvn_kernels.hip, -DMVN_PROBE): re-use a few tiles
-#endif
 template <int N>
 MVN_HD long fx_st_base(const StridedParams& P, long block) {
-  block = MVN_PROBE_BLOCK(block);
   // launches have far fewer than 2^31 tiles (checked by the launcher): 32-bit division
   const unsigned o = (unsigned)block / (unsigned)P.tiles_per_outer;
   const unsigned t = (unsigned)block - o * (unsigned)P.tiles_per_outer;
@@ -444,7 +436,7 @@ MVN_HD long fx_st_base(const StridedParams& P, long block) {
 // where tile `block` finds its PSF-spectrum operands, and the distance between their rows
 template <int N>
 MVN_HD const cfloat* fx_spec_tile(const StridedParams& P, long block, long base) {
-  return P.spec_tiled ? P.spec + (long)MVN_PROBE_BLOCK(block) * ((long)N * FxStridedCfg<N>::T) : P.spec + base;
+  return P.spec_tiled ? P.spec + block * ((long)N * FxStridedCfg<N>::T) : P.spec + base;
 }
 template <int N>
 MVN_HD long fx_spec_estride(const StridedParams& P) {
@@ -630,10 +622,8 @@ MVN_HD void fx_st_stage0_store(const StridedParams& P, long base, const cfloat* 
   }
 }
 
-// tiles first, first + step, ... < total.  WALK = false: exactly one tile per workgroup (the launch
-// has one workgroup per tile), nothing is fetched ahead -- the fused pass then holds only its rows
-// and its PSF operands in registers.
-template <int N, int MODE, typename Ctx, bool WALK = true>
+// tiles first, first + step, ... < total
+template <int N, int MODE, typename Ctx>
 MVN_HD void fx_strided_body(const StridedParams& P, long first, long total, long step, cfloat* lds,
                             Ctx& ctx) {
   typedef FxStridedCfg<N> C;
@@ -643,9 +633,9 @@ MVN_HD void fx_strided_body(const StridedParams& P, long first, long total, long
   cfloat* tws = lds + N * C::TP;
   if (first >= total) return;
   MVN_PHASE(ctx, (fx_st_prologue<N, MODE>(P, fx_st_base<N>(P, first), tws, r, tid)));
-  for (long block = first; block < (WALK ? total : first + 1); block += step) {
+  for (long block = first; block < total; block += step) {
     const long base = fx_st_base<N>(P, block);
-    const bool has_next = WALK && block + step < total;
+    const bool has_next = block + step < total;
     const long next_base = has_next ? fx_st_base<N>(P, block + step) : base;
     if (MODE == MVN_ST_INV) {
       MVN_PHASE(ctx, (fx_st_last_in<N>(P, next_base, has_next, buf, r, tid)));
@@ -677,11 +667,7 @@ MVN_HD void fx_strided_body(const StridedParams& P, long first, long total, long
 template <int N>
 struct FxFusedCfg {
   typedef FxStridedCfg<N> S;
-#if defined(MVN_EXPERIMENTS) && defined(MVN_FX_NO_LDS_FUSED)
-  static constexpr bool USE = false;  // experiment (variant builds only): register-staged body for every length
-#else
   static constexpr bool USE = S::WG_PER_CU >= 2;
-#endif
   static constexpr int T = S::T, TP = S::TP, CH = S::CH;
   // threads: whole tile rows per sweep (N * CH divisible by NT), not more than one radix-8
   // butterfly each; 512 unless that leaves more than eight 16-byte loads per thread
@@ -690,20 +676,11 @@ struct FxFusedCfg {
   // (N = 576 takes nine loads per thread on 512 threads: with the 768 threads that eight loads would
   // mean, the 104 registers of the pass leave ONE 12-wave workgroup per CU where the LDS holds two -
   // measured at 576^3: 0.634 ms with 768 threads, 0.498 ms with 512 threads and 32 bytes of scratch)
-#ifndef MVN_FX_FUSED_MAX_U
-#define MVN_FX_FUSED_MAX_U 9
-#endif
-#ifndef MVN_FX_FUSED_NT_CAP
-#define MVN_FX_FUSED_NT_CAP 1024
-#endif
-  static constexpr int NT = (NT512 > 0 && N * CH / NT512 <= MVN_FX_FUSED_MAX_U) ? NT512 : fx_pick_nt(MVN_FX_FUSED_NT_CAP, FULL, N * CH, N * CH, N * CH);
+  static constexpr int NT = (NT512 > 0 && N * CH / NT512 <= 9) ? NT512 : fx_pick_nt(1024, FULL, N * CH, N * CH, N * CH);
   static constexpr int RPT = NT / CH;  // tile rows covered by one sweep of the workgroup
   static constexpr int U = N / RPT;    // 16-byte loads per thread
-#ifndef MVN_FX_FUSED_MAX_WAVES
-#define MVN_FX_FUSED_MAX_WAVES MVN_FX_ST_MAX_WAVES
-#endif
   static constexpr int WAVES_WANTED = (S::WG_PER_CU * (NT / 64) + 3) / 4;
-  static constexpr int WAVES = WAVES_WANTED > MVN_FX_FUSED_MAX_WAVES ? MVN_FX_FUSED_MAX_WAVES : WAVES_WANTED;
+  static constexpr int WAVES = WAVES_WANTED > kFxStMaxWaves ? kFxStMaxWaves : WAVES_WANTED;
   static_assert(NT >= 64 && N % RPT == 0, "tile rows must divide");
 };
 
@@ -793,14 +770,14 @@ MVN_HD void fx_fused_lds_body(const StridedParams& P, long block, cfloat* lds, C
 // a part of it at a time: NWIN windows of 8 / NWIN sub-lines, each through W = N / NWIN LDS rows.
 //   [window r: loads + last stage -> LDS, inner stages, LDS -> registers] x NWIN -> stage 0 -> stores
 // The 8-column form (64-byte segments, FxStridedCfg) ran these passes at 3.0-3.4 TB/s.
-// Round 4: the windows are a parameter (MVN_FX_SPLIT_NWIN_LONG = 2 or 4 for N >= 1536).  With half-line windows the
+// Round 4 compared two and four windows for N >= 1536.  With half-line windows the
 // rows a thread holds between their loads and the last stage (r.pf) are 80 registers and the NEXT tile's first
 // window cannot be requested before the finished tile's stores (256 VGPRs + scratch, round 3); the counters show the
 // pass short of requests in flight (11.7 k device-wide against 20 k at 512^3, profiles/r04_mem_counters_1920.md).
 // With QUARTER windows (40 registers) the next tile's first window is requested under the last window's stages and
 // the stores, 237 - 247 VGPRs, no scratch - and the pass takes exactly as long (64 x 1920 x 1920, same box:
 // forward 0.436 / 0.434 ms, inverse 0.396 / 0.396, profiles/r04_ab_split_windows_1920.txt): those loads were not what
-// it waits for.  Half windows stay the default (fewer barriers).
+// it waits for.  Half windows stay (fewer barriers).
 // ---------------------------------------------------------------------------------------------
 template <int N>
 struct FxSplitCfg {
@@ -809,14 +786,9 @@ struct FxSplitCfg {
   static constexpr int NS = fx_nstages(N);
   static constexpr int M0 = fx_M(N, 0);
   static constexpr int RL = fx_radix(N, NS - 1);
-#ifndef MVN_FX_SPLIT_NWIN_LONG
-#define MVN_FX_SPLIT_NWIN_LONG 2
-#endif
-  static constexpr int NWIN = N >= 1536 ? MVN_FX_SPLIT_NWIN_LONG : 2;  // windows per tile
-  static constexpr int SUB = 8 / NWIN;                               // sub-lines per window
-  static constexpr int W = N / NWIN;                                 // rows per window
-  // the next tile's first window is requested under the last window's stages and the stores (quarter windows)
-  static constexpr bool NEXT_AHEAD = NWIN > 2;
+  static constexpr int NWIN = 2;        // windows per tile
+  static constexpr int SUB = 8 / NWIN;  // sub-lines per window
+  static constexpr int W = N / NWIN;    // rows per window
   static constexpr int NT1 = M0 * CH;
   // threads: 1280 runs best with 640 (two stage-0 items per thread; 320: +7 %), 1920 with 384 (five items; 640
   // and 960 threads: +2 - 6 %) - profiles/r03_rows_lds.md
@@ -825,11 +797,10 @@ struct FxSplitCfg {
   static constexpr int NWL = (W / RL) * CH;  // last-stage work items per window
   static constexpr int ITL = (NWL + NT - 1) / NT;
   static constexpr int TW1 = 0;  // the whole stage-ordered table sits behind the window
-  // the forward form (row-permuted accesses, a little more register pressure): round 1 measured a
-  // win at 1280 (0.263 -> 0.246 ms) and a loss at 1920 (2.77 -> 2.95 ms, 172 bytes of scratch);
-  // built without SLP vectorisation (packed f32 math costs registers and issue slots on gfx950)
-  // the 1920 kernel keeps 28 bytes of scratch and wins too: 2.91 -> 2.37 ms on 320 x 1920 x 1920
-  static constexpr bool FWD_DEFAULT = true;
+  // the forward passes use this body as well (row-permuted accesses, a little more register pressure): round 1
+  // measured a win at 1280 (0.263 -> 0.246 ms) and a loss at 1920 (2.77 -> 2.95 ms, 172 bytes of scratch); built
+  // without SLP vectorisation (packed f32 math costs registers and issue slots on gfx950) the 1920 kernel keeps 28
+  // bytes of scratch and wins too: 2.91 -> 2.37 ms on 320 x 1920 x 1920
   static constexpr int lds_cfloats = W * TP + (fx_twsize(N) - TW1);
   static_assert(!USE || (fx_radix(N, 0) == 8 && NS >= 3 && N % 128 == 0 && W % RL == 0 && 8 % NWIN == 0), "split plan");
   static_assert(!USE || (NT % 64 == 0 && NT * IT0 == NT1), "split workgroup size");
@@ -1022,9 +993,6 @@ struct FxSplitWindows {
     if constexpr (WIN < C::NWIN) {
       if constexpr (WIN + 1 < C::NWIN) {
         MVN_PHASE(ctx, (fx_sp_last_to_lds<N, SIGN>(buf, r, tid), fx_sp_fetch<N, PERM, 0, C::ITL>(P, base, WIN + 1, r, tid)));
-      } else if constexpr (C::NEXT_AHEAD) {
-        MVN_PHASE(ctx, (fx_sp_last_to_lds<N, SIGN>(buf, r, tid),
-                        has_next ? fx_sp_fetch<N, PERM, 0, C::ITL>(P, next_base, 0, r, tid) : (void)0));
       } else {
         MVN_PHASE(ctx, (fx_sp_last_to_lds<N, SIGN>(buf, r, tid)));
       }
@@ -1053,15 +1021,10 @@ MVN_HD void fx_strided_split_body(const StridedParams& P, long first, long total
   cfloat* twl = lds + C::W * C::TP;
   if (first >= total) return;
   MVN_PHASE(ctx, (fx_sp_tables<N>(P, twl, tid)));
-  if constexpr (C::NEXT_AHEAD) {
-    MVN_PHASE_NOSYNC(ctx, (fx_sp_fetch<N, PERM, 0, C::ITL>(P, fx_sp_base<N>(P, first), 0, r, tid)));
-  }
   for (long block = first; block < total; block += step) {
     MVN_TILE_LOOP_TOP(ctx);
     const long base = fx_sp_base<N>(P, block);
-    if constexpr (!C::NEXT_AHEAD) {
-      MVN_PHASE_NOSYNC(ctx, (fx_sp_fetch<N, PERM, 0, C::ITL>(P, base, 0, r, tid)));
-    }
+    MVN_PHASE_NOSYNC(ctx, (fx_sp_fetch<N, PERM, 0, C::ITL>(P, base, 0, r, tid)));
     const bool has_next = block + step < total;
     const long next_base = has_next ? fx_sp_base<N>(P, block + step) : base;
     FxSplitWindows<N, SIGN, PERM, 0, Ctx>::run(P, base, next_base, has_next, buf, twl, ctx);
@@ -1072,14 +1035,9 @@ MVN_HD void fx_strided_split_body(const StridedParams& P, long first, long total
 // which body, register block and workgroup size a (length, mode) pair uses
 template <int N, int MODE>
 struct FxStridedSel {
-  // the fused pass where two or more workgroups share a CU: 0 = every stage through the LDS with
-  // one column per work item (fx_fused_lds_body), 1 = outer stages in registers, one tile per
-  // workgroup (fx_strided_body<.., WALK = false>: half the LDS traffic, 16-byte LDS accesses)
-#ifndef MVN_FX_FUSED_VARIANT
-#define MVN_FX_FUSED_VARIANT 0
-#endif
-  static constexpr bool ONE_TILE = MODE == MVN_ST_FWD_MUL_INV && FxFusedCfg<N>::USE;
-  static constexpr bool LDS_FUSED = ONE_TILE && MVN_FX_FUSED_VARIANT == 0;
+  // the fused pass where two or more workgroups share a CU: every stage through the LDS with one
+  // column per work item (fx_fused_lds_body)
+  static constexpr bool LDS_FUSED = MODE == MVN_ST_FWD_MUL_INV && FxFusedCfg<N>::USE;
   static constexpr int NT = LDS_FUSED ? FxFusedCfg<N>::NT : FxStridedCfg<N>::NT;
   static constexpr int WAVES = LDS_FUSED ? FxFusedCfg<N>::WAVES : FxStridedCfg<N>::WAVES;
   typedef typename std::conditional<LDS_FUSED, FxFusedRegs<N>, FxStridedRegs<N>>::type Regs;
@@ -1089,9 +1047,6 @@ struct FxStridedSel {
     if constexpr (LDS_FUSED) {
       // launched one workgroup per tile (step == grid size == total)
       for (long block = first; block < total; block += step) fx_fused_lds_body<N>(P, block, lds, ctx);
-    } else if constexpr (ONE_TILE) {
-      for (long block = first; block < total; block += step)
-        fx_strided_body<N, MODE, Ctx, false>(P, block, total, step, lds, ctx);
     } else
       fx_strided_body<N, MODE>(P, first, total, step, lds, ctx);
   }
@@ -1112,14 +1067,12 @@ struct FxStridedSel {
 template <int H>
 struct FxRowsCfg {
   static constexpr bool PAD = fx_pow2(H);  // the spare-row trick relies on power-of-two block sizes
-#ifndef MVN_FX_ROWS_T
-#define MVN_FX_ROWS_T 16
-#endif
   // Two tile classes.  TILED: one 16-row tile per workgroup (8 rows above H = 512), tables rebuilt
   // per tile.  WALKING: small tiles of 2 - 8 rows, several small workgroups per CU that WALK over
   // the tiles of the launch so that the tables (up to 16 KB) are built once per workgroup.  Which
-  // one a length uses is measured (tools/rows_tune.sh on MI355X, fused divide + fused update of
-  // d2^3 cubes, round 2):
+  // one a length uses is measured (`tools/rows_tune.sh`
+  // (removed; see git history before this change) on MI355X, fused divide + fused update of d2^3
+  // cubes, round 2):
   //   H = 96, 128, 256                tiled wins (0.31 vs 0.27..0.33 at 320^3 is the crossover)
   //   H = 160, 288, 320, 384, 512     walking, 4 rows: -12 % (320^3), -29 % (576^3: 2.50 -> 1.77 ms;
   //                                   its 9-wave workgroups of 576 threads were the worst fit),
@@ -1131,37 +1084,26 @@ struct FxRowsCfg {
   //                                   tile leaves ONE workgroup per CU: 3.0 / 3.7 TB/s at 320 x 1920 x
   //                                   1920 in round 1)
   // The plain r2c pass alone would prefer the tiled class for the middle lengths (+1..48 %); it runs
-  // once per call.  MVN_FX_ROWS_SMALL_T > 0 forces the walking class with that many rows for every
-  // H >= MVN_FX_ROWS_SMALL_MIN (tuning builds).
-#ifndef MVN_FX_ROWS_SMALL_MIN
-#define MVN_FX_ROWS_SMALL_MIN 65
-#endif
-#ifndef MVN_FX_ROWS_SMALL_T
-#define MVN_FX_ROWS_SMALL_T 0
-#endif
-  static constexpr int WALK_T = (MVN_FX_ROWS_SMALL_T > 0 && H >= MVN_FX_ROWS_SMALL_MIN) ? MVN_FX_ROWS_SMALL_T
-                                : (H >= 640 || H == 480)                   ? 2
+  // once per call.
+  static constexpr int WALK_T = (H >= 640 || H == 480)                         ? 2
                                 : (H == 192 || H == 144 || H == 80 || H == 48) ? 8
-                                : (H >= 160 && !(fx_pow2(H) && H < 512))   ? 4
-                                                                           : 0;
+                                : (H >= 160 && !(fx_pow2(H) && H < 512))       ? 4
+                                                                               : 0;
   static constexpr bool SMALL = WALK_T > 0;
   static constexpr bool WALK = SMALL;
   // walking kernels transpose the stage twiddles when they copy them to the LDS (fx_tw_fetch)
   static constexpr bool TWT = WALK;
-  static constexpr int T = SMALL ? WALK_T : (H > 512 ? 8 : ((fx_pow2(H) && H >= 128) ? MVN_FX_ROWS_T : 16));
+  static constexpr int T = SMALL ? WALK_T : (H > 512 ? 8 : 16);
   static constexpr int TP = T + 1;
   static constexpr int QR = H / 2;  // 16-byte chunks per spectral row (2 complex bins each)
   static constexpr int R0 = fx_radix(H, 0);
   static constexpr int M0 = fx_M(H, 0);
   // threads: one stage-0 butterfly each where possible (up to 1024 per workgroup), dividing the
   // 16-byte row chunks, the stage-0 butterflies and the bin pairs evenly
-#ifndef MVN_FX_ROWS_NT_CAP
-#define MVN_FX_ROWS_NT_CAP 1024
-#endif
   // (small tiles: one stage-0 butterfly per thread, rounded up to whole waves; the last threads
   // of a sweep then idle -- every per-thread loop below is guarded where the counts do not divide)
   static constexpr int NT = SMALL ? ((M0 * T + 63) / 64) * 64
-                                  : fx_pick_nt(MVN_FX_ROWS_NT_CAP, H * T / 8 >= 64 ? H * T / 8 : 64, T * QR, M0 * T, H / 2 * T);
+                                  : fx_pick_nt(1024, H * T / 8 >= 64 ? H * T / 8 : 64, T * QR, M0 * T, H / 2 * T);
   static constexpr int NTD = NT > 0 ? NT : 1;
   static constexpr int U = (T * QR + NTD - 1) / NTD;   // 16-byte spectral loads/stores per thread
   static constexpr int IT0 = (M0 * T + NTD - 1) / NTD;  // stage-0 butterflies per thread
@@ -1316,14 +1258,12 @@ MVN_HD void fx_r2c_post(const RowsParams& P, long r0, cfloat* buf, const cfloat*
 // 8-byte access per lane, T lanes per line (128 contiguous bytes for 16-row tiles).  Row `r0` of the launch is row
 // P.row_base + r0 of the volume; tiles never straddle planes (T divides the rows of a plane).
 // The line-layout side in 16-byte accesses (two neighbouring rows per lane) or 8-byte ones (one row per lane), per
-// epilogue: measured at 512^3 (tools/ab_libs.sh, profiles/r04_mid_fused.md) the fused divide gains 11 % with 16 bytes
-// (0.337 -> 0.299 ms), the plain r2c pass 6 %, the fused update loses 1.4 % (0.495 -> 0.502: three more streams).
-#ifndef MVN_FX_LINES_16B
-#define MVN_FX_LINES_16B -1  // -1: per epilogue; 0 / 1: all passes 8 / 16 bytes (A/B builds)
-#endif
+// epilogue: measured at 512^3 (`tools/ab_libs.sh` (removed; see git history before this change),
+// profiles/r04_mid_fused.md) the fused divide gains 11 % with 16 bytes (0.337 -> 0.299 ms), the plain r2c pass 6 %, the
+// fused update loses 1.4 % (0.495 -> 0.502: three more streams).
 template <int EPI>
 constexpr bool fx_lines_wide() {
-  return MVN_FX_LINES_16B < 0 ? (EPI != MVN_EPI_UPDATE && EPI != MVN_EPI_DELTA) : MVN_FX_LINES_16B != 0;
+  return EPI != MVN_EPI_UPDATE && EPI != MVN_EPI_DELTA;
 }
 template <int H>
 MVN_HD long fx_lines_base(const RowsParams& P, long r0) {
@@ -1565,15 +1505,11 @@ MVN_HD void fx_rows_c2r_r2c_body(const RowsParams& P, long tile, cfloat* lds, Ct
   cfloat* tws = lds + C::TILE;
   cfloat* twr = tws + fx_twsize(H);
   MVN_PHASE(ctx, (fx_c2r_load<H, EPI, LINES>(P, r0, buf, tws, twr, r, tid)));
-#if !(defined(MVN_EXPERIMENTS) && defined(MVN_EXP_SKIP_PREPOST))  // timing experiment (variant builds only, WRONG results): what two LDS round trips cost
   MVN_PHASE(ctx, (fx_c2r_pre<H>(P, r0, buf, twr, tid)));
-#endif
   fx_dit<H, T, TP, C::PAD, NT, +1, 1, C::TWT>(buf, tws, ctx);
   MVN_PHASE(ctx, (fx_c2r_stage0_epilogue<H, true, EPI>(P, r0, buf, tws, r, tid)));
   fx_dif<H, T, TP, C::PAD, NT, -1, 1, C::TWT>(buf, tws, ctx);
-#if !(defined(MVN_EXPERIMENTS) && defined(MVN_EXP_SKIP_PREPOST))
   MVN_PHASE(ctx, (fx_r2c_post<H>(P, r0, buf, twr, tid)));
-#endif
   MVN_PHASE(ctx, (fx_r2c_store<H, LINES, fx_lines_wide<EPI>()>(P, r0, buf, tid)));
 }
 

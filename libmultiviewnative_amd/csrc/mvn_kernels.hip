@@ -29,23 +29,6 @@
 #include <stdexcept>
 #include <string>
 
-// Every switch that changes what a kernel computes or how much LDS it asks for - timing experiments - is compiled
-// only with -DMVN_EXPERIMENTS, which `make all` never sets (`make probe` / `make variant EXTRA=..` do);
-// tests/test_abi_symbols.py checks the product library for their traces.
-#if defined(MVN_PROBE) && !defined(MVN_EXPERIMENTS)
-#error "MVN_PROBE is a timing experiment: build it with -DMVN_EXPERIMENTS (make probe)"
-#endif
-#ifdef MVN_PROBE
-// Timing probe (never in the product build): every workgroup works on tile (index mod wrap), so the
-// working set of a pass is a few MB that stay in the L2 / Infinity Cache -- what a pass costs when
-// HBM is out of the picture.  Results are garbage.  MVN_PROBE_WRAP_ST / MVN_PROBE_WRAP_ROWS = tiles.
-__device__ int g_probe_wrap_st = 0;
-__device__ int g_probe_wrap_rows = 0;
-#define MVN_PROBE_BLOCK(b) (g_probe_wrap_st > 0 ? (b) % g_probe_wrap_st : (b))
-#define MVN_PROBE_TILE(t) (g_probe_wrap_rows > 0 ? (t) % g_probe_wrap_rows : (t))
-#else
-#define MVN_PROBE_TILE(t) (t)
-#endif
 #include "mvn_backend.hpp"
 #include "mvn_fixed_geom.hpp"
 #include "mvn_wave_rows.hpp"
@@ -125,7 +108,7 @@ __global__ void __launch_bounds__(FxRowsCfg<H>::NT) kx_rows_c2r_r2c(const RowsPa
   typedef FxCtx<FxRowsRegs<H>, FxRowsCfg<H>::NT> Ctx;
   Ctx ctx;
   ctx.tid = (int)threadIdx.x;
-  fx_rows_run<H, 2, EPI, Ctx, LINES>(p, (long)MVN_PROBE_TILE(blockIdx.x), (long)gridDim.x, (cfloat*)mvn_smem, ctx);
+  fx_rows_run<H, 2, EPI, Ctx, LINES>(p, (long)blockIdx.x, (long)gridDim.x, (cfloat*)mvn_smem, ctx);
 }
 
 // the fused middle pass (mvn_mid_fused.hpp): one column (piece) per workgroup
@@ -464,24 +447,7 @@ static void ensure_lds(K kernel, size_t lds_bytes) {
   done[key] = lds_bytes;
 }
 
-#ifdef MVN_PROBE
-static void probe_setup() {
-  static const bool once = [] {
-    const char* a = std::getenv("MVN_PROBE_WRAP_ST");
-    const char* b = std::getenv("MVN_PROBE_WRAP_ROWS");
-    int va = a ? std::atoi(a) : 0, vb = b ? std::atoi(b) : 0;
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_probe_wrap_st), &va, sizeof(int));
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_probe_wrap_rows), &vb, sizeof(int));
-    return true;
-  }();
-  (void)once;
-}
-#else
-static void probe_setup() {}
-#endif
-
 static void check_launch(long nblocks, int nthreads, size_t lds_bytes) {
-  probe_setup();
   if (nblocks < 1 || nblocks > 0x7fffffffL) throw std::invalid_argument("mvn: grid size out of range");
   if (nthreads < 64 || nthreads > 1024 || nthreads % 64) throw std::invalid_argument("mvn: bad block size");
   if (lds_bytes > 160 * 1024) throw std::invalid_argument("mvn: LDS request exceeds 160 KiB");
@@ -502,10 +468,8 @@ static void launch_rows_fixed(K kernel, const RowsParams& p, long nblocks, int n
 
 // Fixed strided kernels walk over several tiles per workgroup (the next tile's loads overlap the
 // current tile's LDS stages): the grid is what the device holds at once, not one block per tile.
-// MVN_PERSIST=0 launches one workgroup per tile (same kernel, no overlap across tiles);
-// MVN_PERSIST=k (k > 1) launches k times the resident number.  The LDS-staged fused pass is
-// launched one workgroup per tile: measured at 512^3, 0.333 ms against 0.380 ms walking (the
-// walking workgroups of a CU stay in step, all loading or all computing at once).
+// The LDS-staged fused pass is launched one workgroup per tile: measured at 512^3, 0.333 ms against
+// 0.380 ms walking (the walking workgroups of a CU stay in step, all loading or all computing at once).
 static int current_device() {
   int dev = 0;
   HIP_CHECK(hipGetDevice(&dev));
@@ -548,14 +512,10 @@ static void launch_walking(K kernel, StridedParams p, long nblocks, int nthreads
                            stream_t s, bool walk, const StridedParams* rider = nullptr, size_t rider_lds = 0) {
   if (rider && rider_lds > lds_bytes) lds_bytes = rider_lds;
   ensure_lds(kernel, lds_bytes);
-  static const int mode = [] {
-    const char* e = std::getenv("MVN_PERSIST");
-    return e ? std::atoi(e) : 1;
-  }();
   long grid = nblocks;
-  if (mode > 0 && walk) {
+  if (walk) {
     const long resident = (long)resident_per_cu(reinterpret_cast<const void*>(kernel), nthreads, lds_bytes) *
-                          device_cu_count() * mode;
+                          device_cu_count();
     if (grid > resident) grid = resident;
   }
   p.nblocks = nblocks;
@@ -569,46 +529,32 @@ static void launch_walking(K kernel, StridedParams p, long nblocks, int nthreads
 // wave-row kernels (d2 = 512): workgroups sweep over the row pairs, the grid is what the device
 // holds at once.  MVN_WAVE_ROWS_MASK selects the passes that use them (1 plain r2c, 2 plain c2r,
 // 4 fused divide, 8 fused update / store, 16 c2r with the DELTA epilogue of the sharded step);
-// MVN_NO_WAVE_ROWS=1 = mask 0.  Default 28 (round 3: the DELTA form 0.498 vs 0.512 ms tiled, 16 workgroups
-// per slot; 8 / 32 per slot 0.507 / 0.504 -- a pass with three read streams is bound by the read path,
-// profiles/r03_mem_counters.md).  Bits 4 and 8: measured at
-// 512^3 on MI355X (tools/ab_env.sh, same box) the fused divide gains 12 % over the tiled kernel
-// (0.376 -> 0.330 ms) and, with the twiddle tables transposed in the LDS, the fused update 2 %
-// (0.485 -> 0.475 ms); the plain r2c / c2r passes, which the tiled kernels already run at the
-// streaming ceiling, lose 3-8 % and stay tiled.
+// default 28 (round 3: the DELTA form 0.498 vs 0.512 ms tiled, 16 workgroups per slot; 8 / 32 per
+// slot 0.507 / 0.504 -- a pass with three read streams is bound by the read path,
+// profiles/r03_mem_counters.md).  Bits 4 and 8: measured at 512^3 on MI355X (`tools/ab_env.sh`
+// (removed; see git history before this change), same box) the fused divide gains 12 % over the
+// tiled kernel (0.376 -> 0.330 ms) and, with the twiddle tables transposed in the LDS, the fused
+// update 2 % (0.485 -> 0.475 ms); the plain r2c / c2r passes, which the tiled kernels already run
+// at the streaming ceiling, lose 3-8 % and stay tiled.
 static bool wave_rows_enabled(const RowsParams& p, int kind_bit) {
-  static const bool off = [] {
-    const char* e = std::getenv("MVN_NO_WAVE_ROWS");
-    return e && *e && std::strcmp(e, "0") != 0;
-  }();
   static const int mask = [] {
     const char* e = std::getenv("MVN_WAVE_ROWS_MASK");
     return e && *e ? std::atoi(e) : 28;
   }();
-  return !off && (mask & kind_bit) && p.fixed && !p.lines && p.h == WrCfg::H && p.C == WrCfg::H;
+  return (mask & kind_bit) && p.fixed && !p.lines && p.h == WrCfg::H && p.C == WrCfg::H;
 }
 
-// `mult_default` workgroups per resident slot: short-lived workgroups that the dispatcher keeps
-// feeding in address order stream better than resident ones that walk (tools/skeleton_probe.hip: a
-// bare 2-reads-1-write skeleton reaches 5.27 TB/s with resident walkers, 5.50 with 64 workgroups per
-// slot, 5.84 one-shot); against that the tables are built once per workgroup.  Measured at 512^3
-// (tools/ab_bench.sh): fused divide 0.336 -> 0.312 ms at 16 per slot, fused update 0.535 -> 0.498 ms
-// at 32; MVN_WR_GRID_MULT overrides both.
+// `mult` workgroups per resident slot: short-lived workgroups that the dispatcher keeps feeding in
+// address order stream better than resident ones that walk (`tools/skeleton_probe.hip` (removed; see
+// git history before this change): a bare 2-reads-1-write skeleton reaches 5.27 TB/s with resident
+// walkers, 5.50 with 64 workgroups per slot, 5.84 one-shot); against that the tables are built once
+// per workgroup.  Measured at 512^3 (`tools/ab_bench.sh` (removed; see git history before this
+// change)): fused divide 0.336 -> 0.312 ms at 16 per slot, fused update 0.535 -> 0.498 ms at 32.
 template <typename K>
-static void launch_wave_rows(K kernel, const RowsParams& p, stream_t s, long mult_default = 16) {
-#if defined(MVN_EXPERIMENTS) && defined(MVN_WR_LDS_PAD_KB)  // variant builds only: extra LDS = fewer resident workgroups
-  const size_t pad = (size_t)MVN_WR_LDS_PAD_KB * 1024;
-#else
-  const size_t pad = 0;
-#endif
-  const size_t lds = sizeof(cfloat) * (size_t)WrCfg::lds_cfloats + pad;
+static void launch_wave_rows(K kernel, const RowsParams& p, stream_t s, long mult = 16) {
+  const size_t lds = sizeof(cfloat) * (size_t)WrCfg::lds_cfloats;
   const long pairs = (p.rows + 1) / 2;
   long grid = (pairs + WrCfg::WAVES - 1) / WrCfg::WAVES;
-  static const long mult_env = [] {
-    const char* e = std::getenv("MVN_WR_GRID_MULT");
-    return (long)(e && *e ? std::atoi(e) : 0);
-  }();
-  const long mult = mult_env > 0 ? mult_env : mult_default;
   const long resident = (long)resident_per_cu(reinterpret_cast<const void*>(kernel), WrCfg::NT, lds) *
                         device_cu_count() * mult;
   if (grid > resident) grid = resident;
@@ -623,12 +569,8 @@ static void launch_rows_fixed(K kernel, const RowsParams& p, long nblocks, int n
     ensure_lds(kernel, lds_bytes);
     // eight workgroups per resident slot (see launch_wave_rows): measured fused divide / update
     // -5 / -3 % at 576^3, -7 / -7 % at 320 x 1920 x 1920 against resident walkers
-    static const long mult = [] {
-      const char* e = std::getenv("MVN_ROWS_GRID_MULT");
-      return (long)(e && *e && std::atoi(e) > 0 ? std::atoi(e) : 8);
-    }();
     const long resident = (long)resident_per_cu(reinterpret_cast<const void*>(kernel), nthreads, lds_bytes) *
-                          device_cu_count() * mult;
+                          device_cu_count() * 8;
     if (nblocks > resident) nblocks = resident;
   }
   launch_pass(kernel, p, nblocks, nthreads, lds_bytes, s);
@@ -771,23 +713,13 @@ static std::atomic<long> g_mid_fused_launches{0};
 long mid_fused_launch_count() { return g_mid_fused_launches.load(); }
 
 // long lines: 16-column tiles through the split-window body when the columns divide (the plan's
-// geometry is for the 8-column kernel); MVN_NO_SPLIT=1 keeps the 8-column kernel
+// geometry is for the 8-column kernel)
 template <int N>
 static bool try_launch_split(int mode, const StridedParams& p, long nblocks, stream_t s, const StridedParams* rider,
                              size_t rider_lds) {
   if constexpr (FxSplitCfg<N>::USE) {
     typedef FxSplitCfg<N> C;
-    static const bool off = [] {
-      const char* e = std::getenv("MVN_NO_SPLIT");
-      return e && *e && std::strcmp(e, "0") != 0;
-    }();
-    static const int fwd_env = [] {  // MVN_SPLIT_FWD=0/1 overrides the per-length default
-      const char* e = std::getenv("MVN_SPLIT_FWD");
-      return e && *e ? (std::strcmp(e, "0") != 0 ? 1 : 0) : -1;
-    }();
-    const bool fwd_ok = fwd_env < 0 ? C::FWD_DEFAULT : fwd_env == 1;
-    if (off || mode == MVN_ST_FWD_MUL_INV || (mode == MVN_ST_FWD && !fwd_ok) || p.cstride != 1 ||
-        p.ncols % C::T != 0 || p.tiles_per_outer < 1)
+    if (mode == MVN_ST_FWD_MUL_INV || p.cstride != 1 || p.ncols % C::T != 0 || p.tiles_per_outer < 1)
       return false;
     StridedParams q = p;
     const long outer = nblocks / p.tiles_per_outer;
@@ -821,7 +753,7 @@ void launch_strided(int mode, const StridedParams& p, long nblocks, int nthreads
     if (try_launch_split<N>(mode, p, nblocks, s, rider, rider_lds)) return;                        \
     if (mode == MVN_ST_FWD) launch_walking(kx_strided<N, MVN_ST_FWD>, p, nblocks, FxStridedSel<N, MVN_ST_FWD>::NT, lds_bytes, s, true, rider, rider_lds); \
     else if (mode == MVN_ST_INV) launch_walking(kx_strided<N, MVN_ST_INV>, p, nblocks, FxStridedSel<N, MVN_ST_INV>::NT, lds_bytes, s, true, rider, rider_lds); \
-    else launch_walking(kx_strided<N, MVN_ST_FWD_MUL_INV>, p, nblocks, FxStridedSel<N, MVN_ST_FWD_MUL_INV>::NT, lds_bytes, s, !FxStridedSel<N, MVN_ST_FWD_MUL_INV>::ONE_TILE); \
+    else launch_walking(kx_strided<N, MVN_ST_FWD_MUL_INV>, p, nblocks, FxStridedSel<N, MVN_ST_FWD_MUL_INV>::NT, lds_bytes, s, !FxStridedSel<N, MVN_ST_FWD_MUL_INV>::LDS_FUSED); \
     return;
       MVN_FIXED_STRIDED_LENGTHS(X)
 #undef X
@@ -862,9 +794,6 @@ void launch_dim0_direct(const Dim0DirectParams& p, stream_t s) {
     if (lds > 64 * 1024) throw std::invalid_argument("mvn: dim0 too long for the packed DC column");
   }
   if (nblocks > 0x7fffffffL) throw std::invalid_argument("mvn: grid size out of range");
-#if defined(MVN_EXPERIMENTS) && defined(MVN_D0_LDS_PAD_KB)  // variant builds only: bounds the workgroups per CU through their LDS
-  if (lds < (size_t)MVN_D0_LDS_PAD_KB * 1024) lds = (size_t)MVN_D0_LDS_PAD_KB * 1024;
-#endif
   switch (mvn_dim0_taps_template(p.k)) {
 #define X(K) case K: hipLaunchKernelGGL(kd_dim0<K>, dim3((unsigned)nblocks), dim3(MVN_D0_WG), lds, hs(s), p, (unsigned)main_blocks); break;
     MVN_D0_TAP_COUNTS(X)

@@ -43,15 +43,6 @@
 // A wave phase here ends where lanes of ONE wave hand data to each other through the LDS: what has to be kept is
 // the order of the wave's LDS instructions (they execute in order), nothing else - in particular the global loads
 // requested ahead must stay in flight across it (the all-address-space fence of MVN_WPHASE waits for them).
-#ifndef MF_LOCAL_FENCE
-#define MF_LOCAL_FENCE 1
-#endif
-#if MF_LOCAL_FENCE
-#define MF_FENCE() __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront", "local")
-#else
-#define MF_FENCE() __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront")
-#endif
-
 #if defined(__HIPCC__) && !defined(MVN_HOST_EMU)
 #define MF_WPHASE(ctx, ...)                                         \
   {                                                                 \
@@ -60,7 +51,7 @@
     (void)r;                                                        \
     __VA_ARGS__;                                                    \
   }                                                                 \
-  MF_FENCE();                                                       \
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront", "local");   \
   __builtin_amdgcn_wave_barrier();
 #else
 #define MF_WPHASE(ctx, ...) MVN_PHASE(ctx, __VA_ARGS__)
@@ -101,9 +92,6 @@ enum { MF_DC_NONE = 0, MF_DC_LOW = 1, MF_DC_HIGH = 2, MF_DC_SELF = 3 };  // a wo
 
 constexpr int mf_slots(int K) { return (K + 7) / 8 * 8; }
 
-#ifndef MF_TW0_AHEAD  // (see mf_tw0_ahead)
-#define MF_TW0_AHEAD 1
-#endif
 template <int K>
 struct MfRegs {
   cfloat tap[K];
@@ -166,9 +154,6 @@ MVN_HD void mf_fetch(const MidFusedParams& P, MfRegs<K>& r, int c, int z0, int b
   const int n = batch * MF_LINES + wv;
   if (n >= nsteps) return;
   const cfloat* src = P.in + ((long)mf_in_plane(P, z0, n) * P.H + c) * MF_N1 + l;
-#if defined(MVN_EXPERIMENTS) && defined(MF_EXP_NOLOAD)  // timing experiment (probe builds only, WRONG results): what the loads cost
-  if (batch > 1) return;
-#endif
 #pragma unroll
   for (int m = 0; m < 8; ++m) r.xr[m] = src[64 * m];
 }
@@ -187,11 +172,8 @@ MVN_HD void mf_setup(const MidFusedParams& P, MfRegs<K>& r, int c, int z0, int n
 
 // twiddle products of the transforms here: two packed instructions each (the scalar form of cmul is four; the LDS-
 // staged FFT passes of mvn_fixed.hpp lost time with the packed form, this kernel is short of vector issue slots)
-#ifndef MF_PK_TWIDDLE
-#define MF_PK_TWIDDLE 1
-#endif
 MVN_HD cfloat mf_cmul(cfloat a, cfloat w) {
-#if defined(MVN_PACKED) && MF_PK_TWIDDLE
+#if defined(MVN_PACKED)
   cfloat t, r;
   MVN_PK2(t, "v_pk_mul_f32", a, w, "op_sel_hi:[0,1]");                                   // (a.x w.x, a.x w.y)
   MVN_PK3(r, "v_pk_fma_f32", a, w, t, "op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[0,1,0]");  // + (-a.y w.y, a.y w.x)
@@ -201,7 +183,7 @@ MVN_HD cfloat mf_cmul(cfloat a, cfloat w) {
 #endif
 }
 MVN_HD cfloat mf_cmulc(cfloat a, cfloat w) {  // a * conj(w)
-#if defined(MVN_PACKED) && MF_PK_TWIDDLE
+#if defined(MVN_PACKED)
   cfloat t, r;
   MVN_PK2(t, "v_pk_mul_f32", a, w, "op_sel_hi:[0,1] neg_hi:[0,1]");       // (a.x w.x, -a.x w.y)
   MVN_PK3(r, "v_pk_fma_f32", a, w, t, "op_sel:[1,1,0] op_sel_hi:[1,0,1]");  // + (a.y w.y, a.y w.x)
@@ -213,7 +195,8 @@ MVN_HD cfloat mf_cmulc(cfloat a, cfloat w) {  // a * conj(w)
 
 // The lanes' twiddles live in the LDS (they would be 28 registers next to the filter's 126): stage 0, lane l:
 // exp(-2 pi i l m / 512) at [m - 1][l]; stage 1: exp(-2 pi i (l & 7) m / 64) at 448 + [m - 1][l & 7].  (As 16-byte
-// pairs, four reads per stage instead of seven: +4 % on the kernel - tools/mf_ab.sh, profiles/r04_mid_fused.md.)
+// pairs, four reads per stage instead of seven: +4 % on the kernel - `tools/mf_ab.sh`
+// (removed; see git history before this change), profiles/r04_mid_fused.md.)
 MVN_HD void mf_build_twiddles(const MidFusedParams& P, cfloat* twl, int tid) {
   if (tid < 448) {
     const int m = tid / 64 + 1, l = tid & 63;
@@ -227,60 +210,28 @@ MVN_HD void mf_build_twiddles(const MidFusedParams& P, cfloat* twl, int tid) {
 MVN_HD cfloat mf_tw0(const cfloat* twl, int l, int m) { return twl[(m - 1) * 64 + l]; }
 MVN_HD cfloat mf_tw1(const cfloat* twl, int l, int m) { return twl[448 + (m - 1) * 8 + (l & 7)]; }
 
-// the transforms' 8-point butterflies (one place for two timing experiments, probe builds only, WRONG results:
-// MF_EXP_NO_DFT leaves them out - what do they cost? -, MF_EXP_MFMA_DUMMY issues beside each the sixteen
-// v_mfma_f32_16x16x4_f32 a 16 x 16 real matrix form of it would take - does the matrix pipe run beside the rest?)
-template <int SIGN>
-MVN_HD void mf_dft8(cfloat* a, cfloat& sink) {
-  (void)sink;
-#if !(defined(MVN_EXPERIMENTS) && defined(MF_EXP_NO_DFT))
-  dftR<8, SIGN>(a);
-#endif
-#if defined(MVN_EXPERIMENTS) && defined(MF_EXP_MFMA_DUMMY) && defined(__HIPCC__) && !defined(MVN_HOST_EMU)
-  typedef float mf_f4 __attribute__((ext_vector_type(4)));
-  mf_f4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = c0, c2 = c0, c3 = c0;
-  const float x = sink.x, y = sink.y;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(x, y, c0, 0, 0, 0);
-    c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(y, x, c1, 0, 0, 0);
-    c2 = __builtin_amdgcn_mfma_f32_16x16x4f32(x, x, c2, 0, 0, 0);
-    c3 = __builtin_amdgcn_mfma_f32_16x16x4f32(y, y, c3, 0, 0, 0);
-  }
-  sink.x += (c0.x + c1.y) + (c2.z + c3.w);
-#endif
-}
-
 // ---- forward transform of a wave's line: registers -> LDS line, bins in the order q = 64 j + 8 k + a ----
 template <int K>
-MVN_HD void mf_fwd0(MfRegs<K>& r, cfloat* buf, const cfloat* twl, int tid) {
+MVN_HD void mf_fwd0(MfRegs<K>& r, cfloat* buf, int tid) {
   const int wv = tid >> 6, l = tid & 63;
   cfloat* line = buf + wv * MF_PITCH;
   cfloat a[8];
 #pragma unroll
   for (int m = 0; m < 8; ++m) a[m] = r.xr[m];
-  mf_dft8<-1>(a, r.bad);
-#if MF_TW0_AHEAD
-  (void)twl;
+  dftR<8, -1>(a);
 #pragma unroll
-  for (int m = 1; m < 8; ++m) a[m] = mf_cmul(a[m], r.t2[m]);
-#else
-#pragma unroll
-  for (int m = 1; m < 8; ++m) a[m] = mf_cmul(a[m], mf_tw0(twl, l, m));
-#endif
+  for (int m = 1; m < 8; ++m) a[m] = mf_cmul(a[m], r.t2[m]);  // (twiddles requested ahead: mf_tw0_ahead)
 #pragma unroll
   for (int m = 0; m < 8; ++m) line[72 * m + l] = a[m];  // sub-line m (frequencies m + 8 .), element l
 }
-// MF_TW0_AHEAD: the first forward stage is the first thing a wave does behind the batch's barrier, and it waited there
+// The first forward stage is the first thing a wave does behind the batch's barrier, and it waited there
 // for its seven twiddles behind every other wave's LDS requests.  They are requested in front of the barrier instead,
 // into r.t2 - which holds nothing between the last forward stage of a batch and the second one of the next.
 template <int K>
 MVN_HD void mf_tw0_ahead(MfRegs<K>& r, const cfloat* twl, int tid) {
-#if MF_TW0_AHEAD
   const int l = tid & 63;
 #pragma unroll
   for (int m = 1; m < 8; ++m) r.t2[m] = mf_tw0(twl, l, m);
-#endif
 }
 // Every exchange stage is a pair: `_a` reads the lane's inputs from the line and computes into r.t, `_b` writes
 // r.t to the places the NEXT stage reads.  On the device the two run back to back (a wave's LDS instructions
@@ -297,7 +248,7 @@ template <int K>
 MVN_HD void mf_fwd1_c(MfRegs<K>& r, const cfloat* twl, int tid) {
   const int l = tid & 63;
   (void)l;
-  mf_dft8<-1>(r.t, r.bad);
+  dftR<8, -1>(r.t);
 #pragma unroll
   for (int m = 1; m < 8; ++m) r.t[m] = mf_cmul(r.t[m], mf_tw1(twl, l, m));
 }
@@ -314,15 +265,12 @@ template <int K>
 MVN_HD void mf_fwd1_c2(MfRegs<K>& r, const cfloat* twl, int tid) {
   const int l = tid & 63;
   (void)l;
-  mf_dft8<-1>(r.t2, r.bad);
+  dftR<8, -1>(r.t2);
 #pragma unroll
   for (int m = 1; m < 8; ++m) r.t2[m] = mf_cmul(r.t2[m], mf_tw1(twl, l, m));
 }
 template <int K>
 MVN_HD void mf_fwd1_b2(const MfRegs<K>& r, cfloat* buf, int tid) {
-#if defined(MVN_EXPERIMENTS) && defined(MF_EXP_NO_S2)  // timing experiment (probe builds only, WRONG results): the exchange between stages 1 and 2 left out
-  if (tid >= 0) return;
-#endif
   const int wv = tid >> 6, l = tid & 63;
   cfloat* p = buf + wv * MF_PITCH + 72 * (l >> 3) + (l & 7);
 #pragma unroll
@@ -330,9 +278,6 @@ MVN_HD void mf_fwd1_b2(const MfRegs<K>& r, cfloat* buf, int tid) {
 }
 template <int K>
 MVN_HD void mf_fwd2_r2(MfRegs<K>& r, const cfloat* buf, int tid) {
-#if defined(MVN_EXPERIMENTS) && defined(MF_EXP_NO_S2)  // timing experiment (probe builds only, WRONG results): the exchange between stages 1 and 2 left out
-  if (tid >= 0) return;
-#endif
   const int wv = tid >> 6, l = tid & 63;
   const cfloat* p = buf + wv * MF_PITCH + 72 * (l >> 3) + 9 * (l & 7);
 #pragma unroll
@@ -367,7 +312,7 @@ MVN_HD void mf_fwd2_r(MfRegs<K>& r, const cfloat* buf, int tid) {
 template <int K>
 MVN_HD void mf_fwd2_a(MfRegs<K>& r, const cfloat* buf, int tid) {
   mf_fwd2_r<K>(r, buf, tid);
-  mf_dft8<-1>(r.t, r.bad);
+  dftR<8, -1>(r.t);
 }
 template <int K>
 MVN_HD void mf_fwd2_b(const MfRegs<K>& r, cfloat* buf, int tid) {
@@ -388,13 +333,10 @@ MVN_HD void mf_inv2_r(MfRegs<K>& r, const cfloat* buf, int tid) {
 template <int K>
 MVN_HD void mf_inv2_a(MfRegs<K>& r, const cfloat* buf, int tid) {
   mf_inv2_r<K>(r, buf, tid);
-  mf_dft8<+1>(r.t, r.bad);
+  dftR<8, +1>(r.t);
 }
 template <int K>
 MVN_HD void mf_inv2_b(const MfRegs<K>& r, cfloat* buf, int tid) {
-#if defined(MVN_EXPERIMENTS) && defined(MF_EXP_NO_S2)  // timing experiment (probe builds only, WRONG results): the exchange between stages 1 and 2 left out
-  if (tid >= 0) return;
-#endif
   const int wv = tid >> 6, l = tid & 63;
   cfloat* p = buf + wv * MF_PITCH + 72 * (l >> 3) + 9 * (l & 7);
 #pragma unroll
@@ -402,9 +344,6 @@ MVN_HD void mf_inv2_b(const MfRegs<K>& r, cfloat* buf, int tid) {
 }
 template <int K>
 MVN_HD void mf_inv1_r(MfRegs<K>& r, const cfloat* buf, int tid) {
-#if defined(MVN_EXPERIMENTS) && defined(MF_EXP_NO_S2)  // timing experiment (probe builds only, WRONG results): the exchange between stages 1 and 2 left out
-  if (tid >= 0) return;
-#endif
   const int wv = tid >> 6, l = tid & 63;
   const cfloat* p = buf + wv * MF_PITCH + 72 * (l >> 3) + (l & 7);
 #pragma unroll
@@ -416,7 +355,7 @@ MVN_HD void mf_inv1_c(MfRegs<K>& r, const cfloat* twl, int tid) {
   (void)l;
 #pragma unroll
   for (int m = 1; m < 8; ++m) r.t[m] = mf_cmulc(r.t[m], mf_tw1(twl, l, m));
-  mf_dft8<+1>(r.t, r.bad);
+  dftR<8, +1>(r.t);
 }
 template <int K>
 MVN_HD void mf_inv1_a(MfRegs<K>& r, const cfloat* buf, const cfloat* twl, int tid) {
@@ -442,10 +381,7 @@ MVN_HD void mf_inv0_c_store(MfRegs<K>& r, const cfloat* twl, cfloat* dst, int ti
   const int l = tid & 63;
 #pragma unroll
   for (int m = 1; m < 8; ++m) r.t[m] = mf_cmulc(r.t[m], mf_tw0(twl, l, m));
-  mf_dft8<+1>(r.t, r.bad);
-#if defined(MVN_EXPERIMENTS) && defined(MF_EXP_NOSTORE)  // timing experiment (probe builds only, WRONG results): what the stores cost
-  if (r.t[0].x == 12345.678f)
-#endif
+  dftR<8, +1>(r.t);
 #pragma unroll
   for (int m = 0; m < 8; ++m) dst[l + 64 * m] = r.t[m];
 }
@@ -527,25 +463,15 @@ MVN_HD void mf_setup_dc(const MidFusedParams& P, MfRegs<K>& r, int tid) {
 // into one of two alternating registers.  Issued inside the variants (behind line C's last multiply-add), each
 // variant's read was a different instruction and the value a merge of them: the compiler read into a scratch register
 // and waited for it at the end of every variant - a whole LDS latency per line, 8 per batch.
-//
-// MF_ALWAYS_TRANSFORM (0: the form before, kept for same-box comparisons): see mf_body.
-#ifndef MF_ALWAYS_TRANSFORM
-#define MF_ALWAYS_TRANSFORM 1
-#endif
 // Issue priorities within a batch (device only).  A SIMD's two waves - w and w + 4 of the workgroup - are served oldest
 // first: wave w runs ahead (good: its transform stages wait for the LDS while wave w + 4 still multiplies), reaches the
 // batch's barrier ~3000 cycles early, and wave w + 4 finishes alone at the pace of one wave (shader-clock stamps,
-// profiles/r04_mid_fused.md).  MF_PRIO_MODE 3 keeps the hardware's order up to point MF_PRIO_SWITCH of the batch (the
-// numbers of the MF_STAMP points) and raises the younger wave from there: both reach the barrier together.  0: none.
+// profiles/r04_mid_fused.md).  mf_body keeps the hardware's order up to filter lines 1 and 2 of the batch and raises
+// the younger wave behind them, in front of stage B's arithmetic: both reach the barrier together.  (Switched behind
+// stage A's arithmetic or behind stage C's requests, the pass was 2 % slower: profiles/r04c_ab_engine_prio_switch.txt.)
 // (Measured and removed: the younger wave always ahead, turns line by line, every wave raised inside its transform
 // stages; the forward stage in front of the batch's other requests; the loads issued later in the batch; stage B's
 // arithmetic of both lines as one block on shared twiddles - profiles/r04_mid_fused.md.)
-#ifndef MF_PRIO_MODE
-#define MF_PRIO_MODE 3
-#endif
-#ifndef MF_PRIO_SWITCH
-#define MF_PRIO_SWITCH 5
-#endif
 template <int K>
 MVN_HD void mf_fread(MfRegs<K>& r, const cfloat* in, int c, bool dc, int tid) {
   r.xn[c & 1] = in[c * MF_PITCH + tid];
@@ -678,139 +604,67 @@ MVN_HD void mf_body(const MidFusedParams& P, long block, cfloat* lds, Ctx& ctx) 
   // transforms (+3 .. +18 %, and the loop that selects the order per wave spills), the forward transform one stage
   // behind the transform back (+8 %: a fourth stage in the batch's chain), the two halves of the CU's waves a third
   // of a batch out of step (+6 %), a stepped schedule read from a per-wave table (290 spills).
-#if defined(__HIPCC__) && !defined(MVN_HOST_EMU) && MF_PRIO_MODE == 3
+#if defined(__HIPCC__) && !defined(MVN_HOST_EMU)
   const int wave_young = mvn_uniform((ctx.tid >> 8) & 1);
+#define MF_PRIO_RESET() __builtin_amdgcn_s_setprio(0);
+#define MF_PRIO_RAISE_YOUNG() \
+  if (wave_young != 0) __builtin_amdgcn_s_setprio(2);
+#else
+#define MF_PRIO_RESET()
+#define MF_PRIO_RAISE_YOUNG()
 #endif
   for (int i = -1; i <= nb; ++i) {
     const cfloat* fin = lds + (i & 1) * MF_BUF;
     cfloat* fout = lds + (2 + (i & 1)) * MF_BUF;
     cfloat* fwd = lds + ((i + 1) & 1) * MF_BUF;
     cfloat* inv = lds + (2 + ((i + 1) & 1)) * MF_BUF;
-    // MF_ALWAYS_TRANSFORM: the transform stages run in EVERY pass of the loop - in the two passes at either end on lines
-    // nobody wrote (their results go nowhere: mf_store_line_c and mf_fetch test the line's number themselves).  Behind
-    // a test each stage's LDS reads were followed, inside the test's block, by a wait and copies into the registers the
-    // next block expects: the latency the lines of the filter step were dealt out to cover was paid on the spot.
-#if MF_ALWAYS_TRANSFORM
-    constexpr bool T1 = true, T2 = true;
-#else
-    const bool T1 = i >= 1, T2 = i + 1 < nb;
-#endif
+    // The transform stages run in EVERY pass of the loop - in the two passes at either end on lines nobody wrote (their
+    // results go nowhere: mf_store_line_c and mf_fetch test the line's number themselves).  Behind a test each stage's
+    // LDS reads were followed, inside the test's block, by a wait and copies into the registers the next block
+    // expects: the latency the lines of the filter step were dealt out to cover was paid on the spot.
     const bool F = i >= 0 && i < nb;
     const bool fill = i * MF_LINES + MF_LINES - 1 < K - 1;
     const int u = F ? i % (mf_slots(K) / 8) : 0;
-#if defined(MVN_EXPERIMENTS) && defined(MF_STAMPS) && defined(__HIPCC__) && !defined(MVN_HOST_EMU)
-    // timing experiment (probe builds only): shader-clock stamps of every batch, kept in scalar registers; those of one
-    // batch of one workgroup go, per wave, to P.poison_peers' place (a debug buffer of 8 waves x 32 stamps the probe
-    // passes there) at the batch's end.  (A stamp is a scalar memory read: the next wait for LDS data behind it is a wait
-    // for ALL the wave's LDS requests.)
-    unsigned long long mf_stamps[14];
-#define MF_STAMP(n) mf_stamps[n] = __builtin_amdgcn_s_memtime();
-#define MF_STAMP_FLUSH()                                                                                          \
-  if (block == 100 && i == 40 && (ctx.tid & 63) == 0) {                                                           \
-    unsigned long long* dst_ = reinterpret_cast<unsigned long long*>(const_cast<unsigned**>(P.poison_peers)) +    \
-                               (ctx.tid >> 6) * 32;                                                               \
-    for (int n_ = 0; n_ < 14; ++n_) dst_[n_] = mf_stamps[n_];                                                     \
-  }
-#define MF_STAMP_VMWAIT() __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) alone
-#else
-#define MF_STAMP(n)
-#define MF_STAMP_FLUSH()
-#define MF_STAMP_VMWAIT()
-#endif
-#if defined(__HIPCC__) && !defined(MVN_HOST_EMU) && MF_PRIO_MODE == 3
-#define MF_PRIO_AT(n)                                         \
-  if ((n) == 0)                                               \
-    __builtin_amdgcn_s_setprio(0);                            \
-  else if ((n) == MF_PRIO_SWITCH && wave_young != 0)          \
-    __builtin_amdgcn_s_setprio(2);
-#else
-#define MF_PRIO_AT(n)
-#endif
 #define MF_FLINE(C)                                                                \
   if (F) {                                                                         \
     MF_WPHASE(ctx, (mf_fread_ahead<K, C>(r, fin, dc, tid), mf_fline_dispatch<K, C, 0>(r, fin, fout, u, fill, dc, tid)));  \
   }
-    MF_STAMP(0)
-    MF_PRIO_AT(0)
-    MF_STAMP_VMWAIT()
-    MF_STAMP(12)
+    MF_PRIO_RESET()
     // stage A: first stage back (reads the line) | first forward stage (reads the registers loaded ahead)
     if (F) {
       MF_WPHASE(ctx, (mf_fread<K>(r, fin, 0, dc, tid)));
     }
-    if (T1) {
-      MF_WPHASE(ctx, (mf_inv2_r<K>(r, inv, tid)));
-      if (dc) {
-        MF_WPHASE(ctx, (mf_inv2_fix_dc<K>(r, inv, tid)));
-      }
+    MF_WPHASE(ctx, (mf_inv2_r<K>(r, inv, tid)));
+    if (dc) {
+      MF_WPHASE(ctx, (mf_inv2_fix_dc<K>(r, inv, tid)));
     }
-    if (T2) {
-      MF_WPHASE(ctx, (mf_fwd0<K>(r, fwd, twl, tid), mf_fetch<K>(P, r, c, z0, i + 2, nsteps, tid)));
-    }
-    MF_STAMP(1)
-    MF_PRIO_AT(1)
+    MF_WPHASE(ctx, (mf_fwd0<K>(r, fwd, tid), mf_fetch<K>(P, r, c, z0, i + 2, nsteps, tid)));
     MF_FLINE(0)
-    MF_STAMP(2)
-    MF_PRIO_AT(2)
-    if (T1) {
-      MF_WPHASE(ctx, (mf_dft8<+1>(r.t, r.bad), mf_inv2_b<K>(r, inv, tid)));
-    }
-    MF_STAMP(3)
-    MF_PRIO_AT(3)
+    MF_WPHASE(ctx, (dftR<8, +1>(r.t), mf_inv2_b<K>(r, inv, tid)));
     // stage B
-    if (T1) {
-      MF_WPHASE(ctx, (mf_inv1_r<K>(r, inv, tid)));
-    }
-    if (T2) {
-      MF_WPHASE(ctx, (mf_fwd1_r2<K>(r, fwd, tid)));
-    }
-    MF_STAMP(4)
-    MF_PRIO_AT(4)
+    MF_WPHASE(ctx, (mf_inv1_r<K>(r, inv, tid)));
+    MF_WPHASE(ctx, (mf_fwd1_r2<K>(r, fwd, tid)));
     MF_FLINE(1)
     MF_FLINE(2)
-    MF_STAMP(5)
-    MF_PRIO_AT(5)
-    if (T1) {
-      MF_WPHASE(ctx, (mf_inv1_c<K>(r, twl, tid), mf_inv1_b<K>(r, inv, tid)));
-    }
-    if (T2) {
-      MF_WPHASE(ctx, (mf_fwd1_c2<K>(r, twl, tid), mf_fwd1_b2<K>(r, fwd, tid)));
-    }
-    MF_STAMP(6)
-    MF_PRIO_AT(6)
+    MF_PRIO_RAISE_YOUNG()
+    MF_WPHASE(ctx, (mf_inv1_c<K>(r, twl, tid), mf_inv1_b<K>(r, inv, tid)));
+    MF_WPHASE(ctx, (mf_fwd1_c2<K>(r, twl, tid), mf_fwd1_b2<K>(r, fwd, tid)));
     // stage C
-    if (T1) {
-      MF_WPHASE(ctx, (mf_inv0_r<K>(r, inv, tid)));
-    }
-    if (T2) {
-      MF_WPHASE(ctx, (mf_fwd2_r2<K>(r, fwd, tid)));
-    }
-    MF_STAMP(7)
-    MF_PRIO_AT(7)
+    MF_WPHASE(ctx, (mf_inv0_r<K>(r, inv, tid)));
+    MF_WPHASE(ctx, (mf_fwd2_r2<K>(r, fwd, tid)));
     MF_FLINE(3)
     MF_FLINE(4)
-    MF_STAMP(8)
-    MF_PRIO_AT(8)
-    if (T1) {
-      MF_WPHASE(ctx, (mf_store_line_c<K>(P, r, twl, c, z0, nout, i - 1, tid)));
-    }
-    if (T2) {
-      MF_WPHASE(ctx, (mf_dft8<-1>(r.t2, r.bad), mf_fwd2_b2<K>(r, fwd, tid)));
-    }
-    MF_STAMP(9)
-    MF_PRIO_AT(9)
+    MF_WPHASE(ctx, (mf_store_line_c<K>(P, r, twl, c, z0, nout, i - 1, tid)));
+    MF_WPHASE(ctx, (dftR<8, -1>(r.t2), mf_fwd2_b2<K>(r, fwd, tid)));
     MF_FLINE(5)
     MF_FLINE(6)
     MF_FLINE(7)
-    MF_STAMP(10)
-    MF_PRIO_AT(10)
 #undef MF_FLINE
     MF_WPHASE(ctx, (mf_tw0_ahead<K>(r, twl, tid)));
     MVN_PHASE(ctx, (void)0);
-    MF_STAMP(11)
-    MF_PRIO_AT(11)
-    MF_STAMP_FLUSH()
   }
+#undef MF_PRIO_RESET
+#undef MF_PRIO_RAISE_YOUNG
   MVN_PHASE_NOSYNC(ctx, (mf_report<K>(P, r)));
 }
 
@@ -840,7 +694,7 @@ MVN_HD void mf_taps_body(const MidFusedParams& P, long block, cfloat* lds, Ctx& 
   cfloat* twl = lds + 4 * MF_BUF;
   MVN_PHASE(ctx, (mf_taps_load(P, r, batch, c, tid), mf_build_twiddles(P, twl, tid)));
   MF_WPHASE(ctx, (mf_tw0_ahead<1>(r, twl, tid)));
-  MF_WPHASE(ctx, (mf_fwd0<1>(r, lds, twl, tid)));
+  MF_WPHASE(ctx, (mf_fwd0<1>(r, lds, tid)));
   MF_WPHASE(ctx, (mf_fwd1_a<1>(r, lds, twl, tid)));
   MF_WPHASE(ctx, (mf_fwd1_b<1>(r, lds, tid)));
   MF_WPHASE(ctx, (mf_fwd2_a<1>(r, lds, tid)));

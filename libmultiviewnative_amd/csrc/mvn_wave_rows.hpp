@@ -171,12 +171,9 @@ MVN_HD void wr_post_pair(cfloat& zk, cfloat& zm, cfloat w) {
 
 // row of lane `tid` in sweep `it` of workgroup `block` (two rows per wave: one per half-wave);
 // consecutive waves take consecutive row pairs
-#ifndef MVN_PROBE_TILE
-#define MVN_PROBE_TILE(t) (t)  // timing probes only (mvn_kernels.hip, -DMVN_PROBE)
-#endif
 MVN_HD long wr_row(long block, long nblocks, long it, int tid) {
   const long pair = (it * nblocks + block) * WrCfg::WAVES + (tid >> 6);
-  return 2 * (long)MVN_PROBE_TILE(pair) + ((tid >> 5) & 1);
+  return 2 * pair + ((tid >> 5) & 1);
 }
 
 // component-wise select (a select of the aggregates goes through a stack slot)
@@ -201,7 +198,8 @@ MVN_HD void wr_fetch_row(const RowsParams& P, long row, WrRegs& r, int tid) {
 }
 
 // the spectral row is requested one sweep ahead where the registers allow it: the divide and the
-// plain forms (the update forms hold psi and the weights as well and would spill)
+// plain forms (the update forms hold psi and the weights as well and would spill; they request it at
+// the start of phase A of the row itself and consume it at once)
 template <int EPI>
 constexpr bool wr_prefetch() {
   return EPI == MVN_EPI_DIVIDE || EPI == MVN_EPI_STORE;
@@ -209,22 +207,9 @@ constexpr bool wr_prefetch() {
 
 // The operands of the pointwise step (view, or psi and weights) of a row are requested one SWEEP
 // ahead as well: right behind the pointwise step of the row before, whose operand registers have
-// just become free (phase C).  Requested in phase A of the row itself (MVN_WR_EPI_AHEAD=0) they are
-// one LDS stage ahead of their use, far less than a loaded HBM round trip, and every wave of the
-// SIMD waits for them in phase C.
-#ifndef MVN_WR_EPI_AHEAD
-#define MVN_WR_EPI_AHEAD 1
-#endif
-// The fused update forms cannot hold the next spectral row across phases A - C next to psi, the
-// weights and the f64 chains; they request it at the start of phase D (MVN_WR_NX_IN_D=0: at the
-// start of phase A of the row itself, consumed at once).
-#ifndef MVN_WR_NX_IN_D
-#define MVN_WR_NX_IN_D 0
-#endif
-template <int MODE, int EPI>
-constexpr bool wr_nx_in_d() {
-  return MVN_WR_NX_IN_D && MODE == MVN_WR_C2R_R2C && !wr_prefetch<EPI>();
-}
+// just become free (phase C).  Requested in phase A of the row itself they would be one LDS stage
+// ahead of their use, far less than a loaded HBM round trip, and every wave of the SIMD would wait
+// for them in phase C.
 
 template <int EPI>
 MVN_HD void wr_fetch_epi(const RowsParams& P, long row, WrRegs& r, int tid) {
@@ -248,7 +233,7 @@ MVN_HD void wr_phase_a(const RowsParams& P, long row, long next_row, cfloat* row
   const int t = tid & 31;
   int ga, gb;
   wr_groups(t, ga, gb);
-  if (!wr_prefetch<EPI>() && !wr_nx_in_d<MODE, EPI>()) wr_fetch_row(P, row, r, tid);
+  if (!wr_prefetch<EPI>()) wr_fetch_row(P, row, r, tid);
   const qfloat a0 = r.nx[0], a1 = r.nx[1], b0 = r.nx[2], b1 = r.nx[3];
   cfloat za[4] = {cmake(a0.x, a0.y), cmake(a0.z, a0.w), cmake(a1.x, a1.y), cmake(a1.z, a1.w)};
   cfloat zb[4] = {cmake(b0.x, b0.y), cmake(b0.z, b0.w), cmake(b1.x, b1.y), cmake(b1.z, b1.w)};
@@ -289,7 +274,6 @@ MVN_HD void wr_phase_a(const RowsParams& P, long row, long next_row, cfloat* row
   }
   MVN_SCHED_FENCE();
   if (wr_prefetch<EPI>()) wr_fetch_row(P, next_row, r, tid);
-  if (!MVN_WR_EPI_AHEAD) wr_fetch_epi<EPI>(P, row, r, tid);
 }
 
 // ---- phases B / D: the radix-8 stage with M = 4 through the LDS ---------------------------------
@@ -345,7 +329,7 @@ MVN_HD void wr_phase_c(const RowsParams& P, long row, long next_row, cfloat* row
         mvn_epilogue_pair_t<EPI>(P.epi, P.out_real, i0 + 64 * jo, a[jo], r.ea[jo], r.eb[jo]);
         if (jo & 1) MVN_SCHED_FENCE();  // four values at a time: the f64 chains of all 16 would not fit
       }
-      if (MVN_WR_EPI_AHEAD) wr_fetch_epi<EPI>(P, next_row, r, tid);
+      wr_fetch_epi<EPI>(P, next_row, r, tid);
       return;
     }
 #pragma unroll
@@ -353,7 +337,7 @@ MVN_HD void wr_phase_c(const RowsParams& P, long row, long next_row, cfloat* row
       a[jo] = fx_epilogue_pair_value<EPI>(P.epi, i0 + 64 * jo, a[jo], r.ea[jo], r.eb[jo]);
       if (jo & 1) MVN_SCHED_FENCE();
     }
-    if (MVN_WR_EPI_AHEAD) wr_fetch_epi<EPI>(P, next_row, r, tid);
+    wr_fetch_epi<EPI>(P, next_row, r, tid);
   }
   dftR<8, -1>(a);
   if (MODE == MVN_WR_C2R_R2C) {
@@ -435,11 +419,9 @@ MVN_HD void wr_rows_body(const RowsParams& P, long block, long nblocks, cfloat* 
   cfloat* tws = lds;
   cfloat* rows = lds + WrCfg::TW;
   MVN_PHASE(ctx, (wr_copy_tables(tws, P.ax.tws, tid), wr_setup(P, r, rows, tid),
-                  (MODE != MVN_WR_R2C && (wr_prefetch<EPI>() || wr_nx_in_d<MODE, EPI>()))
-                      ? wr_fetch_row(P, wr_row(block, nblocks, 0, tid), r, tid)
-                      : (void)0,
-                  (MODE != MVN_WR_R2C && MVN_WR_EPI_AHEAD) ? wr_fetch_epi<EPI>(P, wr_row(block, nblocks, 0, tid), r, tid)
-                                                           : (void)0));
+                  (MODE != MVN_WR_R2C && wr_prefetch<EPI>()) ? wr_fetch_row(P, wr_row(block, nblocks, 0, tid), r, tid)
+                                                              : (void)0,
+                  MODE != MVN_WR_R2C ? wr_fetch_epi<EPI>(P, wr_row(block, nblocks, 0, tid), r, tid) : (void)0));
   const long pairs = (P.rows + 1) / 2;
   const long per_sweep = nblocks * WrCfg::WAVES;
   const long sweeps = (pairs + per_sweep - 1) / per_sweep;
@@ -452,14 +434,8 @@ MVN_HD void wr_rows_body(const RowsParams& P, long block, long nblocks, cfloat* 
     MVN_WPHASE(ctx, (wr_phase_c<MODE, EPI>(P, wr_row(block, nblocks, it, tid), wr_row(block, nblocks, it + 1, tid),
                                            rows, tws, r, tid)));
     if (MODE != MVN_WR_C2R) {
-      MVN_WPHASE(ctx, ((wr_nx_in_d<MODE, EPI>() && MVN_WR_NX_IN_D == 1)
-                           ? wr_fetch_row(P, wr_row(block, nblocks, it + 1, tid), r, tid)
-                           : (void)0,
-                       wr_phase_mid<-1>(wr_row(block, nblocks, it, tid), P.rows, rows, tws, tid)));
-      MVN_WPHASE(ctx, ((wr_nx_in_d<MODE, EPI>() && MVN_WR_NX_IN_D == 2)
-                           ? wr_fetch_row(P, wr_row(block, nblocks, it + 1, tid), r, tid)
-                           : (void)0,
-                       wr_phase_e<EPI>(P, wr_row(block, nblocks, it, tid), rows, r, tid)));
+      MVN_WPHASE(ctx, (wr_phase_mid<-1>(wr_row(block, nblocks, it, tid), P.rows, rows, tws, tid)));
+      MVN_WPHASE(ctx, (wr_phase_e<EPI>(P, wr_row(block, nblocks, it, tid), rows, r, tid)));
     }
   }
 }

@@ -105,19 +105,34 @@ def test_bench_keeps_foreign_output_off_stdout():
     assert "python-level noise" in r.stderr and "c-level noise" in r.stderr
 
 
+# every environment switch the library reads: tests, conftest.py, bench.py or the product table of INTEGRATION.md use
+# each of them (MVN_EMU_SO, the remaining one, is read by native.py alone)
+LIBRARY_ENV_SWITCHES = {
+    "MVN_TRACE", "MVN_DEVICES", "MVN_PAD_MODE", "MVN_PAD_GOOD_SIZE", "MVN_ENGINE_CACHE", "MVN_PSF_CACHE",
+    "MVN_NO_PIPELINE", "MVN_GRAPH", "MVN_GRAPH_MAX_MB", "MVN_MID_FUSED", "MVN_DIM0_DIRECT", "MVN_DIM0_DIRECT_MAX",
+    "MVN_DIM0_DIRECT_MIN_PLANE", "MVN_DIM0_DIRECT_MIN_ITEMS", "MVN_NO_FIXED", "MVN_WAVE_ROWS_MASK", "MVN_D0_STAGGER",
+    "MVN_NYQ_PACKED", "MVN_EMU_DEVICES", "MVN_EMU_TOTAL_MB",
+}
+
+
 def test_product_build_has_no_timing_experiment_switches():
-    # switches that change what a kernel computes (some give WRONG results) or how much LDS it
-    # asks for are timing experiments; they compile only under -DMVN_EXPERIMENTS, which the product target never sets
+    # switches that change what a kernel computes (some gave WRONG results) or how much LDS it
+    # asks for were timing experiments; none is left in the sources, and no make target builds a variant
     csrc = os.path.join(ROOT, "libmultiviewnative_amd", "csrc")
     plan = subprocess.check_output(["make", "-n", "-B", "-C", csrc, "all"]).decode()
     assert "libmultiviewnative.so" in plan and "MVN_EXPERIMENTS" not in plan and "MVN_PROBE" not in plan
     blob = open(native.PRODUCT_SO, "rb").read()
     for trace in (b"MVN_WR_LDS_PAD_KB", b"MVN_PROBE_WRAP", b"MVN_EXP_", b"MVN_D0_LDS_PAD"):
         assert trace not in blob, trace
-    # every experiment switch in the sources sits behind the one define
-    for name in os.listdir(csrc):
+    makefile = open(os.path.join(csrc, "Makefile")).read()
+    assert not re.search(r"^\s*(probe|variant)\b[^=\n]*:", makefile, re.M), "probe / variant target in csrc/Makefile"
+    read = set()
+    for name in sorted(os.listdir(csrc)):
         if not name.endswith((".hpp", ".hip", ".cpp")):
             continue
-        for line in open(os.path.join(csrc, name)):
-            if re.match(r"\s*#\s*if", line) and re.search(r"MVN_(EXP_|FX_NO_LDS_FUSED|WR_LDS_PAD_KB|D0_LDS_PAD_KB)", line):
-                assert "MVN_EXPERIMENTS" in line, (name, line)
+        src = open(os.path.join(csrc, name)).read()
+        for word in ("MVN_EXPERIMENTS", "MVN_PROBE", "MF_EXP_"):
+            assert word not in src, (name, word)
+        read |= set(re.findall(r"\b(?:getenv|env_int)\(\s*\"(\w+)\"", src))
+    # a new switch is a choice between code paths left to the user: it has to be named here on purpose
+    assert read == LIBRARY_ENV_SWITCHES, (sorted(read - LIBRARY_ENV_SWITCHES), sorted(LIBRARY_ENV_SWITCHES - read))

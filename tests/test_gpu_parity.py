@@ -1372,7 +1372,6 @@ def test_wave_row_variants_in_a_child_process(gpu, mask):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MVN_WAVE_ROWS_MASK=mask)
-    env.pop("MVN_NO_WAVE_ROWS", None)
     r = subprocess.run([sys.executable, "-c", _WAVE_ROWS_CHILD, root], capture_output=True, text=True,
                        timeout=600, env=env)
     assert r.returncode == 0 and "wave-row child ok " + mask in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
