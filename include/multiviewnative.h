@@ -25,6 +25,12 @@
  *  - inplace_gpu_convolution and the legacy convolution entry points are cyclic on exactly the
  *    given dims with the kernel centre on the origin, as in the reference (as_is_padding,
  *    src/multiviewnative.cu:29-30,39-40,58-75);
+ *  - stacks that do not fit on the device: by default the call is refused as in the reference's
+ *    all-on-device branch; mvn_set_memory_mode("auto") (mvn_engine_api.h) runs the reference's
+ *    interleaved branch instead - the views that do not fit keep their image and weights stacks
+ *    in host memory and stream them into a ring of device slots for every view update, with the
+ *    same result bit for bit.  mvn_set_memory_budget caps the device memory that mode plans with;
+ *    mvn_deconvolve_memory prices a call before it is made;
  *  - the CPU entry points (inplace_cpu_deconvolve / inplace_cpu_convolution,
  *    inc/multiviewnative.h:43-51) are NOT exported by the product library: this library has
  *    no CPU fallback.  Their restatement lives in oracle/ as test infrastructure.

@@ -45,6 +45,34 @@ MVN_API int mvn_set_pad_mode(const char* mode);
 /* The mode last selected with mvn_set_pad_mode ("zero" | "zero_exact" | "none"), or "" when the
  * environment / default decides -- what a caller that switches the policy for one call restores. */
 MVN_API const char* mvn_get_pad_mode(void);
+/* Memory mode of inplace_gpu_deconvolve / mvn_deconvolve_submit for the calls that follow (process-wide):
+ *   "resident" (default)  every stack on the device; a call whose stacks do not fit is refused ("memory
+ *                         constraints"), as in the reference's all-on-device branch (src/multiviewnative.cu:94-140)
+ *   "auto"                resident when the exact need (mvn_deconvolve_memory with 0 streamed views) fits; otherwise
+ *                         the fewest views whose image and weights stacks stay in host memory and cross PCIe into a
+ *                         ring of 2 (else 1) device slots for every view update, under the compute of the other
+ *                         views -- the reference's min-memory interleaved branch.  Refused only when not even every
+ *                         view streamed with one slot fits.
+ *   "stream"              every view streamed (the smallest footprint)
+ *   "stream:N"            exactly N views streamed (clamped to the view count), ring as in auto; for tests and
+ *                         measurements (auto never streams a single view: with one slot that costs what
+ *                         resident does)
+ * Results are those of the resident call, bit for bit.  NULL or "" returns to the default.  MVN_DEVICES calls
+ * (multiviewnative.h) are not affected. */
+MVN_API int mvn_set_memory_mode(const char* mode);
+/* the mode last selected with mvn_set_memory_mode, or "" when the environment / default decides */
+MVN_API const char* mvn_get_memory_mode(void);
+/* Caps the device memory the auto / stream planner may use: min(free memory, bytes).  bytes <= 0 removes the
+ * cap.  Ignored in resident mode. */
+MVN_API int mvn_set_memory_budget(long long bytes);
+/* Device bytes a call of inplace_gpu_deconvolve with this workspace allocates on a new engine when
+ * `streamed_views` of its views are streamed (0 = resident; > 0 with a ring of 2 slots: a ring of 1 slot needs
+ * bytes(1) - bytes(0) less), under the padding policy in force.  Takes the call's own padding and PSF form
+ * decisions, allocates nothing; only the dims members of the views are read.  For sizing blocks. */
+MVN_API int mvn_deconvolve_memory(struct workspace input, int device, int streamed_views, size_t* bytes);
+/* out[0] = calls that streamed views, out[1] = streamed view updates, out[2] = bytes streamed host -> device,
+ * all since process start */
+MVN_API int mvn_stream_counters(long long out[3]);
 /* A resident engine keeps, per view slot, the PSF spectra of the last call together with host
  * copies of the kernels they were made from; a call (or mvn_engine_set_view) that brings
  * bytewise identical kernels for a slot re-uses the spectra (the reference's

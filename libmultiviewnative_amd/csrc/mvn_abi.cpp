@@ -68,8 +68,9 @@ static std::mutex& device_mutex(int device) {
 
 // One resident engine per device is kept between inplace_gpu_deconvolve calls: Fiji deconvolves
 // block after block of the same shape, and allocating / freeing 4V+2 volumes per call costs more
-// than uploading them.  A call with another shape or view count replaces the
-// cached engine.  MVN_ENGINE_CACHE=0 disables the cache; mvn_release_cached_engines() empties it.
+// than uploading them.  A call with another shape, view count or residency plan
+// (memory modes, plan_engine) replaces the cached engine.  MVN_ENGINE_CACHE=0 disables the cache;
+// mvn_release_cached_engines() empties it.
 // The map is process-wide while calls are serialised per DEVICE only (Fiji runs one host thread
 // per GPU), so it has its own mutex, held just around find / erase / insert.
 static std::mutex& engine_cache_mutex() {
@@ -97,6 +98,118 @@ static std::unique_ptr<Engine> pop_cached_engine(int dev) {
   return e;
 }
 
+// ---------------------------------------------------------------------------------------------
+// memory mode of inplace_gpu_deconvolve / mvn_deconvolve_submit
+//   resident (default)  the check above: every stack on the device, or "memory constraints"
+//   auto                Engine::memory_need decides: resident when the exact need fits; otherwise the
+//                       fewest views s whose image and weights stay in host memory and cross PCIe into a
+//                       ring of device slots for every view update (2 slots where they fit, else 1);
+//                       "memory constraints" only when not even s = V with 1 slot fits (the reference's
+//                       min-memory interleaved branch, src/gpu_deconvolve_methods.cuh:82-326)
+//   stream              every view streamed: the smallest footprint
+//   stream:N            exactly N views streamed (clamped to the view count; tests and measurements: the planner
+//                       itself never streams one view, which costs as much as none with one ring slot)
+// Selected by mvn_set_memory_mode(), else resident.  The planner may use min(free device memory,
+// budget), budget = mvn_set_memory_budget() (ignored in resident mode).  Results are those of the resident call, bit for bit: same kernels, same order.
+// ---------------------------------------------------------------------------------------------
+enum { MVN_MEM_UNSET = -1, MVN_MEM_RESIDENT = 0, MVN_MEM_AUTO = 1, MVN_MEM_STREAM = 2 };
+// a mode is stored as one int: MVN_MEM_STREAM + 1 + N for stream:N
+static std::atomic<int> g_mem_mode{MVN_MEM_UNSET};
+static std::atomic<long long> g_mem_budget{-1};
+
+static int parse_memory_mode(const char* m) {
+  if (!m || !*m) return MVN_MEM_UNSET;
+  if (std::strcmp(m, "resident") == 0) return MVN_MEM_RESIDENT;
+  if (std::strcmp(m, "auto") == 0) return MVN_MEM_AUTO;
+  if (std::strcmp(m, "stream") == 0) return MVN_MEM_STREAM;
+  if (std::strncmp(m, "stream:", 7) == 0 && m[7]) {
+    char* end = nullptr;
+    const long n = std::strtol(m + 7, &end, 10);
+    if (*end == 0 && n >= 0 && n <= 65535) return MVN_MEM_STREAM + 1 + (int)n;
+  }
+  throw std::invalid_argument(std::string("unknown memory mode '") + m + "' (resident | auto | stream | stream:N)");
+}
+
+static int current_memory_mode() {
+  const int m = g_mem_mode.load();
+  return m == MVN_MEM_UNSET ? MVN_MEM_RESIDENT : m;
+}
+
+// the planner's cap below the free memory; 0 = none
+static size_t current_memory_budget() {
+  const long long b = g_mem_budget.load();
+  return b > 0 ? (size_t)b : 0;
+}
+
+static MemoryQuery memory_query(const shape_t& ext, const workspace& input, size_t embed_floats) {
+  MemoryQuery q;
+  q.ext = ext;
+  q.embed_floats = embed_floats;
+  for (int v = 0; v < input.num_views_; ++v) {
+    const view_data& d = input.data_[v];
+    q.kernels.push_back({{d.kernel1_dims_[0], d.kernel1_dims_[1], d.kernel1_dims_[2]}});
+    q.kernels.push_back({{d.kernel2_dims_[0], d.kernel2_dims_[1], d.kernel2_dims_[2]}});
+  }
+  return q;
+}
+
+// s streamed views spread evenly over the sweep (view floor((j + 1/2) V / s) for j < s), so that each upload
+// runs under the resident view updates between two streamed ones
+static std::vector<int> spread_views(int V, int s) {
+  std::vector<int> out;
+  for (int j = 0; j < s; ++j) out.push_back((int)(((2L * j + 1) * V) / (2L * s)));
+  return out;
+}
+
+// caller holds device_mutex(dev); the auto / stream modes of take_engine
+static std::unique_ptr<Engine> plan_engine(int key, int dev, const shape_t& ext, size_t embed_floats,
+                                           const workspace& input, int mode) {
+  const int V = input.num_views_;
+  MemoryQuery q = memory_query(ext, input, embed_floats);
+  auto need = [&](int s, int ring) {
+    q.streamed = s;
+    q.ring = ring;
+    return Engine::memory_need(q);
+  };
+  std::unique_ptr<Engine> cached = pop_cached_engine(key);
+  if (cached && !(engine_cache_enabled() && cached->layout().d0 == ext[0] && cached->layout().d1 == ext[1] &&
+                  cached->layout().d2 == ext[2] && cached->num_views() == V))
+    cached.reset();  // wrong shape: free its memory before the free memory is read
+  size_t free_b = 0, total_b = 0;
+  be::device_mem_info(&free_b, &total_b);
+  size_t avail = free_b;
+  if (cached) avail += need(cached->streamed_count(), cached->ring_size());  // (what re-planning would free)
+  const size_t budget = current_memory_budget();
+  if (budget) avail = std::min(avail, budget);
+  int s = -1, ring = 0;
+  const int first = mode == MVN_MEM_AUTO ? 0 : (mode == MVN_MEM_STREAM ? V : std::min(V, mode - MVN_MEM_STREAM - 1));
+  const int last = mode == MVN_MEM_AUTO ? V : first;
+  for (int c = first; c <= last && s < 0; ++c) {
+    if (c == 0) {
+      if (need(0, 0) <= avail) s = 0;
+      continue;
+    }
+    for (int r = 2; r >= 1 && s < 0; --r)
+      if (need(c, r) <= avail) {
+        s = c;
+        ring = r;
+      }
+  }
+  if (trace_on())
+    std::printf("[lmvn::inplace_gpu_deconvolve] memory plan: %.1f MB available (free %.1f MB, budget %.1f MB): %s\n",
+                avail / 1048576.0, free_b / 1048576.0, budget / 1048576.0,
+                s < 0 ? "does not fit"
+                      : (std::to_string(s) + " of " + std::to_string(V) + " views streamed, ring of " +
+                         std::to_string(ring) + ", " + std::to_string(need(s, ring) >> 20) + " MB")
+                            .c_str());
+  if (s < 0) throw std::runtime_error("FFT: Unable to run on GPU due to memory constraints");
+  if (cached && cached->streamed_count() == s && cached->ring_size() == ring) return cached;
+  cached.reset();  // another residency plan: free it before the new engine allocates
+  std::unique_ptr<Engine> e(new Engine(dev, ext, V));
+  e->set_residency(spread_views(V, s), ring);
+  return e;
+}
+
 // caller holds device_mutex(dev).  The memory heuristic of src/multiviewnative.cu:94-119, restated
 // for the resident layout (4 volumes per view -- view, weights, two spectra -- + psi + work + the
 // spectrum scratch of the PSF preparation, + the host-shaped embedding scratch of the padded
@@ -104,11 +217,13 @@ static std::unique_ptr<Engine> pop_cached_engine(int dev) {
 // shape is re-used as it is (its memory is what the check would ask for), and a stale one of another
 // shape is freed BEFORE the free memory is read -- so that "does not fit" is said here, before any
 // work is queued, not by a failing hipMalloc on the staging thread.
-static std::unique_ptr<Engine> take_engine(int key, int dev, const shape_t& ext, int V, size_t embed_floats) {
+static std::unique_ptr<Engine> take_engine(int key, int dev, const shape_t& ext, int V, size_t embed_floats,
+                                           const workspace& input, int mem_mode) {
+  if (mem_mode != MVN_MEM_RESIDENT) return plan_engine(key, dev, ext, embed_floats, input, mem_mode);
   std::unique_ptr<Engine> e = pop_cached_engine(key);  // key = device + lane * kLaneStride
   if (e && engine_cache_enabled()) {
     const Layout& L = e->layout();
-    if (L.d0 == ext[0] && L.d1 == ext[1] && L.d2 == ext[2] && e->num_views() == V) return e;
+    if (L.d0 == ext[0] && L.d1 == ext[1] && L.d2 == ext[2] && e->num_views() == V && e->streamed_count() == 0) return e;
   }
   e.reset();  // wrong shape: free its memory before the new engine allocates
   Layout L(ext[0], ext[1], ext[2]);
@@ -364,48 +479,82 @@ static bool multi_device_call(imageType* psi, const workspace& input, const shap
   return true;
 }
 
+// extents of the stacks, of the volume the call runs on (padding policy: see the block comment above good_extent())
+// and the stacks' offset inside it; dim0_kept_exact: dim0 was left at image + kernel - 1 for the direct dim0 leg
+static void call_extents(const workspace& input, int pad_mode, shape_t* dims_out, shape_t* ext_out, int off[3],
+                         bool* dim0_kept_exact_out) {
+  const int V = input.num_views_;
+  const shape_t dims = to_shape(input.data_[0].image_dims_);
+  for (int v = 0; v < V; ++v) {
+    const view_data& d = input.data_[v];
+    if (to_shape(d.image_dims_) != dims)
+      throw std::invalid_argument("all views must share image_dims_ (view " + std::to_string(v) + ")");
+    if (d.weights_dims_ && to_shape(d.weights_dims_) != dims)
+      throw std::invalid_argument("weights_dims_ must equal image_dims_ (view " + std::to_string(v) + ")");
+  }
+  for (int d = 0; d < 3; ++d)
+    if (dims[d] < 1) throw std::invalid_argument("image extents must be >= 1");
+  shape_t ext = dims;  // padding policy: see the block comment above good_extent()
+  off[0] = off[1] = off[2] = 0;
+  bool dim0_kept_exact = false;
+  if (pad_mode != MVN_PAD_NONE) {
+    for (int d = 2; d >= 0; --d) {
+      int kmax = 1;
+      for (int v = 0; v < V; ++v) {
+        kmax = std::max(kmax, input.data_[v].kernel1_dims_[d]);
+        kmax = std::max(kmax, input.data_[v].kernel2_dims_[d]);
+      }
+      ext[d] = dims[d] + kmax - 1;
+      off[d] = (kmax - 1) / 2;
+      if (pad_mode != MVN_PAD_ZERO) continue;
+      // dim0 is not transformed when every PSF is thin enough for the direct dim0 leg (mvn_dim0_direct.hpp):
+      // it then keeps the reference's exact image + kernel - 1 (542 planes for a 512-block with 31^3 PSFs, not
+      // 576: 6 % less volume in every pass) - provided the rows of a plane keep whole tiles of the fixed
+      // last-axis kernels whatever the plane count (d1 a multiple of 16)
+      if (d == 0 && ext[1] % 16 == 0 && Engine::direct_ok_for(kmax, ext[0], ext[1], ext[2])) {
+        dim0_kept_exact = true;
+        continue;
+      }
+      ext[d] = good_extent(ext[d], d == 2);
+    }
+  }
+  *dims_out = dims;
+  *ext_out = ext;
+  *dim0_kept_exact_out = dim0_kept_exact;
+}
+
+static size_t embed_floats_of(const shape_t& dims, const shape_t& ext) {
+  const bool embedded = ext[0] != dims[0] || ext[1] != dims[1] || ext[2] != dims[2];
+  return embedded ? (size_t)dims[0] * (size_t)dims[1] * (size_t)dims[2] : 0;
+}
+
+// the engine's own per-kernel decision (Engine::direct_form) taken before any engine exists: when a kernel would not
+// be held in the direct form, dim0 is padded like the other axes (see deconvolve_call)
+static bool all_direct_for(const shape_t& ext, const workspace& input) {
+  const Layout L(ext[0], ext[1], ext[2]);
+  for (int v = 0; v < input.num_views_; ++v)
+    if (!Engine::direct_form_for(L, input.data_[v].kernel1_dims_) || !Engine::direct_form_for(L, input.data_[v].kernel2_dims_))
+      return false;
+  return true;
+}
+
 static void deconvolve_call(imageType* psi, const workspace& input, int device, int lane, int pad_mode) {
   {
     check_workspace(psi, input);
     const int V = input.num_views_;
     if (V == 0 || input.num_iterations_ <= 0) return;  // 0 iterations returns psi unchanged
-    const shape_t dims = to_shape(input.data_[0].image_dims_);
-    for (int v = 0; v < V; ++v) {
-      const view_data& d = input.data_[v];
-      if (to_shape(d.image_dims_) != dims)
-        throw std::invalid_argument("all views must share image_dims_ (view " + std::to_string(v) + ")");
-      if (d.weights_dims_ && to_shape(d.weights_dims_) != dims)
-        throw std::invalid_argument("weights_dims_ must equal image_dims_ (view " + std::to_string(v) + ")");
-    }
-    for (int d = 0; d < 3; ++d)
-      if (dims[d] < 1) throw std::invalid_argument("image extents must be >= 1");
-    shape_t ext = dims;  // padding policy: see the block comment above good_extent()
+    shape_t dims, ext;
     int off[3] = {0, 0, 0};
     bool dim0_kept_exact = false;
-    if (pad_mode != MVN_PAD_NONE) {
-      for (int d = 2; d >= 0; --d) {
-        int kmax = 1;
-        for (int v = 0; v < V; ++v) {
-          kmax = std::max(kmax, input.data_[v].kernel1_dims_[d]);
-          kmax = std::max(kmax, input.data_[v].kernel2_dims_[d]);
-        }
-        ext[d] = dims[d] + kmax - 1;
-        off[d] = (kmax - 1) / 2;
-        if (pad_mode != MVN_PAD_ZERO) continue;
-        // dim0 is not transformed when every PSF is thin enough for the direct dim0 leg (mvn_dim0_direct.hpp):
-        // it then keeps the reference's exact image + kernel - 1 (542 planes for a 512-block with 31^3 PSFs, not
-        // 576: 6 % less volume in every pass) - provided the rows of a plane keep whole tiles of the fixed
-        // last-axis kernels whatever the plane count (d1 a multiple of 16)
-        if (d == 0 && ext[1] % 16 == 0 && Engine::direct_ok_for(kmax, ext[0], ext[1], ext[2])) {
-          dim0_kept_exact = true;
-          continue;
-        }
-        ext[d] = good_extent(ext[d], d == 2);
-      }
-    }
+    call_extents(input, pad_mode, &dims, &ext, off, &dim0_kept_exact);
     if (lane == 0) {  // (the second lane belongs to the block pipeline of mvn_deconvolve_submit)
       const std::vector<int> devs = multi_devices_from_env();
       if (!devs.empty() && multi_device_call(psi, input, dims, ext, off, pad_mode, devs)) return;
+    }
+    const int mem_mode = current_memory_mode();
+    if (mem_mode != MVN_MEM_RESIDENT && dim0_kept_exact && !all_direct_for(ext, input)) {
+      dim0_kept_exact = false;  // (decided before the planner prices the engine; the check below then agrees)
+      ext[0] = good_extent(ext[0], false);
     }
     const int dev = pick_device(device);
     const int key = dev + lane * kLaneStride;
@@ -414,7 +563,7 @@ static void deconvolve_call(imageType* psi, const workspace& input, int device, 
     const bool embedded = ext[0] != dims[0] || ext[1] != dims[1] || ext[2] != dims[2];
     // on failure the engine is simply dropped
     std::unique_ptr<Engine> eng_owner =
-        take_engine(key, dev, ext, V, embedded ? (size_t)dims[0] * (size_t)dims[1] * (size_t)dims[2] : 0);
+        take_engine(key, dev, ext, V, embedded ? (size_t)dims[0] * (size_t)dims[1] * (size_t)dims[2] : 0, input, mem_mode);
     if (dim0_kept_exact) {
       // The static rule above and the engine's own per-kernel decision (Engine::direct_form: also asks that the
       // tap arrays' plan is of the volume plan's kernel family) must agree, or an exact dim0 such as 542 = 2 * 271
@@ -427,7 +576,7 @@ static void deconvolve_call(imageType* psi, const workspace& input, int device, 
         eng_owner.reset();
         ext[0] = good_extent(ext[0], false);
         if (trace_on()) std::printf("[lmvn::trace] direct dim0 leg refused by the engine: dim0 padded to %d\n", ext[0]);
-        eng_owner = take_engine(key, dev, ext, V, (size_t)dims[0] * (size_t)dims[1] * (size_t)dims[2]);
+        eng_owner = take_engine(key, dev, ext, V, (size_t)dims[0] * (size_t)dims[1] * (size_t)dims[2], input, mem_mode);
       }
     }
     Engine& eng = *eng_owner;
@@ -443,7 +592,7 @@ static void deconvolve_call(imageType* psi, const workspace& input, int device, 
       const char* e = std::getenv("MVN_NO_PIPELINE");
       return e && *e && std::strcmp(e, "0") != 0;
     }();
-    if (no_pipeline) {
+    if (no_pipeline && eng.streamed_count() == 0) {  // (streamed views need the uploader thread)
       for (int v = 0; v < V; ++v) {
         const view_data& d = input.data_[v];
         eng.set_view(v, d.image_, d.weights_, d.kernel1_, d.kernel1_dims_, d.kernel2_, d.kernel2_dims_);
@@ -492,6 +641,11 @@ static void deconvolve_call(imageType* psi, const workspace& input, int device, 
           eng.stage_view(v, d.image_, d.weights_, d.kernel1_, d.kernel1_dims_, d.kernel2_, d.kernel2_dims_);
         }
         eng.finish_staging();
+        // out-of-core views: their stacks again for every later sweep, in sweep order, each as soon as its ring
+        // slot is free (Engine::stream_view)
+        for (int it = 1; it < input.num_iterations_ && eng.streamed_count() > 0; ++it)
+          for (int v = 0; v < V; ++v)
+            if (eng.is_streamed(v)) eng.stream_view(v, input.data_[v].image_, input.data_[v].weights_);
         if (trace_on())
           std::printf("[lmvn::trace] %-28s %8.1f ms (uploader thread)\n", "stage all views",
                       std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u0).count());
@@ -505,6 +659,7 @@ static void deconvolve_call(imageType* psi, const workspace& input, int device, 
       eng.iterate(input.num_iterations_, input.lambda_, input.minValue_);
     } catch (...) {
       main_err = std::current_exception();
+      eng.abort_streaming();  // (an uploader waiting for a ring slot that will not be freed)
     }
     lap("enqueue iterations");
     uploader.join();
@@ -516,6 +671,7 @@ static void deconvolve_call(imageType* psi, const workspace& input, int device, 
     lap("wait for the device");
     eng.get_psi(psi);
     lap("download psi");
+    if (eng.streamed_count() > 0) Engine::count_streamed_call();
     give_back_engine(key, std::move(eng_owner));
   }
 }
@@ -623,6 +779,60 @@ const char* mvn_get_pad_mode(void) {
     case MVN_PAD_NONE: return "none";
     default: return "";
   }
+}
+
+int mvn_set_memory_mode(const char* mode) {
+  return guarded("mvn_set_memory_mode", [&] { g_mem_mode.store(parse_memory_mode(mode)); });
+}
+
+const char* mvn_get_memory_mode(void) {
+  static thread_local std::string name;
+  const int m = g_mem_mode.load();
+  switch (m) {
+    case MVN_MEM_UNSET: return "";
+    case MVN_MEM_RESIDENT: return "resident";
+    case MVN_MEM_AUTO: return "auto";
+    case MVN_MEM_STREAM: return "stream";
+    default:
+      name = "stream:" + std::to_string(m - MVN_MEM_STREAM - 1);
+      return name.c_str();
+  }
+}
+
+int mvn_set_memory_budget(long long bytes) {
+  return guarded("mvn_set_memory_budget", [&] { g_mem_budget.store(bytes > 0 ? bytes : -1); });
+}
+
+int mvn_deconvolve_memory(struct workspace input, int device, int streamed_views, size_t* bytes) {
+  return guarded("mvn_deconvolve_memory", [&] {
+    if (!bytes) throw std::invalid_argument("null bytes");
+    *bytes = 0;
+    if (!input.data_ || input.num_views_ < 1) throw std::invalid_argument("no views");
+    for (int v = 0; v < input.num_views_; ++v) {
+      const view_data& d = input.data_[v];
+      if (!d.image_dims_ || !d.kernel1_dims_ || !d.kernel2_dims_)
+        throw std::invalid_argument("view " + std::to_string(v) + " has null dims");
+    }
+    if (streamed_views < 0 || streamed_views > input.num_views_)
+      throw std::invalid_argument("streamed_views must be in [0, num_views_]");
+    pick_device(device);
+    shape_t dims, ext;
+    int off[3];
+    bool dim0_kept_exact = false;
+    call_extents(input, current_pad_mode(), &dims, &ext, off, &dim0_kept_exact);
+    if (dim0_kept_exact && !all_direct_for(ext, input)) ext[0] = good_extent(ext[0], false);
+    MemoryQuery q = memory_query(ext, input, embed_floats_of(dims, ext));
+    q.streamed = streamed_views;
+    q.ring = streamed_views > 0 ? 2 : 0;
+    *bytes = Engine::memory_need(q);
+  });
+}
+
+int mvn_stream_counters(long long out[3]) {
+  return guarded("mvn_stream_counters", [&] {
+    if (!out) throw std::invalid_argument("null out");
+    Engine::stream_counters(out);
+  });
 }
 
 // single convolution on the engine's kernels; shared by the three convolution entry points

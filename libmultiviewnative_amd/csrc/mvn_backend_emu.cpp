@@ -58,7 +58,7 @@ void device_name(int, char* name256) {
   std::strcpy(name256, "mvn host emulation");
 }
 // "device memory" accounting per fake device: total = MVN_EMU_TOTAL_MB (default 8 GiB), free =
-// total - live dmalloc bytes, so that the memory heuristic of the ABI call can be tested
+// total - live dmalloc bytes, so that the memory heuristic and the memory model of the ABI call can be tested
 static std::mutex g_mem_mu;
 static std::map<void*, std::pair<int, size_t>> g_live;  // pointer -> (device, bytes)
 static std::map<int, size_t> g_used;
@@ -78,7 +78,15 @@ void device_arch(int, int* major, int* minor) {
   *minor = 0;
 }
 
+// an allocation beyond the total fails, as hipMalloc would: tests of the memory model (Engine::memory_need) run
+// the ABI call with the total set to the model's figure
 void* dmalloc(size_t bytes) {
+  {
+    std::lock_guard<std::mutex> lk(g_mem_mu);
+    if (g_used[t_device] + bytes > emu_total())
+      throw std::runtime_error("emu: device memory exhausted (" + std::to_string(g_used[t_device]) + " + " +
+                               std::to_string(bytes) + " bytes > MVN_EMU_TOTAL_MB)");
+  }
   void* p = std::malloc(bytes ? bytes : 1);
   if (!p) throw std::bad_alloc();
   std::lock_guard<std::mutex> lk(g_mem_mu);

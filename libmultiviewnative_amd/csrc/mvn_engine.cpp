@@ -1,6 +1,7 @@
 // mvn_engine.cpp -- see mvn_engine.hpp
 #include "mvn_engine.hpp"
 
+#include <algorithm>
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
@@ -699,6 +700,7 @@ Engine::Engine(int device, const shape_t& dims, int num_views) : device_(device)
   be::dzero(poison_own_, 256, stream_);
   poison_ = poison_own_;
   views_.resize((size_t)num_views);
+  stream_pos_.assign((size_t)num_views, -1);
   spec_tiled_ = plan_->tiles_spectra();
   // read per engine (tests).  MVN_DIM0_DIRECT_MAX: most PSF planes the direct dim0 leg takes on
   // (MVN_D0_MAX_TAPS = 33 are instantiated); measured at 512^3 x 6 views on MI355X (profiles/r03_dim0_direct.md)
@@ -733,8 +735,10 @@ Engine::~Engine() {
   } catch (...) {
   }
   for (size_t v = 0; v < views_.size(); ++v) {
-    be::dfree(views_[v].image);
-    be::dfree(views_[v].weights);
+    if (stream_pos_[v] < 0) {  // (a streamed view's pointers are borrowed from the ring during its update)
+      be::dfree(views_[v].image);
+      be::dfree(views_[v].weights);
+    }
     be::dfree(views_[v].spec1);
     be::dfree(views_[v].nyq1);
     be::dfree(views_[v].spec2);
@@ -743,8 +747,14 @@ Engine::~Engine() {
       be::dfree(views_[v].taps[i]);
       be::dfree(views_[v].taps_nyq[i]);
       be::dfree(views_[v].taps_l[i]);
-      be::dfree(views_[v].taps_scr[i]);
     }
+  }
+  be::dfree(taps_scr_);
+  for (size_t r = 0; r < ring_.size(); ++r) {
+    be::dfree(ring_[r].image);
+    be::dfree(ring_[r].weights);
+    if (ring_[r].filled) be::event_destroy(ring_[r].filled);
+    if (ring_[r].freed) be::event_destroy(ring_[r].freed);
   }
   be::dfree(psi_);
   // (work_ and work2_ swap roles at every direct leg: freed by their allocations, not by their roles)
@@ -791,6 +801,10 @@ void Engine::set_embedding(const int dims[3], const int off[3]) {
     if (views_[v].image) be::dzero(views_[v].image, plan_->main_bytes(), stream_);
     if (views_[v].weights) be::dzero(views_[v].weights, plan_->main_bytes(), stream_);
   }
+  for (size_t r = 0; r < ring_.size(); ++r) {
+    be::dzero(ring_[r].image, plan_->main_bytes(), stream_);
+    be::dzero(ring_[r].weights, plan_->main_bytes(), stream_);
+  }
   be::stream_sync(stream_);
   be::dfree(embed_scratch_);
   embed_scratch_ = nullptr;
@@ -820,7 +834,7 @@ void Engine::upload_volume(float* dst, const float* host, be::stream_t s) {
 
 void Engine::alloc_view(ViewSlot& s) {
   const size_t mb = plan_->main_bytes();
-  if (s.image) return;
+  if (s.image || stream_pos_[(size_t)(&s - views_.data())] >= 0) return;  // (streamed views: the ring's slots)
   s.image = (float*)be::dmalloc(mb);
   s.weights = (float*)be::dmalloc(mb);
   // the PSF buffers (3-D spectra or direct-form taps) are allocated by prepare_psf, which knows the form
@@ -911,8 +925,7 @@ void Engine::prepare_psf(ViewSlot& s, int i, const float* d_kernel, const int* k
       s.taps[i] = (float*)be::dmalloc(tp->main_bytes());
       if (tp->nyq_bytes()) s.taps_nyq[i] = (cfloat*)be::dmalloc(tp->nyq_bytes());
       be::dfree(s.taps_l[i]);
-      be::dfree(s.taps_scr[i]);
-      s.taps_l[i] = s.taps_scr[i] = nullptr;
+      s.taps_l[i] = nullptr;
       s.tap_kd[i] = kd;
     }
     s.taps_l_ok[i] = false;
@@ -925,13 +938,19 @@ void Engine::prepare_psf(ViewSlot& s, int i, const float* d_kernel, const int* k
     tp->axis1(MVN_ST_FWD, (cfloat*)s.taps[i], s.taps_nyq[i], st, nullptr);
     if (lines_capable_ && tp->lines_capable() && mvn_dim0_taps_template(kdims[0]) <= 31) {
       // the same planes for the fused middle pass: line layout, Nyquist bins packed, its own bin order along dim1
-      if (!s.taps_l[i]) {
-        s.taps_l[i] = (float*)be::dmalloc(tp->main_bytes());
-        s.taps_scr[i] = (float*)be::dmalloc(tp->main_bytes());
+      if (!s.taps_l[i]) s.taps_l[i] = (float*)be::dmalloc(tp->main_bytes());
+      if (taps_scr_bytes_ < tp->main_bytes()) {  // one scratch per engine, as large as the deepest tap array
+        be::stream_sync(st);
+        be::stream_sync(stream_);
+        be::dfree(taps_scr_);
+        taps_scr_ = nullptr;
+        taps_scr_bytes_ = 0;
+        taps_scr_ = (float*)be::dmalloc(tp->main_bytes());
+        taps_scr_bytes_ = tp->main_bytes();
       }
-      be::dzero(s.taps_scr[i], tp->main_bytes(), st);
-      be::launch_scatter_psf(d_kernel, kdims[0], kdims[1], kdims[2], s.taps_scr[i], kd, L.d1, L.d2, tp->L.RP, scale, st);
-      tp->rows_r2c(s.taps_scr[i], (cfloat*)s.taps_l[i], nullptr, st, nullptr, 0, -1, true);
+      be::dzero(taps_scr_, tp->main_bytes(), st);
+      be::launch_scatter_psf(d_kernel, kdims[0], kdims[1], kdims[2], taps_scr_, kd, L.d1, L.d2, tp->L.RP, scale, st);
+      tp->rows_r2c(taps_scr_, (cfloat*)s.taps_l[i], nullptr, st, nullptr, 0, -1, true);
       tp->taps_to_lines((cfloat*)s.taps_l[i], st);
       s.taps_l_ok[i] = true;
     }
@@ -1288,6 +1307,7 @@ void Engine::set_view(int v, const float* image, const float* weights, const flo
                       const int* k1dims, const float* kernel2, const int* k2dims) {
   if (v < 0 || v >= (int)views_.size()) throw std::out_of_range("mvn: view index");
   be::set_device(device_);
+  if (stream_pos_[(size_t)v] >= 0) throw std::logic_error("mvn: a streamed view is staged by the pipelined call only");
   ViewSlot& s = views_[(size_t)v];
   alloc_view(s);
   upload_volume(s.image, image, stream_);
@@ -1326,6 +1346,11 @@ void Engine::reserve_views() {
   for (size_t v = 0; v < views_.size(); ++v)
     if (!staged_ev_[v]) staged_ev_[v] = be::event_create_sync();
   staged_.assign(views_.size(), 0);
+  {
+    std::lock_guard<std::mutex> lk(stage_mu_);
+    uploads_ = consumed_ = 0;
+    stream_abort_ = false;
+  }
   pipelined_ = true;
 }
 
@@ -1333,8 +1358,12 @@ void Engine::stage_view(int v, const float* image, const float* weights, const f
                         const int* k1dims, const float* kernel2, const int* k2dims) {
   be::set_device(device_);  // the HIP device is per host thread
   ViewSlot& s = views_[(size_t)v];
-  upload_volume(s.image, image, upload_stream_);
-  upload_volume(s.weights, weights, upload_stream_);
+  if (stream_pos_[(size_t)v] >= 0) {
+    ring_upload(v, image, weights);
+  } else {
+    upload_volume(s.image, image, upload_stream_);
+    upload_volume(s.weights, weights, upload_stream_);
+  }
   const float* ks[2] = {kernel1, kernel2};
   const int* kd[2] = {k1dims, k2dims};
   for (int i = 0; i < 2; ++i) {
@@ -1364,6 +1393,7 @@ void Engine::staging_failed() {
     std::lock_guard<std::mutex> lk(stage_mu_);
     for (size_t v = 0; v < staged_.size(); ++v)
       if (staged_[v] == 0) staged_[v] = -1;
+    stream_abort_ = true;  // (a main thread waiting for a ring slot's upload)
   }
   stage_cv_.notify_all();
 }
@@ -1384,6 +1414,186 @@ void Engine::wait_staged(int v) {
   if (staged_[(size_t)v] < 0) throw std::runtime_error("mvn: staging of view " + std::to_string(v) + " failed");
   lk.unlock();
   be::stream_wait_event(stream_, staged_ev_[(size_t)v]);
+}
+
+// ---- out-of-core views ---------------------------------------------------------------------------
+// Upload k of the call (stream order: the streamed views of sweep 0, then of sweep 1, ...) lands in ring slot
+// k % R.  The uploader waits on the host until view update k - R - the slot's previous reader - has been enqueued,
+// then makes the upload stream wait for that update's `freed` event; the main thread waits on the host until
+// upload k has been enqueued, then makes the compute stream wait for its `filled` event.  Both counters move
+// under stage_mu_, so neither event is re-recorded before the wait that refers to its last record was enqueued.
+static std::atomic<long long> g_stream_calls{0}, g_stream_updates{0}, g_stream_bytes{0};
+
+void Engine::stream_counters(long long out[3]) {
+  out[0] = g_stream_calls.load();
+  out[1] = g_stream_updates.load();
+  out[2] = g_stream_bytes.load();
+}
+
+void Engine::count_streamed_call() { ++g_stream_calls; }
+
+void Engine::set_residency(const std::vector<int>& streamed, int ring) {
+  if (!streamed_order_.empty() || !ring_.empty()) throw std::logic_error("mvn: the residency plan is set once");
+  for (size_t v = 0; v < views_.size(); ++v)
+    if (views_[v].image) throw std::logic_error("mvn: the residency plan is set before the views are allocated");
+  if (streamed.empty()) {
+    if (ring != 0) throw std::invalid_argument("mvn: a ring without streamed views");
+    return;
+  }
+  if (ring < 1 || ring > 2) throw std::invalid_argument("mvn: ring of 1 or 2 slots");
+  be::set_device(device_);
+  for (size_t j = 0; j < streamed.size(); ++j) {
+    const int v = streamed[j];
+    if (v < 0 || v >= (int)views_.size() || stream_pos_[(size_t)v] >= 0 || (j && v < streamed[j - 1]))
+      throw std::invalid_argument("mvn: streamed views must be distinct view indices in sweep order");
+    stream_pos_[(size_t)v] = (int)j;
+    streamed_order_.push_back(v);
+  }
+  const size_t mb = plan_->main_bytes();
+  ring_.resize((size_t)ring);
+  for (RingSlot& r : ring_) {  // zeroed once: the padded rows and the embedding margins are never written
+    r.image = (float*)be::dmalloc(mb);
+    r.weights = (float*)be::dmalloc(mb);
+    be::dzero(r.image, mb, stream_);
+    be::dzero(r.weights, mb, stream_);
+    r.filled = be::event_create_sync();
+    r.freed = be::event_create_sync();
+  }
+  be::stream_sync(stream_);
+}
+
+void Engine::ring_upload(int v, const float* image, const float* weights) {
+  if (stream_pos_[(size_t)v] < 0) throw std::logic_error("mvn: view " + std::to_string(v) + " is resident");
+  const long R = (long)ring_.size();
+  long k;
+  {
+    std::unique_lock<std::mutex> lk(stage_mu_);
+    k = uploads_;
+    stage_cv_.wait(lk, [&] { return stream_abort_ || consumed_ >= k - R + 1; });
+    if (stream_abort_) throw std::runtime_error("mvn: streamed call abandoned");
+  }
+  RingSlot& r = ring_[(size_t)(k % R)];
+  if (k >= R) be::stream_wait_event(upload_stream_, r.freed);
+  upload_volume(r.image, image, upload_stream_);
+  upload_volume(r.weights, weights, upload_stream_);
+  be::event_record(r.filled, upload_stream_);
+  g_stream_bytes += (long long)(2 * host_floats() * sizeof(float));
+  {
+    std::lock_guard<std::mutex> lk(stage_mu_);
+    ++uploads_;
+  }
+  stage_cv_.notify_all();
+}
+
+void Engine::stream_view(int v, const float* image, const float* weights) {
+  if (v < 0 || v >= (int)views_.size()) throw std::out_of_range("mvn: view index");
+  be::set_device(device_);
+  ring_upload(v, image, weights);
+}
+
+void Engine::abort_streaming() {
+  {
+    std::lock_guard<std::mutex> lk(stage_mu_);
+    stream_abort_ = true;
+  }
+  stage_cv_.notify_all();
+}
+
+void Engine::ring_acquire(ViewSlot& s) {
+  long k;
+  {
+    std::unique_lock<std::mutex> lk(stage_mu_);
+    k = consumed_;
+    stage_cv_.wait(lk, [&] { return uploads_ > k || stream_abort_; });
+    if (uploads_ <= k) throw std::runtime_error("mvn: upload of a streamed view failed");
+  }
+  const RingSlot& r = ring_[(size_t)(k % (long)ring_.size())];
+  be::stream_wait_event(stream_, r.filled);
+  s.image = r.image;
+  s.weights = r.weights;
+}
+
+// the view update that reads the pair has been enqueued whole (its last reader is the update pass ending
+// conv_pair): the slot is free behind it
+void Engine::ring_release(ViewSlot& s) {
+  const long k = consumed_;  // (written by this thread only)
+  be::event_record(ring_[(size_t)(k % (long)ring_.size())].freed, stream_);
+  s.image = s.weights = nullptr;
+  ++g_stream_updates;
+  {
+    std::lock_guard<std::mutex> lk(stage_mu_);
+    ++consumed_;
+  }
+  stage_cv_.notify_all();
+}
+
+// ---- memory model -------------------------------------------------------------------------------
+// Plan tables (a few twiddle and index arrays per axis), the poison words of the plans and allocator rounding are
+// not listed one by one: every allocation is rounded up to 4 KiB and a fixed slack covers the rest.
+static const size_t kMemSlack = (size_t)1 << 20;
+static size_t alloc_rounded(size_t b) { return (b + 4095) & ~(size_t)4095; }
+
+// Plan3D::lines_capable() of a plan of layout L, from the same host-side decisions and without its device tables
+static bool lines_capable_for(const Layout& L) {
+  if (!rows_fixed(L)) return false;
+  int T = 0, threads = 0;
+  size_t lds = 0;
+  fixed_rows_geom(L.h, &T, &threads, &lds);
+  if (!(L.even && L.h == 256 && L.C == 256 && L.d1 == MF_N1 && T == 16)) return false;
+  const AxisPlanHost ax1(L.d1, ax1_fixed(L));
+  return !ax1.bluestein && ax1.nfft == MF_N1;
+}
+
+bool Engine::direct_form_for(const Layout& L, const int* kdims) {
+  if (env_int("MVN_DIM0_DIRECT", 1) == 0 || kdims[0] > env_int("MVN_DIM0_DIRECT_MAX", MVN_D0_MAX_TAPS) ||
+      !mvn_dim0_direct_possible(kdims[0], L.d0) ||
+      mvn_dim0_items_for(kdims[0], L.d0, (long)L.d1 * L.C, env_int("MVN_DIM0_DIRECT_MIN_PLANE", 131072)) <
+          env_int("MVN_DIM0_DIRECT_MIN_ITEMS", 0))
+    return false;
+  const Layout T(((kdims[0] + 1 + 15) / 16) * 16, L.d1, L.d2);  // (C, RP and parity: same d2 as L)
+  return rows_fixed(T) == rows_fixed(L) && ax1_fixed(T) == ax1_fixed(L);
+}
+
+size_t Engine::memory_need(const MemoryQuery& q) {
+  const Layout L(q.ext[0], q.ext[1], q.ext[2]);
+  const int V = (int)(q.kernels.size() / 2);
+  if (q.kernels.size() % 2 || q.streamed < 0 || q.streamed > V || q.ring < 0 || q.ring > 2 ||
+      (q.streamed > 0) != (q.ring > 0))
+    throw std::invalid_argument("mvn: memory query: bad residency plan");
+  const size_t mb = L.real_floats() * sizeof(float), nb = L.nyq_cplx() * sizeof(cfloat);
+  size_t total = kMemSlack;
+  auto add = [&](size_t bytes, size_t n) {
+    if (bytes) total += n * alloc_rounded(bytes);
+  };
+  add(mb, 1);                                     // psi
+  add(mb, 1), add(nb, 1);                         // work volume
+  if (env_int("MVN_DIM0_DIRECT", 1) != 0) add(mb, 1), add(nb, 1);  // second work volume (reserve_views)
+  add(256, 1);                                    // poison words
+  add(q.embed_floats * sizeof(float), 1);         // embedding scratch of the padded policies
+  add(mb, 2 * (size_t)(V - q.streamed));          // image + weights of the resident views
+  add(mb, 2 * (size_t)q.ring);                    // ring slots of the streamed ones
+  const bool lines = lines_capable_for(L) && env_int("MVN_MID_FUSED", 1) != 0;
+  size_t scr = 0;
+  bool spectra = false;
+  for (const std::array<int, 3>& k : q.kernels) {
+    add(sizeof(float) * (size_t)k[0] * k[1] * k[2], 1);  // the kernel's device copy, until staging has drained
+    if (direct_form_for(L, k.data())) {
+      const Layout T(((k[0] + 1 + 15) / 16) * 16, L.d1, L.d2);
+      const size_t tb = T.real_floats() * sizeof(float);
+      add(tb, 1), add(T.nyq_cplx() * sizeof(cfloat), 1);  // taps
+      if (lines && lines_capable_for(T) && mvn_dim0_taps_template(k[0]) <= 31) {
+        add(tb, 1);  // the fused middle pass's taps
+        scr = std::max(scr, tb);
+      }
+    } else {
+      add(mb, 1), add(nb, 1);  // 3-D spectrum
+      spectra = true;
+    }
+  }
+  add(scr, 1);                                        // the engine's one tap scratch
+  if (spectra && ax0_fixed(L)) add(mb, 1);            // re-tiling scratch of the staging thread
+  // (psi_spec_ and delta_ belong to the simultaneous steps of the view-sharded drivers: never allocated here)
+  return total;
 }
 
 void Engine::set_psi(const float* host) {
@@ -1546,7 +1756,7 @@ void Engine::iterate(int iterations, double lambda, float min_value) {
   // (a captured sweep holds buffer addresses: the two work volumes must be back in their roles after it,
   // i.e. the sweep must contain an even number of direct dim0 legs)
   bool use_graph = graphs_on && !halo_fn_ && iterations >= 3 && !prof_.enabled && plan_->can_fuse_rows() &&
-                   plan_->main_bytes() <= graph_max_bytes;
+                   plan_->main_bytes() <= graph_max_bytes && streamed_order_.empty();
   for (int it = 0; it < iterations; ++it) {
     if (use_graph && it == 1) {  // every view has been staged by now: its PSF forms are known
       int swaps = 0;
@@ -1588,7 +1798,10 @@ void Engine::iterate(int iterations, double lambda, float min_value) {
     for (int v = 0; v < V; ++v) {
       if (pipelined_ && it == 0) wait_staged(v);  // the uploader thread may still be busy with v
       const bool last = (it == iterations - 1) && (v == V - 1);
+      const bool streamed = stream_pos_[(size_t)v] >= 0;
+      if (streamed) ring_acquire(views_[(size_t)v]);
       conv_pair(v, lambda, min_value, MVN_EPI_UPDATE, 0, !last);
+      if (streamed) ring_release(views_[(size_t)v]);
     }
   }
   flush_pending_rows();

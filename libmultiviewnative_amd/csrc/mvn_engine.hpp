@@ -231,11 +231,21 @@ struct ViewSlot {
   int tap_k[2] = {0, 0};
   int tap_kd[2] = {0, 0};
   // the same PSF planes for the fused middle pass (mvn_mid_fused.hpp): [tap_kd][C][d1], Nyquist bins packed, bins
-  // along dim1 in that pass's own order; taps_scr: the scattered PSF the last-axis pass reads (it cannot run in
-  // place into the line layout).  taps_l_ok: valid for the kernel tap_k / tap_kd describe.
+  // along dim1 in that pass's own order.  taps_l_ok: valid for the kernel tap_k / tap_kd describe.
   float* taps_l[2] = {nullptr, nullptr};
-  float* taps_scr[2] = {nullptr, nullptr};
   bool taps_l_ok[2] = {false, false};
+};
+
+// What one ABI call on a new engine allocates on the device (Engine::memory_need): the kernel extents of every
+// view (kernel1 and kernel2), the host-shaped embedding scratch of the padded policies, and the residency plan -
+// how many views keep their image and weights in host memory and how many ring slots (pairs of volumes) they
+// rotate through.
+struct MemoryQuery {
+  shape_t ext = {{0, 0, 0}};
+  std::vector<std::array<int, 3>> kernels;  // 2 per view: kernel1, kernel2
+  size_t embed_floats = 0;
+  int streamed = 0;
+  int ring = 0;
 };
 
 class Engine {
@@ -250,6 +260,28 @@ class Engine {
   int num_views() const { return (int)views_.size(); }
   be::stream_t stream() const { return stream_; }
   Profiler& profiler() { return prof_; }
+
+  // Out-of-core calls: the views listed keep their image and weights stacks in host memory; every view update of
+  // one of them reads the pair from a ring of `ring` device slots, filled by the uploader thread (stage_view in the
+  // first sweep, stream_view after it) under the compute of the other views.  PSF forms, psi and the work volumes
+  // stay resident.  Set once, before the views are allocated; an engine keeps its plan for life.
+  void set_residency(const std::vector<int>& streamed, int ring);
+  int streamed_count() const { return (int)streamed_order_.size(); }
+  int ring_size() const { return (int)ring_.size(); }
+  bool is_streamed(int v) const { return stream_pos_[(size_t)v] >= 0; }
+  // uploader thread, sweeps 1 .. n-1: the next streamed view's stacks into their ring slot (views in sweep order)
+  void stream_view(int v, const float* image, const float* weights);
+  // main thread after an error: wake an uploader that waits for a ring slot
+  void abort_streaming();
+  // Bytes the ABI call described by q allocates on a new engine of extents q.ext, allocating nothing itself: the
+  // same PSF form decisions (direct taps, fused-pass taps, 3-D spectra) the engine will take, plus a small slack for
+  // plan tables and allocator rounding.  The single source of truth of the memory planner (mvn_abi.cpp).
+  static size_t memory_need(const MemoryQuery& q);
+  // direct_form() for an engine of layout L that does not exist yet: same switches, no plans built
+  static bool direct_form_for(const Layout& L, const int* kdims);
+  // calls that streamed views, streamed view updates, bytes streamed (host -> device), since process start
+  static void stream_counters(long long out[3]);
+  static void count_streamed_call();
 
   // host -> device staging (blocking); arrays are dense [d0][d1][d2] floats
   void set_view(int v, const float* image, const float* weights, const float* kernel1,
@@ -403,6 +435,10 @@ class Engine {
                    be::stream_t st);
   bool direct_form(const int* kdims);
   Plan3D* taps_plan(int kd);
+  // scattered PSF planes the last-axis pass of the fused-pass taps reads (it cannot run in place into the line
+  // layout): one buffer per engine, read only by prepare_psf's launches on the stream that prepares
+  float* taps_scr_ = nullptr;
+  size_t taps_scr_bytes_ = 0;
   // dim1 forward -> dim0 leg (direct or fused FFT) -> dim1 inverse on the work volume, with kernel i of s
   // `produce` (optional): the last-axis pass that produces this convolution's input, as a function of a row range
   // (row0, nrows; nrows < 0 = all): launched by middle() - in one piece, or boundary planes first (halo mode)
@@ -478,6 +514,22 @@ class Engine {
   std::mutex stage_mu_;
   std::condition_variable stage_cv_;
   std::vector<float*> stage_scratch_;
+  // out-of-core views (set_residency): per view its position in the sweep's streamed order, or -1 (resident)
+  struct RingSlot {
+    float* image = nullptr;
+    float* weights = nullptr;
+    be::event_t filled = nullptr;  // upload stream: the pair has landed
+    be::event_t freed = nullptr;   // compute stream: the last pass that reads the pair has been enqueued before it
+  };
+  std::vector<int> stream_pos_;
+  std::vector<int> streamed_order_;
+  std::vector<RingSlot> ring_;
+  // uploads enqueued / streamed view updates enqueued in this call (under stage_mu_), upload order == use order
+  long uploads_ = 0, consumed_ = 0;
+  bool stream_abort_ = false;
+  void ring_upload(int v, const float* image, const float* weights);  // uploader thread
+  void ring_acquire(ViewSlot& s);                                     // main thread, before the view update
+  void ring_release(ViewSlot& s);                                     // main thread, after it
   float* psi_ = nullptr;
   float* work_ = nullptr;
   cfloat* work_nyq_ = nullptr;

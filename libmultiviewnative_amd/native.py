@@ -28,7 +28,8 @@ REFERENCE_ABI_SYMBOLS = [
     "getMemDeviceCUDA",
 ]
 ENGINE_ABI_SYMBOLS = [
-    "mvn_last_error", "mvn_backend_name", "mvn_set_pad_mode", "mvn_get_pad_mode", "mvn_release_cached_engines", "mvn_deconvolve_submit", "mvn_deconvolve_wait", "mvn_psf_cache_counters", "mvn_split_launch_count", "mvn_mid_fused_launch_count", "mvn_multi_device_calls", "mvn_group_create", "mvn_group_destroy", "mvn_group_load", "mvn_group_iterate", "mvn_group_get_psi", "mvn_plan_store_add", "mvn_plan_store_has_key",
+    "mvn_last_error", "mvn_backend_name", "mvn_set_pad_mode", "mvn_get_pad_mode", "mvn_set_memory_mode", "mvn_get_memory_mode", "mvn_set_memory_budget", "mvn_deconvolve_memory",
+    "mvn_stream_counters", "mvn_release_cached_engines", "mvn_deconvolve_submit", "mvn_deconvolve_wait", "mvn_psf_cache_counters", "mvn_split_launch_count", "mvn_mid_fused_launch_count", "mvn_multi_device_calls", "mvn_group_create", "mvn_group_destroy", "mvn_group_load", "mvn_group_iterate", "mvn_group_get_psi", "mvn_plan_store_add", "mvn_plan_store_has_key",
     "mvn_plan_store_size", "mvn_plan_store_empty", "mvn_plan_store_clear", "mvn_plan_describe",
     "mvn_fft3_r2c", "mvn_fft3_c2r", "mvn_fft3_time", "mvn_fft3_profile", "mvn_fft3_many_r2c", "mvn_fft3_many_time", "mvn_engine_create", "mvn_engine_destroy",
     "mvn_engine_set_view", "mvn_engine_set_psi", "mvn_engine_get_psi", "mvn_engine_iterate",
@@ -81,6 +82,12 @@ class Binding:
         l.mvn_set_pad_mode.argtypes = [C.c_char_p]
         l.mvn_get_pad_mode.restype = C.c_char_p
         l.mvn_get_pad_mode.argtypes = []
+        l.mvn_set_memory_mode.argtypes = [C.c_char_p]
+        l.mvn_get_memory_mode.restype = C.c_char_p
+        l.mvn_get_memory_mode.argtypes = []
+        l.mvn_set_memory_budget.argtypes = [C.c_longlong]
+        l.mvn_deconvolve_memory.argtypes = [Workspace, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
+        l.mvn_stream_counters.argtypes = [C.POINTER(C.c_longlong)]
         l.inplace_gpu_deconvolve.argtypes = [c_float_p, Workspace, C.c_int]
         l.inplace_gpu_deconvolve.restype = None
         l.mvn_deconvolve_submit.argtypes = [c_float_p, Workspace, C.c_int, C.POINTER(C.c_longlong)]
@@ -181,6 +188,31 @@ class Binding:
     def get_pad_mode(self):
         """The mode selected with set_pad_mode, None when the environment / default decides."""
         return self.l.mvn_get_pad_mode().decode() or None
+
+    def set_memory_mode(self, mode):
+        """'resident' | 'auto' | 'stream' | 'stream:N' | None (back to the default, resident)."""
+        self.check(self.l.mvn_set_memory_mode(mode.encode() if mode else None))
+
+    def get_memory_mode(self):
+        """The mode selected with set_memory_mode, None when the default (resident) applies."""
+        return self.l.mvn_get_memory_mode().decode() or None
+
+    def set_memory_budget(self, nbytes):
+        """Cap of the auto / stream planner in bytes; None or <= 0 removes it."""
+        self.check(self.l.mvn_set_memory_budget(int(nbytes) if nbytes else 0))
+
+    def deconvolve_memory(self, holder, streamed_views=0, device=0):
+        """Device bytes inplace_gpu_deconvolve allocates for this workspace with `streamed_views` views
+        streamed (ring of 2 slots), under the padding policy in force."""
+        out = C.c_size_t(0)
+        self.check(self.l.mvn_deconvolve_memory(holder.ws, device, streamed_views, C.byref(out)))
+        return out.value
+
+    def stream_counters(self):
+        """(calls that streamed views, streamed view updates, bytes streamed) since process start."""
+        out = (C.c_longlong * 3)()
+        self.check(self.l.mvn_stream_counters(out))
+        return tuple(int(x) for x in out)
 
     # ---- reference ABI, numpy in / numpy out ----------------------------------------------
     def gpu_deconvolve(self, psi, holder, device=0, pad_mode="none"):
