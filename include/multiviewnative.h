@@ -81,7 +81,9 @@ typedef struct workspace workspace;
  * call cuts the padded volume into slabs of dim0 planes, one per listed device, and sweeps them in the same
  * view-after-view order with a halo exchange per convolution - same result as on one device, `device` is then
  * ignored.  A call that cannot be cut that way (a PSF deeper than 33 planes, fewer planes per slab than half the
- * deepest PSF, an odd last extent) runs on one device as usual.  See INTEGRATION.md section 4. */
+ * deepest PSF, an odd last extent) runs on one device as usual, and so does a call with convergence statistics
+ * on (mvn_set_convergence >= 0, mvn_engine_api.h): the slab drivers keep none, and mvn_multi_device_calls does not
+ * count such a call.  See INTEGRATION.md section 4. */
 MVN_API void inplace_gpu_deconvolve(imageType* psi, struct workspace input, int device);
 
 /* inc/multiviewnative.h:59-61 (impl. src/multiviewnative.cu:58-75): in-place cyclic

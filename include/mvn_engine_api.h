@@ -73,6 +73,22 @@ MVN_API int mvn_deconvolve_memory(struct workspace input, int device, int stream
 /* out[0] = calls that streamed views, out[1] = streamed view updates, out[2] = bytes streamed host -> device,
  * all since process start */
 MVN_API int mvn_stream_counters(long long out[3]);
+/* Convergence of the Richardson-Lucy loop.  For sweep k (one update of every view), over the voxels returned to
+ * the caller (the stacks' window inside the padded volume; the whole volume under padding "none" and through the
+ * engine API), differenced in float and summed in double:
+ *   S_k = sum over the V view updates and voxels of |psi_after - psi_before|,  M_k = max of the same,
+ *   P_k = sum of psi_after;  r_k = S_k / P_k, the mean relative L1 change per view update.
+ * tolerance < 0: off (default; no statistics, kernels and results as without this switch); 0: statistics of
+ * every sweep, all num_iterations_ run; > 0: also stop after the first sweep k with r_k <= tolerance (psi is then
+ * the estimate after k sweeps).  A NaN makes r_k NaN, which never stops the loop.  Process-wide, captured by
+ * inplace_gpu_deconvolve and mvn_deconvolve_submit at their start.  Multi-device calls (MVN_DEVICES) with
+ * statistics on run on one device. */
+MVN_API int mvn_set_convergence(double tolerance);   /* < 0 off (default), 0 statistics only, > 0 stop at r_k <= t */
+MVN_API int mvn_get_convergence(double* tolerance);
+/* Statistics of the last deconvolution this THREAD completed: inplace_gpu_deconvolve, or mvn_deconvolve_wait of
+ * its ticket.  *iterations_run = sweeps actually run; stats[3k..3k+2] = {S_k, M_k, P_k} for
+ * k < min(capacity, rows); returns the number of rows available (0 when statistics were off), < 0 on error. */
+MVN_API int mvn_last_convergence(int* iterations_run, double* stats, int capacity);
 /* A resident engine keeps, per view slot, the PSF spectra of the last call together with host
  * copies of the kernels they were made from; a call (or mvn_engine_set_view) that brings
  * bytewise identical kernels for a slot re-uses the spectra (the reference's
@@ -133,6 +149,10 @@ MVN_API int mvn_engine_set_psi(mvn_engine* e, const float* psi);
 MVN_API int mvn_engine_get_psi(mvn_engine* e, float* psi);
 /* enqueue `iterations` sequential (Gauss-Seidel) sweeps over the views */
 MVN_API int mvn_engine_iterate(mvn_engine* e, int iterations, double lambda, float min_value);
+/* resident engine, blocking: stats receives 3 doubles per iteration run ({S_k, M_k, P_k} over the whole volume,
+ * see mvn_set_convergence; tolerance as there, < 0 collects nothing) */
+MVN_API int mvn_engine_iterate_converge(mvn_engine* e, int iterations, double lambda, float min_value,
+                                        double tolerance, int* iterations_run, double* stats);
 /* simultaneous (Jacobi) mode, one step: delta = sum_v w_v (next_v - psi) over this engine's
  * views; the caller all-reduces the delta buffer across ranks, then applies it */
 MVN_API int mvn_engine_compute_delta(mvn_engine* e, double lambda, float min_value);

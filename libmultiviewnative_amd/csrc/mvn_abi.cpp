@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -141,10 +142,23 @@ static size_t current_memory_budget() {
   return b > 0 ? (size_t)b : 0;
 }
 
+// ---- convergence statistics (mvn_set_convergence) ------------------------------------------------
+static std::atomic<double> g_conv_tol{-1.};
+// the tolerance of the call this thread runs (captured at submit); NaN outside a call: then the process-wide one
+static thread_local double t_call_tol = NAN;
+static double call_tolerance() { return std::isnan(t_call_tol) ? g_conv_tol.load() : t_call_tol; }
+struct ConvRecord {
+  int iterations_run = 0;
+  std::vector<double> rows;  // {S, M, P} per sweep run
+};
+// the last deconvolution this thread completed (inplace_gpu_deconvolve, or the wait of a ticket)
+static thread_local ConvRecord t_last_conv;
+
 static MemoryQuery memory_query(const shape_t& ext, const workspace& input, size_t embed_floats) {
   MemoryQuery q;
   q.ext = ext;
   q.embed_floats = embed_floats;
+  q.stats_rows = call_tolerance() >= 0. ? std::max(input.num_iterations_, 1) : 0;
   for (int v = 0; v < input.num_views_; ++v) {
     const view_data& d = input.data_[v];
     q.kernels.push_back({{d.kernel1_dims_[0], d.kernel1_dims_[1], d.kernel1_dims_[2]}});
@@ -538,7 +552,14 @@ static bool all_direct_for(const shape_t& ext, const workspace& input) {
   return true;
 }
 
-static void deconvolve_call(imageType* psi, const workspace& input, int device, int lane, int pad_mode) {
+static void deconvolve_call(imageType* psi, const workspace& input, int device, int lane, int pad_mode, double tol,
+                            ConvRecord* conv) {
+  conv->iterations_run = 0;
+  conv->rows.clear();
+  struct TolScope {  // (the memory model of this call counts the statistics buffers: memory_query)
+    explicit TolScope(double t) { t_call_tol = t; }
+    ~TolScope() { t_call_tol = NAN; }
+  } tol_scope(tol);
   {
     check_workspace(psi, input);
     const int V = input.num_views_;
@@ -549,7 +570,10 @@ static void deconvolve_call(imageType* psi, const workspace& input, int device, 
     call_extents(input, pad_mode, &dims, &ext, off, &dim0_kept_exact);
     if (lane == 0) {  // (the second lane belongs to the block pipeline of mvn_deconvolve_submit)
       const std::vector<int> devs = multi_devices_from_env();
-      if (!devs.empty() && multi_device_call(psi, input, dims, ext, off, pad_mode, devs)) return;
+      // the slab drivers keep no convergence statistics: such a call runs on one device
+      if (!devs.empty() && tol >= 0. && trace_on())
+        std::printf("[lmvn::trace] MVN_DEVICES: convergence statistics on - one device\n");
+      if (!devs.empty() && tol < 0. && multi_device_call(psi, input, dims, ext, off, pad_mode, devs)) return;
     }
     const int mem_mode = current_memory_mode();
     if (mem_mode != MVN_MEM_RESIDENT && dim0_kept_exact && !all_direct_for(ext, input)) {
@@ -598,7 +622,7 @@ static void deconvolve_call(imageType* psi, const workspace& input, int device, 
         eng.set_view(v, d.image_, d.weights_, d.kernel1_, d.kernel1_dims_, d.kernel2_, d.kernel2_dims_);
       }
       eng.set_psi(psi);
-      eng.iterate(input.num_iterations_, input.lambda_, input.minValue_);
+      conv->iterations_run = eng.iterate(input.num_iterations_, input.lambda_, input.minValue_, tol, &conv->rows);
       eng.sync();
       eng.get_psi(psi);
       give_back_engine(key, std::move(eng_owner));
@@ -656,7 +680,8 @@ static void deconvolve_call(imageType* psi, const workspace& input, int device, 
     });
     std::exception_ptr main_err;
     try {
-      eng.iterate(input.num_iterations_, input.lambda_, input.minValue_);
+      conv->iterations_run = eng.iterate(input.num_iterations_, input.lambda_, input.minValue_, tol, &conv->rows);
+      if (conv->iterations_run < input.num_iterations_) eng.end_streaming();  // (an early stop)
     } catch (...) {
       main_err = std::current_exception();
       eng.abort_streaming();  // (an uploader waiting for a ring slot that will not be freed)
@@ -677,7 +702,10 @@ static void deconvolve_call(imageType* psi, const workspace& input, int device, 
 }
 
 void inplace_gpu_deconvolve(imageType* psi, struct workspace input, int device) {
-  guarded("inplace_gpu_deconvolve", [&] { deconvolve_call(psi, input, device, 0, current_pad_mode()); });
+  guarded("inplace_gpu_deconvolve", [&] {
+    const double tol = g_conv_tol.load();
+    deconvolve_call(psi, input, device, 0, current_pad_mode(), tol, &t_last_conv);
+  });
 }
 
 // ---- asynchronous pair: mvn_deconvolve_submit / mvn_deconvolve_wait ---------------------------
@@ -690,6 +718,8 @@ struct DeconvJob {
   std::vector<view_data> views;  // the caller's view_data array and dims, copied at submit
   std::vector<int> dims;
   workspace ws;
+  double tol = -1.;  // the convergence tolerance at submit
+  ConvRecord conv;   // moves into the waiting thread's record
 };
 std::mutex& jobs_mutex() {
   static std::mutex* m = new std::mutex();
@@ -725,6 +755,7 @@ int mvn_deconvolve_submit(imageType* psi, struct workspace input, int device, lo
     job->ws.data_ = job->views.data();
     const int dev = pick_device(device);
     const int pad_mode = current_pad_mode();  // the policy in force at submit time
+    job->tol = g_conv_tol.load();             // ... and the tolerance
     static std::atomic<long long> next_ticket{1};
     const long long id = next_ticket.fetch_add(1);
     static std::mutex lane_mu;
@@ -737,7 +768,8 @@ int mvn_deconvolve_submit(imageType* psi, struct workspace input, int device, lo
     DeconvJob* j = job.get();
     // (the worker first, the map entry second: a thread that cannot be started leaves no job behind)
     j->worker = std::thread([j, psi, dev, lane, pad_mode] {
-      j->rc = guarded("mvn_deconvolve_submit (worker)", [&] { deconvolve_call(psi, j->ws, dev, lane, pad_mode); });
+      j->rc = guarded("mvn_deconvolve_submit (worker)",
+                      [&] { deconvolve_call(psi, j->ws, dev, lane, pad_mode, j->tol, &j->conv); });
       if (j->rc < 0) j->error = g_last_error;  // the worker's thread-local message travels with the job
     });
     try {
@@ -764,8 +796,36 @@ int mvn_deconvolve_wait(long long ticket) {
     if (job->worker.joinable()) job->worker.join();
   });
   if (rc < 0) return rc;
+  t_last_conv = std::move(job->conv);
   if (job->rc < 0) g_last_error = job->error;
   return job->rc;
+}
+
+int mvn_set_convergence(double tolerance) {
+  return guarded("mvn_set_convergence", [&] {
+    if (std::isnan(tolerance)) throw std::invalid_argument("tolerance is NaN");
+    g_conv_tol.store(tolerance < 0. ? -1. : tolerance);
+  });
+}
+
+int mvn_get_convergence(double* tolerance) {
+  return guarded("mvn_get_convergence", [&] {
+    if (!tolerance) throw std::invalid_argument("null tolerance");
+    *tolerance = g_conv_tol.load();
+  });
+}
+
+int mvn_last_convergence(int* iterations_run, double* stats, int capacity) {
+  int rows = 0;
+  const int rc = guarded("mvn_last_convergence", [&] {
+    if (capacity < 0 || (capacity > 0 && !stats)) throw std::invalid_argument("bad statistics buffer");
+    const ConvRecord& c = t_last_conv;
+    if (iterations_run) *iterations_run = c.iterations_run;
+    rows = (int)(c.rows.size() / 3);
+    const size_t n = 3 * (size_t)std::min(rows, capacity);
+    if (n) std::memcpy(stats, c.rows.data(), n * sizeof(double));
+  });
+  return rc < 0 ? rc : rows;
 }
 
 int mvn_set_pad_mode(const char* mode) {
@@ -1533,6 +1593,18 @@ int mvn_engine_get_psi(mvn_engine* e, float* psi) {
 
 int mvn_engine_iterate(mvn_engine* e, int iterations, double lambda, float min_value) {
   MVN_ENGINE_CALL("mvn_engine_iterate", E.iterate(iterations, lambda, min_value));
+}
+
+int mvn_engine_iterate_converge(mvn_engine* e, int iterations, double lambda, float min_value, double tolerance,
+                                int* iterations_run, double* stats) {
+  MVN_ENGINE_CALL("mvn_engine_iterate_converge", {
+    if (std::isnan(tolerance)) throw std::invalid_argument("tolerance is NaN");
+    if (tolerance >= 0. && !stats) throw std::invalid_argument("null statistics buffer");
+    std::vector<double> rows;
+    const int ran = E.iterate(iterations, lambda, min_value, tolerance, &rows);
+    if (iterations_run) *iterations_run = ran;
+    if (!rows.empty()) std::memcpy(stats, rows.data(), rows.size() * sizeof(double));
+  });
 }
 
 int mvn_engine_compute_delta(mvn_engine* e, double lambda, float min_value) {

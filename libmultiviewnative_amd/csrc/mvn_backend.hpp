@@ -88,6 +88,9 @@ void launch_rows_c2r(const RowsParams& p, bool even, long ntiles, int nthreads, 
 void launch_rows_c2r_r2c(const RowsParams& p, long ntiles, int nthreads, size_t lds_bytes,
                          stream_t s);
 // launches that went through the long-line (split-window, 16-column) kernels since process start
+// statistics of one sweep: records of `nviews` view updates (view v at rec + 3 v cap) -> out[0..2] = {S, M, P}
+void launch_convergence_reduce(const double* rec, const unsigned* counts, int nviews, long cap, double* out,
+                               stream_t s);
 long split_launch_count();
 // launches of the fused middle pass (mvn_mid_fused.hpp) since process start
 long mid_fused_launch_count();

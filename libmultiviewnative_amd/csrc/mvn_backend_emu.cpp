@@ -184,6 +184,7 @@ static void emu_wave_rows_mode(const RowsParams& p) {
   switch (p.epi.mode) {
     case MVN_EPI_DIVIDE: emu_wave_rows_run<MODE, MVN_EPI_DIVIDE>(p); break;
     case MVN_EPI_UPDATE: emu_wave_rows_run<MODE, MVN_EPI_UPDATE>(p); break;
+    case MVN_EPI_UPDATE_STATS: emu_wave_rows_run<MODE, MVN_EPI_UPDATE_STATS>(p); break;
     case MVN_EPI_DELTA:
       if (MODE == MVN_WR_C2R) {
         emu_wave_rows_run<MVN_WR_C2R, MVN_EPI_DELTA>(p);
@@ -206,6 +207,7 @@ static long emu_rows_grid(long ntiles) {
 static void emu_rows_lines(const RowsParams& p, long ntiles, int kind) {
   constexpr int H = 256;
   typedef FxCtx<FxRowsRegs<H>, FxRowsCfg<H>::NT> Ctx;
+  typedef FxCtx<FxRowsStatRegs<H>, FxRowsCfg<H>::NT> SCtx;  // (MVN_EPI_UPDATE_STATS)
   if (!fx_rows_lines_ok<H>() || !p.fixed || p.h != H || p.C != H || !p.nyq_packed || p.lines_d1 < 1 ||
       p.lines_d1 % FxRowsCfg<H>::T || p.row_base % FxRowsCfg<H>::T || p.rows != ntiles * FxRowsCfg<H>::T)
     throw std::invalid_argument("mvn: line-layout last-axis pass outside its range");
@@ -213,6 +215,7 @@ static void emu_rows_lines(const RowsParams& p, long ntiles, int kind) {
   {
     std::vector<char> lds(sizeof(cfloat) * FxRowsCfg<H>::lds_cfloats + 64);
     std::unique_ptr<Ctx> ctx(new Ctx());
+    std::unique_ptr<SCtx> sctx(new SCtx());
 #pragma omp for schedule(static)
     for (long t = 0; t < ntiles; ++t) {
       cfloat* l = (cfloat*)lds.data();
@@ -222,6 +225,7 @@ static void emu_rows_lines(const RowsParams& p, long ntiles, int kind) {
         switch (p.epi.mode) {
           case MVN_EPI_DIVIDE: fx_rows_run<H, 1, MVN_EPI_DIVIDE, Ctx, true>(p, t, ntiles, l, *ctx); break;
           case MVN_EPI_UPDATE: fx_rows_run<H, 1, MVN_EPI_UPDATE, Ctx, true>(p, t, ntiles, l, *ctx); break;
+          case MVN_EPI_UPDATE_STATS: fx_rows_run_stats<H, 1, SCtx, true>(p, t, ntiles, l, *sctx); break;
           case MVN_EPI_DELTA: fx_rows_run<H, 1, MVN_EPI_DELTA, Ctx, true>(p, t, ntiles, l, *ctx); break;
           default: fx_rows_run<H, 1, MVN_EPI_STORE, Ctx, true>(p, t, ntiles, l, *ctx); break;
         }
@@ -229,6 +233,7 @@ static void emu_rows_lines(const RowsParams& p, long ntiles, int kind) {
         switch (p.epi.mode) {
           case MVN_EPI_DIVIDE: fx_rows_run<H, 2, MVN_EPI_DIVIDE, Ctx, true>(p, t, ntiles, l, *ctx); break;
           case MVN_EPI_UPDATE: fx_rows_run<H, 2, MVN_EPI_UPDATE, Ctx, true>(p, t, ntiles, l, *ctx); break;
+          case MVN_EPI_UPDATE_STATS: fx_rows_run_stats<H, 2, SCtx, true>(p, t, ntiles, l, *sctx); break;
           default: fx_rows_run<H, 2, MVN_EPI_STORE, Ctx, true>(p, t, ntiles, l, *ctx); break;
         }
       }
@@ -279,17 +284,20 @@ void launch_mid_fused(const MidFusedParams& p, stream_t) {
 template <int H>
 static void emu_rows_fused(const RowsParams& p, long ntiles) {
   typedef FxCtx<FxRowsRegs<H>, FxRowsCfg<H>::NT> Ctx;
+  typedef FxCtx<FxRowsStatRegs<H>, FxRowsCfg<H>::NT> SCtx;  // (MVN_EPI_UPDATE_STATS)
   const long grid = emu_rows_grid<H>(ntiles);
 #pragma omp parallel
   {
     std::vector<char> lds(sizeof(cfloat) * FxRowsCfg<H>::lds_cfloats + 64);
     std::unique_ptr<Ctx> ctx(new Ctx());
+    std::unique_ptr<SCtx> sctx(new SCtx());
 #pragma omp for schedule(static)
     for (long t = 0; t < grid; ++t) {
       cfloat* l = (cfloat*)lds.data();
       switch (p.epi.mode) {
         case MVN_EPI_DIVIDE: fx_rows_run<H, 2, MVN_EPI_DIVIDE>(p, t, grid, l, *ctx); break;
         case MVN_EPI_UPDATE: fx_rows_run<H, 2, MVN_EPI_UPDATE>(p, t, grid, l, *ctx); break;
+        case MVN_EPI_UPDATE_STATS: fx_rows_run_stats<H, 2, SCtx>(p, t, grid, l, *sctx); break;
         default: fx_rows_run<H, 2, MVN_EPI_STORE>(p, t, grid, l, *ctx); break;
       }
     }
@@ -308,7 +316,11 @@ void launch_rows_c2r_r2c(const RowsParams& p0, long ntiles, int, size_t lds_byte
 #pragma omp for schedule(static)
       for (long t = 0; t < ntiles; ++t) {
         cfloat* l = (cfloat*)lds.data();
-        MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, true>(p, t, 0, 1, l)));
+        if (p.epi.mode == MVN_EPI_UPDATE_STATS) {
+          MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, true, true>(p, t, 0, 1, l)));
+        } else {
+          MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, true>(p, t, 0, 1, l)));
+        }
       }
     }
     return;
@@ -324,11 +336,13 @@ void launch_rows_c2r_r2c(const RowsParams& p0, long ntiles, int, size_t lds_byte
 template <int H>
 static void emu_rows_fixed(const RowsParams& p, long ntiles, bool r2c) {
   typedef FxCtx<FxRowsRegs<H>, FxRowsCfg<H>::NT> Ctx;
+  typedef FxCtx<FxRowsStatRegs<H>, FxRowsCfg<H>::NT> SCtx;  // (MVN_EPI_UPDATE_STATS)
   const long grid = emu_rows_grid<H>(ntiles);
 #pragma omp parallel
   {
     std::vector<char> lds(sizeof(cfloat) * FxRowsCfg<H>::lds_cfloats + 64);
     std::unique_ptr<Ctx> ctx(new Ctx());
+    std::unique_ptr<SCtx> sctx(new SCtx());
 #pragma omp for schedule(static)
     for (long t = 0; t < grid; ++t) {
       cfloat* l = (cfloat*)lds.data();
@@ -338,6 +352,7 @@ static void emu_rows_fixed(const RowsParams& p, long ntiles, bool r2c) {
         switch (p.epi.mode) {
           case MVN_EPI_DIVIDE: fx_rows_run<H, 1, MVN_EPI_DIVIDE>(p, t, grid, l, *ctx); break;
           case MVN_EPI_UPDATE: fx_rows_run<H, 1, MVN_EPI_UPDATE>(p, t, grid, l, *ctx); break;
+          case MVN_EPI_UPDATE_STATS: fx_rows_run_stats<H, 1, SCtx>(p, t, grid, l, *sctx); break;
           case MVN_EPI_DELTA: fx_rows_run<H, 1, MVN_EPI_DELTA>(p, t, grid, l, *ctx); break;
           default: fx_rows_run<H, 1, MVN_EPI_STORE>(p, t, grid, l, *ctx); break;
         }
@@ -466,13 +481,25 @@ void launch_rows_c2r(const RowsParams& p0, bool even, long ntiles, int, size_t l
 #pragma omp for schedule(static)
     for (long t = 0; t < ntiles; ++t) {
       cfloat* l = (cfloat*)lds.data();
-      if (even) {
+      if (p.epi.mode == MVN_EPI_UPDATE_STATS) {
+        if (even) {
+          MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, false, true>(p, t, 0, 1, l)));
+        } else {
+          MVN_DISPATCH_T(p.T, (rows_c2r_odd_body<TT, true>(p, t, 0, 1, l)));
+        }
+      } else if (even) {
         MVN_DISPATCH_T(p.T, rows_c2r_even_body<TT>(p, t, 0, 1, l));
       } else {
         MVN_DISPATCH_T(p.T, rows_c2r_odd_body<TT>(p, t, 0, 1, l));
       }
     }
   }
+}
+
+void launch_convergence_reduce(const double* rec, const unsigned* counts, int nviews, long cap, double* out,
+                               stream_t) {
+  double lds[3];
+  mvn_convergence_reduce_body(rec, counts, nviews, cap, out, lds, 0, 1);
 }
 
 void launch_strided(int mode, const StridedParams& p, long nblocks, int, size_t lds_bytes,

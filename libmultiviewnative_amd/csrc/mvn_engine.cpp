@@ -313,7 +313,7 @@ void Plan3D::rows_r2c(const float* in_real, cfloat* out, cfloat* out_nyq, be::st
 
 void Plan3D::rows_c2r(const cfloat* in, const cfloat* in_nyq, float* out_real,
                       const EpilogueParams& epi_all, be::stream_t s, Profiler* prof, long row0,
-                      long nrows, bool lines) const {
+                      long nrows, bool lines, const MvnStatsParams* st) const {
   const long R = rows_in_range(*this, row0, nrows);
   const void* cplx0 = in;
   const void* real0 = out_real;
@@ -351,6 +351,10 @@ void Plan3D::rows_c2r(const cfloat* in, const cfloat* in_nyq, float* out_real,
     p.epi.poison = no_poison;
     p.epi.poison_epoch = 0xffffffffu;
   }
+  if (st) {
+    p.st = *st;
+    p.st.row0 = row0;
+  }
   ProfScope ps(prof, KK_ROWS_C2R, s);
   if (fx_rows) {
     p.fixed = 1;
@@ -363,7 +367,7 @@ void Plan3D::rows_c2r(const cfloat* in, const cfloat* in_nyq, float* out_real,
 }
 
 void Plan3D::rows_c2r_r2c(cfloat* data, cfloat* nyq, const EpilogueParams& epi_all, be::stream_t s,
-                          Profiler* prof, long row0, long nrows, bool lines) const {
+                          Profiler* prof, long row0, long nrows, bool lines, const MvnStatsParams* st) const {
   if (!L.even) throw std::logic_error("mvn: rows_c2r_r2c needs an even last extent");
   const long R = rows_in_range(*this, row0, nrows);
   if (!lines) data += row0 * L.C;
@@ -394,7 +398,11 @@ void Plan3D::rows_c2r_r2c(cfloat* data, cfloat* nyq, const EpilogueParams& epi_a
     p.epi.poison = no_poison;
     p.epi.poison_epoch = 0xffffffffu;
   }
-  ProfScope ps(prof, epi.mode == MVN_EPI_UPDATE ? KK_ROWS_FUSED_UPD : KK_ROWS_FUSED, s);
+  if (st) {
+    p.st = *st;
+    p.st.row0 = row0;
+  }
+  ProfScope ps(prof, mvn_epi_reads_psi(epi.mode) ? KK_ROWS_FUSED_UPD : KK_ROWS_FUSED, s);
   if (fx_rows) {
     p.fixed = 1;
     p.T = gx_rows.T;
@@ -734,6 +742,7 @@ Engine::~Engine() {
     if (stream_) be::stream_sync(stream_);
   } catch (...) {
   }
+  stats_free();
   for (size_t v = 0; v < views_.size(); ++v) {
     if (stream_pos_[v] < 0) {  // (a streamed view's pointers are borrowed from the ring during its update)
       be::dfree(views_[v].image);
@@ -1350,6 +1359,7 @@ void Engine::reserve_views() {
     std::lock_guard<std::mutex> lk(stage_mu_);
     uploads_ = consumed_ = 0;
     stream_abort_ = false;
+    stream_done_ = false;
   }
   pipelined_ = true;
 }
@@ -1469,8 +1479,9 @@ void Engine::ring_upload(int v, const float* image, const float* weights) {
   {
     std::unique_lock<std::mutex> lk(stage_mu_);
     k = uploads_;
-    stage_cv_.wait(lk, [&] { return stream_abort_ || consumed_ >= k - R + 1; });
+    stage_cv_.wait(lk, [&] { return stream_abort_ || stream_done_ || consumed_ >= k - R + 1; });
     if (stream_abort_) throw std::runtime_error("mvn: streamed call abandoned");
+    if (stream_done_) return;  // (the loop stopped early: no later sweep reads this upload)
   }
   RingSlot& r = ring_[(size_t)(k % R)];
   if (k >= R) be::stream_wait_event(upload_stream_, r.freed);
@@ -1554,6 +1565,9 @@ bool Engine::direct_form_for(const Layout& L, const int* kdims) {
   return rows_fixed(T) == rows_fixed(L) && ax1_fixed(T) == ax1_fixed(L);
 }
 
+// Every workgroup of an update pass writes one record, and no launch has more workgroups than the volume has rows.
+static long stats_cap(const Layout& L) { return (long)L.rows; }
+
 size_t Engine::memory_need(const MemoryQuery& q) {
   const Layout L(q.ext[0], q.ext[1], q.ext[2]);
   const int V = (int)(q.kernels.size() / 2);
@@ -1592,6 +1606,11 @@ size_t Engine::memory_need(const MemoryQuery& q) {
   }
   add(scr, 1);                                        // the engine's one tap scratch
   if (spectra && ax0_fixed(L)) add(mb, 1);            // re-tiling scratch of the staging thread
+  if (q.stats_rows > 0) {  // convergence statistics (Engine::iterate)
+    add(3 * sizeof(double) * (size_t)stats_cap(L) * (size_t)V, 1);
+    add(sizeof(unsigned) * (size_t)V, 1);
+    add(3 * sizeof(double) * (size_t)q.stats_rows, 1);
+  }
   // (psi_spec_ and delta_ belong to the simultaneous steps of the view-sharded drivers: never allocated here)
   return total;
 }
@@ -1647,7 +1666,9 @@ void Engine::conv_pair(int v, double lambda, float min_value, int final_mode, in
 
   EpilogueParams e2;
   std::memset(&e2, 0, sizeof(e2));
-  e2.mode = final_mode;
+  const bool stats = stats_on_ && final_mode == MVN_EPI_UPDATE;
+  const MvnStatsParams st2 = stats ? stats_for(v) : MvnStatsParams();
+  e2.mode = stats ? MVN_EPI_UPDATE_STATS : final_mode;
   e2.scale = 1.f;
   e2.psi = psi_;
   e2.weights = s.weights;
@@ -1706,18 +1727,21 @@ void Engine::conv_pair(int v, double lambda, float min_value, int final_mode, in
   // (halo mode: the rows of the own planes only)
   const long r0 = halo_ranged() ? (long)halo_planes_ * P.L.d1 : 0;
   const long nr = halo_ranged() ? (long)(P.L.d0 - 2 * halo_planes_) * P.L.d1 : -1;
-  if (fuse && feed_next && final_mode == MVN_EPI_UPDATE) {
+  if (fuse && feed_next && final_mode == MVN_EPI_UPDATE) {  // (with or without the statistics)
     float* w = work_;
     cfloat* wnq = wn();
     const bool ln = lines_;
-    RowsProducer upd = [=](long a, long n) { Pp->rows_c2r_r2c((cfloat*)w, ln ? nullptr : wnq, e2, st, prof, a, n, ln); };
+    RowsProducer upd = [=](long a, long n) {
+      Pp->rows_c2r_r2c((cfloat*)w, ln ? nullptr : wnq, e2, st, prof, a, n, ln, stats ? &st2 : nullptr);
+    };
     if (boundary_first())
       pending_rows_ = std::move(upd);  // runs as the producer of the NEXT convolution, boundary planes first
     else
       upd(r0, nr);
     work_has_psi_spectrum_ = true;
   } else {
-    P.rows_c2r((const cfloat*)work_, lines_ ? nullptr : wn(), psi_, e2, stream_, prof, r0, nr, lines_);
+    P.rows_c2r((const cfloat*)work_, lines_ ? nullptr : wn(), psi_, e2, stream_, prof, r0, nr, lines_,
+               stats ? &st2 : nullptr);
   }
 }
 
@@ -1743,8 +1767,72 @@ bool Engine::boundary_first() const {
 // 256^3 0.308 -> 0.305 ms per view update, against ~11 ms for capture and instantiation, which only
 // a long-lived engine (thousands of small view updates) earns back.  Hence opt-in: MVN_GRAPH=1
 // enables it, MVN_GRAPH_MAX_MB (default 160) bounds the volume.
-void Engine::iterate(int iterations, double lambda, float min_value) {
+// the window of the statistics: the stacks inside the padded volume, or all of it
+MvnStatsParams Engine::stats_for(int v) const {
+  const Layout& L = plan_->L;
+  MvnStatsParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.d1 = L.d1;
+  p.o0 = embedded_ ? host_off_[0] : 0;
+  p.o1 = embedded_ ? host_off_[1] : 0;
+  p.o2 = embedded_ ? host_off_[2] : 0;
+  p.n0 = (unsigned)(embedded_ ? host_dims_[0] : L.d0);
+  p.n1 = (unsigned)(embedded_ ? host_dims_[1] : L.d1);
+  p.n2 = (unsigned)(embedded_ ? host_dims_[2] : L.d2);
+  p.rec = stat_rec_ + 3 * (size_t)stat_cap_ * (size_t)v;
+  p.count = stat_count_ + v;
+  p.cap = stat_cap_;
+  return p;
+}
+
+void Engine::stats_free() {
+  be::dfree(stat_rec_);
+  be::dfree(stat_count_);
+  be::dfree(stat_out_);
+  stat_rec_ = stat_out_ = nullptr;
+  stat_count_ = nullptr;
+  stats_on_ = false;
+}
+
+void Engine::end_streaming() {
+  {
+    std::lock_guard<std::mutex> lk(stage_mu_);
+    stream_done_ = true;
+  }
+  stage_cv_.notify_all();
+}
+
+int Engine::iterate(int iterations, double lambda, float min_value, double tolerance, std::vector<double>* stats) {
   be::set_device(device_);
+  const bool st_on = tolerance >= 0.;
+  if (st_on) {
+    if (halo_fn_) throw std::logic_error("mvn: no convergence statistics on a slab of a multi-device group");
+    const int V = (int)views_.size();
+    stats_free();
+    stat_cap_ = stats_cap(plan_->L);
+    stat_rec_ = (double*)be::dmalloc(3 * sizeof(double) * (size_t)stat_cap_ * (size_t)V);
+    stat_count_ = (unsigned*)be::dmalloc(sizeof(unsigned) * (size_t)V);
+    stat_out_ = (double*)be::dmalloc(3 * sizeof(double) * (size_t)std::max(iterations, 1));
+    stats_on_ = true;
+  }
+  try {
+    const int ran = iterate_sweeps(iterations, lambda, min_value, tolerance, stats);
+    if (st_on) stats_free();
+    return ran;
+  } catch (...) {
+    if (st_on) {
+      try {
+        be::stream_sync(stream_);
+      } catch (...) {
+      }
+      stats_free();
+    }
+    throw;
+  }
+}
+
+int Engine::iterate_sweeps(int iterations, double lambda, float min_value, double tolerance,
+                           std::vector<double>* stats) {
   work_has_psi_spectrum_ = false;  // psi may have been replaced since the last call
   pending_rows_ = nullptr;
   psi_spec_valid_ = false;
@@ -1756,7 +1844,9 @@ void Engine::iterate(int iterations, double lambda, float min_value) {
   // (a captured sweep holds buffer addresses: the two work volumes must be back in their roles after it,
   // i.e. the sweep must contain an even number of direct dim0 legs)
   bool use_graph = graphs_on && !halo_fn_ && iterations >= 3 && !prof_.enabled && plan_->can_fuse_rows() &&
-                   plan_->main_bytes() <= graph_max_bytes && streamed_order_.empty();
+                   plan_->main_bytes() <= graph_max_bytes && streamed_order_.empty() && !stats_on_;
+  std::vector<double> rows;  // {S, M, P} of the sweeps run
+  int ran = 0;
   for (int it = 0; it < iterations; ++it) {
     if (use_graph && it == 1) {  // every view has been staged by now: its PSF forms are known
       int swaps = 0;
@@ -1803,9 +1893,27 @@ void Engine::iterate(int iterations, double lambda, float min_value) {
       conv_pair(v, lambda, min_value, MVN_EPI_UPDATE, 0, !last);
       if (streamed) ring_release(views_[(size_t)v]);
     }
+    ran = it + 1;
+    if (!stats_on_) continue;
+    be::launch_convergence_reduce(stat_rec_, stat_count_, V, stat_cap_, stat_out_ + 3 * (size_t)it, stream_);
+    if (tolerance > 0.) {
+      // (no sweep is enqueued ahead: after a stop psi is the estimate of the sweeps run)
+      double r[3];
+      be::d2h(r, stat_out_ + 3 * (size_t)it, sizeof(r), stream_);
+      be::stream_sync(stream_);
+      rows.insert(rows.end(), r, r + 3);
+      if (r[0] / r[2] <= tolerance) break;  // (NaN never stops the loop)
+    }
   }
   flush_pending_rows();
   work_has_psi_spectrum_ = false;
+  if (stats_on_ && tolerance == 0. && ran > 0) {
+    rows.resize(3 * (size_t)ran);
+    be::d2h(rows.data(), stat_out_, rows.size() * sizeof(double), stream_);
+    be::stream_sync(stream_);
+  }
+  if (stats) *stats = std::move(rows);
+  return ran;
 }
 
 float* Engine::delta_ptr() {

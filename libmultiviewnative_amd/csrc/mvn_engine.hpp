@@ -130,9 +130,10 @@ class Plan3D {
   // packed: the Nyquist pointer must be null); out-of-place for rows_r2c, in place tile by tile for rows_c2r_r2c
   void rows_r2c(const float* in_real, cfloat* out, cfloat* out_nyq, be::stream_t s,
                 Profiler* prof = nullptr, long row0 = 0, long nrows = -1, bool lines = false) const;
+  // (`st`: the window and records of an MVN_EPI_UPDATE_STATS epilogue)
   void rows_c2r(const cfloat* in, const cfloat* in_nyq, float* out_real,
                 const EpilogueParams& epi, be::stream_t s, Profiler* prof = nullptr,
-                long row0 = 0, long nrows = -1, bool lines = false) const;
+                long row0 = 0, long nrows = -1, bool lines = false, const MvnStatsParams* st = nullptr) const;
   // the shape has the line-layout forms of the last-axis kernels and the fused middle pass (d1 = d2 = 512)
   bool lines_capable() const;
   // dim1 forward + K-tap direct convolution along dim0 + dim1 inverse, `in` -> `out` (both in the line layout);
@@ -151,7 +152,8 @@ class Plan3D {
   // (data, nyq); epi.mode is DIVIDE, UPDATE or STORE
   bool can_fuse_rows() const { return L.even; }
   void rows_c2r_r2c(cfloat* data, cfloat* nyq, const EpilogueParams& epi, be::stream_t s,
-                    Profiler* prof = nullptr, long row0 = 0, long nrows = -1, bool lines = false) const;
+                    Profiler* prof = nullptr, long row0 = 0, long nrows = -1, bool lines = false,
+                    const MvnStatsParams* st = nullptr) const;
   // strided passes on the main array and its Nyquist plane; mode = MvnStridedMode
   // `s_nyq` (default: s) is the stream of the small Nyquist-plane launches; giving them their own
   // stream lets the 2 MB plane ride along with the full-volume passes (see SideStream)
@@ -246,6 +248,7 @@ struct MemoryQuery {
   size_t embed_floats = 0;
   int streamed = 0;
   int ring = 0;
+  int stats_rows = 0;  // convergence statistics on: the iterations of the call (Engine::iterate), else 0
 };
 
 class Engine {
@@ -303,8 +306,13 @@ class Engine {
   void finish_staging();  // uploader thread, after the last view: drain and free scratch
 
   // `iterations` Gauss-Seidel sweeps over all views (the reference order,
-  // src/gpu_deconvolve_methods.cuh:487-535); asynchronous on stream()
-  void iterate(int iterations, double lambda, float min_value);
+  // src/gpu_deconvolve_methods.cuh:487-535); asynchronous on stream() while tolerance < 0.
+  // tolerance >= 0: the update passes also reduce the convergence statistics of every sweep k,
+  // {S_k, M_k, P_k} (mvn_engine_api.h), appended to *stats; tolerance > 0 ends the loop after the
+  // first sweep with S_k / P_k <= tolerance (each sweep then waits for its statistics).  Returns the
+  // sweeps run.
+  int iterate(int iterations, double lambda, float min_value, double tolerance = -1.,
+              std::vector<double>* stats = nullptr);
   // simultaneous (Jacobi) mode for view sharding: delta <- sum over this engine's views of
   // w_v (next_v - psi), computed from the current psi without changing it
   void compute_delta(double lambda, float min_value);
@@ -527,6 +535,21 @@ class Engine {
   // uploads enqueued / streamed view updates enqueued in this call (under stage_mu_), upload order == use order
   long uploads_ = 0, consumed_ = 0;
   bool stream_abort_ = false;
+  bool stream_done_ = false;  // the loop ended early: later uploads of streamed views are skipped
+ public:
+  // after an early stop (iterate() returned fewer sweeps than asked): releases an uploader thread that
+  // would wait for ring slots no later view update frees
+  void end_streaming();
+ private:
+  // convergence statistics of the running iterate() (allocated for its duration only; see memory_need)
+  bool stats_on_ = false;
+  double* stat_rec_ = nullptr;     // per view: stat_cap_ records of 3 doubles
+  unsigned* stat_count_ = nullptr; // per view: records of its last update pass
+  double* stat_out_ = nullptr;     // 3 doubles per sweep
+  long stat_cap_ = 0;
+  MvnStatsParams stats_for(int v) const;
+  void stats_free();
+  int iterate_sweeps(int iterations, double lambda, float min_value, double tolerance, std::vector<double>* stats);
   void ring_upload(int v, const float* image, const float* weights);  // uploader thread
   void ring_acquire(ViewSlot& s);                                     // main thread, before the view update
   void ring_release(ViewSlot& s);                                     // main thread, after it

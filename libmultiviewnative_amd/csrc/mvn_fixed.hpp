@@ -1126,6 +1126,13 @@ struct FxRowsRegs {
   cfloat ea[FxRowsCfg<H>::IT0][FxRowsCfg<H>::R0];
   cfloat eb[FxRowsCfg<H>::IT0][FxRowsCfg<H>::R0];
 };
+// the register set of the MVN_EPI_UPDATE_STATS forms: the lane's accumulators as well
+template <int H>
+struct FxRowsStatRegs : FxRowsRegs<H> {
+  MvnStatAcc st;
+};
+template <int H, int EPI>
+using FxRowsRegsFor = typename std::conditional<EPI == MVN_EPI_UPDATE_STATS, FxRowsStatRegs<H>, FxRowsRegs<H>>::type;
 
 // LDS offsets (in cfloat, row * TP) of the two bins the real<->complex step combines: entry k
 // (0 < k < H/2) = {bin k, bin H-k}; entry 0 = {bin 0, bin H/2} (the two self-paired bins).
@@ -1263,7 +1270,7 @@ MVN_HD void fx_r2c_post(const RowsParams& P, long r0, cfloat* buf, const cfloat*
 // fused update loses 1.4 % (0.495 -> 0.502: three more streams).
 template <int EPI>
 constexpr bool fx_lines_wide() {
-  return EPI != MVN_EPI_UPDATE && EPI != MVN_EPI_DELTA;
+  return !mvn_epi_reads_psi(EPI);
 }
 template <int H>
 MVN_HD long fx_lines_base(const RowsParams& P, long r0) {
@@ -1378,7 +1385,7 @@ MVN_HD void fx_c2r_load(const RowsParams& P, long r0, cfloat* buf, cfloat* tws, 
       for (int jo = 0; jo < C::R0; ++jo) r.ea[it][jo] = src[jo * C::M0];
     }
   }
-  if (mode == MVN_EPI_UPDATE || mode == MVN_EPI_DELTA) {
+  if (mvn_epi_reads_psi(mode)) {
 #pragma unroll
     for (int it = 0; it < C::IT0; ++it) {
       const int w = tid + it * NT;
@@ -1454,9 +1461,8 @@ MVN_HD void fx_c2r_pre(const RowsParams& P, long r0, cfloat* buf, const cfloat* 
 // c2r last phase: LDS -> last inverse stage in registers -> pointwise epilogue -> either the
 // real rows in global memory (KEEP = false) or, for the fused pass, straight into the first
 // forward stage of the next transform and back to LDS (KEEP = true)
-template <int H, bool KEEP, int EPI>
-MVN_HD void fx_c2r_stage0_epilogue(const RowsParams& P, long r0, cfloat* buf, const cfloat* tws,
-                                   FxRowsRegs<H>& r, int tid) {
+template <int H, bool KEEP, int EPI, typename Regs>
+MVN_HD void fx_c2r_stage0_epilogue(const RowsParams& P, long r0, cfloat* buf, const cfloat* tws, Regs& r, int tid) {
   typedef FxRowsCfg<H> C;
   constexpr int TP = C::TP, NT = C::NT, R = C::R0, M = C::M0;
 #pragma unroll
@@ -1474,16 +1480,24 @@ MVN_HD void fx_c2r_stage0_epilogue(const RowsParams& P, long r0, cfloat* buf, co
     for (int k = 1; k < R; ++k) a[k] = cmulc(a[k], tw[k]);
     dftR<R, +1>(a);  // a[jo] = z[j2 + M*jo] = (x[2j], x[2j+1])
     const long i0 = (r0 + rho) * P.RP + 2 * j2;
+    if constexpr (EPI == MVN_EPI_UPDATE_STATS) {
+      const bool row_in = mvn_stat_row_in(P.st, r0 + rho);
+#pragma unroll
+      for (int jo = 0; jo < R; ++jo)
+        a[jo] = mvn_update_pair_stats(P.epi, i0 + 2 * jo * M, a[jo], r.ea[it][jo], r.eb[it][jo], r.st, P.st, row_in,
+                                      2 * (j2 + jo * M));
+    }
     if (KEEP) {
 #pragma unroll
       for (int jo = 0; jo < R; ++jo)
-        a[jo] = fx_epilogue_pair_value<EPI>(P.epi, i0 + 2 * jo * M, a[jo], r.ea[it][jo], r.eb[it][jo]);
+        if constexpr (EPI != MVN_EPI_UPDATE_STATS)
+          a[jo] = fx_epilogue_pair_value<EPI>(P.epi, i0 + 2 * jo * M, a[jo], r.ea[it][jo], r.eb[it][jo]);
       dftR<R, -1>(a);
 #pragma unroll
       for (int k = 1; k < R; ++k) a[k] = cmul(a[k], tw[k]);
 #pragma unroll
       for (int k = 0; k < R; ++k) p[fx_rowoff<C::PAD, R, M>(k) * TP] = a[k];
-    } else {
+    } else if constexpr (EPI != MVN_EPI_UPDATE_STATS) {
 #pragma unroll
       for (int jo = 0; jo < R; ++jo)
         mvn_epilogue_pair_t<EPI>(P.epi, P.out_real, i0 + 2 * jo * M, a[jo], r.ea[it][jo], r.eb[it][jo]);
@@ -1564,4 +1578,31 @@ MVN_HD void fx_rows_run(const RowsParams& P, long block, long nblocks, cfloat* l
   } else {
     fx_rows_tile<H, KIND, EPI>(P, block, lds, ctx);
   }
+}
+
+// workgroup end of an UPDATE_STATS launch of the phase-structured kernels: the lanes' accumulators (in their
+// register sets) reduced in a fixed order through the LDS, one record per workgroup
+template <int NT, typename Ctx>
+MVN_HD void fx_stat_flush(const MvnStatsParams& s, long block, long nblocks, cfloat* lds, Ctx& ctx) {
+  constexpr int NT_ = NT;
+  (void)NT_;
+  char* l = reinterpret_cast<char*>(lds);
+  MVN_PHASE(ctx, (void)0);  // (the last phase of the wave-row body ends without a workgroup barrier)
+  MVN_PHASE(ctx, (mvn_stat_put(l, NT, tid, r.st)));
+  for (int h = mvn_pow2_ceil(NT) >> 1; h > 0; h >>= 1) {  // (MVN_PHASE is two statements on the device)
+    MVN_PHASE(ctx, (mvn_stat_tree_step(l, NT, h, tid)));
+  }
+  MVN_PHASE_NOSYNC(ctx, (tid == 0 ? mvn_stat_record(s, l, NT, block, nblocks) : (void)0));
+}
+
+// the MVN_EPI_UPDATE_STATS workgroup: accumulators zeroed, fx_rows_run, one record
+template <int H, int KIND, typename Ctx, bool LINES = false>
+MVN_HD void fx_rows_run_stats(const RowsParams& P, long block, long nblocks, cfloat* lds, Ctx& ctx) {
+  static_assert(mvn_stat_lds_bytes(FxRowsCfg<H>::NT) <= (long)sizeof(cfloat) * FxRowsCfg<H>::lds_cfloats,
+                "statistics scratch exceeds the LDS");
+  constexpr int NT_ = FxRowsCfg<H>::NT;
+  (void)NT_;
+  MVN_PHASE_NOSYNC(ctx, (mvn_stat_init(r.st)));
+  fx_rows_run<H, KIND, MVN_EPI_UPDATE_STATS, Ctx, LINES>(P, block, nblocks, lds, ctx);
+  fx_stat_flush<FxRowsCfg<H>::NT>(P.st, block, nblocks, lds, ctx);
 }

@@ -61,6 +61,15 @@ __global__ void __launch_bounds__(512) k_rows_c2r(const RowsParams p) {
   else
     rows_c2r_odd_body<T>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
 }
+// the same with the update epilogue that also keeps the convergence statistics (MVN_EPI_UPDATE_STATS)
+template <bool EVEN, int T>
+__global__ void __launch_bounds__(512) k_rows_c2r_stats(const RowsParams p) {
+  extern __shared__ __attribute__((aligned(16))) char mvn_smem[];
+  if (EVEN)
+    rows_c2r_even_body<T, false, true>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
+  else
+    rows_c2r_odd_body<T, true>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
+}
 
 // NYQ only tags the launches that work on the Nyquist plane, so that profilers list them apart
 // run-time-radix form of the fused c2r + pointwise + r2c pass (any even d2)
@@ -68,6 +77,18 @@ template <int T>
 __global__ void __launch_bounds__(512) k_rows_c2r_r2c(const RowsParams p) {
   extern __shared__ __attribute__((aligned(16))) char mvn_smem[];
   rows_c2r_even_body<T, true>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
+}
+template <int T>
+__global__ void __launch_bounds__(512) k_rows_c2r_r2c_stats(const RowsParams p) {
+  extern __shared__ __attribute__((aligned(16))) char mvn_smem[];
+  rows_c2r_even_body<T, true, true>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
+}
+
+// once per sweep with statistics on: the records of the sweep's view updates -> {S, M, P} (mvn_pass_bodies.hpp)
+__global__ void __launch_bounds__(256) k_convergence_reduce(const double* rec, const unsigned* counts, int nviews,
+                                                            long cap, double* out) {
+  __shared__ double lds[3 * 256];
+  mvn_convergence_reduce_body(rec, counts, nviews, cap, out, lds, (int)threadIdx.x, (int)blockDim.x);
 }
 
 template <int MODE, int T, bool NYQ>
@@ -92,10 +113,13 @@ __global__ void __launch_bounds__(FxRowsCfg<H>::NT) kx_rows_c2r(const RowsParams
   extern __shared__ __attribute__((aligned(16))) char mvn_smem[];
   RowsParams p = p0;
   mvn_arm_poison(p.epi);
-  typedef FxCtx<FxRowsRegs<H>, FxRowsCfg<H>::NT> Ctx;
+  typedef FxCtx<FxRowsRegsFor<H, EPI>, FxRowsCfg<H>::NT> Ctx;
   Ctx ctx;
   ctx.tid = (int)threadIdx.x;
-  fx_rows_run<H, 1, EPI, Ctx, LINES>(p, (long)blockIdx.x, (long)gridDim.x, (cfloat*)mvn_smem, ctx);
+  if constexpr (EPI == MVN_EPI_UPDATE_STATS)
+    fx_rows_run_stats<H, 1, Ctx, LINES>(p, (long)blockIdx.x, (long)gridDim.x, (cfloat*)mvn_smem, ctx);
+  else
+    fx_rows_run<H, 1, EPI, Ctx, LINES>(p, (long)blockIdx.x, (long)gridDim.x, (cfloat*)mvn_smem, ctx);
 }
 
 // (The divide form needs 93 VGPRs, just above the 84 that would let three 512-thread workgroups
@@ -105,10 +129,13 @@ __global__ void __launch_bounds__(FxRowsCfg<H>::NT) kx_rows_c2r_r2c(const RowsPa
   extern __shared__ __attribute__((aligned(16))) char mvn_smem[];
   RowsParams p = p0;
   mvn_arm_poison(p.epi);
-  typedef FxCtx<FxRowsRegs<H>, FxRowsCfg<H>::NT> Ctx;
+  typedef FxCtx<FxRowsRegsFor<H, EPI>, FxRowsCfg<H>::NT> Ctx;
   Ctx ctx;
   ctx.tid = (int)threadIdx.x;
-  fx_rows_run<H, 2, EPI, Ctx, LINES>(p, (long)blockIdx.x, (long)gridDim.x, (cfloat*)mvn_smem, ctx);
+  if constexpr (EPI == MVN_EPI_UPDATE_STATS)
+    fx_rows_run_stats<H, 2, Ctx, LINES>(p, (long)blockIdx.x, (long)gridDim.x, (cfloat*)mvn_smem, ctx);
+  else
+    fx_rows_run<H, 2, EPI, Ctx, LINES>(p, (long)blockIdx.x, (long)gridDim.x, (cfloat*)mvn_smem, ctx);
 }
 
 // the fused middle pass (mvn_mid_fused.hpp): one column (piece) per workgroup
@@ -631,6 +658,7 @@ void launch_rows_c2r(const RowsParams& p, bool even, long nblocks, int nthreads,
     switch (p.epi.mode) {
       case MVN_EPI_DIVIDE: return launch_pass(kx_rows_c2r<256, MVN_EPI_DIVIDE, true>, p, nblocks, nthreads, lds_bytes, s);
       case MVN_EPI_UPDATE: return launch_pass(kx_rows_c2r<256, MVN_EPI_UPDATE, true>, p, nblocks, nthreads, lds_bytes, s);
+      case MVN_EPI_UPDATE_STATS: return launch_pass(kx_rows_c2r<256, MVN_EPI_UPDATE_STATS, true>, p, nblocks, nthreads, lds_bytes, s);
       case MVN_EPI_DELTA: return launch_pass(kx_rows_c2r<256, MVN_EPI_DELTA, true>, p, nblocks, nthreads, lds_bytes, s);
       default: return launch_pass(kx_rows_c2r<256, MVN_EPI_STORE, true>, p, nblocks, nthreads, lds_bytes, s);
     }
@@ -642,6 +670,7 @@ void launch_rows_c2r(const RowsParams& p, bool even, long nblocks, int nthreads,
       switch (p.epi.mode) {
         case MVN_EPI_DIVIDE: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_DIVIDE>, p, s);
         case MVN_EPI_UPDATE: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_UPDATE>, p, s);
+        case MVN_EPI_UPDATE_STATS: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_UPDATE_STATS>, p, s);
         case MVN_EPI_DELTA: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_DELTA>, p, s);
         default: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_STORE>, p, s);
       }
@@ -652,6 +681,7 @@ void launch_rows_c2r(const RowsParams& p, bool even, long nblocks, int nthreads,
     switch (p.epi.mode) {                                                                     \
       case MVN_EPI_DIVIDE: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_DIVIDE>, p, nblocks, nthreads, lds_bytes, s); break; \
       case MVN_EPI_UPDATE: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_UPDATE>, p, nblocks, nthreads, lds_bytes, s); break; \
+      case MVN_EPI_UPDATE_STATS: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_UPDATE_STATS>, p, nblocks, nthreads, lds_bytes, s); break; \
       case MVN_EPI_DELTA: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_DELTA>, p, nblocks, nthreads, lds_bytes, s); break;   \
       default: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_STORE>, p, nblocks, nthreads, lds_bytes, s); break;             \
     }                                                                                         \
@@ -660,6 +690,15 @@ void launch_rows_c2r(const RowsParams& p, bool even, long nblocks, int nthreads,
 #undef X
       default: throw std::invalid_argument("mvn: no fixed rows kernel for this length");
     }
+  }
+  if (p.epi.mode == MVN_EPI_UPDATE_STATS) {
+    lds_bytes = std::max(lds_bytes, (size_t)mvn_stat_lds_bytes(nthreads));
+    if (even) {
+      MVN_DISPATCH_T(p.T, (k_rows_c2r_stats<true, TT>));
+    } else {
+      MVN_DISPATCH_T(p.T, (k_rows_c2r_stats<false, TT>));
+    }
+    return;
   }
   if (even) {
     MVN_DISPATCH_T(p.T, (k_rows_c2r<true, TT>));
@@ -676,10 +715,16 @@ void launch_rows_c2r_r2c(const RowsParams& p, long nblocks, int nthreads, size_t
     switch (p.epi.mode) {
       case MVN_EPI_DIVIDE: return launch_pass(kx_rows_c2r_r2c<256, MVN_EPI_DIVIDE, true>, p, nblocks, nthreads, lds_bytes, s);
       case MVN_EPI_UPDATE: return launch_pass(kx_rows_c2r_r2c<256, MVN_EPI_UPDATE, true>, p, nblocks, nthreads, lds_bytes, s);
+      case MVN_EPI_UPDATE_STATS: return launch_pass(kx_rows_c2r_r2c<256, MVN_EPI_UPDATE_STATS, true>, p, nblocks, nthreads, lds_bytes, s);
       default: return launch_pass(kx_rows_c2r_r2c<256, MVN_EPI_STORE, true>, p, nblocks, nthreads, lds_bytes, s);
     }
   }
   if (!p.fixed) {
+    if (p.epi.mode == MVN_EPI_UPDATE_STATS) {
+      lds_bytes = std::max(lds_bytes, (size_t)mvn_stat_lds_bytes(nthreads));
+      MVN_DISPATCH_T(p.T, (k_rows_c2r_r2c_stats<TT>));
+      return;
+    }
     MVN_DISPATCH_T(p.T, (k_rows_c2r_r2c<TT>));
     return;
   }
@@ -689,6 +734,7 @@ void launch_rows_c2r_r2c(const RowsParams& p, long nblocks, int nthreads, size_t
     switch (p.epi.mode) {
       case MVN_EPI_DIVIDE: return launch_wave_rows(kw_rows<MVN_WR_C2R_R2C, MVN_EPI_DIVIDE>, p, s);
       case MVN_EPI_UPDATE: return launch_wave_rows(kw_rows<MVN_WR_C2R_R2C, MVN_EPI_UPDATE>, p, s, 32);
+      case MVN_EPI_UPDATE_STATS: return launch_wave_rows(kw_rows<MVN_WR_C2R_R2C, MVN_EPI_UPDATE_STATS>, p, s, 32);
       default: return launch_wave_rows(kw_rows<MVN_WR_C2R_R2C, MVN_EPI_STORE>, p, s);
     }
   }
@@ -698,6 +744,7 @@ void launch_rows_c2r_r2c(const RowsParams& p, long nblocks, int nthreads, size_t
     switch (p.epi.mode) {                                                                     \
       case MVN_EPI_DIVIDE: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r_r2c<H, MVN_EPI_DIVIDE>, p, nblocks, nthreads, lds_bytes, s); break; \
       case MVN_EPI_UPDATE: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r_r2c<H, MVN_EPI_UPDATE>, p, nblocks, nthreads, lds_bytes, s); break; \
+      case MVN_EPI_UPDATE_STATS: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r_r2c<H, MVN_EPI_UPDATE_STATS>, p, nblocks, nthreads, lds_bytes, s); break; \
       default: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r_r2c<H, MVN_EPI_STORE>, p, nblocks, nthreads, lds_bytes, s); break;             \
     }                                                                                         \
     return;
@@ -705,6 +752,12 @@ void launch_rows_c2r_r2c(const RowsParams& p, long nblocks, int nthreads, size_t
 #undef X
     default: throw std::invalid_argument("mvn: no fixed rows kernel for this length");
   }
+}
+
+void launch_convergence_reduce(const double* rec, const unsigned* counts, int nviews, long cap, double* out,
+                               stream_t s) {
+  hipLaunchKernelGGL(k_convergence_reduce, dim3(1), dim3(256), 0, hs(s), rec, counts, nviews, cap, out);
+  HIP_CHECK(hipGetLastError());
 }
 
 static std::atomic<long> g_split_launches{0};

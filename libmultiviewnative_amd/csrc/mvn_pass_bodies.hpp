@@ -31,8 +31,14 @@ enum MvnEpilogue {
   MVN_EPI_STORE = 0,   // out = x * scale
   MVN_EPI_DIVIDE = 1,  // out = view * float(1.0 / (x*scale))
   MVN_EPI_UPDATE = 2,  // psi = w * (next(psi, x*scale) - psi) + psi
-  MVN_EPI_DELTA = 3    // delta (+)= w * (next(psi, x*scale) - psi)     (simultaneous mode)
+  MVN_EPI_DELTA = 3,   // delta (+)= w * (next(psi, x*scale) - psi)     (simultaneous mode)
+  MVN_EPI_UPDATE_STATS = 4  // UPDATE, plus the convergence statistics of the window (MvnStatsParams)
 };
+
+// the epilogues that read psi and the weights
+constexpr bool mvn_epi_reads_psi(int epi) {
+  return epi == MVN_EPI_UPDATE || epi == MVN_EPI_DELTA || epi == MVN_EPI_UPDATE_STATS;
+}
 
 struct EpilogueParams {
   int mode;
@@ -214,6 +220,169 @@ MVN_HD float mvn_blend(float w, float next, float last) {
   return w * (next - last) + last;  // inc/cpu_kernels.h:51-52
 }
 
+// ---------------------------------------------------------------------------------------------
+// convergence statistics (MVN_EPI_UPDATE_STATS).  Every lane sums |psi_after - psi_before| and psi_after, and
+// takes the max of |psi_after - psi_before|, over the voxels of the window it updates; at the end the workgroup
+// reduces its lanes in a fixed order through the LDS and writes ONE record {sum, max, mass} with plain stores.
+// No atomics and no cross-lane instructions: the records, and the per-sweep sums of k_convergence_reduce, are
+// the same bits for the same shape and grid.
+// ---------------------------------------------------------------------------------------------
+struct MvnStatsParams {
+  long row0;              // volume row of the launch's row 0
+  int d1;                 // rows per plane
+  int o0, o1, o2;         // window: first plane, row, column ...
+  unsigned n0, n1, n2;    // ... and extent
+  double* rec;            // 3 doubles per workgroup: {sum |dpsi|, max |dpsi|, sum psi}
+  unsigned* count;        // workgroups of the launch, written by workgroup 0
+  long cap;               // records `rec` holds (a workgroup beyond writes none)
+};
+
+struct MvnStatAcc {
+  double sum, mass;
+  float max;
+};
+
+MVN_HD void mvn_stat_init(MvnStatAcc& a) {
+  a.sum = 0.;
+  a.mass = 0.;
+  a.max = 0.f;
+}
+
+// the row's plane and row inside the window (one division per ROW; the column test is per element)
+MVN_HD bool mvn_stat_row_in(const MvnStatsParams& s, long row) {
+  const unsigned g = (unsigned)(s.row0 + row), d1 = (unsigned)s.d1;
+  const unsigned z = g / d1, y = g - z * d1;
+  return z - (unsigned)s.o0 < s.n0 && y - (unsigned)s.o1 < s.n1;
+}
+
+// a max that keeps a NaN once it has seen one
+MVN_HD float mvn_stat_max(float m, float d) { return (d > m || d != d) ? d : m; }
+
+// one voxel: psi `last` -> `y`, from the integral `x`.  (x - x) is +0 for a finite x and NaN otherwise: a
+// non-finite integral (a poisoned call) makes the statistics NaN although the clamp chain keeps psi finite.
+MVN_HD void mvn_stat_add(MvnStatAcc& a, bool in, float last, float y, float x) {
+  MVN_FP_EXACT
+  const float d = fabsf(y - last) + (x - x);
+  a.sum += in ? (double)d : 0.;
+  a.mass += in ? (double)y : 0.;
+  a.max = in ? mvn_stat_max(a.max, d) : a.max;
+}
+
+// MVN_EPI_UPDATE of the pair (i, i + 1) in columns col, col + 1 of a row, with its statistics: psi (written
+// and returned) is the UPDATE result bit for bit
+MVN_HD cfloat mvn_update_pair_stats(const EpilogueParams& e, long i, cfloat z, cfloat a, cfloat b, MvnStatAcc& acc,
+                                    const MvnStatsParams& s, bool row_in, int col) {
+  MVN_FP_EXACT
+  const float x0 = z.x * e.scale, x1 = z.y * e.scale;
+  const float n0 = mvn_next_value(a.x, x0, e.lambda, e.lambda_inv, e.min_value);
+  const float n1 = mvn_next_value(a.y, x1, e.lambda, e.lambda_inv, e.min_value);
+  const cfloat y = cmake(mvn_blend(b.x, n0, a.x), mvn_blend(b.y, n1, a.y));
+  *reinterpret_cast<cfloat*>(e.psi + i) = y;
+  const unsigned c = (unsigned)(col - s.o2);
+  mvn_stat_add(acc, row_in && c < s.n2, a.x, y.x, x0);
+  mvn_stat_add(acc, row_in && c + 1u < s.n2, a.y, y.y, x1);
+  return y;
+}
+
+// the same for one element (odd d2)
+MVN_HD void mvn_update_stats(const EpilogueParams& e, long i, float x, MvnStatAcc& acc, bool in) {
+  MVN_FP_EXACT
+  x *= e.scale;
+  const float last = e.psi[i];
+  const float next = mvn_next_value(last, x, e.lambda, e.lambda_inv, e.min_value);
+  const float y = e.weights[i] * (next - last) + last;  // inc/cpu_kernels.h:51-52
+  e.psi[i] = y;
+  mvn_stat_add(acc, in, last, y, x);
+}
+
+// scratch of the lane reduction: n doubles (sum), n doubles (mass), n floats (max)
+MVN_HD constexpr long mvn_stat_lds_bytes(int nthreads) { return 20L * nthreads; }
+
+// lanes [tid] of the scratch after a barrier: a tree over the next power of two, pairs (t, t + h) in a fixed order
+MVN_HD void mvn_stat_tree_step(char* lds, int n, int h, int tid) {
+  double* ls = reinterpret_cast<double*>(lds);
+  double* lm = ls + n;
+  float* lx = reinterpret_cast<float*>(lm + n);
+  if (tid < h && tid + h < n) {
+    ls[tid] += ls[tid + h];
+    lm[tid] += lm[tid + h];
+    lx[tid] = mvn_stat_max(lx[tid], lx[tid + h]);
+  }
+}
+MVN_HD void mvn_stat_put(char* lds, int n, int tid, const MvnStatAcc& a) {
+  double* ls = reinterpret_cast<double*>(lds);
+  ls[tid] = a.sum;
+  ls[n + tid] = a.mass;
+  reinterpret_cast<float*>(ls + 2 * n)[tid] = a.max;
+}
+MVN_HD void mvn_stat_record(const MvnStatsParams& s, const char* lds, int n, long block, long nblocks) {
+  const double* ls = reinterpret_cast<const double*>(lds);
+  if (block < s.cap) {
+    s.rec[3 * block] = ls[0];
+    s.rec[3 * block + 1] = (double)reinterpret_cast<const float*>(ls + 2 * n)[0];
+    s.rec[3 * block + 2] = ls[n];
+  }
+  if (block == 0) *s.count = (unsigned)nblocks;
+}
+MVN_HD int mvn_pow2_ceil(int n) {
+  int p = 1;
+  while (p < n) p <<= 1;
+  return p;
+}
+
+// workgroup end of the run-time-radix bodies (tid / nthreads form): every lane calls it
+MVN_HD void mvn_stat_flush(const MvnStatsParams& s, const MvnStatAcc& a, long block, long nblocks, cfloat* lds,
+                           int tid, int nthreads) {
+  char* l = reinterpret_cast<char*>(lds);
+  MVN_SYNC();
+  for (int t = tid; t < nthreads; t += nthreads) mvn_stat_put(l, nthreads, t, a);
+  MVN_SYNC();
+  for (int h = mvn_pow2_ceil(nthreads) >> 1; h > 0; h >>= 1) {
+    for (int t = tid; t < h; t += nthreads) mvn_stat_tree_step(l, nthreads, h, t);
+    MVN_SYNC();
+  }
+  if (tid == 0) mvn_stat_record(s, l, nthreads, block, nblocks);
+}
+
+// k_convergence_reduce: the records of one sweep's V view updates (view v at rec + 3 v cap, counts[v] of them)
+// -> out = {S, M, P}.  Lane t sums records t, t + nthreads, ... view after view, then the lanes are reduced as
+// above.  lds: 3 nthreads doubles.
+MVN_HD void mvn_convergence_reduce_body(const double* rec, const unsigned* counts, int nviews, long cap,
+                                        double* out, double* lds, int tid, int nthreads) {
+  for (int t = tid; t < nthreads; t += nthreads) {
+    double s = 0., m = 0., p = 0.;
+    for (int v = 0; v < nviews; ++v) {
+      const long n = (long)counts[v] < cap ? (long)counts[v] : cap;
+      const double* r = rec + 3 * (long)v * cap;
+      for (long i = t; i < n; i += nthreads) {
+        s += r[3 * i];
+        m = (r[3 * i + 1] > m || r[3 * i + 1] != r[3 * i + 1]) ? r[3 * i + 1] : m;
+        p += r[3 * i + 2];
+      }
+    }
+    lds[t] = s;
+    lds[nthreads + t] = m;
+    lds[2 * nthreads + t] = p;
+  }
+  MVN_SYNC();
+  for (int h = mvn_pow2_ceil(nthreads) >> 1; h > 0; h >>= 1) {
+    for (int t = tid; t < h; t += nthreads) {
+      if (t + h < nthreads) {
+        lds[t] += lds[t + h];
+        const double a = lds[nthreads + t], b = lds[nthreads + t + h];
+        lds[nthreads + t] = (b > a || b != b) ? b : a;
+        lds[2 * nthreads + t] += lds[2 * nthreads + t + h];
+      }
+    }
+    MVN_SYNC();
+  }
+  if (tid == 0) {
+    out[0] = lds[0];
+    out[1] = lds[nthreads];
+    out[2] = lds[2 * nthreads];
+  }
+}
+
 // Pair epilogue of the fused c2r + pointwise + r2c pass: hands the two results back as the packed
 // input z[j] = (y[2j], y[2j+1]) of the next forward transform; UPDATE also writes psi.
 MVN_HD cfloat mvn_epilogue_pair_value(int mode, const EpilogueParams& e, long i, cfloat z, cfloat a,
@@ -275,7 +444,18 @@ struct RowsParams {
   // volume and in_cplx / out_cplx point at the volume's first element.  Fixed kernels only, nyq_packed only.
   int lines, lines_d1;
   long row_base;
+  MvnStatsParams st;  // MVN_EPI_UPDATE_STATS only
 };
+
+// the window bits of the T rows of a tile (run-time-radix bodies: the division stays per row)
+template <int T>
+MVN_HD unsigned mvn_stat_tile_rows(const RowsParams& P, long r0) {
+  static_assert(T <= 32, "one bit per row");
+  unsigned bits = 0;
+  for (int rho = 0; rho < T; ++rho)
+    if (r0 + rho < P.rows && mvn_stat_row_in(P.st, r0 + rho)) bits |= 1u << rho;
+  return bits;
+}
 
 // forward stages + real<->complex step + store of a tile that already sits in LDS as the packed
 // rows z[j] (shared by the plain r2c pass and the fused c2r + pointwise + r2c pass)
@@ -356,12 +536,20 @@ MVN_HD void rows_r2c_even_body(const RowsParams& P, long tile, int tid, int nthr
 // O = (X[k] - conj X[h-k]) exp(+2 pi i k/d2); z = IFFT_h(Z); x[2j] = Re z[j], x[2j+1] = Im z[j]
 // KEEP = true is the fused pass: the epilogue results stay in LDS and run straight through the
 // forward half (rows_r2c_even_tail), writing the half-spectrum of the result over the input.
-template <int T, bool KEEP = false>
+// STATS = true: the UPDATE epilogue with the convergence statistics (P.epi.mode is then MVN_EPI_UPDATE_STATS).
+template <int T, bool KEEP = false, bool STATS = false>
 MVN_HD void rows_c2r_even_body(const RowsParams& P, long tile, int tid, int nthreads, cfloat* lds) {
   // (a copy of the epilogue's few fields, not of P: the run-time radix tables in P are indexed dynamically and a
   // private copy of the whole struct would live in scratch memory)
   EpilogueParams epi = P.epi;
   mvn_arm_poison(epi);
+  MvnStatAcc acc;
+  unsigned rin = 0;
+  if constexpr (STATS) {
+    epi.mode = MVN_EPI_UPDATE;  // operands and psi as UPDATE
+    mvn_stat_init(acc);
+    rin = mvn_stat_tile_rows<T>(P, tile * T);
+  }
   constexpr int U = MVN_ROWS_U;
   const int h = P.h, TP = P.TP;
   const long r0 = tile * T;
@@ -447,7 +635,11 @@ MVN_HD void rows_c2r_even_body(const RowsParams& P, long tile, int tid, int nthr
       const int rho = (int)mvn_fastdiv((unsigned)w, (unsigned)h, P.hmul), j = w - rho * h;
       const long row = r0 + rho;
       if (w < total && row <= last_row) {
-        if (KEEP)
+        if constexpr (STATS) {
+          const cfloat y = mvn_update_pair_stats(epi, row * P.RP + 2 * j, buf[j * TP + rho], ea[u], eb[u], acc,
+                                                 P.st, (rin >> rho) & 1u, 2 * j);
+          if (KEEP) buf[j * TP + rho] = y;
+        } else if (KEEP)
           buf[j * TP + rho] = mvn_epilogue_pair_value(epi.mode, epi, row * P.RP + 2 * j,
                                                       buf[j * TP + rho], ea[u], eb[u]);
         else
@@ -459,6 +651,7 @@ MVN_HD void rows_c2r_even_body(const RowsParams& P, long tile, int tid, int nthr
     MVN_SYNC();
     rows_r2c_even_tail<T>(P, r0, buf, alt, tw, tid, nthreads);
   }
+  if constexpr (STATS) mvn_stat_flush(P.st, acc, tile, (P.rows + T - 1) / T, lds, tid, nthreads);
 }
 
 // odd d2: plain complex transform of the real row, first C = (d2+1)/2 bins kept
@@ -485,12 +678,18 @@ MVN_HD void rows_r2c_odd_body(const RowsParams& P, long tile, int tid, int nthre
   }
 }
 
-template <int T>
+template <int T, bool STATS = false>
 MVN_HD void rows_c2r_odd_body(const RowsParams& P, long tile, int tid, int nthreads, cfloat* lds) {
   // (a copy of the epilogue's few fields, not of P: the run-time radix tables in P are indexed dynamically and a
   // private copy of the whole struct would live in scratch memory)
   EpilogueParams epi = P.epi;
   mvn_arm_poison(epi);
+  MvnStatAcc acc;
+  unsigned rin = 0;
+  if constexpr (STATS) {
+    mvn_stat_init(acc);
+    rin = mvn_stat_tile_rows<T>(P, tile * T);
+  }
   const int n = P.h, TP = P.TP;
   const long r0 = tile * T;
   cfloat* buf = lds;
@@ -515,8 +714,15 @@ MVN_HD void rows_c2r_odd_body(const RowsParams& P, long tile, int tid, int nthre
   for (int w = tid; w < T * n; w += nthreads) {
     const int rho = (int)mvn_fastdiv((unsigned)w, (unsigned)n, P.hmul), j = w - rho * n;
     const long row = r0 + rho;
-    if (row < P.rows) mvn_epilogue(epi, P.out_real, row * P.RP + j, buf[j * TP + rho].x);
+    if constexpr (STATS) {
+      if (row < P.rows)
+        mvn_update_stats(epi, row * P.RP + j, buf[j * TP + rho].x, acc,
+                         ((rin >> rho) & 1u) && (unsigned)(j - P.st.o2) < P.st.n2);
+    } else if (row < P.rows) {
+      mvn_epilogue(epi, P.out_real, row * P.RP + j, buf[j * TP + rho].x);
+    }
   }
+  if constexpr (STATS) mvn_stat_flush(P.st, acc, tile, (P.rows + T - 1) / T, lds, tid, nthreads);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -77,6 +77,7 @@ struct WrRegs {
   cfloat eb[8];
   cfloat pw[4];  // exp(-2 pi i k / d2) of the lane's (k, H - k) pairs
   qfloat nx[4];  // the lane's two groups of the NEXT row of its half-wave, requested one row ahead
+  MvnStatAcc st; // MVN_EPI_UPDATE_STATS
 };
 
 // exp(-2 pi i k / d2) for 0 < k < H from the table of k <= H/2 (P.twr)
@@ -140,7 +141,7 @@ MVN_HD void wr_setup(const RowsParams& P, WrRegs& r, cfloat* rows, int tid) {
 // pair twiddles from a 1 KB LDS table in phases A and E instead of keeping them in 8 registers.
 template <int EPI>
 constexpr bool wr_pw_in_lds() {
-  return EPI == MVN_EPI_UPDATE || EPI == MVN_EPI_DELTA;
+  return mvn_epi_reads_psi(EPI);
 }
 template <int EPI>
 MVN_HD void wr_pw(const WrRegs& r, const cfloat* rows, int t, cfloat* pw) {
@@ -220,7 +221,7 @@ MVN_HD void wr_fetch_epi(const RowsParams& P, long row, WrRegs& r, int tid) {
 #pragma unroll
     for (int jo = 0; jo < 8; ++jo) r.ea[jo] = *reinterpret_cast<const cfloat*>(pa + 64 * jo);
   }
-  if (EPI == MVN_EPI_UPDATE || EPI == MVN_EPI_DELTA) {
+  if (mvn_epi_reads_psi(EPI)) {
     const float* pb = P.epi.weights + row * P.RP + 2 * t;
 #pragma unroll
     for (int jo = 0; jo < 8; ++jo) r.eb[jo] = *reinterpret_cast<const cfloat*>(pb + 64 * jo);
@@ -323,10 +324,15 @@ MVN_HD void wr_phase_c(const RowsParams& P, long row, long next_row, cfloat* row
 #pragma unroll
     for (int k = 1; k < 8; ++k) a[k] = cmulc(a[k], tw[k]);
     dftR<8, +1>(a);  // a[jo] = z[t + 32 jo] = (x[2 j], x[2 j + 1])
+    bool row_in = false;
+    if constexpr (EPI == MVN_EPI_UPDATE_STATS) row_in = mvn_stat_row_in(P.st, row);
     if (MODE == MVN_WR_C2R) {
 #pragma unroll
       for (int jo = 0; jo < 8; ++jo) {
-        mvn_epilogue_pair_t<EPI>(P.epi, P.out_real, i0 + 64 * jo, a[jo], r.ea[jo], r.eb[jo]);
+        if constexpr (EPI == MVN_EPI_UPDATE_STATS)
+          mvn_update_pair_stats(P.epi, i0 + 64 * jo, a[jo], r.ea[jo], r.eb[jo], r.st, P.st, row_in, 2 * t + 64 * jo);
+        else
+          mvn_epilogue_pair_t<EPI>(P.epi, P.out_real, i0 + 64 * jo, a[jo], r.ea[jo], r.eb[jo]);
         if (jo & 1) MVN_SCHED_FENCE();  // four values at a time: the f64 chains of all 16 would not fit
       }
       wr_fetch_epi<EPI>(P, next_row, r, tid);
@@ -334,7 +340,11 @@ MVN_HD void wr_phase_c(const RowsParams& P, long row, long next_row, cfloat* row
     }
 #pragma unroll
     for (int jo = 0; jo < 8; ++jo) {
-      a[jo] = fx_epilogue_pair_value<EPI>(P.epi, i0 + 64 * jo, a[jo], r.ea[jo], r.eb[jo]);
+      if constexpr (EPI == MVN_EPI_UPDATE_STATS)
+        a[jo] = mvn_update_pair_stats(P.epi, i0 + 64 * jo, a[jo], r.ea[jo], r.eb[jo], r.st, P.st, row_in,
+                                      2 * t + 64 * jo);
+      else
+        a[jo] = fx_epilogue_pair_value<EPI>(P.epi, i0 + 64 * jo, a[jo], r.ea[jo], r.eb[jo]);
       if (jo & 1) MVN_SCHED_FENCE();
     }
     wr_fetch_epi<EPI>(P, next_row, r, tid);
@@ -413,7 +423,7 @@ MVN_HD void wr_phase_e(const RowsParams& P, long row, const cfloat* rows, const 
 
 // workgroup `block` of `nblocks`: sweeps over the row pairs (it nblocks + block) WAVES + wave
 template <int MODE, int EPI, typename Ctx>
-MVN_HD void wr_rows_body(const RowsParams& P, long block, long nblocks, cfloat* lds, Ctx& ctx) {
+MVN_HD void wr_rows_walk(const RowsParams& P, long block, long nblocks, cfloat* lds, Ctx& ctx) {
   constexpr int NT_ = WrCfg::NT;
   (void)NT_;
   cfloat* tws = lds;
@@ -437,5 +447,20 @@ MVN_HD void wr_rows_body(const RowsParams& P, long block, long nblocks, cfloat* 
       MVN_WPHASE(ctx, (wr_phase_mid<-1>(wr_row(block, nblocks, it, tid), P.rows, rows, tws, tid)));
       MVN_WPHASE(ctx, (wr_phase_e<EPI>(P, wr_row(block, nblocks, it, tid), rows, r, tid)));
     }
+  }
+}
+
+template <int MODE, int EPI, typename Ctx>
+MVN_HD void wr_rows_body(const RowsParams& P, long block, long nblocks, cfloat* lds, Ctx& ctx) {
+  if constexpr (EPI == MVN_EPI_UPDATE_STATS) {
+    static_assert(mvn_stat_lds_bytes(WrCfg::NT) <= (long)sizeof(cfloat) * WrCfg::lds_cfloats,
+                  "statistics scratch exceeds the LDS");
+    constexpr int NT_ = WrCfg::NT;
+    (void)NT_;
+    MVN_PHASE_NOSYNC(ctx, (mvn_stat_init(r.st)));
+    wr_rows_walk<MODE, EPI>(P, block, nblocks, lds, ctx);
+    fx_stat_flush<WrCfg::NT>(P.st, block, nblocks, lds, ctx);
+  } else {
+    wr_rows_walk<MODE, EPI>(P, block, nblocks, lds, ctx);
   }
 }

@@ -42,6 +42,7 @@ ENGINE_ABI_SYMBOLS = [
     "mvn_slab_create", "mvn_slab_destroy", "mvn_slab_set_view", "mvn_slab_set_psi", "mvn_slab_get_psi",
     "mvn_slab_buffer_sizes", "mvn_slab_buffers", "mvn_slab_bind_buffers", "mvn_slab_begin",
     "mvn_slab_pack", "mvn_slab_mid", "mvn_slab_unpack", "mvn_slab_sync", "mvn_slab_stream",
+    "mvn_set_convergence", "mvn_get_convergence", "mvn_last_convergence", "mvn_engine_iterate_converge",
 ]
 
 
@@ -128,6 +129,11 @@ class Binding:
         l.mvn_engine_set_psi.argtypes = [C.c_void_p, c_float_p]
         l.mvn_engine_get_psi.argtypes = [C.c_void_p, c_float_p]
         l.mvn_engine_iterate.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_float]
+        l.mvn_engine_iterate_converge.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_float, C.c_double,
+                                                  C.POINTER(C.c_int), C.POINTER(C.c_double)]
+        l.mvn_set_convergence.argtypes = [C.c_double]
+        l.mvn_get_convergence.argtypes = [C.POINTER(C.c_double)]
+        l.mvn_last_convergence.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_int]
         l.mvn_engine_compute_delta.argtypes = [C.c_void_p, C.c_double, C.c_float]
         l.mvn_engine_apply_delta.argtypes = [C.c_void_p]
         l.mvn_engine_delta_chunks.argtypes = [C.c_void_p, C.c_int]
@@ -213,6 +219,27 @@ class Binding:
         out = (C.c_longlong * 3)()
         self.check(self.l.mvn_stream_counters(out))
         return tuple(int(x) for x in out)
+
+    def set_convergence(self, tolerance):
+        """Process-wide convergence tolerance: < 0 off (default), 0 statistics only, > 0 stop at
+        S_k / P_k <= tolerance (mvn_engine_api.h)."""
+        self.check(self.l.mvn_set_convergence(float(tolerance)))
+
+    def get_convergence(self):
+        out = C.c_double(0)
+        self.check(self.l.mvn_get_convergence(C.byref(out)))
+        return out.value
+
+    def last_convergence(self):
+        """(iterations run, float64 array [rows, 3] of {S_k, M_k, P_k}) of the last deconvolution this thread
+        completed (inplace_gpu_deconvolve, or the wait of its ticket)."""
+        run = C.c_int(0)
+        rows = self.l.mvn_last_convergence(C.byref(run), None, 0)
+        self.check(rows)
+        out = np.zeros((rows, 3), dtype=np.float64)
+        if rows:
+            self.check(self.l.mvn_last_convergence(C.byref(run), out.ctypes.data_as(C.POINTER(C.c_double)), rows))
+        return run.value, out
 
     # ---- reference ABI, numpy in / numpy out ----------------------------------------------
     def gpu_deconvolve(self, psi, holder, device=0, pad_mode="none"):
@@ -443,6 +470,15 @@ class EngineHandle:
         self.b.check(self.b.l.mvn_engine_iterate(self.h, iterations, lambda_, min_value))
         if sync:
             self.sync()
+
+    def iterate_converge(self, iterations, lambda_, min_value, tolerance):
+        """mvn_engine_iterate_converge (blocking): (iterations run, float64 array [run, 3] of {S_k, M_k, P_k})."""
+        run = C.c_int(0)
+        stats = np.zeros((max(int(iterations), 1), 3), dtype=np.float64)
+        self.b.check(self.b.l.mvn_engine_iterate_converge(self.h, iterations, lambda_, min_value, float(tolerance),
+                                                          C.byref(run),
+                                                          stats.ctypes.data_as(C.POINTER(C.c_double))))
+        return run.value, (stats[:run.value].copy() if tolerance >= 0 else np.zeros((0, 3)))
 
     def time_iterate(self, iterations, lambda_, min_value):
         ms = C.c_float(0)
