@@ -159,12 +159,27 @@ static MemoryQuery memory_query(const shape_t& ext, const workspace& input, size
   q.ext = ext;
   q.embed_floats = embed_floats;
   q.stats_rows = call_tolerance() >= 0. ? std::max(input.num_iterations_, 1) : 0;
-  for (int v = 0; v < input.num_views_; ++v) {
-    const view_data& d = input.data_[v];
-    q.kernels.push_back({{d.kernel1_dims_[0], d.kernel1_dims_[1], d.kernel1_dims_[2]}});
-    q.kernels.push_back({{d.kernel2_dims_[0], d.kernel2_dims_[1], d.kernel2_dims_[2]}});
-  }
+  q.kernels = call_kernels(input);
   return q;
+}
+
+// The PSF form rule (mvn_engine.hpp) for a volume of extents ext on device dev, before any engine exists: the
+// switches in force now, and the plan an engine of these extents will run on - the one in the plan store where it
+// has one (built with the MVN_NO_FIXED of its time), else one built now.  dev < 0: no stored plan is looked at.
+static FormRule call_rule(const shape_t& ext, int dev) {
+  const FormSwitches sw = FormSwitches::from_env();
+  const std::shared_ptr<Plan3D> stored = dev >= 0 ? PlanStore::get().find(dev, ext) : nullptr;
+  return FormRule(Layout(ext[0], ext[1], ext[2]), sw, stored ? stored->fixed : sw.fixed);
+}
+
+// A cached engine serves a call of its extents and view count whose PSF form rule it shares (switches, and the kernel
+// family of its plan): then it holds the call's kernels in the forms call_extents and memory_need assumed.  (The
+// switches are read when an engine is created; tests change them within a process.)
+static bool reusable(const Engine& e, const shape_t& ext, int V) {
+  const Layout& L = e.layout();
+  if (!engine_cache_enabled() || L.d0 != ext[0] || L.d1 != ext[1] || L.d2 != ext[2] || e.num_views() != V) return false;
+  const FormRule mine = e.form_rule(), call = call_rule(ext, e.device());
+  return mine.sw == call.sw && mine.plan_fixed == call.plan_fixed;
 }
 
 // s streamed views spread evenly over the sweep (view floor((j + 1/2) V / s) for j < s), so that each upload
@@ -180,15 +195,15 @@ static std::unique_ptr<Engine> plan_engine(int key, int dev, const shape_t& ext,
                                            const workspace& input, int mode) {
   const int V = input.num_views_;
   MemoryQuery q = memory_query(ext, input, embed_floats);
+  const FormRule rule = call_rule(ext, dev);
   auto need = [&](int s, int ring) {
     q.streamed = s;
     q.ring = ring;
-    return Engine::memory_need(q);
+    return Engine::memory_need(q, rule);
   };
   std::unique_ptr<Engine> cached = pop_cached_engine(key);
-  if (cached && !(engine_cache_enabled() && cached->layout().d0 == ext[0] && cached->layout().d1 == ext[1] &&
-                  cached->layout().d2 == ext[2] && cached->num_views() == V))
-    cached.reset();  // wrong shape: free its memory before the free memory is read
+  if (cached && !reusable(*cached, ext, V))
+    cached.reset();  // wrong shape or rule: free its memory before the free memory is read
   size_t free_b = 0, total_b = 0;
   be::device_mem_info(&free_b, &total_b);
   size_t avail = free_b;
@@ -235,11 +250,8 @@ static std::unique_ptr<Engine> take_engine(int key, int dev, const shape_t& ext,
                                            const workspace& input, int mem_mode) {
   if (mem_mode != MVN_MEM_RESIDENT) return plan_engine(key, dev, ext, embed_floats, input, mem_mode);
   std::unique_ptr<Engine> e = pop_cached_engine(key);  // key = device + lane * kLaneStride
-  if (e && engine_cache_enabled()) {
-    const Layout& L = e->layout();
-    if (L.d0 == ext[0] && L.d1 == ext[1] && L.d2 == ext[2] && e->num_views() == V && e->streamed_count() == 0) return e;
-  }
-  e.reset();  // wrong shape: free its memory before the new engine allocates
+  if (e && reusable(*e, ext, V) && e->streamed_count() == 0) return e;
+  e.reset();  // wrong shape or rule: free its memory before the new engine allocates
   Layout L(ext[0], ext[1], ext[2]);
   const double need = ((4.0 * V + 3.0) * (double)L.B() + 4.0 * (double)embed_floats) * 1.02;
   size_t free_b = 0, total_b = 0;
@@ -494,9 +506,9 @@ static bool multi_device_call(imageType* psi, const workspace& input, const shap
 }
 
 // extents of the stacks, of the volume the call runs on (padding policy: see the block comment above good_extent())
-// and the stacks' offset inside it; dim0_kept_exact: dim0 was left at image + kernel - 1 for the direct dim0 leg
-static void call_extents(const workspace& input, int pad_mode, shape_t* dims_out, shape_t* ext_out, int off[3],
-                         bool* dim0_kept_exact_out) {
+// and the stacks' offset inside it; `dev`: the device the call runs on (call_rule)
+static void call_extents(const workspace& input, int pad_mode, int dev, shape_t* dims_out, shape_t* ext_out,
+                         int off[3]) {
   const int V = input.num_views_;
   const shape_t dims = to_shape(input.data_[0].image_dims_);
   for (int v = 0; v < V; ++v) {
@@ -510,7 +522,6 @@ static void call_extents(const workspace& input, int pad_mode, shape_t* dims_out
     if (dims[d] < 1) throw std::invalid_argument("image extents must be >= 1");
   shape_t ext = dims;  // padding policy: see the block comment above good_extent()
   off[0] = off[1] = off[2] = 0;
-  bool dim0_kept_exact = false;
   if (pad_mode != MVN_PAD_NONE) {
     for (int d = 2; d >= 0; --d) {
       int kmax = 1;
@@ -521,35 +532,22 @@ static void call_extents(const workspace& input, int pad_mode, shape_t* dims_out
       ext[d] = dims[d] + kmax - 1;
       off[d] = (kmax - 1) / 2;
       if (pad_mode != MVN_PAD_ZERO) continue;
-      // dim0 is not transformed when every PSF is thin enough for the direct dim0 leg (mvn_dim0_direct.hpp):
+      // dim0 is not transformed when every PSF of the call is held in the direct dim0 form (mvn_dim0_direct.hpp):
       // it then keeps the reference's exact image + kernel - 1 (542 planes for a 512-block with 31^3 PSFs, not
       // 576: 6 % less volume in every pass) - provided the rows of a plane keep whole tiles of the fixed
-      // last-axis kernels whatever the plane count (d1 a multiple of 16)
-      if (d == 0 && ext[1] % 16 == 0 && Engine::direct_ok_for(kmax, ext[0], ext[1], ext[2])) {
-        dim0_kept_exact = true;
-        continue;
-      }
+      // last-axis kernels whatever the plane count (d1 a multiple of 16).  The engine takes the same decision
+      // from the same rule, so it never holds a kernel of the call as a 3-D spectrum of an exact dim0 such as 542.
+      if (d == 0 && ext[1] % 16 == 0 && call_rule(ext, dev).all_direct(call_kernels(input))) continue;
       ext[d] = good_extent(ext[d], d == 2);
     }
   }
   *dims_out = dims;
   *ext_out = ext;
-  *dim0_kept_exact_out = dim0_kept_exact;
 }
 
 static size_t embed_floats_of(const shape_t& dims, const shape_t& ext) {
   const bool embedded = ext[0] != dims[0] || ext[1] != dims[1] || ext[2] != dims[2];
   return embedded ? (size_t)dims[0] * (size_t)dims[1] * (size_t)dims[2] : 0;
-}
-
-// the engine's own per-kernel decision (Engine::direct_form) taken before any engine exists: when a kernel would not
-// be held in the direct form, dim0 is padded like the other axes (see deconvolve_call)
-static bool all_direct_for(const shape_t& ext, const workspace& input) {
-  const Layout L(ext[0], ext[1], ext[2]);
-  for (int v = 0; v < input.num_views_; ++v)
-    if (!Engine::direct_form_for(L, input.data_[v].kernel1_dims_) || !Engine::direct_form_for(L, input.data_[v].kernel2_dims_))
-      return false;
-  return true;
 }
 
 static void deconvolve_call(imageType* psi, const workspace& input, int device, int lane, int pad_mode, double tol,
@@ -566,21 +564,19 @@ static void deconvolve_call(imageType* psi, const workspace& input, int device, 
     if (V == 0 || input.num_iterations_ <= 0) return;  // 0 iterations returns psi unchanged
     shape_t dims, ext;
     int off[3] = {0, 0, 0};
-    bool dim0_kept_exact = false;
-    call_extents(input, pad_mode, &dims, &ext, off, &dim0_kept_exact);
     if (lane == 0) {  // (the second lane belongs to the block pipeline of mvn_deconvolve_submit)
       const std::vector<int> devs = multi_devices_from_env();
       // the slab drivers keep no convergence statistics: such a call runs on one device
       if (!devs.empty() && tol >= 0. && trace_on())
         std::printf("[lmvn::trace] MVN_DEVICES: convergence statistics on - one device\n");
-      if (!devs.empty() && tol < 0. && multi_device_call(psi, input, dims, ext, off, pad_mode, devs)) return;
-    }
-    const int mem_mode = current_memory_mode();
-    if (mem_mode != MVN_MEM_RESIDENT && dim0_kept_exact && !all_direct_for(ext, input)) {
-      dim0_kept_exact = false;  // (decided before the planner prices the engine; the check below then agrees)
-      ext[0] = good_extent(ext[0], false);
+      if (!devs.empty() && tol < 0.) {
+        call_extents(input, pad_mode, -1, &dims, &ext, off);  // (the slabs run on plans of their own extents)
+        if (multi_device_call(psi, input, dims, ext, off, pad_mode, devs)) return;
+      }
     }
     const int dev = pick_device(device);
+    call_extents(input, pad_mode, dev, &dims, &ext, off);
+    const int mem_mode = current_memory_mode();
     const int key = dev + lane * kLaneStride;
     std::lock_guard<std::mutex> lk(device_mutex(key));
     be::set_device(dev);
@@ -588,21 +584,6 @@ static void deconvolve_call(imageType* psi, const workspace& input, int device, 
     // on failure the engine is simply dropped
     std::unique_ptr<Engine> eng_owner =
         take_engine(key, dev, ext, V, embedded ? (size_t)dims[0] * (size_t)dims[1] * (size_t)dims[2] : 0, input, mem_mode);
-    if (dim0_kept_exact) {
-      // The static rule above and the engine's own per-kernel decision (Engine::direct_form: also asks that the
-      // tap arrays' plan is of the volume plan's kernel family) must agree, or an exact dim0 such as 542 = 2 * 271
-      // would go through the chirp-z FFT leg: the engine has the last word, dim0 is then padded like the others.
-      bool all = true;
-      for (int v = 0; v < V && all; ++v)
-        all = eng_owner->would_be_direct(input.data_[v].kernel1_dims_) &&
-              eng_owner->would_be_direct(input.data_[v].kernel2_dims_);
-      if (!all) {
-        eng_owner.reset();
-        ext[0] = good_extent(ext[0], false);
-        if (trace_on()) std::printf("[lmvn::trace] direct dim0 leg refused by the engine: dim0 padded to %d\n", ext[0]);
-        eng_owner = take_engine(key, dev, ext, V, (size_t)dims[0] * (size_t)dims[1] * (size_t)dims[2], input, mem_mode);
-      }
-    }
     Engine& eng = *eng_owner;
     eng.begin_call();
     // stacks are embedded into / cropped out of the padded volume by the transfers themselves
@@ -638,19 +619,7 @@ static void deconvolve_call(imageType* psi, const workspace& input, int device, 
                   std::chrono::duration<double, std::milli>(t1 - t0).count());
       t0 = t1;
     };
-    eng.reserve_views();
-    {
-      // the loop starts before the last view has been staged: tell it now whether every kernel of the call
-      // will be held in the direct dim0 form (then the Nyquist bins ride in the DC column, mvn_dim0_direct.hpp)
-      bool all = true;
-      for (int v = 0; v < V && all; ++v)
-        all = eng.would_be_direct(input.data_[v].kernel1_dims_) && eng.would_be_direct(input.data_[v].kernel2_dims_);
-      eng.set_all_direct_hint(all);
-      bool lines = all;  // ... and through the fused middle pass (mvn_mid_fused.hpp)
-      for (int v = 0; v < V && lines; ++v)
-        lines = eng.would_be_lines(input.data_[v].kernel1_dims_) && eng.would_be_lines(input.data_[v].kernel2_dims_);
-      eng.set_all_lines_hint(lines);
-    }
+    eng.reserve_views(call_kernels(input));
     lap("allocate view buffers");
     std::unique_lock<std::mutex> pcie(upload_mutex(dev));  // handed to the uploader thread's scope below
     eng.set_psi(psi);
@@ -875,16 +844,14 @@ int mvn_deconvolve_memory(struct workspace input, int device, int streamed_views
     }
     if (streamed_views < 0 || streamed_views > input.num_views_)
       throw std::invalid_argument("streamed_views must be in [0, num_views_]");
-    pick_device(device);
+    const int dev = pick_device(device);
     shape_t dims, ext;
     int off[3];
-    bool dim0_kept_exact = false;
-    call_extents(input, current_pad_mode(), &dims, &ext, off, &dim0_kept_exact);
-    if (dim0_kept_exact && !all_direct_for(ext, input)) ext[0] = good_extent(ext[0], false);
+    call_extents(input, current_pad_mode(), dev, &dims, &ext, off);
     MemoryQuery q = memory_query(ext, input, embed_floats_of(dims, ext));
     q.streamed = streamed_views;
     q.ring = streamed_views > 0 ? 2 : 0;
-    *bytes = Engine::memory_need(q);
+    *bytes = Engine::memory_need(q, call_rule(ext, dev));
   });
 }
 

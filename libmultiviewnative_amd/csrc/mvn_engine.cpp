@@ -172,27 +172,83 @@ PassGeom Plan3D::pick_geom(int n, bool generic, bool rows, int max_t) {
   return g;
 }
 
-// which axes run the fixed-length kernels: known from the extents alone, and needed before the
-// axis plans are built (the fixed kernels have their own radix schedule, see AxisPlanHost::factorize)
-static bool fixed_allowed() { return env_int("MVN_NO_FIXED", 0) == 0; }
-static bool rows_fixed(const Layout& L) {
-  int T = 0, threads = 0;
-  size_t lds = 0;
-  return fixed_allowed() && L.even && fixed_rows_geom(L.h, &T, &threads, &lds) && L.rows % (size_t)T == 0;
-}
-static bool ax1_fixed(const Layout& L) {
-  int T = 0, threads = 0;
-  size_t lds = 0;
-  return fixed_allowed() && fixed_strided_geom(L.d1, &T, &threads, &lds) && L.C % T == 0;
-}
-static bool ax0_fixed(const Layout& L) {
-  int T = 0, threads = 0;
-  size_t lds = 0;
-  return fixed_allowed() && fixed_strided_geom(L.d0, &T, &threads, &lds) && ((long)L.d1 * L.C) % T == 0;
+// ---- the PSF form rule (mvn_engine.hpp) -------------------------------------------------------
+// MVN_DIM0_DIRECT_MAX: most PSF planes the direct dim0 leg takes on (MVN_D0_MAX_TAPS = 33 are instantiated);
+// measured at 512^3 x 6 views on MI355X (profiles/r03_dim0_direct.md) the whole iteration is 6.7 / 4.1 % faster
+// than with the fused FFT pass at 15 / 31 planes.  MVN_DIM0_DIRECT_MIN_PLANE: work items a launch should have
+// (columns are cut into pieces below that, default 131072); MVN_DIM0_DIRECT_MIN_ITEMS: fewest work items for which
+// the leg is used at all (default 0: it wins at every size measured, profiles/r03_shapes.txt - 32^3 0.098 -> 0.062
+// ms per view update, 128^3 0.132 -> 0.079, 256^3 0.311 -> 0.245, 512^3 2.31 -> 2.16, 1024^3 19.9 -> 17.4 - on
+// small volumes because the packed Nyquist layout it allows removes 6 of 14 launches).
+FormSwitches FormSwitches::from_env() {
+  FormSwitches sw;
+  sw.direct = env_int("MVN_DIM0_DIRECT", 1) != 0;
+  sw.direct_max = env_int("MVN_DIM0_DIRECT_MAX", MVN_D0_MAX_TAPS);
+  sw.min_plane = env_int("MVN_DIM0_DIRECT_MIN_PLANE", 131072);
+  sw.min_items = env_int("MVN_DIM0_DIRECT_MIN_ITEMS", 0);
+  sw.mid_fused = env_int("MVN_MID_FUSED", 1);
+  sw.fixed = env_int("MVN_NO_FIXED", 0) == 0;
+  return sw;
 }
 
-Plan3D::Plan3D(int dev, int d0, int d1, int d2)
-    : device(dev), L(d0, d1, d2), ax2(L.h, rows_fixed(L)), ax1(d1, ax1_fixed(L)), ax0(d0, ax0_fixed(L)) {
+bool rows_fixed(const Layout& L, bool fixed) {
+  int T = 0, threads = 0;
+  size_t lds = 0;
+  return fixed && L.even && fixed_rows_geom(L.h, &T, &threads, &lds) && L.rows % (size_t)T == 0;
+}
+bool ax1_fixed(const Layout& L, bool fixed) {
+  int T = 0, threads = 0;
+  size_t lds = 0;
+  return fixed && fixed_strided_geom(L.d1, &T, &threads, &lds) && L.C % T == 0;
+}
+bool ax0_fixed(const Layout& L, bool fixed) {
+  int T = 0, threads = 0;
+  size_t lds = 0;
+  return fixed && fixed_strided_geom(L.d0, &T, &threads, &lds) && ((long)L.d1 * L.C) % T == 0;
+}
+
+// (d1 = MF_N1 = 512 is a power of two: its dim1 transform is a plain radix one of length 512, never chirp-z)
+bool lines_capable(const Layout& L, bool fixed) {
+  int T = 0, threads = 0;
+  size_t lds = 0;
+  return rows_fixed(L, fixed) && fixed_rows_geom(L.h, &T, &threads, &lds) && T == 16 && L.h == 256 && L.C == 256 &&
+         L.d1 == MF_N1;
+}
+
+bool FormRule::direct(const int* kdims) const {
+  if (!sw.direct || kdims[0] > sw.direct_max || !mvn_dim0_direct_possible(kdims[0], L.d0) ||
+      mvn_dim0_items_for(kdims[0], L.d0, (long)L.d1 * L.C, sw.min_plane) < sw.min_items)
+    return false;
+  const Layout T(taps_depth(kdims[0]), L.d1, L.d2);  // (C, RP and parity: same d2 as L)
+  return rows_fixed(T, sw.fixed) == rows_fixed(L, plan_fixed) && ax1_fixed(T, sw.fixed) == ax1_fixed(L, plan_fixed);
+}
+
+bool FormRule::lines_taps(const int* kdims) const {
+  return sw.mid_fused != 0 && lines_capable(L, plan_fixed) && direct(kdims) &&
+         lines_capable(Layout(taps_depth(kdims[0]), L.d1, L.d2), sw.fixed) && mvn_dim0_taps_template(kdims[0]) <= 31;
+}
+
+// A whole column walks d0 + K - 1 steps for d0 outputs (the first K - 1 fill the filter's window).  Measured per view
+// update on (d0, 512, 512) volumes (tools/mid_fused_planes.py, profiles/r04_mid_fused.md): with 31-plane PSFs the two
+// forms meet at 96 - 128 planes (48: +10 %, 256: -15 %, 512: -18 %), with 15 planes the fused pass is ahead from 32
+// planes on (-2 %; 256: -24 %), with 5 planes always (-12 .. -30 %): three PSF depths of planes.
+bool FormRule::lines_worth(int k0) const { return sw.mid_fused >= 2 || L.d0 >= 3 * k0; }
+
+bool FormRule::all_direct(const kernel_list_t& k) const {
+  for (const std::array<int, 3>& d : k)
+    if (!direct(d.data())) return false;
+  return true;
+}
+
+bool FormRule::all_lines(const kernel_list_t& k) const {
+  for (const std::array<int, 3>& d : k)
+    if (!lines(d.data())) return false;
+  return true;
+}
+
+Plan3D::Plan3D(int dev, int d0, int d1, int d2, bool fixed_allowed)
+    : device(dev), L(d0, d1, d2), fixed(fixed_allowed), ax2(L.h, rows_fixed(L, fixed)), ax1(d1, ax1_fixed(L, fixed)),
+      ax0(d0, ax0_fixed(L, fixed)) {
   // the word an epilogue that follows no direct dim0 leg compares with (EpilogueParams::poison is never null
   // on the device): zero, against the epoch 0xffffffff no leg ever has
   no_poison = (unsigned*)be::dmalloc(64);
@@ -221,21 +277,21 @@ Plan3D::Plan3D(int dev, int d0, int d1, int d2)
   {
     int T = 0, threads = 0;
     size_t lds = 0;
-    if (rows_fixed(L)) {
+    if (rows_fixed(L, fixed)) {
       fixed_rows_geom(L.h, &T, &threads, &lds);
       fx_rows = true;
       gx_rows.T = T;
       gx_rows.threads = threads;
       gx_rows.lds_bytes = lds;
     }
-    if (ax1_fixed(L)) {
+    if (ax1_fixed(L, fixed)) {
       fixed_strided_geom(d1, &T, &threads, &lds);
       fx_ax1 = true;
       gx_ax1.T = gx_ax1.TP = T;
       gx_ax1.threads = threads;
       gx_ax1.lds_bytes = lds;
     }
-    if (ax0_fixed(L)) {
+    if (ax0_fixed(L, fixed)) {
       fixed_strided_geom(d0, &T, &threads, &lds);
       fx_ax0 = true;
       gx_ax0.T = gx_ax0.TP = T;
@@ -417,11 +473,6 @@ void Plan3D::rows_c2r_r2c(cfloat* data, cfloat* nyq, const EpilogueParams& epi_a
   p.Cmul = mvn_fastdiv_mul((unsigned)L.C);
   const long ntiles = (R + p.T - 1) / p.T;
   be::launch_rows_c2r_r2c(p, ntiles, g_rows.threads, g_rows.lds_bytes, s);
-}
-
-bool Plan3D::lines_capable() const {
-  return fx_rows && L.even && L.h == 256 && L.C == 256 && L.d1 == MF_N1 && gx_rows.T == 16 && !ax1.host.bluestein &&
-         ax1.host.nfft == MF_N1;
 }
 
 void Plan3D::mid_fused(const cfloat* in, cfloat* out, const cfloat* taps, int k, int kd, unsigned* poison,
@@ -652,7 +703,7 @@ std::shared_ptr<Plan3D> PlanStore::add(int device, const shape_t& shape) {
   if (it != plans_.end()) return it->second;
   const int prev = be::get_device();
   be::set_device(device);
-  std::shared_ptr<Plan3D> p(new Plan3D(device, shape[0], shape[1], shape[2]));
+  std::shared_ptr<Plan3D> p(new Plan3D(device, shape[0], shape[1], shape[2], FormSwitches::from_env().fixed));
   be::set_device(prev);
   plans_[key] = p;
   return p;
@@ -670,6 +721,12 @@ std::shared_ptr<Plan3D> PlanStore::lookup(int device, const shape_t& shape) {
     throw std::runtime_error("mvn::PlanStore: no plan for " + std::to_string(shape[0]) + "x" +
                              std::to_string(shape[1]) + "x" + std::to_string(shape[2]));
   return it->second;
+}
+
+std::shared_ptr<Plan3D> PlanStore::find(int device, const shape_t& shape) {
+  std::lock_guard<std::mutex> lk(mu_);
+  auto it = plans_.find(plan_key(device, shape));
+  return it == plans_.end() ? nullptr : it->second;
 }
 
 bool PlanStore::empty() {
@@ -710,17 +767,9 @@ Engine::Engine(int device, const shape_t& dims, int num_views) : device_(device)
   views_.resize((size_t)num_views);
   stream_pos_.assign((size_t)num_views, -1);
   spec_tiled_ = plan_->tiles_spectra();
-  // read per engine (tests).  MVN_DIM0_DIRECT_MAX: most PSF planes the direct dim0 leg takes on
-  // (MVN_D0_MAX_TAPS = 33 are instantiated); measured at 512^3 x 6 views on MI355X (profiles/r03_dim0_direct.md)
-  // the whole iteration is 6.7 / 4.1 % faster than with the fused FFT pass at 15 / 31 planes
-  direct_enabled_ = env_int("MVN_DIM0_DIRECT", 1) != 0;
-  lines_capable_ = plan_->lines_capable() && env_int("MVN_MID_FUSED", 1) != 0;
-  lines_forced_ = env_int("MVN_MID_FUSED", 1) >= 2;
-  direct_max_taps_ = env_int("MVN_DIM0_DIRECT_MAX", MVN_D0_MAX_TAPS);
-  direct_min_plane_ = env_int("MVN_DIM0_DIRECT_MIN_PLANE", 131072);  // see direct_ok_for()
-  direct_min_items_ = env_int("MVN_DIM0_DIRECT_MIN_ITEMS", 0);
+  sw_ = FormSwitches::from_env();  // read per engine (tests)
   d0_stagger_ = env_int("MVN_D0_STAGGER", 64);
-  packed_allowed_ = packed_layout_for(plan_->main_bytes()) && mvn_dim0_packed_possible(dims[0]);
+  packed_allowed_ = packed_default_ = packed_layout_for(plan_->main_bytes()) && mvn_dim0_packed_possible(dims[0]);
   for (int d = 0; d < 3; ++d) host_dims_[d] = dims[d];
   be::stream_sync(stream_);
 }
@@ -891,23 +940,11 @@ void Engine::make_spectrum(const float* d_kernel, const int* kdims, float scale,
   plan_->retile_spectrum((const cfloat*)scratch, (cfloat*)spec, s);
 }
 
-// The dim0 leg runs as a direct convolution when the PSF has at most MVN_D0_MAX_TAPS planes, the volume is
-// deep enough for the kernel's window, and the small plan of the tap arrays transforms dims 1 and 2
-// exactly as the volume's plan does (same kernel family => same position order of the spectra).
-bool Engine::direct_form(const int* kdims) {
-  if (!direct_enabled_ || kdims[0] > direct_max_taps_ || !mvn_dim0_direct_possible(kdims[0], plan_->L.d0) ||
-      mvn_dim0_items_for(kdims[0], plan_->L.d0, (long)plan_->L.d1 * plan_->L.C, direct_min_plane_) < direct_min_items_)
-    return false;
-  const int kd = ((kdims[0] + 1 + 15) / 16) * 16;
-  const Plan3D* tp = taps_plan(kd);
-  return tp->fx_rows == plan_->fx_rows && tp->fx_ax1 == plan_->fx_ax1 && tp->L.C == plan_->L.C &&
-         tp->L.RP == plan_->L.RP && tp->L.even == plan_->L.even;
-}
-
+// the (kd, d1, d2) plan of the tap arrays, built with the engine's switches (FormRule::direct)
 Plan3D* Engine::taps_plan(int kd) {
   auto it = taps_plans_.find(kd);
   if (it != taps_plans_.end()) return it->second.get();
-  std::unique_ptr<Plan3D> p(new Plan3D(device_, kd, plan_->L.d1, plan_->L.d2));
+  std::unique_ptr<Plan3D> p(new Plan3D(device_, kd, plan_->L.d1, plan_->L.d2, sw_.fixed));
   Plan3D* raw = p.get();
   taps_plans_[kd] = std::move(p);
   return raw;
@@ -921,8 +958,9 @@ void Engine::prepare_psf(ViewSlot& s, int i, const float* d_kernel, const int* k
     if (kdims[d] < 1 || kdims[d] > D) throw std::invalid_argument("mvn: kernel extent must be in [1, image extent]");
   }
   ++graph_gen_;  // a captured sweep holds the PSF buffers, their form and depth
-  if (direct_form(kdims)) {
-    const int kd = ((kdims[0] + 1 + 15) / 16) * 16;
+  const FormRule rule = form_rule();
+  if (rule.direct(kdims)) {
+    const int kd = taps_depth(kdims[0]);
     Plan3D* tp = taps_plan(kd);
     if (s.tap_kd[i] != kd) {  // (re)allocate for this depth; the previous arrays may still be read by the stream
       be::stream_sync(st);
@@ -945,8 +983,9 @@ void Engine::prepare_psf(ViewSlot& s, int i, const float* d_kernel, const int* k
     be::launch_scatter_psf(d_kernel, kdims[0], kdims[1], kdims[2], s.taps[i], kd, L.d1, L.d2, tp->L.RP, scale, st);
     tp->rows_r2c(s.taps[i], (cfloat*)s.taps[i], s.taps_nyq[i], st, nullptr);
     tp->axis1(MVN_ST_FWD, (cfloat*)s.taps[i], s.taps_nyq[i], st, nullptr);
-    if (lines_capable_ && tp->lines_capable() && mvn_dim0_taps_template(kdims[0]) <= 31) {
+    if (rule.lines_taps(kdims)) {
       // the same planes for the fused middle pass: line layout, Nyquist bins packed, its own bin order along dim1
+      // (wherever the kernel could take the pass: decide_lines() asks whether it is worth it)
       if (!s.taps_l[i]) s.taps_l[i] = (float*)be::dmalloc(tp->main_bytes());
       if (taps_scr_bytes_ < tp->main_bytes()) {  // one scratch per engine, as large as the deepest tap array
         be::stream_sync(st);
@@ -1014,7 +1053,7 @@ void Engine::dim0_conv(const ViewSlot& s, int i, const cfloat* in, const cfloat*
   p.stagger = d0_stagger_;
   p.zbeg = zbeg;
   p.zcount = zcount;
-  p.seg1 = mvn_dim0_piece_len(p.k, zcount > 0 ? zcount : L.d0, p.plane, direct_min_plane_);
+  p.seg1 = mvn_dim0_piece_len(p.k, zcount > 0 ? zcount : L.d0, p.plane, sw_.min_plane);
   p.C = L.C;
   p.d1 = L.d1;
   // non-finite inputs are reported under this leg's epoch (never 0, never a value the word may still hold); the
@@ -1110,26 +1149,13 @@ void Engine::decide_layout() {
   lines_ = false;  // (only the sequential sweep asks for the line layout: decide_lines())
 }
 
-bool Engine::would_be_direct(const int* kdims) { return direct_form(kdims); }
-
-// A whole column walks d0 + K - 1 steps for d0 outputs (the first K - 1 fill the filter's window).  Measured per view
-// update on (d0, 512, 512) volumes (tools/mid_fused_planes.py, profiles/r04_mid_fused.md): with 31-plane PSFs the two
-// forms meet at 96 - 128 planes (48: +10 %, 256: -15 %, 512: -18 %), with 15 planes the fused pass is ahead from 32
-// planes on (-2 %; 256: -24 %), with 5 planes always (-12 .. -30 %): three PSF depths of planes.
-// MVN_MID_FUSED=2 takes the fused pass whenever the shape has it (tests).
-bool Engine::lines_worth(int k0) const { return lines_forced_ || plan_->L.d0 >= 3 * k0; }
-
-bool Engine::would_be_lines(const int* kdims) {
-  return lines_capable_ && lines_worth(kdims[0]) && direct_form(kdims) && mvn_dim0_taps_template(kdims[0]) <= 31 &&
-         taps_plan(((kdims[0] + 1 + 15) / 16) * 16)->lines_capable();
-}
-
 // The sequential sweep takes the fused middle pass when the shape has it, every kernel is held in the form it
 // reads and nothing else lays claim to the layout of the work volumes (halo exchanges copy planes of the row-major
 // spectrum).  Decided per iterate() call, behind decide_layout().
 void Engine::decide_lines() {
   const bool was = lines_last_sweep_;
-  bool all = lines_capable_ && !views_.empty();
+  const FormRule rule = form_rule();
+  bool all = rule.sw.mid_fused != 0 && plan_->lines_capable() && !views_.empty();
   if (halo_fn_ || halo_planes_ > 0)  // slabs: the common decision of whoever drives them, on plane ranges
     all = all && halo_fn_ && lines_override_ == 1 && halo_ranged() && halo_nyq_aware_;
   if (all) {
@@ -1138,7 +1164,7 @@ void Engine::decide_lines() {
     } else {
       for (size_t v = 0; v < views_.size() && all; ++v)
         all = views_[v].set && views_[v].tap_k[0] && views_[v].tap_k[1] && views_[v].taps_l_ok[0] && views_[v].taps_l_ok[1] &&
-              lines_worth(views_[v].tap_k[0]) && lines_worth(views_[v].tap_k[1]);
+              rule.lines_worth(views_[v].tap_k[0]) && rule.lines_worth(views_[v].tap_k[1]);
     }
   }
   lines_ = lines_last_sweep_ = all;
@@ -1159,20 +1185,6 @@ void Engine::mid_fused_conv(const ViewSlot& s, int i, Profiler* prof, int zbeg, 
                    poison_table(epoch_));
   std::swap(work_, work2_);
   std::swap(work_nyq_, work2_nyq_);
-}
-
-// Is the direct dim0 leg to be used for PSFs of k0 planes on a (d0, d1, d2) volume?  Switches: MVN_DIM0_DIRECT,
-// MVN_DIM0_DIRECT_MAX (deepest PSF, <= 33), MVN_DIM0_DIRECT_MIN_PLANE (work items a launch should have: columns
-// are cut into pieces below that, default 131072) and MVN_DIM0_DIRECT_MIN_ITEMS (fewest work items for which the
-// leg is used at all, default 0: it wins at every size measured, profiles/r03_shapes.txt - 32^3 0.098 -> 0.062 ms
-// per view update, 128^3 0.132 -> 0.079, 256^3 0.311 -> 0.245, 512^3 2.31 -> 2.16, 1024^3 19.9 -> 17.4 - on small
-// volumes because the packed Nyquist layout it allows removes 6 of 14 launches).
-bool Engine::direct_ok_for(int k0, int d0, int d1, int d2) {
-  const long plane = (long)d1 * (d2 % 2 == 0 ? d2 / 2 : (d2 + 1) / 2);
-  return env_int("MVN_DIM0_DIRECT", 1) != 0 && k0 >= 1 && k0 <= env_int("MVN_DIM0_DIRECT_MAX", MVN_D0_MAX_TAPS) &&
-         mvn_dim0_direct_possible(k0, d0) &&
-         mvn_dim0_items_for(k0, d0, plane, (long)env_int("MVN_DIM0_DIRECT_MIN_PLANE", 131072)) >=
-             (long)env_int("MVN_DIM0_DIRECT_MIN_ITEMS", 0);
 }
 
 void Engine::middle(const ViewSlot& s, int i, Profiler* prof, SideStream* side, const RowsProducer* produce) {
@@ -1346,10 +1358,10 @@ void Engine::set_view(int v, const float* image, const float* weights, const flo
 }
 
 // ---- pipelined staging ------------------------------------------------------------------------
-void Engine::reserve_views() {
+void Engine::reserve_views(const kernel_list_t& kernels) {
   be::set_device(device_);
   for (size_t v = 0; v < views_.size(); ++v) alloc_view(views_[v]);
-  if (direct_enabled_) ensure_work2();  // (not inside the first sweep: the direct dim0 leg is out of place)
+  if (sw_.direct) ensure_work2();  // (not inside the first sweep: the direct dim0 leg is out of place)
   if (!upload_stream_) upload_stream_ = be::stream_create_upload();
   staged_ev_.resize(views_.size(), nullptr);
   for (size_t v = 0; v < views_.size(); ++v)
@@ -1361,6 +1373,11 @@ void Engine::reserve_views() {
     stream_abort_ = false;
     stream_done_ = false;
   }
+  // the loop starts before the last view has been staged: will every kernel of the call be held in the direct dim0
+  // form (then the Nyquist bins ride in the DC column) and take the fused middle pass?
+  const FormRule rule = form_rule();
+  packed_hint_ = rule.all_direct(kernels);
+  lines_hint_ = rule.all_lines(kernels);
   pipelined_ = true;
 }
 
@@ -1544,32 +1561,12 @@ void Engine::ring_release(ViewSlot& s) {
 static const size_t kMemSlack = (size_t)1 << 20;
 static size_t alloc_rounded(size_t b) { return (b + 4095) & ~(size_t)4095; }
 
-// Plan3D::lines_capable() of a plan of layout L, from the same host-side decisions and without its device tables
-static bool lines_capable_for(const Layout& L) {
-  if (!rows_fixed(L)) return false;
-  int T = 0, threads = 0;
-  size_t lds = 0;
-  fixed_rows_geom(L.h, &T, &threads, &lds);
-  if (!(L.even && L.h == 256 && L.C == 256 && L.d1 == MF_N1 && T == 16)) return false;
-  const AxisPlanHost ax1(L.d1, ax1_fixed(L));
-  return !ax1.bluestein && ax1.nfft == MF_N1;
-}
-
-bool Engine::direct_form_for(const Layout& L, const int* kdims) {
-  if (env_int("MVN_DIM0_DIRECT", 1) == 0 || kdims[0] > env_int("MVN_DIM0_DIRECT_MAX", MVN_D0_MAX_TAPS) ||
-      !mvn_dim0_direct_possible(kdims[0], L.d0) ||
-      mvn_dim0_items_for(kdims[0], L.d0, (long)L.d1 * L.C, env_int("MVN_DIM0_DIRECT_MIN_PLANE", 131072)) <
-          env_int("MVN_DIM0_DIRECT_MIN_ITEMS", 0))
-    return false;
-  const Layout T(((kdims[0] + 1 + 15) / 16) * 16, L.d1, L.d2);  // (C, RP and parity: same d2 as L)
-  return rows_fixed(T) == rows_fixed(L) && ax1_fixed(T) == ax1_fixed(L);
-}
-
 // Every workgroup of an update pass writes one record, and no launch has more workgroups than the volume has rows.
 static long stats_cap(const Layout& L) { return (long)L.rows; }
 
-size_t Engine::memory_need(const MemoryQuery& q) {
-  const Layout L(q.ext[0], q.ext[1], q.ext[2]);
+size_t Engine::memory_need(const MemoryQuery& q, const FormRule& rule) {
+  const Layout& L = rule.L;
+  if (L.d0 != q.ext[0] || L.d1 != q.ext[1] || L.d2 != q.ext[2]) throw std::logic_error("mvn: memory query of other extents");
   const int V = (int)(q.kernels.size() / 2);
   if (q.kernels.size() % 2 || q.streamed < 0 || q.streamed > V || q.ring < 0 || q.ring > 2 ||
       (q.streamed > 0) != (q.ring > 0))
@@ -1581,21 +1578,20 @@ size_t Engine::memory_need(const MemoryQuery& q) {
   };
   add(mb, 1);                                     // psi
   add(mb, 1), add(nb, 1);                         // work volume
-  if (env_int("MVN_DIM0_DIRECT", 1) != 0) add(mb, 1), add(nb, 1);  // second work volume (reserve_views)
+  if (rule.sw.direct) add(mb, 1), add(nb, 1);      // second work volume (reserve_views)
   add(256, 1);                                    // poison words
   add(q.embed_floats * sizeof(float), 1);         // embedding scratch of the padded policies
   add(mb, 2 * (size_t)(V - q.streamed));          // image + weights of the resident views
   add(mb, 2 * (size_t)q.ring);                    // ring slots of the streamed ones
-  const bool lines = lines_capable_for(L) && env_int("MVN_MID_FUSED", 1) != 0;
   size_t scr = 0;
   bool spectra = false;
   for (const std::array<int, 3>& k : q.kernels) {
     add(sizeof(float) * (size_t)k[0] * k[1] * k[2], 1);  // the kernel's device copy, until staging has drained
-    if (direct_form_for(L, k.data())) {
-      const Layout T(((k[0] + 1 + 15) / 16) * 16, L.d1, L.d2);
+    if (rule.direct(k.data())) {
+      const Layout T(taps_depth(k[0]), L.d1, L.d2);
       const size_t tb = T.real_floats() * sizeof(float);
       add(tb, 1), add(T.nyq_cplx() * sizeof(cfloat), 1);  // taps
-      if (lines && lines_capable_for(T) && mvn_dim0_taps_template(k[0]) <= 31) {
+      if (rule.lines_taps(k.data())) {
         add(tb, 1);  // the fused middle pass's taps
         scr = std::max(scr, tb);
       }
@@ -1605,7 +1601,7 @@ size_t Engine::memory_need(const MemoryQuery& q) {
     }
   }
   add(scr, 1);                                        // the engine's one tap scratch
-  if (spectra && ax0_fixed(L)) add(mb, 1);            // re-tiling scratch of the staging thread
+  if (spectra && ax0_fixed(L, rule.plan_fixed)) add(mb, 1);  // re-tiling scratch of the staging thread
   if (q.stats_rows > 0) {  // convergence statistics (Engine::iterate)
     add(3 * sizeof(double) * (size_t)stats_cap(L) * (size_t)V, 1);
     add(sizeof(unsigned) * (size_t)V, 1);
@@ -1950,9 +1946,12 @@ void Engine::set_halo_hook(halo_fn_t fn, void* user, bool drain, bool post) {
   halo_user_ = user;
   halo_drain_ = drain;
   halo_post_ = post && fn;
-  if (!fn) {
+  if (!fn) {  // back to the engine's own decisions
     halo_planes_ = 0;
     halo_split_ = false;
+    layout_override_ = -1;
+    lines_override_ = -1;
+    packed_allowed_ = packed_default_;
   }
 }
 

@@ -88,6 +88,61 @@ struct PassGeom {
 };
 
 typedef std::array<int, 3> shape_t;
+typedef std::vector<std::array<int, 3>> kernel_list_t;  // the kernel extents of a call: kernel1, kernel2 of every view
+
+// ---------------------------------------------------------------------------------------------
+// The PSF form rule.  Every kernel is held in one form: the direct dim0 form (taps along dim0, no dim0 transform,
+// mvn_dim0_direct.hpp) or the 3-D spectrum.  The forms of a call's kernels decide whether the sequential sweep takes
+// the fused middle pass (mvn_mid_fused.hpp), whether the Nyquist bins are packed into the DC column, and under the
+// zero padding policy whether dim0 keeps the exact extent image + kernel - 1 (mvn_abi.cpp).  The rule needs no
+// device and no plan, so the ABI can apply it before an engine exists; an engine applies it to its own plan.
+// ---------------------------------------------------------------------------------------------
+struct FormSwitches {
+  bool direct = true;                // MVN_DIM0_DIRECT (0: never the direct form)
+  int direct_max = MVN_D0_MAX_TAPS;  // MVN_DIM0_DIRECT_MAX: most PSF planes of the direct form
+  long min_plane = 131072;           // MVN_DIM0_DIRECT_MIN_PLANE: work items a launch of the leg should have
+  long min_items = 0;                // MVN_DIM0_DIRECT_MIN_ITEMS: fewest work items for which the leg is used at all
+  int mid_fused = 1;                 // MVN_MID_FUSED: 0 never, 1 where it is worth it, 2 whenever the shape has it
+  bool fixed = true;                 // MVN_NO_FIXED unset or 0: plans use the fixed-length kernels where they can
+  static FormSwitches from_env();    // read once per engine and once per ABI call (tests change them in between)
+  bool operator==(const FormSwitches& o) const {
+    return direct == o.direct && direct_max == o.direct_max && min_plane == o.min_plane && min_items == o.min_items &&
+           mid_fused == o.mid_fused && fixed == o.fixed;
+  }
+};
+
+// Which axes of a plan of layout L run the fixed-length kernels (mvn_fixed.hpp), `fixed` being the switch the plan
+// is built with.  Known from the extents alone, and needed before the axis plans are built (the fixed kernels have
+// their own radix schedule, see AxisPlanHost::factorize).
+bool rows_fixed(const Layout& L, bool fixed);
+bool ax1_fixed(const Layout& L, bool fixed);
+bool ax0_fixed(const Layout& L, bool fixed);
+// a plan of layout L has the line-layout forms of the last-axis kernels and the fused middle pass (d1 = d2 = 512)
+bool lines_capable(const Layout& L, bool fixed);
+// planes of the tap arrays of a PSF of k0 planes
+inline int taps_depth(int k0) { return ((k0 + 1 + 15) / 16) * 16; }
+
+// The rule for a volume of layout L whose plan was built with the fixed-length switch `plan_fixed` (a plan in the
+// store keeps the switch of its construction; the tap arrays' plans take sw.fixed).
+struct FormRule {
+  Layout L;
+  FormSwitches sw;
+  bool plan_fixed;
+  FormRule(const Layout& layout, const FormSwitches& s, bool pf) : L(layout), sw(s), plan_fixed(pf) {}
+  // The direct dim0 form: the PSF has at most direct_max planes, the volume is deep enough for the kernel's window
+  // and has enough work items, and the tap arrays' plan transforms dims 1 and 2 with the volume plan's kernel family
+  // (same family => same position order of the spectra).
+  bool direct(const int* kdims) const;
+  // the direct form plus the taps of the fused middle pass: wherever the pass COULD run, worth it or not
+  bool lines_taps(const int* kdims) const;
+  // the fused middle pass is worth it for a PSF of k0 planes (or forced, MVN_MID_FUSED=2)
+  bool lines_worth(int k0) const;
+  // the kernel takes the fused middle pass
+  bool lines(const int* kdims) const { return lines_taps(kdims) && lines_worth(kdims[0]); }
+  // every kernel of a call is held in the direct form / takes the fused middle pass
+  bool all_direct(const kernel_list_t& k) const;
+  bool all_lines(const kernel_list_t& k) const;
+};
 
 // a second stream plus the two events used to fork it from / join it to the main stream
 struct SideStream {
@@ -104,6 +159,7 @@ class Plan3D {
  public:
   const int device;
   const Layout L;
+  const bool fixed;  // built with the fixed-length kernels allowed (FormSwitches::fixed)
   DevAxis ax2, ax1, ax0;
   cfloat* twr = nullptr;  // d2-th roots of unity (even d2)
   unsigned* no_poison = nullptr;  // a zero word: what EpilogueParams::poison points to after an FFT dim0 leg
@@ -115,7 +171,7 @@ class Plan3D {
   bool nyq_rides() const { return fx_ax1; }
   PassGeom gx_rows, gx_ax1, gx_ax0;
 
-  Plan3D(int device, int d0, int d1, int d2);
+  Plan3D(int device, int d0, int d1, int d2, bool fixed);
   ~Plan3D();
 
   size_t main_bytes() const { return L.real_floats() * sizeof(float); }
@@ -134,8 +190,7 @@ class Plan3D {
   void rows_c2r(const cfloat* in, const cfloat* in_nyq, float* out_real,
                 const EpilogueParams& epi, be::stream_t s, Profiler* prof = nullptr,
                 long row0 = 0, long nrows = -1, bool lines = false, const MvnStatsParams* st = nullptr) const;
-  // the shape has the line-layout forms of the last-axis kernels and the fused middle pass (d1 = d2 = 512)
-  bool lines_capable() const;
+  bool lines_capable() const { return mvn::lines_capable(L, fixed); }
   // dim1 forward + K-tap direct convolution along dim0 + dim1 inverse, `in` -> `out` (both in the line layout);
   // taps: [kd][C][d1] as prepared by taps_to_lines()
   // zcount > 0: the output planes [zbeg, zbeg + zcount) only (slabs with halo planes); peers: further poison words
@@ -204,6 +259,7 @@ class PlanStore {
   bool has_key(int device, const shape_t& shape);
   // throws std::runtime_error on a miss, like the reference (inc/plan_store.cuh:140-152)
   std::shared_ptr<Plan3D> lookup(int device, const shape_t& shape);
+  std::shared_ptr<Plan3D> find(int device, const shape_t& shape);  // nullptr on a miss
   bool empty();
   size_t size();
   void clear();
@@ -244,7 +300,7 @@ struct ViewSlot {
 // rotate through.
 struct MemoryQuery {
   shape_t ext = {{0, 0, 0}};
-  std::vector<std::array<int, 3>> kernels;  // 2 per view: kernel1, kernel2
+  kernel_list_t kernels;  // 2 per view: kernel1, kernel2
   size_t embed_floats = 0;
   int streamed = 0;
   int ring = 0;
@@ -277,11 +333,9 @@ class Engine {
   // main thread after an error: wake an uploader that waits for a ring slot
   void abort_streaming();
   // Bytes the ABI call described by q allocates on a new engine of extents q.ext, allocating nothing itself: the
-  // same PSF form decisions (direct taps, fused-pass taps, 3-D spectra) the engine will take, plus a small slack for
+  // PSF forms (direct taps, fused-pass taps, 3-D spectra) that `rule` gives for its kernels, plus a small slack for
   // plan tables and allocator rounding.  The single source of truth of the memory planner (mvn_abi.cpp).
-  static size_t memory_need(const MemoryQuery& q);
-  // direct_form() for an engine of layout L that does not exist yet: same switches, no plans built
-  static bool direct_form_for(const Layout& L, const int* kdims);
+  static size_t memory_need(const MemoryQuery& q, const FormRule& rule);
   // calls that streamed views, streamed view updates, bytes streamed (host -> device), since process start
   static void stream_counters(long long out[3]);
   static void count_streamed_call();
@@ -295,11 +349,13 @@ class Engine {
   // Pipelined staging for the blocking ABI call (what the reference's "interleaved" driver was
   // after, src/gpu_deconvolve_methods.cuh:82-326): a second host thread uploads view after view
   // on its own stream while the first RL iteration already runs on the views that have arrived.
-  //   reserve_views()            main thread: allocate every view's buffers up front
+  //   reserve_views(kernels)     main thread: allocate every view's buffers up front; from the call's kernel
+  //                              extents, decide whether the loop starts on the packed Nyquist layout and the fused
+  //                              middle pass before the last view has been staged
   //   stage_view(v, ...)         uploader thread: H2D + PSF spectra of view v on the upload stream
   //   staging_failed()           uploader thread: wake the main thread up after an error
   //   iterate(...)               main thread: waits for view v only before its first use
-  void reserve_views();
+  void reserve_views(const kernel_list_t& kernels);
   void stage_view(int v, const float* image, const float* weights, const float* kernel1,
                   const int* k1dims, const float* kernel2, const int* k2dims);
   void staging_failed();
@@ -390,18 +446,12 @@ class Engine {
   void set_embedding(const int dims[3], const int off[3]);
   // quotient 0 wherever the view is exactly 0 (see EpilogueParams::guard_zero_view)
   void set_quotient_guard(bool on) { quotient_guard_ = on; }
-  // pipelined ABI call: will a kernel of these extents be held in the direct dim0 form? / every kernel of the
-  // call will (so the loop may start on the packed Nyquist layout before the last view has been staged)
-  bool would_be_direct(const int* kdims);
-  // the direct dim0 leg is enabled and is the better leg for PSFs of this depth on a volume of these extents
-  static bool direct_ok_for(int k0, int d0, int d1, int d2);
+  // the PSF form rule on this engine's plan, with the switches read when the engine was built
+  FormRule form_rule() const { return FormRule(plan_->L, sw_, plan_->fixed); }
+  // will a kernel of these extents be held in the direct dim0 form?
+  bool would_be_direct(const int* kdims) const { return form_rule().direct(kdims); }
   // does a volume of this size keep its Nyquist bins packed in the DC column (when every PSF is in the direct form)?
   static bool packed_layout_for(size_t volume_bytes);
-  void set_all_direct_hint(bool all) { packed_hint_ = all; }
-  // the fused middle pass (mvn_mid_fused.hpp): will a kernel of these extents run through it? / every kernel of
-  // the call will (pipelined calls: the loop starts before the last view has been staged)
-  bool would_be_lines(const int* kdims);
-  void set_all_lines_hint(bool all) { lines_hint_ = all; }
   // Halo mode (slabs of one volume): the slabs must all run the same middle - they exchange planes of its input -, so
   // whoever drives them decides for all of them (mvn_multi.cpp): on = the fused middle pass where this slab has it.
   // A hook set without this call keeps the three passes.
@@ -436,12 +486,11 @@ class Engine {
   void make_spectrum(const float* d_kernel, const int* kdims, float scale, float* spec, cfloat* nyq,
                      float* scratch, be::stream_t s);
   // Kernel i of slot s from its device-resident copy: the direct dim0 form (taps) where the PSF is thin
-  // enough along dim0 (direct_form), the 3-D spectrum otherwise; buffers are allocated on first use.
+  // enough along dim0 (FormRule::direct), the 3-D spectrum otherwise; buffers are allocated on first use.
   // `scratch` (one volume, or nullptr = allocate one with the staging scratch) serves the re-tiling of a
   // 3-D spectrum.
   void prepare_psf(ViewSlot& s, int i, const float* d_kernel, const int* kdims, float* scratch, bool staging,
                    be::stream_t st);
-  bool direct_form(const int* kdims);
   Plan3D* taps_plan(int kd);
   // scattered PSF planes the last-axis pass of the fused-pass taps reads (it cannot run in place into the line
   // layout): one buffer per engine, read only by prepare_psf's launches on the stream that prepares
@@ -467,12 +516,11 @@ class Engine {
   cfloat* wn() const { return packed_ ? nullptr : work_nyq_; }
   cfloat* pn() const { return packed_ ? nullptr : psi_spec_nyq_; }
   bool packed_ = false, packed_hint_ = false, packed_allowed_ = true;
+  bool packed_default_ = true;  // packed_allowed_ as the constructor decided it (a removed halo hook restores it)
   // the loops run their convolutions as last-axis pass -> fused middle pass -> last-axis pass on the line layout
   // (decided per iterate() call / per simultaneous step; halo and slab modes keep the three-pass middle)
-  bool lines_capable_ = false, lines_ = false, lines_hint_ = false, lines_last_sweep_ = false;
+  bool lines_ = false, lines_hint_ = false, lines_last_sweep_ = false;
   bool psi_spec_lines_ = false;  // the shared spectrum of psi (simultaneous steps) is in the line layout
-  bool lines_forced_ = false;    // MVN_MID_FUSED=2: whenever the shape has the pass, however few planes
-  bool lines_worth(int k0) const;
   void decide_lines();
   void mid_fused_conv(const ViewSlot& s, int i, Profiler* prof, int zbeg = 0, int zcount = 0);
   int lines_override_ = -1;  // halo mode: -1 = three-pass middle (a hook of unknown kind), 0 / 1 = the slabs' common decision
@@ -498,10 +546,8 @@ class Engine {
   unsigned armed_epoch_ = 0;  // != 0: the convolution in flight ran a direct leg with this epoch
   // hands the report of the convolution's direct leg (if it had one) to the last-axis pass that ends it
   void arm(EpilogueParams& e);
-  bool direct_enabled_ = true;
+  FormSwitches sw_;
   int d0_stagger_ = 0;
-  int direct_max_taps_ = MVN_D0_MAX_TAPS;
-  long direct_min_plane_ = 131072, direct_min_items_ = 0;
   std::map<int, std::unique_ptr<Plan3D>> taps_plans_;  // (kd, d1, d2) plans of the tap arrays, private to the engine
   // second work volume: the direct dim0 leg is out of place, work_ and work2_ swap roles after it
   float* work2_ = nullptr;

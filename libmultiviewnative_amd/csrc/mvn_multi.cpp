@@ -143,14 +143,20 @@ HaloGroup::~HaloGroup() {
   }
 }
 
-bool HaloGroup::all_direct(const workspace& input) {
-  for (size_t r = 0; r < slabs_.size(); ++r) {
-    be::set_device(slabs_[r].dev);
-    for (int v = 0; v < input.num_views_; ++v)
-      if (!slabs_[r].eng->would_be_direct(input.data_[v].kernel1_dims_) ||
-          !slabs_[r].eng->would_be_direct(input.data_[v].kernel2_dims_))
-        return false;
+kernel_list_t call_kernels(const workspace& input) {
+  kernel_list_t k;
+  for (int v = 0; v < input.num_views_; ++v) {
+    const view_data& d = input.data_[v];
+    k.push_back({{d.kernel1_dims_[0], d.kernel1_dims_[1], d.kernel1_dims_[2]}});
+    k.push_back({{d.kernel2_dims_[0], d.kernel2_dims_[1], d.kernel2_dims_[2]}});
   }
+  return k;
+}
+
+bool HaloGroup::all_direct(const workspace& input) {
+  const kernel_list_t k = call_kernels(input);
+  for (size_t r = 0; r < slabs_.size(); ++r)
+    if (!slabs_[r].eng->form_rule().all_direct(k)) return false;
   return true;
 }
 
@@ -301,13 +307,9 @@ void HaloGroup::load(const imageType* psi, const workspace& input, const shape_t
     e.set_psi(psi + first);
   });
   // the slabs exchange planes of the middle's input: all of them take the fused middle pass (mvn_mid_fused.hpp), or none
+  const kernel_list_t k = call_kernels(input);
   bool lines = true;
-  for (int r = 0; r < P && lines; ++r) {
-    be::set_device(slabs_[(size_t)r].dev);
-    for (int v = 0; v < V_ && lines; ++v)
-      lines = slabs_[(size_t)r].eng->would_be_lines(input.data_[v].kernel1_dims_) &&
-              slabs_[(size_t)r].eng->would_be_lines(input.data_[v].kernel2_dims_);
-  }
+  for (int r = 0; r < P && lines; ++r) lines = slabs_[(size_t)r].eng->form_rule().all_lines(k);
   for (int r = 0; r < P; ++r) slabs_[(size_t)r].eng->set_lines_in_halo_mode(lines);
   loaded_ = true;
 }

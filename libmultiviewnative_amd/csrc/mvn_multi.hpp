@@ -56,6 +56,9 @@ class HostBarrier {
 // does not exist
 std::vector<int> multi_devices_from_env();
 
+// the kernel extents of a call: kernel1, kernel2 of every view (what FormRule::all_direct / all_lines read)
+kernel_list_t call_kernels(const workspace& input);
+
 class HaloGroup {
  public:
   // ext = extents of the (padded) volume, h = halo planes = (deepest PSF) / 2, V = views

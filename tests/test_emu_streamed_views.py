@@ -29,10 +29,16 @@ from libmultiviewnative_amd.abi import WorkspaceHolder
 from oracle import binding as orc
 from ref_fixtures import realistic_views
 emu = native.Binding(native.EMU_SO)
-what, pad, V, s_arg = sys.argv[2], sys.argv[3], int(sys.argv[4]), sys.argv[5]
+what, pad, V, s_arg, kernels = sys.argv[2], sys.argv[3], int(sys.argv[4]), sys.argv[5], sys.argv[6]
 MB = 1 << 20
-_, views, k1, k2, w, psi0 = realistic_views((32, 128, 126), V, (5, 5, 5), seed=11)
-k2 = [np.ascontiguousarray(k[1:4]) for k in k2]  # (another depth: a second tap plan in the direct form)
+# kernels "exact*": d1 + 4 = 128, a multiple of 16, so that the zero policy may keep dim0 exact: 34 + 4 = 38 planes
+# when every PSF is held in the direct form, else good_extent(38) = 40
+shape = (34, 124, 126) if kernels.startswith("exact") else (32, 128, 126)
+_, views, k1, k2, w, psi0 = realistic_views(shape, V, (21 if kernels == "mixed" else 5, 5, 5), seed=11)
+k2 = [np.ascontiguousarray(k[k.shape[0] // 2 - 1:k.shape[0] // 2 + 2]) for k in k2]  # (3 planes: another tap plan)
+if kernels == "mixed":  # PSF depths 21, 17, 15 across the views: under MVN_DIM0_DIRECT_MAX=17 one 3-D spectrum and
+    # direct forms of two tap depths (32, 16) in one call
+    k1 = [np.ascontiguousarray(k[(21 - d) // 2:(21 - d) // 2 + d]) for d, k in zip([21, 17, 15] * V, k1)]
 h = WorkspaceHolder(views, k1, k2, w, 0.006, 1e-4, 2)
 emu.set_pad_mode(pad)
 
@@ -58,6 +64,12 @@ if what == "exact":
     assert np.isfinite(got).all() and not np.array_equal(got, psi0), "the call did not run"
     err = emu.l.mvn_last_error().decode()
     assert not err, err
+    if kernels.startswith("exact"):  # the extents the call ran on: dim0 exact (38) or padded (40), never both
+        import ctypes
+        def has(d0):
+            return any(emu.l.mvn_plan_store_has_key(0, (ctypes.c_int * 3)(d0, 128, e2)) == 1 for e2 in range(130, 180))
+        want = 38 if kernels == "exact" else 40
+        assert has(want) and not has(78 - want), (has(38), has(40))
     # one MB less: auto streams more views, or refuses cleanly - never a failed allocation
     fresh()
     os.environ["MVN_EMU_TOTAL_MB"] = str(-(-need // MB) - 1)
@@ -105,12 +117,12 @@ elif what == "refuse":
 """
 
 
-def _child(what, pad, V, s, direct=False, env_extra=None, timeout=900):
+def _child(what, pad, V, s, direct=False, env_extra=None, timeout=900, kernels="same"):
     env = dict(os.environ, OMP_NUM_THREADS="4", **(env_extra or {}))
     env.pop("MVN_EMU_TOTAL_MB", None)
     if direct:  # the direct dim0 leg (taps) at this size: the suite pins it to large volumes (tests/conftest.py)
         env["MVN_DIM0_DIRECT_MIN_ITEMS"] = "0"
-    r = subprocess.run([sys.executable, "-c", _CHILD, ROOT, what, pad, str(V), str(s)], env=env,
+    r = subprocess.run([sys.executable, "-c", _CHILD, ROOT, what, pad, str(V), str(s), kernels], env=env,
                        capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0 and "ok" in r.stdout.split("\n")[-2], (r.stdout[-2000:], r.stderr[-4000:])
     assert "exhausted" not in r.stderr, r.stderr[-4000:]
@@ -123,11 +135,18 @@ def emu():
     return native.Binding(native.EMU_SO)
 
 
-@pytest.mark.parametrize("s", ["0", "1", "V"])
-@pytest.mark.parametrize("form", ["fft", "direct"])
-@pytest.mark.parametrize("pad", ["none", "zero"])
-def test_memory_model_is_exact(emu, pad, form, s):
-    _child("exact", pad, 3, s, direct=form == "direct")
+@pytest.mark.parametrize("pad, form, s, kernels", [
+    pytest.param(pad, form, s, "same", id="%s-%s-%s" % (pad, form, s))
+    for pad in ("none", "zero") for form in ("fft", "direct") for s in ("0", "1", "V")] + [
+    # PSF depths differ across the views: one rule decides the form of every kernel (a 3-D spectrum, two tap depths)
+    pytest.param("zero", "direct", "1", "mixed", id="zero-direct-1-mixed"),
+    # dim0 kept at image + kernel - 1 by that rule, before the engine exists / padded when the rule refuses a PSF
+    pytest.param("zero", "direct", "0", "exact", id="zero-direct-0-exact"),
+    pytest.param("zero", "direct", "0", "exact-refused", id="zero-direct-0-exact-refused"),
+])
+def test_memory_model_is_exact(emu, pad, form, s, kernels):
+    extra = {"mixed": {"MVN_DIM0_DIRECT_MAX": "17"}, "exact-refused": {"MVN_DIM0_DIRECT_MAX": "4"}}.get(kernels)
+    _child("exact", pad, 3, s, direct=form == "direct", env_extra=extra, kernels=kernels)
 
 
 @pytest.mark.parametrize("form", ["fft", "direct"])
