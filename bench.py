@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: multi-view Richardson-Lucy iterations/s on 512^3 float32, 6 views.
 
-    python bench.py --gpus N --steps K --warmup W [--config 1|2|3|4]
+    python bench.py --gpus N --steps K --warmup W [--config 1|2|3|4] [--full]
 
 A "step" is one RL iteration = one update of psi from ALL views of ONE problem (BASELINE.json
 configs[2] by default: 512^3 f32, 6 views, 31^3 PSFs), with every stack, both PSF spectra per
@@ -25,9 +25,16 @@ N > 1   one process per GPU (torch.distributed, backend "nccl" = RCCL over xGMI)
 --config 3  512^3, 8 views (1 per GPU at N=8)  (configs[3])
 --config 4  320x1920x1920, 6 views, 31^3 PSFs  (configs[4]; 2+2+1+1 at N=4)
 
-Rank 0 prints ONE JSON line (the driver's contract) with extra objects:
+Rank 0 prints ONE JSON line (the driver's contract).  A plain run does only what that line's
+headline needs: set-up, warm-up, the timed steps, --dump-outputs, and from the timed region itself
   roofline      dominant kernel: algorithmic bytes per launch / average launch duration (HIP
                 events on the engine's stream, taken inside the timed region) vs 8 TB/s HBM
+With --full the line also carries the measurements and checks that take runs of their own (each
+can still be left out with --no-side, --no-abi or --no-cpu-baseline):
+  scaling_baseline  N = 1: the simultaneous (Jacobi) loop on the same engine
+  roofline.traffic  the dominant kernel's HBM bytes measured by rocprofv3 counter passes of a child
+                process (a plain run reports the static record, profiles/pmc_traffic.json)
+  ms_per_fft    one resident 3-D FFT of the volume
   cpu_baseline  the oracle (CPU restatement of inplace_cpu_deconvolve) timed on this host on a
                 bounded sample: ONE view update of the timed problem, started from the psi the
                 timed region left (rank 0 only)
@@ -35,6 +42,8 @@ Rank 0 prints ONE JSON line (the driver's contract) with extra objects:
                 (inplace_gpu_deconvolve, host buffers) compared with the oracle's result
   abi_end_to_end  one inplace_gpu_deconvolve call with host buffers (what the reference's
                 bench/bench_gpu_deconvolve_synthetic.cu:190-203 times), PCIe included; never `value`
+  exact_halo_mode  the same problem as ONE volume on dim0 slabs (N = 1: one slab that is its own
+                neighbour and a two-slab rehearsal; N > 1: slabs over all devices, in a child process)
 """
 import argparse
 import json
@@ -343,6 +352,9 @@ def main():
     ap.add_argument("--size", type=int, nargs=3, default=None, help="override the volume (test rehearsals)")
     ap.add_argument("--views", type=int, default=None, help="override the TOTAL number of views")
     ap.add_argument("--psf", type=int, default=None, help="override the PSF edge")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the measurements and checks that take runs of their own "
+                         "(see the module docstring); a plain run does only what the headline needs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true", help="no per-kernel events in the timed region")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL)")
@@ -354,14 +366,13 @@ def main():
     ap.add_argument("--host-sync", action="store_true",
                     help="N > 1: order collectives against the engine with host synchronisation instead of stream events")
     ap.add_argument("--no-side", action="store_true",
-                    help="skip ms_per_fft, the one-view parity check and the ABI end-to-end call "
-                         "(keeps rocprof --stats averages clean)")
+                    help="with --full: skip everything --full adds (a plain run)")
     ap.add_argument("--no-abi", action="store_true", help="skip the ABI end-to-end call")
     ap.add_argument("--force-dist", action="store_true",
                     help="one rank that still goes through torch.distributed and the chunked all-reduce "
                          "(rehearses the N > 1 code path, stream ordering included, on a one-GPU box)")
     ap.add_argument("--check-parity", action="store_true",
-                    help="N > 1: rank 0 still runs the one-view parity check / CPU sample (default: N = 1 only)")
+                    help="N > 1 with --full: rank 0 still runs the one-view parity check / CPU sample (default: N = 1 only)")
     ap.add_argument("--dump-psi", default=None, help="rank 0 saves the final psi here (.npy)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="rank 0 writes what the timed path computed (psi after the last timed step) as DIR/<name>.npy, "
@@ -370,6 +381,7 @@ def main():
                     help="internal: run only the exact_halo_mode measurement on these devices (comma separated) and "
                          "print its JSON block (the N > 1 lines start it as a child process with a time limit)")
     args = ap.parse_args()
+    args.side = args.full and not args.no_side
     if args.exact_halo_child:
         cfg = CONFIGS[args.config]
         shape = tuple(args.size or cfg["size"])
@@ -594,7 +606,7 @@ def run_rank(args, world_env):
         # The N > 1 lines time the simultaneous (Jacobi) loop, this line's `value` the reference-order
         # sequential sweep: a scaling series must be read against the SAME loop on one rank, so the
         # N = 1 line carries that rate too (same engine, same stacks, same step count).
-        if world == 1 and driver is None and not args.no_side:
+        if world == 1 and driver is None and args.side:
             jac = SimultaneousDriver(eng, None, None)
             jac.run(max(1, args.warmup), LAMBDA, MIN_VALUE)
             eng.sync()
@@ -615,7 +627,7 @@ def run_rank(args, world_env):
         eng.bind_delta(None)
     eng.close()
 
-    if rank == 0 and not args.no_side and (world == 1 or args.check_parity):
+    if rank == 0 and args.side and (world == 1 or args.check_parity):
         try:
             if world == 1 and out.get("roofline") and not args.no_abi:
                 live = measured_traffic(out["roofline"]["kernel"], shape)  # (the engine is closed: the GPU is free)
@@ -664,7 +676,7 @@ def run_rank(args, world_env):
     # (MVN_BENCH_EXACT_DEVICES=0,0: rehearsal of this step on a one-GPU box, where every rank sits on one device)
     exact_devices = os.environ.get("MVN_BENCH_EXACT_DEVICES") or (
         ",".join(str(d) for d in range(world)) if args.all_ranks_on_device < 0 else "")
-    if use_dist and world > 1 and not args.no_side and exact_devices:
+    if use_dist and world > 1 and args.side and exact_devices:
         # The N > 1 lines' `value` is the north-star mode (views sharded, one all-reduce per iteration: Jacobi).
         # The mode that keeps the REFERENCE's update order on N GPUs - dim0 slabs with a halo exchange, driven from
         # ONE process (rank 0) - rides along.  The other ranks wait on the HOST (a key in the rendezvous store, not

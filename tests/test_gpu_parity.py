@@ -1089,8 +1089,7 @@ def test_bench_multi_rank_launch_path_vs_oracle(gpu, orc, tmp_path, launch):
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--size", "64", "64", "64", "--views", str(V),
            "--psf", str(psf), "--steps", str(its), "--warmup", "0", "--no-profile", "--dump-psi", dump]
     exact = launch.endswith("exact_halo_mode")
-    if not exact:
-        cmd += ["--no-side"]
+    cmd += ["--full"] if exact else ["--no-side"]
     if launch == "one_rank_nccl":
         cmd += ["--gpus", "1", "--force-dist", "--backend", "nccl"]
     else:
