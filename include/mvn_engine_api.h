@@ -37,6 +37,49 @@ MVN_API int mvn_release_cached_engines(void);
  * be waited for exactly once; inplace_gpu_deconvolve == submit + wait on the first engine. */
 MVN_API int mvn_deconvolve_submit(imageType* psi, struct workspace input, int device, long long* ticket);
 MVN_API int mvn_deconvolve_wait(long long ticket);
+/* ---- stacks as the caller has them: device memory, uint16, strides ---------------------------------------------
+ * mvn_deconvolve_described is inplace_gpu_deconvolve for stacks that are not dense float32 arrays in host memory.
+ * `workspace` keeps its meaning - kernels and every *_dims_ member are host memory, dense float32 / int - while
+ * image_, weights_ and psi are read through descriptors:
+ *   dtype     MVN_F32 or, for images only, MVN_U16 (what a camera delivers; the conversion to float32 is exact)
+ *   location  MVN_HOST or MVN_DEVICE.  A stack in device memory is read (psi: also written) where it lies, by one pass
+ *             that converts, embeds and pads (csrc/mvn_ingest.hpp): no copy, no scratch.  A stack in host memory
+ *             crosses PCIe as it is - uint16 as uint16, half the bytes - and then goes through the same pass; only
+ *             float32 into a volume of its own extents (padding "none", the engine API) is placed by the copy itself.
+ *   stride    in ELEMENTS, per dimension of image_dims_.  dense is {d1 * d2, d2, 1}.  Inputs may repeat elements:
+ *             a stride of 0 along a dimension, and {0, 0, 0} = one value for every voxel (constant weights); negative
+ *             strides are refused.  psi, which is written, needs positive strides that do not overlap.  Stacks in
+ *             HOST memory need contiguous rows (stride[2] == 1, stride[1] >= d2; planes anywhere: they cross with
+ *             2-D copies) or {0, 0, 0}; any other host layout is refused - the library does not gather on the host.
+ * A NULL descriptor array means dense float32 in host memory for every view.
+ * The call blocks like inplace_gpu_deconvolve: on return psi is written and the library's streams are drained.
+ * `stream` is the hipStream_t the caller produced its device stacks on: the library records an event there and its
+ * own streams wait for it before their first read - the host never waits on the caller's stream.  NULL: the stacks
+ * are complete when the call is made.
+ * Everything else is the blocking call's: the padding policy in force, engine and PSF caches, convergence statistics,
+ * the quotient guard, and errors (< 0, message in mvn_last_error(), psi untouched).  The result is bit for bit that of
+ * inplace_gpu_deconvolve on the same values as dense float32 host stacks.
+ * With any stack in device memory the call runs on the device that owns it (device < 0 picks it; another device,
+ * stacks on two devices, or a pointer whose location is not the one described - asked of the runtime's pointer
+ * attributes before anything reads it - is an error), ignores MVN_DEVICES and runs resident whatever the memory
+ * mode: it is refused with "memory constraints" when mvn_deconvolve_memory's figure (less the embedding scratch when
+ * no stack needs it) does not fit.  Calls with host stacks only keep the memory modes - a streamed uint16 view
+ * streams uint16, mvn_stream_counters counts the bytes that crossed - and MVN_DEVICES when every descriptor is the
+ * default one. */
+enum { MVN_F32 = 0, MVN_U16 = 1 };     /* element type */
+enum { MVN_HOST = 0, MVN_DEVICE = 1 }; /* where the pointer lives */
+typedef struct mvn_stack_desc {
+  int dtype;
+  int location;
+  long long stride[3];
+} mvn_stack_desc;
+typedef struct mvn_call_desc {
+  mvn_stack_desc psi;            /* in/out, MVN_F32 */
+  const mvn_stack_desc* image;   /* num_views_ entries, or NULL = all dense host float32 */
+  const mvn_stack_desc* weights; /* num_views_ entries (MVN_F32), or NULL = all dense host float32 */
+  void* stream;
+} mvn_call_desc;
+MVN_API int mvn_deconvolve_described(void* psi, struct workspace input, const mvn_call_desc* desc, int device);
 /* Padding policy of inplace_gpu_deconvolve for the calls that follow (process-wide): "zero"
  * (default: the reference GPU entry's zero_padd with FFT-friendly padded extents), "zero_exact"
  * (exactly image + kernel - 1), "none" (the reference CPU path's cyclic no_padd); NULL or ""
@@ -147,6 +190,15 @@ MVN_API int mvn_engine_set_view(mvn_engine* e, int v, const float* image, const 
                                 const int k2dims[3]);
 MVN_API int mvn_engine_set_psi(mvn_engine* e, const float* psi);
 MVN_API int mvn_engine_get_psi(mvn_engine* e, float* psi);
+/* The same three for described stacks (mvn_stack_desc above; a NULL descriptor = dense float32 in host memory).  The
+ * set_* calls return once the source has been consumed (the caller may free or overwrite it); `stream` as in
+ * mvn_call_desc.  Stacks in device memory must be on the engine's device.  get_psi blocks. */
+MVN_API int mvn_engine_set_view_described(mvn_engine* e, int v, const void* image, const mvn_stack_desc* image_desc,
+                                          const void* weights, const mvn_stack_desc* weights_desc,
+                                          const float* kernel1, const int k1dims[3],
+                                          const float* kernel2, const int k2dims[3], void* stream);
+MVN_API int mvn_engine_set_psi_described(mvn_engine* e, const void* psi, const mvn_stack_desc* d, void* stream);
+MVN_API int mvn_engine_get_psi_described(mvn_engine* e, void* psi, const mvn_stack_desc* d);
 /* enqueue `iterations` sequential (Gauss-Seidel) sweeps over the views */
 MVN_API int mvn_engine_iterate(mvn_engine* e, int iterations, double lambda, float min_value);
 /* resident engine, blocking: stats receives 3 doubles per iteration run ({S_k, M_k, P_k} over the whole volume,

@@ -42,6 +42,77 @@ assert Workspace.lambda_.offset == 16 and Workspace.minValue_.offset == 24
 assert Workspace.num_iterations_.offset == 28
 
 
+# ---- described stacks (include/mvn_engine_api.h: mvn_stack_desc, mvn_call_desc) --------------------------------
+MVN_F32, MVN_U16 = 0, 1
+MVN_HOST, MVN_DEVICE = 0, 1
+
+
+class StackDesc(C.Structure):
+    _fields_ = [
+        ("dtype", C.c_int),
+        ("location", C.c_int),
+        ("stride", C.c_longlong * 3),
+    ]
+
+
+class CallDesc(C.Structure):
+    _fields_ = [
+        ("psi", StackDesc),
+        ("image", C.POINTER(StackDesc)),
+        ("weights", C.POINTER(StackDesc)),
+        ("stream", C.c_void_p),
+    ]
+
+
+assert C.sizeof(StackDesc) == 32 and StackDesc.stride.offset == 8
+assert C.sizeof(CallDesc) == 56
+assert (CallDesc.image.offset, CallDesc.weights.offset, CallDesc.stream.offset) == (32, 40, 48)
+
+
+def _is_tensor(a):
+    # (torch is never imported here: an object that is not a numpy array and has these is taken for a tensor)
+    return not isinstance(a, np.ndarray) and hasattr(a, "data_ptr") and hasattr(a, "stride")
+
+
+def describe_stack(a, int16_is_uint16=False):
+    """(pointer, StackDesc, shape, device index or None) of a numpy array (float32 / uint16, strides that are
+    multiples of the item size) or a torch tensor (CPU or cuda; float32 or uint16; int16 only with int16_is_uint16,
+    for a torch without uint16: the bits are then read as uint16)."""
+    d = StackDesc()
+    device = None
+    if _is_tensor(a):
+        name = str(a.dtype)
+        if name == "torch.float32":
+            d.dtype = MVN_F32
+        elif name == "torch.uint16" or (name == "torch.int16" and int16_is_uint16):
+            d.dtype = MVN_U16
+        else:
+            raise TypeError("stacks are float32 or uint16, not %s" % name)
+        ptr, strides, shape = a.data_ptr(), tuple(a.stride()), tuple(a.shape)
+        if a.is_cuda:
+            d.location = MVN_DEVICE
+            device = a.device.index
+        else:
+            d.location = MVN_HOST
+    else:
+        a = np.asarray(a)
+        if a.dtype == np.float32:
+            d.dtype = MVN_F32
+        elif a.dtype == np.uint16:
+            d.dtype = MVN_U16
+        else:
+            raise TypeError("stacks are float32 or uint16, not %s" % a.dtype)
+        if any(st % a.itemsize for st in a.strides):
+            raise ValueError("strides must be multiples of the item size")
+        ptr, strides, shape = a.ctypes.data, tuple(st // a.itemsize for st in a.strides), a.shape
+        d.location = MVN_HOST
+    if len(shape) != 3:
+        raise ValueError("stacks are 3-D")
+    for k in range(3):
+        d.stride[k] = int(strides[k])
+    return ptr, d, tuple(int(x) for x in shape), device
+
+
 def fptr(a):
     return a.ctypes.data_as(c_float_p)
 

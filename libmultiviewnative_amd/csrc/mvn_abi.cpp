@@ -113,7 +113,7 @@ static std::unique_ptr<Engine> pop_cached_engine(int dev) {
 // Selected by mvn_set_memory_mode(), else resident.  The planner may use min(free device memory,
 // budget), budget = mvn_set_memory_budget() (ignored in resident mode).  Results are those of the resident call, bit for bit: same kernels, same order.
 // ---------------------------------------------------------------------------------------------
-enum { MVN_MEM_UNSET = -1, MVN_MEM_RESIDENT = 0, MVN_MEM_AUTO = 1, MVN_MEM_STREAM = 2 };
+enum { MVN_MEM_EXACT = -2, MVN_MEM_UNSET = -1, MVN_MEM_RESIDENT = 0, MVN_MEM_AUTO = 1, MVN_MEM_STREAM = 2 };
 // a mode is stored as one int: MVN_MEM_STREAM + 1 + N for stream:N
 static std::atomic<int> g_mem_mode{MVN_MEM_UNSET};
 static std::atomic<long long> g_mem_budget{-1};
@@ -192,7 +192,7 @@ static std::vector<int> spread_views(int V, int s) {
 
 // caller holds device_mutex(dev); the auto / stream modes of take_engine
 static std::unique_ptr<Engine> plan_engine(int key, int dev, const shape_t& ext, size_t embed_floats,
-                                           const workspace& input, int mode) {
+                                           const workspace& input, int mode, bool use_budget = true) {
   const int V = input.num_views_;
   MemoryQuery q = memory_query(ext, input, embed_floats);
   const FormRule rule = call_rule(ext, dev);
@@ -207,8 +207,14 @@ static std::unique_ptr<Engine> plan_engine(int key, int dev, const shape_t& ext,
   size_t free_b = 0, total_b = 0;
   be::device_mem_info(&free_b, &total_b);
   size_t avail = free_b;
-  if (cached) avail += need(cached->streamed_count(), cached->ring_size());  // (what re-planning would free)
-  const size_t budget = current_memory_budget();
+  if (cached) {  // what re-planning would free: the cached engine as it stands, with the scratch it holds
+    MemoryQuery held = q;
+    held.embed_floats = cached->scratch_floats();
+    held.streamed = cached->streamed_count();
+    held.ring = cached->ring_size();
+    avail += Engine::memory_need(held, rule);
+  }
+  const size_t budget = use_budget ? current_memory_budget() : 0;
   if (budget) avail = std::min(avail, budget);
   int s = -1, ring = 0;
   const int first = mode == MVN_MEM_AUTO ? 0 : (mode == MVN_MEM_STREAM ? V : std::min(V, mode - MVN_MEM_STREAM - 1));
@@ -248,6 +254,8 @@ static std::unique_ptr<Engine> plan_engine(int key, int dev, const shape_t& ext,
 // work is queued, not by a failing hipMalloc on the staging thread.
 static std::unique_ptr<Engine> take_engine(int key, int dev, const shape_t& ext, int V, size_t embed_floats,
                                            const workspace& input, int mem_mode) {
+  // (MVN_MEM_EXACT: resident, priced by the exact model - a described call with stacks in device memory)
+  if (mem_mode == MVN_MEM_EXACT) return plan_engine(key, dev, ext, embed_floats, input, MVN_MEM_STREAM + 1, false);
   if (mem_mode != MVN_MEM_RESIDENT) return plan_engine(key, dev, ext, embed_floats, input, mem_mode);
   std::unique_ptr<Engine> e = pop_cached_engine(key);  // key = device + lane * kLaneStride
   if (e && reusable(*e, ext, V) && e->streamed_count() == 0) return e;
@@ -550,8 +558,74 @@ static size_t embed_floats_of(const shape_t& dims, const shape_t& ext) {
   return embedded ? (size_t)dims[0] * (size_t)dims[1] * (size_t)dims[2] : 0;
 }
 
+// ---- described stacks (mvn_deconvolve_described, mvn_engine_*_described) ----------------------------------------
+struct DescribedCall {
+  StackRef psi;
+  std::vector<StackRef> image, weights;
+  void* stream = nullptr;
+  bool any_device = false;
+  int device = -1;           // the device that owns the stacks in device memory
+  bool need_scratch = false; // some stack passes through the host-shaped embedding scratch
+};
+
+// a descriptor and its pointer as a StackRef, everything about it checked that can be without touching the memory
+static StackRef described_stack(const void* ptr, const mvn_stack_desc* d, const int* dims, const std::string& what,
+                                bool may_u16, bool written) {
+  if (!ptr) throw std::invalid_argument(what + ": null pointer");
+  if (!d) return StackRef::dense_host((const float*)ptr, dims);
+  if (d->dtype != MVN_F32 && d->dtype != MVN_U16) throw std::invalid_argument(what + ": unknown dtype " + std::to_string(d->dtype));
+  if (d->dtype == MVN_U16 && !may_u16) throw std::invalid_argument(what + ": only images may be uint16");
+  if (d->location != MVN_HOST && d->location != MVN_DEVICE)
+    throw std::invalid_argument(what + ": unknown location " + std::to_string(d->location));
+  StackRef r;
+  r.ptr = ptr;
+  r.u16 = d->dtype == MVN_U16;
+  r.device = d->location == MVN_DEVICE;
+  for (int k = 0; k < 3; ++k) {
+    r.stride[k] = d->stride[k];
+    if (r.stride[k] < 0) throw std::invalid_argument(what + ": negative stride");
+  }
+  if (written) {  // every element its own address
+    int order[3] = {0, 1, 2};
+    std::sort(order, order + 3, [&](int a, int b) { return r.stride[a] < r.stride[b]; });
+    long long reach = 0;  // largest element offset of the dimensions passed so far
+    for (int k : order) {
+      if (dims[k] == 1) continue;
+      if (r.stride[k] <= reach) throw std::invalid_argument(what + ": strides must be positive and must not overlap");
+      reach += r.stride[k] * (long long)(dims[k] - 1);
+    }
+  }
+  return r;
+}
+
+// the pointer is where its descriptor says (the runtime's pointer attributes; nothing is read); *owner collects the
+// device of the stacks in device memory
+static void check_location(const StackRef& r, const std::string& what, int* owner) {
+  const int where = be::pointer_device(r.ptr);
+  if (r.device) {
+    if (where == be::POINTER_HOST) throw std::invalid_argument(what + ": described as device memory, but it is host memory");
+    if (where >= 0) {
+      if (*owner >= 0 && *owner != where) throw std::invalid_argument(what + ": stacks on two different devices");
+      *owner = where;
+    }
+  } else if (where >= 0) {
+    throw std::invalid_argument(what + ": described as host memory, but it is device memory");
+  }
+}
+
+static bool plain_stack(const StackRef& r, const int* dims) {
+  const StackRef d = StackRef::dense_host(nullptr, dims);
+  if (r.u16 || r.device) return false;
+  for (int k = 0; k < 3; ++k)
+    if (dims[k] > 1 && r.stride[k] != d.stride[k]) return false;
+  return true;
+}
+
+// does the stack pass through the engine's host-shaped scratch when the call embeds its stacks?
+static bool through_scratch(const StackRef& r) { return !r.device && !r.broadcast(); }
+
 static void deconvolve_call(imageType* psi, const workspace& input, int device, int lane, int pad_mode, double tol,
-                            ConvRecord* conv) {
+                            ConvRecord* conv, const DescribedCall* dc = nullptr) {
   conv->iterations_run = 0;
   conv->rows.clear();
   struct TolScope {  // (the memory model of this call counts the statistics buffers: memory_query)
@@ -569,27 +643,31 @@ static void deconvolve_call(imageType* psi, const workspace& input, int device, 
       // the slab drivers keep no convergence statistics: such a call runs on one device
       if (!devs.empty() && tol >= 0. && trace_on())
         std::printf("[lmvn::trace] MVN_DEVICES: convergence statistics on - one device\n");
-      if (!devs.empty() && tol < 0.) {
+      if (!devs.empty() && dc && trace_on())
+        std::printf("[lmvn::trace] MVN_DEVICES: described stacks - one device\n");
+      if (!devs.empty() && tol < 0. && !dc) {
         call_extents(input, pad_mode, -1, &dims, &ext, off);  // (the slabs run on plans of their own extents)
         if (multi_device_call(psi, input, dims, ext, off, pad_mode, devs)) return;
       }
     }
     const int dev = pick_device(device);
     call_extents(input, pad_mode, dev, &dims, &ext, off);
-    const int mem_mode = current_memory_mode();
+    // stacks in device memory: resident whatever the mode, priced by the exact model
+    const int mem_mode = dc && dc->any_device ? (int)MVN_MEM_EXACT : current_memory_mode();
     const int key = dev + lane * kLaneStride;
     std::lock_guard<std::mutex> lk(device_mutex(key));
     be::set_device(dev);
     const bool embedded = ext[0] != dims[0] || ext[1] != dims[1] || ext[2] != dims[2];
     // on failure the engine is simply dropped
-    std::unique_ptr<Engine> eng_owner =
-        take_engine(key, dev, ext, V, embedded ? (size_t)dims[0] * (size_t)dims[1] * (size_t)dims[2] : 0, input, mem_mode);
+    const bool scratch = !dc || dc->need_scratch;
+    std::unique_ptr<Engine> eng_owner = take_engine(
+        key, dev, ext, V, embedded && scratch ? (size_t)dims[0] * (size_t)dims[1] * (size_t)dims[2] : 0, input, mem_mode);
     Engine& eng = *eng_owner;
     eng.begin_call();
     // stacks are embedded into / cropped out of the padded volume by the transfers themselves
     // (strided device copies), so the padded modes keep the pipelined upload
     const int dims_i[3] = {dims[0], dims[1], dims[2]};
-    eng.set_embedding(dims_i, off);
+    eng.set_embedding(dims_i, off, scratch);
     // extra zeros beyond the PSF's reach: the blurred estimate is exactly or nearly 0 there and
     // the reference's pointwise math would give 0 * 1/0 = NaN; the one deliberate deviation
     eng.set_quotient_guard(pad_mode == MVN_PAD_ZERO);
@@ -598,14 +676,19 @@ static void deconvolve_call(imageType* psi, const workspace& input, int device, 
       return e && *e && std::strcmp(e, "0") != 0;
     }();
     if (no_pipeline && eng.streamed_count() == 0) {  // (streamed views need the uploader thread)
+      if (dc) eng.wait_for_caller(dc->stream);
       for (int v = 0; v < V; ++v) {
         const view_data& d = input.data_[v];
-        eng.set_view(v, d.image_, d.weights_, d.kernel1_, d.kernel1_dims_, d.kernel2_, d.kernel2_dims_);
+        if (dc)
+          eng.set_view_described(v, dc->image[(size_t)v], dc->weights[(size_t)v], d.kernel1_, d.kernel1_dims_, d.kernel2_,
+                                 d.kernel2_dims_);
+        else
+          eng.set_view(v, d.image_, d.weights_, d.kernel1_, d.kernel1_dims_, d.kernel2_, d.kernel2_dims_);
       }
-      eng.set_psi(psi);
+      dc ? eng.set_psi_described(dc->psi) : eng.set_psi(psi);
       conv->iterations_run = eng.iterate(input.num_iterations_, input.lambda_, input.minValue_, tol, &conv->rows);
       eng.sync();
-      eng.get_psi(psi);
+      dc ? eng.get_psi_described(dc->psi) : eng.get_psi(psi);
       give_back_engine(key, std::move(eng_owner));
       return;
     }
@@ -622,7 +705,16 @@ static void deconvolve_call(imageType* psi, const workspace& input, int device, 
     eng.reserve_views(call_kernels(input));
     lap("allocate view buffers");
     std::unique_lock<std::mutex> pcie(upload_mutex(dev));  // handed to the uploader thread's scope below
-    eng.set_psi(psi);
+    if (dc) {
+      eng.wait_for_caller(dc->stream);
+      eng.set_psi_described(dc->psi);
+      // views that are in device memory already: ingested on the compute stream, in view order
+      for (int v = 0; v < V; ++v)
+        if (dc->image[(size_t)v].device && dc->weights[(size_t)v].device)
+          eng.ingest_device_view(v, dc->image[(size_t)v], dc->weights[(size_t)v]);
+    } else {
+      eng.set_psi(psi);
+    }
     lap("upload psi");
     std::exception_ptr up_err;
     std::thread uploader([&] {
@@ -631,14 +723,23 @@ static void deconvolve_call(imageType* psi, const workspace& input, int device, 
         auto u0 = std::chrono::steady_clock::now();
         for (int v = 0; v < V; ++v) {
           const view_data& d = input.data_[v];
-          eng.stage_view(v, d.image_, d.weights_, d.kernel1_, d.kernel1_dims_, d.kernel2_, d.kernel2_dims_);
+          if (dc)
+            eng.stage_view_described(v, dc->image[(size_t)v], dc->weights[(size_t)v], d.kernel1_, d.kernel1_dims_,
+                                     d.kernel2_, d.kernel2_dims_);
+          else
+            eng.stage_view(v, d.image_, d.weights_, d.kernel1_, d.kernel1_dims_, d.kernel2_, d.kernel2_dims_);
         }
         eng.finish_staging();
         // out-of-core views: their stacks again for every later sweep, in sweep order, each as soon as its ring
         // slot is free (Engine::stream_view)
         for (int it = 1; it < input.num_iterations_ && eng.streamed_count() > 0; ++it)
           for (int v = 0; v < V; ++v)
-            if (eng.is_streamed(v)) eng.stream_view(v, input.data_[v].image_, input.data_[v].weights_);
+            if (eng.is_streamed(v)) {
+              if (dc)
+                eng.stream_view_described(v, dc->image[(size_t)v], dc->weights[(size_t)v]);
+              else
+                eng.stream_view(v, input.data_[v].image_, input.data_[v].weights_);
+            }
         if (trace_on())
           std::printf("[lmvn::trace] %-28s %8.1f ms (uploader thread)\n", "stage all views",
                       std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u0).count());
@@ -663,7 +764,7 @@ static void deconvolve_call(imageType* psi, const workspace& input, int device, 
     if (main_err) std::rethrow_exception(main_err);
     eng.sync();
     lap("wait for the device");
-    eng.get_psi(psi);
+    dc ? eng.get_psi_described(dc->psi) : eng.get_psi(psi);
     lap("download psi");
     if (eng.streamed_count() > 0) Engine::count_streamed_call();
     give_back_engine(key, std::move(eng_owner));
@@ -674,6 +775,56 @@ void inplace_gpu_deconvolve(imageType* psi, struct workspace input, int device) 
   guarded("inplace_gpu_deconvolve", [&] {
     const double tol = g_conv_tol.load();
     deconvolve_call(psi, input, device, 0, current_pad_mode(), tol, &t_last_conv);
+  });
+}
+
+int mvn_deconvolve_described(void* psi, struct workspace input, const mvn_call_desc* desc, int device) {
+  return guarded("mvn_deconvolve_described", [&] {
+    const double tol = g_conv_tol.load();
+    if (!desc) {
+      deconvolve_call((imageType*)psi, input, device, 0, current_pad_mode(), tol, &t_last_conv);
+      return;
+    }
+    check_workspace((const imageType*)psi, input);
+    const int V = input.num_views_;
+    if (V == 0) return;
+    const int* dims = input.data_[0].image_dims_;
+    for (int d = 0; d < 3; ++d)
+      if (dims[d] < 1) throw std::invalid_argument("image extents must be >= 1");
+    // everything about the descriptors is settled before any stack is touched
+    DescribedCall dc;
+    dc.stream = desc->stream;
+    dc.psi = described_stack(psi, &desc->psi, dims, "psi", false, true);
+    int owner = -1;
+    check_location(dc.psi, "psi", &owner);
+    bool plain = plain_stack(dc.psi, dims);
+    for (int v = 0; v < V; ++v) {
+      const view_data& d = input.data_[v];
+      const std::string n = std::to_string(v);
+      dc.image.push_back(described_stack(d.image_, desc->image ? desc->image + v : nullptr, d.image_dims_, "image " + n, true, false));
+      dc.weights.push_back(described_stack(d.weights_, desc->weights ? desc->weights + v : nullptr, d.image_dims_, "weights " + n, false, false));
+      check_location(dc.image.back(), "image " + n, &owner);
+      check_location(dc.weights.back(), "weights " + n, &owner);
+      plain = plain && plain_stack(dc.image.back(), d.image_dims_) && plain_stack(dc.weights.back(), d.image_dims_);
+    }
+    if (plain) {  // today's layout throughout: today's call
+      deconvolve_call((imageType*)psi, input, device, 0, current_pad_mode(), tol, &t_last_conv);
+      return;
+    }
+    dc.need_scratch = through_scratch(dc.psi);
+    dc.any_device = dc.psi.device;
+    for (int v = 0; v < V; ++v) {
+      dc.need_scratch = dc.need_scratch || through_scratch(dc.image[(size_t)v]) || through_scratch(dc.weights[(size_t)v]);
+      dc.any_device = dc.any_device || dc.image[(size_t)v].device || dc.weights[(size_t)v].device;
+    }
+    if (dc.any_device) {
+      if (owner >= 0 && device >= 0 && device != owner)
+        throw std::invalid_argument("the stacks live on device " + std::to_string(owner) + ", not on device " +
+                                    std::to_string(device));
+      if (owner >= 0) device = owner;
+      dc.device = device;
+    }
+    deconvolve_call((imageType*)psi, input, device, 0, current_pad_mode(), tol, &t_last_conv, &dc);
   });
 }
 
@@ -1556,6 +1707,50 @@ int mvn_engine_set_psi(mvn_engine* e, const float* psi) {
 
 int mvn_engine_get_psi(mvn_engine* e, float* psi) {
   MVN_ENGINE_CALL("mvn_engine_get_psi", E.get_psi(psi));
+}
+
+int mvn_engine_set_view_described(mvn_engine* e, int v, const void* image, const mvn_stack_desc* image_desc,
+                                  const void* weights, const mvn_stack_desc* weights_desc, const float* kernel1,
+                                  const int k1dims[3], const float* kernel2, const int k2dims[3], void* stream) {
+  MVN_ENGINE_CALL("mvn_engine_set_view_described", {
+    if (!kernel1 || !kernel2 || !k1dims || !k2dims) throw std::invalid_argument("null kernel");
+    const Layout& L = E.layout();
+    const int dims[3] = {L.d0, L.d1, L.d2};
+    const StackRef im = described_stack(image, image_desc, dims, "image", true, false);
+    const StackRef w = described_stack(weights, weights_desc, dims, "weights", false, false);
+    int owner = -1;
+    check_location(im, "image", &owner);
+    check_location(w, "weights", &owner);
+    if (owner >= 0 && owner != E.device()) throw std::invalid_argument("the stacks live on another device than the engine");
+    E.wait_for_caller(stream);
+    E.set_view_described(v, im, w, kernel1, k1dims, kernel2, k2dims);
+  });
+}
+
+int mvn_engine_set_psi_described(mvn_engine* e, const void* psi, const mvn_stack_desc* d, void* stream) {
+  MVN_ENGINE_CALL("mvn_engine_set_psi_described", {
+    const Layout& L = E.layout();
+    const int dims[3] = {L.d0, L.d1, L.d2};
+    const StackRef r = described_stack(psi, d, dims, "psi", false, false);
+    int owner = -1;
+    check_location(r, "psi", &owner);
+    if (owner >= 0 && owner != E.device()) throw std::invalid_argument("psi lives on another device than the engine");
+    E.wait_for_caller(stream);
+    E.set_psi_described(r);
+  });
+}
+
+int mvn_engine_get_psi_described(mvn_engine* e, void* psi, const mvn_stack_desc* d) {
+  MVN_ENGINE_CALL("mvn_engine_get_psi_described", {
+    const Layout& L = E.layout();
+    const int dims[3] = {L.d0, L.d1, L.d2};
+    const StackRef r = described_stack(psi, d, dims, "psi", false, true);
+    int owner = -1;
+    check_location(r, "psi", &owner);
+    if (owner >= 0 && owner != E.device()) throw std::invalid_argument("psi lives on another device than the engine");
+    E.sync();
+    E.get_psi_described(r);
+  });
 }
 
 int mvn_engine_iterate(mvn_engine* e, int iterations, double lambda, float min_value) {

@@ -13,6 +13,7 @@
 #include "mvn_pass_bodies.hpp"
 #include "mvn_dim0_direct.hpp"
 #include "mvn_mid_fused.hpp"
+#include "mvn_ingest.hpp"
 
 namespace mvn {
 namespace be {
@@ -46,6 +47,11 @@ void dzero(void* d, size_t bytes, stream_t s);
 // reach memory of `peer` (once per pair; a no-op for dev == peer), and a device-to-device copy between two
 // devices' memories enqueued on a stream of either
 void enable_peer_access(int dev, int peer);
+// Where the memory behind `p` lives, asked of the runtime's pointer attributes - `p` itself is never read: the
+// ordinal of the device that owns it, POINTER_HOST for host memory (pinned, registered or unknown to the runtime),
+// POINTER_ANY for memory either side may use (managed memory; every pointer of the host emulation).
+enum { POINTER_HOST = -1, POINTER_ANY = -2 };
+int pointer_device(const void* p);
 void copy_peer(void* dst, int dst_dev, const void* src, int src_dev, size_t bytes, stream_t s);
 
 stream_t stream_create();
@@ -119,6 +125,12 @@ void launch_scatter_psf(const float* kernel, int k0, int k1, int k2, float* targ
 // 537-549, done by the reference on the host)
 void launch_copy3d(float* dst, long drow, long dplane, const float* src, long srow, long splane,
                    int nx, int ny, int nz, stream_t s);
+
+// a caller's stack (float32 or uint16, element strides) into the engine volume in one pass that writes every float of
+// the volume, and the window of psi back out into a strided float32 destination (mvn_ingest.hpp); the stack is
+// DEVICE memory here (host stacks cross PCIe first, Engine::ingest_stack)
+void launch_ingest3d(const IngestParams& p, bool u16, stream_t s);
+void launch_extract3d(const ExtractParams& p, stream_t s);
 
 // stand-alone pointwise ops on flat arrays (legacy ABI: compute_quotient / compute_final_values)
 void launch_divide(const float* view, float* inout, size_t n, stream_t s);

@@ -130,6 +130,8 @@ void enable_peer_access(int dev, int peer) {
 }
 void copy_peer(void* dst, int, const void* src, int, size_t bytes, stream_t) { std::memmove(dst, src, bytes); }
 
+int pointer_device(const void*) { return POINTER_ANY; }  // "device memory" is host memory here
+
 stream_t stream_create() { return (stream_t)1; }
 stream_t stream_create_upload() { return (stream_t)1; }
 void stream_destroy(stream_t) {}
@@ -587,6 +589,25 @@ void launch_copy3d(float* dst, long drow, long dplane, const float* src, long sr
   for (long z = 0; z < nz; ++z)
     for (long y = 0; y < ny; ++y)
       std::memcpy(dst + z * dplane + y * drow, src + z * splane + y * srow, sizeof(float) * (size_t)nx);
+}
+
+void launch_ingest3d(const IngestParams& p, bool u16, stream_t) {
+  const long nblocks = mvn_ingest_blocks(p.rows);
+#pragma omp parallel for schedule(static)
+  for (long blk = 0; blk < nblocks; ++blk)
+    for (int t = 0; t < MVN_INGEST_WG; ++t) {
+      if (u16)
+        mvn_ingest_rows<uint16_t>(p, blk, t);
+      else
+        mvn_ingest_rows<float>(p, blk, t);
+    }
+}
+
+void launch_extract3d(const ExtractParams& p, stream_t) {
+  const long nblocks = mvn_extract_blocks(p);
+#pragma omp parallel for schedule(static)
+  for (long blk = 0; blk < nblocks; ++blk)
+    for (int t = 0; t < MVN_INGEST_WG; ++t) mvn_extract_rows(p, blk, t);
 }
 
 void launch_divide(const float* view, float* inout, size_t n, stream_t) {

@@ -823,6 +823,7 @@ Engine::~Engine() {
   be::dfree(psi_spec_);
   be::dfree(psi_spec_nyq_);
   be::dfree(embed_scratch_);
+  if (caller_ev_) be::event_destroy(caller_ev_);
   be::dfree(poison_own_);
   be::graph_destroy(sweep_graph_);
   if (!delta_external_) be::dfree(delta_);
@@ -841,7 +842,7 @@ Engine::~Engine() {
   if (stream_) be::stream_destroy(stream_);
 }
 
-void Engine::set_embedding(const int dims[3], const int off[3]) {
+void Engine::set_embedding(const int dims[3], const int off[3], bool scratch) {
   be::set_device(device_);
   const Layout& L = plan_->L;
   const int ext[3] = {L.d0, L.d1, L.d2};
@@ -852,7 +853,15 @@ void Engine::set_embedding(const int dims[3], const int off[3]) {
     dense = dense && dims[d] == ext[d];
     same = same && host_dims_[d] == dims[d] && host_off_[d] == off[d];
   }
-  if (same && embedded_ == !dense) return;
+  if (same && embedded_ == !dense) {
+    if (embedded_ && scratch && !embed_scratch_) embed_scratch_ = (float*)be::dmalloc(host_floats() * sizeof(float));
+    if (!scratch && embed_scratch_) {
+      be::stream_sync(stream_);
+      be::dfree(embed_scratch_);
+      embed_scratch_ = nullptr;
+    }
+    return;
+  }
   be::stream_sync(stream_);
   // the interior moves: what used to be interior may now be padding and must read zero
   for (size_t v = 0; v < views_.size(); ++v) {
@@ -871,7 +880,7 @@ void Engine::set_embedding(const int dims[3], const int off[3]) {
     host_off_[d] = off[d];
   }
   embedded_ = !dense;
-  if (embedded_) embed_scratch_ = (float*)be::dmalloc(host_floats() * sizeof(float));
+  if (embedded_ && scratch) embed_scratch_ = (float*)be::dmalloc(host_floats() * sizeof(float));
 }
 
 void Engine::upload_volume(float* dst, const float* host, be::stream_t s) {
@@ -888,6 +897,101 @@ void Engine::upload_volume(float* dst, const float* host, be::stream_t s) {
   else
     be::h2d_2d(dst, (size_t)L.RP * sizeof(float), host, (size_t)L.d2 * sizeof(float),
                (size_t)L.d2 * sizeof(float), L.rows, s);
+}
+
+// ---- described stacks (mvn_ingest.hpp) ---------------------------------------------------------------
+// rows of a host stack as 2-D copies: [n0][n1] rows of `width` bytes, source pitches in bytes, destination pitches
+// drow / dplane bytes; one copy where the source's planes continue its row pitch, else one per plane
+static void host_rows_to_device(char* dst, size_t drow, size_t dplane, const char* src, long long s0b, long long s1b,
+                                size_t width, const int* n, be::stream_t s) {
+  if (n[1] == 1) {  // (one row per plane: its row stride means nothing)
+    for (int z = 0; z < n[0]; ++z) be::h2d(dst + z * dplane, src + z * s0b, width, s);
+    return;
+  }
+  if (n[0] == 1 || (s0b == (long long)n[1] * s1b && dplane == (size_t)n[1] * drow)) {
+    be::h2d_2d(dst, drow, src, (size_t)s1b, width, (size_t)n[0] * n[1], s);
+    return;
+  }
+  for (int z = 0; z < n[0]; ++z) be::h2d_2d(dst + z * dplane, drow, src + z * s0b, (size_t)s1b, width, (size_t)n[1], s);
+}
+
+static void check_host_rows(const StackRef& st, const int* n) {
+  if (n[2] > 1 && st.stride[2] != 1)
+    throw std::invalid_argument("mvn: a stack in host memory needs contiguous rows (stride[2] == 1); gather it or hand it over in device memory");
+  if ((n[1] > 1 && st.stride[1] < n[2]) || (n[0] > 1 && st.stride[0] < 0))
+    throw std::invalid_argument("mvn: rows of a stack in host memory must not overlap (stride[1] >= extent[2])");
+}
+
+long long Engine::ingest_stack(float* dst, const StackRef& st, float* scratch, bool dst_dirty, be::stream_t s) {
+  const Layout& L = plan_->L;
+  const int* n = host_dims_;
+  if (!st.ptr) throw std::invalid_argument("mvn: null stack");
+  for (int d = 0; d < 3; ++d)
+    if (st.stride[d] < 0) throw std::invalid_argument("mvn: negative stride");
+  IngestParams p;
+  p.dst = dst, p.RP = L.RP, p.D1 = L.d1, p.rows = (long)L.rows;
+  p.n0 = n[0], p.n1 = n[1], p.n2 = n[2];
+  p.o0 = host_off_[0], p.o1 = host_off_[1], p.o2 = host_off_[2];
+  p.src = st.ptr, p.s0 = st.stride[0], p.s1 = st.stride[1], p.s2 = st.stride[2];
+  p.use_value = 0, p.value = 0.f;
+  if (st.device) {  // read where it lies
+    be::launch_ingest3d(p, st.u16, s);
+    return 0;
+  }
+  if (st.broadcast()) {  // one value in host memory: it travels as a kernel argument
+    p.use_value = 1;
+    p.value = st.u16 ? (float)*(const uint16_t*)st.ptr : *(const float*)st.ptr;
+    p.src = nullptr;
+    be::launch_ingest3d(p, false, s);
+    return 0;
+  }
+  check_host_rows(st, n);
+  const size_t esz = st.u16 ? sizeof(uint16_t) : sizeof(float);
+  const long long bytes = (long long)(host_floats() * esz);
+  const bool dense = (n[1] == 1 || st.stride[1] == n[2]) && (n[0] == 1 || st.stride[0] == (long long)n[1] * n[2]);
+  if (!embedded_ && !st.u16) {  // float32 into a volume of its own extents: the copy itself places it
+    if (dst_dirty && L.RP != L.d2) be::dzero(dst, plan_->main_bytes(), s);
+    if (dense)
+      upload_volume(dst, (const float*)st.ptr, s);
+    else
+      host_rows_to_device((char*)dst, (size_t)L.RP * sizeof(float), (size_t)L.d1 * L.RP * sizeof(float),
+                          (const char*)st.ptr, st.stride[0] * 4, st.stride[1] * 4, (size_t)n[2] * sizeof(float), n, s);
+    return bytes;
+  }
+  if (!scratch) throw std::logic_error("mvn: no scratch for a host stack");
+  if (dense)
+    be::h2d(scratch, st.ptr, (size_t)bytes, s);
+  else
+    host_rows_to_device((char*)scratch, (size_t)n[2] * esz, (size_t)n[1] * n[2] * esz, (const char*)st.ptr,
+                        st.stride[0] * (long long)esz, st.stride[1] * (long long)esz, (size_t)n[2] * esz, n, s);
+  p.src = scratch, p.s0 = (long long)n[1] * n[2], p.s1 = n[2], p.s2 = 1;
+  be::launch_ingest3d(p, st.u16, s);
+  return bytes;
+}
+
+long long Engine::ingest_pair(float* image_dst, float* weights_dst, const StackRef& image, const StackRef& weights,
+                              be::stream_t s) {
+  if (weights.u16) throw std::invalid_argument("mvn: weights are float32");
+  float* scr = embed_scratch_;
+  bool dirty = false;
+  if (!scr && !image.device && !image.broadcast() && image.u16) {
+    // (no embedding, so no scratch: the raw uint16 stack lands in the view's weights volume, which is filled next,
+    //  on the same stream)
+    scr = weights_dst;
+    dirty = true;
+  }
+  long long bytes = ingest_stack(image_dst, image, scr, false, s);
+  bytes += ingest_stack(weights_dst, weights, embed_scratch_, dirty, s);
+  return bytes;
+}
+
+void Engine::wait_for_caller(void* caller_stream) {
+  if (!caller_stream) return;
+  be::set_device(device_);
+  if (!caller_ev_) caller_ev_ = be::event_create_sync();
+  be::event_record(caller_ev_, (be::stream_t)caller_stream);
+  be::stream_wait_event(stream_, caller_ev_);
+  if (upload_stream_) be::stream_wait_event(upload_stream_, caller_ev_);
 }
 
 void Engine::alloc_view(ViewSlot& s) {
@@ -1357,6 +1461,39 @@ void Engine::set_view(int v, const float* image, const float* weights, const flo
   s.set = true;
 }
 
+void Engine::set_view_described(int v, const StackRef& image, const StackRef& weights, const float* kernel1,
+                                const int* k1dims, const float* kernel2, const int* k2dims) {
+  if (v < 0 || v >= (int)views_.size()) throw std::out_of_range("mvn: view index");
+  be::set_device(device_);
+  if (stream_pos_[(size_t)v] >= 0) throw std::logic_error("mvn: a streamed view is staged by the pipelined call only");
+  ViewSlot& s = views_[(size_t)v];
+  alloc_view(s);
+  ingest_pair(s.image, s.weights, image, weights, stream_);
+  be::stream_sync(stream_);  // the sources have been consumed
+  // the PSFs exactly as set_view prepares them
+  const float* ks[2] = {kernel1, kernel2};
+  const int* kd[2] = {k1dims, k2dims};
+  for (int i = 0; i < 2; ++i) {
+    if (psf_resident(s, i, ks[i], kd[i])) continue;
+    const size_t kb = sizeof(float) * (size_t)kd[i][0] * (size_t)kd[i][1] * (size_t)kd[i][2];
+    float* dk = (float*)be::dmalloc(kb);
+    be::h2d(dk, ks[i], kb, stream_);
+    try {
+      work_has_psi_spectrum_ = false;
+      prepare_psf(s, i, dk, kd[i], work_, false, stream_);
+      if (s.tap_k[i]) ensure_work2();
+    } catch (...) {
+      be::stream_sync(stream_);
+      be::dfree(dk);
+      s.kcopy[i].clear();
+      throw;
+    }
+    be::stream_sync(stream_);
+    be::dfree(dk);
+  }
+  s.set = true;
+}
+
 // ---- pipelined staging ------------------------------------------------------------------------
 void Engine::reserve_views(const kernel_list_t& kernels) {
   be::set_device(device_);
@@ -1367,6 +1504,7 @@ void Engine::reserve_views(const kernel_list_t& kernels) {
   for (size_t v = 0; v < views_.size(); ++v)
     if (!staged_ev_[v]) staged_ev_[v] = be::event_create_sync();
   staged_.assign(views_.size(), 0);
+  pre_ingested_.assign(views_.size(), 0);
   {
     std::lock_guard<std::mutex> lk(stage_mu_);
     uploads_ = consumed_ = 0;
@@ -1391,6 +1529,31 @@ void Engine::stage_view(int v, const float* image, const float* weights, const f
     upload_volume(s.image, image, upload_stream_);
     upload_volume(s.weights, weights, upload_stream_);
   }
+  stage_psfs(v, kernel1, k1dims, kernel2, k2dims);
+}
+
+void Engine::ingest_device_view(int v, const StackRef& image, const StackRef& weights) {
+  be::set_device(device_);
+  ViewSlot& s = views_[(size_t)v];
+  if (stream_pos_[(size_t)v] >= 0) throw std::logic_error("mvn: a call with stacks in device memory runs resident");
+  ingest_pair(s.image, s.weights, image, weights, stream_);
+  pre_ingested_[(size_t)v] = 1;
+}
+
+void Engine::stage_view_described(int v, const StackRef& image, const StackRef& weights, const float* kernel1,
+                                  const int* k1dims, const float* kernel2, const int* k2dims) {
+  be::set_device(device_);
+  ViewSlot& s = views_[(size_t)v];
+  if (stream_pos_[(size_t)v] >= 0)
+    ring_upload(v, nullptr, nullptr, &image, &weights);
+  else if (!pre_ingested_[(size_t)v])
+    ingest_pair(s.image, s.weights, image, weights, upload_stream_);
+  stage_psfs(v, kernel1, k1dims, kernel2, k2dims);
+}
+
+// uploader thread: the PSFs of view v on the upload stream, then the view is staged
+void Engine::stage_psfs(int v, const float* kernel1, const int* k1dims, const float* kernel2, const int* k2dims) {
+  ViewSlot& s = views_[(size_t)v];
   const float* ks[2] = {kernel1, kernel2};
   const int* kd[2] = {k1dims, k2dims};
   for (int i = 0; i < 2; ++i) {
@@ -1489,7 +1652,8 @@ void Engine::set_residency(const std::vector<int>& streamed, int ring) {
   be::stream_sync(stream_);
 }
 
-void Engine::ring_upload(int v, const float* image, const float* weights) {
+void Engine::ring_upload(int v, const float* image, const float* weights, const StackRef* dimage,
+                         const StackRef* dweights) {
   if (stream_pos_[(size_t)v] < 0) throw std::logic_error("mvn: view " + std::to_string(v) + " is resident");
   const long R = (long)ring_.size();
   long k;
@@ -1502,10 +1666,15 @@ void Engine::ring_upload(int v, const float* image, const float* weights) {
   }
   RingSlot& r = ring_[(size_t)(k % R)];
   if (k >= R) be::stream_wait_event(upload_stream_, r.freed);
-  upload_volume(r.image, image, upload_stream_);
-  upload_volume(r.weights, weights, upload_stream_);
+  if (dimage) {
+    if (dimage->device || dweights->device) throw std::logic_error("mvn: a call with stacks in device memory runs resident");
+    g_stream_bytes += ingest_pair(r.image, r.weights, *dimage, *dweights, upload_stream_);
+  } else {
+    upload_volume(r.image, image, upload_stream_);
+    upload_volume(r.weights, weights, upload_stream_);
+    g_stream_bytes += (long long)(2 * host_floats() * sizeof(float));
+  }
   be::event_record(r.filled, upload_stream_);
-  g_stream_bytes += (long long)(2 * host_floats() * sizeof(float));
   {
     std::lock_guard<std::mutex> lk(stage_mu_);
     ++uploads_;
@@ -1517,6 +1686,12 @@ void Engine::stream_view(int v, const float* image, const float* weights) {
   if (v < 0 || v >= (int)views_.size()) throw std::out_of_range("mvn: view index");
   be::set_device(device_);
   ring_upload(v, image, weights);
+}
+
+void Engine::stream_view_described(int v, const StackRef& image, const StackRef& weights) {
+  if (v < 0 || v >= (int)views_.size()) throw std::out_of_range("mvn: view index");
+  be::set_device(device_);
+  ring_upload(v, nullptr, nullptr, &image, &weights);
 }
 
 void Engine::abort_streaming() {
@@ -1635,6 +1810,53 @@ void Engine::get_psi(float* host) {
   else
     be::d2h_2d(host, (size_t)L.d2 * sizeof(float), psi_, (size_t)L.RP * sizeof(float),
                (size_t)L.d2 * sizeof(float), L.rows, stream_);
+  be::stream_sync(stream_);
+}
+
+void Engine::set_psi_described(const StackRef& st) {
+  if (st.u16) throw std::invalid_argument("mvn: psi is float32");
+  be::set_device(device_);
+  psi_spec_valid_ = false;
+  ingest_stack(psi_, st, embed_scratch_, false, stream_);
+  be::stream_sync(stream_);
+}
+
+void Engine::get_psi_described(const StackRef& st) {
+  if (st.u16) throw std::invalid_argument("mvn: psi is float32");
+  be::set_device(device_);
+  const Layout& L = plan_->L;
+  const int* n = host_dims_;
+  for (int d = 0; d < 3; ++d)
+    if (n[d] > 1 && st.stride[d] <= 0) throw std::invalid_argument("mvn: psi needs positive strides");
+  ExtractParams e;
+  e.src = psi_, e.RP = L.RP, e.D1 = L.d1;
+  e.n0 = n[0], e.n1 = n[1], e.n2 = n[2];
+  e.o0 = host_off_[0], e.o1 = host_off_[1], e.o2 = host_off_[2];
+  if (st.device) {  // straight into the caller's memory
+    e.dst = (float*)st.ptr, e.s0 = st.stride[0], e.s1 = st.stride[1], e.s2 = st.stride[2];
+    be::launch_extract3d(e, stream_);
+    be::stream_sync(stream_);
+    return;
+  }
+  check_host_rows(st, n);
+  const bool dense = (n[1] == 1 || st.stride[1] == n[2]) && (n[0] == 1 || st.stride[0] == (long long)n[1] * n[2]);
+  if (dense) {
+    get_psi((float*)st.ptr);
+    return;
+  }
+  const char* src = (const char*)psi_;
+  size_t srow = (size_t)L.RP * sizeof(float), splane = (size_t)L.d1 * srow;
+  if (embedded_) {
+    if (!embed_scratch_) throw std::logic_error("mvn: no scratch for a host stack");
+    e.dst = embed_scratch_, e.s0 = (long long)n[1] * n[2], e.s1 = n[2], e.s2 = 1;
+    be::launch_extract3d(e, stream_);
+    src = (const char*)embed_scratch_;
+    srow = (size_t)n[2] * sizeof(float), splane = (size_t)n[1] * srow;
+  }
+  const size_t width = (size_t)n[2] * sizeof(float);
+  for (int z = 0; z < n[0]; ++z)
+    be::d2h_2d((char*)st.ptr + (long long)z * st.stride[0] * 4, n[1] == 1 ? width : (size_t)st.stride[1] * 4,
+               src + z * splane, srow, width, (size_t)n[1], stream_);
   be::stream_sync(stream_);
 }
 

@@ -307,6 +307,22 @@ struct MemoryQuery {
   int stats_rows = 0;  // convergence statistics on: the iterations of the call (Engine::iterate), else 0
 };
 
+// A stack as the described entry points take it (mvn_stack_desc, include/mvn_engine_api.h): where element (0, 0, 0)
+// lives, what it is made of and how far apart its elements are.  Extents are the engine's embedding window.
+struct StackRef {
+  const void* ptr = nullptr;
+  bool u16 = false;     // uint16 elements (images only), else float32
+  bool device = false;  // device memory: the ingest / extract kernels work on it directly
+  long long stride[3] = {0, 0, 0};  // in elements; all zero: one value for every voxel (inputs only)
+  bool broadcast() const { return stride[0] == 0 && stride[1] == 0 && stride[2] == 0; }
+  static StackRef dense_host(const float* p, const int* dims) {
+    StackRef r;
+    r.ptr = p;
+    r.stride[0] = (long long)dims[1] * dims[2], r.stride[1] = dims[2], r.stride[2] = 1;
+    return r;
+  }
+};
+
 class Engine {
  public:
   Engine(int device, const shape_t& dims, int num_views);
@@ -345,6 +361,23 @@ class Engine {
                 const int* k1dims, const float* kernel2, const int* k2dims);
   void set_psi(const float* host);
   void get_psi(float* host);
+
+  // The same three for described stacks (StackRef; mvn_ingest.hpp): a stack in device memory is read by the ingest
+  // pass where it lies, one in host memory crosses PCIe as it is (uint16 as uint16; rows must be contiguous) and is
+  // then converted and embedded by the same pass.  Blocking.
+  void set_view_described(int v, const StackRef& image, const StackRef& weights, const float* kernel1,
+                          const int* k1dims, const float* kernel2, const int* k2dims);
+  void set_psi_described(const StackRef& psi);
+  void get_psi_described(const StackRef& psi);
+  // the caller produced its device stacks on `caller_stream`: the engine's streams wait for what is enqueued there
+  // now (an event, no host wait); nullptr: nothing to wait for
+  void wait_for_caller(void* caller_stream);
+  // described ABI call, main thread, after reserve_views(): a view whose two stacks are both in device memory is
+  // ingested on the compute stream (nothing to hide behind an upload); stage_view_described then only prepares its PSFs
+  void ingest_device_view(int v, const StackRef& image, const StackRef& weights);
+  void stage_view_described(int v, const StackRef& image, const StackRef& weights, const float* kernel1,
+                            const int* k1dims, const float* kernel2, const int* k2dims);
+  void stream_view_described(int v, const StackRef& image, const StackRef& weights);
 
   // Pipelined staging for the blocking ABI call (what the reference's "interleaved" driver was
   // after, src/gpu_deconvolve_methods.cuh:82-326): a second host thread uploads view after view
@@ -443,7 +476,9 @@ class Engine {
   // rest of which holds zeros: set_view / stage_view / set_psi embed, get_psi crops (the
   // reference's zero_padd policy, inc/padd_utils.h:121-190, without the host-side staging
   // copies).  dims == engine extents and off == 0 is the dense default.
-  void set_embedding(const int dims[3], const int off[3]);
+  // scratch = false: no stack of the call passes through host-shaped device scratch (all of them are in device
+  // memory or broadcast), so none is kept.
+  void set_embedding(const int dims[3], const int off[3], bool scratch = true);
   // quotient 0 wherever the view is exactly 0 (see EpilogueParams::guard_zero_view)
   void set_quotient_guard(bool on) { quotient_guard_ = on; }
   // the PSF form rule on this engine's plan, with the switches read when the engine was built
@@ -476,10 +511,24 @@ class Engine {
   void conv_pair(int v, double lambda, float min_value, int final_mode, int accumulate,
                  bool feed_next);
   void upload_volume(float* dst, const float* host, be::stream_t s);
+  // one described stack into volume `dst` on stream s; `scratch`: where a host stack that needs converting or embedding
+  // lands first; dst_dirty: dst has been used as such a scratch since its padding was cleared.  Returns the bytes
+  // that crossed PCIe.
+  long long ingest_stack(float* dst, const StackRef& st, float* scratch, bool dst_dirty, be::stream_t s);
+  // image and weights of one view; without an embedding scratch a uint16 image lands in the weights volume first
+  long long ingest_pair(float* image_dst, float* weights_dst, const StackRef& image, const StackRef& weights,
+                        be::stream_t s);
+  void stage_psfs(int v, const float* kernel1, const int* k1dims, const float* kernel2, const int* k2dims);
+  std::vector<char> pre_ingested_;  // per view: ingest_device_view has taken its stacks
+  be::event_t caller_ev_ = nullptr;
   bool embedded_ = false;
   int host_dims_[3] = {0, 0, 0}, host_off_[3] = {0, 0, 0};
   float* embed_scratch_ = nullptr;  // one dense host-shaped stack: H2D lands here, a strided device copy embeds it
   size_t host_floats() const { return (size_t)host_dims_[0] * host_dims_[1] * host_dims_[2]; }
+ public:
+  // floats of the embedding scratch this engine holds now (0: none) - what the memory planner prices it by
+  size_t scratch_floats() const { return embed_scratch_ ? host_floats() : 0; }
+ private:
   void alloc_view(ViewSlot& s);
   // PSF spectrum of slot array `spec` from a device-resident kernel: forward transform, then (where
   // the plan wants it) the tile-contiguous re-ordering through `scratch` (one volume)
@@ -596,7 +645,9 @@ class Engine {
   MvnStatsParams stats_for(int v) const;
   void stats_free();
   int iterate_sweeps(int iterations, double lambda, float min_value, double tolerance, std::vector<double>* stats);
-  void ring_upload(int v, const float* image, const float* weights);  // uploader thread
+  // uploader thread (described: the stacks as StackRefs instead)
+  void ring_upload(int v, const float* image, const float* weights, const StackRef* dimage = nullptr,
+                   const StackRef* dweights = nullptr);
   void ring_acquire(ViewSlot& s);                                     // main thread, before the view update
   void ring_release(ViewSlot& s);                                     // main thread, after it
   float* psi_ = nullptr;

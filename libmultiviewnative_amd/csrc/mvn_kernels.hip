@@ -239,6 +239,17 @@ __global__ void k_copy3d(float* __restrict__ dst, long drow, long dplane, const 
   }
 }
 
+// a caller's stack into the engine volume / psi's window back out (mvn_ingest.hpp): pure streaming, a handful of
+// registers, 4 waves per workgroup so that 8 workgroups fill a CU's wave slots
+template <typename T>
+__global__ __launch_bounds__(MVN_INGEST_WG) void k_ingest3d(const IngestParams p) {
+  mvn_ingest_rows<T>(p, (long)blockIdx.x, (int)threadIdx.x);
+}
+
+__global__ __launch_bounds__(MVN_INGEST_WG) void k_extract3d(const ExtractParams p) {
+  mvn_extract_rows(p, (long)blockIdx.x, (int)threadIdx.x);
+}
+
 __global__ void k_divide(const float* __restrict__ view, float* __restrict__ inout, size_t n) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
@@ -392,6 +403,21 @@ void copy_peer(void* dst, int dst_dev, const void* src, int src_dev, size_t byte
     HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, hs(s)));
   else
     HIP_CHECK(hipMemcpyPeerAsync(dst, dst_dev, src, src_dev, bytes, hs(s)));
+}
+
+int pointer_device(const void* p) {
+  hipPointerAttribute_t attr;
+  std::memset(&attr, 0, sizeof(attr));
+  const hipError_t e = hipPointerGetAttributes(&attr, p);
+  if (e != hipSuccess) {  // (memory the runtime has never seen: plain host memory)
+    (void)hipGetLastError();
+    return POINTER_HOST;
+  }
+  switch (attr.type) {
+    case hipMemoryTypeDevice: return attr.device;
+    case hipMemoryTypeManaged: return POINTER_ANY;
+    default: return POINTER_HOST;
+  }
 }
 
 stream_t stream_create() {
@@ -901,6 +927,23 @@ void launch_copy3d(float* dst, long drow, long dplane, const float* src, long sr
   const unsigned grid = (unsigned)(rows < 256L * 32 ? rows : 256L * 32);
   hipLaunchKernelGGL(k_copy3d, dim3(grid), dim3(block), 0, hs(s), dst, drow, dplane, src, srow, splane,
                      nx, ny, nz);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_ingest3d(const IngestParams& p, bool u16, stream_t s) {
+  const long nblocks = mvn_ingest_blocks(p.rows);
+  if (nblocks < 1 || nblocks > 0x7fffffffL) throw std::invalid_argument("mvn: grid size out of range");
+  if (u16)
+    hipLaunchKernelGGL(k_ingest3d<uint16_t>, dim3((unsigned)nblocks), dim3(MVN_INGEST_WG), 0, hs(s), p);
+  else
+    hipLaunchKernelGGL(k_ingest3d<float>, dim3((unsigned)nblocks), dim3(MVN_INGEST_WG), 0, hs(s), p);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_extract3d(const ExtractParams& p, stream_t s) {
+  const long nblocks = mvn_extract_blocks(p);
+  if (nblocks < 1 || nblocks > 0x7fffffffL) throw std::invalid_argument("mvn: grid size out of range");
+  hipLaunchKernelGGL(k_extract3d, dim3((unsigned)nblocks), dim3(MVN_INGEST_WG), 0, hs(s), p);
   HIP_CHECK(hipGetLastError());
 }
 

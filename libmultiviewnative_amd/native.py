@@ -12,7 +12,7 @@ import os
 
 import numpy as np
 
-from .abi import Workspace, c_float_p, c_int_p, fptr, iptr
+from .abi import CallDesc, StackDesc, ViewData, Workspace, c_float_p, c_int_p, describe_stack, fptr, iptr
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(_HERE, "lib")
@@ -43,7 +43,23 @@ ENGINE_ABI_SYMBOLS = [
     "mvn_slab_buffer_sizes", "mvn_slab_buffers", "mvn_slab_bind_buffers", "mvn_slab_begin",
     "mvn_slab_pack", "mvn_slab_mid", "mvn_slab_unpack", "mvn_slab_sync", "mvn_slab_stream",
     "mvn_set_convergence", "mvn_get_convergence", "mvn_last_convergence", "mvn_engine_iterate_converge",
+    "mvn_deconvolve_described", "mvn_engine_set_view_described", "mvn_engine_set_psi_described",
+    "mvn_engine_get_psi_described",
 ]
+
+
+def _caller_stream(tensors):
+    """The hipStream_t the device tensors among `tensors` were produced on (torch's current stream of their device), or
+    None.  Work on the legacy default stream is waited for here: NULL means 'complete' to the library."""
+    dev = [t for t in tensors if not isinstance(t, np.ndarray) and getattr(t, "is_cuda", False)]
+    if not dev:
+        return None
+    import torch
+    s = torch.cuda.current_stream(dev[0].device)
+    if not s.cuda_stream:
+        s.synchronize()
+        return None
+    return s.cuda_stream
 
 
 class MvnError(RuntimeError):
@@ -93,6 +109,12 @@ class Binding:
         l.inplace_gpu_deconvolve.restype = None
         l.mvn_deconvolve_submit.argtypes = [c_float_p, Workspace, C.c_int, C.POINTER(C.c_longlong)]
         l.mvn_deconvolve_wait.argtypes = [C.c_longlong]
+        sd = C.POINTER(StackDesc)
+        l.mvn_deconvolve_described.argtypes = [C.c_void_p, Workspace, C.POINTER(CallDesc), C.c_int]
+        l.mvn_engine_set_view_described.argtypes = [C.c_void_p, C.c_int, C.c_void_p, sd, C.c_void_p, sd, c_float_p, i3,
+                                                    c_float_p, i3, C.c_void_p]
+        l.mvn_engine_set_psi_described.argtypes = [C.c_void_p, C.c_void_p, sd, C.c_void_p]
+        l.mvn_engine_get_psi_described.argtypes = [C.c_void_p, C.c_void_p, sd]
         for n in ("inplace_gpu_convolution", "convolution3DfftCUDAInPlace"):
             getattr(l, n).argtypes = [c_float_p, c_int_p, c_float_p, c_int_p, C.c_int]
             getattr(l, n).restype = None
@@ -258,6 +280,63 @@ class Binding:
                 self.set_pad_mode(before)
         return out
 
+    def describe_call(self, psi, views, weights, kernels1, kernels2, lambda_, min_value, iterations,
+                      int16_is_uint16=False):
+        """The arguments of mvn_deconvolve_described for these objects, as a DescribedCall: `.desc` (mvn_call_desc),
+        `.image` / `.weights` (its mvn_stack_desc arrays), `.ws` (the workspace); `.run(device)` makes the call.
+        See deconvolve_described for what the objects may be."""
+        n = len(views)
+        if not (len(weights) == n and len(kernels1) == n and len(kernels2) == n):
+            raise ValueError("one weights stack and two kernels per view")
+        c = DescribedCall()
+        c.binding, c.psi = self, psi
+        c.keep = [[np.ascontiguousarray(k, dtype=np.float32) for k in ks] for ks in (kernels1, kernels2)]
+        k1, k2 = c.keep
+        c.psi_ptr, p_desc, shape, p_dev = describe_stack(psi)
+        c.image, c.weights = (StackDesc * n)(), (StackDesc * n)()
+        data = (ViewData * n)()
+        devices = [p_dev]
+        for v in range(n):
+            i_ptr, c.image[v], i_shape, i_dev = describe_stack(views[v], int16_is_uint16)
+            w_ptr, c.weights[v], w_shape, w_dev = describe_stack(weights[v])
+            if i_shape != shape or w_shape != shape:
+                raise ValueError("view %d: every stack has psi's shape %r" % (v, shape))
+            devices += [i_dev, w_dev]
+            dims = [np.array(s_, dtype=np.int32) for s_ in (shape, k1[v].shape, k2[v].shape, shape)]
+            c.keep.append(dims)
+            d = data[v]
+            d.image_, d.weights_ = C.cast(C.c_void_p(i_ptr), c_float_p), C.cast(C.c_void_p(w_ptr), c_float_p)
+            d.kernel1_, d.kernel2_ = fptr(k1[v]), fptr(k2[v])
+            d.image_dims_, d.kernel1_dims_, d.kernel2_dims_, d.weights_dims_ = [iptr(x) for x in dims]
+        c.keep += [data, list(views), list(weights)]
+        c.ws = Workspace()
+        c.ws.data_ = C.cast(data, C.POINTER(ViewData))
+        c.ws.num_views_, c.ws.lambda_, c.ws.minValue_, c.ws.num_iterations_ = (
+            n, float(lambda_), float(min_value), int(iterations))
+        c.desc = CallDesc()
+        c.desc.psi = p_desc
+        c.desc.image = C.cast(c.image, C.POINTER(StackDesc))
+        c.desc.weights = C.cast(c.weights, C.POINTER(StackDesc))
+        owners = [x for x in devices if x is not None]
+        c.device = owners[0] if owners else 0
+        return c
+
+    def deconvolve_described(self, psi, views, weights, kernels1, kernels2, lambda_, min_value, iterations,
+                             device=None, int16_is_uint16=False):
+        """mvn_deconvolve_described: inplace_gpu_deconvolve on stacks as the caller has them.  psi, every view and
+        every weights stack may be a numpy array (float32; views also uint16; any strides that are multiples of the
+        item size) or a torch tensor (CPU or cuda; uint16 views as torch.uint16 - a torch without that type may pass
+        torch.int16 tensors holding the same bits with int16_is_uint16=True, otherwise int16 is refused); pointer,
+        element type, location and strides are taken from the object, the stream from torch.cuda.current_stream()
+        when a tensor is on the device - the stacks need not be complete on the host's side, only enqueued on that
+        stream.  Stacks in host memory need contiguous rows, or strides of 0 throughout (np.broadcast_to of a scalar:
+        constant weights).  psi (float32, non-overlapping) is updated in place and returned; the process-wide padding
+        policy applies.  Kernels are dense float32 host arrays.
+        torch is imported only when a tensor is passed, and the rule of INTEGRATION.md section 3 is the caller's:
+        import torch BEFORE this library is loaded in the process."""
+        return self.describe_call(psi, views, weights, kernels1, kernels2, lambda_, min_value, iterations,
+                                  int16_is_uint16).run(device)
+
     def deconvolve_submit(self, psi, holder, device=0):
         """mvn_deconvolve_submit: starts inplace_gpu_deconvolve on `psi` (C-contiguous float32, updated in
         place by the time deconvolve_wait returns) and returns the ticket.  `psi` and `holder` must be
@@ -384,6 +463,18 @@ class Binding:
         return GroupHandle(self, devices, shape, halo_planes, num_views)
 
 
+class DescribedCall:
+    """One prepared mvn_deconvolve_described call (Binding.describe_call); keeps what its pointers refer to alive."""
+
+    def run(self, device=None):
+        """makes the call (blocking); psi is updated in place and returned"""
+        self.desc.stream = _caller_stream([self.psi] + self.keep[-2] + self.keep[-1])
+        b = self.binding
+        b.check(b.l.mvn_deconvolve_described(C.c_void_p(self.psi_ptr), self.ws, C.byref(self.desc),
+                                             int(self.device if device is None else device)))
+        return self.psi
+
+
 class GroupHandle:
     """One volume as dim0 slabs on several devices of this process (``mvn_group_*``; what MVN_DEVICES runs inside
     ``inplace_gpu_deconvolve``), stacks resident between ``load`` and ``get_psi``."""
@@ -450,20 +541,71 @@ class EngineHandle:
         except Exception:
             pass
 
+    @staticmethod
+    def _stack(x):
+        """A stack as the engine's symbols take it: a tensor as it is; anything else as a numpy array - float32 or
+        uint16, and copied to a dense one where the described symbols would refuse its layout in host memory (rows
+        that are not contiguous, negative strides), as these methods always did."""
+        if not isinstance(x, np.ndarray) and hasattr(x, "data_ptr"):
+            return x
+        a = np.asarray(x)
+        if a.dtype != np.uint16 and a.dtype != np.float32:
+            return np.ascontiguousarray(a, dtype=np.float32)
+        it = a.itemsize
+        ok = a.ndim == 3 and (all(st == 0 for st in a.strides) or (
+            all(st >= 0 and st % it == 0 for st in a.strides) and (a.shape[2] == 1 or a.strides[2] == it)
+            and (a.shape[1] == 1 or a.strides[1] >= a.shape[2] * it)))
+        return a if ok else np.ascontiguousarray(a)
+
+    @staticmethod
+    def _plain(a):
+        return isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags["C_CONTIGUOUS"]
+
     def set_view(self, v, image, weights, kernel1, kernel2):
-        a = [np.ascontiguousarray(x, dtype=np.float32) for x in (image, weights, kernel1, kernel2)]
-        assert a[0].shape == self.shape and a[1].shape == self.shape
-        self.b.check(self.b.l.mvn_engine_set_view(self.h, v, fptr(a[0]), fptr(a[1]), fptr(a[2]),
-                                                  _dims(a[2].shape), fptr(a[3]), _dims(a[3].shape)))
+        """image / weights: dense float32 arrays (the plain symbol), or anything Binding.deconvolve_described takes -
+        uint16, strided, torch tensors on the host or the device (mvn_engine_set_view_described)."""
+        k = [np.ascontiguousarray(x, dtype=np.float32) for x in (kernel1, kernel2)]
+        image, weights = self._stack(image), self._stack(weights)
+        if self._plain(image) and self._plain(weights):
+            assert image.shape == self.shape and weights.shape == self.shape
+            self.b.check(self.b.l.mvn_engine_set_view(self.h, v, fptr(image), fptr(weights), fptr(k[0]),
+                                                      _dims(k[0].shape), fptr(k[1]), _dims(k[1].shape)))
+            return
+        i_ptr, i_desc, i_shape, _ = describe_stack(image)
+        w_ptr, w_desc, w_shape, _ = describe_stack(weights)
+        assert i_shape == self.shape and w_shape == self.shape
+        self.b.check(self.b.l.mvn_engine_set_view_described(
+            self.h, v, C.c_void_p(i_ptr), C.byref(i_desc), C.c_void_p(w_ptr), C.byref(w_desc), fptr(k[0]),
+            _dims(k[0].shape), fptr(k[1]), _dims(k[1].shape), _caller_stream([image, weights])))
 
     def set_psi(self, psi):
-        p = np.ascontiguousarray(psi, dtype=np.float32)
-        assert p.shape == self.shape
-        self.b.check(self.b.l.mvn_engine_set_psi(self.h, fptr(p)))
+        psi = self._stack(psi)
+        if isinstance(psi, np.ndarray) and psi.dtype == np.uint16:
+            psi = psi.astype(np.float32)
+        if self._plain(psi):
+            assert psi.shape == self.shape
+            self.b.check(self.b.l.mvn_engine_set_psi(self.h, fptr(psi)))
+            return
+        ptr, desc, shape, _ = describe_stack(psi)
+        assert shape == self.shape
+        self.b.check(self.b.l.mvn_engine_set_psi_described(self.h, C.c_void_p(ptr), C.byref(desc),
+                                                           _caller_stream([psi])))
 
-    def get_psi(self):
-        out = np.empty(self.shape, np.float32)
-        self.b.check(self.b.l.mvn_engine_get_psi(self.h, fptr(out)))
+    def get_psi(self, out=None):
+        """A new dense float32 array, or psi written into `out`: a float32 numpy array (any non-overlapping strides
+        with contiguous rows) or torch tensor (host or device), which is returned.  The call is blocking and has no
+        stream of the caller's to order itself behind: for a tensor on the device, torch's current stream of that
+        device is synchronised first, so that work enqueued there on `out` has ended before the library writes."""
+        if out is None:
+            out = np.empty(self.shape, np.float32)
+            self.b.check(self.b.l.mvn_engine_get_psi(self.h, fptr(out)))
+            return out
+        ptr, desc, shape, _ = describe_stack(out)
+        assert shape == self.shape
+        if not isinstance(out, np.ndarray) and getattr(out, "is_cuda", False):
+            import torch
+            torch.cuda.current_stream(out.device).synchronize()
+        self.b.check(self.b.l.mvn_engine_get_psi_described(self.h, C.c_void_p(ptr), C.byref(desc)))
         return out
 
     def iterate(self, iterations, lambda_, min_value, sync=True):
