@@ -132,6 +132,24 @@ MVN_API int mvn_get_convergence(double* tolerance);
  * its ticket.  *iterations_run = sweeps actually run; stats[3k..3k+2] = {S_k, M_k, P_k} for
  * k < min(capacity, rows); returns the number of rows available (0 when statistics were off), < 0 on error. */
 MVN_API int mvn_last_convergence(int* iterations_run, double* stats, int capacity);
+/* Acceleration of the Richardson-Lucy loop by vector extrapolation between sweeps (Biggs & Andrews 1997, first
+ * order).  With x_k the result of sweep k and y_{k-1} the estimate it started from (x_0 = y_0 = psi as handed in):
+ *   g_k = x_k - y_{k-1},   a_k = clamp(sum g_k g_{k-1} / sum g_{k-1} g_{k-1}, 0, 1)  (a_1 = 0; sums in double over
+ *   the engine's volume - the padded one under "zero" / "zero_exact"; 0 for an empty or non-finite ratio),
+ *   y_k = max(x_k + a_k (x_k - x_{k-1}), minValue)  (float32; y_1 = x_1),
+ * and sweep k + 1 starts from y_k.  No extrapolation follows the last sweep run: psi is always a sweep's own
+ * result x_k, so 1 or 2 iterations give the bits of the plain loop.  Convergence statistics keep their meaning (r_k
+ * is measured inside sweep k) and the tolerance stop works as without acceleration.  The loop needs three more
+ * volumes for the duration of the call (mvn_deconvolve_memory and the "auto" planner count them) and two streaming
+ * passes per sweep.  mode 0: off (default; launches and results as without this switch); 1: on; anything else is an
+ * error.  Process-wide, captured by inplace_gpu_deconvolve, mvn_deconvolve_submit and mvn_deconvolve_described at
+ * their start.  Multi-device calls (MVN_DEVICES) with acceleration on run on one device. */
+MVN_API int mvn_set_acceleration(int mode);
+MVN_API int mvn_get_acceleration(int* mode);
+/* The last deconvolution this THREAD completed (as mvn_last_convergence): alphas[k - 1] = a_k for the sweeps run,
+ * k - 1 < min(capacity, rows); the entry of the last sweep run is 0 (nothing followed it).  Returns the number of
+ * rows available (0 when acceleration was off), < 0 on error. */
+MVN_API int mvn_last_acceleration(double* alphas, int capacity);
 /* A resident engine keeps, per view slot, the PSF spectra of the last call together with host
  * copies of the kernels they were made from; a call (or mvn_engine_set_view) that brings
  * bytewise identical kernels for a slot re-uses the spectra (the reference's
@@ -205,6 +223,11 @@ MVN_API int mvn_engine_iterate(mvn_engine* e, int iterations, double lambda, flo
  * see mvn_set_convergence; tolerance as there, < 0 collects nothing) */
 MVN_API int mvn_engine_iterate_converge(mvn_engine* e, int iterations, double lambda, float min_value,
                                         double tolerance, int* iterations_run, double* stats);
+/* resident engine, blocking: `iterations` sweeps with the extrapolation of mvn_set_acceleration between them.
+ * tolerance, *iterations_run and stats as in mvn_engine_iterate_converge; alphas receives one double per sweep run
+ * (a_k, the last one 0).  stats and alphas may be NULL.  Refused by an engine in halo mode (a slab of a group). */
+MVN_API int mvn_engine_iterate_accelerated(mvn_engine* e, int iterations, double lambda, float min_value,
+                                           double tolerance, int* iterations_run, double* stats, double* alphas);
 /* simultaneous (Jacobi) mode, one step: delta = sum_v w_v (next_v - psi) over this engine's
  * views; the caller all-reduces the delta buffer across ranks, then applies it */
 MVN_API int mvn_engine_compute_delta(mvn_engine* e, double lambda, float min_value);

@@ -147,9 +147,14 @@ static std::atomic<double> g_conv_tol{-1.};
 // the tolerance of the call this thread runs (captured at submit); NaN outside a call: then the process-wide one
 static thread_local double t_call_tol = NAN;
 static double call_tolerance() { return std::isnan(t_call_tol) ? g_conv_tol.load() : t_call_tol; }
+// ---- acceleration (mvn_set_acceleration): captured at the start of a call, like the tolerance ----
+static std::atomic<int> g_accel{0};
+static thread_local int t_call_accel = -1;  // the mode of the call this thread runs; -1 outside a call
+static int call_accel() { return t_call_accel < 0 ? g_accel.load() : t_call_accel; }
 struct ConvRecord {
   int iterations_run = 0;
-  std::vector<double> rows;  // {S, M, P} per sweep run
+  std::vector<double> rows;    // {S, M, P} per sweep run
+  std::vector<double> alphas;  // acceleration on: a_k per sweep run
 };
 // the last deconvolution this thread completed (inplace_gpu_deconvolve, or the wait of a ticket)
 static thread_local ConvRecord t_last_conv;
@@ -159,6 +164,7 @@ static MemoryQuery memory_query(const shape_t& ext, const workspace& input, size
   q.ext = ext;
   q.embed_floats = embed_floats;
   q.stats_rows = call_tolerance() >= 0. ? std::max(input.num_iterations_, 1) : 0;
+  q.accel_rows = call_accel() ? std::max(input.num_iterations_, 1) : 0;
   q.kernels = call_kernels(input);
   return q;
 }
@@ -624,14 +630,29 @@ static bool plain_stack(const StackRef& r, const int* dims) {
 // does the stack pass through the engine's host-shaped scratch when the call embeds its stacks?
 static bool through_scratch(const StackRef& r) { return !r.device && !r.broadcast(); }
 
-static void deconvolve_call(imageType* psi, const workspace& input, int device, int lane, int pad_mode, double tol,
+// what a call captures at its start: the convergence tolerance and the acceleration mode
+struct LoopMode {
+  double tol = -1.;
+  int accel = 0;
+  static LoopMode current() {
+    LoopMode m;
+    m.tol = g_conv_tol.load();
+    m.accel = g_accel.load();
+    return m;
+  }
+};
+
+static void deconvolve_call(imageType* psi, const workspace& input, int device, int lane, int pad_mode, LoopMode mode,
                             ConvRecord* conv, const DescribedCall* dc = nullptr) {
+  const double tol = mode.tol;
+  const int accel = mode.accel;
   conv->iterations_run = 0;
   conv->rows.clear();
-  struct TolScope {  // (the memory model of this call counts the statistics buffers: memory_query)
-    explicit TolScope(double t) { t_call_tol = t; }
-    ~TolScope() { t_call_tol = NAN; }
-  } tol_scope(tol);
+  conv->alphas.clear();
+  struct LoopScope {  // (the memory model of this call counts the statistics and acceleration buffers: memory_query)
+    LoopScope(double t, int a) { t_call_tol = t, t_call_accel = a; }
+    ~LoopScope() { t_call_tol = NAN, t_call_accel = -1; }
+  } loop_scope(tol, accel);
   {
     check_workspace(psi, input);
     const int V = input.num_views_;
@@ -645,7 +666,9 @@ static void deconvolve_call(imageType* psi, const workspace& input, int device, 
         std::printf("[lmvn::trace] MVN_DEVICES: convergence statistics on - one device\n");
       if (!devs.empty() && dc && trace_on())
         std::printf("[lmvn::trace] MVN_DEVICES: described stacks - one device\n");
-      if (!devs.empty() && tol < 0. && !dc) {
+      // ... and no acceleration
+      if (!devs.empty() && accel && trace_on()) std::printf("[lmvn::trace] MVN_DEVICES: acceleration on - one device\n");
+      if (!devs.empty() && tol < 0. && !dc && !accel) {
         call_extents(input, pad_mode, -1, &dims, &ext, off);  // (the slabs run on plans of their own extents)
         if (multi_device_call(psi, input, dims, ext, off, pad_mode, devs)) return;
       }
@@ -686,7 +709,8 @@ static void deconvolve_call(imageType* psi, const workspace& input, int device, 
           eng.set_view(v, d.image_, d.weights_, d.kernel1_, d.kernel1_dims_, d.kernel2_, d.kernel2_dims_);
       }
       dc ? eng.set_psi_described(dc->psi) : eng.set_psi(psi);
-      conv->iterations_run = eng.iterate(input.num_iterations_, input.lambda_, input.minValue_, tol, &conv->rows);
+      conv->iterations_run = eng.iterate(input.num_iterations_, input.lambda_, input.minValue_, tol, &conv->rows, accel,
+                                         accel ? &conv->alphas : nullptr);
       eng.sync();
       dc ? eng.get_psi_described(dc->psi) : eng.get_psi(psi);
       give_back_engine(key, std::move(eng_owner));
@@ -750,7 +774,8 @@ static void deconvolve_call(imageType* psi, const workspace& input, int device, 
     });
     std::exception_ptr main_err;
     try {
-      conv->iterations_run = eng.iterate(input.num_iterations_, input.lambda_, input.minValue_, tol, &conv->rows);
+      conv->iterations_run = eng.iterate(input.num_iterations_, input.lambda_, input.minValue_, tol, &conv->rows, accel,
+                                         accel ? &conv->alphas : nullptr);
       if (conv->iterations_run < input.num_iterations_) eng.end_streaming();  // (an early stop)
     } catch (...) {
       main_err = std::current_exception();
@@ -773,16 +798,16 @@ static void deconvolve_call(imageType* psi, const workspace& input, int device, 
 
 void inplace_gpu_deconvolve(imageType* psi, struct workspace input, int device) {
   guarded("inplace_gpu_deconvolve", [&] {
-    const double tol = g_conv_tol.load();
-    deconvolve_call(psi, input, device, 0, current_pad_mode(), tol, &t_last_conv);
+    const LoopMode mode = LoopMode::current();
+    deconvolve_call(psi, input, device, 0, current_pad_mode(), mode, &t_last_conv);
   });
 }
 
 int mvn_deconvolve_described(void* psi, struct workspace input, const mvn_call_desc* desc, int device) {
   return guarded("mvn_deconvolve_described", [&] {
-    const double tol = g_conv_tol.load();
+    const LoopMode mode = LoopMode::current();
     if (!desc) {
-      deconvolve_call((imageType*)psi, input, device, 0, current_pad_mode(), tol, &t_last_conv);
+      deconvolve_call((imageType*)psi, input, device, 0, current_pad_mode(), mode, &t_last_conv);
       return;
     }
     check_workspace((const imageType*)psi, input);
@@ -808,7 +833,7 @@ int mvn_deconvolve_described(void* psi, struct workspace input, const mvn_call_d
       plain = plain && plain_stack(dc.image.back(), d.image_dims_) && plain_stack(dc.weights.back(), d.image_dims_);
     }
     if (plain) {  // today's layout throughout: today's call
-      deconvolve_call((imageType*)psi, input, device, 0, current_pad_mode(), tol, &t_last_conv);
+      deconvolve_call((imageType*)psi, input, device, 0, current_pad_mode(), mode, &t_last_conv);
       return;
     }
     dc.need_scratch = through_scratch(dc.psi);
@@ -824,7 +849,7 @@ int mvn_deconvolve_described(void* psi, struct workspace input, const mvn_call_d
       if (owner >= 0) device = owner;
       dc.device = device;
     }
-    deconvolve_call((imageType*)psi, input, device, 0, current_pad_mode(), tol, &t_last_conv, &dc);
+    deconvolve_call((imageType*)psi, input, device, 0, current_pad_mode(), mode, &t_last_conv, &dc);
   });
 }
 
@@ -838,7 +863,7 @@ struct DeconvJob {
   std::vector<view_data> views;  // the caller's view_data array and dims, copied at submit
   std::vector<int> dims;
   workspace ws;
-  double tol = -1.;  // the convergence tolerance at submit
+  LoopMode mode;     // the convergence tolerance and the acceleration mode at submit
   ConvRecord conv;   // moves into the waiting thread's record
 };
 std::mutex& jobs_mutex() {
@@ -875,7 +900,7 @@ int mvn_deconvolve_submit(imageType* psi, struct workspace input, int device, lo
     job->ws.data_ = job->views.data();
     const int dev = pick_device(device);
     const int pad_mode = current_pad_mode();  // the policy in force at submit time
-    job->tol = g_conv_tol.load();             // ... and the tolerance
+    job->mode = LoopMode::current();           // ... and the tolerance and the acceleration mode
     static std::atomic<long long> next_ticket{1};
     const long long id = next_ticket.fetch_add(1);
     static std::mutex lane_mu;
@@ -889,7 +914,7 @@ int mvn_deconvolve_submit(imageType* psi, struct workspace input, int device, lo
     // (the worker first, the map entry second: a thread that cannot be started leaves no job behind)
     j->worker = std::thread([j, psi, dev, lane, pad_mode] {
       j->rc = guarded("mvn_deconvolve_submit (worker)",
-                      [&] { deconvolve_call(psi, j->ws, dev, lane, pad_mode, j->tol, &j->conv); });
+                      [&] { deconvolve_call(psi, j->ws, dev, lane, pad_mode, j->mode, &j->conv); });
       if (j->rc < 0) j->error = g_last_error;  // the worker's thread-local message travels with the job
     });
     try {
@@ -944,6 +969,32 @@ int mvn_last_convergence(int* iterations_run, double* stats, int capacity) {
     rows = (int)(c.rows.size() / 3);
     const size_t n = 3 * (size_t)std::min(rows, capacity);
     if (n) std::memcpy(stats, c.rows.data(), n * sizeof(double));
+  });
+  return rc < 0 ? rc : rows;
+}
+
+int mvn_set_acceleration(int mode) {
+  return guarded("mvn_set_acceleration", [&] {
+    if (mode != 0 && mode != 1) throw std::invalid_argument("acceleration mode must be 0 (off) or 1 (vector extrapolation)");
+    g_accel.store(mode);
+  });
+}
+
+int mvn_get_acceleration(int* mode) {
+  return guarded("mvn_get_acceleration", [&] {
+    if (!mode) throw std::invalid_argument("null mode");
+    *mode = g_accel.load();
+  });
+}
+
+int mvn_last_acceleration(double* alphas, int capacity) {
+  int rows = 0;
+  const int rc = guarded("mvn_last_acceleration", [&] {
+    if (capacity < 0 || (capacity > 0 && !alphas)) throw std::invalid_argument("bad alpha buffer");
+    const ConvRecord& c = t_last_conv;
+    rows = (int)c.alphas.size();
+    const size_t n = (size_t)std::min(rows, capacity);
+    if (n) std::memcpy(alphas, c.alphas.data(), n * sizeof(double));
   });
   return rc < 0 ? rc : rows;
 }
@@ -1766,6 +1817,18 @@ int mvn_engine_iterate_converge(mvn_engine* e, int iterations, double lambda, fl
     const int ran = E.iterate(iterations, lambda, min_value, tolerance, &rows);
     if (iterations_run) *iterations_run = ran;
     if (!rows.empty()) std::memcpy(stats, rows.data(), rows.size() * sizeof(double));
+  });
+}
+
+int mvn_engine_iterate_accelerated(mvn_engine* e, int iterations, double lambda, float min_value, double tolerance,
+                                   int* iterations_run, double* stats, double* alphas) {
+  MVN_ENGINE_CALL("mvn_engine_iterate_accelerated", {
+    if (std::isnan(tolerance)) throw std::invalid_argument("tolerance is NaN");
+    std::vector<double> rows, al;
+    const int ran = E.iterate(iterations, lambda, min_value, tolerance, &rows, 1, alphas ? &al : nullptr);
+    if (iterations_run) *iterations_run = ran;
+    if (stats && !rows.empty()) std::memcpy(stats, rows.data(), rows.size() * sizeof(double));
+    if (alphas && !al.empty()) std::memcpy(alphas, al.data(), al.size() * sizeof(double));
   });
 }
 

@@ -14,6 +14,7 @@
 #include "mvn_dim0_direct.hpp"
 #include "mvn_mid_fused.hpp"
 #include "mvn_ingest.hpp"
+#include "mvn_extrapolate.hpp"
 
 namespace mvn {
 namespace be {
@@ -98,6 +99,11 @@ void launch_rows_c2r_r2c(const RowsParams& p, long ntiles, int nthreads, size_t 
 void launch_convergence_reduce(const double* rec, const unsigned* counts, int nviews, long cap, double* out,
                                stream_t s);
 long split_launch_count();
+// vector extrapolation between sweeps (mvn_extrapolate.hpp): pass A with its records, the reduction of `nrec` records
+// into the device word *alpha, pass B
+void launch_accel_a(const AccelParams& p, stream_t s);
+void launch_accel_reduce(const double* rec, long nrec, float* alpha, stream_t s);
+void launch_accel_b(const AccelParams& p, stream_t s);
 // launches of the fused middle pass (mvn_mid_fused.hpp) since process start
 long mid_fused_launch_count();
 // `rider` (plain fixed-length passes only): a second pass of the same mode with tiles of ONE line (T = 1, run-time

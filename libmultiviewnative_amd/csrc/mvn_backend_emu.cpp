@@ -610,6 +610,10 @@ void launch_extract3d(const ExtractParams& p, stream_t) {
     for (int t = 0; t < MVN_INGEST_WG; ++t) mvn_extract_rows(p, blk, t);
 }
 
+void launch_accel_a(const AccelParams& p, stream_t) { mvn_accel_host_a(p); }
+void launch_accel_reduce(const double* rec, long nrec, float* alpha, stream_t) { mvn_accel_host_reduce(rec, nrec, alpha); }
+void launch_accel_b(const AccelParams& p, stream_t) { mvn_accel_host_b(p); }
+
 void launch_divide(const float* view, float* inout, size_t n, stream_t) {
   for (size_t i = 0; i < n; ++i) inout[i] = mvn_quotient(view[i], inout[i]);
 }

@@ -1739,6 +1739,9 @@ static size_t alloc_rounded(size_t b) { return (b + 4095) & ~(size_t)4095; }
 // Every workgroup of an update pass writes one record, and no launch has more workgroups than the volume has rows.
 static long stats_cap(const Layout& L) { return (long)L.rows; }
 
+// workgroups of the extrapolation's pass A (mvn_extrapolate.hpp): a function of the extents only
+static long accel_records(const Layout& L) { return mvn_accel_blocks((long)L.real_floats(), L.RP == L.d2 ? 4 : 2); }
+
 size_t Engine::memory_need(const MemoryQuery& q, const FormRule& rule) {
   const Layout& L = rule.L;
   if (L.d0 != q.ext[0] || L.d1 != q.ext[1] || L.d2 != q.ext[2]) throw std::logic_error("mvn: memory query of other extents");
@@ -1781,6 +1784,11 @@ size_t Engine::memory_need(const MemoryQuery& q, const FormRule& rule) {
     add(3 * sizeof(double) * (size_t)stats_cap(L) * (size_t)V, 1);
     add(sizeof(unsigned) * (size_t)V, 1);
     add(3 * sizeof(double) * (size_t)q.stats_rows, 1);
+  }
+  if (q.accel_rows > 0) {  // vector extrapolation (Engine::iterate)
+    add(mb, 3);  // x_prev, g, the saved y
+    add(2 * sizeof(double) * (size_t)accel_records(L), 1);
+    add(sizeof(float) * (size_t)q.accel_rows, 1);
   }
   // (psi_spec_ and delta_ belong to the simultaneous steps of the view-sharded drivers: never allocated here)
   return total;
@@ -2020,9 +2028,43 @@ void Engine::end_streaming() {
   stage_cv_.notify_all();
 }
 
-int Engine::iterate(int iterations, double lambda, float min_value, double tolerance, std::vector<double>* stats) {
+void Engine::accel_free() {
+  be::dfree(accel_xprev_);
+  be::dfree(accel_g_);
+  be::dfree(accel_ysave_);
+  be::dfree(accel_rec_);
+  be::dfree(accel_alpha_);
+  accel_xprev_ = accel_g_ = accel_ysave_ = accel_alpha_ = nullptr;
+  accel_rec_ = nullptr;
+  accel_on_ = false;
+}
+
+// psi = x_k -> psi = y_k (mvn_extrapolate.hpp); a_k stays in accel_alpha_[k - 1]
+void Engine::accel_extrapolate(int k, float min_value) {
+  const Layout& L = plan_->L;
+  AccelParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.psi = psi_, p.ysave = accel_ysave_, p.g = accel_g_, p.xprev = accel_xprev_;
+  p.n = (long)L.real_floats();
+  p.RP = L.RP, p.d2 = L.d2;
+  p.first = k == 1;
+  p.rec = accel_rec_;
+  p.alpha = accel_alpha_ + (k - 1);
+  p.min_value = min_value;
+  be::launch_accel_a(p, stream_);
+  be::launch_accel_reduce(accel_rec_, accel_records(L), accel_alpha_ + (k - 1), stream_);
+  be::launch_accel_b(p, stream_);
+}
+
+int Engine::iterate(int iterations, double lambda, float min_value, double tolerance, std::vector<double>* stats,
+                    int accel, std::vector<double>* alphas) {
   be::set_device(device_);
+  if (accel != 0 && accel != 1) throw std::invalid_argument("mvn: acceleration mode must be 0 (off) or 1");
+  if (alphas) alphas->clear();
   const bool st_on = tolerance >= 0.;
+  const bool ac_on = accel == 1 && iterations > 0;
+  if (accel == 1 && halo_fn_)
+    throw std::logic_error("mvn: no acceleration on a slab of a multi-device group (halo mode)");
   if (st_on) {
     if (halo_fn_) throw std::logic_error("mvn: no convergence statistics on a slab of a multi-device group");
     const int V = (int)views_.size();
@@ -2034,23 +2076,37 @@ int Engine::iterate(int iterations, double lambda, float min_value, double toler
     stats_on_ = true;
   }
   try {
-    const int ran = iterate_sweeps(iterations, lambda, min_value, tolerance, stats);
+    if (ac_on) {
+      accel_free();
+      accel_on_ = true;
+      accel_xprev_ = (float*)be::dmalloc(plan_->main_bytes());
+      accel_g_ = (float*)be::dmalloc(plan_->main_bytes());
+      accel_ysave_ = (float*)be::dmalloc(plan_->main_bytes());
+      accel_rec_ = (double*)be::dmalloc(2 * sizeof(double) * (size_t)accel_records(plan_->L));
+      accel_alpha_ = (float*)be::dmalloc(sizeof(float) * (size_t)iterations);
+    }
+    const int ran = iterate_sweeps(iterations, lambda, min_value, tolerance, stats, alphas);
     if (st_on) stats_free();
+    if (ac_on) {  // (the state lives for the call: the passes that use it have to be done before it goes)
+      be::stream_sync(stream_);
+      accel_free();
+    }
     return ran;
   } catch (...) {
-    if (st_on) {
+    if (st_on || ac_on) {
       try {
         be::stream_sync(stream_);
       } catch (...) {
       }
       stats_free();
+      accel_free();
     }
     throw;
   }
 }
 
 int Engine::iterate_sweeps(int iterations, double lambda, float min_value, double tolerance,
-                           std::vector<double>* stats) {
+                           std::vector<double>* stats, std::vector<double>* alphas) {
   work_has_psi_spectrum_ = false;  // psi may have been replaced since the last call
   pending_rows_ = nullptr;
   psi_spec_valid_ = false;
@@ -2062,9 +2118,10 @@ int Engine::iterate_sweeps(int iterations, double lambda, float min_value, doubl
   // (a captured sweep holds buffer addresses: the two work volumes must be back in their roles after it,
   // i.e. the sweep must contain an even number of direct dim0 legs)
   bool use_graph = graphs_on && !halo_fn_ && iterations >= 3 && !prof_.enabled && plan_->can_fuse_rows() &&
-                   plan_->main_bytes() <= graph_max_bytes && streamed_order_.empty() && !stats_on_;
+                   plan_->main_bytes() <= graph_max_bytes && streamed_order_.empty() && !stats_on_ && !accel_on_;
   std::vector<double> rows;  // {S, M, P} of the sweeps run
   int ran = 0;
+  if (accel_on_) be::d2d(accel_ysave_, psi_, plan_->main_bytes(), stream_);  // y_0
   for (int it = 0; it < iterations; ++it) {
     if (use_graph && it == 1) {  // every view has been staged by now: its PSF forms are known
       int swaps = 0;
@@ -2108,20 +2165,28 @@ int Engine::iterate_sweeps(int iterations, double lambda, float min_value, doubl
       const bool last = (it == iterations - 1) && (v == V - 1);
       const bool streamed = stream_pos_[(size_t)v] >= 0;
       if (streamed) ring_acquire(views_[(size_t)v]);
-      conv_pair(v, lambda, min_value, MVN_EPI_UPDATE, 0, !last);
+      // (acceleration: psi changes between the sweeps, so the last view update leaves no spectrum of it behind
+      // and the next sweep starts from rows_r2c of the new psi, as the first sweep of a call does.  Not after
+      // sweep 1: y_1 = x_1, psi stays, and so does the fused pass - 2 iterations are the plain loop's launches.
+      // The fused pass has written all of psi when pass A reads it: pending_rows_ is only ever set under
+      // boundary_first(), which needs a halo hook, and an engine with one refuses acceleration)
+      conv_pair(v, lambda, min_value, MVN_EPI_UPDATE, 0, !last && !(accel_on_ && v == V - 1 && it >= 1));
       if (streamed) ring_release(views_[(size_t)v]);
     }
     ran = it + 1;
-    if (!stats_on_) continue;
-    be::launch_convergence_reduce(stat_rec_, stat_count_, V, stat_cap_, stat_out_ + 3 * (size_t)it, stream_);
-    if (tolerance > 0.) {
-      // (no sweep is enqueued ahead: after a stop psi is the estimate of the sweeps run)
-      double r[3];
-      be::d2h(r, stat_out_ + 3 * (size_t)it, sizeof(r), stream_);
-      be::stream_sync(stream_);
-      rows.insert(rows.end(), r, r + 3);
-      if (r[0] / r[2] <= tolerance) break;  // (NaN never stops the loop)
+    if (stats_on_) {
+      be::launch_convergence_reduce(stat_rec_, stat_count_, V, stat_cap_, stat_out_ + 3 * (size_t)it, stream_);
+      if (tolerance > 0.) {
+        // (no sweep is enqueued ahead: after a stop psi is the estimate of the sweeps run)
+        double r[3];
+        be::d2h(r, stat_out_ + 3 * (size_t)it, sizeof(r), stream_);
+        be::stream_sync(stream_);
+        rows.insert(rows.end(), r, r + 3);
+        if (r[0] / r[2] <= tolerance) break;  // (NaN never stops the loop)
+      }
     }
+    // (no extrapolation after the last sweep run: psi stays x_k)
+    if (accel_on_ && it < iterations - 1) accel_extrapolate(it + 1, min_value);
   }
   flush_pending_rows();
   work_has_psi_spectrum_ = false;
@@ -2131,6 +2196,15 @@ int Engine::iterate_sweeps(int iterations, double lambda, float min_value, doubl
     be::stream_sync(stream_);
   }
   if (stats) *stats = std::move(rows);
+  if (accel_on_ && alphas) {  // a_1 .. a_ran; the last sweep run was not followed by an extrapolation
+    alphas->assign((size_t)ran, 0.);
+    if (ran > 1) {
+      std::vector<float> a((size_t)ran - 1);
+      be::d2h(a.data(), accel_alpha_, a.size() * sizeof(float), stream_);
+      be::stream_sync(stream_);
+      for (size_t k = 0; k < a.size(); ++k) (*alphas)[k] = (double)a[k];
+    }
+  }
   return ran;
 }
 

@@ -305,6 +305,7 @@ struct MemoryQuery {
   int streamed = 0;
   int ring = 0;
   int stats_rows = 0;  // convergence statistics on: the iterations of the call (Engine::iterate), else 0
+  int accel_rows = 0;  // acceleration on: the iterations of the call, else 0
 };
 
 // A stack as the described entry points take it (mvn_stack_desc, include/mvn_engine_api.h): where element (0, 0, 0)
@@ -400,8 +401,12 @@ class Engine {
   // {S_k, M_k, P_k} (mvn_engine_api.h), appended to *stats; tolerance > 0 ends the loop after the
   // first sweep with S_k / P_k <= tolerance (each sweep then waits for its statistics).  Returns the
   // sweeps run.
+  // accel == 1: vector extrapolation between the sweeps (mvn_extrapolate.hpp) - the next sweep starts from
+  // y_k = x_k + a_k (x_k - x_{k-1}) instead of x_k; no extrapolation follows the last sweep run, so psi is
+  // always a sweep's own result.  a_1 .. a_ran (the last one 0) go to *alphas, which costs a wait for the stream.
+  // Not for an engine with a halo hook (a slab of a multi-device group).
   int iterate(int iterations, double lambda, float min_value, double tolerance = -1.,
-              std::vector<double>* stats = nullptr);
+              std::vector<double>* stats = nullptr, int accel = 0, std::vector<double>* alphas = nullptr);
   // simultaneous (Jacobi) mode for view sharding: delta <- sum over this engine's views of
   // w_v (next_v - psi), computed from the current psi without changing it
   void compute_delta(double lambda, float min_value);
@@ -644,7 +649,17 @@ class Engine {
   long stat_cap_ = 0;
   MvnStatsParams stats_for(int v) const;
   void stats_free();
-  int iterate_sweeps(int iterations, double lambda, float min_value, double tolerance, std::vector<double>* stats);
+  int iterate_sweeps(int iterations, double lambda, float min_value, double tolerance, std::vector<double>* stats,
+                     std::vector<double>* alphas);
+  // vector extrapolation of the running iterate() (allocated for its duration only; see memory_need)
+  bool accel_on_ = false;
+  float* accel_xprev_ = nullptr;  // x_{k-1}
+  float* accel_g_ = nullptr;      // g_{k-1}
+  float* accel_ysave_ = nullptr;  // y_{k-1}: what the sweep started from
+  double* accel_rec_ = nullptr;   // pass A's records, 2 doubles per workgroup
+  float* accel_alpha_ = nullptr;  // a_k per sweep boundary
+  void accel_free();
+  void accel_extrapolate(int k, float min_value);  // after sweep k (1-based), before sweep k + 1
   // uploader thread (described: the stacks as StackRefs instead)
   void ring_upload(int v, const float* image, const float* weights, const StackRef* dimage = nullptr,
                    const StackRef* dweights = nullptr);

@@ -250,6 +250,23 @@ __global__ __launch_bounds__(MVN_INGEST_WG) void k_extract3d(const ExtractParams
   mvn_extract_rows(p, (long)blockIdx.x, (int)threadIdx.x);
 }
 
+// vector extrapolation between sweeps (mvn_extrapolate.hpp): two streaming passes and the reduction between them
+template <int W>
+__global__ __launch_bounds__(MVN_ACCEL_WG) void k_accel_a(const AccelParams p) {
+  __shared__ double lds[2 * MVN_ACCEL_WG];
+  mvn_accel_a_body<W>(p, (long)blockIdx.x, lds, (int)threadIdx.x, MVN_ACCEL_WG);
+}
+
+__global__ __launch_bounds__(MVN_ACCEL_WG) void k_accel_reduce(const double* rec, long nrec, float* alpha) {
+  __shared__ double lds[2 * MVN_ACCEL_WG];
+  mvn_accel_reduce_body(rec, nrec, alpha, lds, (int)threadIdx.x, MVN_ACCEL_WG);
+}
+
+template <int W>
+__global__ __launch_bounds__(MVN_ACCEL_WG) void k_accel_b(const AccelParams p) {
+  mvn_accel_b_body<W>(p, (long)blockIdx.x, (int)threadIdx.x, MVN_ACCEL_WG);
+}
+
 __global__ void k_divide(const float* __restrict__ view, float* __restrict__ inout, size_t n) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
@@ -944,6 +961,33 @@ void launch_extract3d(const ExtractParams& p, stream_t s) {
   const long nblocks = mvn_extract_blocks(p);
   if (nblocks < 1 || nblocks > 0x7fffffffL) throw std::invalid_argument("mvn: grid size out of range");
   hipLaunchKernelGGL(k_extract3d, dim3((unsigned)nblocks), dim3(MVN_INGEST_WG), 0, hs(s), p);
+  HIP_CHECK(hipGetLastError());
+}
+
+static unsigned accel_grid(const AccelParams& p, int W) {
+  const long nblocks = mvn_accel_blocks(p.n, W);
+  if (nblocks < 1 || nblocks > 0x7fffffffL) throw std::invalid_argument("mvn: grid size out of range");
+  return (unsigned)nblocks;
+}
+
+void launch_accel_a(const AccelParams& p, stream_t s) {
+  if (p.RP == p.d2)
+    hipLaunchKernelGGL(k_accel_a<4>, dim3(accel_grid(p, 4)), dim3(MVN_ACCEL_WG), 0, hs(s), p);
+  else
+    hipLaunchKernelGGL(k_accel_a<2>, dim3(accel_grid(p, 2)), dim3(MVN_ACCEL_WG), 0, hs(s), p);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_accel_reduce(const double* rec, long nrec, float* alpha, stream_t s) {
+  hipLaunchKernelGGL(k_accel_reduce, dim3(1), dim3(MVN_ACCEL_WG), 0, hs(s), rec, nrec, alpha);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_accel_b(const AccelParams& p, stream_t s) {
+  if (p.RP == p.d2)
+    hipLaunchKernelGGL(k_accel_b<4>, dim3(accel_grid(p, 4)), dim3(MVN_ACCEL_WG), 0, hs(s), p);
+  else
+    hipLaunchKernelGGL(k_accel_b<2>, dim3(accel_grid(p, 2)), dim3(MVN_ACCEL_WG), 0, hs(s), p);
   HIP_CHECK(hipGetLastError());
 }
 

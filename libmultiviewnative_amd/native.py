@@ -45,6 +45,7 @@ ENGINE_ABI_SYMBOLS = [
     "mvn_set_convergence", "mvn_get_convergence", "mvn_last_convergence", "mvn_engine_iterate_converge",
     "mvn_deconvolve_described", "mvn_engine_set_view_described", "mvn_engine_set_psi_described",
     "mvn_engine_get_psi_described",
+    "mvn_set_acceleration", "mvn_get_acceleration", "mvn_last_acceleration", "mvn_engine_iterate_accelerated",
 ]
 
 
@@ -156,6 +157,11 @@ class Binding:
         l.mvn_set_convergence.argtypes = [C.c_double]
         l.mvn_get_convergence.argtypes = [C.POINTER(C.c_double)]
         l.mvn_last_convergence.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_int]
+        l.mvn_set_acceleration.argtypes = [C.c_int]
+        l.mvn_get_acceleration.argtypes = [C.POINTER(C.c_int)]
+        l.mvn_last_acceleration.argtypes = [C.POINTER(C.c_double), C.c_int]
+        l.mvn_engine_iterate_accelerated.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_float, C.c_double,
+                                                     C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         l.mvn_engine_compute_delta.argtypes = [C.c_void_p, C.c_double, C.c_float]
         l.mvn_engine_apply_delta.argtypes = [C.c_void_p]
         l.mvn_engine_delta_chunks.argtypes = [C.c_void_p, C.c_int]
@@ -262,6 +268,25 @@ class Binding:
         if rows:
             self.check(self.l.mvn_last_convergence(C.byref(run), out.ctypes.data_as(C.POINTER(C.c_double)), rows))
         return run.value, out
+
+    def set_acceleration(self, mode):
+        """Process-wide acceleration of the RL loop: 0 off (default), 1 vector extrapolation between sweeps
+        (mvn_engine_api.h)."""
+        self.check(self.l.mvn_set_acceleration(int(mode)))
+
+    def get_acceleration(self):
+        out = C.c_int(0)
+        self.check(self.l.mvn_get_acceleration(C.byref(out)))
+        return out.value
+
+    def last_acceleration(self):
+        """float64 array of a_1 .. a_ran of the last deconvolution this thread completed (empty when acceleration
+        was off); the entry of the last sweep run is 0."""
+        rows = self.check(self.l.mvn_last_acceleration(None, 0))
+        out = np.zeros(rows, dtype=np.float64)
+        if rows:
+            self.check(self.l.mvn_last_acceleration(out.ctypes.data_as(C.POINTER(C.c_double)), rows))
+        return out
 
     # ---- reference ABI, numpy in / numpy out ----------------------------------------------
     def gpu_deconvolve(self, psi, holder, device=0, pad_mode="none"):
@@ -621,6 +646,19 @@ class EngineHandle:
                                                           C.byref(run),
                                                           stats.ctypes.data_as(C.POINTER(C.c_double))))
         return run.value, (stats[:run.value].copy() if tolerance >= 0 else np.zeros((0, 3)))
+
+    def iterate_accelerated(self, iterations, lambda_, min_value, tolerance=-1.0):
+        """mvn_engine_iterate_accelerated (blocking): (iterations run, [run, 3] statistics - empty with
+        tolerance < 0 -, float64 array of a_1 .. a_run)."""
+        run = C.c_int(0)
+        stats = np.zeros((max(int(iterations), 1), 3), dtype=np.float64)
+        alphas = np.zeros(max(int(iterations), 1), dtype=np.float64)
+        self.b.check(self.b.l.mvn_engine_iterate_accelerated(self.h, iterations, lambda_, min_value, float(tolerance),
+                                                             C.byref(run),
+                                                             stats.ctypes.data_as(C.POINTER(C.c_double)),
+                                                             alphas.ctypes.data_as(C.POINTER(C.c_double))))
+        return (run.value, (stats[:run.value].copy() if tolerance >= 0 else np.zeros((0, 3))),
+                alphas[:run.value].copy())
 
     def time_iterate(self, iterations, lambda_, min_value):
         ms = C.c_float(0)
