@@ -564,13 +564,14 @@ static size_t embed_floats_of(const shape_t& dims, const shape_t& ext) {
   return embedded ? (size_t)dims[0] * (size_t)dims[1] * (size_t)dims[2] : 0;
 }
 
-// ---- described stacks (mvn_deconvolve_described, mvn_engine_*_described) ----------------------------------------
-struct DescribedCall {
+// ---- the stacks of a call ----------------------------------------------------------------------------------------
+// Every entry point hands deconvolve_call its stacks in this form: the described ones from their descriptors
+// (mvn_deconvolve_described), the others as dense float32 stacks in host memory (workspace_stacks).
+struct CallStacks {
   StackRef psi;
   std::vector<StackRef> image, weights;
-  void* stream = nullptr;
+  void* stream = nullptr;    // the caller's stream its device stacks were produced on
   bool any_device = false;
-  int device = -1;           // the device that owns the stacks in device memory
   bool need_scratch = false; // some stack passes through the host-shaped embedding scratch
 };
 
@@ -630,6 +631,21 @@ static bool plain_stack(const StackRef& r, const int* dims) {
 // does the stack pass through the engine's host-shaped scratch when the call embeds its stacks?
 static bool through_scratch(const StackRef& r) { return !r.device && !r.broadcast(); }
 
+// the stacks of a workspace as the reference's entry points mean them: dense float32 in host memory (nothing is asked
+// about the pointers)
+static CallStacks workspace_stacks(const imageType* psi, const workspace& input) {
+  check_workspace(psi, input);
+  CallStacks cs;
+  cs.need_scratch = true;
+  if (input.num_views_ > 0) cs.psi = StackRef::dense_host(psi, input.data_[0].image_dims_);
+  for (int v = 0; v < input.num_views_; ++v) {
+    const view_data& d = input.data_[v];
+    cs.image.push_back(StackRef::dense_host(d.image_, d.image_dims_));
+    cs.weights.push_back(StackRef::dense_host(d.weights_, d.image_dims_));
+  }
+  return cs;
+}
+
 // what a call captures at its start: the convergence tolerance and the acceleration mode
 struct LoopMode {
   double tol = -1.;
@@ -642,8 +658,9 @@ struct LoopMode {
   }
 };
 
-static void deconvolve_call(imageType* psi, const workspace& input, int device, int lane, int pad_mode, LoopMode mode,
-                            ConvRecord* conv, const DescribedCall* dc = nullptr) {
+// (the caller has checked the workspace: check_workspace)
+static void deconvolve_call(const workspace& input, const CallStacks& cs, int device, int lane, int pad_mode,
+                            LoopMode mode, ConvRecord* conv) {
   const double tol = mode.tol;
   const int accel = mode.accel;
   conv->iterations_run = 0;
@@ -654,7 +671,6 @@ static void deconvolve_call(imageType* psi, const workspace& input, int device, 
     ~LoopScope() { t_call_tol = NAN, t_call_accel = -1; }
   } loop_scope(tol, accel);
   {
-    check_workspace(psi, input);
     const int V = input.num_views_;
     if (V == 0 || input.num_iterations_ <= 0) return;  // 0 iterations returns psi unchanged
     shape_t dims, ext;
@@ -664,25 +680,30 @@ static void deconvolve_call(imageType* psi, const workspace& input, int device, 
       // the slab drivers keep no convergence statistics: such a call runs on one device
       if (!devs.empty() && tol >= 0. && trace_on())
         std::printf("[lmvn::trace] MVN_DEVICES: convergence statistics on - one device\n");
-      if (!devs.empty() && dc && trace_on())
+      // ... take dense float32 stacks in host memory only
+      bool plain = !devs.empty() && plain_stack(cs.psi, input.data_[0].image_dims_);
+      for (int v = 0; plain && v < V; ++v)
+        plain = plain_stack(cs.image[(size_t)v], input.data_[v].image_dims_) &&
+                plain_stack(cs.weights[(size_t)v], input.data_[v].image_dims_);
+      if (!devs.empty() && !plain && trace_on())
         std::printf("[lmvn::trace] MVN_DEVICES: described stacks - one device\n");
       // ... and no acceleration
       if (!devs.empty() && accel && trace_on()) std::printf("[lmvn::trace] MVN_DEVICES: acceleration on - one device\n");
-      if (!devs.empty() && tol < 0. && !dc && !accel) {
+      if (plain && tol < 0. && !accel) {
         call_extents(input, pad_mode, -1, &dims, &ext, off);  // (the slabs run on plans of their own extents)
-        if (multi_device_call(psi, input, dims, ext, off, pad_mode, devs)) return;
+        if (multi_device_call((imageType*)cs.psi.ptr, input, dims, ext, off, pad_mode, devs)) return;
       }
     }
     const int dev = pick_device(device);
     call_extents(input, pad_mode, dev, &dims, &ext, off);
     // stacks in device memory: resident whatever the mode, priced by the exact model
-    const int mem_mode = dc && dc->any_device ? (int)MVN_MEM_EXACT : current_memory_mode();
+    const int mem_mode = cs.any_device ? (int)MVN_MEM_EXACT : current_memory_mode();
     const int key = dev + lane * kLaneStride;
     std::lock_guard<std::mutex> lk(device_mutex(key));
     be::set_device(dev);
     const bool embedded = ext[0] != dims[0] || ext[1] != dims[1] || ext[2] != dims[2];
     // on failure the engine is simply dropped
-    const bool scratch = !dc || dc->need_scratch;
+    const bool scratch = cs.need_scratch;
     std::unique_ptr<Engine> eng_owner = take_engine(
         key, dev, ext, V, embedded && scratch ? (size_t)dims[0] * (size_t)dims[1] * (size_t)dims[2] : 0, input, mem_mode);
     Engine& eng = *eng_owner;
@@ -699,20 +720,17 @@ static void deconvolve_call(imageType* psi, const workspace& input, int device, 
       return e && *e && std::strcmp(e, "0") != 0;
     }();
     if (no_pipeline && eng.streamed_count() == 0) {  // (streamed views need the uploader thread)
-      if (dc) eng.wait_for_caller(dc->stream);
+      eng.wait_for_caller(cs.stream);
       for (int v = 0; v < V; ++v) {
         const view_data& d = input.data_[v];
-        if (dc)
-          eng.set_view_described(v, dc->image[(size_t)v], dc->weights[(size_t)v], d.kernel1_, d.kernel1_dims_, d.kernel2_,
-                                 d.kernel2_dims_);
-        else
-          eng.set_view(v, d.image_, d.weights_, d.kernel1_, d.kernel1_dims_, d.kernel2_, d.kernel2_dims_);
+        eng.set_view(v, cs.image[(size_t)v], cs.weights[(size_t)v], d.kernel1_, d.kernel1_dims_, d.kernel2_,
+                     d.kernel2_dims_);
       }
-      dc ? eng.set_psi_described(dc->psi) : eng.set_psi(psi);
+      eng.set_psi(cs.psi);
       conv->iterations_run = eng.iterate(input.num_iterations_, input.lambda_, input.minValue_, tol, &conv->rows, accel,
                                          accel ? &conv->alphas : nullptr);
       eng.sync();
-      dc ? eng.get_psi_described(dc->psi) : eng.get_psi(psi);
+      eng.get_psi(cs.psi);
       give_back_engine(key, std::move(eng_owner));
       return;
     }
@@ -729,16 +747,12 @@ static void deconvolve_call(imageType* psi, const workspace& input, int device, 
     eng.reserve_views(call_kernels(input));
     lap("allocate view buffers");
     std::unique_lock<std::mutex> pcie(upload_mutex(dev));  // handed to the uploader thread's scope below
-    if (dc) {
-      eng.wait_for_caller(dc->stream);
-      eng.set_psi_described(dc->psi);
-      // views that are in device memory already: ingested on the compute stream, in view order
-      for (int v = 0; v < V; ++v)
-        if (dc->image[(size_t)v].device && dc->weights[(size_t)v].device)
-          eng.ingest_device_view(v, dc->image[(size_t)v], dc->weights[(size_t)v]);
-    } else {
-      eng.set_psi(psi);
-    }
+    eng.wait_for_caller(cs.stream);
+    eng.set_psi(cs.psi);
+    // views that are in device memory already: ingested on the compute stream, in view order
+    for (int v = 0; v < V; ++v)
+      if (cs.image[(size_t)v].device && cs.weights[(size_t)v].device)
+        eng.ingest_device_view(v, cs.image[(size_t)v], cs.weights[(size_t)v]);
     lap("upload psi");
     std::exception_ptr up_err;
     std::thread uploader([&] {
@@ -747,23 +761,15 @@ static void deconvolve_call(imageType* psi, const workspace& input, int device, 
         auto u0 = std::chrono::steady_clock::now();
         for (int v = 0; v < V; ++v) {
           const view_data& d = input.data_[v];
-          if (dc)
-            eng.stage_view_described(v, dc->image[(size_t)v], dc->weights[(size_t)v], d.kernel1_, d.kernel1_dims_,
-                                     d.kernel2_, d.kernel2_dims_);
-          else
-            eng.stage_view(v, d.image_, d.weights_, d.kernel1_, d.kernel1_dims_, d.kernel2_, d.kernel2_dims_);
+          eng.stage_view(v, cs.image[(size_t)v], cs.weights[(size_t)v], d.kernel1_, d.kernel1_dims_, d.kernel2_,
+                         d.kernel2_dims_);
         }
         eng.finish_staging();
         // out-of-core views: their stacks again for every later sweep, in sweep order, each as soon as its ring
         // slot is free (Engine::stream_view)
         for (int it = 1; it < input.num_iterations_ && eng.streamed_count() > 0; ++it)
           for (int v = 0; v < V; ++v)
-            if (eng.is_streamed(v)) {
-              if (dc)
-                eng.stream_view_described(v, dc->image[(size_t)v], dc->weights[(size_t)v]);
-              else
-                eng.stream_view(v, input.data_[v].image_, input.data_[v].weights_);
-            }
+            if (eng.is_streamed(v)) eng.stream_view(v, cs.image[(size_t)v], cs.weights[(size_t)v]);
         if (trace_on())
           std::printf("[lmvn::trace] %-28s %8.1f ms (uploader thread)\n", "stage all views",
                       std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u0).count());
@@ -789,17 +795,24 @@ static void deconvolve_call(imageType* psi, const workspace& input, int device, 
     if (main_err) std::rethrow_exception(main_err);
     eng.sync();
     lap("wait for the device");
-    dc ? eng.get_psi_described(dc->psi) : eng.get_psi(psi);
+    eng.get_psi(cs.psi);
     lap("download psi");
     if (eng.streamed_count() > 0) Engine::count_streamed_call();
     give_back_engine(key, std::move(eng_owner));
   }
 }
 
+// the call of the reference's entry points (the record is empty again before the workspace is looked at)
+static void workspace_call(imageType* psi, const workspace& input, int device, int lane, int pad_mode, LoopMode mode,
+                           ConvRecord* conv) {
+  *conv = ConvRecord();
+  deconvolve_call(input, workspace_stacks(psi, input), device, lane, pad_mode, mode, conv);
+}
+
 void inplace_gpu_deconvolve(imageType* psi, struct workspace input, int device) {
   guarded("inplace_gpu_deconvolve", [&] {
     const LoopMode mode = LoopMode::current();
-    deconvolve_call(psi, input, device, 0, current_pad_mode(), mode, &t_last_conv);
+    workspace_call(psi, input, device, 0, current_pad_mode(), mode, &t_last_conv);
   });
 }
 
@@ -807,7 +820,7 @@ int mvn_deconvolve_described(void* psi, struct workspace input, const mvn_call_d
   return guarded("mvn_deconvolve_described", [&] {
     const LoopMode mode = LoopMode::current();
     if (!desc) {
-      deconvolve_call((imageType*)psi, input, device, 0, current_pad_mode(), mode, &t_last_conv);
+      workspace_call((imageType*)psi, input, device, 0, current_pad_mode(), mode, &t_last_conv);
       return;
     }
     check_workspace((const imageType*)psi, input);
@@ -817,12 +830,11 @@ int mvn_deconvolve_described(void* psi, struct workspace input, const mvn_call_d
     for (int d = 0; d < 3; ++d)
       if (dims[d] < 1) throw std::invalid_argument("image extents must be >= 1");
     // everything about the descriptors is settled before any stack is touched
-    DescribedCall dc;
+    CallStacks dc;
     dc.stream = desc->stream;
     dc.psi = described_stack(psi, &desc->psi, dims, "psi", false, true);
     int owner = -1;
     check_location(dc.psi, "psi", &owner);
-    bool plain = plain_stack(dc.psi, dims);
     for (int v = 0; v < V; ++v) {
       const view_data& d = input.data_[v];
       const std::string n = std::to_string(v);
@@ -830,11 +842,6 @@ int mvn_deconvolve_described(void* psi, struct workspace input, const mvn_call_d
       dc.weights.push_back(described_stack(d.weights_, desc->weights ? desc->weights + v : nullptr, d.image_dims_, "weights " + n, false, false));
       check_location(dc.image.back(), "image " + n, &owner);
       check_location(dc.weights.back(), "weights " + n, &owner);
-      plain = plain && plain_stack(dc.image.back(), d.image_dims_) && plain_stack(dc.weights.back(), d.image_dims_);
-    }
-    if (plain) {  // today's layout throughout: today's call
-      deconvolve_call((imageType*)psi, input, device, 0, current_pad_mode(), mode, &t_last_conv);
-      return;
     }
     dc.need_scratch = through_scratch(dc.psi);
     dc.any_device = dc.psi.device;
@@ -847,9 +854,8 @@ int mvn_deconvolve_described(void* psi, struct workspace input, const mvn_call_d
         throw std::invalid_argument("the stacks live on device " + std::to_string(owner) + ", not on device " +
                                     std::to_string(device));
       if (owner >= 0) device = owner;
-      dc.device = device;
     }
-    deconvolve_call((imageType*)psi, input, device, 0, current_pad_mode(), mode, &t_last_conv, &dc);
+    deconvolve_call(input, dc, device, 0, current_pad_mode(), mode, &t_last_conv);
   });
 }
 
@@ -914,7 +920,7 @@ int mvn_deconvolve_submit(imageType* psi, struct workspace input, int device, lo
     // (the worker first, the map entry second: a thread that cannot be started leaves no job behind)
     j->worker = std::thread([j, psi, dev, lane, pad_mode] {
       j->rc = guarded("mvn_deconvolve_submit (worker)",
-                      [&] { deconvolve_call(psi, j->ws, dev, lane, pad_mode, j->mode, &j->conv); });
+                      [&] { workspace_call(psi, j->ws, dev, lane, pad_mode, j->mode, &j->conv); });
       if (j->rc < 0) j->error = g_last_error;  // the worker's thread-local message travels with the job
     });
     try {
@@ -1742,65 +1748,75 @@ int mvn_engine_destroy(mvn_engine* e) {
     __VA_ARGS__;                                                   \
   })
 
-int mvn_engine_set_view(mvn_engine* e, int v, const float* image, const float* weights,
-                        const float* kernel1, const int k1dims[3], const float* kernel2,
-                        const int k2dims[3]) {
-  MVN_ENGINE_CALL("mvn_engine_set_view", {
-    if (!image || !weights || !kernel1 || !kernel2 || !k1dims || !k2dims)
-      throw std::invalid_argument("null argument");
-    E.set_view(v, image, weights, kernel1, k1dims, kernel2, k2dims);
-  });
+// a stack of the engine entry points: a null descriptor means a dense float32 stack in host memory
+static StackRef engine_stack(Engine& E, const void* ptr, const mvn_stack_desc* d, const char* what, bool may_u16,
+                             bool written) {
+  const Layout& L = E.layout();
+  const int dims[3] = {L.d0, L.d1, L.d2};
+  return described_stack(ptr, d, dims, what, may_u16, written);
 }
 
-int mvn_engine_set_psi(mvn_engine* e, const float* psi) {
-  MVN_ENGINE_CALL("mvn_engine_set_psi", E.set_psi(psi));
-}
-
-int mvn_engine_get_psi(mvn_engine* e, float* psi) {
-  MVN_ENGINE_CALL("mvn_engine_get_psi", E.get_psi(psi));
-}
-
-int mvn_engine_set_view_described(mvn_engine* e, int v, const void* image, const mvn_stack_desc* image_desc,
-                                  const void* weights, const mvn_stack_desc* weights_desc, const float* kernel1,
-                                  const int k1dims[3], const float* kernel2, const int k2dims[3], void* stream) {
-  MVN_ENGINE_CALL("mvn_engine_set_view_described", {
-    if (!kernel1 || !kernel2 || !k1dims || !k2dims) throw std::invalid_argument("null kernel");
-    const Layout& L = E.layout();
-    const int dims[3] = {L.d0, L.d1, L.d2};
-    const StackRef im = described_stack(image, image_desc, dims, "image", true, false);
-    const StackRef w = described_stack(weights, weights_desc, dims, "weights", false, false);
+// `checked` (here and in engine_psi): a described entry point - the pointers must be where their descriptors say, on
+// the engine's device, and the engine waits for the caller's stream; the plain entry points ask nothing about theirs
+static void engine_set_view(Engine& E, int v, const void* image, const mvn_stack_desc* image_desc, const void* weights,
+                            const mvn_stack_desc* weights_desc, const float* kernel1, const int* k1dims,
+                            const float* kernel2, const int* k2dims, void* stream, bool checked) {
+  if (!kernel1 || !kernel2 || !k1dims || !k2dims) throw std::invalid_argument("null kernel");
+  const StackRef im = engine_stack(E, image, image_desc, "image", true, false);
+  const StackRef w = engine_stack(E, weights, weights_desc, "weights", false, false);
+  if (checked) {
     int owner = -1;
     check_location(im, "image", &owner);
     check_location(w, "weights", &owner);
     if (owner >= 0 && owner != E.device()) throw std::invalid_argument("the stacks live on another device than the engine");
     E.wait_for_caller(stream);
-    E.set_view_described(v, im, w, kernel1, k1dims, kernel2, k2dims);
-  });
+  }
+  E.set_view(v, im, w, kernel1, k1dims, kernel2, k2dims);
+}
+
+static StackRef engine_psi(Engine& E, const void* psi, const mvn_stack_desc* d, bool written, bool checked) {
+  const StackRef r = engine_stack(E, psi, d, "psi", false, written);
+  int owner = -1;
+  if (checked) check_location(r, "psi", &owner);
+  if (owner >= 0 && owner != E.device()) throw std::invalid_argument("psi lives on another device than the engine");
+  return r;
+}
+
+int mvn_engine_set_view(mvn_engine* e, int v, const float* image, const float* weights,
+                        const float* kernel1, const int k1dims[3], const float* kernel2,
+                        const int k2dims[3]) {
+  MVN_ENGINE_CALL("mvn_engine_set_view",
+                  engine_set_view(E, v, image, nullptr, weights, nullptr, kernel1, k1dims, kernel2, k2dims, nullptr, false));
+}
+
+int mvn_engine_set_psi(mvn_engine* e, const float* psi) {
+  MVN_ENGINE_CALL("mvn_engine_set_psi", E.set_psi(engine_psi(E, psi, nullptr, false, false)));
+}
+
+int mvn_engine_get_psi(mvn_engine* e, float* psi) {
+  MVN_ENGINE_CALL("mvn_engine_get_psi", E.get_psi(engine_psi(E, psi, nullptr, true, false)));
+}
+
+int mvn_engine_set_view_described(mvn_engine* e, int v, const void* image, const mvn_stack_desc* image_desc,
+                                  const void* weights, const mvn_stack_desc* weights_desc, const float* kernel1,
+                                  const int k1dims[3], const float* kernel2, const int k2dims[3], void* stream) {
+  MVN_ENGINE_CALL("mvn_engine_set_view_described", engine_set_view(E, v, image, image_desc, weights, weights_desc, kernel1,
+                                                                   k1dims, kernel2, k2dims, stream, true));
 }
 
 int mvn_engine_set_psi_described(mvn_engine* e, const void* psi, const mvn_stack_desc* d, void* stream) {
   MVN_ENGINE_CALL("mvn_engine_set_psi_described", {
-    const Layout& L = E.layout();
-    const int dims[3] = {L.d0, L.d1, L.d2};
-    const StackRef r = described_stack(psi, d, dims, "psi", false, false);
-    int owner = -1;
-    check_location(r, "psi", &owner);
-    if (owner >= 0 && owner != E.device()) throw std::invalid_argument("psi lives on another device than the engine");
+    const StackRef r = engine_psi(E, psi, d, false, true);
     E.wait_for_caller(stream);
-    E.set_psi_described(r);
+    E.set_psi(r);
   });
 }
 
 int mvn_engine_get_psi_described(mvn_engine* e, void* psi, const mvn_stack_desc* d) {
   MVN_ENGINE_CALL("mvn_engine_get_psi_described", {
-    const Layout& L = E.layout();
-    const int dims[3] = {L.d0, L.d1, L.d2};
-    const StackRef r = described_stack(psi, d, dims, "psi", false, true);
-    int owner = -1;
-    check_location(r, "psi", &owner);
-    if (owner >= 0 && owner != E.device()) throw std::invalid_argument("psi lives on another device than the engine");
+    const StackRef r = engine_psi(E, psi, d, true, true);
     E.sync();
-    E.get_psi_described(r);
+    E.get_psi(r);
   });
 }
 

@@ -883,23 +883,7 @@ void Engine::set_embedding(const int dims[3], const int off[3], bool scratch) {
   if (embedded_ && scratch) embed_scratch_ = (float*)be::dmalloc(host_floats() * sizeof(float));
 }
 
-void Engine::upload_volume(float* dst, const float* host, be::stream_t s) {
-  const Layout& L = plan_->L;
-  if (embedded_) {
-    be::h2d(embed_scratch_, host, host_floats() * sizeof(float), s);
-    be::launch_copy3d(dst + ((size_t)host_off_[0] * L.d1 + host_off_[1]) * L.RP + host_off_[2], L.RP,
-                      (long)L.d1 * L.RP, embed_scratch_, host_dims_[2], (long)host_dims_[1] * host_dims_[2],
-                      host_dims_[2], host_dims_[1], host_dims_[0], s);
-    return;
-  }
-  if (L.RP == L.d2)
-    be::h2d(dst, host, L.logical() * sizeof(float), s);
-  else
-    be::h2d_2d(dst, (size_t)L.RP * sizeof(float), host, (size_t)L.d2 * sizeof(float),
-               (size_t)L.d2 * sizeof(float), L.rows, s);
-}
-
-// ---- described stacks (mvn_ingest.hpp) ---------------------------------------------------------------
+// ---- stacks in and out (mvn_ingest.hpp) -------------------------------------------------------------
 // rows of a host stack as 2-D copies: [n0][n1] rows of `width` bytes, source pitches in bytes, destination pitches
 // drow / dplane bytes; one copy where the source's planes continue its row pitch, else one per plane
 static void host_rows_to_device(char* dst, size_t drow, size_t dplane, const char* src, long long s0b, long long s1b,
@@ -951,21 +935,31 @@ long long Engine::ingest_stack(float* dst, const StackRef& st, float* scratch, b
   const bool dense = (n[1] == 1 || st.stride[1] == n[2]) && (n[0] == 1 || st.stride[0] == (long long)n[1] * n[2]);
   if (!embedded_ && !st.u16) {  // float32 into a volume of its own extents: the copy itself places it
     if (dst_dirty && L.RP != L.d2) be::dzero(dst, plan_->main_bytes(), s);
-    if (dense)
-      upload_volume(dst, (const float*)st.ptr, s);
-    else
+    if (!dense)
       host_rows_to_device((char*)dst, (size_t)L.RP * sizeof(float), (size_t)L.d1 * L.RP * sizeof(float),
                           (const char*)st.ptr, st.stride[0] * 4, st.stride[1] * 4, (size_t)n[2] * sizeof(float), n, s);
+    else if (L.RP == L.d2)
+      be::h2d(dst, st.ptr, (size_t)bytes, s);
+    else
+      be::h2d_2d(dst, (size_t)L.RP * sizeof(float), st.ptr, (size_t)L.d2 * sizeof(float), (size_t)L.d2 * sizeof(float),
+                 L.rows, s);
     return bytes;
   }
   if (!scratch) throw std::logic_error("mvn: no scratch for a host stack");
+  // (a float32 stack is copied into its window only: margins that are no longer the zeros of their allocation go first)
+  if (!st.u16 && dst_dirty) be::dzero(dst, plan_->main_bytes(), s);
   if (dense)
     be::h2d(scratch, st.ptr, (size_t)bytes, s);
   else
     host_rows_to_device((char*)scratch, (size_t)n[2] * esz, (size_t)n[1] * n[2] * esz, (const char*)st.ptr,
                         st.stride[0] * (long long)esz, st.stride[1] * (long long)esz, (size_t)n[2] * esz, n, s);
+  if (!st.u16) {  // float32 into its window: a strided device copy
+    be::launch_copy3d(dst + ((size_t)host_off_[0] * L.d1 + host_off_[1]) * L.RP + host_off_[2], L.RP, (long)L.d1 * L.RP,
+                      scratch, n[2], (long)n[1] * n[2], n[2], n[1], n[0], s);
+    return bytes;
+  }
   p.src = scratch, p.s0 = (long long)n[1] * n[2], p.s1 = n[2], p.s2 = 1;
-  be::launch_ingest3d(p, st.u16, s);
+  be::launch_ingest3d(p, true, s);
   return bytes;
 }
 
@@ -1428,41 +1422,8 @@ void Engine::middle(const ViewSlot& s, int i, Profiler* prof, SideStream* side, 
   if (use_side) side->join_into(stream_);  // the next last-axis pass on stream_ reads the plane
 }
 
-void Engine::set_view(int v, const float* image, const float* weights, const float* kernel1,
-                      const int* k1dims, const float* kernel2, const int* k2dims) {
-  if (v < 0 || v >= (int)views_.size()) throw std::out_of_range("mvn: view index");
-  be::set_device(device_);
-  if (stream_pos_[(size_t)v] >= 0) throw std::logic_error("mvn: a streamed view is staged by the pipelined call only");
-  ViewSlot& s = views_[(size_t)v];
-  alloc_view(s);
-  upload_volume(s.image, image, stream_);
-  upload_volume(s.weights, weights, stream_);
-  const float* ks[2] = {kernel1, kernel2};
-  const int* kd[2] = {k1dims, k2dims};
-  for (int i = 0; i < 2; ++i) {
-    if (psf_resident(s, i, ks[i], kd[i])) continue;
-    const size_t kb = sizeof(float) * (size_t)kd[i][0] * (size_t)kd[i][1] * (size_t)kd[i][2];
-    float* dk = (float*)be::dmalloc(kb);
-    be::h2d(dk, ks[i], kb, stream_);
-    try {
-      // nothing else runs on this engine during a blocking set_view: the work volume is the scratch
-      work_has_psi_spectrum_ = false;
-      prepare_psf(s, i, dk, kd[i], work_, false, stream_);
-      if (s.tap_k[i]) ensure_work2();  // the direct leg's second work volume: allocated here, not inside a sweep
-    } catch (...) {
-      be::stream_sync(stream_);
-      be::dfree(dk);
-      s.kcopy[i].clear();  // the spectrum is in an unknown state
-      throw;
-    }
-    be::stream_sync(stream_);
-    be::dfree(dk);
-  }
-  s.set = true;
-}
-
-void Engine::set_view_described(int v, const StackRef& image, const StackRef& weights, const float* kernel1,
-                                const int* k1dims, const float* kernel2, const int* k2dims) {
+void Engine::set_view(int v, const StackRef& image, const StackRef& weights, const float* kernel1, const int* k1dims,
+                      const float* kernel2, const int* k2dims) {
   if (v < 0 || v >= (int)views_.size()) throw std::out_of_range("mvn: view index");
   be::set_device(device_);
   if (stream_pos_[(size_t)v] >= 0) throw std::logic_error("mvn: a streamed view is staged by the pipelined call only");
@@ -1470,28 +1431,39 @@ void Engine::set_view_described(int v, const StackRef& image, const StackRef& we
   alloc_view(s);
   ingest_pair(s.image, s.weights, image, weights, stream_);
   be::stream_sync(stream_);  // the sources have been consumed
-  // the PSFs exactly as set_view prepares them
+  prepare_psfs(s, kernel1, k1dims, kernel2, k2dims, false, stream_);
+  s.set = true;
+}
+
+void Engine::prepare_psfs(ViewSlot& s, const float* kernel1, const int* k1dims, const float* kernel2, const int* k2dims,
+                          bool staging, be::stream_t st) {
   const float* ks[2] = {kernel1, kernel2};
   const int* kd[2] = {k1dims, k2dims};
   for (int i = 0; i < 2; ++i) {
     if (psf_resident(s, i, ks[i], kd[i])) continue;
     const size_t kb = sizeof(float) * (size_t)kd[i][0] * (size_t)kd[i][1] * (size_t)kd[i][2];
     float* dk = (float*)be::dmalloc(kb);
-    be::h2d(dk, ks[i], kb, stream_);
+    if (staging) stage_scratch_.push_back(dk);  // freed in finish_staging(), after the stream has drained
+    be::h2d(dk, ks[i], kb, st);
     try {
-      work_has_psi_spectrum_ = false;
-      prepare_psf(s, i, dk, kd[i], work_, false, stream_);
-      if (s.tap_k[i]) ensure_work2();
+      // nothing else runs on this engine during a blocking set_view: the work volume is the scratch
+      if (!staging) work_has_psi_spectrum_ = false;
+      prepare_psf(s, i, dk, kd[i], staging ? nullptr : work_, staging, st);
+      // the direct leg's second work volume: allocated here, not inside a sweep (reserve_views has, when staging)
+      if (!staging && s.tap_k[i]) ensure_work2();
     } catch (...) {
-      be::stream_sync(stream_);
-      be::dfree(dk);
-      s.kcopy[i].clear();
+      if (!staging) {
+        be::stream_sync(st);
+        be::dfree(dk);
+      }
+      s.kcopy[i].clear();  // the resident form is in an unknown state: never a cache hit
       throw;
     }
-    be::stream_sync(stream_);
-    be::dfree(dk);
+    if (!staging) {
+      be::stream_sync(st);
+      be::dfree(dk);
+    }
   }
-  s.set = true;
 }
 
 // ---- pipelined staging ------------------------------------------------------------------------
@@ -1519,19 +1491,6 @@ void Engine::reserve_views(const kernel_list_t& kernels) {
   pipelined_ = true;
 }
 
-void Engine::stage_view(int v, const float* image, const float* weights, const float* kernel1,
-                        const int* k1dims, const float* kernel2, const int* k2dims) {
-  be::set_device(device_);  // the HIP device is per host thread
-  ViewSlot& s = views_[(size_t)v];
-  if (stream_pos_[(size_t)v] >= 0) {
-    ring_upload(v, image, weights);
-  } else {
-    upload_volume(s.image, image, upload_stream_);
-    upload_volume(s.weights, weights, upload_stream_);
-  }
-  stage_psfs(v, kernel1, k1dims, kernel2, k2dims);
-}
-
 void Engine::ingest_device_view(int v, const StackRef& image, const StackRef& weights) {
   be::set_device(device_);
   ViewSlot& s = views_[(size_t)v];
@@ -1540,35 +1499,16 @@ void Engine::ingest_device_view(int v, const StackRef& image, const StackRef& we
   pre_ingested_[(size_t)v] = 1;
 }
 
-void Engine::stage_view_described(int v, const StackRef& image, const StackRef& weights, const float* kernel1,
-                                  const int* k1dims, const float* kernel2, const int* k2dims) {
-  be::set_device(device_);
+// uploader thread: the stacks and the PSFs of view v on the upload stream, then the view is staged
+void Engine::stage_view(int v, const StackRef& image, const StackRef& weights, const float* kernel1, const int* k1dims,
+                        const float* kernel2, const int* k2dims) {
+  be::set_device(device_);  // the HIP device is per host thread
   ViewSlot& s = views_[(size_t)v];
   if (stream_pos_[(size_t)v] >= 0)
-    ring_upload(v, nullptr, nullptr, &image, &weights);
+    ring_upload(v, image, weights);
   else if (!pre_ingested_[(size_t)v])
     ingest_pair(s.image, s.weights, image, weights, upload_stream_);
-  stage_psfs(v, kernel1, k1dims, kernel2, k2dims);
-}
-
-// uploader thread: the PSFs of view v on the upload stream, then the view is staged
-void Engine::stage_psfs(int v, const float* kernel1, const int* k1dims, const float* kernel2, const int* k2dims) {
-  ViewSlot& s = views_[(size_t)v];
-  const float* ks[2] = {kernel1, kernel2};
-  const int* kd[2] = {k1dims, k2dims};
-  for (int i = 0; i < 2; ++i) {
-    if (psf_resident(s, i, ks[i], kd[i])) continue;
-    const size_t kb = sizeof(float) * (size_t)kd[i][0] * (size_t)kd[i][1] * (size_t)kd[i][2];
-    float* dk = (float*)be::dmalloc(kb);
-    stage_scratch_.push_back(dk);  // freed in finish_staging(), after the stream has drained
-    be::h2d(dk, ks[i], kb, upload_stream_);
-    try {
-      prepare_psf(s, i, dk, kd[i], nullptr, true, upload_stream_);
-    } catch (...) {
-      s.kcopy[i].clear();  // the resident form is in an unknown state: never a cache hit
-      throw;
-    }
-  }
+  prepare_psfs(s, kernel1, k1dims, kernel2, k2dims, true, upload_stream_);
   be::event_record(staged_ev_[(size_t)v], upload_stream_);
   s.set = true;
   {
@@ -1652,8 +1592,7 @@ void Engine::set_residency(const std::vector<int>& streamed, int ring) {
   be::stream_sync(stream_);
 }
 
-void Engine::ring_upload(int v, const float* image, const float* weights, const StackRef* dimage,
-                         const StackRef* dweights) {
+void Engine::ring_upload(int v, const StackRef& image, const StackRef& weights) {
   if (stream_pos_[(size_t)v] < 0) throw std::logic_error("mvn: view " + std::to_string(v) + " is resident");
   const long R = (long)ring_.size();
   long k;
@@ -1666,14 +1605,8 @@ void Engine::ring_upload(int v, const float* image, const float* weights, const 
   }
   RingSlot& r = ring_[(size_t)(k % R)];
   if (k >= R) be::stream_wait_event(upload_stream_, r.freed);
-  if (dimage) {
-    if (dimage->device || dweights->device) throw std::logic_error("mvn: a call with stacks in device memory runs resident");
-    g_stream_bytes += ingest_pair(r.image, r.weights, *dimage, *dweights, upload_stream_);
-  } else {
-    upload_volume(r.image, image, upload_stream_);
-    upload_volume(r.weights, weights, upload_stream_);
-    g_stream_bytes += (long long)(2 * host_floats() * sizeof(float));
-  }
+  if (image.device || weights.device) throw std::logic_error("mvn: a call with stacks in device memory runs resident");
+  g_stream_bytes += ingest_pair(r.image, r.weights, image, weights, upload_stream_);
   be::event_record(r.filled, upload_stream_);
   {
     std::lock_guard<std::mutex> lk(stage_mu_);
@@ -1682,16 +1615,10 @@ void Engine::ring_upload(int v, const float* image, const float* weights, const 
   stage_cv_.notify_all();
 }
 
-void Engine::stream_view(int v, const float* image, const float* weights) {
+void Engine::stream_view(int v, const StackRef& image, const StackRef& weights) {
   if (v < 0 || v >= (int)views_.size()) throw std::out_of_range("mvn: view index");
   be::set_device(device_);
   ring_upload(v, image, weights);
-}
-
-void Engine::stream_view_described(int v, const StackRef& image, const StackRef& weights) {
-  if (v < 0 || v >= (int)views_.size()) throw std::out_of_range("mvn: view index");
-  be::set_device(device_);
-  ring_upload(v, nullptr, nullptr, &image, &weights);
 }
 
 void Engine::abort_streaming() {
@@ -1794,42 +1721,15 @@ size_t Engine::memory_need(const MemoryQuery& q, const FormRule& rule) {
   return total;
 }
 
-void Engine::set_psi(const float* host) {
-  be::set_device(device_);
-  psi_spec_valid_ = false;
-  if (embedded_) be::dzero(psi_, plan_->main_bytes(), stream_);
-  upload_volume(psi_, host, stream_);
-  be::stream_sync(stream_);
-}
-
-void Engine::get_psi(float* host) {
-  be::set_device(device_);
-  const Layout& L = plan_->L;
-  if (embedded_) {
-    be::launch_copy3d(embed_scratch_, host_dims_[2], (long)host_dims_[1] * host_dims_[2],
-                      psi_ + ((size_t)host_off_[0] * L.d1 + host_off_[1]) * L.RP + host_off_[2], L.RP,
-                      (long)L.d1 * L.RP, host_dims_[2], host_dims_[1], host_dims_[0], stream_);
-    be::d2h(host, embed_scratch_, host_floats() * sizeof(float), stream_);
-    be::stream_sync(stream_);
-    return;
-  }
-  if (L.RP == L.d2)
-    be::d2h(host, psi_, L.logical() * sizeof(float), stream_);
-  else
-    be::d2h_2d(host, (size_t)L.d2 * sizeof(float), psi_, (size_t)L.RP * sizeof(float),
-               (size_t)L.d2 * sizeof(float), L.rows, stream_);
-  be::stream_sync(stream_);
-}
-
-void Engine::set_psi_described(const StackRef& st) {
+void Engine::set_psi(const StackRef& st) {
   if (st.u16) throw std::invalid_argument("mvn: psi is float32");
   be::set_device(device_);
   psi_spec_valid_ = false;
-  ingest_stack(psi_, st, embed_scratch_, false, stream_);
+  ingest_stack(psi_, st, embed_scratch_, embedded_, stream_);  // (the loop has written the margins of an embedded psi)
   be::stream_sync(stream_);
 }
 
-void Engine::get_psi_described(const StackRef& st) {
+void Engine::get_psi(const StackRef& st) {
   if (st.u16) throw std::invalid_argument("mvn: psi is float32");
   be::set_device(device_);
   const Layout& L = plan_->L;
@@ -1847,24 +1747,31 @@ void Engine::get_psi_described(const StackRef& st) {
     return;
   }
   check_host_rows(st, n);
+  if (embedded_ && !embed_scratch_) throw std::logic_error("mvn: no scratch for a host stack");
   const bool dense = (n[1] == 1 || st.stride[1] == n[2]) && (n[0] == 1 || st.stride[0] == (long long)n[1] * n[2]);
-  if (dense) {
-    get_psi((float*)st.ptr);
-    return;
-  }
   const char* src = (const char*)psi_;
   size_t srow = (size_t)L.RP * sizeof(float), splane = (size_t)L.d1 * srow;
-  if (embedded_) {
-    if (!embed_scratch_) throw std::logic_error("mvn: no scratch for a host stack");
-    e.dst = embed_scratch_, e.s0 = (long long)n[1] * n[2], e.s1 = n[2], e.s2 = 1;
-    be::launch_extract3d(e, stream_);
+  if (embedded_) {  // the window into the scratch first: a strided device copy for dense rows, the extract pass else
+    if (dense) {
+      be::launch_copy3d(embed_scratch_, n[2], (long)n[1] * n[2],
+                        psi_ + ((size_t)host_off_[0] * L.d1 + host_off_[1]) * L.RP + host_off_[2], L.RP,
+                        (long)L.d1 * L.RP, n[2], n[1], n[0], stream_);
+    } else {
+      e.dst = embed_scratch_, e.s0 = (long long)n[1] * n[2], e.s1 = n[2], e.s2 = 1;
+      be::launch_extract3d(e, stream_);
+    }
     src = (const char*)embed_scratch_;
     srow = (size_t)n[2] * sizeof(float), splane = (size_t)n[1] * srow;
   }
   const size_t width = (size_t)n[2] * sizeof(float);
-  for (int z = 0; z < n[0]; ++z)
-    be::d2h_2d((char*)st.ptr + (long long)z * st.stride[0] * 4, n[1] == 1 ? width : (size_t)st.stride[1] * 4,
-               src + z * splane, srow, width, (size_t)n[1], stream_);
+  if (dense && srow == width)
+    be::d2h((void*)st.ptr, src, host_floats() * sizeof(float), stream_);
+  else if (dense)
+    be::d2h_2d((void*)st.ptr, width, src, srow, width, L.rows, stream_);
+  else
+    for (int z = 0; z < n[0]; ++z)
+      be::d2h_2d((char*)st.ptr + (long long)z * st.stride[0] * 4, n[1] == 1 ? width : (size_t)st.stride[1] * 4,
+                 src + z * splane, srow, width, (size_t)n[1], stream_);
   be::stream_sync(stream_);
 }
 

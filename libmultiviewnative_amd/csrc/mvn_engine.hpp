@@ -308,8 +308,9 @@ struct MemoryQuery {
   int accel_rows = 0;  // acceleration on: the iterations of the call, else 0
 };
 
-// A stack as the described entry points take it (mvn_stack_desc, include/mvn_engine_api.h): where element (0, 0, 0)
-// lives, what it is made of and how far apart its elements are.  Extents are the engine's embedding window.
+// A stack as the engine takes it (the described entry points' mvn_stack_desc, include/mvn_engine_api.h; the plain ones
+// hand over dense float32 host stacks, Engine::dense): where element (0, 0, 0) lives, what it is made of and how far
+// apart its elements are.  Extents are the engine's embedding window.
 struct StackRef {
   const void* ptr = nullptr;
   bool u16 = false;     // uint16 elements (images only), else float32
@@ -346,7 +347,7 @@ class Engine {
   int ring_size() const { return (int)ring_.size(); }
   bool is_streamed(int v) const { return stream_pos_[(size_t)v] >= 0; }
   // uploader thread, sweeps 1 .. n-1: the next streamed view's stacks into their ring slot (views in sweep order)
-  void stream_view(int v, const float* image, const float* weights);
+  void stream_view(int v, const StackRef& image, const StackRef& weights);
   // main thread after an error: wake an uploader that waits for a ring slot
   void abort_streaming();
   // Bytes the ABI call described by q allocates on a new engine of extents q.ext, allocating nothing itself: the
@@ -357,28 +358,21 @@ class Engine {
   static void stream_counters(long long out[3]);
   static void count_streamed_call();
 
-  // host -> device staging (blocking); arrays are dense [d0][d1][d2] floats
-  void set_view(int v, const float* image, const float* weights, const float* kernel1,
-                const int* k1dims, const float* kernel2, const int* k2dims);
-  void set_psi(const float* host);
-  void get_psi(float* host);
-
-  // The same three for described stacks (StackRef; mvn_ingest.hpp): a stack in device memory is read by the ingest
-  // pass where it lies, one in host memory crosses PCIe as it is (uint16 as uint16; rows must be contiguous) and is
-  // then converted and embedded by the same pass.  Blocking.
-  void set_view_described(int v, const StackRef& image, const StackRef& weights, const float* kernel1,
-                          const int* k1dims, const float* kernel2, const int* k2dims);
-  void set_psi_described(const StackRef& psi);
-  void get_psi_described(const StackRef& psi);
+  // Staging (blocking).  A stack enters and leaves as a StackRef (mvn_ingest.hpp), whatever it is made of: a float32
+  // stack in host memory (rows must be contiguous) is placed by the copy of its window - H2D, or H2D into the embedding
+  // scratch and a strided device copy into margins that were cleared when the volume was allocated; a stack in device
+  // memory is read by the ingest pass where it lies, and one value for every voxel (strides 0) is written by it; a
+  // uint16 stack in host memory crosses PCIe as uint16 and is then converted and embedded by the same pass.
+  void set_view(int v, const StackRef& image, const StackRef& weights, const float* kernel1, const int* k1dims,
+                const float* kernel2, const int* k2dims);
+  void set_psi(const StackRef& psi);
+  void get_psi(const StackRef& psi);
   // the caller produced its device stacks on `caller_stream`: the engine's streams wait for what is enqueued there
   // now (an event, no host wait); nullptr: nothing to wait for
   void wait_for_caller(void* caller_stream);
-  // described ABI call, main thread, after reserve_views(): a view whose two stacks are both in device memory is
-  // ingested on the compute stream (nothing to hide behind an upload); stage_view_described then only prepares its PSFs
+  // ABI call, main thread, after reserve_views(): a view whose two stacks are both in device memory is ingested on
+  // the compute stream (nothing to hide behind an upload); stage_view then only prepares its PSFs
   void ingest_device_view(int v, const StackRef& image, const StackRef& weights);
-  void stage_view_described(int v, const StackRef& image, const StackRef& weights, const float* kernel1,
-                            const int* k1dims, const float* kernel2, const int* k2dims);
-  void stream_view_described(int v, const StackRef& image, const StackRef& weights);
 
   // Pipelined staging for the blocking ABI call (what the reference's "interleaved" driver was
   // after, src/gpu_deconvolve_methods.cuh:82-326): a second host thread uploads view after view
@@ -390,8 +384,8 @@ class Engine {
   //   staging_failed()           uploader thread: wake the main thread up after an error
   //   iterate(...)               main thread: waits for view v only before its first use
   void reserve_views(const kernel_list_t& kernels);
-  void stage_view(int v, const float* image, const float* weights, const float* kernel1,
-                  const int* k1dims, const float* kernel2, const int* k2dims);
+  void stage_view(int v, const StackRef& image, const StackRef& weights, const float* kernel1, const int* k1dims,
+                  const float* kernel2, const int* k2dims);
   void staging_failed();
   void finish_staging();  // uploader thread, after the last view: drain and free scratch
 
@@ -484,6 +478,8 @@ class Engine {
   // scratch = false: no stack of the call passes through host-shaped device scratch (all of them are in device
   // memory or broadcast), so none is kept.
   void set_embedding(const int dims[3], const int off[3], bool scratch = true);
+  // a dense float32 stack in host memory, of the extents of the current embedding window
+  StackRef dense(const float* host) const { return StackRef::dense_host(host, host_dims_); }
   // quotient 0 wherever the view is exactly 0 (see EpilogueParams::guard_zero_view)
   void set_quotient_guard(bool on) { quotient_guard_ = on; }
   // the PSF form rule on this engine's plan, with the switches read when the engine was built
@@ -515,15 +511,18 @@ class Engine {
   bool psf_resident(ViewSlot& s, int i, const float* kernel, const int* kdims);
   void conv_pair(int v, double lambda, float min_value, int final_mode, int accumulate,
                  bool feed_next);
-  void upload_volume(float* dst, const float* host, be::stream_t s);
-  // one described stack into volume `dst` on stream s; `scratch`: where a host stack that needs converting or embedding
+  // one stack into volume `dst` on stream s; `scratch`: where a host stack that needs converting or embedding
   // lands first; dst_dirty: dst has been used as such a scratch since its padding was cleared.  Returns the bytes
   // that crossed PCIe.
   long long ingest_stack(float* dst, const StackRef& st, float* scratch, bool dst_dirty, be::stream_t s);
   // image and weights of one view; without an embedding scratch a uint16 image lands in the weights volume first
   long long ingest_pair(float* image_dst, float* weights_dst, const StackRef& image, const StackRef& weights,
                         be::stream_t s);
-  void stage_psfs(int v, const float* kernel1, const int* k1dims, const float* kernel2, const int* k2dims);
+  // Both kernels of slot s on stream st, each unless the slot holds it already (psf_resident): device copy of the
+  // kernel, then prepare_psf.  Blocking (set_view): the work volume is the scratch and each copy is freed once the
+  // stream has drained.  Staging (stage_view): the staging scratch, and the copies are parked in stage_scratch_.
+  void prepare_psfs(ViewSlot& s, const float* kernel1, const int* k1dims, const float* kernel2, const int* k2dims,
+                    bool staging, be::stream_t st);
   std::vector<char> pre_ingested_;  // per view: ingest_device_view has taken its stacks
   be::event_t caller_ev_ = nullptr;
   bool embedded_ = false;
@@ -660,9 +659,7 @@ class Engine {
   float* accel_alpha_ = nullptr;  // a_k per sweep boundary
   void accel_free();
   void accel_extrapolate(int k, float min_value);  // after sweep k (1-based), before sweep k + 1
-  // uploader thread (described: the stacks as StackRefs instead)
-  void ring_upload(int v, const float* image, const float* weights, const StackRef* dimage = nullptr,
-                   const StackRef* dweights = nullptr);
+  void ring_upload(int v, const StackRef& image, const StackRef& weights);  // uploader thread
   void ring_acquire(ViewSlot& s);                                     // main thread, before the view update
   void ring_release(ViewSlot& s);                                     // main thread, after it
   float* psi_ = nullptr;

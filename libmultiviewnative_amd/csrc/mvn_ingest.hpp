@@ -1,10 +1,12 @@
 // mvn_ingest.hpp -- a caller's stack into the engine's volume in ONE pass, and psi back out.
 //
-// The described entry points (mvn_deconvolve_described, mvn_engine_*_described; include/mvn_engine_api.h) take
-// stacks as the caller has them: float32 or uint16, in host or device memory, with element strides.  The plain
-// float32 host path places a stack with a copy of its window (H2D, or H2D into the embedding scratch and a strided
-// device copy) and relies on margins cleared when the volume was allocated; the ingest pass converts, follows
-// strides, reads the caller's device memory and depends on no earlier clear:
+// Every stack enters the engine as a StackRef (mvn_engine.hpp) through Engine::ingest_stack: float32 or uint16, in host
+// or device memory, with element strides (the described entry points, mvn_deconvolve_described and
+// mvn_engine_*_described in include/mvn_engine_api.h, take stacks as the caller has them; the plain ones describe theirs
+// as dense float32 in host memory).  A float32 stack in host memory with contiguous rows is placed with a copy of its
+// window (H2D, or H2D into the embedding scratch and a strided device copy), which relies on margins cleared when the
+// volume was allocated; every other stack - uint16, in device memory, or one value for every voxel - takes the ingest
+// pass, which converts, follows strides, reads the caller's device memory and depends on no earlier clear:
 //
 //   k_ingest3d<T>   one workgroup per run of MVN_INGEST_ROWS rows of the engine volume (row pitch RP floats, plane
 //                   pitch D1 * RP).  It writes EVERY float of its rows - the converted source inside the embedding

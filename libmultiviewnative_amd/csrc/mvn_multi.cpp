@@ -302,9 +302,10 @@ void HaloGroup::load(const imageType* psi, const workspace& input, const shape_t
     const size_t first = (size_t)s.host_a * (size_t)dims[1] * (size_t)dims[2];
     for (int v = 0; v < V_; ++v) {
       const view_data& d = input.data_[v];
-      e.set_view(v, d.image_ + first, d.weights_ + first, d.kernel1_, d.kernel1_dims_, d.kernel2_, d.kernel2_dims_);
+      e.set_view(v, e.dense(d.image_ + first), e.dense(d.weights_ + first), d.kernel1_, d.kernel1_dims_, d.kernel2_,
+                 d.kernel2_dims_);
     }
-    e.set_psi(psi + first);
+    e.set_psi(e.dense(psi + first));
   });
   // the slabs exchange planes of the middle's input: all of them take the fused middle pass (mvn_mid_fused.hpp), or none
   const kernel_list_t k = call_kernels(input);
@@ -339,7 +340,7 @@ double HaloGroup::iterate(int iterations, double lambda, float min_value) {
 void HaloGroup::fetch(imageType* psi) {
   if (!loaded_) throw std::logic_error("mvn: group without stacks");
   on_every_slab([&](Slab& s) {
-    s.eng->get_psi(psi + (size_t)s.host_a * (size_t)host_dims_[1] * (size_t)host_dims_[2]);
+    s.eng->get_psi(s.eng->dense(psi + (size_t)s.host_a * (size_t)host_dims_[1] * (size_t)host_dims_[2]));
   });
 }
 

@@ -322,6 +322,50 @@ def test_convergence_statistics_of_a_described_call(emu):
         emu.set_convergence(-1.0)
 
 
+# ---- the blocking branch of the ABI call (MVN_NO_PIPELINE, read once per process: a child) ---------------------------
+_BLOCKING_CHILD = r"""
+import os, sys
+import numpy as np
+root, out = sys.argv[1], sys.argv[2]
+sys.path.insert(0, root); sys.path.insert(0, os.path.join(root, "tests"))
+from libmultiviewnative_amd import native
+import test_emu_described_stacks as t
+emu = native.Binding(native.EMU_SO)
+for pad in t.BLOCKING_PADS:
+    plain, desc = t.blocking_calls(emu, pad)
+    np.save(os.path.join(out, "plain_%s.npy" % pad), plain)
+    np.save(os.path.join(out, "described_%s.npy" % pad), desc)
+assert not emu.l.mvn_last_error().decode(), emu.l.mvn_last_error().decode()
+print("blocking child ok", flush=True)
+"""
+
+BLOCKING_PADS = ("none", "zero")
+
+
+def blocking_calls(b, pad):
+    """one plain call, and one described call with uint16 images in unaligned windows and psi in a window"""
+    shape = SHAPES[1]  # odd last extent: rows are padded and the pitched copy runs; "zero" embeds the stacks
+    views, _, _, w, psi0 = case(shape)
+    u16 = [window(np.rint(v).astype(np.uint16), off=(1, 2, 3), fill=9)[1] for v in views]
+    return plain(b, shape, 0.006, pad)[0], described(b, window(psi0)[1], u16, w, shape, 0.006, pad).copy()
+
+
+def test_blocking_call_gives_what_the_pipelined_call_gives(emu, tmp_path):
+    # the library against itself on another code path, bit for bit (the anchor outside it: the oracle comparison of
+    # test_dense_float32_through_descriptors)
+    env = dict(os.environ, OMP_NUM_THREADS="4", MVN_NO_PIPELINE="1", MVN_TRACE="1")
+    r = subprocess.run([sys.executable, "-c", _BLOCKING_CHILD, ROOT, str(tmp_path)], env=env, capture_output=True,
+                       text=True, timeout=600)
+    assert r.returncode == 0 and "blocking child ok" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
+    # the child took the blocking branch: its calls were traced, and none of them started the uploader thread
+    assert "[lmvn::inplace_gpu_deconvolve]" in r.stdout and "(uploader thread)" not in r.stdout, r.stdout[-4000:]
+    for pad in BLOCKING_PADS:
+        ref, ref16 = blocking_calls(emu, pad)
+        assert not np.array_equal(ref, case(SHAPES[1])[4]) and not np.array_equal(ref16, ref)
+        assert np.array_equal(np.load(str(tmp_path / ("plain_%s.npy" % pad))), ref), pad
+        assert np.array_equal(np.load(str(tmp_path / ("described_%s.npy" % pad))), ref16), pad
+
+
 _ASAN_CHILD = r"""
 import os, sys
 import numpy as np

@@ -31,10 +31,14 @@ def gpu():
     return b
 
 
-@pytest.fixture(scope="module")
-def stacks():
+def make_stacks():
     _, views, k1, k2, w, psi0 = realistic_views(SHAPE, V, (7, 5, 5), seed=71)
     return views, k1, k2, w, psi0
+
+
+@pytest.fixture(scope="module")
+def stacks():
+    return make_stacks()
 
 
 def plain(gpu, stacks, lam, pad, views=None):
@@ -71,9 +75,9 @@ def test_host_stacks_dense_uint16_strided(gpu, stacks, lam, pad):
         from oracle import binding as orc
         o = orc.cpu_deconvolve(psi0, WorkspaceHolder(views, stacks[1], stacks[2], w, lam, 1e-4, ITERS), 4)
         assert np.abs(ref - o).max() <= 1e-4 * np.abs(o).max()
-    # dense float32 through descriptors (every descriptor the default one: the library hands this to the plain call)
+    # dense float32 through descriptors (every descriptor the default one: what the plain call builds for itself)
     assert np.array_equal(described(gpu, stacks, psi0.copy(), views, w, lam, pad), ref)
-    # dense float32 views and weights on the described path itself: psi in a window keeps the call off the shortcut
+    # dense float32 views and weights next to a strided stack: psi in a window
     assert np.array_equal(described(gpu, stacks, window(psi0)[1], views, w, lam, pad), ref)
     # windows of larger arrays, constant weights as a broadcast scalar, psi into a window
     consts = [np.broadcast_to(np.float32(1.0 / V), SHAPE) for _ in range(V)]
@@ -177,6 +181,50 @@ def test_errors_leave_psi_untouched(gpu, stacks):
             assert np.array_equal(psi, psi0), what
     finally:
         gpu.set_pad_mode(None)
+
+
+# ---- the blocking branch of the ABI call (MVN_NO_PIPELINE, read once per process: a child) ---------------------------
+_BLOCKING_CHILD = r"""
+import os, sys
+import numpy as np
+root, out = sys.argv[1], sys.argv[2]
+sys.path.insert(0, root); sys.path.insert(0, os.path.join(root, "tests"))
+from libmultiviewnative_amd import native
+import test_gpu_described_stacks as t
+gpu = native.lib()
+assert gpu.backend_name() == "hip-gfx950"
+stacks = t.make_stacks()
+for pad in t.BLOCKING_PADS:
+    plain, desc = t.blocking_calls(gpu, stacks, pad)
+    np.save(os.path.join(out, "plain_%s.npy" % pad), plain)
+    np.save(os.path.join(out, "described_%s.npy" % pad), desc)
+print("blocking child ok", flush=True)
+"""
+
+BLOCKING_PADS = ("none", "zero")
+
+
+def blocking_calls(b, stacks, pad):
+    """one plain call, and one described call with uint16 images in unaligned windows and psi in a window"""
+    views, _, _, w, psi0 = stacks
+    u16 = [window(np.rint(v).astype(np.uint16), off=(1, 2, 3), fill=9)[1] for v in views]
+    return plain(b, stacks, 0.006, pad), described(b, stacks, window(psi0)[1], u16, w, 0.006, pad).copy()
+
+
+def test_blocking_call_gives_what_the_pipelined_call_gives(gpu, stacks, tmp_path):
+    # the library against itself on another code path, bit for bit (the anchor outside it: the oracle comparison of
+    # test_host_stacks_dense_uint16_strided).  The module's own library handle stays idle while the child works.
+    # Time limit: loading the library into a new process and creating its plans takes seconds, the calls less.
+    r = subprocess.run([sys.executable, "-c", _BLOCKING_CHILD, ROOT, str(tmp_path)], capture_output=True, text=True,
+                       timeout=120, env=dict(os.environ, MVN_NO_PIPELINE="1", MVN_TRACE="1"))
+    assert r.returncode == 0 and "blocking child ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    # the child took the blocking branch: its calls were traced, and none of them started the uploader thread
+    assert "[lmvn::inplace_gpu_deconvolve]" in r.stdout and "(uploader thread)" not in r.stdout, r.stdout[-4000:]
+    for pad in BLOCKING_PADS:
+        ref, ref16 = blocking_calls(gpu, stacks, pad)
+        assert not np.array_equal(ref16, ref)
+        assert np.array_equal(np.load(str(tmp_path / ("plain_%s.npy" % pad))), ref), pad
+        assert np.array_equal(np.load(str(tmp_path / ("described_%s.npy" % pad))), ref16), pad
 
 
 _CHILD = r"""
