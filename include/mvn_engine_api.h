@@ -80,6 +80,30 @@ typedef struct mvn_call_desc {
   void* stream;
 } mvn_call_desc;
 MVN_API int mvn_deconvolve_described(void* psi, struct workspace input, const mvn_call_desc* desc, int device);
+/* How uint16 IMAGE stacks of described calls are held on the device for the calls that follow (process-wide, captured
+ * at the start of mvn_deconvolve_described / at mvn_engine_set_view_described):
+ * 0 (default) converted to float32 on entry, as before - launches and results as without this switch;
+ * 1 kept as uint16: the volume (and a streamed view's ring slot) holds 2 bytes per voxel, the divide pass reads them.
+ * Results are bit for bit those of mode 0.  float32 images, weights and psi are never affected.  Anything else: error.
+ * In mode 1 a uint16 stack in host memory with contiguous rows, under padding "none" (and through the engine API), is
+ * placed by the copy itself, with no pass behind it; every other uint16 stack (device memory, other strides, the padded
+ * policies) takes the ingest pass in its uint16 -> uint16 form (csrc/mvn_ingest.hpp).  The views of one call may mix
+ * element types.  The streamed views of a call share their ring slots: they are kept as uint16 when all of them are
+ * uint16 stacks, and converted as in mode 0 otherwise.
+ * Out of scope, and unchanged by the mode: weights and psi (float32); float32 images (never narrowed); a uint16 image
+ * that is one value for every voxel (strides {0, 0, 0}: converted); the slab engine (mvn_slab_*); mvn_group_* and
+ * MVN_DEVICES (which a described call with other than default descriptors does not use anyway); halo mode -
+ * mvn_engine_set_view_described on an engine with a halo hook keeps the image as float32, and
+ * mvn_engine_set_halo_hook on an engine that holds a uint16 image volume is an error. */
+MVN_API int mvn_set_image_storage(int mode);
+MVN_API int mvn_get_image_storage(int* mode);
+/* mvn_deconvolve_memory for a described call: prices uint16 images at 2 bytes per voxel when the storage mode in force
+ * keeps them (only dtype and strides of desc->image are read).  desc == NULL, or mode 0: exactly
+ * mvn_deconvolve_memory's figure. */
+MVN_API int mvn_deconvolve_memory_described(struct workspace input, const mvn_call_desc* desc, int device,
+                                            int streamed_views, size_t* bytes);
+/* out[0] = divide passes launched on a uint16 image, out[1] = ingest passes that wrote a uint16 volume, since process start */
+MVN_API int mvn_image_storage_counters(long long out[2]);
 /* Padding policy of inplace_gpu_deconvolve for the calls that follow (process-wide): "zero"
  * (default: the reference GPU entry's zero_padd with FFT-friendly padded extents), "zero_exact"
  * (exactly image + kernel - 1), "none" (the reference CPU path's cyclic no_padd); NULL or ""

@@ -159,8 +159,15 @@ struct ConvRecord {
 // the last deconvolution this thread completed (inplace_gpu_deconvolve, or the wait of a ticket)
 static thread_local ConvRecord t_last_conv;
 
-static MemoryQuery memory_query(const shape_t& ext, const workspace& input, size_t embed_floats) {
+// ---- image storage (mvn_set_image_storage): captured at the start of a described call ----
+static std::atomic<int> g_image_storage{0};
+// per view: a described call in storage mode `mode` wants this image kept as uint16
+static bool keeps_u16(const StackRef& image, int mode) { return mode == 1 && image.u16 && !image.broadcast(); }
+
+static MemoryQuery memory_query(const shape_t& ext, const workspace& input, size_t embed_floats,
+                                const std::vector<char>& keep_u16 = std::vector<char>()) {
   MemoryQuery q;
+  q.image_u16 = keep_u16;
   q.ext = ext;
   q.embed_floats = embed_floats;
   q.stats_rows = call_tolerance() >= 0. ? std::max(input.num_iterations_, 1) : 0;
@@ -188,19 +195,12 @@ static bool reusable(const Engine& e, const shape_t& ext, int V) {
   return mine.sw == call.sw && mine.plan_fixed == call.plan_fixed;
 }
 
-// s streamed views spread evenly over the sweep (view floor((j + 1/2) V / s) for j < s), so that each upload
-// runs under the resident view updates between two streamed ones
-static std::vector<int> spread_views(int V, int s) {
-  std::vector<int> out;
-  for (int j = 0; j < s; ++j) out.push_back((int)(((2L * j + 1) * V) / (2L * s)));
-  return out;
-}
-
 // caller holds device_mutex(dev); the auto / stream modes of take_engine
 static std::unique_ptr<Engine> plan_engine(int key, int dev, const shape_t& ext, size_t embed_floats,
-                                           const workspace& input, int mode, bool use_budget = true) {
+                                           const workspace& input, int mode, const std::vector<char>& keep_u16,
+                                           bool use_budget = true) {
   const int V = input.num_views_;
-  MemoryQuery q = memory_query(ext, input, embed_floats);
+  MemoryQuery q = memory_query(ext, input, embed_floats, keep_u16);
   const FormRule rule = call_rule(ext, dev);
   auto need = [&](int s, int ring) {
     q.streamed = s;
@@ -218,6 +218,7 @@ static std::unique_ptr<Engine> plan_engine(int key, int dev, const shape_t& ext,
     held.embed_floats = cached->scratch_floats();
     held.streamed = cached->streamed_count();
     held.ring = cached->ring_size();
+    held.image_u16 = cached->image_types();
     avail += Engine::memory_need(held, rule);
   }
   const size_t budget = use_budget ? current_memory_budget() : 0;
@@ -247,7 +248,7 @@ static std::unique_ptr<Engine> plan_engine(int key, int dev, const shape_t& ext,
   if (cached && cached->streamed_count() == s && cached->ring_size() == ring) return cached;
   cached.reset();  // another residency plan: free it before the new engine allocates
   std::unique_ptr<Engine> e(new Engine(dev, ext, V));
-  e->set_residency(spread_views(V, s), ring);
+  e->set_residency(Engine::spread_views(V, s), ring);
   return e;
 }
 
@@ -255,18 +256,31 @@ static std::unique_ptr<Engine> plan_engine(int key, int dev, const shape_t& ext,
 // for the resident layout (4 volumes per view -- view, weights, two spectra -- + psi + work + the
 // spectrum scratch of the PSF preparation, + the host-shaped embedding scratch of the padded
 // policies, + 2 % slack), is applied only when the call has to allocate: a cached engine of the same
-// shape is re-used as it is (its memory is what the check would ask for), and a stale one of another
+// shape is re-used as it is (its memory is what the check would ask for, but for uint16 image slots that have to
+// grow: see below), and a stale one of another
 // shape is freed BEFORE the free memory is read -- so that "does not fit" is said here, before any
 // work is queued, not by a failing hipMalloc on the staging thread.
 static std::unique_ptr<Engine> take_engine(int key, int dev, const shape_t& ext, int V, size_t embed_floats,
-                                           const workspace& input, int mem_mode) {
+                                           const workspace& input, int mem_mode, const std::vector<char>& keep_u16) {
   // (MVN_MEM_EXACT: resident, priced by the exact model - a described call with stacks in device memory)
-  if (mem_mode == MVN_MEM_EXACT) return plan_engine(key, dev, ext, embed_floats, input, MVN_MEM_STREAM + 1, false);
-  if (mem_mode != MVN_MEM_RESIDENT) return plan_engine(key, dev, ext, embed_floats, input, mem_mode);
+  if (mem_mode == MVN_MEM_EXACT)
+    return plan_engine(key, dev, ext, embed_floats, input, MVN_MEM_STREAM + 1, keep_u16, false);
+  if (mem_mode != MVN_MEM_RESIDENT) return plan_engine(key, dev, ext, embed_floats, input, mem_mode, keep_u16);
   std::unique_ptr<Engine> e = pop_cached_engine(key);  // key = device + lane * kLaneStride
-  if (e && reusable(*e, ext, V) && e->streamed_count() == 0) return e;
-  e.reset();  // wrong shape or rule: free its memory before the new engine allocates
   Layout L(ext[0], ext[1], ext[2]);
+  if (e && reusable(*e, ext, V) && e->streamed_count() == 0) {
+    // (image storage mode 1: a slot that holds a uint16 image grows by half a volume when this call brings it a
+    //  float32 one - the one allocation a re-used engine still makes; it has to fit, or the engine goes and the
+    //  check below speaks)
+    const std::vector<char> held = e->image_types();
+    size_t grow = 0;
+    for (int v = 0; v < V; ++v)
+      if (held[(size_t)v] && !(v < (int)keep_u16.size() && keep_u16[(size_t)v])) grow += L.real_floats() * 2;
+    size_t free_b = 0, total_b = 0;
+    if (grow) be::device_mem_info(&free_b, &total_b);
+    if (grow == 0 || grow < free_b) return e;
+  }
+  e.reset();  // wrong shape or rule: free its memory before the new engine allocates
   const double need = ((4.0 * V + 3.0) * (double)L.B() + 4.0 * (double)embed_floats) * 1.02;
   size_t free_b = 0, total_b = 0;
   be::device_mem_info(&free_b, &total_b);
@@ -573,6 +587,8 @@ struct CallStacks {
   void* stream = nullptr;    // the caller's stream its device stacks were produced on
   bool any_device = false;
   bool need_scratch = false; // some stack passes through the host-shaped embedding scratch
+  int storage = 0;              // the image storage mode the call captured (mvn_set_image_storage)
+  std::vector<char> keep_u16;   // per view: keeps_u16 of its image; empty: none
 };
 
 // a descriptor and its pointer as a StackRef, everything about it checked that can be without touching the memory
@@ -705,9 +721,12 @@ static void deconvolve_call(const workspace& input, const CallStacks& cs, int de
     // on failure the engine is simply dropped
     const bool scratch = cs.need_scratch;
     std::unique_ptr<Engine> eng_owner = take_engine(
-        key, dev, ext, V, embedded && scratch ? (size_t)dims[0] * (size_t)dims[1] * (size_t)dims[2] : 0, input, mem_mode);
+        key, dev, ext, V, embedded && scratch ? (size_t)dims[0] * (size_t)dims[1] * (size_t)dims[2] : 0, input, mem_mode,
+        cs.keep_u16);
     Engine& eng = *eng_owner;
     eng.begin_call();
+    eng.set_image_storage(cs.storage);
+    eng.plan_image_types(cs.keep_u16);
     // stacks are embedded into / cropped out of the padded volume by the transfers themselves
     // (strided device copies), so the padded modes keep the pipelined upload
     const int dims_i[3] = {dims[0], dims[1], dims[2]};
@@ -843,6 +862,8 @@ int mvn_deconvolve_described(void* psi, struct workspace input, const mvn_call_d
       check_location(dc.image.back(), "image " + n, &owner);
       check_location(dc.weights.back(), "weights " + n, &owner);
     }
+    dc.storage = g_image_storage.load();
+    for (int v = 0; v < V; ++v) dc.keep_u16.push_back(keeps_u16(dc.image[(size_t)v], dc.storage) ? 1 : 0);
     dc.need_scratch = through_scratch(dc.psi);
     dc.any_device = dc.psi.device;
     for (int v = 0; v < V; ++v) {
@@ -1040,26 +1061,65 @@ int mvn_set_memory_budget(long long bytes) {
   return guarded("mvn_set_memory_budget", [&] { g_mem_budget.store(bytes > 0 ? bytes : -1); });
 }
 
-int mvn_deconvolve_memory(struct workspace input, int device, int streamed_views, size_t* bytes) {
-  return guarded("mvn_deconvolve_memory", [&] {
-    if (!bytes) throw std::invalid_argument("null bytes");
-    *bytes = 0;
-    if (!input.data_ || input.num_views_ < 1) throw std::invalid_argument("no views");
+// desc: the descriptors of a described call (their pointers are not looked at), or null
+static void deconvolve_memory(struct workspace input, const mvn_call_desc* desc, int device, int streamed_views,
+                              size_t* bytes) {
+  if (!bytes) throw std::invalid_argument("null bytes");
+  *bytes = 0;
+  if (!input.data_ || input.num_views_ < 1) throw std::invalid_argument("no views");
+  for (int v = 0; v < input.num_views_; ++v) {
+    const view_data& d = input.data_[v];
+    if (!d.image_dims_ || !d.kernel1_dims_ || !d.kernel2_dims_)
+      throw std::invalid_argument("view " + std::to_string(v) + " has null dims");
+  }
+  if (streamed_views < 0 || streamed_views > input.num_views_)
+    throw std::invalid_argument("streamed_views must be in [0, num_views_]");
+  std::vector<char> keep;
+  const int storage = g_image_storage.load();
+  if (desc && desc->image && storage == 1)
     for (int v = 0; v < input.num_views_; ++v) {
-      const view_data& d = input.data_[v];
-      if (!d.image_dims_ || !d.kernel1_dims_ || !d.kernel2_dims_)
-        throw std::invalid_argument("view " + std::to_string(v) + " has null dims");
+      const mvn_stack_desc& d = desc->image[v];
+      keep.push_back(d.dtype == MVN_U16 && (d.stride[0] != 0 || d.stride[1] != 0 || d.stride[2] != 0) ? 1 : 0);
     }
-    if (streamed_views < 0 || streamed_views > input.num_views_)
-      throw std::invalid_argument("streamed_views must be in [0, num_views_]");
-    const int dev = pick_device(device);
-    shape_t dims, ext;
-    int off[3];
-    call_extents(input, current_pad_mode(), dev, &dims, &ext, off);
-    MemoryQuery q = memory_query(ext, input, embed_floats_of(dims, ext));
-    q.streamed = streamed_views;
-    q.ring = streamed_views > 0 ? 2 : 0;
-    *bytes = Engine::memory_need(q, call_rule(ext, dev));
+  const int dev = pick_device(device);
+  shape_t dims, ext;
+  int off[3];
+  call_extents(input, current_pad_mode(), dev, &dims, &ext, off);
+  MemoryQuery q = memory_query(ext, input, embed_floats_of(dims, ext), keep);
+  q.streamed = streamed_views;
+  q.ring = streamed_views > 0 ? 2 : 0;
+  *bytes = Engine::memory_need(q, call_rule(ext, dev));
+}
+
+int mvn_deconvolve_memory(struct workspace input, int device, int streamed_views, size_t* bytes) {
+  return guarded("mvn_deconvolve_memory", [&] { deconvolve_memory(input, nullptr, device, streamed_views, bytes); });
+}
+
+int mvn_deconvolve_memory_described(struct workspace input, const mvn_call_desc* desc, int device, int streamed_views,
+                                    size_t* bytes) {
+  return guarded("mvn_deconvolve_memory_described",
+                 [&] { deconvolve_memory(input, desc, device, streamed_views, bytes); });
+}
+
+int mvn_set_image_storage(int mode) {
+  return guarded("mvn_set_image_storage", [&] {
+    if (mode != 0 && mode != 1)
+      throw std::invalid_argument("image storage mode must be 0 (float32 on entry) or 1 (uint16 images kept as uint16)");
+    g_image_storage.store(mode);
+  });
+}
+
+int mvn_get_image_storage(int* mode) {
+  return guarded("mvn_get_image_storage", [&] {
+    if (!mode) throw std::invalid_argument("null mode");
+    *mode = g_image_storage.load();
+  });
+}
+
+int mvn_image_storage_counters(long long out[2]) {
+  return guarded("mvn_image_storage_counters", [&] {
+    if (!out) throw std::invalid_argument("null out");
+    Engine::image_storage_counters(out);
   });
 }
 
@@ -1771,6 +1831,7 @@ static void engine_set_view(Engine& E, int v, const void* image, const mvn_stack
     if (owner >= 0 && owner != E.device()) throw std::invalid_argument("the stacks live on another device than the engine");
     E.wait_for_caller(stream);
   }
+  E.set_image_storage(checked ? g_image_storage.load() : 0);  // (the plain entry point brings float32)
   E.set_view(v, im, w, kernel1, k1dims, kernel2, k2dims);
 }
 

@@ -135,7 +135,8 @@ void launch_copy3d(float* dst, long drow, long dplane, const float* src, long sr
 // a caller's stack (float32 or uint16, element strides) into the engine volume in one pass that writes every float of
 // the volume, and the window of psi back out into a strided float32 destination (mvn_ingest.hpp); the stack is
 // DEVICE memory here (host stacks cross PCIe first, Engine::ingest_stack)
-void launch_ingest3d(const IngestParams& p, bool u16, stream_t s);
+// (dst_u16: a uint16 stack into a uint16 volume, unconverted)
+void launch_ingest3d(const IngestParams& p, bool u16, stream_t s, bool dst_u16 = false);
 void launch_extract3d(const ExtractParams& p, stream_t s);
 
 // stand-alone pointwise ops on flat arrays (legacy ABI: compute_quotient / compute_final_values)

@@ -185,6 +185,7 @@ template <int MODE>
 static void emu_wave_rows_mode(const RowsParams& p) {
   switch (p.epi.mode) {
     case MVN_EPI_DIVIDE: emu_wave_rows_run<MODE, MVN_EPI_DIVIDE>(p); break;
+    case MVN_EPI_DIVIDE_U16: emu_wave_rows_run<MODE, MVN_EPI_DIVIDE_U16>(p); break;
     case MVN_EPI_UPDATE: emu_wave_rows_run<MODE, MVN_EPI_UPDATE>(p); break;
     case MVN_EPI_UPDATE_STATS: emu_wave_rows_run<MODE, MVN_EPI_UPDATE_STATS>(p); break;
     case MVN_EPI_DELTA:
@@ -226,6 +227,7 @@ static void emu_rows_lines(const RowsParams& p, long ntiles, int kind) {
       } else if (kind == 1) {
         switch (p.epi.mode) {
           case MVN_EPI_DIVIDE: fx_rows_run<H, 1, MVN_EPI_DIVIDE, Ctx, true>(p, t, ntiles, l, *ctx); break;
+          case MVN_EPI_DIVIDE_U16: fx_rows_run<H, 1, MVN_EPI_DIVIDE_U16, Ctx, true>(p, t, ntiles, l, *ctx); break;
           case MVN_EPI_UPDATE: fx_rows_run<H, 1, MVN_EPI_UPDATE, Ctx, true>(p, t, ntiles, l, *ctx); break;
           case MVN_EPI_UPDATE_STATS: fx_rows_run_stats<H, 1, SCtx, true>(p, t, ntiles, l, *sctx); break;
           case MVN_EPI_DELTA: fx_rows_run<H, 1, MVN_EPI_DELTA, Ctx, true>(p, t, ntiles, l, *ctx); break;
@@ -234,6 +236,7 @@ static void emu_rows_lines(const RowsParams& p, long ntiles, int kind) {
       } else {
         switch (p.epi.mode) {
           case MVN_EPI_DIVIDE: fx_rows_run<H, 2, MVN_EPI_DIVIDE, Ctx, true>(p, t, ntiles, l, *ctx); break;
+          case MVN_EPI_DIVIDE_U16: fx_rows_run<H, 2, MVN_EPI_DIVIDE_U16, Ctx, true>(p, t, ntiles, l, *ctx); break;
           case MVN_EPI_UPDATE: fx_rows_run<H, 2, MVN_EPI_UPDATE, Ctx, true>(p, t, ntiles, l, *ctx); break;
           case MVN_EPI_UPDATE_STATS: fx_rows_run_stats<H, 2, SCtx, true>(p, t, ntiles, l, *sctx); break;
           default: fx_rows_run<H, 2, MVN_EPI_STORE, Ctx, true>(p, t, ntiles, l, *ctx); break;
@@ -298,6 +301,7 @@ static void emu_rows_fused(const RowsParams& p, long ntiles) {
       cfloat* l = (cfloat*)lds.data();
       switch (p.epi.mode) {
         case MVN_EPI_DIVIDE: fx_rows_run<H, 2, MVN_EPI_DIVIDE>(p, t, grid, l, *ctx); break;
+        case MVN_EPI_DIVIDE_U16: fx_rows_run<H, 2, MVN_EPI_DIVIDE_U16>(p, t, grid, l, *ctx); break;
         case MVN_EPI_UPDATE: fx_rows_run<H, 2, MVN_EPI_UPDATE>(p, t, grid, l, *ctx); break;
         case MVN_EPI_UPDATE_STATS: fx_rows_run_stats<H, 2, SCtx>(p, t, grid, l, *sctx); break;
         default: fx_rows_run<H, 2, MVN_EPI_STORE>(p, t, grid, l, *ctx); break;
@@ -310,7 +314,7 @@ void launch_rows_c2r_r2c(const RowsParams& p0, long ntiles, int, size_t lds_byte
   RowsParams p = p0;
   mvn_arm_poison(p.epi);  // (the device kernels do this at their entry)
   if (p.lines) return emu_rows_lines(p, ntiles, 2);
-  if (emu_wave_rows(p, p.epi.mode == MVN_EPI_DIVIDE ? 4 : 8)) return emu_wave_rows_mode<MVN_WR_C2R_R2C>(p);
+  if (emu_wave_rows(p, mvn_epi_math(p.epi.mode) == MVN_EPI_DIVIDE ? 4 : 8)) return emu_wave_rows_mode<MVN_WR_C2R_R2C>(p);
   if (!p.fixed) {  // run-time-radix form of the fused pass (any even d2)
 #pragma omp parallel
     {
@@ -320,6 +324,8 @@ void launch_rows_c2r_r2c(const RowsParams& p0, long ntiles, int, size_t lds_byte
         cfloat* l = (cfloat*)lds.data();
         if (p.epi.mode == MVN_EPI_UPDATE_STATS) {
           MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, true, true>(p, t, 0, 1, l)));
+        } else if (p.epi.mode == MVN_EPI_DIVIDE_U16) {
+          MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, true, false, true>(p, t, 0, 1, l)));
         } else {
           MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, true>(p, t, 0, 1, l)));
         }
@@ -353,6 +359,7 @@ static void emu_rows_fixed(const RowsParams& p, long ntiles, bool r2c) {
       else {
         switch (p.epi.mode) {
           case MVN_EPI_DIVIDE: fx_rows_run<H, 1, MVN_EPI_DIVIDE>(p, t, grid, l, *ctx); break;
+          case MVN_EPI_DIVIDE_U16: fx_rows_run<H, 1, MVN_EPI_DIVIDE_U16>(p, t, grid, l, *ctx); break;
           case MVN_EPI_UPDATE: fx_rows_run<H, 1, MVN_EPI_UPDATE>(p, t, grid, l, *ctx); break;
           case MVN_EPI_UPDATE_STATS: fx_rows_run_stats<H, 1, SCtx>(p, t, grid, l, *sctx); break;
           case MVN_EPI_DELTA: fx_rows_run<H, 1, MVN_EPI_DELTA>(p, t, grid, l, *ctx); break;
@@ -489,6 +496,12 @@ void launch_rows_c2r(const RowsParams& p0, bool even, long ntiles, int, size_t l
         } else {
           MVN_DISPATCH_T(p.T, (rows_c2r_odd_body<TT, true>(p, t, 0, 1, l)));
         }
+      } else if (p.epi.mode == MVN_EPI_DIVIDE_U16) {
+        if (even) {
+          MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, false, false, true>(p, t, 0, 1, l)));
+        } else {
+          MVN_DISPATCH_T(p.T, (rows_c2r_odd_body<TT, false, true>(p, t, 0, 1, l)));
+        }
       } else if (even) {
         MVN_DISPATCH_T(p.T, rows_c2r_even_body<TT>(p, t, 0, 1, l));
       } else {
@@ -591,12 +604,15 @@ void launch_copy3d(float* dst, long drow, long dplane, const float* src, long sr
       std::memcpy(dst + z * dplane + y * drow, src + z * splane + y * srow, sizeof(float) * (size_t)nx);
 }
 
-void launch_ingest3d(const IngestParams& p, bool u16, stream_t) {
+void launch_ingest3d(const IngestParams& p, bool u16, stream_t, bool dst_u16) {
+  if (dst_u16 && (!u16 || p.use_value)) throw std::invalid_argument("mvn: a uint16 volume takes a uint16 stack");
   const long nblocks = mvn_ingest_blocks(p.rows);
 #pragma omp parallel for schedule(static)
   for (long blk = 0; blk < nblocks; ++blk)
     for (int t = 0; t < MVN_INGEST_WG; ++t) {
-      if (u16)
+      if (dst_u16)
+        mvn_ingest_rows<uint16_t, uint16_t>(p, blk, t);
+      else if (u16)
         mvn_ingest_rows<uint16_t>(p, blk, t);
       else
         mvn_ingest_rows<float>(p, blk, t);

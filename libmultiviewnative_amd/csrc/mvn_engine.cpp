@@ -378,6 +378,8 @@ void Plan3D::rows_c2r(const cfloat* in, const cfloat* in_nyq, float* out_real,
   if (out_real) out_real += row0 * L.RP;
   EpilogueParams epi = epi_all;
   const long eoff = row0 * L.RP;
+  // (the offsets below are in floats: a uint16 view is only ever divided by whole-volume launches, Engine::set_halo_hook)
+  if (epi.mode == MVN_EPI_DIVIDE_U16 && row0 != 0) throw std::logic_error("mvn: a row range on a uint16 image volume");
   if (epi.view) epi.view += eoff;
   if (epi.psi) epi.psi += eoff;
   if (epi.weights) epi.weights += eoff;
@@ -430,6 +432,8 @@ void Plan3D::rows_c2r_r2c(cfloat* data, cfloat* nyq, const EpilogueParams& epi_a
   if (nyq) nyq += row0;
   EpilogueParams epi = epi_all;
   const long eoff = row0 * L.RP;
+  // (the offsets below are in floats: a uint16 view is only ever divided by whole-volume launches, Engine::set_halo_hook)
+  if (epi.mode == MVN_EPI_DIVIDE_U16 && row0 != 0) throw std::logic_error("mvn: a row range on a uint16 image volume");
   if (epi.view) epi.view += eoff;
   if (epi.psi) epi.psi += eoff;
   if (epi.weights) epi.weights += eoff;
@@ -766,6 +770,7 @@ Engine::Engine(int device, const shape_t& dims, int num_views) : device_(device)
   poison_ = poison_own_;
   views_.resize((size_t)num_views);
   stream_pos_.assign((size_t)num_views, -1);
+  want_u16_.assign((size_t)num_views, 0);
   spec_tiled_ = plan_->tiles_spectra();
   sw_ = FormSwitches::from_env();  // read per engine (tests)
   d0_stagger_ = env_int("MVN_D0_STAGGER", 64);
@@ -865,11 +870,11 @@ void Engine::set_embedding(const int dims[3], const int off[3], bool scratch) {
   be::stream_sync(stream_);
   // the interior moves: what used to be interior may now be padding and must read zero
   for (size_t v = 0; v < views_.size(); ++v) {
-    if (views_[v].image) be::dzero(views_[v].image, plan_->main_bytes(), stream_);
-    if (views_[v].weights) be::dzero(views_[v].weights, plan_->main_bytes(), stream_);
+    if (views_[v].image && stream_pos_[v] < 0) be::dzero(views_[v].image, image_bytes(views_[v].image_u16), stream_);
+    if (views_[v].weights && stream_pos_[v] < 0) be::dzero(views_[v].weights, plan_->main_bytes(), stream_);
   }
   for (size_t r = 0; r < ring_.size(); ++r) {
-    be::dzero(ring_[r].image, plan_->main_bytes(), stream_);
+    if (ring_[r].image) be::dzero(ring_[r].image, image_bytes(ring_[r].image_u16), stream_);
     be::dzero(ring_[r].weights, plan_->main_bytes(), stream_);
   }
   be::stream_sync(stream_);
@@ -906,10 +911,18 @@ static void check_host_rows(const StackRef& st, const int* n) {
     throw std::invalid_argument("mvn: rows of a stack in host memory must not overlap (stride[1] >= extent[2])");
 }
 
-long long Engine::ingest_stack(float* dst, const StackRef& st, float* scratch, bool dst_dirty, be::stream_t s) {
+static std::atomic<long long> g_u16_divides{0}, g_u16_ingests{0};
+void Engine::image_storage_counters(long long out[2]) {
+  out[0] = g_u16_divides.load();
+  out[1] = g_u16_ingests.load();
+}
+
+long long Engine::ingest_stack(float* dst, const StackRef& st, float* scratch, bool dst_dirty, be::stream_t s,
+                               bool dst_u16) {
   const Layout& L = plan_->L;
   const int* n = host_dims_;
   if (!st.ptr) throw std::invalid_argument("mvn: null stack");
+  if (dst_u16 && (!st.u16 || st.broadcast())) throw std::logic_error("mvn: a uint16 volume takes a uint16 stack");
   for (int d = 0; d < 3; ++d)
     if (st.stride[d] < 0) throw std::invalid_argument("mvn: negative stride");
   IngestParams p;
@@ -919,7 +932,8 @@ long long Engine::ingest_stack(float* dst, const StackRef& st, float* scratch, b
   p.src = st.ptr, p.s0 = st.stride[0], p.s1 = st.stride[1], p.s2 = st.stride[2];
   p.use_value = 0, p.value = 0.f;
   if (st.device) {  // read where it lies
-    be::launch_ingest3d(p, st.u16, s);
+    be::launch_ingest3d(p, st.u16, s, dst_u16);
+    if (dst_u16) ++g_u16_ingests;
     return 0;
   }
   if (st.broadcast()) {  // one value in host memory: it travels as a kernel argument
@@ -933,16 +947,15 @@ long long Engine::ingest_stack(float* dst, const StackRef& st, float* scratch, b
   const size_t esz = st.u16 ? sizeof(uint16_t) : sizeof(float);
   const long long bytes = (long long)(host_floats() * esz);
   const bool dense = (n[1] == 1 || st.stride[1] == n[2]) && (n[0] == 1 || st.stride[0] == (long long)n[1] * n[2]);
-  if (!embedded_ && !st.u16) {  // float32 into a volume of its own extents: the copy itself places it
-    if (dst_dirty && L.RP != L.d2) be::dzero(dst, plan_->main_bytes(), s);
+  if (!embedded_ && (!st.u16 || dst_u16)) {  // into a volume of its own extents and element type: the copy itself places it
+    if (dst_dirty && L.RP != L.d2) be::dzero(dst, image_bytes(dst_u16), s);
     if (!dense)
-      host_rows_to_device((char*)dst, (size_t)L.RP * sizeof(float), (size_t)L.d1 * L.RP * sizeof(float),
-                          (const char*)st.ptr, st.stride[0] * 4, st.stride[1] * 4, (size_t)n[2] * sizeof(float), n, s);
+      host_rows_to_device((char*)dst, (size_t)L.RP * esz, (size_t)L.d1 * L.RP * esz, (const char*)st.ptr,
+                          st.stride[0] * (long long)esz, st.stride[1] * (long long)esz, (size_t)n[2] * esz, n, s);
     else if (L.RP == L.d2)
       be::h2d(dst, st.ptr, (size_t)bytes, s);
     else
-      be::h2d_2d(dst, (size_t)L.RP * sizeof(float), st.ptr, (size_t)L.d2 * sizeof(float), (size_t)L.d2 * sizeof(float),
-                 L.rows, s);
+      be::h2d_2d(dst, (size_t)L.RP * esz, st.ptr, (size_t)L.d2 * esz, (size_t)L.d2 * esz, L.rows, s);
     return bytes;
   }
   if (!scratch) throw std::logic_error("mvn: no scratch for a host stack");
@@ -959,22 +972,23 @@ long long Engine::ingest_stack(float* dst, const StackRef& st, float* scratch, b
     return bytes;
   }
   p.src = scratch, p.s0 = (long long)n[1] * n[2], p.s1 = n[2], p.s2 = 1;
-  be::launch_ingest3d(p, true, s);
+  be::launch_ingest3d(p, true, s, dst_u16);
+  if (dst_u16) ++g_u16_ingests;
   return bytes;
 }
 
 long long Engine::ingest_pair(float* image_dst, float* weights_dst, const StackRef& image, const StackRef& weights,
-                              be::stream_t s) {
+                              be::stream_t s, bool image_u16) {
   if (weights.u16) throw std::invalid_argument("mvn: weights are float32");
   float* scr = embed_scratch_;
   bool dirty = false;
-  if (!scr && !image.device && !image.broadcast() && image.u16) {
+  if (!image_u16 && !scr && !image.device && !image.broadcast() && image.u16) {
     // (no embedding, so no scratch: the raw uint16 stack lands in the view's weights volume, which is filled next,
     //  on the same stream)
     scr = weights_dst;
     dirty = true;
   }
-  long long bytes = ingest_stack(image_dst, image, scr, false, s);
+  long long bytes = ingest_stack(image_dst, image, scr, false, s, image_u16);
   bytes += ingest_stack(weights_dst, weights, embed_scratch_, dirty, s);
   return bytes;
 }
@@ -990,13 +1004,25 @@ void Engine::wait_for_caller(void* caller_stream) {
 
 void Engine::alloc_view(ViewSlot& s) {
   const size_t mb = plan_->main_bytes();
-  if (s.image || stream_pos_[(size_t)(&s - views_.data())] >= 0) return;  // (streamed views: the ring's slots)
-  s.image = (float*)be::dmalloc(mb);
-  s.weights = (float*)be::dmalloc(mb);
+  const size_t v = (size_t)(&s - views_.data());
+  if (stream_pos_[v] >= 0) return;  // (streamed views: the ring's slots)
+  const bool u16 = want_u16_[v] != 0;
+  if (s.image && s.image_u16 != u16) {  // the slot held the other element type: its image alone is re-allocated
+    be::stream_sync(stream_);
+    be::dfree(s.image);
+    s.image = nullptr;
+    ++graph_gen_;
+  }
+  const bool new_image = !s.image, new_weights = !s.weights;
+  if (new_image) {
+    s.image = (float*)be::dmalloc(image_bytes(u16));
+    s.image_u16 = u16;
+  }
+  if (new_weights) s.weights = (float*)be::dmalloc(mb);
   // the PSF buffers (3-D spectra or direct-form taps) are allocated by prepare_psf, which knows the form
-  if (plan_->L.RP != plan_->L.d2 || embedded_) {  // odd d2 / embedded stacks: the padding must hold zeros
-    be::dzero(s.image, mb, stream_);
-    be::dzero(s.weights, mb, stream_);
+  if ((new_image || new_weights) && (plan_->L.RP != plan_->L.d2 || embedded_)) {  // odd d2 / embedded stacks: the padding must hold zeros
+    if (new_image) be::dzero(s.image, image_bytes(u16), stream_);
+    if (new_weights) be::dzero(s.weights, mb, stream_);
     be::stream_sync(stream_);
   }
 }
@@ -1428,8 +1454,10 @@ void Engine::set_view(int v, const StackRef& image, const StackRef& weights, con
   be::set_device(device_);
   if (stream_pos_[(size_t)v] >= 0) throw std::logic_error("mvn: a streamed view is staged by the pipelined call only");
   ViewSlot& s = views_[(size_t)v];
+  // (halo mode divides row ranges, whose offsets are in floats: the image stays float32 under a hook)
+  want_u16_[(size_t)v] = image_storage_ == 1 && image.u16 && !image.broadcast() && !halo_fn_;
   alloc_view(s);
-  ingest_pair(s.image, s.weights, image, weights, stream_);
+  ingest_pair(s.image, s.weights, image, weights, stream_, s.image_u16);
   be::stream_sync(stream_);  // the sources have been consumed
   prepare_psfs(s, kernel1, k1dims, kernel2, k2dims, false, stream_);
   s.set = true;
@@ -1495,7 +1523,7 @@ void Engine::ingest_device_view(int v, const StackRef& image, const StackRef& we
   be::set_device(device_);
   ViewSlot& s = views_[(size_t)v];
   if (stream_pos_[(size_t)v] >= 0) throw std::logic_error("mvn: a call with stacks in device memory runs resident");
-  ingest_pair(s.image, s.weights, image, weights, stream_);
+  ingest_pair(s.image, s.weights, image, weights, stream_, s.image_u16);
   pre_ingested_[(size_t)v] = 1;
 }
 
@@ -1507,7 +1535,7 @@ void Engine::stage_view(int v, const StackRef& image, const StackRef& weights, c
   if (stream_pos_[(size_t)v] >= 0)
     ring_upload(v, image, weights);
   else if (!pre_ingested_[(size_t)v])
-    ingest_pair(s.image, s.weights, image, weights, upload_stream_);
+    ingest_pair(s.image, s.weights, image, weights, upload_stream_, s.image_u16);
   prepare_psfs(s, kernel1, k1dims, kernel2, k2dims, true, upload_stream_);
   be::event_record(staged_ev_[(size_t)v], upload_stream_);
   s.set = true;
@@ -1562,6 +1590,64 @@ void Engine::stream_counters(long long out[3]) {
 
 void Engine::count_streamed_call() { ++g_stream_calls; }
 
+std::vector<int> Engine::spread_views(int V, int s) {
+  std::vector<int> out;
+  for (int j = 0; j < s; ++j) out.push_back((int)(((2L * j + 1) * V) / (2L * s)));
+  return out;
+}
+
+std::vector<char> Engine::kept_u16(const std::vector<char>& want, const std::vector<int>& streamed, int V) {
+  std::vector<char> out((size_t)V, 0);
+  if (want.empty()) return out;
+  if ((int)want.size() != V) throw std::invalid_argument("mvn: one image storage wish per view");
+  for (int v = 0; v < V; ++v) out[(size_t)v] = want[(size_t)v] ? 1 : 0;
+  bool all = true;
+  for (int v : streamed) all = all && out[(size_t)v];
+  if (!all)
+    for (int v : streamed) out[(size_t)v] = 0;
+  return out;
+}
+
+void Engine::plan_image_types(const std::vector<char>& want) {
+  be::set_device(device_);
+  want_u16_ = kept_u16(want, streamed_order_, (int)views_.size());
+  if (ring_.empty()) return;
+  const bool u16 = want_u16_[(size_t)streamed_order_[0]] != 0;  // (all streamed views, or none)
+  if (ring_[0].image && ring_[0].image_u16 == u16) return;
+  alloc_ring_images(u16);
+}
+
+// the ring's image volumes (again): zeroed once, the padded rows and the embedding margins are never written
+void Engine::alloc_ring_images(bool u16) {
+  be::stream_sync(stream_);
+  for (RingSlot& r : ring_) {
+    be::dfree(r.image);
+    r.image = nullptr;
+  }
+  for (RingSlot& r : ring_) {
+    r.image = (float*)be::dmalloc(image_bytes(u16));
+    r.image_u16 = u16;
+    be::dzero(r.image, image_bytes(u16), stream_);
+  }
+  be::stream_sync(stream_);
+}
+
+int Engine::u16_views() const {
+  int n = 0;
+  for (const ViewSlot& s : views_) n += (s.image && s.image_u16) ? 1 : 0;
+  return n;
+}
+
+void Engine::divide_epilogue(EpilogueParams& e, const ViewSlot& s) const {
+  e.view = s.image;
+  e.mode = MVN_EPI_DIVIDE;
+  if (s.image_u16) {
+    e.view16 = (const unsigned short*)s.image;
+    e.mode = MVN_EPI_DIVIDE_U16;
+    ++g_u16_divides;
+  }
+}
+
 void Engine::set_residency(const std::vector<int>& streamed, int ring) {
   if (!streamed_order_.empty() || !ring_.empty()) throw std::logic_error("mvn: the residency plan is set once");
   for (size_t v = 0; v < views_.size(); ++v)
@@ -1582,9 +1668,8 @@ void Engine::set_residency(const std::vector<int>& streamed, int ring) {
   const size_t mb = plan_->main_bytes();
   ring_.resize((size_t)ring);
   for (RingSlot& r : ring_) {  // zeroed once: the padded rows and the embedding margins are never written
-    r.image = (float*)be::dmalloc(mb);
+    // (the image volumes come with the call's image types: plan_image_types)
     r.weights = (float*)be::dmalloc(mb);
-    be::dzero(r.image, mb, stream_);
     be::dzero(r.weights, mb, stream_);
     r.filled = be::event_create_sync();
     r.freed = be::event_create_sync();
@@ -1606,7 +1691,8 @@ void Engine::ring_upload(int v, const StackRef& image, const StackRef& weights) 
   RingSlot& r = ring_[(size_t)(k % R)];
   if (k >= R) be::stream_wait_event(upload_stream_, r.freed);
   if (image.device || weights.device) throw std::logic_error("mvn: a call with stacks in device memory runs resident");
-  g_stream_bytes += ingest_pair(r.image, r.weights, image, weights, upload_stream_);
+  if (!r.image) throw std::logic_error("mvn: the ring has no image volumes (plan_image_types)");
+  g_stream_bytes += ingest_pair(r.image, r.weights, image, weights, upload_stream_, r.image_u16);
   be::event_record(r.filled, upload_stream_);
   {
     std::lock_guard<std::mutex> lk(stage_mu_);
@@ -1640,6 +1726,7 @@ void Engine::ring_acquire(ViewSlot& s) {
   const RingSlot& r = ring_[(size_t)(k % (long)ring_.size())];
   be::stream_wait_event(stream_, r.filled);
   s.image = r.image;
+  s.image_u16 = r.image_u16;
   s.weights = r.weights;
 }
 
@@ -1686,8 +1773,15 @@ size_t Engine::memory_need(const MemoryQuery& q, const FormRule& rule) {
   if (rule.sw.direct) add(mb, 1), add(nb, 1);      // second work volume (reserve_views)
   add(256, 1);                                    // poison words
   add(q.embed_floats * sizeof(float), 1);         // embedding scratch of the padded policies
-  add(mb, 2 * (size_t)(V - q.streamed));          // image + weights of the resident views
-  add(mb, 2 * (size_t)q.ring);                    // ring slots of the streamed ones
+  // image + weights of the resident views, ring slots of the streamed ones; an image held as uint16 (kept_u16) is
+  // the same element grid at 2 bytes per voxel
+  const std::vector<int> sv = spread_views(V, q.streamed);
+  const std::vector<char> kept = kept_u16(q.image_u16, sv, V);
+  std::vector<char> streams((size_t)V, 0);
+  for (int v : sv) streams[(size_t)v] = 1;
+  for (int v = 0; v < V; ++v)
+    if (!streams[(size_t)v]) add(kept[(size_t)v] ? mb / 2 : mb, 1), add(mb, 1);
+  if (q.ring) add(kept[(size_t)sv[0]] ? mb / 2 : mb, (size_t)q.ring), add(mb, (size_t)q.ring);
   size_t scr = 0;
   bool spectra = false;
   for (const std::array<int, 3>& k : q.kernels) {
@@ -1792,9 +1886,8 @@ void Engine::conv_pair(int v, double lambda, float min_value, int final_mode, in
 
   EpilogueParams e1;
   std::memset(&e1, 0, sizeof(e1));
-  e1.mode = MVN_EPI_DIVIDE;
   e1.scale = 1.f;  // 1/N already lives in the PSF spectrum
-  e1.view = s.image;
+  divide_epilogue(e1, s);
   e1.guard_zero_view = quotient_guard_ ? 1 : 0;
 
   EpilogueParams e2;
@@ -2042,6 +2135,7 @@ int Engine::iterate_sweeps(int iterations, double lambda, float min_value, doubl
         be::graph_destroy(sweep_graph_);
         sweep_graph_ = nullptr;
       }
+      if (sweep_graph_) g_u16_divides += u16_views();  // (a replay; the capture below counts through conv_pair)
       if (!sweep_graph_) {
         // all views were used by sweep 0, so none is still being staged
         const float* work_at_capture = work_;
@@ -2140,6 +2234,9 @@ void Engine::set_halo_planes(int planes, bool split) {
 
 void Engine::set_halo_hook(halo_fn_t fn, void* user, bool drain, bool post) {
   if (fn) {
+    // halo mode divides ranges of rows, whose operand offsets are in floats (Plan3D::rows_c2r*)
+    if (u16_views() > 0)
+      throw std::invalid_argument("mvn: no halo hook on an engine that holds a uint16 image volume (image storage mode 1)");
     if (!plan_->L.even || !mvn_dim0_packed_possible(plan_->L.d0))
       throw std::invalid_argument("mvn: halo mode needs an even last extent and at most 4062 planes per rank");
     packed_allowed_ = true;  // (a hook that also exchanges the Nyquist plane says so: set_halo_nyq_aware)
@@ -2272,9 +2369,8 @@ void Engine::compute_delta_head(double lambda, float min_value) {
     prof = (prof_.enabled && (pair_counter_++ % every) == 0) ? &prof_ : nullptr;
     EpilogueParams e1;
     std::memset(&e1, 0, sizeof(e1));
-    e1.mode = MVN_EPI_DIVIDE;
     e1.scale = 1.f;
-    e1.view = s.image;
+    divide_epilogue(e1, s);
     e1.guard_zero_view = quotient_guard_ ? 1 : 0;
     EpilogueParams e2;
     std::memset(&e2, 0, sizeof(e2));

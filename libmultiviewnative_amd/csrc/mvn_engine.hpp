@@ -270,7 +270,8 @@ class PlanStore {
 };
 
 struct ViewSlot {
-  float* image = nullptr;
+  float* image = nullptr;   // image_u16: a uint16 volume (the same element grid at 2 bytes per voxel) behind this pointer
+  bool image_u16 = false;
   float* weights = nullptr;
   float* spec1 = nullptr;  // main array of the kernel1 spectrum (pre-scaled by 1/N)
   cfloat* nyq1 = nullptr;
@@ -306,6 +307,9 @@ struct MemoryQuery {
   int ring = 0;
   int stats_rows = 0;  // convergence statistics on: the iterations of the call (Engine::iterate), else 0
   int accel_rows = 0;  // acceleration on: the iterations of the call, else 0
+  // per view: the call wants its image kept as uint16 (image storage mode 1 and a uint16 stack that is no broadcast);
+  // empty: none.  What is then held as uint16: Engine::kept_u16.
+  std::vector<char> image_u16;
 };
 
 // A stack as the engine takes it (the described entry points' mvn_stack_desc, include/mvn_engine_api.h; the plain ones
@@ -354,6 +358,22 @@ class Engine {
   // PSF forms (direct taps, fused-pass taps, 3-D spectra) that `rule` gives for its kernels, plus a small slack for
   // plan tables and allocator rounding.  The single source of truth of the memory planner (mvn_abi.cpp).
   static size_t memory_need(const MemoryQuery& q, const FormRule& rule);
+  // The views s of V views stream: spread evenly over the sweep (view floor((j + 1/2) V / s) for j < s), so that
+  // each upload runs under the resident view updates between two streamed ones.
+  static std::vector<int> spread_views(int V, int s);
+  // Image storage (mvn_set_image_storage, include/mvn_engine_api.h).  `want`: per view, keep the image as uint16.
+  // A resident view is held as it is wanted.  The streamed views share the ring's slots, whose margins are cleared
+  // once and never rewritten by a float32 upload: they are held as uint16 only when every streamed view is wanted so
+  // (a ring slot is as wide as the widest streamed image).  Used by memory_need and by plan_image_types alike.
+  static std::vector<char> kept_u16(const std::vector<char>& want, const std::vector<int>& streamed, int V);
+  // ABI call, before reserve_views(): the call's wishes; slots (and the ring) that held the other element type are
+  // re-allocated, their PSF forms stay
+  void plan_image_types(const std::vector<char>& want);
+  std::vector<char> image_types() const { return want_u16_; }
+  // engine API (set_view): 1 = a uint16 image stack that is no broadcast is kept as uint16 unless a halo hook is set
+  void set_image_storage(int mode) { image_storage_ = mode; }
+  // divide passes launched on a uint16 image, ingest passes that wrote a uint16 volume, since process start
+  static void image_storage_counters(long long out[2]);
   // calls that streamed views, streamed view updates, bytes streamed (host -> device), since process start
   static void stream_counters(long long out[3]);
   static void count_streamed_call();
@@ -362,7 +382,8 @@ class Engine {
   // stack in host memory (rows must be contiguous) is placed by the copy of its window - H2D, or H2D into the embedding
   // scratch and a strided device copy into margins that were cleared when the volume was allocated; a stack in device
   // memory is read by the ingest pass where it lies, and one value for every voxel (strides 0) is written by it; a
-  // uint16 stack in host memory crosses PCIe as uint16 and is then converted and embedded by the same pass.
+  // uint16 stack in host memory crosses PCIe as uint16 and is then converted and embedded by the same pass - or, where
+  // the view's image is held as uint16 (plan_image_types / set_image_storage), placed or embedded unconverted.
   void set_view(int v, const StackRef& image, const StackRef& weights, const float* kernel1, const int* k1dims,
                 const float* kernel2, const int* k2dims);
   void set_psi(const StackRef& psi);
@@ -514,10 +535,21 @@ class Engine {
   // one stack into volume `dst` on stream s; `scratch`: where a host stack that needs converting or embedding
   // lands first; dst_dirty: dst has been used as such a scratch since its padding was cleared.  Returns the bytes
   // that crossed PCIe.
-  long long ingest_stack(float* dst, const StackRef& st, float* scratch, bool dst_dirty, be::stream_t s);
-  // image and weights of one view; without an embedding scratch a uint16 image lands in the weights volume first
+  // dst_u16: dst is a uint16 volume and st a uint16 stack, kept unconverted - placed by the copy itself where a
+  // float32 stack would be, by the uint16 -> uint16 ingest pass otherwise
+  long long ingest_stack(float* dst, const StackRef& st, float* scratch, bool dst_dirty, be::stream_t s,
+                         bool dst_u16 = false);
+  // image and weights of one view; without an embedding scratch a uint16 image that is converted lands in the weights
+  // volume first
   long long ingest_pair(float* image_dst, float* weights_dst, const StackRef& image, const StackRef& weights,
-                        be::stream_t s);
+                        be::stream_t s, bool image_u16);
+  std::vector<char> want_u16_;  // per view: its image is (to be) held as uint16
+  int image_storage_ = 0;
+  size_t image_bytes(bool u16) const { return u16 ? plan_->main_bytes() / 2 : plan_->main_bytes(); }
+  void alloc_ring_images(bool u16);
+  // the DIVIDE epilogue of view slot s: MVN_EPI_DIVIDE, or MVN_EPI_DIVIDE_U16 on a uint16 volume (counted)
+  void divide_epilogue(EpilogueParams& e, const ViewSlot& s) const;
+  int u16_views() const;
   // Both kernels of slot s on stream st, each unless the slot holds it already (psf_resident): device copy of the
   // kernel, then prepare_psf.  Blocking (set_view): the work volume is the scratch and each copy is freed once the
   // stream has drained.  Staging (stage_view): the staging scratch, and the copies are parked in stage_scratch_.
@@ -624,6 +656,7 @@ class Engine {
   // out-of-core views (set_residency): per view its position in the sweep's streamed order, or -1 (resident)
   struct RingSlot {
     float* image = nullptr;
+    bool image_u16 = false;  // the image is a uint16 volume (every streamed view of the call is held as uint16)
     float* weights = nullptr;
     be::event_t filled = nullptr;  // upload stream: the pair has landed
     be::event_t freed = nullptr;   // compute stream: the last pass that reads the pair has been enqueued before it

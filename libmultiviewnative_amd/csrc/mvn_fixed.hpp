@@ -1125,6 +1125,8 @@ struct FxRowsRegs {
   // epilogue operands of the elements this thread finishes in the last inverse stage
   cfloat ea[FxRowsCfg<H>::IT0][FxRowsCfg<H>::R0];
   cfloat eb[FxRowsCfg<H>::IT0][FxRowsCfg<H>::R0];
+  // MVN_EPI_DIVIDE_U16: the view's pairs instead of ea, one 4-byte word each
+  unsigned eu[FxRowsCfg<H>::IT0][FxRowsCfg<H>::R0];
 };
 // the register set of the MVN_EPI_UPDATE_STATS forms: the lane's accumulators as well
 template <int H>
@@ -1339,6 +1341,15 @@ MVN_HD cfloat fx_epilogue_pair_value(const EpilogueParams& e, long i, cfloat z, 
   return mvn_epilogue_pair_value(EPI, e, i, z, a, b);
 }
 
+// the first epilogue operand at its use: a uint16 pair is widened here, not where it was fetched
+template <int EPI>
+MVN_HD cfloat fx_operand(cfloat a, unsigned u) {
+  if constexpr (EPI == MVN_EPI_DIVIDE_U16)
+    return mvn_u16_pair_widen(u);
+  else
+    return a;
+}
+
 // c2r phase 0: spectral rows -> LDS (position order both sides), plus the epilogue operands of the
 // elements this thread will finish in the last inverse stage, fetched a whole transform ahead
 template <int H, int EPI, bool LINES = false>
@@ -1375,7 +1386,17 @@ MVN_HD void fx_c2r_load(const RowsParams& P, long r0, cfloat* buf, cfloat* tws, 
   }
   constexpr int mode = EPI;
   const float* pa = mode == MVN_EPI_DIVIDE ? P.epi.view : P.epi.psi;
-  if (mode != MVN_EPI_STORE) {
+  if constexpr (mode == MVN_EPI_DIVIDE_U16) {
+    // the same pairs from a uint16 volume: one 4-byte word each, widened at its use (fx_operand)
+#pragma unroll
+    for (int it = 0; it < C::IT0; ++it) {
+      const int w = tid + it * NT;
+      if (!C::EXACT && w >= C::M0 * C::T) break;
+      const unsigned short* src = P.epi.view16 + (r0 + w / C::M0) * P.RP + 2 * (w % C::M0);
+#pragma unroll
+      for (int jo = 0; jo < C::R0; ++jo) r.eu[it][jo] = mvn_u16_pair_fetch(src + 2 * jo * C::M0);
+    }
+  } else if (mode != MVN_EPI_STORE) {
 #pragma unroll
     for (int it = 0; it < C::IT0; ++it) {
       const int w = tid + it * NT;
@@ -1491,7 +1512,8 @@ MVN_HD void fx_c2r_stage0_epilogue(const RowsParams& P, long r0, cfloat* buf, co
 #pragma unroll
       for (int jo = 0; jo < R; ++jo)
         if constexpr (EPI != MVN_EPI_UPDATE_STATS)
-          a[jo] = fx_epilogue_pair_value<EPI>(P.epi, i0 + 2 * jo * M, a[jo], r.ea[it][jo], r.eb[it][jo]);
+          a[jo] = fx_epilogue_pair_value<mvn_epi_math(EPI)>(P.epi, i0 + 2 * jo * M, a[jo], fx_operand<EPI>(r.ea[it][jo], r.eu[it][jo]),
+                                                            r.eb[it][jo]);
       dftR<R, -1>(a);
 #pragma unroll
       for (int k = 1; k < R; ++k) a[k] = cmul(a[k], tw[k]);
@@ -1500,7 +1522,8 @@ MVN_HD void fx_c2r_stage0_epilogue(const RowsParams& P, long r0, cfloat* buf, co
     } else if constexpr (EPI != MVN_EPI_UPDATE_STATS) {
 #pragma unroll
       for (int jo = 0; jo < R; ++jo)
-        mvn_epilogue_pair_t<EPI>(P.epi, P.out_real, i0 + 2 * jo * M, a[jo], r.ea[it][jo], r.eb[it][jo]);
+        mvn_epilogue_pair_t<mvn_epi_math(EPI)>(P.epi, P.out_real, i0 + 2 * jo * M, a[jo], fx_operand<EPI>(r.ea[it][jo], r.eu[it][jo]),
+                                               r.eb[it][jo]);
     }
   }
 }

@@ -6,7 +6,9 @@
 // as dense float32 in host memory).  A float32 stack in host memory with contiguous rows is placed with a copy of its
 // window (H2D, or H2D into the embedding scratch and a strided device copy), which relies on margins cleared when the
 // volume was allocated; every other stack - uint16, in device memory, or one value for every voxel - takes the ingest
-// pass, which converts, follows strides, reads the caller's device memory and depends on no earlier clear:
+// pass, which converts, follows strides, reads the caller's device memory and depends on no earlier clear.  (In image
+// storage mode 1 a uint16 image keeps its element type: a host stack with contiguous rows into a volume of its own
+// extents is then placed by the copy as well, with 2-byte pitches, and the pass has a uint16 -> uint16 form.)
 //
 //   k_ingest3d<T>   one workgroup per run of MVN_INGEST_ROWS rows of the engine volume (row pitch RP floats, plane
 //                   pitch D1 * RP).  It writes EVERY float of its rows - the converted source inside the embedding
@@ -21,6 +23,12 @@
 //                   extent with RP = 2 mod 4 take 4-byte stores).  The source is read once: the loads carry the
 //                   non-temporal hint, the stores are plain (the first pass of the loop reads them back).
 //                   General form (any positive stride[2], and the broadcast {0, 0, 0}): scalar loads, same stores.
+//                   uint16 destination (k_ingest3d_u16, image storage mode 1, mvn_engine_api.h): the
+//                   same pass without the conversion - the volume is the float32 volume's element grid (row pitch RP
+//                   elements) at 2 bytes per voxel.  A work item owns 8 columns: 16 source bytes as above, ONE 16-byte
+//                   store where RP is a multiple of 8 (every row then starts 16-byte aligned and ends with a whole
+//                   group); other row pitches (RP is even: odd last extents, and even ones such as 20) take 4-byte
+//                   stores of column pairs, the last pair of a row included.
 //   k_extract3d     the window of psi out of the engine volume into a strided float32 destination.
 //
 // The bodies are plain C++ shared with the host emulation (mvn_backend_emu.cpp), like every other pass.
@@ -35,8 +43,8 @@
 #define MVN_INGEST_ROWS 16   // rows of a workgroup: 4 per wave, 32 KB of output at 512 floats per row
 
 struct IngestParams {
-  float* dst;            // the engine volume
-  long RP;               // its row pitch in floats (even)
+  void* dst;             // the engine volume: float32, or uint16 for the uint16 -> uint16 form
+  long RP;               // its row pitch in elements (even)
   int D1;                // rows of a plane
   long rows;             // D0 * D1
   const void* src;       // element (0, 0, 0) of the stack; unused with use_value
@@ -94,9 +102,27 @@ MVN_HD T mvn_ingest_load1(const T* p) {
 
 MVN_HD long mvn_ingest_blocks(long rows) { return (rows + MVN_INGEST_ROWS - 1) / MVN_INGEST_ROWS; }
 
-template <typename T>
+typedef unsigned int mvn_v4u32 __attribute__((vector_size(16)));
+
+// 8 uint16 values of a work item into the uint16 row d at column x0
+MVN_HD void mvn_ingest_store_u16(uint16_t* d, int x0, long RP, const uint16_t* v) {
+  unsigned w[4];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) w[g] = (unsigned)v[2 * g] | ((unsigned)v[2 * g + 1] << 16);
+  if ((RP & 7) == 0) {  // (x0 + 8 <= RP for every work item of the row)
+    mvn_v4u32 o = {w[0], w[1], w[2], w[3]};
+    *(mvn_v4u32*)(void*)(d + x0) = o;
+  } else {
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+      if (x0 + 2 * g < RP) __builtin_memcpy(__builtin_assume_aligned(d + x0 + 2 * g, 4), &w[g], 4);
+  }
+}
+
+template <typename T, typename D = float>
 MVN_HD void mvn_ingest_rows(const IngestParams& p, long block, int tid) {
   constexpr int E = 16 / (int)sizeof(T);  // columns of a work item
+  static_assert(sizeof(D) == 4 || (sizeof(D) == 2 && sizeof(T) == 2), "float32 volumes, or uint16 -> uint16");
   const int wave = mvn_uniform(tid / MVN_INGEST_WAVE), lane = tid % MVN_INGEST_WAVE;
   const long r_end = block * MVN_INGEST_ROWS + MVN_INGEST_ROWS < p.rows ? block * MVN_INGEST_ROWS + MVN_INGEST_ROWS : p.rows;
   const int items = (int)((p.RP + E - 1) / E);
@@ -108,28 +134,30 @@ MVN_HD void mvn_ingest_rows(const IngestParams& p, long block, int tid) {
     const long zi = z - p.o0;
     const int yi = y - p.o1;
     const bool inside = zi >= 0 && zi < p.n0 && yi >= 0 && yi < p.n1;
-    float* d = mvn_uniform(p.dst + r * p.RP);
+    D* d = mvn_uniform((D*)p.dst + r * p.RP);
     const T* s = nullptr;
     if (inside && !p.use_value) s = mvn_uniform((const T*)p.src + zi * p.s0 + (long long)yi * p.s1);
     // the source of column group x0 is s + (x0 - o2): 16-byte aligned for every group of the row, or for none
     const bool vec = s && p.s2 == 1 && (((uintptr_t)s - (uintptr_t)p.o2 * sizeof(T)) & 15) == 0;
     for (int q = lane; q < items; q += MVN_INGEST_WAVE) {
       const int x0 = q * E, xi0 = x0 - p.o2;
-      float v[E];
+      D v[E];
       if (vec && xi0 >= 0 && xi0 + E <= p.n2) {
         const typename IngestVec<T>::type t = mvn_ingest_load16<typename IngestVec<T>::type>(s + xi0);
 #pragma unroll
-        for (int j = 0; j < E; ++j) v[j] = (float)t[j];
+        for (int j = 0; j < E; ++j) v[j] = (D)t[j];
       } else {
 #pragma unroll
         for (int j = 0; j < E; ++j) {
           const int xi = xi0 + j;
-          float f = 0.f;
-          if (inside && xi >= 0 && xi < p.n2) f = p.use_value ? p.value : (float)mvn_ingest_load1(s + (long long)xi * p.s2);
+          D f = 0;
+          if (inside && xi >= 0 && xi < p.n2) f = p.use_value ? (D)p.value : (D)mvn_ingest_load1(s + (long long)xi * p.s2);
           v[j] = f;
         }
       }
-      if (wide_stores) {
+      if constexpr (sizeof(D) == 2) {
+        mvn_ingest_store_u16((uint16_t*)d, x0, p.RP, (const uint16_t*)v);
+      } else if (wide_stores) {
 #pragma unroll
         for (int g = 0; g < E; g += 4)
           if (x0 + g < p.RP) {

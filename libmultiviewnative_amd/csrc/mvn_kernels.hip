@@ -71,6 +71,21 @@ __global__ void __launch_bounds__(512) k_rows_c2r_stats(const RowsParams p) {
     rows_c2r_odd_body<T, true>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
 }
 
+// the divide epilogue on a view held as uint16 (MVN_EPI_DIVIDE_U16), plain and fused
+template <bool EVEN, int T>
+__global__ void __launch_bounds__(512) k_rows_c2r_u16(const RowsParams p) {
+  extern __shared__ __attribute__((aligned(16))) char mvn_smem[];
+  if (EVEN)
+    rows_c2r_even_body<T, false, false, true>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
+  else
+    rows_c2r_odd_body<T, false, true>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
+}
+template <int T>
+__global__ void __launch_bounds__(512) k_rows_c2r_r2c_u16(const RowsParams p) {
+  extern __shared__ __attribute__((aligned(16))) char mvn_smem[];
+  rows_c2r_even_body<T, true, false, true>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
+}
+
 // NYQ only tags the launches that work on the Nyquist plane, so that profilers list them apart
 // run-time-radix form of the fused c2r + pointwise + r2c pass (any even d2)
 template <int T>
@@ -244,6 +259,10 @@ __global__ void k_copy3d(float* __restrict__ dst, long drow, long dplane, const 
 template <typename T>
 __global__ __launch_bounds__(MVN_INGEST_WG) void k_ingest3d(const IngestParams p) {
   mvn_ingest_rows<T>(p, (long)blockIdx.x, (int)threadIdx.x);
+}
+// a uint16 stack into a uint16 volume, unconverted (image storage mode 1)
+__global__ __launch_bounds__(MVN_INGEST_WG) void k_ingest3d_u16(const IngestParams p) {
+  mvn_ingest_rows<uint16_t, uint16_t>(p, (long)blockIdx.x, (int)threadIdx.x);
 }
 
 __global__ __launch_bounds__(MVN_INGEST_WG) void k_extract3d(const ExtractParams p) {
@@ -700,6 +719,7 @@ void launch_rows_c2r(const RowsParams& p, bool even, long nblocks, int nthreads,
     check_lines(p, nblocks);
     switch (p.epi.mode) {
       case MVN_EPI_DIVIDE: return launch_pass(kx_rows_c2r<256, MVN_EPI_DIVIDE, true>, p, nblocks, nthreads, lds_bytes, s);
+      case MVN_EPI_DIVIDE_U16: return launch_pass(kx_rows_c2r<256, MVN_EPI_DIVIDE_U16, true>, p, nblocks, nthreads, lds_bytes, s);
       case MVN_EPI_UPDATE: return launch_pass(kx_rows_c2r<256, MVN_EPI_UPDATE, true>, p, nblocks, nthreads, lds_bytes, s);
       case MVN_EPI_UPDATE_STATS: return launch_pass(kx_rows_c2r<256, MVN_EPI_UPDATE_STATS, true>, p, nblocks, nthreads, lds_bytes, s);
       case MVN_EPI_DELTA: return launch_pass(kx_rows_c2r<256, MVN_EPI_DELTA, true>, p, nblocks, nthreads, lds_bytes, s);
@@ -712,6 +732,7 @@ void launch_rows_c2r(const RowsParams& p, bool even, long nblocks, int nthreads,
     if (wave_rows_enabled(p, p.epi.mode == MVN_EPI_DELTA ? 16 : 2)) {
       switch (p.epi.mode) {
         case MVN_EPI_DIVIDE: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_DIVIDE>, p, s);
+        case MVN_EPI_DIVIDE_U16: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_DIVIDE_U16>, p, s);
         case MVN_EPI_UPDATE: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_UPDATE>, p, s);
         case MVN_EPI_UPDATE_STATS: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_UPDATE_STATS>, p, s);
         case MVN_EPI_DELTA: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_DELTA>, p, s);
@@ -723,6 +744,7 @@ void launch_rows_c2r(const RowsParams& p, bool even, long nblocks, int nthreads,
   case H:                                                                                     \
     switch (p.epi.mode) {                                                                     \
       case MVN_EPI_DIVIDE: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_DIVIDE>, p, nblocks, nthreads, lds_bytes, s); break; \
+      case MVN_EPI_DIVIDE_U16: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_DIVIDE_U16>, p, nblocks, nthreads, lds_bytes, s); break; \
       case MVN_EPI_UPDATE: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_UPDATE>, p, nblocks, nthreads, lds_bytes, s); break; \
       case MVN_EPI_UPDATE_STATS: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_UPDATE_STATS>, p, nblocks, nthreads, lds_bytes, s); break; \
       case MVN_EPI_DELTA: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_DELTA>, p, nblocks, nthreads, lds_bytes, s); break;   \
@@ -743,6 +765,14 @@ void launch_rows_c2r(const RowsParams& p, bool even, long nblocks, int nthreads,
     }
     return;
   }
+  if (p.epi.mode == MVN_EPI_DIVIDE_U16) {
+    if (even) {
+      MVN_DISPATCH_T(p.T, (k_rows_c2r_u16<true, TT>));
+    } else {
+      MVN_DISPATCH_T(p.T, (k_rows_c2r_u16<false, TT>));
+    }
+    return;
+  }
   if (even) {
     MVN_DISPATCH_T(p.T, (k_rows_c2r<true, TT>));
   } else {
@@ -757,6 +787,7 @@ void launch_rows_c2r_r2c(const RowsParams& p, long nblocks, int nthreads, size_t
     check_lines(p, nblocks);
     switch (p.epi.mode) {
       case MVN_EPI_DIVIDE: return launch_pass(kx_rows_c2r_r2c<256, MVN_EPI_DIVIDE, true>, p, nblocks, nthreads, lds_bytes, s);
+      case MVN_EPI_DIVIDE_U16: return launch_pass(kx_rows_c2r_r2c<256, MVN_EPI_DIVIDE_U16, true>, p, nblocks, nthreads, lds_bytes, s);
       case MVN_EPI_UPDATE: return launch_pass(kx_rows_c2r_r2c<256, MVN_EPI_UPDATE, true>, p, nblocks, nthreads, lds_bytes, s);
       case MVN_EPI_UPDATE_STATS: return launch_pass(kx_rows_c2r_r2c<256, MVN_EPI_UPDATE_STATS, true>, p, nblocks, nthreads, lds_bytes, s);
       default: return launch_pass(kx_rows_c2r_r2c<256, MVN_EPI_STORE, true>, p, nblocks, nthreads, lds_bytes, s);
@@ -768,14 +799,19 @@ void launch_rows_c2r_r2c(const RowsParams& p, long nblocks, int nthreads, size_t
       MVN_DISPATCH_T(p.T, (k_rows_c2r_r2c_stats<TT>));
       return;
     }
+    if (p.epi.mode == MVN_EPI_DIVIDE_U16) {
+      MVN_DISPATCH_T(p.T, (k_rows_c2r_r2c_u16<TT>));
+      return;
+    }
     MVN_DISPATCH_T(p.T, (k_rows_c2r_r2c<TT>));
     return;
   }
   check_aligned16(p.in_cplx, "input");
   check_aligned16(p.out_cplx, "output");
-  if (wave_rows_enabled(p, p.epi.mode == MVN_EPI_DIVIDE ? 4 : 8)) {
+  if (wave_rows_enabled(p, mvn_epi_math(p.epi.mode) == MVN_EPI_DIVIDE ? 4 : 8)) {
     switch (p.epi.mode) {
       case MVN_EPI_DIVIDE: return launch_wave_rows(kw_rows<MVN_WR_C2R_R2C, MVN_EPI_DIVIDE>, p, s);
+      case MVN_EPI_DIVIDE_U16: return launch_wave_rows(kw_rows<MVN_WR_C2R_R2C, MVN_EPI_DIVIDE_U16>, p, s);
       case MVN_EPI_UPDATE: return launch_wave_rows(kw_rows<MVN_WR_C2R_R2C, MVN_EPI_UPDATE>, p, s, 32);
       case MVN_EPI_UPDATE_STATS: return launch_wave_rows(kw_rows<MVN_WR_C2R_R2C, MVN_EPI_UPDATE_STATS>, p, s, 32);
       default: return launch_wave_rows(kw_rows<MVN_WR_C2R_R2C, MVN_EPI_STORE>, p, s);
@@ -786,6 +822,7 @@ void launch_rows_c2r_r2c(const RowsParams& p, long nblocks, int nthreads, size_t
   case H:                                                                                     \
     switch (p.epi.mode) {                                                                     \
       case MVN_EPI_DIVIDE: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r_r2c<H, MVN_EPI_DIVIDE>, p, nblocks, nthreads, lds_bytes, s); break; \
+      case MVN_EPI_DIVIDE_U16: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r_r2c<H, MVN_EPI_DIVIDE_U16>, p, nblocks, nthreads, lds_bytes, s); break; \
       case MVN_EPI_UPDATE: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r_r2c<H, MVN_EPI_UPDATE>, p, nblocks, nthreads, lds_bytes, s); break; \
       case MVN_EPI_UPDATE_STATS: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r_r2c<H, MVN_EPI_UPDATE_STATS>, p, nblocks, nthreads, lds_bytes, s); break; \
       default: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r_r2c<H, MVN_EPI_STORE>, p, nblocks, nthreads, lds_bytes, s); break;             \
@@ -947,10 +984,13 @@ void launch_copy3d(float* dst, long drow, long dplane, const float* src, long sr
   HIP_CHECK(hipGetLastError());
 }
 
-void launch_ingest3d(const IngestParams& p, bool u16, stream_t s) {
+void launch_ingest3d(const IngestParams& p, bool u16, stream_t s, bool dst_u16) {
   const long nblocks = mvn_ingest_blocks(p.rows);
   if (nblocks < 1 || nblocks > 0x7fffffffL) throw std::invalid_argument("mvn: grid size out of range");
-  if (u16)
+  if (dst_u16 && (!u16 || p.use_value)) throw std::invalid_argument("mvn: a uint16 volume takes a uint16 stack");
+  if (dst_u16)
+    hipLaunchKernelGGL(k_ingest3d_u16, dim3((unsigned)nblocks), dim3(MVN_INGEST_WG), 0, hs(s), p);
+  else if (u16)
     hipLaunchKernelGGL(k_ingest3d<uint16_t>, dim3((unsigned)nblocks), dim3(MVN_INGEST_WG), 0, hs(s), p);
   else
     hipLaunchKernelGGL(k_ingest3d<float>, dim3((unsigned)nblocks), dim3(MVN_INGEST_WG), 0, hs(s), p);

@@ -32,18 +32,24 @@ enum MvnEpilogue {
   MVN_EPI_DIVIDE = 1,  // out = view * float(1.0 / (x*scale))
   MVN_EPI_UPDATE = 2,  // psi = w * (next(psi, x*scale) - psi) + psi
   MVN_EPI_DELTA = 3,   // delta (+)= w * (next(psi, x*scale) - psi)     (simultaneous mode)
-  MVN_EPI_UPDATE_STATS = 4  // UPDATE, plus the convergence statistics of the window (MvnStatsParams)
+  MVN_EPI_UPDATE_STATS = 4,  // UPDATE, plus the convergence statistics of the window (MvnStatsParams)
+  MVN_EPI_DIVIDE_U16 = 5     // DIVIDE with the view held as uint16 (EpilogueParams::view16): same quotient, bit for bit
 };
 
 // the epilogues that read psi and the weights
 constexpr bool mvn_epi_reads_psi(int epi) {
   return epi == MVN_EPI_UPDATE || epi == MVN_EPI_DELTA || epi == MVN_EPI_UPDATE_STATS;
 }
+// the mode whose arithmetic an epilogue runs once its operands are floats
+constexpr int mvn_epi_math(int epi) { return epi == MVN_EPI_DIVIDE_U16 ? (int)MVN_EPI_DIVIDE : epi; }
 
 struct EpilogueParams {
   int mode;
   float scale;          // applied to the raw inverse-transform output first
-  const float* view;    // DIVIDE
+  union {
+    const float* view;            // DIVIDE
+    const unsigned short* view16; // DIVIDE_U16: the same element grid (row pitch RP elements) at 2 bytes per voxel
+  };
   float* psi;           // UPDATE (in/out), DELTA (in)
   const float* weights; // UPDATE / DELTA
   float* delta;         // DELTA
@@ -76,6 +82,18 @@ MVN_HD void mvn_arm_poison(EpilogueParams& e) {
 
 // quotient with the optional guard above
 MVN_HD float mvn_quotient_g(float view, float blurred, int guard);
+
+// ---- uint16 views (MVN_EPI_DIVIDE_U16) -------------------------------------------------------------------------
+// The pair (i, i + 1), i even, of a uint16 volume is ONE aligned 4-byte word (RP is even: rows start 4-byte
+// aligned).  It is requested where the float32 form requests its 8-byte pair and waits in one register;
+// mvn_u16_pair_widen turns it into the two floats at the use.  uint16 -> float is exact, so the quotient sees the
+// float a converted volume would have held.
+MVN_HD unsigned mvn_u16_pair_fetch(const unsigned short* p) {
+  unsigned w;
+  __builtin_memcpy(&w, __builtin_assume_aligned(p, 4), sizeof(w));
+  return w;
+}
+MVN_HD cfloat mvn_u16_pair_widen(unsigned w) { return cmake((float)(w & 0xffffu), (float)(w >> 16)); }
 
 // inc/cpu_kernels.h:22-25: TransferT temp = 1. / out; out = in * temp, i.e. a DOUBLE divide
 // rounded to float.  Double carries 53 >= 2*24+2 bits, so that double rounding is innocuous and
@@ -185,6 +203,13 @@ MVN_HD void mvn_epilogue_fetch_batch(const EpilogueParams& e, const long* idx, c
 #pragma unroll
     for (int u = 0; u < U; ++u) b[u] = *reinterpret_cast<const cfloat*>(e.weights + idx[u]);
   }
+}
+
+// the same for a view held as uint16 (MVN_EPI_DIVIDE_U16): one word per pair
+template <int U>
+MVN_HD void mvn_epilogue_fetch_batch_u16(const EpilogueParams& e, const long* idx, unsigned* a) {
+#pragma unroll
+  for (int u = 0; u < U; ++u) a[u] = mvn_u16_pair_fetch(e.view16 + idx[u]);
 }
 
 MVN_HD void mvn_epilogue_pair(const EpilogueParams& e, float* out, long i, cfloat z, cfloat a,
@@ -537,7 +562,8 @@ MVN_HD void rows_r2c_even_body(const RowsParams& P, long tile, int tid, int nthr
 // KEEP = true is the fused pass: the epilogue results stay in LDS and run straight through the
 // forward half (rows_r2c_even_tail), writing the half-spectrum of the result over the input.
 // STATS = true: the UPDATE epilogue with the convergence statistics (P.epi.mode is then MVN_EPI_UPDATE_STATS).
-template <int T, bool KEEP = false, bool STATS = false>
+// U16 = true: the DIVIDE epilogue on a uint16 view (P.epi.mode is then MVN_EPI_DIVIDE_U16).
+template <int T, bool KEEP = false, bool STATS = false, bool U16 = false>
 MVN_HD void rows_c2r_even_body(const RowsParams& P, long tile, int tid, int nthreads, cfloat* lds) {
   // (a copy of the epilogue's few fields, not of P: the run-time radix tables in P are indexed dynamically and a
   // private copy of the whole struct would live in scratch memory)
@@ -550,6 +576,7 @@ MVN_HD void rows_c2r_even_body(const RowsParams& P, long tile, int tid, int nthr
     mvn_stat_init(acc);
     rin = mvn_stat_tile_rows<T>(P, tile * T);
   }
+  if constexpr (U16) epi.mode = MVN_EPI_DIVIDE;  // the arithmetic of DIVIDE, on operands widened at the use
   constexpr int U = MVN_ROWS_U;
   const int h = P.h, TP = P.TP;
   const long r0 = tile * T;
@@ -559,10 +586,12 @@ MVN_HD void rows_c2r_even_body(const RowsParams& P, long tile, int tid, int nthr
   cfloat* alt = lds + P.lds_alt;
   const cfloat* tw = lds_stage_twiddles(lds + P.lds_tw, P.ax, tid, nthreads);
   cfloat ea[U], eb[U];  // epilogue operands, fetched a whole transform ahead when `single`
+  unsigned eu[U];       // (U16: the view's pairs, one word each)
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     ea[u] = cmake(0.f, 0.f);
     eb[u] = cmake(0.f, 0.f);
+    eu[u] = 0u;
   }
   const long last_row = P.rows - 1;
   for (int w0 = tid; w0 < total; w0 += U * nthreads) {
@@ -579,7 +608,12 @@ MVN_HD void rows_c2r_even_body(const RowsParams& P, long tile, int tid, int nthr
       v[u] = P.in_cplx[row * P.C + k];
       idx[u] = row * P.RP + 2 * k;
     }
-    if (single) mvn_epilogue_fetch_batch<U>(epi, idx, ea, eb);
+    if (single) {
+      if constexpr (U16)
+        mvn_epilogue_fetch_batch_u16<U>(epi, idx, eu);
+      else
+        mvn_epilogue_fetch_batch<U>(epi, idx, ea, eb);
+    }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int w = w0 + u * nthreads;
@@ -627,7 +661,10 @@ MVN_HD void rows_c2r_even_body(const RowsParams& P, long tile, int tid, int nthr
         row = row < last_row ? row : last_row;
         idx[u] = row * P.RP + 2 * j;
       }
-      mvn_epilogue_fetch_batch<U>(epi, idx, ea, eb);
+      if constexpr (U16)
+        mvn_epilogue_fetch_batch_u16<U>(epi, idx, eu);
+      else
+        mvn_epilogue_fetch_batch<U>(epi, idx, ea, eb);
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -635,6 +672,7 @@ MVN_HD void rows_c2r_even_body(const RowsParams& P, long tile, int tid, int nthr
       const int rho = (int)mvn_fastdiv((unsigned)w, (unsigned)h, P.hmul), j = w - rho * h;
       const long row = r0 + rho;
       if (w < total && row <= last_row) {
+        if constexpr (U16) ea[u] = mvn_u16_pair_widen(eu[u]);
         if constexpr (STATS) {
           const cfloat y = mvn_update_pair_stats(epi, row * P.RP + 2 * j, buf[j * TP + rho], ea[u], eb[u], acc,
                                                  P.st, (rin >> rho) & 1u, 2 * j);
@@ -678,7 +716,7 @@ MVN_HD void rows_r2c_odd_body(const RowsParams& P, long tile, int tid, int nthre
   }
 }
 
-template <int T, bool STATS = false>
+template <int T, bool STATS = false, bool U16 = false>
 MVN_HD void rows_c2r_odd_body(const RowsParams& P, long tile, int tid, int nthreads, cfloat* lds) {
   // (a copy of the epilogue's few fields, not of P: the run-time radix tables in P are indexed dynamically and a
   // private copy of the whole struct would live in scratch memory)
@@ -718,6 +756,13 @@ MVN_HD void rows_c2r_odd_body(const RowsParams& P, long tile, int tid, int nthre
       if (row < P.rows)
         mvn_update_stats(epi, row * P.RP + j, buf[j * TP + rho].x, acc,
                          ((rin >> rho) & 1u) && (unsigned)(j - P.st.o2) < P.st.n2);
+    } else if constexpr (U16) {  // (rows of an odd extent: one element at a time, as mvn_epilogue)
+      MVN_FP_EXACT
+      if (row < P.rows) {
+        const long i = row * P.RP + j;
+        const float view = (float)epi.view16[i];
+        P.out_real[i] = mvn_quotient_g(view, buf[j * TP + rho].x * epi.scale, epi.guard_zero_view);
+      }
     } else if (row < P.rows) {
       mvn_epilogue(epi, P.out_real, row * P.RP + j, buf[j * TP + rho].x);
     }

@@ -75,6 +75,7 @@ struct WrRegs {
   cfloat z[8];   // the lane's 8 bins of its row
   cfloat ea[8];  // epilogue operands of the 16 reals the lane finishes in phase C
   cfloat eb[8];
+  unsigned eu[8];  // MVN_EPI_DIVIDE_U16: the view's pairs instead of ea, one 4-byte word each
   cfloat pw[4];  // exp(-2 pi i k / d2) of the lane's (k, H - k) pairs
   qfloat nx[4];  // the lane's two groups of the NEXT row of its half-wave, requested one row ahead
   MvnStatAcc st; // MVN_EPI_UPDATE_STATS
@@ -203,7 +204,7 @@ MVN_HD void wr_fetch_row(const RowsParams& P, long row, WrRegs& r, int tid) {
 // the start of phase A of the row itself and consume it at once)
 template <int EPI>
 constexpr bool wr_prefetch() {
-  return EPI == MVN_EPI_DIVIDE || EPI == MVN_EPI_STORE;
+  return EPI == MVN_EPI_DIVIDE || EPI == MVN_EPI_DIVIDE_U16 || EPI == MVN_EPI_STORE;
 }
 
 // The operands of the pointwise step (view, or psi and weights) of a row are requested one SWEEP
@@ -216,7 +217,11 @@ template <int EPI>
 MVN_HD void wr_fetch_epi(const RowsParams& P, long row, WrRegs& r, int tid) {
   if (row >= P.rows) return;
   const int t = tid & 31;  // the lane finishes reals 2 (t + 32 jo), 2 (t + 32 jo) + 1 in phase C
-  if (EPI != MVN_EPI_STORE) {
+  if constexpr (EPI == MVN_EPI_DIVIDE_U16) {  // a uint16 view: one 4-byte word per pair, widened at its use in phase C
+    const unsigned short* pa = P.epi.view16 + row * P.RP + 2 * t;
+#pragma unroll
+    for (int jo = 0; jo < 8; ++jo) r.eu[jo] = mvn_u16_pair_fetch(pa + 64 * jo);
+  } else if (EPI != MVN_EPI_STORE) {
     const float* pa = (EPI == MVN_EPI_DIVIDE ? P.epi.view : P.epi.psi) + row * P.RP + 2 * t;
 #pragma unroll
     for (int jo = 0; jo < 8; ++jo) r.ea[jo] = *reinterpret_cast<const cfloat*>(pa + 64 * jo);
@@ -332,7 +337,7 @@ MVN_HD void wr_phase_c(const RowsParams& P, long row, long next_row, cfloat* row
         if constexpr (EPI == MVN_EPI_UPDATE_STATS)
           mvn_update_pair_stats(P.epi, i0 + 64 * jo, a[jo], r.ea[jo], r.eb[jo], r.st, P.st, row_in, 2 * t + 64 * jo);
         else
-          mvn_epilogue_pair_t<EPI>(P.epi, P.out_real, i0 + 64 * jo, a[jo], r.ea[jo], r.eb[jo]);
+          mvn_epilogue_pair_t<mvn_epi_math(EPI)>(P.epi, P.out_real, i0 + 64 * jo, a[jo], fx_operand<EPI>(r.ea[jo], r.eu[jo]), r.eb[jo]);
         if (jo & 1) MVN_SCHED_FENCE();  // four values at a time: the f64 chains of all 16 would not fit
       }
       wr_fetch_epi<EPI>(P, next_row, r, tid);
@@ -344,7 +349,7 @@ MVN_HD void wr_phase_c(const RowsParams& P, long row, long next_row, cfloat* row
         a[jo] = mvn_update_pair_stats(P.epi, i0 + 64 * jo, a[jo], r.ea[jo], r.eb[jo], r.st, P.st, row_in,
                                       2 * t + 64 * jo);
       else
-        a[jo] = fx_epilogue_pair_value<EPI>(P.epi, i0 + 64 * jo, a[jo], r.ea[jo], r.eb[jo]);
+        a[jo] = fx_epilogue_pair_value<mvn_epi_math(EPI)>(P.epi, i0 + 64 * jo, a[jo], fx_operand<EPI>(r.ea[jo], r.eu[jo]), r.eb[jo]);
       if (jo & 1) MVN_SCHED_FENCE();
     }
     wr_fetch_epi<EPI>(P, next_row, r, tid);

@@ -46,6 +46,7 @@ ENGINE_ABI_SYMBOLS = [
     "mvn_deconvolve_described", "mvn_engine_set_view_described", "mvn_engine_set_psi_described",
     "mvn_engine_get_psi_described",
     "mvn_set_acceleration", "mvn_get_acceleration", "mvn_last_acceleration", "mvn_engine_iterate_accelerated",
+    "mvn_set_image_storage", "mvn_get_image_storage", "mvn_deconvolve_memory_described", "mvn_image_storage_counters",
 ]
 
 
@@ -115,6 +116,11 @@ class Binding:
         l.mvn_engine_set_view_described.argtypes = [C.c_void_p, C.c_int, C.c_void_p, sd, C.c_void_p, sd, c_float_p, i3,
                                                     c_float_p, i3, C.c_void_p]
         l.mvn_engine_set_psi_described.argtypes = [C.c_void_p, C.c_void_p, sd, C.c_void_p]
+        l.mvn_set_image_storage.argtypes = [C.c_int]
+        l.mvn_get_image_storage.argtypes = [C.POINTER(C.c_int)]
+        l.mvn_deconvolve_memory_described.argtypes = [Workspace, C.POINTER(CallDesc), C.c_int, C.c_int,
+                                                      C.POINTER(C.c_size_t)]
+        l.mvn_image_storage_counters.argtypes = [C.POINTER(C.c_longlong)]
         l.mvn_engine_get_psi_described.argtypes = [C.c_void_p, C.c_void_p, sd]
         for n in ("inplace_gpu_convolution", "convolution3DfftCUDAInPlace"):
             getattr(l, n).argtypes = [c_float_p, c_int_p, c_float_p, c_int_p, C.c_int]
@@ -246,6 +252,30 @@ class Binding:
         """(calls that streamed views, streamed view updates, bytes streamed) since process start."""
         out = (C.c_longlong * 3)()
         self.check(self.l.mvn_stream_counters(out))
+        return tuple(int(x) for x in out)
+
+    def set_image_storage(self, mode):
+        """How uint16 image stacks of described calls are held on the device: 0 (default) converted to float32 on
+        entry, 1 kept as uint16 (mvn_engine_api.h).  Results are the same bits."""
+        self.check(self.l.mvn_set_image_storage(int(mode)))
+
+    def get_image_storage(self):
+        out = C.c_int(0)
+        self.check(self.l.mvn_get_image_storage(C.byref(out)))
+        return out.value
+
+    def deconvolve_memory_described(self, call, streamed_views=0, device=0):
+        """deconvolve_memory for a prepared described call (describe_call), or for a WorkspaceHolder (no descriptors:
+        exactly deconvolve_memory): uint16 images are priced at 2 bytes per voxel when the storage mode keeps them."""
+        out = C.c_size_t(0)
+        desc = C.byref(call.desc) if hasattr(call, "desc") else None
+        self.check(self.l.mvn_deconvolve_memory_described(call.ws, desc, device, streamed_views, C.byref(out)))
+        return out.value
+
+    def image_storage_counters(self):
+        """(divide passes launched on a uint16 image, ingest passes that wrote a uint16 volume) since process start."""
+        out = (C.c_longlong * 2)()
+        self.check(self.l.mvn_image_storage_counters(out))
         return tuple(int(x) for x in out)
 
     def set_convergence(self, tolerance):
