@@ -174,6 +174,38 @@ MVN_API int mvn_get_acceleration(int* mode);
  * k - 1 < min(capacity, rows); the entry of the last sweep run is 0 (nothing followed it).  Returns the number of
  * rows available (0 when acceleration was off), < 0 on error. */
 MVN_API int mvn_last_acceleration(double* alphas, int capacity);
+/* The regulariser of the Richardson-Lucy loop.  MVN_REG_TIKHONOV (default; epsilon ignored): workspace.lambda_ > 0
+ * selects the reference's Tikhonov branch, launches and results as without this switch.  MVN_REG_TV: total
+ * variation (Dey et al. 2006) - workspace.lambda_ is the TV weight, the Tikhonov branch is off, and the update of
+ * view v becomes
+ *   psi <- w_v * (next(psi, integral_v * t) - psi) + psi,      t = 1 / (1 - lambda * div(grad psi / |grad psi|_eps))
+ * with `next` the clamp chain of the plain loop and t computed from psi as it stands before this view's update.
+ * All arithmetic is float32 without contraction, every operation correctly rounded, on the engine's volume (the
+ * padded one under "zero" / "zero_exact"), every axis cyclic at the extent of that volume.  For voxel (z, y, x),
+ * u = psi:
+ *   gz = u[z+1,y,x] - u    gy = u[z,y+1,x] - u    gx = u[z,y,x+1] - u
+ *   m  = sqrt(((gx*gx + gy*gy) + gz*gz) + e2)          e2 = (float)epsilon * (float)epsilon
+ *   r  = 1.0f / m          px = gx*r   py = gy*r   pz = gz*r
+ *   dv = ((px - px[x-1]) + (py - py[y-1])) + (pz - pz[z-1])
+ *   t  = 1.0f / (1.0f - (float)lambda * dv)
+ * An extent of 1 along an axis makes that neighbour the voxel itself; the row padding of an odd last extent is never
+ * read as a neighbour and never written.  |p| <= 1, so |dv| <= 6: a call with TV on and lambda_ >= 1/12 is refused
+ * (error, psi untouched), which keeps 1 - lambda dv > 0.5 with no clamp in the kernel.  lambda_ == 0 with TV on is
+ * the plain loop: no TV launch, the plain loop's bits.  A non-finite t reaches `next` as a NaN value and becomes
+ * minValue through the clamp chain.  One more volume (t) is held while TV is on and lambda_ > 0; mvn_deconvolve_memory
+ * and the "auto" planner count it.  Kind 1 needs a finite epsilon > 0; any other kind is an error.  Process-wide,
+ * captured by inplace_gpu_deconvolve, mvn_deconvolve_submit and mvn_deconvolve_described at their start.
+ * Multi-device calls (MVN_DEVICES) with TV on run on one device. */
+enum { MVN_REG_TIKHONOV = 0, MVN_REG_TV = 1 };
+MVN_API int mvn_set_regularization(int kind, double epsilon);
+MVN_API int mvn_get_regularization(int* kind, double* epsilon);
+/* Test and bench utilities of the TV pass.  mvn_tv_factor: t of the dense host volume psi[dims] into the dense host
+ * volume t.  mvn_tv_time: ms[0] = milliseconds per launch of the pass on a resident volume of these extents (`reps`
+ * launches between two stream events), ms[1] = the same for a plain streaming copy of the volume (one read, one
+ * write).  mvn_tv_launch_count: launches of the pass since process start. */
+MVN_API int mvn_tv_factor(int device, const int dims[3], const float* psi, double lambda, double epsilon, float* t);
+MVN_API int mvn_tv_time(int device, const int dims[3], int reps, float* ms);
+MVN_API long mvn_tv_launch_count(void);
 /* A resident engine keeps, per view slot, the PSF spectra of the last call together with host
  * copies of the kernels they were made from; a call (or mvn_engine_set_view) that brings
  * bytewise identical kernels for a slot re-uses the spectra (the reference's
@@ -252,6 +284,9 @@ MVN_API int mvn_engine_iterate_converge(mvn_engine* e, int iterations, double la
  * (a_k, the last one 0).  stats and alphas may be NULL.  Refused by an engine in halo mode (a slab of a group). */
 MVN_API int mvn_engine_iterate_accelerated(mvn_engine* e, int iterations, double lambda, float min_value,
                                            double tolerance, int* iterations_run, double* stats, double* alphas);
+/* the regulariser (mvn_set_regularization) of the mvn_engine_iterate* calls that follow on this engine.  Refused by
+ * an engine in halo mode; mvn_engine_set_halo_hook and mvn_engine_compute_delta* are errors on a TV engine. */
+MVN_API int mvn_engine_set_regularization(mvn_engine* e, int kind, double epsilon);
 /* simultaneous (Jacobi) mode, one step: delta = sum_v w_v (next_v - psi) over this engine's
  * views; the caller all-reduces the delta buffer across ranks, then applies it */
 MVN_API int mvn_engine_compute_delta(mvn_engine* e, double lambda, float min_value);

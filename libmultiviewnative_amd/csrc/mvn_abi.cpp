@@ -151,6 +151,24 @@ static double call_tolerance() { return std::isnan(t_call_tol) ? g_conv_tol.load
 static std::atomic<int> g_accel{0};
 static thread_local int t_call_accel = -1;  // the mode of the call this thread runs; -1 outside a call
 static int call_accel() { return t_call_accel < 0 ? g_accel.load() : t_call_accel; }
+// ---- regularisation (mvn_set_regularization): captured at the start of a call, like the tolerance ----
+struct RegMode {
+  int kind = 0;        // MVN_REG_TIKHONOV / MVN_REG_TV
+  double epsilon = 0.; // MVN_REG_TV only
+};
+static std::mutex g_reg_mu;
+static RegMode g_reg;
+static RegMode current_reg() {
+  std::lock_guard<std::mutex> lk(g_reg_mu);
+  return g_reg;
+}
+static thread_local int t_call_reg_kind = -1;  // the kind of the call this thread runs; -1 outside a call
+static int call_reg_kind() { return t_call_reg_kind < 0 ? current_reg().kind : t_call_reg_kind; }
+// a call with total variation on and a weight the kernel has no clamp for: refused before psi is touched
+static void check_tv_lambda(int kind, double lambda) {
+  if (kind == 1 && !(lambda >= 0. && lambda < 1. / 12.))
+    throw std::invalid_argument("total-variation regularisation needs 0 <= lambda_ < 1/12");
+}
 struct ConvRecord {
   int iterations_run = 0;
   std::vector<double> rows;    // {S, M, P} per sweep run
@@ -172,6 +190,7 @@ static MemoryQuery memory_query(const shape_t& ext, const workspace& input, size
   q.embed_floats = embed_floats;
   q.stats_rows = call_tolerance() >= 0. ? std::max(input.num_iterations_, 1) : 0;
   q.accel_rows = call_accel() ? std::max(input.num_iterations_, 1) : 0;
+  q.tv = call_reg_kind() == 1 && input.lambda_ > 0.;
   q.kernels = call_kernels(input);
   return q;
 }
@@ -662,14 +681,16 @@ static CallStacks workspace_stacks(const imageType* psi, const workspace& input)
   return cs;
 }
 
-// what a call captures at its start: the convergence tolerance and the acceleration mode
+// what a call captures at its start: the convergence tolerance, the acceleration mode and the regulariser
 struct LoopMode {
   double tol = -1.;
   int accel = 0;
+  RegMode reg;
   static LoopMode current() {
     LoopMode m;
     m.tol = g_conv_tol.load();
     m.accel = g_accel.load();
+    m.reg = current_reg();
     return m;
   }
 };
@@ -682,13 +703,15 @@ static void deconvolve_call(const workspace& input, const CallStacks& cs, int de
   conv->iterations_run = 0;
   conv->rows.clear();
   conv->alphas.clear();
-  struct LoopScope {  // (the memory model of this call counts the statistics and acceleration buffers: memory_query)
-    LoopScope(double t, int a) { t_call_tol = t, t_call_accel = a; }
-    ~LoopScope() { t_call_tol = NAN, t_call_accel = -1; }
-  } loop_scope(tol, accel);
+  const bool tv = mode.reg.kind == 1;
+  struct LoopScope {  // (the memory model of this call counts the statistics, acceleration and TV buffers: memory_query)
+    LoopScope(double t, int a, int r) { t_call_tol = t, t_call_accel = a, t_call_reg_kind = r; }
+    ~LoopScope() { t_call_tol = NAN, t_call_accel = -1, t_call_reg_kind = -1; }
+  } loop_scope(tol, accel, mode.reg.kind);
   {
     const int V = input.num_views_;
     if (V == 0 || input.num_iterations_ <= 0) return;  // 0 iterations returns psi unchanged
+    check_tv_lambda(mode.reg.kind, input.lambda_);
     shape_t dims, ext;
     int off[3] = {0, 0, 0};
     if (lane == 0) {  // (the second lane belongs to the block pipeline of mvn_deconvolve_submit)
@@ -705,7 +728,9 @@ static void deconvolve_call(const workspace& input, const CallStacks& cs, int de
         std::printf("[lmvn::trace] MVN_DEVICES: described stacks - one device\n");
       // ... and no acceleration
       if (!devs.empty() && accel && trace_on()) std::printf("[lmvn::trace] MVN_DEVICES: acceleration on - one device\n");
-      if (plain && tol < 0. && !accel) {
+      // ... and no total variation
+      if (!devs.empty() && tv && trace_on()) std::printf("[lmvn::trace] MVN_DEVICES: total variation on - one device\n");
+      if (plain && tol < 0. && !accel && !tv) {
         call_extents(input, pad_mode, -1, &dims, &ext, off);  // (the slabs run on plans of their own extents)
         if (multi_device_call((imageType*)cs.psi.ptr, input, dims, ext, off, pad_mode, devs)) return;
       }
@@ -725,6 +750,7 @@ static void deconvolve_call(const workspace& input, const CallStacks& cs, int de
         cs.keep_u16);
     Engine& eng = *eng_owner;
     eng.begin_call();
+    eng.set_regularization(mode.reg.kind, mode.reg.epsilon);
     eng.set_image_storage(cs.storage);
     eng.plan_image_types(cs.keep_u16);
     // stacks are embedded into / cropped out of the padded volume by the transfers themselves
@@ -1024,6 +1050,130 @@ int mvn_last_acceleration(double* alphas, int capacity) {
     if (n) std::memcpy(alphas, c.alphas.data(), n * sizeof(double));
   });
   return rc < 0 ? rc : rows;
+}
+
+int mvn_set_regularization(int kind, double epsilon) {
+  return guarded("mvn_set_regularization", [&] {
+    if (kind != MVN_REG_TIKHONOV && kind != MVN_REG_TV)
+      throw std::invalid_argument("regularisation kind must be 0 (Tikhonov) or 1 (total variation)");
+    if (kind == MVN_REG_TV && !(epsilon > 0. && std::isfinite(epsilon)))
+      throw std::invalid_argument("total-variation regularisation needs a finite epsilon > 0");
+    std::lock_guard<std::mutex> lk(g_reg_mu);
+    g_reg.kind = kind;
+    g_reg.epsilon = kind == MVN_REG_TV ? epsilon : 0.;
+  });
+}
+
+int mvn_get_regularization(int* kind, double* epsilon) {
+  return guarded("mvn_get_regularization", [&] {
+    if (!kind || !epsilon) throw std::invalid_argument("null argument");
+    const RegMode r = current_reg();
+    *kind = r.kind;
+    *epsilon = r.epsilon;
+  });
+}
+
+long mvn_tv_launch_count(void) { return be::tv_launch_count(); }
+
+// the pass of mvn_tv.hpp on a dense host volume: a test and bench utility
+int mvn_tv_factor(int device, const int dims[3], const float* psi, double lambda, double epsilon, float* t) {
+  return guarded("mvn_tv_factor", [&] {
+    if (!dims || !psi || !t) throw std::invalid_argument("null argument");
+    if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1) throw std::invalid_argument("extents must be positive");
+    if (!(epsilon > 0. && std::isfinite(epsilon))) throw std::invalid_argument("epsilon must be finite and > 0");
+    check_tv_lambda(1, lambda);
+    const int dev = pick_device(device);
+    std::lock_guard<std::mutex> lk(device_mutex(dev));
+    be::set_device(dev);
+    const Layout L(dims[0], dims[1], dims[2]);
+    const size_t bytes = L.real_floats() * sizeof(float), width = (size_t)L.d2 * sizeof(float),
+                 pitch = (size_t)L.RP * sizeof(float);
+    float *du = nullptr, *dt = nullptr;
+    be::stream_t s = nullptr;
+    try {
+      du = (float*)be::dmalloc(bytes);
+      dt = (float*)be::dmalloc(bytes);
+      s = be::stream_create();
+      be::dzero(du, bytes, s);
+      be::h2d_2d(du, pitch, psi, width, width, (size_t)L.rows, s);
+      TvParams p;
+      std::memset(&p, 0, sizeof(p));
+      p.psi = du, p.t = dt;
+      p.d0 = L.d0, p.d1 = L.d1, p.d2 = L.d2, p.RP = L.RP;
+      p.lambda = (float)lambda;
+      p.e2 = (float)epsilon * (float)epsilon;
+      be::launch_tv(p, s);
+      be::d2h_2d(t, width, dt, pitch, width, (size_t)L.rows, s);
+      be::stream_sync(s);
+    } catch (...) {
+      if (s) be::stream_destroy(s);
+      be::dfree(du);
+      be::dfree(dt);
+      throw;
+    }
+    be::stream_destroy(s);
+    be::dfree(du);
+    be::dfree(dt);
+  });
+}
+
+// ms[0]: the pass of mvn_tv.hpp on a resident volume of these extents, per launch over `reps` launches between two
+// stream events; ms[1]: a plain streaming copy of the same volume (launch_copy3d: one read and one write), likewise
+int mvn_tv_time(int device, const int dims[3], int reps, float* ms) {
+  return guarded("mvn_tv_time", [&] {
+    if (!dims || !ms) throw std::invalid_argument("null argument");
+    if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1 || reps < 1) throw std::invalid_argument("extents and reps must be positive");
+    const int dev = pick_device(device);
+    std::lock_guard<std::mutex> lk(device_mutex(dev));
+    be::set_device(dev);
+    const Layout L(dims[0], dims[1], dims[2]);
+    const size_t bytes = L.real_floats() * sizeof(float);
+    float *du = nullptr, *dt = nullptr;
+    be::stream_t s = nullptr;
+    be::event_t a = nullptr, b = nullptr;
+    try {
+      du = (float*)be::dmalloc(bytes);
+      dt = (float*)be::dmalloc(bytes);
+      s = be::stream_create();
+      a = be::event_create();
+      b = be::event_create();
+      // a ramp with a ripple: finite gradients everywhere
+      std::vector<float> h(L.real_floats());
+      for (size_t i = 0; i < h.size(); ++i) h[i] = 1.f + 0.001f * (float)(i % 977) + 0.01f * (float)(i % 13);
+      be::h2d(du, h.data(), bytes, s);
+      TvParams p;
+      std::memset(&p, 0, sizeof(p));
+      p.psi = du, p.t = dt;
+      p.d0 = L.d0, p.d1 = L.d1, p.d2 = L.d2, p.RP = L.RP;
+      p.lambda = 0.005f;
+      p.e2 = 1e-4f;
+      const long plane = (long)L.d1 * L.RP;
+      for (int kind = 0; kind < 2; ++kind) {
+        for (int i = -1; i < reps; ++i) {  // (one launch to warm up)
+          if (i == 0) be::event_record(a, s);
+          if (kind == 0)
+            be::launch_tv(p, s);
+          else
+            be::launch_copy3d(dt, L.RP, plane, du, L.RP, plane, L.d2, L.d1, L.d0, s);
+        }
+        be::event_record(b, s);
+        be::event_sync(b);
+        ms[kind] = be::event_elapsed_ms(a, b) / (float)reps;
+      }
+    } catch (...) {
+      if (a) be::event_destroy(a);
+      if (b) be::event_destroy(b);
+      if (s) be::stream_destroy(s);
+      be::dfree(du);
+      be::dfree(dt);
+      throw;
+    }
+    be::event_destroy(a);
+    be::event_destroy(b);
+    be::stream_destroy(s);
+    be::dfree(du);
+    be::dfree(dt);
+  });
 }
 
 int mvn_set_pad_mode(const char* mode) {
@@ -1907,6 +2057,10 @@ int mvn_engine_iterate_accelerated(mvn_engine* e, int iterations, double lambda,
     if (stats && !rows.empty()) std::memcpy(stats, rows.data(), rows.size() * sizeof(double));
     if (alphas && !al.empty()) std::memcpy(alphas, al.data(), al.size() * sizeof(double));
   });
+}
+
+int mvn_engine_set_regularization(mvn_engine* e, int kind, double epsilon) {
+  MVN_ENGINE_CALL("mvn_engine_set_regularization", E.set_regularization(kind, epsilon));
 }
 
 int mvn_engine_compute_delta(mvn_engine* e, double lambda, float min_value) {

@@ -15,6 +15,7 @@
 #include "mvn_mid_fused.hpp"
 #include "mvn_ingest.hpp"
 #include "mvn_extrapolate.hpp"
+#include "mvn_tv.hpp"
 
 namespace mvn {
 namespace be {
@@ -104,6 +105,10 @@ long split_launch_count();
 void launch_accel_a(const AccelParams& p, stream_t s);
 void launch_accel_reduce(const double* rec, long nrec, float* alpha, stream_t s);
 void launch_accel_b(const AccelParams& p, stream_t s);
+// the total-variation factor of p.psi into p.t (mvn_tv.hpp; the geometry fields of p are filled in here), and the
+// launches of it since process start
+void launch_tv(const TvParams& p, stream_t s);
+long tv_launch_count();
 // launches of the fused middle pass (mvn_mid_fused.hpp) since process start
 long mid_fused_launch_count();
 // `rider` (plain fixed-length passes only): a second pass of the same mode with tiles of ONE line (T = 1, run-time

@@ -188,6 +188,8 @@ static void emu_wave_rows_mode(const RowsParams& p) {
     case MVN_EPI_DIVIDE_U16: emu_wave_rows_run<MODE, MVN_EPI_DIVIDE_U16>(p); break;
     case MVN_EPI_UPDATE: emu_wave_rows_run<MODE, MVN_EPI_UPDATE>(p); break;
     case MVN_EPI_UPDATE_STATS: emu_wave_rows_run<MODE, MVN_EPI_UPDATE_STATS>(p); break;
+    case MVN_EPI_UPDATE_TV: emu_wave_rows_run<MODE, MVN_EPI_UPDATE_TV>(p); break;
+    case MVN_EPI_UPDATE_STATS_TV: emu_wave_rows_run<MODE, MVN_EPI_UPDATE_STATS_TV>(p); break;
     case MVN_EPI_DELTA:
       if (MODE == MVN_WR_C2R) {
         emu_wave_rows_run<MVN_WR_C2R, MVN_EPI_DELTA>(p);
@@ -230,6 +232,8 @@ static void emu_rows_lines(const RowsParams& p, long ntiles, int kind) {
           case MVN_EPI_DIVIDE_U16: fx_rows_run<H, 1, MVN_EPI_DIVIDE_U16, Ctx, true>(p, t, ntiles, l, *ctx); break;
           case MVN_EPI_UPDATE: fx_rows_run<H, 1, MVN_EPI_UPDATE, Ctx, true>(p, t, ntiles, l, *ctx); break;
           case MVN_EPI_UPDATE_STATS: fx_rows_run_stats<H, 1, SCtx, true>(p, t, ntiles, l, *sctx); break;
+          case MVN_EPI_UPDATE_TV: fx_rows_run<H, 1, MVN_EPI_UPDATE_TV, Ctx, true>(p, t, ntiles, l, *ctx); break;
+          case MVN_EPI_UPDATE_STATS_TV: fx_rows_run_stats<H, 1, SCtx, true, MVN_EPI_UPDATE_STATS_TV>(p, t, ntiles, l, *sctx); break;
           case MVN_EPI_DELTA: fx_rows_run<H, 1, MVN_EPI_DELTA, Ctx, true>(p, t, ntiles, l, *ctx); break;
           default: fx_rows_run<H, 1, MVN_EPI_STORE, Ctx, true>(p, t, ntiles, l, *ctx); break;
         }
@@ -239,6 +243,8 @@ static void emu_rows_lines(const RowsParams& p, long ntiles, int kind) {
           case MVN_EPI_DIVIDE_U16: fx_rows_run<H, 2, MVN_EPI_DIVIDE_U16, Ctx, true>(p, t, ntiles, l, *ctx); break;
           case MVN_EPI_UPDATE: fx_rows_run<H, 2, MVN_EPI_UPDATE, Ctx, true>(p, t, ntiles, l, *ctx); break;
           case MVN_EPI_UPDATE_STATS: fx_rows_run_stats<H, 2, SCtx, true>(p, t, ntiles, l, *sctx); break;
+          case MVN_EPI_UPDATE_TV: fx_rows_run<H, 2, MVN_EPI_UPDATE_TV, Ctx, true>(p, t, ntiles, l, *ctx); break;
+          case MVN_EPI_UPDATE_STATS_TV: fx_rows_run_stats<H, 2, SCtx, true, MVN_EPI_UPDATE_STATS_TV>(p, t, ntiles, l, *sctx); break;
           default: fx_rows_run<H, 2, MVN_EPI_STORE, Ctx, true>(p, t, ntiles, l, *ctx); break;
         }
       }
@@ -304,6 +310,8 @@ static void emu_rows_fused(const RowsParams& p, long ntiles) {
         case MVN_EPI_DIVIDE_U16: fx_rows_run<H, 2, MVN_EPI_DIVIDE_U16>(p, t, grid, l, *ctx); break;
         case MVN_EPI_UPDATE: fx_rows_run<H, 2, MVN_EPI_UPDATE>(p, t, grid, l, *ctx); break;
         case MVN_EPI_UPDATE_STATS: fx_rows_run_stats<H, 2, SCtx>(p, t, grid, l, *sctx); break;
+        case MVN_EPI_UPDATE_TV: fx_rows_run<H, 2, MVN_EPI_UPDATE_TV>(p, t, grid, l, *ctx); break;
+        case MVN_EPI_UPDATE_STATS_TV: fx_rows_run_stats<H, 2, SCtx, false, MVN_EPI_UPDATE_STATS_TV>(p, t, grid, l, *sctx); break;
         default: fx_rows_run<H, 2, MVN_EPI_STORE>(p, t, grid, l, *ctx); break;
       }
     }
@@ -324,6 +332,10 @@ void launch_rows_c2r_r2c(const RowsParams& p0, long ntiles, int, size_t lds_byte
         cfloat* l = (cfloat*)lds.data();
         if (p.epi.mode == MVN_EPI_UPDATE_STATS) {
           MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, true, true>(p, t, 0, 1, l)));
+        } else if (p.epi.mode == MVN_EPI_UPDATE_STATS_TV) {
+          MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, true, true, false, true>(p, t, 0, 1, l)));
+        } else if (p.epi.mode == MVN_EPI_UPDATE_TV) {
+          MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, true, false, false, true>(p, t, 0, 1, l)));
         } else if (p.epi.mode == MVN_EPI_DIVIDE_U16) {
           MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, true, false, true>(p, t, 0, 1, l)));
         } else {
@@ -362,6 +374,8 @@ static void emu_rows_fixed(const RowsParams& p, long ntiles, bool r2c) {
           case MVN_EPI_DIVIDE_U16: fx_rows_run<H, 1, MVN_EPI_DIVIDE_U16>(p, t, grid, l, *ctx); break;
           case MVN_EPI_UPDATE: fx_rows_run<H, 1, MVN_EPI_UPDATE>(p, t, grid, l, *ctx); break;
           case MVN_EPI_UPDATE_STATS: fx_rows_run_stats<H, 1, SCtx>(p, t, grid, l, *sctx); break;
+          case MVN_EPI_UPDATE_TV: fx_rows_run<H, 1, MVN_EPI_UPDATE_TV>(p, t, grid, l, *ctx); break;
+          case MVN_EPI_UPDATE_STATS_TV: fx_rows_run_stats<H, 1, SCtx, false, MVN_EPI_UPDATE_STATS_TV>(p, t, grid, l, *sctx); break;
           case MVN_EPI_DELTA: fx_rows_run<H, 1, MVN_EPI_DELTA>(p, t, grid, l, *ctx); break;
           default: fx_rows_run<H, 1, MVN_EPI_STORE>(p, t, grid, l, *ctx); break;
         }
@@ -496,6 +510,18 @@ void launch_rows_c2r(const RowsParams& p0, bool even, long ntiles, int, size_t l
         } else {
           MVN_DISPATCH_T(p.T, (rows_c2r_odd_body<TT, true>(p, t, 0, 1, l)));
         }
+      } else if (p.epi.mode == MVN_EPI_UPDATE_STATS_TV) {
+        if (even) {
+          MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, false, true, false, true>(p, t, 0, 1, l)));
+        } else {
+          MVN_DISPATCH_T(p.T, (rows_c2r_odd_body<TT, true, false, true>(p, t, 0, 1, l)));
+        }
+      } else if (p.epi.mode == MVN_EPI_UPDATE_TV) {
+        if (even) {
+          MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, false, false, false, true>(p, t, 0, 1, l)));
+        } else {
+          MVN_DISPATCH_T(p.T, (rows_c2r_odd_body<TT, false, false, true>(p, t, 0, 1, l)));
+        }
       } else if (p.epi.mode == MVN_EPI_DIVIDE_U16) {
         if (even) {
           MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, false, false, true>(p, t, 0, 1, l)));
@@ -624,6 +650,17 @@ void launch_extract3d(const ExtractParams& p, stream_t) {
 #pragma omp parallel for schedule(static)
   for (long blk = 0; blk < nblocks; ++blk)
     for (int t = 0; t < MVN_INGEST_WG; ++t) mvn_extract_rows(p, blk, t);
+}
+
+static std::atomic<long> g_tv_launches{0};
+long tv_launch_count() { return g_tv_launches.load(); }
+void launch_tv(const TvParams& p0, stream_t) {
+  TvParams p = p0;
+  mvn_tv_geometry(p);
+  if (p.d0 < 1 || p.d1 < 1 || p.d2 < 1 || p.RP < p.d2 || (long)p.d1 * p.RP > 0x7fffffffL)
+    throw std::invalid_argument("mvn: total-variation pass outside its range");
+  ++g_tv_launches;
+  mvn_tv_host(p);
 }
 
 void launch_accel_a(const AccelParams& p, stream_t) { mvn_accel_host_a(p); }

@@ -2,6 +2,7 @@
 #include "mvn_engine.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
@@ -23,7 +24,8 @@ const char* kernel_kind_name(int k) {
   static const char* names[KK_COUNT] = {"rows_r2c",    "rows_c2r",  "rows_fused_div",
                                         "rows_fused_upd", "axis1_fwd", "axis1_inv",
                                         "axis0_fused", "axis0_fwd",  "axis0_inv",
-                                        "nyquist",     "other",     "axis0_direct", "mid_fused"};
+                                        "nyquist",     "other",     "axis0_direct", "mid_fused",
+                                        "tv_factor"};
   return (k >= 0 && k < KK_COUNT) ? names[k] : "?";
 }
 
@@ -384,6 +386,7 @@ void Plan3D::rows_c2r(const cfloat* in, const cfloat* in_nyq, float* out_real,
   if (epi.psi) epi.psi += eoff;
   if (epi.weights) epi.weights += eoff;
   if (epi.delta) epi.delta += eoff;
+  if (epi.tv) epi.tv += eoff;
   RowsParams p;
   std::memset(&p, 0, sizeof(p));
   p.ax = ax2.view;
@@ -438,6 +441,7 @@ void Plan3D::rows_c2r_r2c(cfloat* data, cfloat* nyq, const EpilogueParams& epi_a
   if (epi.psi) epi.psi += eoff;
   if (epi.weights) epi.weights += eoff;
   if (epi.delta) epi.delta += eoff;
+  if (epi.tv) epi.tv += eoff;
   RowsParams p;
   std::memset(&p, 0, sizeof(p));
   p.ax = ax2.view;
@@ -832,6 +836,7 @@ Engine::~Engine() {
   be::dfree(poison_own_);
   be::graph_destroy(sweep_graph_);
   if (!delta_external_) be::dfree(delta_);
+  be::dfree(tv_);
   try {
     if (side_.s) be::stream_sync(side_.s);
   } catch (...) {
@@ -1806,6 +1811,7 @@ size_t Engine::memory_need(const MemoryQuery& q, const FormRule& rule) {
     add(sizeof(unsigned) * (size_t)V, 1);
     add(3 * sizeof(double) * (size_t)q.stats_rows, 1);
   }
+  if (q.tv) add(mb, 1);  // the total-variation factor volume (Engine::set_regularization)
   if (q.accel_rows > 0) {  // vector extrapolation (Engine::iterate)
     add(mb, 3);  // x_prev, g, the saved y
     add(2 * sizeof(double) * (size_t)accel_records(L), 1);
@@ -1895,6 +1901,24 @@ void Engine::conv_pair(int v, double lambda, float min_value, int final_mode, in
   const bool stats = stats_on_ && final_mode == MVN_EPI_UPDATE;
   const MvnStatsParams st2 = stats ? stats_for(v) : MvnStatsParams();
   e2.mode = stats ? MVN_EPI_UPDATE_STATS : final_mode;
+  // total variation: the factor of psi as it stands now - psi does not change before this view's update pass -
+  // multiplies the integral there; lambda is the TV weight and the Tikhonov branch stays off
+  const bool tv = tv_on_ && final_mode == MVN_EPI_UPDATE;
+  if (tv) {
+    const Layout& L = P.L;
+    TvParams t;
+    std::memset(&t, 0, sizeof(t));
+    t.psi = psi_;
+    t.t = tv_;
+    t.d0 = L.d0, t.d1 = L.d1, t.d2 = L.d2, t.RP = L.RP;
+    t.lambda = (float)lambda;
+    t.e2 = (float)reg_eps_ * (float)reg_eps_;
+    ProfScope ps(prof, KK_TV, stream_);
+    be::launch_tv(t, stream_);
+    e2.mode = stats ? MVN_EPI_UPDATE_STATS_TV : MVN_EPI_UPDATE_TV;
+    e2.tv = tv_;
+    lambda = 0.;
+  }
   e2.scale = 1.f;
   e2.psi = psi_;
   e2.weights = s.weights;
@@ -2028,6 +2052,33 @@ void Engine::end_streaming() {
   stage_cv_.notify_all();
 }
 
+void Engine::tv_free() {
+  if (!tv_) return;
+  be::stream_sync(stream_);  // (a pass that reads it may still be in flight)
+  // a captured sweep of a TV call holds the volume's address (the pass's store target and the update's operand):
+  // it goes with the volume, as in bind_poison, and the key below holds the address as well
+  be::graph_destroy(sweep_graph_);
+  sweep_graph_ = nullptr;
+  be::dfree(tv_);
+  tv_ = nullptr;
+}
+
+void Engine::refuse_tv(const char* what) const {
+  if (reg_kind_ == 1) throw std::logic_error(std::string("mvn: ") + what + " with total-variation regularisation");
+}
+
+void Engine::set_regularization(int kind, double epsilon) {
+  if (kind != 0 && kind != 1) throw std::invalid_argument("mvn: regularisation kind must be 0 (Tikhonov) or 1 (total variation)");
+  if (kind == 1 && !(epsilon > 0. && std::isfinite(epsilon)))
+    throw std::invalid_argument("mvn: total-variation regularisation needs a finite epsilon > 0");
+  if (kind == 1 && halo_fn_)
+    throw std::logic_error("mvn: no total-variation regularisation on a slab of a multi-device group (halo mode)");
+  be::set_device(device_);
+  if (kind == 0) tv_free();
+  reg_kind_ = kind;
+  reg_eps_ = kind == 1 ? epsilon : 0.;
+}
+
 void Engine::accel_free() {
   be::dfree(accel_xprev_);
   be::dfree(accel_g_);
@@ -2063,6 +2114,16 @@ int Engine::iterate(int iterations, double lambda, float min_value, double toler
   if (alphas) alphas->clear();
   const bool st_on = tolerance >= 0.;
   const bool ac_on = accel == 1 && iterations > 0;
+  tv_on_ = false;
+  if (reg_kind_ == 1) {
+    if (halo_fn_) throw std::logic_error("mvn: no total-variation regularisation on a slab of a multi-device group (halo mode)");
+    // |div p| <= 6: below 1/12 the denominator 1 - lambda div p stays above 0.5 with no clamp in the kernel
+    if (!(lambda >= 0. && lambda < 1. / 12.))
+      throw std::invalid_argument("mvn: total-variation regularisation needs 0 <= lambda < 1/12");
+    tv_on_ = lambda > 0. && iterations > 0;
+    if (tv_on_ && !tv_) tv_ = (float*)be::dmalloc(plan_->main_bytes());
+    if (!tv_on_) tv_free();
+  }
   if (accel == 1 && halo_fn_)
     throw std::logic_error("mvn: no acceleration on a slab of a multi-device group (halo mode)");
   if (st_on) {
@@ -2131,6 +2192,8 @@ int Engine::iterate_sweeps(int iterations, double lambda, float min_value, doubl
     if (use_graph && it >= 1 && it < iterations - 1) {
       if (sweep_graph_ && (graph_lambda_ != lambda || graph_min_ != min_value ||
                            graph_guard_ != quotient_guard_ || graph_captured_gen_ != graph_gen_ ||
+                           graph_reg_kind_ != reg_kind_ || graph_reg_eps_ != reg_eps_ ||
+                           graph_tv_ != (tv_on_ ? tv_ : nullptr) ||
                            graph_work_ != work_)) {
         be::graph_destroy(sweep_graph_);
         sweep_graph_ = nullptr;
@@ -2153,6 +2216,9 @@ int Engine::iterate_sweeps(int iterations, double lambda, float min_value, doubl
         }
         sweep_graph_ = be::capture_end(stream_);
         graph_lambda_ = lambda;
+        graph_reg_kind_ = reg_kind_;
+        graph_reg_eps_ = reg_eps_;
+        graph_tv_ = tv_on_ ? tv_ : nullptr;
         graph_min_ = min_value;
         graph_guard_ = quotient_guard_;
         graph_captured_gen_ = graph_gen_;
@@ -2234,6 +2300,7 @@ void Engine::set_halo_planes(int planes, bool split) {
 
 void Engine::set_halo_hook(halo_fn_t fn, void* user, bool drain, bool post) {
   if (fn) {
+    refuse_tv("no halo hook on an engine");
     // halo mode divides ranges of rows, whose operand offsets are in floats (Plan3D::rows_c2r*)
     if (u16_views() > 0)
       throw std::invalid_argument("mvn: no halo hook on an engine that holds a uint16 image volume (image storage mode 1)");
@@ -2326,6 +2393,7 @@ void Engine::delta_chunk_range(int c, int n, size_t* first_float, size_t* n_floa
 }
 
 void Engine::compute_delta_head(double lambda, float min_value) {
+  refuse_tv("no simultaneous (delta) step on an engine");
   be::set_device(device_);
   delta_ptr();
   tail_pending_ = false;

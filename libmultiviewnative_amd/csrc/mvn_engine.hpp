@@ -37,6 +37,7 @@ enum KernelKind {
   KK_OTHER,
   KK_AXIS0_DIRECT,  // dim0 leg as a direct convolution with the PSF's planes (mvn_dim0_direct.hpp)
   KK_MID_FUSED,     // dim1 forward + direct dim0 leg + dim1 inverse in one pass (mvn_mid_fused.hpp)
+  KK_TV,            // the total-variation factor of psi (mvn_tv.hpp)
   KK_COUNT
 };
 const char* kernel_kind_name(int k);
@@ -307,6 +308,7 @@ struct MemoryQuery {
   int ring = 0;
   int stats_rows = 0;  // convergence statistics on: the iterations of the call (Engine::iterate), else 0
   int accel_rows = 0;  // acceleration on: the iterations of the call, else 0
+  bool tv = false;     // total-variation regularisation with lambda > 0: the factor volume
   // per view: the call wants its image kept as uint16 (image storage mode 1 and a uint16 stack that is no broadcast);
   // empty: none.  What is then held as uint16: Engine::kept_u16.
   std::vector<char> image_u16;
@@ -422,6 +424,13 @@ class Engine {
   // Not for an engine with a halo hook (a slab of a multi-device group).
   int iterate(int iterations, double lambda, float min_value, double tolerance = -1.,
               std::vector<double>* stats = nullptr, int accel = 0, std::vector<double>* alphas = nullptr);
+  // The regulariser of the iterate() calls that follow (mvn_engine_api.h, MVN_REG_*).  kind 0: `lambda` is the
+  // reference's Tikhonov weight.  kind 1: total variation - lambda is the TV weight, the Tikhonov branch is off and
+  // every view update is preceded by the pass of mvn_tv.hpp, whose factor volume is allocated at first need and kept
+  // while the kind stays; lambda >= 1/12 is refused, lambda == 0 is the plain loop.  Not for an engine with a halo
+  // hook, and compute_delta* refuse a TV engine.
+  void set_regularization(int kind, double epsilon);
+  int regularization_kind() const { return reg_kind_; }
   // simultaneous (Jacobi) mode for view sharding: delta <- sum over this engine's views of
   // w_v (next_v - psi), computed from the current psi without changing it
   void compute_delta(double lambda, float min_value);
@@ -683,6 +692,13 @@ class Engine {
   void stats_free();
   int iterate_sweeps(int iterations, double lambda, float min_value, double tolerance, std::vector<double>* stats,
                      std::vector<double>* alphas);
+  // total-variation regularisation (set_regularization)
+  int reg_kind_ = 0;
+  double reg_eps_ = 0.;
+  bool tv_on_ = false;    // the running iterate() multiplies the integrals by the factor volume
+  float* tv_ = nullptr;   // the factor volume, psi's layout
+  void tv_free();
+  void refuse_tv(const char* what) const;
   // vector extrapolation of the running iterate() (allocated for its duration only; see memory_need)
   bool accel_on_ = false;
   float* accel_xprev_ = nullptr;  // x_{k-1}
@@ -717,6 +733,9 @@ class Engine {
   // valid for the parameters it was captured with, buffers never move during an engine's life
   be::graph_exec_t sweep_graph_ = nullptr;
   double graph_lambda_ = 0;
+  int graph_reg_kind_ = 0;  // the regulariser the sweep was captured with
+  double graph_reg_eps_ = 0;
+  const float* graph_tv_ = nullptr;  // ... and the factor volume its launches address
   float graph_min_ = 0;
   bool graph_guard_ = false;
   // PSF preparations and layout changes so far / at capture: the graph bakes in the PSF buffers, their form

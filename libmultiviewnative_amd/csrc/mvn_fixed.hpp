@@ -1134,7 +1134,7 @@ struct FxRowsStatRegs : FxRowsRegs<H> {
   MvnStatAcc st;
 };
 template <int H, int EPI>
-using FxRowsRegsFor = typename std::conditional<EPI == MVN_EPI_UPDATE_STATS, FxRowsStatRegs<H>, FxRowsRegs<H>>::type;
+using FxRowsRegsFor = typename std::conditional<mvn_epi_base(EPI) == MVN_EPI_UPDATE_STATS, FxRowsStatRegs<H>, FxRowsRegs<H>>::type;
 
 // LDS offsets (in cfloat, row * TP) of the two bins the real<->complex step combines: entry k
 // (0 < k < H/2) = {bin k, bin H-k}; entry 0 = {bin 0, bin H/2} (the two self-paired bins).
@@ -1338,7 +1338,7 @@ MVN_HD void fx_rows_r2c_body(const RowsParams& P, long tile, cfloat* lds, Ctx& c
 // mode so that a mode's dead operand registers and branches vanish
 template <int EPI>
 MVN_HD cfloat fx_epilogue_pair_value(const EpilogueParams& e, long i, cfloat z, cfloat a, cfloat b) {
-  return mvn_epilogue_pair_value(EPI, e, i, z, a, b);
+  return mvn_epilogue_pair_value<mvn_epi_tv(EPI)>(mvn_epi_math(EPI), e, i, z, a, b);
 }
 
 // the first epilogue operand at its use: a uint16 pair is widened here, not where it was fetched
@@ -1501,28 +1501,28 @@ MVN_HD void fx_c2r_stage0_epilogue(const RowsParams& P, long r0, cfloat* buf, co
     for (int k = 1; k < R; ++k) a[k] = cmulc(a[k], tw[k]);
     dftR<R, +1>(a);  // a[jo] = z[j2 + M*jo] = (x[2j], x[2j+1])
     const long i0 = (r0 + rho) * P.RP + 2 * j2;
-    if constexpr (EPI == MVN_EPI_UPDATE_STATS) {
+    if constexpr (mvn_epi_base(EPI) == MVN_EPI_UPDATE_STATS) {
       const bool row_in = mvn_stat_row_in(P.st, r0 + rho);
 #pragma unroll
       for (int jo = 0; jo < R; ++jo)
-        a[jo] = mvn_update_pair_stats(P.epi, i0 + 2 * jo * M, a[jo], r.ea[it][jo], r.eb[it][jo], r.st, P.st, row_in,
+        a[jo] = mvn_update_pair_stats<mvn_epi_tv(EPI)>(P.epi, i0 + 2 * jo * M, a[jo], r.ea[it][jo], r.eb[it][jo], r.st, P.st, row_in,
                                       2 * (j2 + jo * M));
     }
     if (KEEP) {
 #pragma unroll
       for (int jo = 0; jo < R; ++jo)
-        if constexpr (EPI != MVN_EPI_UPDATE_STATS)
-          a[jo] = fx_epilogue_pair_value<mvn_epi_math(EPI)>(P.epi, i0 + 2 * jo * M, a[jo], fx_operand<EPI>(r.ea[it][jo], r.eu[it][jo]),
+        if constexpr (mvn_epi_base(EPI) != MVN_EPI_UPDATE_STATS)
+          a[jo] = fx_epilogue_pair_value<EPI>(P.epi, i0 + 2 * jo * M, a[jo], fx_operand<EPI>(r.ea[it][jo], r.eu[it][jo]),
                                                             r.eb[it][jo]);
       dftR<R, -1>(a);
 #pragma unroll
       for (int k = 1; k < R; ++k) a[k] = cmul(a[k], tw[k]);
 #pragma unroll
       for (int k = 0; k < R; ++k) p[fx_rowoff<C::PAD, R, M>(k) * TP] = a[k];
-    } else if constexpr (EPI != MVN_EPI_UPDATE_STATS) {
+    } else if constexpr (mvn_epi_base(EPI) != MVN_EPI_UPDATE_STATS) {
 #pragma unroll
       for (int jo = 0; jo < R; ++jo)
-        mvn_epilogue_pair_t<mvn_epi_math(EPI)>(P.epi, P.out_real, i0 + 2 * jo * M, a[jo], fx_operand<EPI>(r.ea[it][jo], r.eu[it][jo]),
+        mvn_epilogue_pair_t<EPI>(P.epi, P.out_real, i0 + 2 * jo * M, a[jo], fx_operand<EPI>(r.ea[it][jo], r.eu[it][jo]),
                                                r.eb[it][jo]);
     }
   }
@@ -1618,14 +1618,14 @@ MVN_HD void fx_stat_flush(const MvnStatsParams& s, long block, long nblocks, cfl
   MVN_PHASE_NOSYNC(ctx, (tid == 0 ? mvn_stat_record(s, l, NT, block, nblocks) : (void)0));
 }
 
-// the MVN_EPI_UPDATE_STATS workgroup: accumulators zeroed, fx_rows_run, one record
-template <int H, int KIND, typename Ctx, bool LINES = false>
+// the MVN_EPI_UPDATE_STATS (or MVN_EPI_UPDATE_STATS_TV) workgroup: accumulators zeroed, fx_rows_run, one record
+template <int H, int KIND, typename Ctx, bool LINES = false, int EPI = MVN_EPI_UPDATE_STATS>
 MVN_HD void fx_rows_run_stats(const RowsParams& P, long block, long nblocks, cfloat* lds, Ctx& ctx) {
   static_assert(mvn_stat_lds_bytes(FxRowsCfg<H>::NT) <= (long)sizeof(cfloat) * FxRowsCfg<H>::lds_cfloats,
                 "statistics scratch exceeds the LDS");
   constexpr int NT_ = FxRowsCfg<H>::NT;
   (void)NT_;
   MVN_PHASE_NOSYNC(ctx, (mvn_stat_init(r.st)));
-  fx_rows_run<H, KIND, MVN_EPI_UPDATE_STATS, Ctx, LINES>(P, block, nblocks, lds, ctx);
+  fx_rows_run<H, KIND, EPI, Ctx, LINES>(P, block, nblocks, lds, ctx);
   fx_stat_flush<FxRowsCfg<H>::NT>(P.st, block, nblocks, lds, ctx);
 }

@@ -86,6 +86,22 @@ __global__ void __launch_bounds__(512) k_rows_c2r_r2c_u16(const RowsParams p) {
   rows_c2r_even_body<T, true, false, true>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
 }
 
+// the update epilogue on the integral times the total-variation factor (MVN_EPI_UPDATE_TV, MVN_EPI_UPDATE_STATS_TV),
+// plain and fused
+template <bool EVEN, int T, bool STATS>
+__global__ void __launch_bounds__(512) k_rows_c2r_tv(const RowsParams p) {
+  extern __shared__ __attribute__((aligned(16))) char mvn_smem[];
+  if (EVEN)
+    rows_c2r_even_body<T, false, STATS, false, true>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
+  else
+    rows_c2r_odd_body<T, STATS, false, true>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
+}
+template <int T, bool STATS>
+__global__ void __launch_bounds__(512) k_rows_c2r_r2c_tv(const RowsParams p) {
+  extern __shared__ __attribute__((aligned(16))) char mvn_smem[];
+  rows_c2r_even_body<T, true, STATS, false, true>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
+}
+
 // NYQ only tags the launches that work on the Nyquist plane, so that profilers list them apart
 // run-time-radix form of the fused c2r + pointwise + r2c pass (any even d2)
 template <int T>
@@ -131,8 +147,8 @@ __global__ void __launch_bounds__(FxRowsCfg<H>::NT) kx_rows_c2r(const RowsParams
   typedef FxCtx<FxRowsRegsFor<H, EPI>, FxRowsCfg<H>::NT> Ctx;
   Ctx ctx;
   ctx.tid = (int)threadIdx.x;
-  if constexpr (EPI == MVN_EPI_UPDATE_STATS)
-    fx_rows_run_stats<H, 1, Ctx, LINES>(p, (long)blockIdx.x, (long)gridDim.x, (cfloat*)mvn_smem, ctx);
+  if constexpr (mvn_epi_base(EPI) == MVN_EPI_UPDATE_STATS)
+    fx_rows_run_stats<H, 1, Ctx, LINES, EPI>(p, (long)blockIdx.x, (long)gridDim.x, (cfloat*)mvn_smem, ctx);
   else
     fx_rows_run<H, 1, EPI, Ctx, LINES>(p, (long)blockIdx.x, (long)gridDim.x, (cfloat*)mvn_smem, ctx);
 }
@@ -147,8 +163,8 @@ __global__ void __launch_bounds__(FxRowsCfg<H>::NT) kx_rows_c2r_r2c(const RowsPa
   typedef FxCtx<FxRowsRegsFor<H, EPI>, FxRowsCfg<H>::NT> Ctx;
   Ctx ctx;
   ctx.tid = (int)threadIdx.x;
-  if constexpr (EPI == MVN_EPI_UPDATE_STATS)
-    fx_rows_run_stats<H, 2, Ctx, LINES>(p, (long)blockIdx.x, (long)gridDim.x, (cfloat*)mvn_smem, ctx);
+  if constexpr (mvn_epi_base(EPI) == MVN_EPI_UPDATE_STATS)
+    fx_rows_run_stats<H, 2, Ctx, LINES, EPI>(p, (long)blockIdx.x, (long)gridDim.x, (cfloat*)mvn_smem, ctx);
   else
     fx_rows_run<H, 2, EPI, Ctx, LINES>(p, (long)blockIdx.x, (long)gridDim.x, (cfloat*)mvn_smem, ctx);
 }
@@ -284,6 +300,12 @@ __global__ __launch_bounds__(MVN_ACCEL_WG) void k_accel_reduce(const double* rec
 template <int W>
 __global__ __launch_bounds__(MVN_ACCEL_WG) void k_accel_b(const AccelParams p) {
   mvn_accel_b_body<W>(p, (long)blockIdx.x, (int)threadIdx.x, MVN_ACCEL_WG);
+}
+
+// the total-variation factor of psi (mvn_tv.hpp): a tile of a plane per workgroup, walked along dim0
+__global__ __launch_bounds__(MVN_TV_WG) void k_tv_factor(const TvParams p) {
+  __shared__ float lds[MVN_TV_LDS_FLOATS];
+  mvn_tv_body<1>(p, (long)blockIdx.x, lds, (int)threadIdx.x, MVN_TV_WG);
 }
 
 __global__ void k_divide(const float* __restrict__ view, float* __restrict__ inout, size_t n) {
@@ -722,6 +744,8 @@ void launch_rows_c2r(const RowsParams& p, bool even, long nblocks, int nthreads,
       case MVN_EPI_DIVIDE_U16: return launch_pass(kx_rows_c2r<256, MVN_EPI_DIVIDE_U16, true>, p, nblocks, nthreads, lds_bytes, s);
       case MVN_EPI_UPDATE: return launch_pass(kx_rows_c2r<256, MVN_EPI_UPDATE, true>, p, nblocks, nthreads, lds_bytes, s);
       case MVN_EPI_UPDATE_STATS: return launch_pass(kx_rows_c2r<256, MVN_EPI_UPDATE_STATS, true>, p, nblocks, nthreads, lds_bytes, s);
+      case MVN_EPI_UPDATE_TV: return launch_pass(kx_rows_c2r<256, MVN_EPI_UPDATE_TV, true>, p, nblocks, nthreads, lds_bytes, s);
+      case MVN_EPI_UPDATE_STATS_TV: return launch_pass(kx_rows_c2r<256, MVN_EPI_UPDATE_STATS_TV, true>, p, nblocks, nthreads, lds_bytes, s);
       case MVN_EPI_DELTA: return launch_pass(kx_rows_c2r<256, MVN_EPI_DELTA, true>, p, nblocks, nthreads, lds_bytes, s);
       default: return launch_pass(kx_rows_c2r<256, MVN_EPI_STORE, true>, p, nblocks, nthreads, lds_bytes, s);
     }
@@ -735,6 +759,8 @@ void launch_rows_c2r(const RowsParams& p, bool even, long nblocks, int nthreads,
         case MVN_EPI_DIVIDE_U16: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_DIVIDE_U16>, p, s);
         case MVN_EPI_UPDATE: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_UPDATE>, p, s);
         case MVN_EPI_UPDATE_STATS: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_UPDATE_STATS>, p, s);
+        case MVN_EPI_UPDATE_TV: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_UPDATE_TV>, p, s);
+        case MVN_EPI_UPDATE_STATS_TV: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_UPDATE_STATS_TV>, p, s);
         case MVN_EPI_DELTA: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_DELTA>, p, s);
         default: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_STORE>, p, s);
       }
@@ -747,6 +773,8 @@ void launch_rows_c2r(const RowsParams& p, bool even, long nblocks, int nthreads,
       case MVN_EPI_DIVIDE_U16: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_DIVIDE_U16>, p, nblocks, nthreads, lds_bytes, s); break; \
       case MVN_EPI_UPDATE: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_UPDATE>, p, nblocks, nthreads, lds_bytes, s); break; \
       case MVN_EPI_UPDATE_STATS: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_UPDATE_STATS>, p, nblocks, nthreads, lds_bytes, s); break; \
+      case MVN_EPI_UPDATE_TV: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_UPDATE_TV>, p, nblocks, nthreads, lds_bytes, s); break; \
+      case MVN_EPI_UPDATE_STATS_TV: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_UPDATE_STATS_TV>, p, nblocks, nthreads, lds_bytes, s); break; \
       case MVN_EPI_DELTA: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_DELTA>, p, nblocks, nthreads, lds_bytes, s); break;   \
       default: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_STORE>, p, nblocks, nthreads, lds_bytes, s); break;             \
     }                                                                                         \
@@ -762,6 +790,20 @@ void launch_rows_c2r(const RowsParams& p, bool even, long nblocks, int nthreads,
       MVN_DISPATCH_T(p.T, (k_rows_c2r_stats<true, TT>));
     } else {
       MVN_DISPATCH_T(p.T, (k_rows_c2r_stats<false, TT>));
+    }
+    return;
+  }
+  if (mvn_epi_tv(p.epi.mode)) {
+    const bool stats = p.epi.mode == MVN_EPI_UPDATE_STATS_TV;
+    if (stats) lds_bytes = std::max(lds_bytes, (size_t)mvn_stat_lds_bytes(nthreads));
+    if (even && stats) {
+      MVN_DISPATCH_T(p.T, (k_rows_c2r_tv<true, TT, true>));
+    } else if (even) {
+      MVN_DISPATCH_T(p.T, (k_rows_c2r_tv<true, TT, false>));
+    } else if (stats) {
+      MVN_DISPATCH_T(p.T, (k_rows_c2r_tv<false, TT, true>));
+    } else {
+      MVN_DISPATCH_T(p.T, (k_rows_c2r_tv<false, TT, false>));
     }
     return;
   }
@@ -790,6 +832,8 @@ void launch_rows_c2r_r2c(const RowsParams& p, long nblocks, int nthreads, size_t
       case MVN_EPI_DIVIDE_U16: return launch_pass(kx_rows_c2r_r2c<256, MVN_EPI_DIVIDE_U16, true>, p, nblocks, nthreads, lds_bytes, s);
       case MVN_EPI_UPDATE: return launch_pass(kx_rows_c2r_r2c<256, MVN_EPI_UPDATE, true>, p, nblocks, nthreads, lds_bytes, s);
       case MVN_EPI_UPDATE_STATS: return launch_pass(kx_rows_c2r_r2c<256, MVN_EPI_UPDATE_STATS, true>, p, nblocks, nthreads, lds_bytes, s);
+      case MVN_EPI_UPDATE_TV: return launch_pass(kx_rows_c2r_r2c<256, MVN_EPI_UPDATE_TV, true>, p, nblocks, nthreads, lds_bytes, s);
+      case MVN_EPI_UPDATE_STATS_TV: return launch_pass(kx_rows_c2r_r2c<256, MVN_EPI_UPDATE_STATS_TV, true>, p, nblocks, nthreads, lds_bytes, s);
       default: return launch_pass(kx_rows_c2r_r2c<256, MVN_EPI_STORE, true>, p, nblocks, nthreads, lds_bytes, s);
     }
   }
@@ -797,6 +841,15 @@ void launch_rows_c2r_r2c(const RowsParams& p, long nblocks, int nthreads, size_t
     if (p.epi.mode == MVN_EPI_UPDATE_STATS) {
       lds_bytes = std::max(lds_bytes, (size_t)mvn_stat_lds_bytes(nthreads));
       MVN_DISPATCH_T(p.T, (k_rows_c2r_r2c_stats<TT>));
+      return;
+    }
+    if (p.epi.mode == MVN_EPI_UPDATE_STATS_TV) {
+      lds_bytes = std::max(lds_bytes, (size_t)mvn_stat_lds_bytes(nthreads));
+      MVN_DISPATCH_T(p.T, (k_rows_c2r_r2c_tv<TT, true>));
+      return;
+    }
+    if (p.epi.mode == MVN_EPI_UPDATE_TV) {
+      MVN_DISPATCH_T(p.T, (k_rows_c2r_r2c_tv<TT, false>));
       return;
     }
     if (p.epi.mode == MVN_EPI_DIVIDE_U16) {
@@ -814,6 +867,8 @@ void launch_rows_c2r_r2c(const RowsParams& p, long nblocks, int nthreads, size_t
       case MVN_EPI_DIVIDE_U16: return launch_wave_rows(kw_rows<MVN_WR_C2R_R2C, MVN_EPI_DIVIDE_U16>, p, s);
       case MVN_EPI_UPDATE: return launch_wave_rows(kw_rows<MVN_WR_C2R_R2C, MVN_EPI_UPDATE>, p, s, 32);
       case MVN_EPI_UPDATE_STATS: return launch_wave_rows(kw_rows<MVN_WR_C2R_R2C, MVN_EPI_UPDATE_STATS>, p, s, 32);
+      case MVN_EPI_UPDATE_TV: return launch_wave_rows(kw_rows<MVN_WR_C2R_R2C, MVN_EPI_UPDATE_TV>, p, s, 32);
+      case MVN_EPI_UPDATE_STATS_TV: return launch_wave_rows(kw_rows<MVN_WR_C2R_R2C, MVN_EPI_UPDATE_STATS_TV>, p, s, 32);
       default: return launch_wave_rows(kw_rows<MVN_WR_C2R_R2C, MVN_EPI_STORE>, p, s);
     }
   }
@@ -825,6 +880,8 @@ void launch_rows_c2r_r2c(const RowsParams& p, long nblocks, int nthreads, size_t
       case MVN_EPI_DIVIDE_U16: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r_r2c<H, MVN_EPI_DIVIDE_U16>, p, nblocks, nthreads, lds_bytes, s); break; \
       case MVN_EPI_UPDATE: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r_r2c<H, MVN_EPI_UPDATE>, p, nblocks, nthreads, lds_bytes, s); break; \
       case MVN_EPI_UPDATE_STATS: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r_r2c<H, MVN_EPI_UPDATE_STATS>, p, nblocks, nthreads, lds_bytes, s); break; \
+      case MVN_EPI_UPDATE_TV: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r_r2c<H, MVN_EPI_UPDATE_TV>, p, nblocks, nthreads, lds_bytes, s); break; \
+      case MVN_EPI_UPDATE_STATS_TV: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r_r2c<H, MVN_EPI_UPDATE_STATS_TV>, p, nblocks, nthreads, lds_bytes, s); break; \
       default: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r_r2c<H, MVN_EPI_STORE>, p, nblocks, nthreads, lds_bytes, s); break;             \
     }                                                                                         \
     return;
@@ -1028,6 +1085,21 @@ void launch_accel_b(const AccelParams& p, stream_t s) {
     hipLaunchKernelGGL(k_accel_b<4>, dim3(accel_grid(p, 4)), dim3(MVN_ACCEL_WG), 0, hs(s), p);
   else
     hipLaunchKernelGGL(k_accel_b<2>, dim3(accel_grid(p, 2)), dim3(MVN_ACCEL_WG), 0, hs(s), p);
+  HIP_CHECK(hipGetLastError());
+}
+
+static std::atomic<long> g_tv_launches{0};
+long tv_launch_count() { return g_tv_launches.load(); }
+
+void launch_tv(const TvParams& p0, stream_t s) {
+  TvParams p = p0;
+  mvn_tv_geometry(p);
+  const long nblocks = mvn_tv_blocks(p);
+  if (p.d0 < 1 || p.d1 < 1 || p.d2 < 1 || p.RP < p.d2 || (long)p.d1 * p.RP > 0x7fffffffL || nblocks < 1 ||
+      nblocks > 0x7fffffffL)
+    throw std::invalid_argument("mvn: total-variation pass outside its range");
+  ++g_tv_launches;
+  hipLaunchKernelGGL(k_tv_factor, dim3((unsigned)nblocks), dim3(MVN_TV_WG), 0, hs(s), p);
   HIP_CHECK(hipGetLastError());
 }
 

@@ -33,15 +33,24 @@ enum MvnEpilogue {
   MVN_EPI_UPDATE = 2,  // psi = w * (next(psi, x*scale) - psi) + psi
   MVN_EPI_DELTA = 3,   // delta (+)= w * (next(psi, x*scale) - psi)     (simultaneous mode)
   MVN_EPI_UPDATE_STATS = 4,  // UPDATE, plus the convergence statistics of the window (MvnStatsParams)
-  MVN_EPI_DIVIDE_U16 = 5     // DIVIDE with the view held as uint16 (EpilogueParams::view16): same quotient, bit for bit
+  MVN_EPI_DIVIDE_U16 = 5,    // DIVIDE with the view held as uint16 (EpilogueParams::view16): same quotient, bit for bit
+  // total-variation regularisation (mvn_tv.hpp): the integral x*scale is multiplied by the factor tv[i] before `next`
+  MVN_EPI_UPDATE_TV = 6,        // psi = w * (next(psi, (x*scale) * tv) - psi) + psi
+  MVN_EPI_UPDATE_STATS_TV = 7   // UPDATE_TV, plus the convergence statistics
 };
 
 // the epilogues that read psi and the weights
 constexpr bool mvn_epi_reads_psi(int epi) {
-  return epi == MVN_EPI_UPDATE || epi == MVN_EPI_DELTA || epi == MVN_EPI_UPDATE_STATS;
+  return epi == MVN_EPI_UPDATE || epi == MVN_EPI_DELTA || epi == MVN_EPI_UPDATE_STATS || epi == MVN_EPI_UPDATE_TV ||
+         epi == MVN_EPI_UPDATE_STATS_TV;
+}
+// the epilogues that multiply the integral by the total-variation factor, and the mode each of them extends
+constexpr bool mvn_epi_tv(int epi) { return epi == MVN_EPI_UPDATE_TV || epi == MVN_EPI_UPDATE_STATS_TV; }
+constexpr int mvn_epi_base(int epi) {
+  return epi == MVN_EPI_UPDATE_TV ? (int)MVN_EPI_UPDATE : epi == MVN_EPI_UPDATE_STATS_TV ? (int)MVN_EPI_UPDATE_STATS : epi;
 }
 // the mode whose arithmetic an epilogue runs once its operands are floats
-constexpr int mvn_epi_math(int epi) { return epi == MVN_EPI_DIVIDE_U16 ? (int)MVN_EPI_DIVIDE : epi; }
+constexpr int mvn_epi_math(int epi) { return epi == MVN_EPI_DIVIDE_U16 ? (int)MVN_EPI_DIVIDE : mvn_epi_base(epi); }
 
 struct EpilogueParams {
   int mode;
@@ -66,7 +75,24 @@ struct EpilogueParams {
   // epoch 0xffffffff (Plan3D::no_poison) - the pointer is never null when a pass is launched.
   const unsigned* poison;
   unsigned poison_epoch;
+  const float* tv;      // UPDATE_TV / UPDATE_STATS_TV: the factor volume, psi's layout (mvn_tv.hpp)
 };
+
+// the total-variation factor of element i / of the pair (i, i + 1), loaded at its use
+template <bool TV>
+MVN_HD float mvn_tv_one(const EpilogueParams& e, long i) {
+  if constexpr (TV)
+    return e.tv[i];
+  else
+    return 1.f;
+}
+template <bool TV>
+MVN_HD cfloat mvn_tv_pair(const EpilogueParams& e, long i) {
+  if constexpr (TV)
+    return *reinterpret_cast<const cfloat*>(e.tv + i);
+  else
+    return cmake(1.f, 1.f);
+}
 
 // Once per workgroup, before the first epilogue: a reported non-finite input turns the scale every raw output is
 // multiplied with first into NaN - and with it every voxel (DIVIDE: view * 1 / NaN; UPDATE / DELTA: the clamp
@@ -168,9 +194,11 @@ MVN_HD float mvn_legacy_tikhonov_value(float image, float integral, float weight
   return weight * (nv - t) + t;
 }
 
+template <bool TV = false>
 MVN_HD void mvn_epilogue(const EpilogueParams& e, float* out, long i, float x) {
   MVN_FP_EXACT
   x *= e.scale;
+  if constexpr (TV) x *= mvn_tv_one<TV>(e, i);
   switch (e.mode) {
     case MVN_EPI_STORE: out[i] = x; break;
     case MVN_EPI_DIVIDE: out[i] = mvn_quotient_g(e.view[i], x, e.guard_zero_view); break;
@@ -212,10 +240,15 @@ MVN_HD void mvn_epilogue_fetch_batch_u16(const EpilogueParams& e, const long* id
   for (int u = 0; u < U; ++u) a[u] = mvn_u16_pair_fetch(e.view16 + idx[u]);
 }
 
+template <bool TV = false>
 MVN_HD void mvn_epilogue_pair(const EpilogueParams& e, float* out, long i, cfloat z, cfloat a,
                               cfloat b) {
   MVN_FP_EXACT
-  const float x0 = z.x * e.scale, x1 = z.y * e.scale;
+  float x0 = z.x * e.scale, x1 = z.y * e.scale;
+  if constexpr (TV) {
+    const cfloat t = mvn_tv_pair<TV>(e, i);
+    x0 *= t.x, x1 *= t.y;
+  }
   switch (e.mode) {
     case MVN_EPI_STORE: *reinterpret_cast<cfloat*>(out + i) = cmake(x0, x1); break;
     case MVN_EPI_DIVIDE:
@@ -295,10 +328,15 @@ MVN_HD void mvn_stat_add(MvnStatAcc& a, bool in, float last, float y, float x) {
 
 // MVN_EPI_UPDATE of the pair (i, i + 1) in columns col, col + 1 of a row, with its statistics: psi (written
 // and returned) is the UPDATE result bit for bit
+template <bool TV = false>
 MVN_HD cfloat mvn_update_pair_stats(const EpilogueParams& e, long i, cfloat z, cfloat a, cfloat b, MvnStatAcc& acc,
                                     const MvnStatsParams& s, bool row_in, int col) {
   MVN_FP_EXACT
-  const float x0 = z.x * e.scale, x1 = z.y * e.scale;
+  float x0 = z.x * e.scale, x1 = z.y * e.scale;
+  if constexpr (TV) {
+    const cfloat t = mvn_tv_pair<TV>(e, i);
+    x0 *= t.x, x1 *= t.y;
+  }
   const float n0 = mvn_next_value(a.x, x0, e.lambda, e.lambda_inv, e.min_value);
   const float n1 = mvn_next_value(a.y, x1, e.lambda, e.lambda_inv, e.min_value);
   const cfloat y = cmake(mvn_blend(b.x, n0, a.x), mvn_blend(b.y, n1, a.y));
@@ -310,9 +348,11 @@ MVN_HD cfloat mvn_update_pair_stats(const EpilogueParams& e, long i, cfloat z, c
 }
 
 // the same for one element (odd d2)
+template <bool TV = false>
 MVN_HD void mvn_update_stats(const EpilogueParams& e, long i, float x, MvnStatAcc& acc, bool in) {
   MVN_FP_EXACT
   x *= e.scale;
+  if constexpr (TV) x *= mvn_tv_one<TV>(e, i);
   const float last = e.psi[i];
   const float next = mvn_next_value(last, x, e.lambda, e.lambda_inv, e.min_value);
   const float y = e.weights[i] * (next - last) + last;  // inc/cpu_kernels.h:51-52
@@ -410,10 +450,15 @@ MVN_HD void mvn_convergence_reduce_body(const double* rec, const unsigned* count
 
 // Pair epilogue of the fused c2r + pointwise + r2c pass: hands the two results back as the packed
 // input z[j] = (y[2j], y[2j+1]) of the next forward transform; UPDATE also writes psi.
+template <bool TV = false>
 MVN_HD cfloat mvn_epilogue_pair_value(int mode, const EpilogueParams& e, long i, cfloat z, cfloat a,
                                       cfloat b) {
   MVN_FP_EXACT
-  const float x0 = z.x * e.scale, x1 = z.y * e.scale;
+  float x0 = z.x * e.scale, x1 = z.y * e.scale;
+  if constexpr (TV) {
+    const cfloat t = mvn_tv_pair<TV>(e, i);
+    x0 *= t.x, x1 *= t.y;
+  }
   if (mode == MVN_EPI_DIVIDE)
     return cmake(mvn_quotient_g(a.x, x0, e.guard_zero_view), mvn_quotient_g(a.y, x1, e.guard_zero_view));
   if (mode == MVN_EPI_UPDATE) {
@@ -431,8 +476,8 @@ template <int EPI>
 MVN_HD void mvn_epilogue_pair_t(const EpilogueParams& e, float* out, long i, cfloat z, cfloat a,
                                 cfloat b) {
   EpilogueParams ee = e;
-  ee.mode = EPI;
-  mvn_epilogue_pair(ee, out, i, z, a, b);
+  ee.mode = mvn_epi_math(EPI);
+  mvn_epilogue_pair<mvn_epi_tv(EPI)>(ee, out, i, z, a, b);
 }
 
 #define MVN_ROWS_U 8
@@ -563,7 +608,9 @@ MVN_HD void rows_r2c_even_body(const RowsParams& P, long tile, int tid, int nthr
 // forward half (rows_r2c_even_tail), writing the half-spectrum of the result over the input.
 // STATS = true: the UPDATE epilogue with the convergence statistics (P.epi.mode is then MVN_EPI_UPDATE_STATS).
 // U16 = true: the DIVIDE epilogue on a uint16 view (P.epi.mode is then MVN_EPI_DIVIDE_U16).
-template <int T, bool KEEP = false, bool STATS = false, bool U16 = false>
+// TV = true: the UPDATE epilogue (with STATS or without) on the integral times the total-variation factor (P.epi.mode
+// is then MVN_EPI_UPDATE_TV / MVN_EPI_UPDATE_STATS_TV); the factor is loaded at its use.
+template <int T, bool KEEP = false, bool STATS = false, bool U16 = false, bool TV = false>
 MVN_HD void rows_c2r_even_body(const RowsParams& P, long tile, int tid, int nthreads, cfloat* lds) {
   // (a copy of the epilogue's few fields, not of P: the run-time radix tables in P are indexed dynamically and a
   // private copy of the whole struct would live in scratch memory)
@@ -577,6 +624,7 @@ MVN_HD void rows_c2r_even_body(const RowsParams& P, long tile, int tid, int nthr
     rin = mvn_stat_tile_rows<T>(P, tile * T);
   }
   if constexpr (U16) epi.mode = MVN_EPI_DIVIDE;  // the arithmetic of DIVIDE, on operands widened at the use
+  if constexpr (TV) epi.mode = MVN_EPI_UPDATE;   // operands and psi as UPDATE
   constexpr int U = MVN_ROWS_U;
   const int h = P.h, TP = P.TP;
   const long r0 = tile * T;
@@ -674,14 +722,14 @@ MVN_HD void rows_c2r_even_body(const RowsParams& P, long tile, int tid, int nthr
       if (w < total && row <= last_row) {
         if constexpr (U16) ea[u] = mvn_u16_pair_widen(eu[u]);
         if constexpr (STATS) {
-          const cfloat y = mvn_update_pair_stats(epi, row * P.RP + 2 * j, buf[j * TP + rho], ea[u], eb[u], acc,
-                                                 P.st, (rin >> rho) & 1u, 2 * j);
+          const cfloat y = mvn_update_pair_stats<TV>(epi, row * P.RP + 2 * j, buf[j * TP + rho], ea[u], eb[u], acc,
+                                                     P.st, (rin >> rho) & 1u, 2 * j);
           if (KEEP) buf[j * TP + rho] = y;
         } else if (KEEP)
-          buf[j * TP + rho] = mvn_epilogue_pair_value(epi.mode, epi, row * P.RP + 2 * j,
-                                                      buf[j * TP + rho], ea[u], eb[u]);
+          buf[j * TP + rho] = mvn_epilogue_pair_value<TV>(epi.mode, epi, row * P.RP + 2 * j,
+                                                          buf[j * TP + rho], ea[u], eb[u]);
         else
-          mvn_epilogue_pair(epi, P.out_real, row * P.RP + 2 * j, buf[j * TP + rho], ea[u], eb[u]);
+          mvn_epilogue_pair<TV>(epi, P.out_real, row * P.RP + 2 * j, buf[j * TP + rho], ea[u], eb[u]);
       }
     }
   }
@@ -716,7 +764,7 @@ MVN_HD void rows_r2c_odd_body(const RowsParams& P, long tile, int tid, int nthre
   }
 }
 
-template <int T, bool STATS = false, bool U16 = false>
+template <int T, bool STATS = false, bool U16 = false, bool TV = false>
 MVN_HD void rows_c2r_odd_body(const RowsParams& P, long tile, int tid, int nthreads, cfloat* lds) {
   // (a copy of the epilogue's few fields, not of P: the run-time radix tables in P are indexed dynamically and a
   // private copy of the whole struct would live in scratch memory)
@@ -728,6 +776,7 @@ MVN_HD void rows_c2r_odd_body(const RowsParams& P, long tile, int tid, int nthre
     mvn_stat_init(acc);
     rin = mvn_stat_tile_rows<T>(P, tile * T);
   }
+  if constexpr (TV) epi.mode = MVN_EPI_UPDATE;  // (MVN_EPI_UPDATE_TV: the arithmetic of UPDATE on the integral times tv)
   const int n = P.h, TP = P.TP;
   const long r0 = tile * T;
   cfloat* buf = lds;
@@ -754,7 +803,7 @@ MVN_HD void rows_c2r_odd_body(const RowsParams& P, long tile, int tid, int nthre
     const long row = r0 + rho;
     if constexpr (STATS) {
       if (row < P.rows)
-        mvn_update_stats(epi, row * P.RP + j, buf[j * TP + rho].x, acc,
+        mvn_update_stats<TV>(epi, row * P.RP + j, buf[j * TP + rho].x, acc,
                          ((rin >> rho) & 1u) && (unsigned)(j - P.st.o2) < P.st.n2);
     } else if constexpr (U16) {  // (rows of an odd extent: one element at a time, as mvn_epilogue)
       MVN_FP_EXACT
@@ -764,7 +813,7 @@ MVN_HD void rows_c2r_odd_body(const RowsParams& P, long tile, int tid, int nthre
         P.out_real[i] = mvn_quotient_g(view, buf[j * TP + rho].x * epi.scale, epi.guard_zero_view);
       }
     } else if (row < P.rows) {
-      mvn_epilogue(epi, P.out_real, row * P.RP + j, buf[j * TP + rho].x);
+      mvn_epilogue<TV>(epi, P.out_real, row * P.RP + j, buf[j * TP + rho].x);
     }
   }
   if constexpr (STATS) mvn_stat_flush(P.st, acc, tile, (P.rows + T - 1) / T, lds, tid, nthreads);

@@ -330,14 +330,14 @@ MVN_HD void wr_phase_c(const RowsParams& P, long row, long next_row, cfloat* row
     for (int k = 1; k < 8; ++k) a[k] = cmulc(a[k], tw[k]);
     dftR<8, +1>(a);  // a[jo] = z[t + 32 jo] = (x[2 j], x[2 j + 1])
     bool row_in = false;
-    if constexpr (EPI == MVN_EPI_UPDATE_STATS) row_in = mvn_stat_row_in(P.st, row);
+    if constexpr (mvn_epi_base(EPI) == MVN_EPI_UPDATE_STATS) row_in = mvn_stat_row_in(P.st, row);
     if (MODE == MVN_WR_C2R) {
 #pragma unroll
       for (int jo = 0; jo < 8; ++jo) {
-        if constexpr (EPI == MVN_EPI_UPDATE_STATS)
-          mvn_update_pair_stats(P.epi, i0 + 64 * jo, a[jo], r.ea[jo], r.eb[jo], r.st, P.st, row_in, 2 * t + 64 * jo);
+        if constexpr (mvn_epi_base(EPI) == MVN_EPI_UPDATE_STATS)
+          mvn_update_pair_stats<mvn_epi_tv(EPI)>(P.epi, i0 + 64 * jo, a[jo], r.ea[jo], r.eb[jo], r.st, P.st, row_in, 2 * t + 64 * jo);
         else
-          mvn_epilogue_pair_t<mvn_epi_math(EPI)>(P.epi, P.out_real, i0 + 64 * jo, a[jo], fx_operand<EPI>(r.ea[jo], r.eu[jo]), r.eb[jo]);
+          mvn_epilogue_pair_t<EPI>(P.epi, P.out_real, i0 + 64 * jo, a[jo], fx_operand<EPI>(r.ea[jo], r.eu[jo]), r.eb[jo]);
         if (jo & 1) MVN_SCHED_FENCE();  // four values at a time: the f64 chains of all 16 would not fit
       }
       wr_fetch_epi<EPI>(P, next_row, r, tid);
@@ -345,11 +345,11 @@ MVN_HD void wr_phase_c(const RowsParams& P, long row, long next_row, cfloat* row
     }
 #pragma unroll
     for (int jo = 0; jo < 8; ++jo) {
-      if constexpr (EPI == MVN_EPI_UPDATE_STATS)
-        a[jo] = mvn_update_pair_stats(P.epi, i0 + 64 * jo, a[jo], r.ea[jo], r.eb[jo], r.st, P.st, row_in,
+      if constexpr (mvn_epi_base(EPI) == MVN_EPI_UPDATE_STATS)
+        a[jo] = mvn_update_pair_stats<mvn_epi_tv(EPI)>(P.epi, i0 + 64 * jo, a[jo], r.ea[jo], r.eb[jo], r.st, P.st, row_in,
                                       2 * t + 64 * jo);
       else
-        a[jo] = fx_epilogue_pair_value<mvn_epi_math(EPI)>(P.epi, i0 + 64 * jo, a[jo], fx_operand<EPI>(r.ea[jo], r.eu[jo]), r.eb[jo]);
+        a[jo] = fx_epilogue_pair_value<EPI>(P.epi, i0 + 64 * jo, a[jo], fx_operand<EPI>(r.ea[jo], r.eu[jo]), r.eb[jo]);
       if (jo & 1) MVN_SCHED_FENCE();
     }
     wr_fetch_epi<EPI>(P, next_row, r, tid);
@@ -457,7 +457,7 @@ MVN_HD void wr_rows_walk(const RowsParams& P, long block, long nblocks, cfloat* 
 
 template <int MODE, int EPI, typename Ctx>
 MVN_HD void wr_rows_body(const RowsParams& P, long block, long nblocks, cfloat* lds, Ctx& ctx) {
-  if constexpr (EPI == MVN_EPI_UPDATE_STATS) {
+  if constexpr (mvn_epi_base(EPI) == MVN_EPI_UPDATE_STATS) {
     static_assert(mvn_stat_lds_bytes(WrCfg::NT) <= (long)sizeof(cfloat) * WrCfg::lds_cfloats,
                   "statistics scratch exceeds the LDS");
     constexpr int NT_ = WrCfg::NT;

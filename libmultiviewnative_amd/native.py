@@ -46,6 +46,8 @@ ENGINE_ABI_SYMBOLS = [
     "mvn_deconvolve_described", "mvn_engine_set_view_described", "mvn_engine_set_psi_described",
     "mvn_engine_get_psi_described",
     "mvn_set_acceleration", "mvn_get_acceleration", "mvn_last_acceleration", "mvn_engine_iterate_accelerated",
+    "mvn_set_regularization", "mvn_get_regularization", "mvn_engine_set_regularization", "mvn_tv_factor",
+    "mvn_tv_time", "mvn_tv_launch_count",
     "mvn_set_image_storage", "mvn_get_image_storage", "mvn_deconvolve_memory_described", "mvn_image_storage_counters",
 ]
 
@@ -168,6 +170,14 @@ class Binding:
         l.mvn_last_acceleration.argtypes = [C.POINTER(C.c_double), C.c_int]
         l.mvn_engine_iterate_accelerated.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_float, C.c_double,
                                                      C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        l.mvn_set_regularization.argtypes = [C.c_int, C.c_double]
+        l.mvn_get_regularization.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_double)]
+        l.mvn_engine_set_regularization.argtypes = [C.c_void_p, C.c_int, C.c_double]
+        l.mvn_tv_factor.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_double, C.c_double,
+                                    C.POINTER(C.c_float)]
+        l.mvn_tv_time.argtypes = [C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_float)]
+        l.mvn_tv_launch_count.restype = C.c_long
+        l.mvn_tv_launch_count.argtypes = []
         l.mvn_engine_compute_delta.argtypes = [C.c_void_p, C.c_double, C.c_float]
         l.mvn_engine_apply_delta.argtypes = [C.c_void_p]
         l.mvn_engine_delta_chunks.argtypes = [C.c_void_p, C.c_int]
@@ -317,6 +327,36 @@ class Binding:
         if rows:
             self.check(self.l.mvn_last_acceleration(out.ctypes.data_as(C.POINTER(C.c_double)), rows))
         return out
+
+    def set_regularization(self, kind, epsilon=0.0):
+        """Process-wide regulariser of the RL loop: 0 Tikhonov (default; epsilon ignored), 1 total variation with
+        workspace.lambda_ as its weight and a finite epsilon > 0 (mvn_engine_api.h)."""
+        self.check(self.l.mvn_set_regularization(int(kind), float(epsilon)))
+
+    def get_regularization(self):
+        kind, eps = C.c_int(0), C.c_double(0)
+        self.check(self.l.mvn_get_regularization(C.byref(kind), C.byref(eps)))
+        return kind.value, eps.value
+
+    def tv_factor(self, psi, lambda_, epsilon, device=0):
+        """mvn_tv_factor: the total-variation factor t of the float32 volume psi."""
+        psi = np.ascontiguousarray(psi, dtype=np.float32)
+        assert psi.ndim == 3
+        out = np.empty_like(psi)
+        dims = (C.c_int * 3)(*psi.shape)
+        self.check(self.l.mvn_tv_factor(device, dims, psi.ctypes.data_as(C.POINTER(C.c_float)), float(lambda_),
+                                        float(epsilon), out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def tv_time(self, shape, reps=10, device=0):
+        """mvn_tv_time: (ms per launch of the TV pass, ms per plain copy of the same volume)."""
+        ms = (C.c_float * 2)(0, 0)
+        dims = (C.c_int * 3)(*shape)
+        self.check(self.l.mvn_tv_time(device, dims, int(reps), ms))
+        return float(ms[0]), float(ms[1])
+
+    def tv_launch_count(self):
+        return int(self.l.mvn_tv_launch_count())
 
     # ---- reference ABI, numpy in / numpy out ----------------------------------------------
     def gpu_deconvolve(self, psi, holder, device=0, pad_mode="none"):
@@ -676,6 +716,10 @@ class EngineHandle:
                                                           C.byref(run),
                                                           stats.ctypes.data_as(C.POINTER(C.c_double))))
         return run.value, (stats[:run.value].copy() if tolerance >= 0 else np.zeros((0, 3)))
+
+    def set_regularization(self, kind, epsilon=0.0):
+        """mvn_engine_set_regularization: the regulariser of the iterate* calls that follow."""
+        self.b.check(self.b.l.mvn_engine_set_regularization(self.h, int(kind), float(epsilon)))
 
     def iterate_accelerated(self, iterations, lambda_, min_value, tolerance=-1.0):
         """mvn_engine_iterate_accelerated (blocking): (iterations run, [run, 3] statistics - empty with
