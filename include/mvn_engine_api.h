@@ -199,6 +199,36 @@ MVN_API int mvn_last_acceleration(double* alphas, int capacity);
 enum { MVN_REG_TIKHONOV = 0, MVN_REG_TV = 1 };
 MVN_API int mvn_set_regularization(int kind, double epsilon);
 MVN_API int mvn_get_regularization(int* kind, double* epsilon);
+/* The noise model of the Richardson-Lucy loop: a camera background per view, and the per-sweep likelihood.  An sCMOS
+ * frame is Poisson(H psi) + offset; with a background the offset is carried in the forward model instead of being
+ * deconvolved as light.  For view v, with `x` the inverse-transform output times `scale`, `b = background[v]` and `y`
+ * the image voxel widened to float32:
+ *   m = x + b        (float32, one correctly rounded add, never contracted with the multiply by scale;
+ *                     with b == 0 the add is NOT performed: m = x, -0 stays -0)
+ *   q = quotient_g(y, m, guard)                      (the existing quotient, unchanged)
+ *   term = y > 0 ? (y * logf(q) - y) + m : m - y     (float32, no contraction; q is the value written)
+ * Per (sweep k, view v) the statistics are summed in double over the voxels handed back to the caller - the stacks'
+ * window inside the padded volume; the whole volume under "none" and through the engine API:
+ *   D_kv = sum term      Y_kv = sum y      M_kv = sum m
+ * D is the Poisson negative log-likelihood of the estimate up to a constant (Csiszar's I-divergence).  The statistics
+ * are unweighted.  A NaN anywhere makes D_kv NaN (a poisoned convolution therefore gives NaN).  D_kv is measured
+ * against psi as it stands before view v's update of sweep k.
+ * mvn_set_background: count 0 or NULL: off (default); 1: the value for every view; otherwise a call whose num_views_
+ * != count is refused, psi untouched.  Values finite and >= 0, else error.  mvn_set_likelihood: 0 off (default),
+ * 1 on, else error.  With every background 0 and the likelihood off the loop is the plain one, launches and bits;
+ * otherwise the divide pass runs its noise-model form (the statistics are always summed then), the records are
+ * counted by mvn_deconvolve_memory* and the "auto" planner, the call waits for its rows, and no captured sweep graph
+ * (MVN_GRAPH) is used.  Process-wide, captured by inplace_gpu_deconvolve, mvn_deconvolve_submit and
+ * mvn_deconvolve_described at their start, like mvn_set_regularization.  Multi-device calls (MVN_DEVICES) with
+ * either switch on run on one device. */
+MVN_API int mvn_set_background(const float* values, int count);
+MVN_API int mvn_get_background(float* values, int capacity); /* returns count */
+MVN_API int mvn_set_likelihood(int mode);
+MVN_API int mvn_get_likelihood(int* mode);
+/* The last deconvolution this THREAD completed (as mvn_last_convergence): stats[3 * (k * V + v) ..] = {D, Y, M} of
+ * sweep k, view v, for the sweeps run (a tolerance stop of mvn_set_convergence ends them early), k * V + v <
+ * min(capacity_rows, rows); *num_views = V.  Returns the rows available (0 when both switches were off), < 0 on error. */
+MVN_API int mvn_last_likelihood(int* iterations_run, int* num_views, double* stats, int capacity_rows);
 /* Test and bench utilities of the TV pass.  mvn_tv_factor: t of the dense host volume psi[dims] into the dense host
  * volume t.  mvn_tv_time: ms[0] = milliseconds per launch of the pass on a resident volume of these extents (`reps`
  * launches between two stream events), ms[1] = the same for a plain streaming copy of the volume (one read, one
@@ -287,6 +317,13 @@ MVN_API int mvn_engine_iterate_accelerated(mvn_engine* e, int iterations, double
 /* the regulariser (mvn_set_regularization) of the mvn_engine_iterate* calls that follow on this engine.  Refused by
  * an engine in halo mode; mvn_engine_set_halo_hook and mvn_engine_compute_delta* are errors on a TV engine. */
 MVN_API int mvn_engine_set_regularization(mvn_engine* e, int kind, double epsilon);
+/* the noise model (mvn_set_background, mvn_set_likelihood) of the mvn_engine_iterate* calls that follow on this
+ * engine: background = one value per view, or NULL for none; likelihood 0 / 1.  Refused by an engine in halo mode;
+ * mvn_engine_set_halo_hook and mvn_engine_compute_delta* are errors on an engine in the mode (a background != 0 or the
+ * likelihood on).  mvn_engine_last_likelihood drains the stream and hands out the rows of the last iterate call as
+ * mvn_last_likelihood does (rows of V views each); returns the rows available. */
+MVN_API int mvn_engine_set_noise_model(mvn_engine* e, const float* background, int likelihood);
+MVN_API int mvn_engine_last_likelihood(mvn_engine* e, int* iterations_run, double* stats, int capacity_rows);
 /* simultaneous (Jacobi) mode, one step: delta = sum_v w_v (next_v - psi) over this engine's
  * views; the caller all-reduces the delta buffer across ranks, then applies it */
 MVN_API int mvn_engine_compute_delta(mvn_engine* e, double lambda, float min_value);

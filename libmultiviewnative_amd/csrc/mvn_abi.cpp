@@ -169,8 +169,36 @@ static void check_tv_lambda(int kind, double lambda) {
   if (kind == 1 && !(lambda >= 0. && lambda < 1. / 12.))
     throw std::invalid_argument("total-variation regularisation needs 0 <= lambda_ < 1/12");
 }
+// ---- noise model (mvn_set_background, mvn_set_likelihood): captured at the start of a call, like the regulariser ----
+struct NoiseMode {
+  std::vector<float> background;  // empty: off; one value: every view; else one per view
+  int likelihood = 0;
+  bool on() const {
+    if (likelihood) return true;
+    for (float b : background)
+      if (b != 0.f) return true;
+    return false;
+  }
+};
+static std::mutex g_nm_mu;
+static NoiseMode g_nm;
+static NoiseMode current_nm() {
+  std::lock_guard<std::mutex> lk(g_nm_mu);
+  return g_nm;
+}
+static thread_local int t_call_nm = -1;  // the call this thread runs has the noise model on (1) or off (0); -1 outside a call
+static bool call_nm_on() { return t_call_nm < 0 ? current_nm().on() : t_call_nm != 0; }
+// a call whose view count the per-view backgrounds do not match: refused before psi is touched
+static void check_background_count(const NoiseMode& nm, int V) {
+  const size_t n = nm.background.size();
+  if (n > 1 && n != (size_t)V)
+    throw std::invalid_argument(std::to_string(n) + " background values (mvn_set_background) for a call of " +
+                                std::to_string(V) + " views");
+}
 struct ConvRecord {
   int iterations_run = 0;
+  std::vector<double> like;    // noise model on: {D, Y, M} per (sweep run, view)
+  int like_views = 0;
   std::vector<double> rows;    // {S, M, P} per sweep run
   std::vector<double> alphas;  // acceleration on: a_k per sweep run
 };
@@ -191,6 +219,7 @@ static MemoryQuery memory_query(const shape_t& ext, const workspace& input, size
   q.stats_rows = call_tolerance() >= 0. ? std::max(input.num_iterations_, 1) : 0;
   q.accel_rows = call_accel() ? std::max(input.num_iterations_, 1) : 0;
   q.tv = call_reg_kind() == 1 && input.lambda_ > 0.;
+  q.nm_rows = call_nm_on() ? std::max(input.num_iterations_, 1) : 0;
   q.kernels = call_kernels(input);
   return q;
 }
@@ -686,8 +715,10 @@ struct LoopMode {
   double tol = -1.;
   int accel = 0;
   RegMode reg;
+  NoiseMode nm;
   static LoopMode current() {
     LoopMode m;
+    m.nm = current_nm();
     m.tol = g_conv_tol.load();
     m.accel = g_accel.load();
     m.reg = current_reg();
@@ -703,15 +734,19 @@ static void deconvolve_call(const workspace& input, const CallStacks& cs, int de
   conv->iterations_run = 0;
   conv->rows.clear();
   conv->alphas.clear();
+  conv->like.clear();
+  conv->like_views = 0;
   const bool tv = mode.reg.kind == 1;
+  const bool nm = mode.nm.on();
   struct LoopScope {  // (the memory model of this call counts the statistics, acceleration and TV buffers: memory_query)
-    LoopScope(double t, int a, int r) { t_call_tol = t, t_call_accel = a, t_call_reg_kind = r; }
-    ~LoopScope() { t_call_tol = NAN, t_call_accel = -1, t_call_reg_kind = -1; }
-  } loop_scope(tol, accel, mode.reg.kind);
+    LoopScope(double t, int a, int r, int n) { t_call_tol = t, t_call_accel = a, t_call_reg_kind = r, t_call_nm = n; }
+    ~LoopScope() { t_call_tol = NAN, t_call_accel = -1, t_call_reg_kind = -1, t_call_nm = -1; }
+  } loop_scope(tol, accel, mode.reg.kind, nm ? 1 : 0);
   {
     const int V = input.num_views_;
     if (V == 0 || input.num_iterations_ <= 0) return;  // 0 iterations returns psi unchanged
     check_tv_lambda(mode.reg.kind, input.lambda_);
+    check_background_count(mode.nm, V);
     shape_t dims, ext;
     int off[3] = {0, 0, 0};
     if (lane == 0) {  // (the second lane belongs to the block pipeline of mvn_deconvolve_submit)
@@ -730,7 +765,9 @@ static void deconvolve_call(const workspace& input, const CallStacks& cs, int de
       if (!devs.empty() && accel && trace_on()) std::printf("[lmvn::trace] MVN_DEVICES: acceleration on - one device\n");
       // ... and no total variation
       if (!devs.empty() && tv && trace_on()) std::printf("[lmvn::trace] MVN_DEVICES: total variation on - one device\n");
-      if (plain && tol < 0. && !accel && !tv) {
+      // ... and no noise model
+      if (!devs.empty() && nm && trace_on()) std::printf("[lmvn::trace] MVN_DEVICES: noise model on - one device\n");
+      if (plain && tol < 0. && !accel && !tv && !nm) {
         call_extents(input, pad_mode, -1, &dims, &ext, off);  // (the slabs run on plans of their own extents)
         if (multi_device_call((imageType*)cs.psi.ptr, input, dims, ext, off, pad_mode, devs)) return;
       }
@@ -751,6 +788,7 @@ static void deconvolve_call(const workspace& input, const CallStacks& cs, int de
     Engine& eng = *eng_owner;
     eng.begin_call();
     eng.set_regularization(mode.reg.kind, mode.reg.epsilon);
+    eng.set_noise_model(mode.nm.background.data(), (int)mode.nm.background.size(), mode.nm.likelihood != 0);
     eng.set_image_storage(cs.storage);
     eng.plan_image_types(cs.keep_u16);
     // stacks are embedded into / cropped out of the padded volume by the transfers themselves
@@ -774,6 +812,7 @@ static void deconvolve_call(const workspace& input, const CallStacks& cs, int de
       eng.set_psi(cs.psi);
       conv->iterations_run = eng.iterate(input.num_iterations_, input.lambda_, input.minValue_, tol, &conv->rows, accel,
                                          accel ? &conv->alphas : nullptr);
+      conv->like = eng.last_likelihood(), conv->like_views = V;
       eng.sync();
       eng.get_psi(cs.psi);
       give_back_engine(key, std::move(eng_owner));
@@ -827,6 +866,7 @@ static void deconvolve_call(const workspace& input, const CallStacks& cs, int de
     try {
       conv->iterations_run = eng.iterate(input.num_iterations_, input.lambda_, input.minValue_, tol, &conv->rows, accel,
                                          accel ? &conv->alphas : nullptr);
+      conv->like = eng.last_likelihood(), conv->like_views = V;
       if (conv->iterations_run < input.num_iterations_) eng.end_streaming();  // (an early stop)
     } catch (...) {
       main_err = std::current_exception();
@@ -1071,6 +1111,58 @@ int mvn_get_regularization(int* kind, double* epsilon) {
     *kind = r.kind;
     *epsilon = r.epsilon;
   });
+}
+
+int mvn_set_background(const float* values, int count) {
+  return guarded("mvn_set_background", [&] {
+    if (count < 0) throw std::invalid_argument("negative count");
+    if (!values) count = 0;
+    for (int i = 0; i < count; ++i)
+      if (!(values[i] >= 0.f && std::isfinite(values[i])))
+        throw std::invalid_argument("background values must be finite and >= 0");
+    std::lock_guard<std::mutex> lk(g_nm_mu);
+    g_nm.background.assign(values, values + count);
+  });
+}
+
+int mvn_get_background(float* values, int capacity) {
+  int count = 0;
+  const int rc = guarded("mvn_get_background", [&] {
+    if (capacity < 0 || (capacity > 0 && !values)) throw std::invalid_argument("bad background buffer");
+    const NoiseMode m = current_nm();
+    count = (int)m.background.size();
+    for (int i = 0; i < std::min(count, capacity); ++i) values[i] = m.background[(size_t)i];
+  });
+  return rc < 0 ? rc : count;
+}
+
+int mvn_set_likelihood(int mode) {
+  return guarded("mvn_set_likelihood", [&] {
+    if (mode != 0 && mode != 1) throw std::invalid_argument("likelihood mode must be 0 (off) or 1 (on)");
+    std::lock_guard<std::mutex> lk(g_nm_mu);
+    g_nm.likelihood = mode;
+  });
+}
+
+int mvn_get_likelihood(int* mode) {
+  return guarded("mvn_get_likelihood", [&] {
+    if (!mode) throw std::invalid_argument("null mode");
+    *mode = current_nm().likelihood;
+  });
+}
+
+int mvn_last_likelihood(int* iterations_run, int* num_views, double* stats, int capacity_rows) {
+  int rows = 0;
+  const int rc = guarded("mvn_last_likelihood", [&] {
+    if (capacity_rows < 0 || (capacity_rows > 0 && !stats)) throw std::invalid_argument("bad statistics buffer");
+    const ConvRecord& c = t_last_conv;
+    if (iterations_run) *iterations_run = c.iterations_run;
+    if (num_views) *num_views = c.like_views;
+    rows = (int)(c.like.size() / 3);
+    const size_t n = 3 * (size_t)std::min(rows, capacity_rows);
+    if (n) std::memcpy(stats, c.like.data(), n * sizeof(double));
+  });
+  return rc < 0 ? rc : rows;
 }
 
 long mvn_tv_launch_count(void) { return be::tv_launch_count(); }
@@ -2061,6 +2153,29 @@ int mvn_engine_iterate_accelerated(mvn_engine* e, int iterations, double lambda,
 
 int mvn_engine_set_regularization(mvn_engine* e, int kind, double epsilon) {
   MVN_ENGINE_CALL("mvn_engine_set_regularization", E.set_regularization(kind, epsilon));
+}
+
+int mvn_engine_set_noise_model(mvn_engine* e, const float* background, int likelihood) {
+  MVN_ENGINE_CALL("mvn_engine_set_noise_model", {
+    if (likelihood != 0 && likelihood != 1) throw std::invalid_argument("likelihood mode must be 0 (off) or 1 (on)");
+    E.set_noise_model(background, background ? E.num_views() : 0, likelihood != 0);
+  });
+}
+
+int mvn_engine_last_likelihood(mvn_engine* e, int* iterations_run, double* stats, int capacity_rows) {
+  int rows = 0;
+  const int rc = guarded("mvn_engine_last_likelihood", [&] {
+    if (!e || !e->impl) throw std::invalid_argument("null engine");
+    if (capacity_rows < 0 || (capacity_rows > 0 && !stats)) throw std::invalid_argument("bad statistics buffer");
+    Engine& E = *e->impl;
+    E.sync();
+    const std::vector<double>& r = E.last_likelihood();
+    if (iterations_run) *iterations_run = E.last_likelihood_sweeps();
+    rows = (int)(r.size() / 3);
+    const size_t n = 3 * (size_t)std::min(rows, capacity_rows);
+    if (n) std::memcpy(stats, r.data(), n * sizeof(double));
+  });
+  return rc < 0 ? rc : rows;
 }
 
 int mvn_engine_compute_delta(mvn_engine* e, double lambda, float min_value) {

@@ -99,6 +99,8 @@ void launch_rows_c2r_r2c(const RowsParams& p, long ntiles, int nthreads, size_t 
 // statistics of one sweep: records of `nviews` view updates (view v at rec + 3 v cap) -> out[0..2] = {S, M, P}
 void launch_convergence_reduce(const double* rec, const unsigned* counts, int nviews, long cap, double* out,
                                stream_t s);
+// noise model: the records of `nviews` divide passes (view v at rec + 3 v cap) -> out[3 v ..] = {D, Y, M} of view v
+void launch_nm_reduce(const double* rec, const unsigned* counts, int nviews, long cap, double* out, stream_t s);
 long split_launch_count();
 // vector extrapolation between sweeps (mvn_extrapolate.hpp): pass A with its records, the reduction of `nrec` records
 // into the device word *alpha, pass B

@@ -186,6 +186,8 @@ static void emu_wave_rows_mode(const RowsParams& p) {
   switch (p.epi.mode) {
     case MVN_EPI_DIVIDE: emu_wave_rows_run<MODE, MVN_EPI_DIVIDE>(p); break;
     case MVN_EPI_DIVIDE_U16: emu_wave_rows_run<MODE, MVN_EPI_DIVIDE_U16>(p); break;
+    case MVN_EPI_DIVIDE_NM: emu_wave_rows_run<MODE, MVN_EPI_DIVIDE_NM>(p); break;
+    case MVN_EPI_DIVIDE_NM_U16: emu_wave_rows_run<MODE, MVN_EPI_DIVIDE_NM_U16>(p); break;
     case MVN_EPI_UPDATE: emu_wave_rows_run<MODE, MVN_EPI_UPDATE>(p); break;
     case MVN_EPI_UPDATE_STATS: emu_wave_rows_run<MODE, MVN_EPI_UPDATE_STATS>(p); break;
     case MVN_EPI_UPDATE_TV: emu_wave_rows_run<MODE, MVN_EPI_UPDATE_TV>(p); break;
@@ -213,6 +215,7 @@ static void emu_rows_lines(const RowsParams& p, long ntiles, int kind) {
   constexpr int H = 256;
   typedef FxCtx<FxRowsRegs<H>, FxRowsCfg<H>::NT> Ctx;
   typedef FxCtx<FxRowsStatRegs<H>, FxRowsCfg<H>::NT> SCtx;  // (MVN_EPI_UPDATE_STATS)
+  typedef FxCtx<FxRowsNmRegs<H>, FxRowsCfg<H>::NT> NCtx;    // (MVN_EPI_DIVIDE_NM)
   if (!fx_rows_lines_ok<H>() || !p.fixed || p.h != H || p.C != H || !p.nyq_packed || p.lines_d1 < 1 ||
       p.lines_d1 % FxRowsCfg<H>::T || p.row_base % FxRowsCfg<H>::T || p.rows != ntiles * FxRowsCfg<H>::T)
     throw std::invalid_argument("mvn: line-layout last-axis pass outside its range");
@@ -221,6 +224,7 @@ static void emu_rows_lines(const RowsParams& p, long ntiles, int kind) {
     std::vector<char> lds(sizeof(cfloat) * FxRowsCfg<H>::lds_cfloats + 64);
     std::unique_ptr<Ctx> ctx(new Ctx());
     std::unique_ptr<SCtx> sctx(new SCtx());
+    std::unique_ptr<NCtx> nctx(new NCtx());
 #pragma omp for schedule(static)
     for (long t = 0; t < ntiles; ++t) {
       cfloat* l = (cfloat*)lds.data();
@@ -230,6 +234,8 @@ static void emu_rows_lines(const RowsParams& p, long ntiles, int kind) {
         switch (p.epi.mode) {
           case MVN_EPI_DIVIDE: fx_rows_run<H, 1, MVN_EPI_DIVIDE, Ctx, true>(p, t, ntiles, l, *ctx); break;
           case MVN_EPI_DIVIDE_U16: fx_rows_run<H, 1, MVN_EPI_DIVIDE_U16, Ctx, true>(p, t, ntiles, l, *ctx); break;
+          case MVN_EPI_DIVIDE_NM: fx_rows_run_nm<H, 1, MVN_EPI_DIVIDE_NM, NCtx, true>(p, t, ntiles, l, *nctx); break;
+          case MVN_EPI_DIVIDE_NM_U16: fx_rows_run_nm<H, 1, MVN_EPI_DIVIDE_NM_U16, NCtx, true>(p, t, ntiles, l, *nctx); break;
           case MVN_EPI_UPDATE: fx_rows_run<H, 1, MVN_EPI_UPDATE, Ctx, true>(p, t, ntiles, l, *ctx); break;
           case MVN_EPI_UPDATE_STATS: fx_rows_run_stats<H, 1, SCtx, true>(p, t, ntiles, l, *sctx); break;
           case MVN_EPI_UPDATE_TV: fx_rows_run<H, 1, MVN_EPI_UPDATE_TV, Ctx, true>(p, t, ntiles, l, *ctx); break;
@@ -241,6 +247,8 @@ static void emu_rows_lines(const RowsParams& p, long ntiles, int kind) {
         switch (p.epi.mode) {
           case MVN_EPI_DIVIDE: fx_rows_run<H, 2, MVN_EPI_DIVIDE, Ctx, true>(p, t, ntiles, l, *ctx); break;
           case MVN_EPI_DIVIDE_U16: fx_rows_run<H, 2, MVN_EPI_DIVIDE_U16, Ctx, true>(p, t, ntiles, l, *ctx); break;
+          case MVN_EPI_DIVIDE_NM: fx_rows_run_nm<H, 2, MVN_EPI_DIVIDE_NM, NCtx, true>(p, t, ntiles, l, *nctx); break;
+          case MVN_EPI_DIVIDE_NM_U16: fx_rows_run_nm<H, 2, MVN_EPI_DIVIDE_NM_U16, NCtx, true>(p, t, ntiles, l, *nctx); break;
           case MVN_EPI_UPDATE: fx_rows_run<H, 2, MVN_EPI_UPDATE, Ctx, true>(p, t, ntiles, l, *ctx); break;
           case MVN_EPI_UPDATE_STATS: fx_rows_run_stats<H, 2, SCtx, true>(p, t, ntiles, l, *sctx); break;
           case MVN_EPI_UPDATE_TV: fx_rows_run<H, 2, MVN_EPI_UPDATE_TV, Ctx, true>(p, t, ntiles, l, *ctx); break;
@@ -296,18 +304,22 @@ template <int H>
 static void emu_rows_fused(const RowsParams& p, long ntiles) {
   typedef FxCtx<FxRowsRegs<H>, FxRowsCfg<H>::NT> Ctx;
   typedef FxCtx<FxRowsStatRegs<H>, FxRowsCfg<H>::NT> SCtx;  // (MVN_EPI_UPDATE_STATS)
+  typedef FxCtx<FxRowsNmRegs<H>, FxRowsCfg<H>::NT> NCtx;    // (MVN_EPI_DIVIDE_NM)
   const long grid = emu_rows_grid<H>(ntiles);
 #pragma omp parallel
   {
     std::vector<char> lds(sizeof(cfloat) * FxRowsCfg<H>::lds_cfloats + 64);
     std::unique_ptr<Ctx> ctx(new Ctx());
     std::unique_ptr<SCtx> sctx(new SCtx());
+    std::unique_ptr<NCtx> nctx(new NCtx());
 #pragma omp for schedule(static)
     for (long t = 0; t < grid; ++t) {
       cfloat* l = (cfloat*)lds.data();
       switch (p.epi.mode) {
         case MVN_EPI_DIVIDE: fx_rows_run<H, 2, MVN_EPI_DIVIDE>(p, t, grid, l, *ctx); break;
         case MVN_EPI_DIVIDE_U16: fx_rows_run<H, 2, MVN_EPI_DIVIDE_U16>(p, t, grid, l, *ctx); break;
+        case MVN_EPI_DIVIDE_NM: fx_rows_run_nm<H, 2, MVN_EPI_DIVIDE_NM, NCtx>(p, t, grid, l, *nctx); break;
+        case MVN_EPI_DIVIDE_NM_U16: fx_rows_run_nm<H, 2, MVN_EPI_DIVIDE_NM_U16, NCtx>(p, t, grid, l, *nctx); break;
         case MVN_EPI_UPDATE: fx_rows_run<H, 2, MVN_EPI_UPDATE>(p, t, grid, l, *ctx); break;
         case MVN_EPI_UPDATE_STATS: fx_rows_run_stats<H, 2, SCtx>(p, t, grid, l, *sctx); break;
         case MVN_EPI_UPDATE_TV: fx_rows_run<H, 2, MVN_EPI_UPDATE_TV>(p, t, grid, l, *ctx); break;
@@ -322,7 +334,7 @@ void launch_rows_c2r_r2c(const RowsParams& p0, long ntiles, int, size_t lds_byte
   RowsParams p = p0;
   mvn_arm_poison(p.epi);  // (the device kernels do this at their entry)
   if (p.lines) return emu_rows_lines(p, ntiles, 2);
-  if (emu_wave_rows(p, mvn_epi_math(p.epi.mode) == MVN_EPI_DIVIDE ? 4 : 8)) return emu_wave_rows_mode<MVN_WR_C2R_R2C>(p);
+  if (emu_wave_rows(p, mvn_epi_divides(p.epi.mode) ? 4 : 8)) return emu_wave_rows_mode<MVN_WR_C2R_R2C>(p);
   if (!p.fixed) {  // run-time-radix form of the fused pass (any even d2)
 #pragma omp parallel
     {
@@ -336,6 +348,10 @@ void launch_rows_c2r_r2c(const RowsParams& p0, long ntiles, int, size_t lds_byte
           MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, true, true, false, true>(p, t, 0, 1, l)));
         } else if (p.epi.mode == MVN_EPI_UPDATE_TV) {
           MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, true, false, false, true>(p, t, 0, 1, l)));
+        } else if (p.epi.mode == MVN_EPI_DIVIDE_NM) {
+          MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, true, false, false, false, true>(p, t, 0, 1, l)));
+        } else if (p.epi.mode == MVN_EPI_DIVIDE_NM_U16) {
+          MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, true, false, true, false, true>(p, t, 0, 1, l)));
         } else if (p.epi.mode == MVN_EPI_DIVIDE_U16) {
           MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, true, false, true>(p, t, 0, 1, l)));
         } else {
@@ -357,12 +373,14 @@ template <int H>
 static void emu_rows_fixed(const RowsParams& p, long ntiles, bool r2c) {
   typedef FxCtx<FxRowsRegs<H>, FxRowsCfg<H>::NT> Ctx;
   typedef FxCtx<FxRowsStatRegs<H>, FxRowsCfg<H>::NT> SCtx;  // (MVN_EPI_UPDATE_STATS)
+  typedef FxCtx<FxRowsNmRegs<H>, FxRowsCfg<H>::NT> NCtx;    // (MVN_EPI_DIVIDE_NM)
   const long grid = emu_rows_grid<H>(ntiles);
 #pragma omp parallel
   {
     std::vector<char> lds(sizeof(cfloat) * FxRowsCfg<H>::lds_cfloats + 64);
     std::unique_ptr<Ctx> ctx(new Ctx());
     std::unique_ptr<SCtx> sctx(new SCtx());
+    std::unique_ptr<NCtx> nctx(new NCtx());
 #pragma omp for schedule(static)
     for (long t = 0; t < grid; ++t) {
       cfloat* l = (cfloat*)lds.data();
@@ -372,6 +390,8 @@ static void emu_rows_fixed(const RowsParams& p, long ntiles, bool r2c) {
         switch (p.epi.mode) {
           case MVN_EPI_DIVIDE: fx_rows_run<H, 1, MVN_EPI_DIVIDE>(p, t, grid, l, *ctx); break;
           case MVN_EPI_DIVIDE_U16: fx_rows_run<H, 1, MVN_EPI_DIVIDE_U16>(p, t, grid, l, *ctx); break;
+          case MVN_EPI_DIVIDE_NM: fx_rows_run_nm<H, 1, MVN_EPI_DIVIDE_NM, NCtx>(p, t, grid, l, *nctx); break;
+          case MVN_EPI_DIVIDE_NM_U16: fx_rows_run_nm<H, 1, MVN_EPI_DIVIDE_NM_U16, NCtx>(p, t, grid, l, *nctx); break;
           case MVN_EPI_UPDATE: fx_rows_run<H, 1, MVN_EPI_UPDATE>(p, t, grid, l, *ctx); break;
           case MVN_EPI_UPDATE_STATS: fx_rows_run_stats<H, 1, SCtx>(p, t, grid, l, *sctx); break;
           case MVN_EPI_UPDATE_TV: fx_rows_run<H, 1, MVN_EPI_UPDATE_TV>(p, t, grid, l, *ctx); break;
@@ -522,6 +542,18 @@ void launch_rows_c2r(const RowsParams& p0, bool even, long ntiles, int, size_t l
         } else {
           MVN_DISPATCH_T(p.T, (rows_c2r_odd_body<TT, false, false, true>(p, t, 0, 1, l)));
         }
+      } else if (p.epi.mode == MVN_EPI_DIVIDE_NM) {
+        if (even) {
+          MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, false, false, false, false, true>(p, t, 0, 1, l)));
+        } else {
+          MVN_DISPATCH_T(p.T, (rows_c2r_odd_body<TT, false, false, false, true>(p, t, 0, 1, l)));
+        }
+      } else if (p.epi.mode == MVN_EPI_DIVIDE_NM_U16) {
+        if (even) {
+          MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, false, false, true, false, true>(p, t, 0, 1, l)));
+        } else {
+          MVN_DISPATCH_T(p.T, (rows_c2r_odd_body<TT, false, true, false, true>(p, t, 0, 1, l)));
+        }
       } else if (p.epi.mode == MVN_EPI_DIVIDE_U16) {
         if (even) {
           MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, false, false, true>(p, t, 0, 1, l)));
@@ -541,6 +573,11 @@ void launch_convergence_reduce(const double* rec, const unsigned* counts, int nv
                                stream_t) {
   double lds[3];
   mvn_convergence_reduce_body(rec, counts, nviews, cap, out, lds, 0, 1);
+}
+
+void launch_nm_reduce(const double* rec, const unsigned* counts, int nviews, long cap, double* out, stream_t) {
+  double lds[3];
+  for (long v = 0; v < nviews; ++v) mvn_nm_reduce_body(rec + 3 * v * cap, counts + v, cap, out + 3 * v, lds, 0, 1);
 }
 
 void launch_strided(int mode, const StridedParams& p, long nblocks, int, size_t lds_bytes,

@@ -381,7 +381,7 @@ void Plan3D::rows_c2r(const cfloat* in, const cfloat* in_nyq, float* out_real,
   EpilogueParams epi = epi_all;
   const long eoff = row0 * L.RP;
   // (the offsets below are in floats: a uint16 view is only ever divided by whole-volume launches, Engine::set_halo_hook)
-  if (epi.mode == MVN_EPI_DIVIDE_U16 && row0 != 0) throw std::logic_error("mvn: a row range on a uint16 image volume");
+  if (mvn_epi_u16(epi.mode) && row0 != 0) throw std::logic_error("mvn: a row range on a uint16 image volume");
   if (epi.view) epi.view += eoff;
   if (epi.psi) epi.psi += eoff;
   if (epi.weights) epi.weights += eoff;
@@ -436,7 +436,7 @@ void Plan3D::rows_c2r_r2c(cfloat* data, cfloat* nyq, const EpilogueParams& epi_a
   EpilogueParams epi = epi_all;
   const long eoff = row0 * L.RP;
   // (the offsets below are in floats: a uint16 view is only ever divided by whole-volume launches, Engine::set_halo_hook)
-  if (epi.mode == MVN_EPI_DIVIDE_U16 && row0 != 0) throw std::logic_error("mvn: a row range on a uint16 image volume");
+  if (mvn_epi_u16(epi.mode) && row0 != 0) throw std::logic_error("mvn: a row range on a uint16 image volume");
   if (epi.view) epi.view += eoff;
   if (epi.psi) epi.psi += eoff;
   if (epi.weights) epi.weights += eoff;
@@ -801,6 +801,7 @@ Engine::~Engine() {
   } catch (...) {
   }
   stats_free();
+  nm_free();
   for (size_t v = 0; v < views_.size(); ++v) {
     if (stream_pos_[v] < 0) {  // (a streamed view's pointers are borrowed from the ring during its update)
       be::dfree(views_[v].image);
@@ -1812,6 +1813,11 @@ size_t Engine::memory_need(const MemoryQuery& q, const FormRule& rule) {
     add(3 * sizeof(double) * (size_t)q.stats_rows, 1);
   }
   if (q.tv) add(mb, 1);  // the total-variation factor volume (Engine::set_regularization)
+  if (q.nm_rows > 0) {   // noise model (Engine::iterate): records, counts, rows
+    add(3 * sizeof(double) * (size_t)stats_cap(L) * (size_t)V, 1);
+    add(sizeof(unsigned) * (size_t)V, 1);
+    add(3 * sizeof(double) * (size_t)q.nm_rows * (size_t)V, 1);
+  }
   if (q.accel_rows > 0) {  // vector extrapolation (Engine::iterate)
     add(mb, 3);  // x_prev, g, the saved y
     add(2 * sizeof(double) * (size_t)accel_records(L), 1);
@@ -1895,6 +1901,13 @@ void Engine::conv_pair(int v, double lambda, float min_value, int final_mode, in
   e1.scale = 1.f;  // 1/N already lives in the PSF spectrum
   divide_epilogue(e1, s);
   e1.guard_zero_view = quotient_guard_ ? 1 : 0;
+  // noise model: the same pass with the view's background in the forward model and the statistics of the window
+  const bool nm = nm_on_ && final_mode == MVN_EPI_UPDATE;
+  const MvnStatsParams st1 = nm ? nm_stats_for(v) : MvnStatsParams();
+  if (nm) {
+    e1.mode = e1.mode == MVN_EPI_DIVIDE_U16 ? MVN_EPI_DIVIDE_NM_U16 : MVN_EPI_DIVIDE_NM;
+    e1.background = nm_background_.empty() ? 0.f : nm_background_[(size_t)v];
+  }
 
   EpilogueParams e2;
   std::memset(&e2, 0, sizeof(e2));
@@ -1961,12 +1974,13 @@ void Engine::conv_pair(int v, double lambda, float min_value, int final_mode, in
     cfloat* wnq = wn();
     const bool ln = lines_;
     RowsProducer p2 = [=](long r0, long nr) {
+      const MvnStatsParams* s1 = nm ? &st1 : nullptr;
       if (ln) {
-        Pp->rows_c2r_r2c((cfloat*)w, nullptr, e1, st, prof, r0, nr, true);
+        Pp->rows_c2r_r2c((cfloat*)w, nullptr, e1, st, prof, r0, nr, true, s1);
       } else if (fuse) {
-        Pp->rows_c2r_r2c((cfloat*)w, wnq, e1, st, prof, r0, nr);
+        Pp->rows_c2r_r2c((cfloat*)w, wnq, e1, st, prof, r0, nr, false, s1);
       } else {
-        Pp->rows_c2r((const cfloat*)w, wnq, w, e1, st, prof, r0, nr);
+        Pp->rows_c2r((const cfloat*)w, wnq, w, e1, st, prof, r0, nr, false, s1);
         Pp->rows_r2c(w, (cfloat*)w, wnq, st, prof, r0, nr);
       }
     };
@@ -2033,6 +2047,52 @@ MvnStatsParams Engine::stats_for(int v) const {
   p.count = stat_count_ + v;
   p.cap = stat_cap_;
   return p;
+}
+
+// the same window for the noise-model statistics of view v's divide pass
+MvnStatsParams Engine::nm_stats_for(int v) const {
+  MvnStatsParams p = stats_for(v);
+  p.rec = nm_rec_ + 3 * (size_t)nm_cap_ * (size_t)v;
+  p.count = nm_count_ + v;
+  p.cap = nm_cap_;
+  return p;
+}
+
+void Engine::nm_free() {
+  be::dfree(nm_rec_);
+  be::dfree(nm_count_);
+  be::dfree(nm_out_);
+  nm_rec_ = nm_out_ = nullptr;
+  nm_count_ = nullptr;
+  nm_on_ = false;
+}
+
+bool Engine::noise_model_on() const {
+  if (nm_like_) return true;
+  for (float b : nm_background_)
+    if (b != 0.f) return true;
+  return false;
+}
+
+void Engine::refuse_nm(const char* what) const {
+  if (noise_model_on()) throw std::logic_error(std::string("mvn: ") + what + " with a noise model (background or likelihood)");
+}
+
+void Engine::set_noise_model(const float* background, int count, bool likelihood) {
+  const int V = (int)views_.size();
+  if (count < 0 || (count > 0 && !background)) throw std::invalid_argument("mvn: bad background array");
+  if (count != 0 && count != 1 && count != V)
+    throw std::invalid_argument("mvn: " + std::to_string(count) + " background values for " + std::to_string(V) + " views");
+  for (int i = 0; i < count; ++i)
+    if (!(background[i] >= 0.f && std::isfinite(background[i])))
+      throw std::invalid_argument("mvn: background values must be finite and >= 0");
+  bool on = likelihood;
+  for (int i = 0; i < count; ++i) on = on || background[i] != 0.f;
+  if (on && halo_fn_)
+    throw std::logic_error("mvn: no noise model on a slab of a multi-device group (halo mode)");
+  nm_background_.clear();
+  for (int v = 0; v < V && count > 0; ++v) nm_background_.push_back(background[count == 1 ? 0 : v]);
+  nm_like_ = likelihood;
 }
 
 void Engine::stats_free() {
@@ -2114,6 +2174,10 @@ int Engine::iterate(int iterations, double lambda, float min_value, double toler
   if (alphas) alphas->clear();
   const bool st_on = tolerance >= 0.;
   const bool ac_on = accel == 1 && iterations > 0;
+  nm_rows_.clear();
+  nm_ran_ = 0;
+  const bool nm_on = noise_model_on() && iterations > 0;
+  if (nm_on && halo_fn_) throw std::logic_error("mvn: no noise model on a slab of a multi-device group (halo mode)");
   tv_on_ = false;
   if (reg_kind_ == 1) {
     if (halo_fn_) throw std::logic_error("mvn: no total-variation regularisation on a slab of a multi-device group (halo mode)");
@@ -2137,6 +2201,15 @@ int Engine::iterate(int iterations, double lambda, float min_value, double toler
     stats_on_ = true;
   }
   try {
+    if (nm_on) {
+      const int V = (int)views_.size();
+      nm_free();
+      nm_cap_ = stats_cap(plan_->L);
+      nm_rec_ = (double*)be::dmalloc(3 * sizeof(double) * (size_t)nm_cap_ * (size_t)V);
+      nm_count_ = (unsigned*)be::dmalloc(sizeof(unsigned) * (size_t)V);
+      nm_out_ = (double*)be::dmalloc(3 * sizeof(double) * (size_t)iterations * (size_t)V);
+      nm_on_ = true;
+    }
     if (ac_on) {
       accel_free();
       accel_on_ = true;
@@ -2148,19 +2221,21 @@ int Engine::iterate(int iterations, double lambda, float min_value, double toler
     }
     const int ran = iterate_sweeps(iterations, lambda, min_value, tolerance, stats, alphas);
     if (st_on) stats_free();
+    if (nm_on) nm_free();  // (iterate_sweeps has waited for the stream)
     if (ac_on) {  // (the state lives for the call: the passes that use it have to be done before it goes)
       be::stream_sync(stream_);
       accel_free();
     }
     return ran;
   } catch (...) {
-    if (st_on || ac_on) {
+    if (st_on || ac_on || nm_on) {
       try {
         be::stream_sync(stream_);
       } catch (...) {
       }
       stats_free();
       accel_free();
+      nm_free();
     }
     throw;
   }
@@ -2179,7 +2254,8 @@ int Engine::iterate_sweeps(int iterations, double lambda, float min_value, doubl
   // (a captured sweep holds buffer addresses: the two work volumes must be back in their roles after it,
   // i.e. the sweep must contain an even number of direct dim0 legs)
   bool use_graph = graphs_on && !halo_fn_ && iterations >= 3 && !prof_.enabled && plan_->can_fuse_rows() &&
-                   plan_->main_bytes() <= graph_max_bytes && streamed_order_.empty() && !stats_on_ && !accel_on_;
+                   plan_->main_bytes() <= graph_max_bytes && streamed_order_.empty() && !stats_on_ && !accel_on_ &&
+                   !nm_on_;  // (a captured sweep would bake in the backgrounds and the records' addresses)
   std::vector<double> rows;  // {S, M, P} of the sweeps run
   int ran = 0;
   if (accel_on_) be::d2d(accel_ysave_, psi_, plan_->main_bytes(), stream_);  // y_0
@@ -2241,6 +2317,7 @@ int Engine::iterate_sweeps(int iterations, double lambda, float min_value, doubl
       if (streamed) ring_release(views_[(size_t)v]);
     }
     ran = it + 1;
+    if (nm_on_) be::launch_nm_reduce(nm_rec_, nm_count_, V, nm_cap_, nm_out_ + 3 * (size_t)V * (size_t)it, stream_);
     if (stats_on_) {
       be::launch_convergence_reduce(stat_rec_, stat_count_, V, stat_cap_, stat_out_ + 3 * (size_t)it, stream_);
       if (tolerance > 0.) {
@@ -2263,6 +2340,12 @@ int Engine::iterate_sweeps(int iterations, double lambda, float min_value, doubl
     be::stream_sync(stream_);
   }
   if (stats) *stats = std::move(rows);
+  if (nm_on_ && ran > 0) {  // {D, Y, M} per (sweep, view) of the sweeps run
+    nm_rows_.resize(3 * (size_t)V * (size_t)ran);
+    be::d2h(nm_rows_.data(), nm_out_, nm_rows_.size() * sizeof(double), stream_);
+    be::stream_sync(stream_);
+    nm_ran_ = ran;
+  }
   if (accel_on_ && alphas) {  // a_1 .. a_ran; the last sweep run was not followed by an extrapolation
     alphas->assign((size_t)ran, 0.);
     if (ran > 1) {
@@ -2301,6 +2384,7 @@ void Engine::set_halo_planes(int planes, bool split) {
 void Engine::set_halo_hook(halo_fn_t fn, void* user, bool drain, bool post) {
   if (fn) {
     refuse_tv("no halo hook on an engine");
+    refuse_nm("no halo hook on an engine");
     // halo mode divides ranges of rows, whose operand offsets are in floats (Plan3D::rows_c2r*)
     if (u16_views() > 0)
       throw std::invalid_argument("mvn: no halo hook on an engine that holds a uint16 image volume (image storage mode 1)");
@@ -2394,6 +2478,7 @@ void Engine::delta_chunk_range(int c, int n, size_t* first_float, size_t* n_floa
 
 void Engine::compute_delta_head(double lambda, float min_value) {
   refuse_tv("no simultaneous (delta) step on an engine");
+  refuse_nm("no simultaneous (delta) step on an engine");
   be::set_device(device_);
   delta_ptr();
   tail_pending_ = false;

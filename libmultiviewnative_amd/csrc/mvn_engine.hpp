@@ -309,6 +309,7 @@ struct MemoryQuery {
   int stats_rows = 0;  // convergence statistics on: the iterations of the call (Engine::iterate), else 0
   int accel_rows = 0;  // acceleration on: the iterations of the call, else 0
   bool tv = false;     // total-variation regularisation with lambda > 0: the factor volume
+  int nm_rows = 0;     // noise model on (a background != 0 or the likelihood): the iterations of the call, else 0
   // per view: the call wants its image kept as uint16 (image storage mode 1 and a uint16 stack that is no broadcast);
   // empty: none.  What is then held as uint16: Engine::kept_u16.
   std::vector<char> image_u16;
@@ -431,6 +432,18 @@ class Engine {
   // hook, and compute_delta* refuse a TV engine.
   void set_regularization(int kind, double epsilon);
   int regularization_kind() const { return reg_kind_; }
+  // The noise model of the iterate() calls that follow (mvn_engine_api.h): view v's camera background b_v enters the
+  // forward model, quotient = image / (H psi + b_v), and - with `likelihood` or any b_v != 0 - the divide pass also
+  // sums {D, Y, M} per (sweep, view) over the stacks' window (MVN_EPI_DIVIDE_NM, mvn_pass_bodies.hpp).  count 0: no
+  // background; 1: one value for every view; else one per view.  Values finite and >= 0.  Both off (the default): the
+  // plain divide pass, launch for launch.  On: iterate() waits for the stream before it returns (the rows cross to
+  // the host), and no captured sweep graph is used.  Not for an engine with a halo hook; compute_delta* refuse an
+  // engine in the mode.
+  void set_noise_model(const float* background, int count, bool likelihood);
+  bool noise_model_on() const;
+  // {D, Y, M} of the last iterate(): 3 doubles per (sweep k, view v) at 3 (k V + v), for the sweeps that ran
+  const std::vector<double>& last_likelihood() const { return nm_rows_; }
+  int last_likelihood_sweeps() const { return nm_ran_; }
   // simultaneous (Jacobi) mode for view sharding: delta <- sum over this engine's views of
   // w_v (next_v - psi), computed from the current psi without changing it
   void compute_delta(double lambda, float min_value);
@@ -692,6 +705,19 @@ class Engine {
   void stats_free();
   int iterate_sweeps(int iterations, double lambda, float min_value, double tolerance, std::vector<double>* stats,
                      std::vector<double>* alphas);
+  // noise model (set_noise_model); the records live for the running iterate() only (see memory_need)
+  std::vector<float> nm_background_;  // per view; empty: none
+  bool nm_like_ = false;
+  bool nm_on_ = false;              // the running iterate() divides through MVN_EPI_DIVIDE_NM
+  double* nm_rec_ = nullptr;        // per view: nm_cap_ records of 3 doubles
+  unsigned* nm_count_ = nullptr;    // per view: records of its last divide pass
+  double* nm_out_ = nullptr;        // 3 doubles per (sweep, view)
+  long nm_cap_ = 0;
+  std::vector<double> nm_rows_;
+  int nm_ran_ = 0;
+  MvnStatsParams nm_stats_for(int v) const;
+  void nm_free();
+  void refuse_nm(const char* what) const;
   // total-variation regularisation (set_regularization)
   int reg_kind_ = 0;
   double reg_eps_ = 0.;

@@ -1133,8 +1133,15 @@ template <int H>
 struct FxRowsStatRegs : FxRowsRegs<H> {
   MvnStatAcc st;
 };
+// the register set of the noise-model divide forms (MVN_EPI_DIVIDE_NM, MVN_EPI_DIVIDE_NM_U16)
+template <int H>
+struct FxRowsNmRegs : FxRowsRegs<H> {
+  MvnNmAcc nm;
+};
 template <int H, int EPI>
-using FxRowsRegsFor = typename std::conditional<mvn_epi_base(EPI) == MVN_EPI_UPDATE_STATS, FxRowsStatRegs<H>, FxRowsRegs<H>>::type;
+using FxRowsRegsFor = typename std::conditional<
+    mvn_epi_base(EPI) == MVN_EPI_UPDATE_STATS, FxRowsStatRegs<H>,
+    typename std::conditional<mvn_epi_nm(EPI), FxRowsNmRegs<H>, FxRowsRegs<H>>::type>::type;
 
 // LDS offsets (in cfloat, row * TP) of the two bins the real<->complex step combines: entry k
 // (0 < k < H/2) = {bin k, bin H-k}; entry 0 = {bin 0, bin H/2} (the two self-paired bins).
@@ -1344,7 +1351,7 @@ MVN_HD cfloat fx_epilogue_pair_value(const EpilogueParams& e, long i, cfloat z, 
 // the first epilogue operand at its use: a uint16 pair is widened here, not where it was fetched
 template <int EPI>
 MVN_HD cfloat fx_operand(cfloat a, unsigned u) {
-  if constexpr (EPI == MVN_EPI_DIVIDE_U16)
+  if constexpr (mvn_epi_u16(EPI))
     return mvn_u16_pair_widen(u);
   else
     return a;
@@ -1385,8 +1392,8 @@ MVN_HD void fx_c2r_load(const RowsParams& P, long r0, cfloat* buf, cfloat* tws, 
   }
   }
   constexpr int mode = EPI;
-  const float* pa = mode == MVN_EPI_DIVIDE ? P.epi.view : P.epi.psi;
-  if constexpr (mode == MVN_EPI_DIVIDE_U16) {
+  const float* pa = mvn_epi_divides(mode) ? P.epi.view : P.epi.psi;
+  if constexpr (mvn_epi_u16(mode)) {
     // the same pairs from a uint16 volume: one 4-byte word each, widened at its use (fx_operand)
 #pragma unroll
     for (int it = 0; it < C::IT0; ++it) {
@@ -1501,6 +1508,14 @@ MVN_HD void fx_c2r_stage0_epilogue(const RowsParams& P, long r0, cfloat* buf, co
     for (int k = 1; k < R; ++k) a[k] = cmulc(a[k], tw[k]);
     dftR<R, +1>(a);  // a[jo] = z[j2 + M*jo] = (x[2j], x[2j+1])
     const long i0 = (r0 + rho) * P.RP + 2 * j2;
+    if constexpr (mvn_epi_nm(EPI)) {
+      const bool row_in = mvn_stat_row_in(P.st, r0 + rho);
+#pragma unroll
+      for (int jo = 0; jo < R; ++jo) {
+        a[jo] = mvn_nm_pair(P.epi, a[jo], fx_operand<EPI>(r.ea[it][jo], r.eu[it][jo]), r.nm, P.st, row_in, 2 * (j2 + jo * M));
+        if (!KEEP) *reinterpret_cast<cfloat*>(P.out_real + i0 + 2 * jo * M) = a[jo];
+      }
+    }
     if constexpr (mvn_epi_base(EPI) == MVN_EPI_UPDATE_STATS) {
       const bool row_in = mvn_stat_row_in(P.st, r0 + rho);
 #pragma unroll
@@ -1511,7 +1526,7 @@ MVN_HD void fx_c2r_stage0_epilogue(const RowsParams& P, long r0, cfloat* buf, co
     if (KEEP) {
 #pragma unroll
       for (int jo = 0; jo < R; ++jo)
-        if constexpr (mvn_epi_base(EPI) != MVN_EPI_UPDATE_STATS)
+        if constexpr (mvn_epi_base(EPI) != MVN_EPI_UPDATE_STATS && !mvn_epi_nm(EPI))
           a[jo] = fx_epilogue_pair_value<EPI>(P.epi, i0 + 2 * jo * M, a[jo], fx_operand<EPI>(r.ea[it][jo], r.eu[it][jo]),
                                                             r.eb[it][jo]);
       dftR<R, -1>(a);
@@ -1519,7 +1534,7 @@ MVN_HD void fx_c2r_stage0_epilogue(const RowsParams& P, long r0, cfloat* buf, co
       for (int k = 1; k < R; ++k) a[k] = cmul(a[k], tw[k]);
 #pragma unroll
       for (int k = 0; k < R; ++k) p[fx_rowoff<C::PAD, R, M>(k) * TP] = a[k];
-    } else if constexpr (mvn_epi_base(EPI) != MVN_EPI_UPDATE_STATS) {
+    } else if constexpr (mvn_epi_base(EPI) != MVN_EPI_UPDATE_STATS && !mvn_epi_nm(EPI)) {
 #pragma unroll
       for (int jo = 0; jo < R; ++jo)
         mvn_epilogue_pair_t<EPI>(P.epi, P.out_real, i0 + 2 * jo * M, a[jo], fx_operand<EPI>(r.ea[it][jo], r.eu[it][jo]),
@@ -1628,4 +1643,30 @@ MVN_HD void fx_rows_run_stats(const RowsParams& P, long block, long nblocks, cfl
   MVN_PHASE_NOSYNC(ctx, (mvn_stat_init(r.st)));
   fx_rows_run<H, KIND, EPI, Ctx, LINES>(P, block, nblocks, lds, ctx);
   fx_stat_flush<FxRowsCfg<H>::NT>(P.st, block, nblocks, lds, ctx);
+}
+
+// the same for the noise-model divide forms: the lanes' {D, Y, M} accumulators, one record per workgroup
+template <int NT, typename Ctx>
+MVN_HD void fx_nm_flush(const MvnStatsParams& s, long block, long nblocks, cfloat* lds, Ctx& ctx) {
+  constexpr int NT_ = NT;
+  (void)NT_;
+  char* l = reinterpret_cast<char*>(lds);
+  MVN_PHASE(ctx, (void)0);  // (the last phase of the wave-row body ends without a workgroup barrier)
+  MVN_PHASE(ctx, (mvn_nm_put(l, NT, tid, r.nm)));
+  for (int h = mvn_pow2_ceil(NT) >> 1; h > 0; h >>= 1) {  // (MVN_PHASE is two statements on the device)
+    MVN_PHASE(ctx, (mvn_nm_tree_step(l, NT, h, tid)));
+  }
+  MVN_PHASE_NOSYNC(ctx, (tid == 0 ? mvn_nm_record(s, l, NT, block, nblocks) : (void)0));
+}
+
+template <int H, int KIND, int EPI, typename Ctx, bool LINES = false>
+MVN_HD void fx_rows_run_nm(const RowsParams& P, long block, long nblocks, cfloat* lds, Ctx& ctx) {
+  static_assert(mvn_epi_nm(EPI), "a noise-model divide epilogue");
+  static_assert(mvn_nm_lds_bytes(FxRowsCfg<H>::NT) <= (long)sizeof(cfloat) * FxRowsCfg<H>::lds_cfloats,
+                "statistics scratch exceeds the LDS");
+  constexpr int NT_ = FxRowsCfg<H>::NT;
+  (void)NT_;
+  MVN_PHASE_NOSYNC(ctx, (mvn_nm_init(r.nm)));
+  fx_rows_run<H, KIND, EPI, Ctx, LINES>(P, block, nblocks, lds, ctx);
+  fx_nm_flush<FxRowsCfg<H>::NT>(P.st, block, nblocks, lds, ctx);
 }

@@ -102,6 +102,27 @@ __global__ void __launch_bounds__(512) k_rows_c2r_r2c_tv(const RowsParams p) {
   rows_c2r_even_body<T, true, STATS, false, true>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
 }
 
+// the noise-model divide epilogue (MVN_EPI_DIVIDE_NM, MVN_EPI_DIVIDE_NM_U16), plain and fused
+template <bool EVEN, int T, bool U16>
+__global__ void __launch_bounds__(512) k_rows_c2r_nm(const RowsParams p) {
+  extern __shared__ __attribute__((aligned(16))) char mvn_smem[];
+  if (EVEN)
+    rows_c2r_even_body<T, false, false, U16, false, true>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
+  else
+    rows_c2r_odd_body<T, false, U16, false, true>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
+}
+template <int T, bool U16>
+__global__ void __launch_bounds__(512) k_rows_c2r_r2c_nm(const RowsParams p) {
+  extern __shared__ __attribute__((aligned(16))) char mvn_smem[];
+  rows_c2r_even_body<T, true, false, U16, false, true>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
+}
+// once per sweep with the noise model on: workgroup v sums the records of view v's divide pass -> out + 3 v = {D, Y, M}
+__global__ void __launch_bounds__(256) k_nm_reduce(const double* rec, const unsigned* counts, long cap, double* out) {
+  __shared__ double lds[3 * 256];
+  const long v = (long)blockIdx.x;
+  mvn_nm_reduce_body(rec + 3 * v * cap, counts + v, cap, out + 3 * v, lds, (int)threadIdx.x, (int)blockDim.x);
+}
+
 // NYQ only tags the launches that work on the Nyquist plane, so that profilers list them apart
 // run-time-radix form of the fused c2r + pointwise + r2c pass (any even d2)
 template <int T>
@@ -149,6 +170,8 @@ __global__ void __launch_bounds__(FxRowsCfg<H>::NT) kx_rows_c2r(const RowsParams
   ctx.tid = (int)threadIdx.x;
   if constexpr (mvn_epi_base(EPI) == MVN_EPI_UPDATE_STATS)
     fx_rows_run_stats<H, 1, Ctx, LINES, EPI>(p, (long)blockIdx.x, (long)gridDim.x, (cfloat*)mvn_smem, ctx);
+  else if constexpr (mvn_epi_nm(EPI))
+    fx_rows_run_nm<H, 1, EPI, Ctx, LINES>(p, (long)blockIdx.x, (long)gridDim.x, (cfloat*)mvn_smem, ctx);
   else
     fx_rows_run<H, 1, EPI, Ctx, LINES>(p, (long)blockIdx.x, (long)gridDim.x, (cfloat*)mvn_smem, ctx);
 }
@@ -165,6 +188,8 @@ __global__ void __launch_bounds__(FxRowsCfg<H>::NT) kx_rows_c2r_r2c(const RowsPa
   ctx.tid = (int)threadIdx.x;
   if constexpr (mvn_epi_base(EPI) == MVN_EPI_UPDATE_STATS)
     fx_rows_run_stats<H, 2, Ctx, LINES, EPI>(p, (long)blockIdx.x, (long)gridDim.x, (cfloat*)mvn_smem, ctx);
+  else if constexpr (mvn_epi_nm(EPI))
+    fx_rows_run_nm<H, 2, EPI, Ctx, LINES>(p, (long)blockIdx.x, (long)gridDim.x, (cfloat*)mvn_smem, ctx);
   else
     fx_rows_run<H, 2, EPI, Ctx, LINES>(p, (long)blockIdx.x, (long)gridDim.x, (cfloat*)mvn_smem, ctx);
 }
@@ -742,6 +767,8 @@ void launch_rows_c2r(const RowsParams& p, bool even, long nblocks, int nthreads,
     switch (p.epi.mode) {
       case MVN_EPI_DIVIDE: return launch_pass(kx_rows_c2r<256, MVN_EPI_DIVIDE, true>, p, nblocks, nthreads, lds_bytes, s);
       case MVN_EPI_DIVIDE_U16: return launch_pass(kx_rows_c2r<256, MVN_EPI_DIVIDE_U16, true>, p, nblocks, nthreads, lds_bytes, s);
+      case MVN_EPI_DIVIDE_NM: return launch_pass(kx_rows_c2r<256, MVN_EPI_DIVIDE_NM, true>, p, nblocks, nthreads, lds_bytes, s);
+      case MVN_EPI_DIVIDE_NM_U16: return launch_pass(kx_rows_c2r<256, MVN_EPI_DIVIDE_NM_U16, true>, p, nblocks, nthreads, lds_bytes, s);
       case MVN_EPI_UPDATE: return launch_pass(kx_rows_c2r<256, MVN_EPI_UPDATE, true>, p, nblocks, nthreads, lds_bytes, s);
       case MVN_EPI_UPDATE_STATS: return launch_pass(kx_rows_c2r<256, MVN_EPI_UPDATE_STATS, true>, p, nblocks, nthreads, lds_bytes, s);
       case MVN_EPI_UPDATE_TV: return launch_pass(kx_rows_c2r<256, MVN_EPI_UPDATE_TV, true>, p, nblocks, nthreads, lds_bytes, s);
@@ -757,6 +784,8 @@ void launch_rows_c2r(const RowsParams& p, bool even, long nblocks, int nthreads,
       switch (p.epi.mode) {
         case MVN_EPI_DIVIDE: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_DIVIDE>, p, s);
         case MVN_EPI_DIVIDE_U16: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_DIVIDE_U16>, p, s);
+        case MVN_EPI_DIVIDE_NM: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_DIVIDE_NM>, p, s);
+        case MVN_EPI_DIVIDE_NM_U16: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_DIVIDE_NM_U16>, p, s);
         case MVN_EPI_UPDATE: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_UPDATE>, p, s);
         case MVN_EPI_UPDATE_STATS: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_UPDATE_STATS>, p, s);
         case MVN_EPI_UPDATE_TV: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_UPDATE_TV>, p, s);
@@ -771,6 +800,8 @@ void launch_rows_c2r(const RowsParams& p, bool even, long nblocks, int nthreads,
     switch (p.epi.mode) {                                                                     \
       case MVN_EPI_DIVIDE: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_DIVIDE>, p, nblocks, nthreads, lds_bytes, s); break; \
       case MVN_EPI_DIVIDE_U16: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_DIVIDE_U16>, p, nblocks, nthreads, lds_bytes, s); break; \
+      case MVN_EPI_DIVIDE_NM: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_DIVIDE_NM>, p, nblocks, nthreads, lds_bytes, s); break; \
+      case MVN_EPI_DIVIDE_NM_U16: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_DIVIDE_NM_U16>, p, nblocks, nthreads, lds_bytes, s); break; \
       case MVN_EPI_UPDATE: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_UPDATE>, p, nblocks, nthreads, lds_bytes, s); break; \
       case MVN_EPI_UPDATE_STATS: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_UPDATE_STATS>, p, nblocks, nthreads, lds_bytes, s); break; \
       case MVN_EPI_UPDATE_TV: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_UPDATE_TV>, p, nblocks, nthreads, lds_bytes, s); break; \
@@ -807,6 +838,20 @@ void launch_rows_c2r(const RowsParams& p, bool even, long nblocks, int nthreads,
     }
     return;
   }
+  if (mvn_epi_nm(p.epi.mode)) {
+    lds_bytes = std::max(lds_bytes, (size_t)mvn_nm_lds_bytes(nthreads));
+    const bool u16 = p.epi.mode == MVN_EPI_DIVIDE_NM_U16;
+    if (even && u16) {
+      MVN_DISPATCH_T(p.T, (k_rows_c2r_nm<true, TT, true>));
+    } else if (even) {
+      MVN_DISPATCH_T(p.T, (k_rows_c2r_nm<true, TT, false>));
+    } else if (u16) {
+      MVN_DISPATCH_T(p.T, (k_rows_c2r_nm<false, TT, true>));
+    } else {
+      MVN_DISPATCH_T(p.T, (k_rows_c2r_nm<false, TT, false>));
+    }
+    return;
+  }
   if (p.epi.mode == MVN_EPI_DIVIDE_U16) {
     if (even) {
       MVN_DISPATCH_T(p.T, (k_rows_c2r_u16<true, TT>));
@@ -830,6 +875,8 @@ void launch_rows_c2r_r2c(const RowsParams& p, long nblocks, int nthreads, size_t
     switch (p.epi.mode) {
       case MVN_EPI_DIVIDE: return launch_pass(kx_rows_c2r_r2c<256, MVN_EPI_DIVIDE, true>, p, nblocks, nthreads, lds_bytes, s);
       case MVN_EPI_DIVIDE_U16: return launch_pass(kx_rows_c2r_r2c<256, MVN_EPI_DIVIDE_U16, true>, p, nblocks, nthreads, lds_bytes, s);
+      case MVN_EPI_DIVIDE_NM: return launch_pass(kx_rows_c2r_r2c<256, MVN_EPI_DIVIDE_NM, true>, p, nblocks, nthreads, lds_bytes, s);
+      case MVN_EPI_DIVIDE_NM_U16: return launch_pass(kx_rows_c2r_r2c<256, MVN_EPI_DIVIDE_NM_U16, true>, p, nblocks, nthreads, lds_bytes, s);
       case MVN_EPI_UPDATE: return launch_pass(kx_rows_c2r_r2c<256, MVN_EPI_UPDATE, true>, p, nblocks, nthreads, lds_bytes, s);
       case MVN_EPI_UPDATE_STATS: return launch_pass(kx_rows_c2r_r2c<256, MVN_EPI_UPDATE_STATS, true>, p, nblocks, nthreads, lds_bytes, s);
       case MVN_EPI_UPDATE_TV: return launch_pass(kx_rows_c2r_r2c<256, MVN_EPI_UPDATE_TV, true>, p, nblocks, nthreads, lds_bytes, s);
@@ -852,6 +899,15 @@ void launch_rows_c2r_r2c(const RowsParams& p, long nblocks, int nthreads, size_t
       MVN_DISPATCH_T(p.T, (k_rows_c2r_r2c_tv<TT, false>));
       return;
     }
+    if (mvn_epi_nm(p.epi.mode)) {
+      lds_bytes = std::max(lds_bytes, (size_t)mvn_nm_lds_bytes(nthreads));
+      if (p.epi.mode == MVN_EPI_DIVIDE_NM_U16) {
+        MVN_DISPATCH_T(p.T, (k_rows_c2r_r2c_nm<TT, true>));
+      } else {
+        MVN_DISPATCH_T(p.T, (k_rows_c2r_r2c_nm<TT, false>));
+      }
+      return;
+    }
     if (p.epi.mode == MVN_EPI_DIVIDE_U16) {
       MVN_DISPATCH_T(p.T, (k_rows_c2r_r2c_u16<TT>));
       return;
@@ -861,10 +917,12 @@ void launch_rows_c2r_r2c(const RowsParams& p, long nblocks, int nthreads, size_t
   }
   check_aligned16(p.in_cplx, "input");
   check_aligned16(p.out_cplx, "output");
-  if (wave_rows_enabled(p, mvn_epi_math(p.epi.mode) == MVN_EPI_DIVIDE ? 4 : 8)) {
+  if (wave_rows_enabled(p, mvn_epi_divides(p.epi.mode) ? 4 : 8)) {
     switch (p.epi.mode) {
       case MVN_EPI_DIVIDE: return launch_wave_rows(kw_rows<MVN_WR_C2R_R2C, MVN_EPI_DIVIDE>, p, s);
       case MVN_EPI_DIVIDE_U16: return launch_wave_rows(kw_rows<MVN_WR_C2R_R2C, MVN_EPI_DIVIDE_U16>, p, s);
+      case MVN_EPI_DIVIDE_NM: return launch_wave_rows(kw_rows<MVN_WR_C2R_R2C, MVN_EPI_DIVIDE_NM>, p, s);
+      case MVN_EPI_DIVIDE_NM_U16: return launch_wave_rows(kw_rows<MVN_WR_C2R_R2C, MVN_EPI_DIVIDE_NM_U16>, p, s);
       case MVN_EPI_UPDATE: return launch_wave_rows(kw_rows<MVN_WR_C2R_R2C, MVN_EPI_UPDATE>, p, s, 32);
       case MVN_EPI_UPDATE_STATS: return launch_wave_rows(kw_rows<MVN_WR_C2R_R2C, MVN_EPI_UPDATE_STATS>, p, s, 32);
       case MVN_EPI_UPDATE_TV: return launch_wave_rows(kw_rows<MVN_WR_C2R_R2C, MVN_EPI_UPDATE_TV>, p, s, 32);
@@ -878,6 +936,8 @@ void launch_rows_c2r_r2c(const RowsParams& p, long nblocks, int nthreads, size_t
     switch (p.epi.mode) {                                                                     \
       case MVN_EPI_DIVIDE: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r_r2c<H, MVN_EPI_DIVIDE>, p, nblocks, nthreads, lds_bytes, s); break; \
       case MVN_EPI_DIVIDE_U16: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r_r2c<H, MVN_EPI_DIVIDE_U16>, p, nblocks, nthreads, lds_bytes, s); break; \
+      case MVN_EPI_DIVIDE_NM: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r_r2c<H, MVN_EPI_DIVIDE_NM>, p, nblocks, nthreads, lds_bytes, s); break; \
+      case MVN_EPI_DIVIDE_NM_U16: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r_r2c<H, MVN_EPI_DIVIDE_NM_U16>, p, nblocks, nthreads, lds_bytes, s); break; \
       case MVN_EPI_UPDATE: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r_r2c<H, MVN_EPI_UPDATE>, p, nblocks, nthreads, lds_bytes, s); break; \
       case MVN_EPI_UPDATE_STATS: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r_r2c<H, MVN_EPI_UPDATE_STATS>, p, nblocks, nthreads, lds_bytes, s); break; \
       case MVN_EPI_UPDATE_TV: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r_r2c<H, MVN_EPI_UPDATE_TV>, p, nblocks, nthreads, lds_bytes, s); break; \
@@ -894,6 +954,11 @@ void launch_rows_c2r_r2c(const RowsParams& p, long nblocks, int nthreads, size_t
 void launch_convergence_reduce(const double* rec, const unsigned* counts, int nviews, long cap, double* out,
                                stream_t s) {
   hipLaunchKernelGGL(k_convergence_reduce, dim3(1), dim3(256), 0, hs(s), rec, counts, nviews, cap, out);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_nm_reduce(const double* rec, const unsigned* counts, int nviews, long cap, double* out, stream_t s) {
+  hipLaunchKernelGGL(k_nm_reduce, dim3((unsigned)nviews), dim3(256), 0, hs(s), rec, counts, cap, out);
   HIP_CHECK(hipGetLastError());
 }
 

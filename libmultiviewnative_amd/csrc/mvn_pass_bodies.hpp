@@ -36,7 +36,11 @@ enum MvnEpilogue {
   MVN_EPI_DIVIDE_U16 = 5,    // DIVIDE with the view held as uint16 (EpilogueParams::view16): same quotient, bit for bit
   // total-variation regularisation (mvn_tv.hpp): the integral x*scale is multiplied by the factor tv[i] before `next`
   MVN_EPI_UPDATE_TV = 6,        // psi = w * (next(psi, (x*scale) * tv) - psi) + psi
-  MVN_EPI_UPDATE_STATS_TV = 7   // UPDATE_TV, plus the convergence statistics
+  MVN_EPI_UPDATE_STATS_TV = 7,  // UPDATE_TV, plus the convergence statistics
+  // noise model (camera background + per-sweep likelihood): the quotient against m = x*scale + background, plus the
+  // statistics {D, Y, M} of the window (MvnStatsParams, MvnNmAcc)
+  MVN_EPI_DIVIDE_NM = 8,     // view as float32
+  MVN_EPI_DIVIDE_NM_U16 = 9  // view as uint16 (EpilogueParams::view16)
 };
 
 // the epilogues that read psi and the weights
@@ -51,6 +55,10 @@ constexpr int mvn_epi_base(int epi) {
 }
 // the mode whose arithmetic an epilogue runs once its operands are floats
 constexpr int mvn_epi_math(int epi) { return epi == MVN_EPI_DIVIDE_U16 ? (int)MVN_EPI_DIVIDE : mvn_epi_base(epi); }
+// the noise-model divide epilogues, the epilogues on a uint16 view, and every epilogue that forms the quotient
+constexpr bool mvn_epi_nm(int epi) { return epi == MVN_EPI_DIVIDE_NM || epi == MVN_EPI_DIVIDE_NM_U16; }
+constexpr bool mvn_epi_u16(int epi) { return epi == MVN_EPI_DIVIDE_U16 || epi == MVN_EPI_DIVIDE_NM_U16; }
+constexpr bool mvn_epi_divides(int epi) { return epi == MVN_EPI_DIVIDE || mvn_epi_u16(epi) || mvn_epi_nm(epi); }
 
 struct EpilogueParams {
   int mode;
@@ -75,6 +83,7 @@ struct EpilogueParams {
   // epoch 0xffffffff (Plan3D::no_poison) - the pointer is never null when a pass is launched.
   const unsigned* poison;
   unsigned poison_epoch;
+  float background;     // DIVIDE_NM / DIVIDE_NM_U16: the view's camera offset b, m = x*scale + b (0: m = x*scale)
   const float* tv;      // UPDATE_TV / UPDATE_STATS_TV: the factor volume, psi's layout (mvn_tv.hpp)
 };
 
@@ -448,6 +457,119 @@ MVN_HD void mvn_convergence_reduce_body(const double* rec, const unsigned* count
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// noise model (MVN_EPI_DIVIDE_NM, MVN_EPI_DIVIDE_NM_U16).  For a voxel with the inverse-transform output times
+// scale x, the view's background b and the image voxel y widened to float32:
+//   m = x + b        (float32, one correctly rounded add, never contracted with the multiply by scale;
+//                     with b == 0 the add is NOT performed: m = x, -0 stays -0)
+//   q = quotient_g(y, m, guard)                      (the existing quotient, unchanged)
+//   term = y > 0 ? (y * logf(q) - y) + m : m - y     (float32, no contraction; q is the value written)
+// Every lane sums term, y and m in double over the voxels of the window it divides; the workgroup reduces its lanes in
+// a fixed order through the LDS and writes ONE record {D, Y, M} with plain stores, as the convergence statistics do.
+// ---------------------------------------------------------------------------------------------
+struct MvnNmAcc {
+  double d, y, m;
+};
+
+MVN_HD void mvn_nm_init(MvnNmAcc& a) {
+  a.d = 0.;
+  a.y = 0.;
+  a.m = 0.;
+}
+
+// one voxel: the quotient (returned) and the voxel's share of the statistics; x is already scaled
+MVN_HD float mvn_nm_one(const EpilogueParams& e, float y, float x, MvnNmAcc& a, bool in) {
+  MVN_FP_EXACT
+  const float m = e.background != 0.f ? x + e.background : x;  // (the condition is the same for every lane)
+  const float q = mvn_quotient_g(y, m, e.guard_zero_view);
+  const float term = y > 0.f ? (y * logf(q) - y) + m : m - y;
+  a.d += in ? (double)term : 0.;
+  a.y += in ? (double)y : 0.;
+  a.m += in ? (double)m : 0.;
+  return q;
+}
+
+// the pair (i, i + 1) in columns col, col + 1 of a row: view pair a, raw transform output z
+MVN_HD cfloat mvn_nm_pair(const EpilogueParams& e, cfloat z, cfloat a, MvnNmAcc& acc, const MvnStatsParams& s,
+                          bool row_in, int col) {
+  MVN_FP_EXACT
+  const float x0 = z.x * e.scale, x1 = z.y * e.scale;
+  const unsigned c = (unsigned)(col - s.o2);
+  const float q0 = mvn_nm_one(e, a.x, x0, acc, row_in && c < s.n2);
+  const float q1 = mvn_nm_one(e, a.y, x1, acc, row_in && c + 1u < s.n2);
+  return cmake(q0, q1);
+}
+
+// scratch of the lane reduction: 3 n doubles
+MVN_HD constexpr long mvn_nm_lds_bytes(int nthreads) { return 24L * nthreads; }
+
+MVN_HD void mvn_nm_put(char* lds, int n, int tid, const MvnNmAcc& a) {
+  double* l = reinterpret_cast<double*>(lds);
+  l[tid] = a.d;
+  l[n + tid] = a.y;
+  l[2 * n + tid] = a.m;
+}
+// a tree over the next power of two, pairs (t, t + h) in a fixed order
+MVN_HD void mvn_nm_tree_step(char* lds, int n, int h, int tid) {
+  double* l = reinterpret_cast<double*>(lds);
+  if (tid < h && tid + h < n) {
+    l[tid] += l[tid + h];
+    l[n + tid] += l[n + tid + h];
+    l[2 * n + tid] += l[2 * n + tid + h];
+  }
+}
+MVN_HD void mvn_nm_record(const MvnStatsParams& s, const char* lds, int n, long block, long nblocks) {
+  const double* l = reinterpret_cast<const double*>(lds);
+  if (block < s.cap) {
+    s.rec[3 * block] = l[0];
+    s.rec[3 * block + 1] = l[n];
+    s.rec[3 * block + 2] = l[2 * n];
+  }
+  if (block == 0) *s.count = (unsigned)nblocks;
+}
+
+// workgroup end of the run-time-radix bodies (tid / nthreads form): every lane calls it
+MVN_HD void mvn_nm_flush(const MvnStatsParams& s, const MvnNmAcc& a, long block, long nblocks, cfloat* lds, int tid,
+                         int nthreads) {
+  char* l = reinterpret_cast<char*>(lds);
+  MVN_SYNC();
+  for (int t = tid; t < nthreads; t += nthreads) mvn_nm_put(l, nthreads, t, a);
+  MVN_SYNC();
+  for (int h = mvn_pow2_ceil(nthreads) >> 1; h > 0; h >>= 1) {
+    for (int t = tid; t < h; t += nthreads) mvn_nm_tree_step(l, nthreads, h, t);
+    MVN_SYNC();
+  }
+  if (tid == 0) mvn_nm_record(s, l, nthreads, block, nblocks);
+}
+
+// k_nm_reduce: the records of ONE view's divide pass (rec, *count of them, at most cap) -> out = {D, Y, M}.  Lane t
+// sums records t, t + nthreads, ..., then the lanes are reduced as above.  lds: 3 nthreads doubles.
+MVN_HD void mvn_nm_reduce_body(const double* rec, const unsigned* count, long cap, double* out, double* lds, int tid,
+                               int nthreads) {
+  for (int t = tid; t < nthreads; t += nthreads) {
+    double d = 0., y = 0., m = 0.;
+    const long n = (long)*count < cap ? (long)*count : cap;
+    for (long i = t; i < n; i += nthreads) {
+      d += rec[3 * i];
+      y += rec[3 * i + 1];
+      m += rec[3 * i + 2];
+    }
+    lds[t] = d;
+    lds[nthreads + t] = y;
+    lds[2 * nthreads + t] = m;
+  }
+  MVN_SYNC();
+  for (int h = mvn_pow2_ceil(nthreads) >> 1; h > 0; h >>= 1) {
+    for (int t = tid; t < h; t += nthreads) mvn_nm_tree_step(reinterpret_cast<char*>(lds), nthreads, h, t);
+    MVN_SYNC();
+  }
+  if (tid == 0) {
+    out[0] = lds[0];
+    out[1] = lds[nthreads];
+    out[2] = lds[2 * nthreads];
+  }
+}
+
 // Pair epilogue of the fused c2r + pointwise + r2c pass: hands the two results back as the packed
 // input z[j] = (y[2j], y[2j+1]) of the next forward transform; UPDATE also writes psi.
 template <bool TV = false>
@@ -514,7 +636,7 @@ struct RowsParams {
   // volume and in_cplx / out_cplx point at the volume's first element.  Fixed kernels only, nyq_packed only.
   int lines, lines_d1;
   long row_base;
-  MvnStatsParams st;  // MVN_EPI_UPDATE_STATS only
+  MvnStatsParams st;  // MVN_EPI_UPDATE_STATS (and _TV); MVN_EPI_DIVIDE_NM (and _U16): the window and the records
 };
 
 // the window bits of the T rows of a tile (run-time-radix bodies: the division stays per row)
@@ -610,7 +732,8 @@ MVN_HD void rows_r2c_even_body(const RowsParams& P, long tile, int tid, int nthr
 // U16 = true: the DIVIDE epilogue on a uint16 view (P.epi.mode is then MVN_EPI_DIVIDE_U16).
 // TV = true: the UPDATE epilogue (with STATS or without) on the integral times the total-variation factor (P.epi.mode
 // is then MVN_EPI_UPDATE_TV / MVN_EPI_UPDATE_STATS_TV); the factor is loaded at its use.
-template <int T, bool KEEP = false, bool STATS = false, bool U16 = false, bool TV = false>
+// NM = true: the noise-model divide (P.epi.mode is then MVN_EPI_DIVIDE_NM, or MVN_EPI_DIVIDE_NM_U16 with U16).
+template <int T, bool KEEP = false, bool STATS = false, bool U16 = false, bool TV = false, bool NM = false>
 MVN_HD void rows_c2r_even_body(const RowsParams& P, long tile, int tid, int nthreads, cfloat* lds) {
   // (a copy of the epilogue's few fields, not of P: the run-time radix tables in P are indexed dynamically and a
   // private copy of the whole struct would live in scratch memory)
@@ -625,6 +748,12 @@ MVN_HD void rows_c2r_even_body(const RowsParams& P, long tile, int tid, int nthr
   }
   if constexpr (U16) epi.mode = MVN_EPI_DIVIDE;  // the arithmetic of DIVIDE, on operands widened at the use
   if constexpr (TV) epi.mode = MVN_EPI_UPDATE;   // operands and psi as UPDATE
+  MvnNmAcc nacc;
+  if constexpr (NM) {
+    epi.mode = MVN_EPI_DIVIDE;  // operands as DIVIDE
+    mvn_nm_init(nacc);
+    rin = mvn_stat_tile_rows<T>(P, tile * T);
+  }
   constexpr int U = MVN_ROWS_U;
   const int h = P.h, TP = P.TP;
   const long r0 = tile * T;
@@ -721,7 +850,13 @@ MVN_HD void rows_c2r_even_body(const RowsParams& P, long tile, int tid, int nthr
       const long row = r0 + rho;
       if (w < total && row <= last_row) {
         if constexpr (U16) ea[u] = mvn_u16_pair_widen(eu[u]);
-        if constexpr (STATS) {
+        if constexpr (NM) {
+          const cfloat q = mvn_nm_pair(epi, buf[j * TP + rho], ea[u], nacc, P.st, (rin >> rho) & 1u, 2 * j);
+          if (KEEP)
+            buf[j * TP + rho] = q;
+          else
+            *reinterpret_cast<cfloat*>(P.out_real + row * P.RP + 2 * j) = q;
+        } else if constexpr (STATS) {
           const cfloat y = mvn_update_pair_stats<TV>(epi, row * P.RP + 2 * j, buf[j * TP + rho], ea[u], eb[u], acc,
                                                      P.st, (rin >> rho) & 1u, 2 * j);
           if (KEEP) buf[j * TP + rho] = y;
@@ -738,6 +873,7 @@ MVN_HD void rows_c2r_even_body(const RowsParams& P, long tile, int tid, int nthr
     rows_r2c_even_tail<T>(P, r0, buf, alt, tw, tid, nthreads);
   }
   if constexpr (STATS) mvn_stat_flush(P.st, acc, tile, (P.rows + T - 1) / T, lds, tid, nthreads);
+  if constexpr (NM) mvn_nm_flush(P.st, nacc, tile, (P.rows + T - 1) / T, lds, tid, nthreads);
 }
 
 // odd d2: plain complex transform of the real row, first C = (d2+1)/2 bins kept
@@ -764,7 +900,7 @@ MVN_HD void rows_r2c_odd_body(const RowsParams& P, long tile, int tid, int nthre
   }
 }
 
-template <int T, bool STATS = false, bool U16 = false, bool TV = false>
+template <int T, bool STATS = false, bool U16 = false, bool TV = false, bool NM = false>
 MVN_HD void rows_c2r_odd_body(const RowsParams& P, long tile, int tid, int nthreads, cfloat* lds) {
   // (a copy of the epilogue's few fields, not of P: the run-time radix tables in P are indexed dynamically and a
   // private copy of the whole struct would live in scratch memory)
@@ -777,6 +913,11 @@ MVN_HD void rows_c2r_odd_body(const RowsParams& P, long tile, int tid, int nthre
     rin = mvn_stat_tile_rows<T>(P, tile * T);
   }
   if constexpr (TV) epi.mode = MVN_EPI_UPDATE;  // (MVN_EPI_UPDATE_TV: the arithmetic of UPDATE on the integral times tv)
+  MvnNmAcc nacc;
+  if constexpr (NM) {
+    mvn_nm_init(nacc);
+    rin = mvn_stat_tile_rows<T>(P, tile * T);
+  }
   const int n = P.h, TP = P.TP;
   const long r0 = tile * T;
   cfloat* buf = lds;
@@ -801,7 +942,15 @@ MVN_HD void rows_c2r_odd_body(const RowsParams& P, long tile, int tid, int nthre
   for (int w = tid; w < T * n; w += nthreads) {
     const int rho = (int)mvn_fastdiv((unsigned)w, (unsigned)n, P.hmul), j = w - rho * n;
     const long row = r0 + rho;
-    if constexpr (STATS) {
+    if constexpr (NM) {  // (one element at a time, the view as float32 or uint16)
+      MVN_FP_EXACT
+      if (row < P.rows) {
+        const long i = row * P.RP + j;
+        const float view = U16 ? (float)epi.view16[i] : epi.view[i];
+        P.out_real[i] = mvn_nm_one(epi, view, buf[j * TP + rho].x * epi.scale, nacc,
+                                   ((rin >> rho) & 1u) && (unsigned)(j - P.st.o2) < P.st.n2);
+      }
+    } else if constexpr (STATS) {
       if (row < P.rows)
         mvn_update_stats<TV>(epi, row * P.RP + j, buf[j * TP + rho].x, acc,
                          ((rin >> rho) & 1u) && (unsigned)(j - P.st.o2) < P.st.n2);
@@ -817,6 +966,7 @@ MVN_HD void rows_c2r_odd_body(const RowsParams& P, long tile, int tid, int nthre
     }
   }
   if constexpr (STATS) mvn_stat_flush(P.st, acc, tile, (P.rows + T - 1) / T, lds, tid, nthreads);
+  if constexpr (NM) mvn_nm_flush(P.st, nacc, tile, (P.rows + T - 1) / T, lds, tid, nthreads);
 }
 
 // ---------------------------------------------------------------------------------------------

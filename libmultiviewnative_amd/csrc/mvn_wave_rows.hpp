@@ -79,6 +79,7 @@ struct WrRegs {
   cfloat pw[4];  // exp(-2 pi i k / d2) of the lane's (k, H - k) pairs
   qfloat nx[4];  // the lane's two groups of the NEXT row of its half-wave, requested one row ahead
   MvnStatAcc st; // MVN_EPI_UPDATE_STATS
+  MvnNmAcc nm;   // MVN_EPI_DIVIDE_NM, MVN_EPI_DIVIDE_NM_U16
 };
 
 // exp(-2 pi i k / d2) for 0 < k < H from the table of k <= H/2 (P.twr)
@@ -142,7 +143,7 @@ MVN_HD void wr_setup(const RowsParams& P, WrRegs& r, cfloat* rows, int tid) {
 // pair twiddles from a 1 KB LDS table in phases A and E instead of keeping them in 8 registers.
 template <int EPI>
 constexpr bool wr_pw_in_lds() {
-  return mvn_epi_reads_psi(EPI);
+  return mvn_epi_reads_psi(EPI) || mvn_epi_nm(EPI);  // (the noise-model divide: its accumulators and the log's temporaries)
 }
 template <int EPI>
 MVN_HD void wr_pw(const WrRegs& r, const cfloat* rows, int t, cfloat* pw) {
@@ -204,7 +205,7 @@ MVN_HD void wr_fetch_row(const RowsParams& P, long row, WrRegs& r, int tid) {
 // the start of phase A of the row itself and consume it at once)
 template <int EPI>
 constexpr bool wr_prefetch() {
-  return EPI == MVN_EPI_DIVIDE || EPI == MVN_EPI_DIVIDE_U16 || EPI == MVN_EPI_STORE;
+  return (mvn_epi_divides(EPI) && !mvn_epi_nm(EPI)) || EPI == MVN_EPI_STORE;
 }
 
 // The operands of the pointwise step (view, or psi and weights) of a row are requested one SWEEP
@@ -217,12 +218,12 @@ template <int EPI>
 MVN_HD void wr_fetch_epi(const RowsParams& P, long row, WrRegs& r, int tid) {
   if (row >= P.rows) return;
   const int t = tid & 31;  // the lane finishes reals 2 (t + 32 jo), 2 (t + 32 jo) + 1 in phase C
-  if constexpr (EPI == MVN_EPI_DIVIDE_U16) {  // a uint16 view: one 4-byte word per pair, widened at its use in phase C
+  if constexpr (mvn_epi_u16(EPI)) {  // a uint16 view: one 4-byte word per pair, widened at its use in phase C
     const unsigned short* pa = P.epi.view16 + row * P.RP + 2 * t;
 #pragma unroll
     for (int jo = 0; jo < 8; ++jo) r.eu[jo] = mvn_u16_pair_fetch(pa + 64 * jo);
   } else if (EPI != MVN_EPI_STORE) {
-    const float* pa = (EPI == MVN_EPI_DIVIDE ? P.epi.view : P.epi.psi) + row * P.RP + 2 * t;
+    const float* pa = (mvn_epi_divides(EPI) ? P.epi.view : P.epi.psi) + row * P.RP + 2 * t;
 #pragma unroll
     for (int jo = 0; jo < 8; ++jo) r.ea[jo] = *reinterpret_cast<const cfloat*>(pa + 64 * jo);
   }
@@ -330,11 +331,14 @@ MVN_HD void wr_phase_c(const RowsParams& P, long row, long next_row, cfloat* row
     for (int k = 1; k < 8; ++k) a[k] = cmulc(a[k], tw[k]);
     dftR<8, +1>(a);  // a[jo] = z[t + 32 jo] = (x[2 j], x[2 j + 1])
     bool row_in = false;
-    if constexpr (mvn_epi_base(EPI) == MVN_EPI_UPDATE_STATS) row_in = mvn_stat_row_in(P.st, row);
+    if constexpr (mvn_epi_base(EPI) == MVN_EPI_UPDATE_STATS || mvn_epi_nm(EPI)) row_in = mvn_stat_row_in(P.st, row);
     if (MODE == MVN_WR_C2R) {
 #pragma unroll
       for (int jo = 0; jo < 8; ++jo) {
-        if constexpr (mvn_epi_base(EPI) == MVN_EPI_UPDATE_STATS)
+        if constexpr (mvn_epi_nm(EPI))
+          *reinterpret_cast<cfloat*>(P.out_real + i0 + 64 * jo) =
+              mvn_nm_pair(P.epi, a[jo], fx_operand<EPI>(r.ea[jo], r.eu[jo]), r.nm, P.st, row_in, 2 * t + 64 * jo);
+        else if constexpr (mvn_epi_base(EPI) == MVN_EPI_UPDATE_STATS)
           mvn_update_pair_stats<mvn_epi_tv(EPI)>(P.epi, i0 + 64 * jo, a[jo], r.ea[jo], r.eb[jo], r.st, P.st, row_in, 2 * t + 64 * jo);
         else
           mvn_epilogue_pair_t<EPI>(P.epi, P.out_real, i0 + 64 * jo, a[jo], fx_operand<EPI>(r.ea[jo], r.eu[jo]), r.eb[jo]);
@@ -345,7 +349,9 @@ MVN_HD void wr_phase_c(const RowsParams& P, long row, long next_row, cfloat* row
     }
 #pragma unroll
     for (int jo = 0; jo < 8; ++jo) {
-      if constexpr (mvn_epi_base(EPI) == MVN_EPI_UPDATE_STATS)
+      if constexpr (mvn_epi_nm(EPI))
+        a[jo] = mvn_nm_pair(P.epi, a[jo], fx_operand<EPI>(r.ea[jo], r.eu[jo]), r.nm, P.st, row_in, 2 * t + 64 * jo);
+      else if constexpr (mvn_epi_base(EPI) == MVN_EPI_UPDATE_STATS)
         a[jo] = mvn_update_pair_stats<mvn_epi_tv(EPI)>(P.epi, i0 + 64 * jo, a[jo], r.ea[jo], r.eb[jo], r.st, P.st, row_in,
                                       2 * t + 64 * jo);
       else
@@ -465,6 +471,14 @@ MVN_HD void wr_rows_body(const RowsParams& P, long block, long nblocks, cfloat* 
     MVN_PHASE_NOSYNC(ctx, (mvn_stat_init(r.st)));
     wr_rows_walk<MODE, EPI>(P, block, nblocks, lds, ctx);
     fx_stat_flush<WrCfg::NT>(P.st, block, nblocks, lds, ctx);
+  } else if constexpr (mvn_epi_nm(EPI)) {
+    static_assert(mvn_nm_lds_bytes(WrCfg::NT) <= (long)sizeof(cfloat) * WrCfg::lds_cfloats,
+                  "statistics scratch exceeds the LDS");
+    constexpr int NT_ = WrCfg::NT;
+    (void)NT_;
+    MVN_PHASE_NOSYNC(ctx, (mvn_nm_init(r.nm)));
+    wr_rows_walk<MODE, EPI>(P, block, nblocks, lds, ctx);
+    fx_nm_flush<WrCfg::NT>(P.st, block, nblocks, lds, ctx);
   } else {
     wr_rows_walk<MODE, EPI>(P, block, nblocks, lds, ctx);
   }

@@ -49,6 +49,8 @@ ENGINE_ABI_SYMBOLS = [
     "mvn_set_regularization", "mvn_get_regularization", "mvn_engine_set_regularization", "mvn_tv_factor",
     "mvn_tv_time", "mvn_tv_launch_count",
     "mvn_set_image_storage", "mvn_get_image_storage", "mvn_deconvolve_memory_described", "mvn_image_storage_counters",
+    "mvn_set_background", "mvn_get_background", "mvn_set_likelihood", "mvn_get_likelihood", "mvn_last_likelihood",
+    "mvn_engine_set_noise_model", "mvn_engine_last_likelihood",
 ]
 
 
@@ -176,6 +178,13 @@ class Binding:
         l.mvn_tv_factor.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_double, C.c_double,
                                     C.POINTER(C.c_float)]
         l.mvn_tv_time.argtypes = [C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_float)]
+        l.mvn_set_background.argtypes = [C.POINTER(C.c_float), C.c_int]
+        l.mvn_get_background.argtypes = [C.POINTER(C.c_float), C.c_int]
+        l.mvn_set_likelihood.argtypes = [C.c_int]
+        l.mvn_get_likelihood.argtypes = [C.POINTER(C.c_int)]
+        l.mvn_last_likelihood.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_int]
+        l.mvn_engine_set_noise_model.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int]
+        l.mvn_engine_last_likelihood.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_int]
         l.mvn_tv_launch_count.restype = C.c_long
         l.mvn_tv_launch_count.argtypes = []
         l.mvn_engine_compute_delta.argtypes = [C.c_void_p, C.c_double, C.c_float]
@@ -337,6 +346,41 @@ class Binding:
         kind, eps = C.c_int(0), C.c_double(0)
         self.check(self.l.mvn_get_regularization(C.byref(kind), C.byref(eps)))
         return kind.value, eps.value
+
+    def set_background(self, values=None):
+        """Process-wide camera background of the RL loop's forward model, quotient = image / (H psi + b_v): None or
+        empty: off (default); one value: every view; else one per view (mvn_engine_api.h)."""
+        vals = np.atleast_1d(np.asarray([] if values is None else values, dtype=np.float32)).ravel()
+        self.check(self.l.mvn_set_background(vals.ctypes.data_as(C.POINTER(C.c_float)) if vals.size else None,
+                                             int(vals.size)))
+
+    def get_background(self):
+        n = self.check(self.l.mvn_get_background(None, 0))
+        out = np.zeros(n, dtype=np.float32)
+        if n:
+            self.check(self.l.mvn_get_background(out.ctypes.data_as(C.POINTER(C.c_float)), n))
+        return out
+
+    def set_likelihood(self, mode):
+        """Process-wide: 1 = the divide pass also sums {D, Y, M} per (sweep, view); 0 off (default)."""
+        self.check(self.l.mvn_set_likelihood(int(mode)))
+
+    def get_likelihood(self):
+        out = C.c_int(0)
+        self.check(self.l.mvn_get_likelihood(C.byref(out)))
+        return out.value
+
+    def last_likelihood(self):
+        """float64 array [sweeps run, V, 3] of {D, Y, M} of the last deconvolution this thread completed (no rows
+        when background and likelihood were off)."""
+        run, nv = C.c_int(0), C.c_int(0)
+        rows = self.check(self.l.mvn_last_likelihood(C.byref(run), C.byref(nv), None, 0))
+        out = np.zeros((rows, 3), dtype=np.float64)
+        if rows:
+            self.check(self.l.mvn_last_likelihood(C.byref(run), C.byref(nv), out.ctypes.data_as(C.POINTER(C.c_double)),
+                                                  rows))
+        v = max(nv.value, 1)
+        return out.reshape(rows // v, v, 3)
 
     def tv_factor(self, psi, lambda_, epsilon, device=0):
         """mvn_tv_factor: the total-variation factor t of the float32 volume psi."""
@@ -720,6 +764,26 @@ class EngineHandle:
     def set_regularization(self, kind, epsilon=0.0):
         """mvn_engine_set_regularization: the regulariser of the iterate* calls that follow."""
         self.b.check(self.b.l.mvn_engine_set_regularization(self.h, int(kind), float(epsilon)))
+
+    def set_noise_model(self, background=None, likelihood=0):
+        """mvn_engine_set_noise_model: one background per view (or None) and the likelihood switch of the iterate*
+        calls that follow."""
+        ptr = None
+        if background is not None:
+            vals = np.ascontiguousarray(background, dtype=np.float32).ravel()
+            assert vals.size == self.num_views, "one background value per view"
+            ptr = vals.ctypes.data_as(C.POINTER(C.c_float))
+        self.b.check(self.b.l.mvn_engine_set_noise_model(self.h, ptr, int(likelihood)))
+
+    def last_likelihood(self):
+        """float64 array [sweeps run, V, 3] of {D, Y, M} of the last iterate* call (drains the stream)."""
+        run = C.c_int(0)
+        rows = self.b.check(self.b.l.mvn_engine_last_likelihood(self.h, C.byref(run), None, 0))
+        out = np.zeros((rows, 3), dtype=np.float64)
+        if rows:
+            self.b.check(self.b.l.mvn_engine_last_likelihood(self.h, C.byref(run),
+                                                             out.ctypes.data_as(C.POINTER(C.c_double)), rows))
+        return out.reshape(-1, self.num_views, 3)
 
     def iterate_accelerated(self, iterations, lambda_, min_value, tolerance=-1.0):
         """mvn_engine_iterate_accelerated (blocking): (iterations run, [run, 3] statistics - empty with
