@@ -142,84 +142,47 @@ static size_t current_memory_budget() {
   return b > 0 ? (size_t)b : 0;
 }
 
-// ---- convergence statistics (mvn_set_convergence) ------------------------------------------------
-static std::atomic<double> g_conv_tol{-1.};
-// the tolerance of the call this thread runs (captured at submit); NaN outside a call: then the process-wide one
-static thread_local double t_call_tol = NAN;
-static double call_tolerance() { return std::isnan(t_call_tol) ? g_conv_tol.load() : t_call_tol; }
-// ---- acceleration (mvn_set_acceleration): captured at the start of a call, like the tolerance ----
-static std::atomic<int> g_accel{0};
-static thread_local int t_call_accel = -1;  // the mode of the call this thread runs; -1 outside a call
-static int call_accel() { return t_call_accel < 0 ? g_accel.load() : t_call_accel; }
-// ---- regularisation (mvn_set_regularization): captured at the start of a call, like the tolerance ----
-struct RegMode {
-  int kind = 0;        // MVN_REG_TIKHONOV / MVN_REG_TV
-  double epsilon = 0.; // MVN_REG_TV only
-};
-static std::mutex g_reg_mu;
-static RegMode g_reg;
-static RegMode current_reg() {
-  std::lock_guard<std::mutex> lk(g_reg_mu);
-  return g_reg;
+// ---- the switches of the loop (mvn_set_convergence, mvn_set_acceleration, mvn_set_regularization, mvn_set_background,
+// mvn_set_likelihood): one process-wide value, which a call copies at its start and hands down ----
+static std::mutex g_loop_mu;
+static LoopOptions g_loop;
+static LoopOptions current_loop() {
+  std::lock_guard<std::mutex> lk(g_loop_mu);
+  return g_loop;
 }
-static thread_local int t_call_reg_kind = -1;  // the kind of the call this thread runs; -1 outside a call
-static int call_reg_kind() { return t_call_reg_kind < 0 ? current_reg().kind : t_call_reg_kind; }
-// a call with total variation on and a weight the kernel has no clamp for: refused before psi is touched
-static void check_tv_lambda(int kind, double lambda) {
-  if (kind == 1 && !(lambda >= 0. && lambda < 1. / 12.))
-    throw std::invalid_argument("total-variation regularisation needs 0 <= lambda_ < 1/12");
+// a setter: the edited value replaces the process-wide one if it is valid
+template <typename F>
+static void edit_loop(F&& edit) {
+  std::lock_guard<std::mutex> lk(g_loop_mu);
+  LoopOptions o = g_loop;
+  edit(o);
+  o.validate(LoopOptions::kAbi);
+  g_loop = std::move(o);
 }
-// ---- noise model (mvn_set_background, mvn_set_likelihood): captured at the start of a call, like the regulariser ----
-struct NoiseMode {
-  std::vector<float> background;  // empty: off; one value: every view; else one per view
-  int likelihood = 0;
-  bool on() const {
-    if (likelihood) return true;
-    for (float b : background)
-      if (b != 0.f) return true;
-    return false;
-  }
-};
-static std::mutex g_nm_mu;
-static NoiseMode g_nm;
-static NoiseMode current_nm() {
-  std::lock_guard<std::mutex> lk(g_nm_mu);
-  return g_nm;
-}
-static thread_local int t_call_nm = -1;  // the call this thread runs has the noise model on (1) or off (0); -1 outside a call
-static bool call_nm_on() { return t_call_nm < 0 ? current_nm().on() : t_call_nm != 0; }
-// a call whose view count the per-view backgrounds do not match: refused before psi is touched
-static void check_background_count(const NoiseMode& nm, int V) {
-  const size_t n = nm.background.size();
-  if (n > 1 && n != (size_t)V)
-    throw std::invalid_argument(std::to_string(n) + " background values (mvn_set_background) for a call of " +
-                                std::to_string(V) + " views");
-}
-struct ConvRecord {
-  int iterations_run = 0;
-  std::vector<double> like;    // noise model on: {D, Y, M} per (sweep run, view)
-  int like_views = 0;
-  std::vector<double> rows;    // {S, M, P} per sweep run
-  std::vector<double> alphas;  // acceleration on: a_k per sweep run
-};
 // the last deconvolution this thread completed (inplace_gpu_deconvolve, or the wait of a ticket)
-static thread_local ConvRecord t_last_conv;
+static thread_local LoopResult t_last_conv;
+// the read-out of a record: min(rows, capacity) rows of `width` doubles; returns the rows there are
+static int copy_rows(const std::vector<double>& from, int width, double* to, int capacity) {
+  const int rows = (int)(from.size() / (size_t)width);
+  const size_t n = (size_t)width * (size_t)std::min(rows, capacity);
+  if (n) std::memcpy(to, from.data(), n * sizeof(double));
+  return rows;
+}
 
 // ---- image storage (mvn_set_image_storage): captured at the start of a described call ----
 static std::atomic<int> g_image_storage{0};
 // per view: a described call in storage mode `mode` wants this image kept as uint16
 static bool keeps_u16(const StackRef& image, int mode) { return mode == 1 && image.u16 && !image.broadcast(); }
 
-static MemoryQuery memory_query(const shape_t& ext, const workspace& input, size_t embed_floats,
-                                const std::vector<char>& keep_u16 = std::vector<char>()) {
+static MemoryQuery memory_query(const shape_t& ext, const workspace& input, const LoopOptions& loop,
+                                size_t embed_floats, const std::vector<char>& keep_u16) {
   MemoryQuery q;
   q.image_u16 = keep_u16;
   q.ext = ext;
   q.embed_floats = embed_floats;
-  q.stats_rows = call_tolerance() >= 0. ? std::max(input.num_iterations_, 1) : 0;
-  q.accel_rows = call_accel() ? std::max(input.num_iterations_, 1) : 0;
-  q.tv = call_reg_kind() == 1 && input.lambda_ > 0.;
-  q.nm_rows = call_nm_on() ? std::max(input.num_iterations_, 1) : 0;
+  q.loop = loop;
+  q.iterations = std::max(input.num_iterations_, 1);
+  q.lambda = input.lambda_;
   q.kernels = call_kernels(input);
   return q;
 }
@@ -245,10 +208,10 @@ static bool reusable(const Engine& e, const shape_t& ext, int V) {
 
 // caller holds device_mutex(dev); the auto / stream modes of take_engine
 static std::unique_ptr<Engine> plan_engine(int key, int dev, const shape_t& ext, size_t embed_floats,
-                                           const workspace& input, int mode, const std::vector<char>& keep_u16,
-                                           bool use_budget = true) {
+                                           const workspace& input, const LoopOptions& loop, int mode,
+                                           const std::vector<char>& keep_u16, bool use_budget = true) {
   const int V = input.num_views_;
-  MemoryQuery q = memory_query(ext, input, embed_floats, keep_u16);
+  MemoryQuery q = memory_query(ext, input, loop, embed_floats, keep_u16);
   const FormRule rule = call_rule(ext, dev);
   auto need = [&](int s, int ring) {
     q.streamed = s;
@@ -309,11 +272,12 @@ static std::unique_ptr<Engine> plan_engine(int key, int dev, const shape_t& ext,
 // shape is freed BEFORE the free memory is read -- so that "does not fit" is said here, before any
 // work is queued, not by a failing hipMalloc on the staging thread.
 static std::unique_ptr<Engine> take_engine(int key, int dev, const shape_t& ext, int V, size_t embed_floats,
-                                           const workspace& input, int mem_mode, const std::vector<char>& keep_u16) {
+                                           const workspace& input, const LoopOptions& loop, int mem_mode,
+                                           const std::vector<char>& keep_u16) {
   // (MVN_MEM_EXACT: resident, priced by the exact model - a described call with stacks in device memory)
   if (mem_mode == MVN_MEM_EXACT)
-    return plan_engine(key, dev, ext, embed_floats, input, MVN_MEM_STREAM + 1, keep_u16, false);
-  if (mem_mode != MVN_MEM_RESIDENT) return plan_engine(key, dev, ext, embed_floats, input, mem_mode, keep_u16);
+    return plan_engine(key, dev, ext, embed_floats, input, loop, MVN_MEM_STREAM + 1, keep_u16, false);
+  if (mem_mode != MVN_MEM_RESIDENT) return plan_engine(key, dev, ext, embed_floats, input, loop, mem_mode, keep_u16);
   std::unique_ptr<Engine> e = pop_cached_engine(key);  // key = device + lane * kLaneStride
   Layout L(ext[0], ext[1], ext[2]);
   if (e && reusable(*e, ext, V) && e->streamed_count() == 0) {
@@ -710,64 +674,29 @@ static CallStacks workspace_stacks(const imageType* psi, const workspace& input)
   return cs;
 }
 
-// what a call captures at its start: the convergence tolerance, the acceleration mode and the regulariser
-struct LoopMode {
-  double tol = -1.;
-  int accel = 0;
-  RegMode reg;
-  NoiseMode nm;
-  static LoopMode current() {
-    LoopMode m;
-    m.nm = current_nm();
-    m.tol = g_conv_tol.load();
-    m.accel = g_accel.load();
-    m.reg = current_reg();
-    return m;
-  }
-};
-
-// (the caller has checked the workspace: check_workspace)
+// (the caller has checked the workspace: check_workspace; loop: the switches as the call captured them at its start)
 static void deconvolve_call(const workspace& input, const CallStacks& cs, int device, int lane, int pad_mode,
-                            LoopMode mode, ConvRecord* conv) {
-  const double tol = mode.tol;
-  const int accel = mode.accel;
-  conv->iterations_run = 0;
-  conv->rows.clear();
-  conv->alphas.clear();
-  conv->like.clear();
-  conv->like_views = 0;
-  const bool tv = mode.reg.kind == 1;
-  const bool nm = mode.nm.on();
-  struct LoopScope {  // (the memory model of this call counts the statistics, acceleration and TV buffers: memory_query)
-    LoopScope(double t, int a, int r, int n) { t_call_tol = t, t_call_accel = a, t_call_reg_kind = r, t_call_nm = n; }
-    ~LoopScope() { t_call_tol = NAN, t_call_accel = -1, t_call_reg_kind = -1, t_call_nm = -1; }
-  } loop_scope(tol, accel, mode.reg.kind, nm ? 1 : 0);
+                            const LoopOptions& loop, LoopResult* conv) {
+  *conv = LoopResult();
   {
     const int V = input.num_views_;
     if (V == 0 || input.num_iterations_ <= 0) return;  // 0 iterations returns psi unchanged
-    check_tv_lambda(mode.reg.kind, input.lambda_);
-    check_background_count(mode.nm, V);
+    loop.check_call(V, input.lambda_, LoopOptions::kAbi);  // (refused before psi is touched)
     shape_t dims, ext;
     int off[3] = {0, 0, 0};
-    if (lane == 0) {  // (the second lane belongs to the block pipeline of mvn_deconvolve_submit)
-      const std::vector<int> devs = multi_devices_from_env();
-      // the slab drivers keep no convergence statistics: such a call runs on one device
-      if (!devs.empty() && tol >= 0. && trace_on())
-        std::printf("[lmvn::trace] MVN_DEVICES: convergence statistics on - one device\n");
-      // ... take dense float32 stacks in host memory only
-      bool plain = !devs.empty() && plain_stack(cs.psi, input.data_[0].image_dims_);
+    const std::vector<int> devs = lane == 0 ? multi_devices_from_env() : std::vector<int>();
+    if (!devs.empty()) {  // (the second lane belongs to the block pipeline of mvn_deconvolve_submit)
+      // the slab drivers know none of the loop's switches, and take dense float32 stacks in host memory only
+      const char* why = loop.needs_single_device();
+      bool plain = plain_stack(cs.psi, input.data_[0].image_dims_);
       for (int v = 0; plain && v < V; ++v)
         plain = plain_stack(cs.image[(size_t)v], input.data_[v].image_dims_) &&
                 plain_stack(cs.weights[(size_t)v], input.data_[v].image_dims_);
-      if (!devs.empty() && !plain && trace_on())
-        std::printf("[lmvn::trace] MVN_DEVICES: described stacks - one device\n");
-      // ... and no acceleration
-      if (!devs.empty() && accel && trace_on()) std::printf("[lmvn::trace] MVN_DEVICES: acceleration on - one device\n");
-      // ... and no total variation
-      if (!devs.empty() && tv && trace_on()) std::printf("[lmvn::trace] MVN_DEVICES: total variation on - one device\n");
-      // ... and no noise model
-      if (!devs.empty() && nm && trace_on()) std::printf("[lmvn::trace] MVN_DEVICES: noise model on - one device\n");
-      if (plain && tol < 0. && !accel && !tv && !nm) {
+      if (why || !plain) {
+        if (trace_on())
+          std::printf("[lmvn::trace] MVN_DEVICES: %s%s - one device\n", why ? why : "described stacks",
+                      why ? " on" : "");
+      } else {
         call_extents(input, pad_mode, -1, &dims, &ext, off);  // (the slabs run on plans of their own extents)
         if (multi_device_call((imageType*)cs.psi.ptr, input, dims, ext, off, pad_mode, devs)) return;
       }
@@ -783,12 +712,11 @@ static void deconvolve_call(const workspace& input, const CallStacks& cs, int de
     // on failure the engine is simply dropped
     const bool scratch = cs.need_scratch;
     std::unique_ptr<Engine> eng_owner = take_engine(
-        key, dev, ext, V, embedded && scratch ? (size_t)dims[0] * (size_t)dims[1] * (size_t)dims[2] : 0, input, mem_mode,
-        cs.keep_u16);
+        key, dev, ext, V, embedded && scratch ? (size_t)dims[0] * (size_t)dims[1] * (size_t)dims[2] : 0, input, loop,
+        mem_mode, cs.keep_u16);
     Engine& eng = *eng_owner;
     eng.begin_call();
-    eng.set_regularization(mode.reg.kind, mode.reg.epsilon);
-    eng.set_noise_model(mode.nm.background.data(), (int)mode.nm.background.size(), mode.nm.likelihood != 0);
+    eng.set_options(loop);  // (an engine that comes back from TV gives up the factor volume before it allocates)
     eng.set_image_storage(cs.storage);
     eng.plan_image_types(cs.keep_u16);
     // stacks are embedded into / cropped out of the padded volume by the transfers themselves
@@ -810,9 +738,7 @@ static void deconvolve_call(const workspace& input, const CallStacks& cs, int de
                      d.kernel2_dims_);
       }
       eng.set_psi(cs.psi);
-      conv->iterations_run = eng.iterate(input.num_iterations_, input.lambda_, input.minValue_, tol, &conv->rows, accel,
-                                         accel ? &conv->alphas : nullptr);
-      conv->like = eng.last_likelihood(), conv->like_views = V;
+      eng.iterate(input.num_iterations_, input.lambda_, input.minValue_, loop, conv);
       eng.sync();
       eng.get_psi(cs.psi);
       give_back_engine(key, std::move(eng_owner));
@@ -864,10 +790,8 @@ static void deconvolve_call(const workspace& input, const CallStacks& cs, int de
     });
     std::exception_ptr main_err;
     try {
-      conv->iterations_run = eng.iterate(input.num_iterations_, input.lambda_, input.minValue_, tol, &conv->rows, accel,
-                                         accel ? &conv->alphas : nullptr);
-      conv->like = eng.last_likelihood(), conv->like_views = V;
-      if (conv->iterations_run < input.num_iterations_) eng.end_streaming();  // (an early stop)
+      eng.iterate(input.num_iterations_, input.lambda_, input.minValue_, loop, conv);
+      if (conv->ran < input.num_iterations_) eng.end_streaming();  // (an early stop)
     } catch (...) {
       main_err = std::current_exception();
       eng.abort_streaming();  // (an uploader waiting for a ring slot that will not be freed)
@@ -888,22 +812,22 @@ static void deconvolve_call(const workspace& input, const CallStacks& cs, int de
 }
 
 // the call of the reference's entry points (the record is empty again before the workspace is looked at)
-static void workspace_call(imageType* psi, const workspace& input, int device, int lane, int pad_mode, LoopMode mode,
-                           ConvRecord* conv) {
-  *conv = ConvRecord();
-  deconvolve_call(input, workspace_stacks(psi, input), device, lane, pad_mode, mode, conv);
+static void workspace_call(imageType* psi, const workspace& input, int device, int lane, int pad_mode,
+                           const LoopOptions& loop, LoopResult* conv) {
+  *conv = LoopResult();
+  deconvolve_call(input, workspace_stacks(psi, input), device, lane, pad_mode, loop, conv);
 }
 
 void inplace_gpu_deconvolve(imageType* psi, struct workspace input, int device) {
   guarded("inplace_gpu_deconvolve", [&] {
-    const LoopMode mode = LoopMode::current();
+    const LoopOptions mode = current_loop();
     workspace_call(psi, input, device, 0, current_pad_mode(), mode, &t_last_conv);
   });
 }
 
 int mvn_deconvolve_described(void* psi, struct workspace input, const mvn_call_desc* desc, int device) {
   return guarded("mvn_deconvolve_described", [&] {
-    const LoopMode mode = LoopMode::current();
+    const LoopOptions mode = current_loop();
     if (!desc) {
       workspace_call((imageType*)psi, input, device, 0, current_pad_mode(), mode, &t_last_conv);
       return;
@@ -956,8 +880,8 @@ struct DeconvJob {
   std::vector<view_data> views;  // the caller's view_data array and dims, copied at submit
   std::vector<int> dims;
   workspace ws;
-  LoopMode mode;     // the convergence tolerance and the acceleration mode at submit
-  ConvRecord conv;   // moves into the waiting thread's record
+  LoopOptions mode;  // the switches of the loop at submit
+  LoopResult conv;   // moves into the waiting thread's record
 };
 std::mutex& jobs_mutex() {
   static std::mutex* m = new std::mutex();
@@ -993,7 +917,7 @@ int mvn_deconvolve_submit(imageType* psi, struct workspace input, int device, lo
     job->ws.data_ = job->views.data();
     const int dev = pick_device(device);
     const int pad_mode = current_pad_mode();  // the policy in force at submit time
-    job->mode = LoopMode::current();           // ... and the tolerance and the acceleration mode
+    job->mode = current_loop();                // ... and the switches of the loop
     static std::atomic<long long> next_ticket{1};
     const long long id = next_ticket.fetch_add(1);
     static std::mutex lane_mu;
@@ -1041,15 +965,14 @@ int mvn_deconvolve_wait(long long ticket) {
 
 int mvn_set_convergence(double tolerance) {
   return guarded("mvn_set_convergence", [&] {
-    if (std::isnan(tolerance)) throw std::invalid_argument("tolerance is NaN");
-    g_conv_tol.store(tolerance < 0. ? -1. : tolerance);
+    edit_loop([&](LoopOptions& o) { o.tolerance = tolerance < 0. ? -1. : tolerance; });
   });
 }
 
 int mvn_get_convergence(double* tolerance) {
   return guarded("mvn_get_convergence", [&] {
     if (!tolerance) throw std::invalid_argument("null tolerance");
-    *tolerance = g_conv_tol.load();
+    *tolerance = current_loop().tolerance;
   });
 }
 
@@ -1057,26 +980,20 @@ int mvn_last_convergence(int* iterations_run, double* stats, int capacity) {
   int rows = 0;
   const int rc = guarded("mvn_last_convergence", [&] {
     if (capacity < 0 || (capacity > 0 && !stats)) throw std::invalid_argument("bad statistics buffer");
-    const ConvRecord& c = t_last_conv;
-    if (iterations_run) *iterations_run = c.iterations_run;
-    rows = (int)(c.rows.size() / 3);
-    const size_t n = 3 * (size_t)std::min(rows, capacity);
-    if (n) std::memcpy(stats, c.rows.data(), n * sizeof(double));
+    if (iterations_run) *iterations_run = t_last_conv.ran;
+    rows = copy_rows(t_last_conv.rows, 3, stats, capacity);
   });
   return rc < 0 ? rc : rows;
 }
 
 int mvn_set_acceleration(int mode) {
-  return guarded("mvn_set_acceleration", [&] {
-    if (mode != 0 && mode != 1) throw std::invalid_argument("acceleration mode must be 0 (off) or 1 (vector extrapolation)");
-    g_accel.store(mode);
-  });
+  return guarded("mvn_set_acceleration", [&] { edit_loop([&](LoopOptions& o) { o.accel = mode; }); });
 }
 
 int mvn_get_acceleration(int* mode) {
   return guarded("mvn_get_acceleration", [&] {
     if (!mode) throw std::invalid_argument("null mode");
-    *mode = g_accel.load();
+    *mode = current_loop().accel;
   });
 }
 
@@ -1084,32 +1001,29 @@ int mvn_last_acceleration(double* alphas, int capacity) {
   int rows = 0;
   const int rc = guarded("mvn_last_acceleration", [&] {
     if (capacity < 0 || (capacity > 0 && !alphas)) throw std::invalid_argument("bad alpha buffer");
-    const ConvRecord& c = t_last_conv;
-    rows = (int)c.alphas.size();
-    const size_t n = (size_t)std::min(rows, capacity);
-    if (n) std::memcpy(alphas, c.alphas.data(), n * sizeof(double));
+    rows = copy_rows(t_last_conv.alphas, 1, alphas, capacity);
   });
   return rc < 0 ? rc : rows;
 }
 
+// (epsilon belongs to total variation: the other kind keeps none)
+static void set_regulariser(LoopOptions& o, int kind, double epsilon) {
+  o.reg_kind = kind;
+  o.epsilon = kind == MVN_REG_TV ? epsilon : 0.;
+}
+
 int mvn_set_regularization(int kind, double epsilon) {
   return guarded("mvn_set_regularization", [&] {
-    if (kind != MVN_REG_TIKHONOV && kind != MVN_REG_TV)
-      throw std::invalid_argument("regularisation kind must be 0 (Tikhonov) or 1 (total variation)");
-    if (kind == MVN_REG_TV && !(epsilon > 0. && std::isfinite(epsilon)))
-      throw std::invalid_argument("total-variation regularisation needs a finite epsilon > 0");
-    std::lock_guard<std::mutex> lk(g_reg_mu);
-    g_reg.kind = kind;
-    g_reg.epsilon = kind == MVN_REG_TV ? epsilon : 0.;
+    edit_loop([&](LoopOptions& o) { set_regulariser(o, kind, epsilon); });
   });
 }
 
 int mvn_get_regularization(int* kind, double* epsilon) {
   return guarded("mvn_get_regularization", [&] {
     if (!kind || !epsilon) throw std::invalid_argument("null argument");
-    const RegMode r = current_reg();
-    *kind = r.kind;
-    *epsilon = r.epsilon;
+    const LoopOptions o = current_loop();
+    *kind = o.reg_kind;
+    *epsilon = o.epsilon;
   });
 }
 
@@ -1117,11 +1031,7 @@ int mvn_set_background(const float* values, int count) {
   return guarded("mvn_set_background", [&] {
     if (count < 0) throw std::invalid_argument("negative count");
     if (!values) count = 0;
-    for (int i = 0; i < count; ++i)
-      if (!(values[i] >= 0.f && std::isfinite(values[i])))
-        throw std::invalid_argument("background values must be finite and >= 0");
-    std::lock_guard<std::mutex> lk(g_nm_mu);
-    g_nm.background.assign(values, values + count);
+    edit_loop([&](LoopOptions& o) { o.background.assign(values, values + count); });
   });
 }
 
@@ -1129,25 +1039,21 @@ int mvn_get_background(float* values, int capacity) {
   int count = 0;
   const int rc = guarded("mvn_get_background", [&] {
     if (capacity < 0 || (capacity > 0 && !values)) throw std::invalid_argument("bad background buffer");
-    const NoiseMode m = current_nm();
-    count = (int)m.background.size();
-    for (int i = 0; i < std::min(count, capacity); ++i) values[i] = m.background[(size_t)i];
+    const LoopOptions o = current_loop();
+    count = (int)o.background.size();
+    for (int i = 0; i < std::min(count, capacity); ++i) values[i] = o.background[(size_t)i];
   });
   return rc < 0 ? rc : count;
 }
 
 int mvn_set_likelihood(int mode) {
-  return guarded("mvn_set_likelihood", [&] {
-    if (mode != 0 && mode != 1) throw std::invalid_argument("likelihood mode must be 0 (off) or 1 (on)");
-    std::lock_guard<std::mutex> lk(g_nm_mu);
-    g_nm.likelihood = mode;
-  });
+  return guarded("mvn_set_likelihood", [&] { edit_loop([&](LoopOptions& o) { o.likelihood = mode; }); });
 }
 
 int mvn_get_likelihood(int* mode) {
   return guarded("mvn_get_likelihood", [&] {
     if (!mode) throw std::invalid_argument("null mode");
-    *mode = current_nm().likelihood;
+    *mode = current_loop().likelihood;
   });
 }
 
@@ -1155,12 +1061,9 @@ int mvn_last_likelihood(int* iterations_run, int* num_views, double* stats, int 
   int rows = 0;
   const int rc = guarded("mvn_last_likelihood", [&] {
     if (capacity_rows < 0 || (capacity_rows > 0 && !stats)) throw std::invalid_argument("bad statistics buffer");
-    const ConvRecord& c = t_last_conv;
-    if (iterations_run) *iterations_run = c.iterations_run;
-    if (num_views) *num_views = c.like_views;
-    rows = (int)(c.like.size() / 3);
-    const size_t n = 3 * (size_t)std::min(rows, capacity_rows);
-    if (n) std::memcpy(stats, c.like.data(), n * sizeof(double));
+    if (iterations_run) *iterations_run = t_last_conv.ran;
+    if (num_views) *num_views = t_last_conv.views;
+    rows = copy_rows(t_last_conv.like, 3, stats, capacity_rows);
   });
   return rc < 0 ? rc : rows;
 }
@@ -1172,8 +1075,8 @@ int mvn_tv_factor(int device, const int dims[3], const float* psi, double lambda
   return guarded("mvn_tv_factor", [&] {
     if (!dims || !psi || !t) throw std::invalid_argument("null argument");
     if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1) throw std::invalid_argument("extents must be positive");
-    if (!(epsilon > 0. && std::isfinite(epsilon))) throw std::invalid_argument("epsilon must be finite and > 0");
-    check_tv_lambda(1, lambda);
+    if (!LoopOptions::tv_epsilon_ok(epsilon)) throw std::invalid_argument("epsilon must be finite and > 0");
+    LoopOptions::check_tv_lambda(lambda, LoopOptions::kAbi);
     const int dev = pick_device(device);
     std::lock_guard<std::mutex> lk(device_mutex(dev));
     be::set_device(dev);
@@ -1188,13 +1091,7 @@ int mvn_tv_factor(int device, const int dims[3], const float* psi, double lambda
       s = be::stream_create();
       be::dzero(du, bytes, s);
       be::h2d_2d(du, pitch, psi, width, width, (size_t)L.rows, s);
-      TvParams p;
-      std::memset(&p, 0, sizeof(p));
-      p.psi = du, p.t = dt;
-      p.d0 = L.d0, p.d1 = L.d1, p.d2 = L.d2, p.RP = L.RP;
-      p.lambda = (float)lambda;
-      p.e2 = (float)epsilon * (float)epsilon;
-      be::launch_tv(p, s);
+      be::launch_tv(tv_params(L, du, dt, lambda, epsilon), s);
       be::d2h_2d(t, width, dt, pitch, width, (size_t)L.rows, s);
       be::stream_sync(s);
     } catch (...) {
@@ -1233,12 +1130,7 @@ int mvn_tv_time(int device, const int dims[3], int reps, float* ms) {
       std::vector<float> h(L.real_floats());
       for (size_t i = 0; i < h.size(); ++i) h[i] = 1.f + 0.001f * (float)(i % 977) + 0.01f * (float)(i % 13);
       be::h2d(du, h.data(), bytes, s);
-      TvParams p;
-      std::memset(&p, 0, sizeof(p));
-      p.psi = du, p.t = dt;
-      p.d0 = L.d0, p.d1 = L.d1, p.d2 = L.d2, p.RP = L.RP;
-      p.lambda = 0.005f;
-      p.e2 = 1e-4f;
+      const TvParams p = tv_params(L, du, dt, 0.005, 0.01);
       const long plane = (long)L.d1 * L.RP;
       for (int kind = 0; kind < 2; ++kind) {
         for (int i = -1; i < reps; ++i) {  // (one launch to warm up)
@@ -1327,7 +1219,8 @@ static void deconvolve_memory(struct workspace input, const mvn_call_desc* desc,
   shape_t dims, ext;
   int off[3];
   call_extents(input, current_pad_mode(), dev, &dims, &ext, off);
-  MemoryQuery q = memory_query(ext, input, embed_floats_of(dims, ext), keep);
+  // (outside a call: the process-wide switches, whatever calls other threads are running)
+  MemoryQuery q = memory_query(ext, input, current_loop(), embed_floats_of(dims, ext), keep);
   q.streamed = streamed_views;
   q.ring = streamed_views > 0 ? 2 : 0;
   *bytes = Engine::memory_need(q, call_rule(ext, dev));
@@ -2127,38 +2020,49 @@ int mvn_engine_iterate(mvn_engine* e, int iterations, double lambda, float min_v
   MVN_ENGINE_CALL("mvn_engine_iterate", E.iterate(iterations, lambda, min_value));
 }
 
+// one iterate() under the options the engine holds plus what the call itself asks for; returns the sweeps run
+static int engine_iterate(Engine& E, int iterations, double lambda, float min_value, double tolerance, int accel,
+                          double* stats, double* alphas) {
+  LoopOptions o = E.options();
+  o.tolerance = tolerance, o.accel = accel;
+  LoopResult r;
+  E.iterate(iterations, lambda, min_value, o, &r);
+  if (stats && !r.rows.empty()) std::memcpy(stats, r.rows.data(), r.rows.size() * sizeof(double));
+  if (alphas && !r.alphas.empty()) std::memcpy(alphas, r.alphas.data(), r.alphas.size() * sizeof(double));
+  return r.ran;
+}
+
 int mvn_engine_iterate_converge(mvn_engine* e, int iterations, double lambda, float min_value, double tolerance,
                                 int* iterations_run, double* stats) {
   MVN_ENGINE_CALL("mvn_engine_iterate_converge", {
-    if (std::isnan(tolerance)) throw std::invalid_argument("tolerance is NaN");
     if (tolerance >= 0. && !stats) throw std::invalid_argument("null statistics buffer");
-    std::vector<double> rows;
-    const int ran = E.iterate(iterations, lambda, min_value, tolerance, &rows);
+    const int ran = engine_iterate(E, iterations, lambda, min_value, tolerance, 0, stats, nullptr);
     if (iterations_run) *iterations_run = ran;
-    if (!rows.empty()) std::memcpy(stats, rows.data(), rows.size() * sizeof(double));
   });
 }
 
 int mvn_engine_iterate_accelerated(mvn_engine* e, int iterations, double lambda, float min_value, double tolerance,
                                    int* iterations_run, double* stats, double* alphas) {
   MVN_ENGINE_CALL("mvn_engine_iterate_accelerated", {
-    if (std::isnan(tolerance)) throw std::invalid_argument("tolerance is NaN");
-    std::vector<double> rows, al;
-    const int ran = E.iterate(iterations, lambda, min_value, tolerance, &rows, 1, alphas ? &al : nullptr);
+    const int ran = engine_iterate(E, iterations, lambda, min_value, tolerance, 1, stats, alphas);
     if (iterations_run) *iterations_run = ran;
-    if (stats && !rows.empty()) std::memcpy(stats, rows.data(), rows.size() * sizeof(double));
-    if (alphas && !al.empty()) std::memcpy(alphas, al.data(), al.size() * sizeof(double));
   });
 }
 
 int mvn_engine_set_regularization(mvn_engine* e, int kind, double epsilon) {
-  MVN_ENGINE_CALL("mvn_engine_set_regularization", E.set_regularization(kind, epsilon));
+  MVN_ENGINE_CALL("mvn_engine_set_regularization", {
+    LoopOptions o = E.options();
+    set_regulariser(o, kind, epsilon);
+    E.set_options(o);
+  });
 }
 
 int mvn_engine_set_noise_model(mvn_engine* e, const float* background, int likelihood) {
   MVN_ENGINE_CALL("mvn_engine_set_noise_model", {
-    if (likelihood != 0 && likelihood != 1) throw std::invalid_argument("likelihood mode must be 0 (off) or 1 (on)");
-    E.set_noise_model(background, background ? E.num_views() : 0, likelihood != 0);
+    LoopOptions o = E.options();
+    o.background.assign(background, background + (background ? E.num_views() : 0));
+    o.likelihood = likelihood;
+    E.set_options(o);
   });
 }
 
@@ -2169,11 +2073,9 @@ int mvn_engine_last_likelihood(mvn_engine* e, int* iterations_run, double* stats
     if (capacity_rows < 0 || (capacity_rows > 0 && !stats)) throw std::invalid_argument("bad statistics buffer");
     Engine& E = *e->impl;
     E.sync();
-    const std::vector<double>& r = E.last_likelihood();
-    if (iterations_run) *iterations_run = E.last_likelihood_sweeps();
-    rows = (int)(r.size() / 3);
-    const size_t n = 3 * (size_t)std::min(rows, capacity_rows);
-    if (n) std::memcpy(stats, r.data(), n * sizeof(double));
+    const LoopResult& r = E.last_result();
+    if (iterations_run) *iterations_run = r.like.empty() ? 0 : r.ran;
+    rows = copy_rows(r.like, 3, stats, capacity_rows);
   });
   return rc < 0 ? rc : rows;
 }

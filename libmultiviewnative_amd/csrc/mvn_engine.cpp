@@ -800,8 +800,7 @@ Engine::~Engine() {
     if (stream_) be::stream_sync(stream_);
   } catch (...) {
   }
-  stats_free();
-  nm_free();
+  loop_.release(0, LoopState::N_BUFFERS);
   for (size_t v = 0; v < views_.size(); ++v) {
     if (stream_pos_[v] < 0) {  // (a streamed view's pointers are borrowed from the ring during its update)
       be::dfree(views_[v].image);
@@ -837,7 +836,6 @@ Engine::~Engine() {
   be::dfree(poison_own_);
   be::graph_destroy(sweep_graph_);
   if (!delta_external_) be::dfree(delta_);
-  be::dfree(tv_);
   try {
     if (side_.s) be::stream_sync(side_.s);
   } catch (...) {
@@ -1756,11 +1754,41 @@ void Engine::ring_release(ViewSlot& s) {
 static const size_t kMemSlack = (size_t)1 << 20;
 static size_t alloc_rounded(size_t b) { return (b + 4095) & ~(size_t)4095; }
 
-// Every workgroup of an update pass writes one record, and no launch has more workgroups than the volume has rows.
-static long stats_cap(const Layout& L) { return (long)L.rows; }
+// The table of the loop state: which buffers the switches of a call need, and how large (a buffer of 0 bytes is not
+// needed).  Read by Engine::memory_need and by Engine::iterate alike.
+void LoopState::bytes_of(const Layout& L, int V, int iterations, double lambda, const LoopOptions& o,
+                         size_t bytes[N_BUFFERS]) {
+  const size_t mb = L.real_floats() * sizeof(float), n = (size_t)std::max(iterations, 0);
+  const size_t records = 3 * sizeof(double) * (size_t)record_cap(L) * (size_t)V, counts = sizeof(unsigned) * (size_t)V;
+  std::fill(bytes, bytes + N_BUFFERS, (size_t)0);
+  if (o.stats_on()) {
+    bytes[STAT_REC] = records, bytes[STAT_COUNT] = counts;
+    bytes[STAT_OUT] = 3 * sizeof(double) * std::max(n, (size_t)1);
+  }
+  if (n == 0) return;  // (the other switches add nothing to a call without sweeps)
+  if (o.noise_model_on()) {
+    bytes[NM_REC] = records, bytes[NM_COUNT] = counts;
+    bytes[NM_OUT] = 3 * sizeof(double) * n * (size_t)V;
+  }
+  if (o.accel_on()) {
+    bytes[X_PREV] = bytes[G_PREV] = bytes[Y_SAVE] = mb;
+    bytes[ACCEL_REC] = 2 * sizeof(double) * (size_t)accel_records(L);
+    bytes[ALPHA] = sizeof(float) * n;
+  }
+  if (o.tv_on(lambda)) bytes[TV] = mb;
+}
 
-// workgroups of the extrapolation's pass A (mvn_extrapolate.hpp): a function of the extents only
-static long accel_records(const Layout& L) { return mvn_accel_blocks((long)L.real_floats(), L.RP == L.d2 ? 4 : 2); }
+void LoopState::allocate(const size_t bytes[N_BUFFERS]) {
+  for (int b = 0; b < N_BUFFERS; ++b)
+    if (bytes[b] && !buf[b]) buf[b] = be::dmalloc(bytes[b]);
+}
+
+void LoopState::release(int first, int last) {
+  for (int b = first; b < last; ++b) {
+    be::dfree(buf[b]);
+    buf[b] = nullptr;
+  }
+}
 
 size_t Engine::memory_need(const MemoryQuery& q, const FormRule& rule) {
   const Layout& L = rule.L;
@@ -1807,22 +1835,9 @@ size_t Engine::memory_need(const MemoryQuery& q, const FormRule& rule) {
   }
   add(scr, 1);                                        // the engine's one tap scratch
   if (spectra && ax0_fixed(L, rule.plan_fixed)) add(mb, 1);  // re-tiling scratch of the staging thread
-  if (q.stats_rows > 0) {  // convergence statistics (Engine::iterate)
-    add(3 * sizeof(double) * (size_t)stats_cap(L) * (size_t)V, 1);
-    add(sizeof(unsigned) * (size_t)V, 1);
-    add(3 * sizeof(double) * (size_t)q.stats_rows, 1);
-  }
-  if (q.tv) add(mb, 1);  // the total-variation factor volume (Engine::set_regularization)
-  if (q.nm_rows > 0) {   // noise model (Engine::iterate): records, counts, rows
-    add(3 * sizeof(double) * (size_t)stats_cap(L) * (size_t)V, 1);
-    add(sizeof(unsigned) * (size_t)V, 1);
-    add(3 * sizeof(double) * (size_t)q.nm_rows * (size_t)V, 1);
-  }
-  if (q.accel_rows > 0) {  // vector extrapolation (Engine::iterate)
-    add(mb, 3);  // x_prev, g, the saved y
-    add(2 * sizeof(double) * (size_t)accel_records(L), 1);
-    add(sizeof(float) * (size_t)q.accel_rows, 1);
-  }
+  size_t loop[LoopState::N_BUFFERS];  // what the switches of the loop add (Engine::iterate)
+  LoopState::bytes_of(L, V, q.iterations, q.lambda, q.loop, loop);
+  for (size_t b : loop) add(b, 1);
   // (psi_spec_ and delta_ belong to the simultaneous steps of the view-sharded drivers: never allocated here)
   return total;
 }
@@ -1902,34 +1917,26 @@ void Engine::conv_pair(int v, double lambda, float min_value, int final_mode, in
   divide_epilogue(e1, s);
   e1.guard_zero_view = quotient_guard_ ? 1 : 0;
   // noise model: the same pass with the view's background in the forward model and the statistics of the window
-  const bool nm = nm_on_ && final_mode == MVN_EPI_UPDATE;
-  const MvnStatsParams st1 = nm ? nm_stats_for(v) : MvnStatsParams();
+  const bool nm = nm_records().on() && final_mode == MVN_EPI_UPDATE;
+  const MvnStatsParams st1 = nm ? params_for(nm_records(), v) : MvnStatsParams();
   if (nm) {
     e1.mode = e1.mode == MVN_EPI_DIVIDE_U16 ? MVN_EPI_DIVIDE_NM_U16 : MVN_EPI_DIVIDE_NM;
-    e1.background = nm_background_.empty() ? 0.f : nm_background_[(size_t)v];
+    e1.background = loop_.o.background_of(v);
   }
 
   EpilogueParams e2;
   std::memset(&e2, 0, sizeof(e2));
-  const bool stats = stats_on_ && final_mode == MVN_EPI_UPDATE;
-  const MvnStatsParams st2 = stats ? stats_for(v) : MvnStatsParams();
+  const bool stats = stat_records().on() && final_mode == MVN_EPI_UPDATE;
+  const MvnStatsParams st2 = stats ? params_for(stat_records(), v) : MvnStatsParams();
   e2.mode = stats ? MVN_EPI_UPDATE_STATS : final_mode;
   // total variation: the factor of psi as it stands now - psi does not change before this view's update pass -
   // multiplies the integral there; lambda is the TV weight and the Tikhonov branch stays off
-  const bool tv = tv_on_ && final_mode == MVN_EPI_UPDATE;
+  const bool tv = tv_volume() && final_mode == MVN_EPI_UPDATE;
   if (tv) {
-    const Layout& L = P.L;
-    TvParams t;
-    std::memset(&t, 0, sizeof(t));
-    t.psi = psi_;
-    t.t = tv_;
-    t.d0 = L.d0, t.d1 = L.d1, t.d2 = L.d2, t.RP = L.RP;
-    t.lambda = (float)lambda;
-    t.e2 = (float)reg_eps_ * (float)reg_eps_;
     ProfScope ps(prof, KK_TV, stream_);
-    be::launch_tv(t, stream_);
+    be::launch_tv(tv_params(P.L, psi_, tv_volume(), lambda, loop_.o.epsilon), stream_);
     e2.mode = stats ? MVN_EPI_UPDATE_STATS_TV : MVN_EPI_UPDATE_TV;
-    e2.tv = tv_;
+    e2.tv = tv_volume();
     lambda = 0.;
   }
   e2.scale = 1.f;
@@ -2031,8 +2038,8 @@ bool Engine::boundary_first() const {
 // 256^3 0.308 -> 0.305 ms per view update, against ~11 ms for capture and instantiation, which only
 // a long-lived engine (thousands of small view updates) earns back.  Hence opt-in: MVN_GRAPH=1
 // enables it, MVN_GRAPH_MAX_MB (default 160) bounds the volume.
-// the window of the statistics: the stacks inside the padded volume, or all of it
-MvnStatsParams Engine::stats_for(int v) const {
+// the records of view v's pass in r, and their window: the stacks inside the padded volume, or all of it
+MvnStatsParams Engine::params_for(const RecordSet& r, int v) const {
   const Layout& L = plan_->L;
   MvnStatsParams p;
   std::memset(&p, 0, sizeof(p));
@@ -2043,65 +2050,71 @@ MvnStatsParams Engine::stats_for(int v) const {
   p.n0 = (unsigned)(embedded_ ? host_dims_[0] : L.d0);
   p.n1 = (unsigned)(embedded_ ? host_dims_[1] : L.d1);
   p.n2 = (unsigned)(embedded_ ? host_dims_[2] : L.d2);
-  p.rec = stat_rec_ + 3 * (size_t)stat_cap_ * (size_t)v;
-  p.count = stat_count_ + v;
-  p.cap = stat_cap_;
+  p.rec = r.rec + 3 * (size_t)r.cap * (size_t)v;
+  p.count = r.count + v;
+  p.cap = r.cap;
   return p;
 }
 
-// the same window for the noise-model statistics of view v's divide pass
-MvnStatsParams Engine::nm_stats_for(int v) const {
-  MvnStatsParams p = stats_for(v);
-  p.rec = nm_rec_ + 3 * (size_t)nm_cap_ * (size_t)v;
-  p.count = nm_count_ + v;
-  p.cap = nm_cap_;
-  return p;
+bool LoopOptions::tv_epsilon_ok(double epsilon) { return epsilon > 0. && std::isfinite(epsilon); }
+
+void LoopOptions::check_tv_lambda(double lambda, const Voice& who) {
+  if (!(lambda >= 0. && lambda < 1. / 12.))
+    throw std::invalid_argument(std::string(who.prefix) + "total-variation regularisation needs 0 <= " + who.lambda +
+                                " < 1/12");
 }
 
-void Engine::nm_free() {
-  be::dfree(nm_rec_);
-  be::dfree(nm_count_);
-  be::dfree(nm_out_);
-  nm_rec_ = nm_out_ = nullptr;
-  nm_count_ = nullptr;
-  nm_on_ = false;
+void LoopOptions::validate(const Voice& who) const {
+  const std::string p = who.prefix;
+  // (the first three are arguments of C entry points under either API, and have always been reported in their words)
+  if (std::isnan(tolerance)) throw std::invalid_argument("tolerance is NaN");
+  if (accel != 0 && accel != 1)
+    throw std::invalid_argument("acceleration mode must be 0 (off) or 1 (vector extrapolation)");
+  if (likelihood != 0 && likelihood != 1) throw std::invalid_argument("likelihood mode must be 0 (off) or 1 (on)");
+  if (reg_kind != 0 && reg_kind != 1)
+    throw std::invalid_argument(p + "regularisation kind must be 0 (Tikhonov) or 1 (total variation)");
+  if (reg_kind == 1 && !tv_epsilon_ok(epsilon))
+    throw std::invalid_argument(p + "total-variation regularisation needs a finite epsilon > 0");
+  for (float b : background)
+    if (!(b >= 0.f && std::isfinite(b))) throw std::invalid_argument(p + "background values must be finite and >= 0");
 }
 
-bool Engine::noise_model_on() const {
-  if (nm_like_) return true;
-  for (float b : nm_background_)
-    if (b != 0.f) return true;
-  return false;
+void LoopOptions::check_call(int V, double lambda, const Voice& who) const {
+  if (reg_kind == 1) check_tv_lambda(lambda, who);
+  const size_t n = background.size();
+  if (n > 1 && n != (size_t)V)
+    throw std::invalid_argument(who.prefix + std::to_string(n) + " background values (mvn_set_background) for a call of "
+                                + std::to_string(V) + " views");
 }
 
-void Engine::refuse_nm(const char* what) const {
-  if (noise_model_on()) throw std::logic_error(std::string("mvn: ") + what + " with a noise model (background or likelihood)");
+const char* LoopOptions::needs_single_device() const {
+  if (stats_on()) return "convergence statistics";
+  if (accel_on()) return "acceleration";
+  if (reg_kind == 1) return "total variation";
+  return noise_model_on() ? "noise model" : nullptr;
 }
 
-void Engine::set_noise_model(const float* background, int count, bool likelihood) {
-  const int V = (int)views_.size();
-  if (count < 0 || (count > 0 && !background)) throw std::invalid_argument("mvn: bad background array");
-  if (count != 0 && count != 1 && count != V)
-    throw std::invalid_argument("mvn: " + std::to_string(count) + " background values for " + std::to_string(V) + " views");
-  for (int i = 0; i < count; ++i)
-    if (!(background[i] >= 0.f && std::isfinite(background[i])))
-      throw std::invalid_argument("mvn: background values must be finite and >= 0");
-  bool on = likelihood;
-  for (int i = 0; i < count; ++i) on = on || background[i] != 0.f;
-  if (on && halo_fn_)
-    throw std::logic_error("mvn: no noise model on a slab of a multi-device group (halo mode)");
-  nm_background_.clear();
-  for (int v = 0; v < V && count > 0; ++v) nm_background_.push_back(background[count == 1 ? 0 : v]);
-  nm_like_ = likelihood;
+void LoopOptions::refuse(const char* what) const {
+  const struct {
+    bool on;
+    const char *name, *held, *tail;
+  } switches[] = {{noise_model_on(), "noise model", "a noise model (background or likelihood)", " (halo mode)"},
+                  {reg_kind == 1, "total-variation regularisation", "total-variation regularisation", " (halo mode)"},
+                  {accel_on(), "acceleration", "acceleration", " (halo mode)"},
+                  {stats_on(), "convergence statistics", "convergence statistics", ""}};
+  for (const auto& s : switches) {
+    if (!s.on) continue;
+    if (what) throw std::logic_error(std::string("mvn: ") + what + " with " + s.held);
+    throw std::logic_error(std::string("mvn: no ") + s.name + " on a slab of a multi-device group" + s.tail);
+  }
 }
 
-void Engine::stats_free() {
-  be::dfree(stat_rec_);
-  be::dfree(stat_count_);
-  be::dfree(stat_out_);
-  stat_rec_ = stat_out_ = nullptr;
-  stat_count_ = nullptr;
-  stats_on_ = false;
+void Engine::set_options(const LoopOptions& o) {
+  o.validate(LoopOptions::kEngine);
+  if (halo_fn_) o.refuse();
+  be::set_device(device_);
+  if (o.reg_kind == 0) tv_free();
+  held_ = o;
 }
 
 void Engine::end_streaming() {
@@ -2113,136 +2126,71 @@ void Engine::end_streaming() {
 }
 
 void Engine::tv_free() {
-  if (!tv_) return;
+  if (!tv_volume()) return;
   be::stream_sync(stream_);  // (a pass that reads it may still be in flight)
   // a captured sweep of a TV call holds the volume's address (the pass's store target and the update's operand):
   // it goes with the volume, as in bind_poison, and the key below holds the address as well
   be::graph_destroy(sweep_graph_);
   sweep_graph_ = nullptr;
-  be::dfree(tv_);
-  tv_ = nullptr;
+  loop_.release(LoopState::TV, LoopState::TV + 1);
 }
 
-void Engine::refuse_tv(const char* what) const {
-  if (reg_kind_ == 1) throw std::logic_error(std::string("mvn: ") + what + " with total-variation regularisation");
-}
-
-void Engine::set_regularization(int kind, double epsilon) {
-  if (kind != 0 && kind != 1) throw std::invalid_argument("mvn: regularisation kind must be 0 (Tikhonov) or 1 (total variation)");
-  if (kind == 1 && !(epsilon > 0. && std::isfinite(epsilon)))
-    throw std::invalid_argument("mvn: total-variation regularisation needs a finite epsilon > 0");
-  if (kind == 1 && halo_fn_)
-    throw std::logic_error("mvn: no total-variation regularisation on a slab of a multi-device group (halo mode)");
-  be::set_device(device_);
-  if (kind == 0) tv_free();
-  reg_kind_ = kind;
-  reg_eps_ = kind == 1 ? epsilon : 0.;
-}
-
-void Engine::accel_free() {
-  be::dfree(accel_xprev_);
-  be::dfree(accel_g_);
-  be::dfree(accel_ysave_);
-  be::dfree(accel_rec_);
-  be::dfree(accel_alpha_);
-  accel_xprev_ = accel_g_ = accel_ysave_ = accel_alpha_ = nullptr;
-  accel_rec_ = nullptr;
-  accel_on_ = false;
-}
-
-// psi = x_k -> psi = y_k (mvn_extrapolate.hpp); a_k stays in accel_alpha_[k - 1]
+// psi = x_k -> psi = y_k (mvn_extrapolate.hpp); a_k stays in ALPHA[k - 1]
 void Engine::accel_extrapolate(int k, float min_value) {
   const Layout& L = plan_->L;
   AccelParams p;
   std::memset(&p, 0, sizeof(p));
-  p.psi = psi_, p.ysave = accel_ysave_, p.g = accel_g_, p.xprev = accel_xprev_;
+  p.psi = psi_, p.ysave = loop_.at<float>(LoopState::Y_SAVE), p.g = loop_.at<float>(LoopState::G_PREV);
+  p.xprev = loop_.at<float>(LoopState::X_PREV);
   p.n = (long)L.real_floats();
   p.RP = L.RP, p.d2 = L.d2;
   p.first = k == 1;
-  p.rec = accel_rec_;
-  p.alpha = accel_alpha_ + (k - 1);
+  p.rec = loop_.at<double>(LoopState::ACCEL_REC);
+  float* const alpha = loop_.at<float>(LoopState::ALPHA) + (k - 1);
+  p.alpha = alpha;
   p.min_value = min_value;
   be::launch_accel_a(p, stream_);
-  be::launch_accel_reduce(accel_rec_, accel_records(L), accel_alpha_ + (k - 1), stream_);
+  be::launch_accel_reduce(p.rec, LoopState::accel_records(L), alpha, stream_);
   be::launch_accel_b(p, stream_);
 }
 
-int Engine::iterate(int iterations, double lambda, float min_value, double tolerance, std::vector<double>* stats,
-                    int accel, std::vector<double>* alphas) {
+int Engine::iterate(int iterations, double lambda, float min_value, const LoopOptions& o, LoopResult* result) {
   be::set_device(device_);
-  if (accel != 0 && accel != 1) throw std::invalid_argument("mvn: acceleration mode must be 0 (off) or 1");
-  if (alphas) alphas->clear();
-  const bool st_on = tolerance >= 0.;
-  const bool ac_on = accel == 1 && iterations > 0;
-  nm_rows_.clear();
-  nm_ran_ = 0;
-  const bool nm_on = noise_model_on() && iterations > 0;
-  if (nm_on && halo_fn_) throw std::logic_error("mvn: no noise model on a slab of a multi-device group (halo mode)");
-  tv_on_ = false;
-  if (reg_kind_ == 1) {
-    if (halo_fn_) throw std::logic_error("mvn: no total-variation regularisation on a slab of a multi-device group (halo mode)");
-    // |div p| <= 6: below 1/12 the denominator 1 - lambda div p stays above 0.5 with no clamp in the kernel
-    if (!(lambda >= 0. && lambda < 1. / 12.))
-      throw std::invalid_argument("mvn: total-variation regularisation needs 0 <= lambda < 1/12");
-    tv_on_ = lambda > 0. && iterations > 0;
-    if (tv_on_ && !tv_) tv_ = (float*)be::dmalloc(plan_->main_bytes());
-    if (!tv_on_) tv_free();
-  }
-  if (accel == 1 && halo_fn_)
-    throw std::logic_error("mvn: no acceleration on a slab of a multi-device group (halo mode)");
-  if (st_on) {
-    if (halo_fn_) throw std::logic_error("mvn: no convergence statistics on a slab of a multi-device group");
-    const int V = (int)views_.size();
-    stats_free();
-    stat_cap_ = stats_cap(plan_->L);
-    stat_rec_ = (double*)be::dmalloc(3 * sizeof(double) * (size_t)stat_cap_ * (size_t)V);
-    stat_count_ = (unsigned*)be::dmalloc(sizeof(unsigned) * (size_t)V);
-    stat_out_ = (double*)be::dmalloc(3 * sizeof(double) * (size_t)std::max(iterations, 1));
-    stats_on_ = true;
-  }
-  try {
-    if (nm_on) {
-      const int V = (int)views_.size();
-      nm_free();
-      nm_cap_ = stats_cap(plan_->L);
-      nm_rec_ = (double*)be::dmalloc(3 * sizeof(double) * (size_t)nm_cap_ * (size_t)V);
-      nm_count_ = (unsigned*)be::dmalloc(sizeof(unsigned) * (size_t)V);
-      nm_out_ = (double*)be::dmalloc(3 * sizeof(double) * (size_t)iterations * (size_t)V);
-      nm_on_ = true;
-    }
-    if (ac_on) {
-      accel_free();
-      accel_on_ = true;
-      accel_xprev_ = (float*)be::dmalloc(plan_->main_bytes());
-      accel_g_ = (float*)be::dmalloc(plan_->main_bytes());
-      accel_ysave_ = (float*)be::dmalloc(plan_->main_bytes());
-      accel_rec_ = (double*)be::dmalloc(2 * sizeof(double) * (size_t)accel_records(plan_->L));
-      accel_alpha_ = (float*)be::dmalloc(sizeof(float) * (size_t)iterations);
-    }
-    const int ran = iterate_sweeps(iterations, lambda, min_value, tolerance, stats, alphas);
-    if (st_on) stats_free();
-    if (nm_on) nm_free();  // (iterate_sweeps has waited for the stream)
-    if (ac_on) {  // (the state lives for the call: the passes that use it have to be done before it goes)
-      be::stream_sync(stream_);
-      accel_free();
-    }
-    return ran;
-  } catch (...) {
-    if (st_on || ac_on || nm_on) {
+  const int V = (int)views_.size();
+  o.validate(LoopOptions::kEngine);
+  o.check_call(V, lambda, LoopOptions::kEngine);
+  if (halo_fn_) o.refuse();
+  last_ = LoopResult();
+  last_.views = V;
+  size_t bytes[LoopState::N_BUFFERS];
+  LoopState::bytes_of(plan_->L, V, iterations, lambda, o, bytes);
+  if (!bytes[LoopState::TV]) tv_free();
+  // the record sets and the extrapolation state live for this call: once the passes that use them are done, they go
+  struct CallScope {
+    Engine& e;
+    ~CallScope() {
+      bool held = false;
+      for (int b = 0; b < LoopState::kKept; ++b) held = held || e.loop_.buf[b];
+      if (!held) return;
       try {
-        be::stream_sync(stream_);
+        be::stream_sync(e.stream_);
       } catch (...) {
       }
-      stats_free();
-      accel_free();
-      nm_free();
+      e.loop_.release(0, LoopState::kKept);
     }
-    throw;
-  }
+  } scope{*this};
+  loop_.o = o;
+  loop_.allocate(bytes);
+  last_.ran = iterate_sweeps(iterations, lambda, min_value);
+  if (result) *result = last_;
+  return last_.ran;
 }
 
-int Engine::iterate_sweeps(int iterations, double lambda, float min_value, double tolerance,
-                           std::vector<double>* stats, std::vector<double>* alphas) {
+int Engine::iterate_sweeps(int iterations, double lambda, float min_value) {
+  const LoopOptions& o = loop_.o;
+  const double tolerance = o.tolerance;
+  const RecordSet st = stat_records(), nm = nm_records();
+  const bool accel = accel_running();
   work_has_psi_spectrum_ = false;  // psi may have been replaced since the last call
   pending_rows_ = nullptr;
   psi_spec_valid_ = false;
@@ -2254,11 +2202,11 @@ int Engine::iterate_sweeps(int iterations, double lambda, float min_value, doubl
   // (a captured sweep holds buffer addresses: the two work volumes must be back in their roles after it,
   // i.e. the sweep must contain an even number of direct dim0 legs)
   bool use_graph = graphs_on && !halo_fn_ && iterations >= 3 && !prof_.enabled && plan_->can_fuse_rows() &&
-                   plan_->main_bytes() <= graph_max_bytes && streamed_order_.empty() && !stats_on_ && !accel_on_ &&
-                   !nm_on_;  // (a captured sweep would bake in the backgrounds and the records' addresses)
-  std::vector<double> rows;  // {S, M, P} of the sweeps run
+                   plan_->main_bytes() <= graph_max_bytes && streamed_order_.empty() && !st.on() && !accel &&
+                   !nm.on();  // (a captured sweep would bake in the backgrounds and the records' addresses)
+  std::vector<double>& rows = last_.rows;  // {S, M, P} of the sweeps run
   int ran = 0;
-  if (accel_on_) be::d2d(accel_ysave_, psi_, plan_->main_bytes(), stream_);  // y_0
+  if (accel) be::d2d(loop_.buf[LoopState::Y_SAVE], psi_, plan_->main_bytes(), stream_);  // y_0
   for (int it = 0; it < iterations; ++it) {
     if (use_graph && it == 1) {  // every view has been staged by now: its PSF forms are known
       int swaps = 0;
@@ -2268,8 +2216,8 @@ int Engine::iterate_sweeps(int iterations, double lambda, float min_value, doubl
     if (use_graph && it >= 1 && it < iterations - 1) {
       if (sweep_graph_ && (graph_lambda_ != lambda || graph_min_ != min_value ||
                            graph_guard_ != quotient_guard_ || graph_captured_gen_ != graph_gen_ ||
-                           graph_reg_kind_ != reg_kind_ || graph_reg_eps_ != reg_eps_ ||
-                           graph_tv_ != (tv_on_ ? tv_ : nullptr) ||
+                           graph_reg_kind_ != o.reg_kind || graph_reg_eps_ != o.epsilon ||
+                           graph_tv_ != tv_volume() ||
                            graph_work_ != work_)) {
         be::graph_destroy(sweep_graph_);
         sweep_graph_ = nullptr;
@@ -2292,9 +2240,9 @@ int Engine::iterate_sweeps(int iterations, double lambda, float min_value, doubl
         }
         sweep_graph_ = be::capture_end(stream_);
         graph_lambda_ = lambda;
-        graph_reg_kind_ = reg_kind_;
-        graph_reg_eps_ = reg_eps_;
-        graph_tv_ = tv_on_ ? tv_ : nullptr;
+        graph_reg_kind_ = o.reg_kind;
+        graph_reg_eps_ = o.epsilon;
+        graph_tv_ = tv_volume();
         graph_min_ = min_value;
         graph_guard_ = quotient_guard_;
         graph_captured_gen_ = graph_gen_;
@@ -2313,46 +2261,44 @@ int Engine::iterate_sweeps(int iterations, double lambda, float min_value, doubl
       // sweep 1: y_1 = x_1, psi stays, and so does the fused pass - 2 iterations are the plain loop's launches.
       // The fused pass has written all of psi when pass A reads it: pending_rows_ is only ever set under
       // boundary_first(), which needs a halo hook, and an engine with one refuses acceleration)
-      conv_pair(v, lambda, min_value, MVN_EPI_UPDATE, 0, !last && !(accel_on_ && v == V - 1 && it >= 1));
+      conv_pair(v, lambda, min_value, MVN_EPI_UPDATE, 0, !last && !(accel && v == V - 1 && it >= 1));
       if (streamed) ring_release(views_[(size_t)v]);
     }
     ran = it + 1;
-    if (nm_on_) be::launch_nm_reduce(nm_rec_, nm_count_, V, nm_cap_, nm_out_ + 3 * (size_t)V * (size_t)it, stream_);
-    if (stats_on_) {
-      be::launch_convergence_reduce(stat_rec_, stat_count_, V, stat_cap_, stat_out_ + 3 * (size_t)it, stream_);
+    if (nm.on()) be::launch_nm_reduce(nm.rec, nm.count, V, nm.cap, nm.out + 3 * (size_t)V * (size_t)it, stream_);
+    if (st.on()) {
+      be::launch_convergence_reduce(st.rec, st.count, V, st.cap, st.out + 3 * (size_t)it, stream_);
       if (tolerance > 0.) {
         // (no sweep is enqueued ahead: after a stop psi is the estimate of the sweeps run)
         double r[3];
-        be::d2h(r, stat_out_ + 3 * (size_t)it, sizeof(r), stream_);
+        be::d2h(r, st.out + 3 * (size_t)it, sizeof(r), stream_);
         be::stream_sync(stream_);
         rows.insert(rows.end(), r, r + 3);
         if (r[0] / r[2] <= tolerance) break;  // (NaN never stops the loop)
       }
     }
     // (no extrapolation after the last sweep run: psi stays x_k)
-    if (accel_on_ && it < iterations - 1) accel_extrapolate(it + 1, min_value);
+    if (accel && it < iterations - 1) accel_extrapolate(it + 1, min_value);
   }
   flush_pending_rows();
   work_has_psi_spectrum_ = false;
-  if (stats_on_ && tolerance == 0. && ran > 0) {
+  if (st.on() && tolerance == 0. && ran > 0) {
     rows.resize(3 * (size_t)ran);
-    be::d2h(rows.data(), stat_out_, rows.size() * sizeof(double), stream_);
+    be::d2h(rows.data(), st.out, rows.size() * sizeof(double), stream_);
     be::stream_sync(stream_);
   }
-  if (stats) *stats = std::move(rows);
-  if (nm_on_ && ran > 0) {  // {D, Y, M} per (sweep, view) of the sweeps run
-    nm_rows_.resize(3 * (size_t)V * (size_t)ran);
-    be::d2h(nm_rows_.data(), nm_out_, nm_rows_.size() * sizeof(double), stream_);
+  if (nm.on() && ran > 0) {  // {D, Y, M} per (sweep, view) of the sweeps run
+    last_.like.resize(3 * (size_t)V * (size_t)ran);
+    be::d2h(last_.like.data(), nm.out, last_.like.size() * sizeof(double), stream_);
     be::stream_sync(stream_);
-    nm_ran_ = ran;
   }
-  if (accel_on_ && alphas) {  // a_1 .. a_ran; the last sweep run was not followed by an extrapolation
-    alphas->assign((size_t)ran, 0.);
+  if (accel) {  // a_1 .. a_ran; the last sweep run was not followed by an extrapolation
+    last_.alphas.assign((size_t)ran, 0.);
     if (ran > 1) {
       std::vector<float> a((size_t)ran - 1);
-      be::d2h(a.data(), accel_alpha_, a.size() * sizeof(float), stream_);
+      be::d2h(a.data(), loop_.buf[LoopState::ALPHA], a.size() * sizeof(float), stream_);
       be::stream_sync(stream_);
-      for (size_t k = 0; k < a.size(); ++k) (*alphas)[k] = (double)a[k];
+      for (size_t k = 0; k < a.size(); ++k) last_.alphas[k] = (double)a[k];
     }
   }
   return ran;
@@ -2383,8 +2329,7 @@ void Engine::set_halo_planes(int planes, bool split) {
 
 void Engine::set_halo_hook(halo_fn_t fn, void* user, bool drain, bool post) {
   if (fn) {
-    refuse_tv("no halo hook on an engine");
-    refuse_nm("no halo hook on an engine");
+    held_.refuse("no halo hook on an engine");
     // halo mode divides ranges of rows, whose operand offsets are in floats (Plan3D::rows_c2r*)
     if (u16_views() > 0)
       throw std::invalid_argument("mvn: no halo hook on an engine that holds a uint16 image volume (image storage mode 1)");
@@ -2477,8 +2422,7 @@ void Engine::delta_chunk_range(int c, int n, size_t* first_float, size_t* n_floa
 }
 
 void Engine::compute_delta_head(double lambda, float min_value) {
-  refuse_tv("no simultaneous (delta) step on an engine");
-  refuse_nm("no simultaneous (delta) step on an engine");
+  held_.refuse("no simultaneous (delta) step on an engine");
   be::set_device(device_);
   delta_ptr();
   tail_pending_ = false;

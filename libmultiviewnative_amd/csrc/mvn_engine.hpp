@@ -296,20 +296,129 @@ struct ViewSlot {
   bool taps_l_ok[2] = {false, false};
 };
 
+// ---------------------------------------------------------------------------------------------
+// The opt-in switches of the Richardson-Lucy loop, as one value: what one call of the loop can be asked to do
+// beyond the reference's sweeps (mvn_engine_api.h).  The ABI keeps one process-wide value and hands every call a
+// copy; an engine holds one for its own API.  The only copy of each rule lives here.
+// ---------------------------------------------------------------------------------------------
+struct LoopOptions {
+  double tolerance = -1.;  // >= 0: the update passes reduce {S, M, P} per sweep; > 0: the loop ends at S / P <= tolerance
+  int accel = 0;           // 1: vector extrapolation between the sweeps (mvn_extrapolate.hpp)
+  int reg_kind = 0;        // MVN_REG_TIKHONOV / MVN_REG_TV
+  double epsilon = 0.;     // MVN_REG_TV only
+  std::vector<float> background;  // camera background: empty none, one value every view, else one per view
+  int likelihood = 0;      // 1: the divide pass sums {D, Y, M} per (sweep, view)
+
+  // Who reports a broken rule, in the words each API has always used: the engine speaks of `lambda` under "mvn: ",
+  // the reference-shaped entry points of the workspace's `lambda_`.
+  struct Voice {
+    const char* prefix;
+    const char* lambda;
+  };
+  static constexpr Voice kEngine = {"mvn: ", "lambda"};
+  static constexpr Voice kAbi = {"", "lambda_"};
+
+  bool stats_on() const { return tolerance >= 0.; }
+  bool accel_on() const { return accel == 1; }
+  bool tv_on(double lambda) const { return reg_kind == 1 && lambda > 0.; }
+  bool noise_model_on() const {
+    if (likelihood) return true;
+    for (float b : background)
+      if (b != 0.f) return true;
+    return false;
+  }
+  float background_of(int v) const {
+    return background.empty() ? 0.f : background[background.size() == 1 ? 0 : (size_t)v];
+  }
+  static bool tv_epsilon_ok(double epsilon);
+  // |div p| <= 6: below 1/12 the denominator 1 - lambda div p stays above 0.5 with no clamp in the kernel
+  static void check_tv_lambda(double lambda, const Voice& who);
+  // the ranges of the values themselves
+  void validate(const Voice& who) const;
+  // what can only be judged against a call: the TV weight, and the background count against the view count
+  void check_call(int V, double lambda, const Voice& who) const;
+  // The slab drivers (MVN_DEVICES) know none of the switches: the name of one that is on, or nullptr.
+  const char* needs_single_device() const;
+  // Halo mode (a slab of a multi-device group) and the simultaneous step run none of them either.  what == nullptr:
+  // these options were asked of an engine in halo mode; else `what` ("no halo hook on an engine", ...) was asked of
+  // an engine that holds them.  Throws when a switch is on.
+  void refuse(const char* what = nullptr) const;
+};
+
+// What one call of the loop reports back.
+struct LoopResult {
+  int ran = 0;                 // sweeps run
+  int views = 0;
+  std::vector<double> rows;    // statistics on: {S, M, P} per sweep run
+  std::vector<double> alphas;  // acceleration on: a_1 .. a_ran (the last one 0)
+  std::vector<double> like;    // noise model on: {D, Y, M} per (sweep run k, view v) at 3 (k V + v)
+};
+
+// One set of records of the loop: every workgroup of a pass writes one record of 3 doubles for its view, and one
+// reduce launch per sweep folds them into rows (convergence: the update passes; noise model: the divide passes).
+struct RecordSet {
+  double* rec = nullptr;      // per view: cap records
+  unsigned* count = nullptr;  // per view: records of its last pass
+  double* out = nullptr;      // the rows
+  long cap = 0;
+  bool on() const { return rec != nullptr; }
+};
+
+// The device state of the loop's switches.  bytes_of() is the one table of (buffer, bytes): Engine::memory_need
+// prices a call by it and Engine::iterate allocates by it.  The buffers before kKept live for one iterate(); the TV
+// factor volume stays with the engine while the calls keep asking for it.
+struct LoopState {
+  enum Buffer {
+    STAT_REC, STAT_COUNT, STAT_OUT,          // convergence statistics
+    NM_REC, NM_COUNT, NM_OUT,                // noise model
+    X_PREV, G_PREV, Y_SAVE, ACCEL_REC, ALPHA,  // extrapolation: x_{k-1}, g_{k-1}, y_{k-1}, pass A's records, the a_k
+    TV,                                      // the total-variation factor volume, psi's layout
+    N_BUFFERS,
+    kKept = TV
+  };
+  void* buf[N_BUFFERS] = {};
+  LoopOptions o;  // of the running iterate()
+  static void bytes_of(const Layout& L, int V, int iterations, double lambda, const LoopOptions& o,
+                       size_t bytes[N_BUFFERS]);
+  // every workgroup of an update or divide pass writes one record; no launch has more workgroups than the volume has rows
+  static long record_cap(const Layout& L) { return (long)L.rows; }
+  // workgroups of the extrapolation's pass A (mvn_extrapolate.hpp): a function of the extents only
+  static long accel_records(const Layout& L) { return mvn_accel_blocks((long)L.real_floats(), L.RP == L.d2 ? 4 : 2); }
+  template <typename T>
+  T* at(Buffer b) const { return (T*)buf[b]; }
+  RecordSet records(Buffer first, const Layout& L) const {
+    RecordSet r;
+    r.rec = at<double>(first), r.count = at<unsigned>((Buffer)(first + 1)), r.out = at<double>((Buffer)(first + 2));
+    r.cap = record_cap(L);
+    return r;
+  }
+  void allocate(const size_t bytes[N_BUFFERS]);  // what the table asks for and is not held yet
+  void release(int first, int last);             // buffers [first, last)
+};
+
+// the launch parameters of the pass of mvn_tv.hpp on a volume of layout L
+inline TvParams tv_params(const Layout& L, const float* psi, float* t, double lambda, double epsilon) {
+  TvParams p = {};
+  p.psi = psi, p.t = t;
+  p.d0 = L.d0, p.d1 = L.d1, p.d2 = L.d2, p.RP = L.RP;
+  p.lambda = (float)lambda;
+  p.e2 = (float)epsilon * (float)epsilon;
+  return p;
+}
+
 // What one ABI call on a new engine allocates on the device (Engine::memory_need): the kernel extents of every
-// view (kernel1 and kernel2), the host-shaped embedding scratch of the padded policies, and the residency plan -
+// view (kernel1 and kernel2), the host-shaped embedding scratch of the padded policies, the residency plan -
 // how many views keep their image and weights in host memory and how many ring slots (pairs of volumes) they
-// rotate through.
+// rotate through - and what the loop's switches add (LoopState::bytes_of).
 struct MemoryQuery {
   shape_t ext = {{0, 0, 0}};
   kernel_list_t kernels;  // 2 per view: kernel1, kernel2
   size_t embed_floats = 0;
   int streamed = 0;
   int ring = 0;
-  int stats_rows = 0;  // convergence statistics on: the iterations of the call (Engine::iterate), else 0
-  int accel_rows = 0;  // acceleration on: the iterations of the call, else 0
-  bool tv = false;     // total-variation regularisation with lambda > 0: the factor volume
-  int nm_rows = 0;     // noise model on (a background != 0 or the likelihood): the iterations of the call, else 0
+  LoopOptions loop;  // the switches of the call,
+  int iterations = 1;  // ... its sweeps
+  double lambda = 0.;  // ... and its regularisation weight
   // per view: the call wants its image kept as uint16 (image storage mode 1 and a uint16 stack that is no broadcast);
   // empty: none.  What is then held as uint16: Engine::kept_u16.
   std::vector<char> image_u16;
@@ -358,8 +467,9 @@ class Engine {
   // main thread after an error: wake an uploader that waits for a ring slot
   void abort_streaming();
   // Bytes the ABI call described by q allocates on a new engine of extents q.ext, allocating nothing itself: the
-  // PSF forms (direct taps, fused-pass taps, 3-D spectra) that `rule` gives for its kernels, plus a small slack for
-  // plan tables and allocator rounding.  The single source of truth of the memory planner (mvn_abi.cpp).
+  // PSF forms (direct taps, fused-pass taps, 3-D spectra) that `rule` gives for its kernels, the loop state of its
+  // switches (LoopState::bytes_of), plus a small slack for plan tables and allocator rounding.  The single source of
+  // truth of the memory planner (mvn_abi.cpp).
   static size_t memory_need(const MemoryQuery& q, const FormRule& rule);
   // The views s of V views stream: spread evenly over the sweep (view floor((j + 1/2) V / s) for j < s), so that
   // each upload runs under the resident view updates between two streamed ones.
@@ -414,36 +524,33 @@ class Engine {
   void finish_staging();  // uploader thread, after the last view: drain and free scratch
 
   // `iterations` Gauss-Seidel sweeps over all views (the reference order,
-  // src/gpu_deconvolve_methods.cuh:487-535); asynchronous on stream() while tolerance < 0.
-  // tolerance >= 0: the update passes also reduce the convergence statistics of every sweep k,
-  // {S_k, M_k, P_k} (mvn_engine_api.h), appended to *stats; tolerance > 0 ends the loop after the
-  // first sweep with S_k / P_k <= tolerance (each sweep then waits for its statistics).  Returns the
-  // sweeps run.
-  // accel == 1: vector extrapolation between the sweeps (mvn_extrapolate.hpp) - the next sweep starts from
-  // y_k = x_k + a_k (x_k - x_{k-1}) instead of x_k; no extrapolation follows the last sweep run, so psi is
-  // always a sweep's own result.  a_1 .. a_ran (the last one 0) go to *alphas, which costs a wait for the stream.
-  // Not for an engine with a halo hook (a slab of a multi-device group).
-  int iterate(int iterations, double lambda, float min_value, double tolerance = -1.,
-              std::vector<double>* stats = nullptr, int accel = 0, std::vector<double>* alphas = nullptr);
-  // The regulariser of the iterate() calls that follow (mvn_engine_api.h, MVN_REG_*).  kind 0: `lambda` is the
-  // reference's Tikhonov weight.  kind 1: total variation - lambda is the TV weight, the Tikhonov branch is off and
-  // every view update is preceded by the pass of mvn_tv.hpp, whose factor volume is allocated at first need and kept
-  // while the kind stays; lambda >= 1/12 is refused, lambda == 0 is the plain loop.  Not for an engine with a halo
-  // hook, and compute_delta* refuse a TV engine.
-  void set_regularization(int kind, double epsilon);
-  int regularization_kind() const { return reg_kind_; }
-  // The noise model of the iterate() calls that follow (mvn_engine_api.h): view v's camera background b_v enters the
-  // forward model, quotient = image / (H psi + b_v), and - with `likelihood` or any b_v != 0 - the divide pass also
-  // sums {D, Y, M} per (sweep, view) over the stacks' window (MVN_EPI_DIVIDE_NM, mvn_pass_bodies.hpp).  count 0: no
-  // background; 1: one value for every view; else one per view.  Values finite and >= 0.  Both off (the default): the
-  // plain divide pass, launch for launch.  On: iterate() waits for the stream before it returns (the rows cross to
-  // the host), and no captured sweep graph is used.  Not for an engine with a halo hook; compute_delta* refuse an
-  // engine in the mode.
-  void set_noise_model(const float* background, int count, bool likelihood);
-  bool noise_model_on() const;
-  // {D, Y, M} of the last iterate(): 3 doubles per (sweep k, view v) at 3 (k V + v), for the sweeps that ran
-  const std::vector<double>& last_likelihood() const { return nm_rows_; }
-  int last_likelihood_sweeps() const { return nm_ran_; }
+  // src/gpu_deconvolve_methods.cuh:487-535) under the options o; asynchronous on stream() while every switch is
+  // off.  Returns the sweeps run; *result (optional) takes what last_result() keeps.
+  //   o.tolerance >= 0: the update passes also reduce the convergence statistics of every sweep k, {S_k, M_k, P_k}
+  //     (mvn_engine_api.h); tolerance > 0 ends the loop after the first sweep with S_k / P_k <= tolerance (each
+  //     sweep then waits for its statistics).
+  //   o.accel == 1: vector extrapolation between the sweeps (mvn_extrapolate.hpp) - the next sweep starts from
+  //     y_k = x_k + a_k (x_k - x_{k-1}) instead of x_k; no extrapolation follows the last sweep run, so psi is
+  //     always a sweep's own result.
+  //   o.reg_kind 0: `lambda` is the reference's Tikhonov weight.  1: total variation - lambda is the TV weight, the
+  //     Tikhonov branch is off and every view update is preceded by the pass of mvn_tv.hpp, whose factor volume is
+  //     allocated at first need and kept while the calls stay TV; lambda >= 1/12 is refused, lambda == 0 is the
+  //     plain loop.
+  //   o.background, o.likelihood: view v's camera background b_v enters the forward model, quotient = image /
+  //     (H psi + b_v), and - with the likelihood or any b_v != 0 - the divide pass also sums {D, Y, M} per (sweep,
+  //     view) over the stacks' window (MVN_EPI_DIVIDE_NM, mvn_pass_bodies.hpp).  Both off: the plain divide pass,
+  //     launch for launch.  On: no captured sweep graph is used.
+  // A switch that is on makes iterate() wait for the stream before it returns (its rows cross to the host and its
+  // buffers go).  None is for an engine with a halo hook (a slab of a multi-device group).
+  int iterate(int iterations, double lambda, float min_value, const LoopOptions& o, LoopResult* result = nullptr);
+  // ... under the options the engine holds
+  int iterate(int iterations, double lambda, float min_value) { return iterate(iterations, lambda, min_value, held_); }
+  // The options the engine holds for its own API (mvn_engine_set_regularization, mvn_engine_set_noise_model): validated
+  // here, refused on an engine with a halo hook; set_halo_hook and compute_delta* refuse an engine that holds TV or a
+  // noise model.  Back at Tikhonov the factor volume goes.
+  void set_options(const LoopOptions& o);
+  const LoopOptions& options() const { return held_; }
+  const LoopResult& last_result() const { return last_; }
   // simultaneous (Jacobi) mode for view sharding: delta <- sum over this engine's views of
   // w_v (next_v - psi), computed from the current psi without changing it
   void compute_delta(double lambda, float min_value);
@@ -695,44 +802,19 @@ class Engine {
   // would wait for ring slots no later view update frees
   void end_streaming();
  private:
-  // convergence statistics of the running iterate() (allocated for its duration only; see memory_need)
-  bool stats_on_ = false;
-  double* stat_rec_ = nullptr;     // per view: stat_cap_ records of 3 doubles
-  unsigned* stat_count_ = nullptr; // per view: records of its last update pass
-  double* stat_out_ = nullptr;     // 3 doubles per sweep
-  long stat_cap_ = 0;
-  MvnStatsParams stats_for(int v) const;
-  void stats_free();
-  int iterate_sweeps(int iterations, double lambda, float min_value, double tolerance, std::vector<double>* stats,
-                     std::vector<double>* alphas);
-  // noise model (set_noise_model); the records live for the running iterate() only (see memory_need)
-  std::vector<float> nm_background_;  // per view; empty: none
-  bool nm_like_ = false;
-  bool nm_on_ = false;              // the running iterate() divides through MVN_EPI_DIVIDE_NM
-  double* nm_rec_ = nullptr;        // per view: nm_cap_ records of 3 doubles
-  unsigned* nm_count_ = nullptr;    // per view: records of its last divide pass
-  double* nm_out_ = nullptr;        // 3 doubles per (sweep, view)
-  long nm_cap_ = 0;
-  std::vector<double> nm_rows_;
-  int nm_ran_ = 0;
-  MvnStatsParams nm_stats_for(int v) const;
-  void nm_free();
-  void refuse_nm(const char* what) const;
-  // total-variation regularisation (set_regularization)
-  int reg_kind_ = 0;
-  double reg_eps_ = 0.;
-  bool tv_on_ = false;    // the running iterate() multiplies the integrals by the factor volume
-  float* tv_ = nullptr;   // the factor volume, psi's layout
+  // the switches of the loop: the options the engine holds, the device state of the running iterate() (a buffer that
+  // is held = its switch is on), and what the last one reported
+  LoopOptions held_;
+  LoopState loop_;
+  LoopResult last_;
+  RecordSet stat_records() const { return loop_.records(LoopState::STAT_REC, plan_->L); }
+  RecordSet nm_records() const { return loop_.records(LoopState::NM_REC, plan_->L); }
+  bool accel_running() const { return loop_.buf[LoopState::X_PREV] != nullptr; }
+  float* tv_volume() const { return loop_.at<float>(LoopState::TV); }
+  // the records of view v's pass and the window they cover: the stacks inside the padded volume, or all of it
+  MvnStatsParams params_for(const RecordSet& r, int v) const;
+  int iterate_sweeps(int iterations, double lambda, float min_value);
   void tv_free();
-  void refuse_tv(const char* what) const;
-  // vector extrapolation of the running iterate() (allocated for its duration only; see memory_need)
-  bool accel_on_ = false;
-  float* accel_xprev_ = nullptr;  // x_{k-1}
-  float* accel_g_ = nullptr;      // g_{k-1}
-  float* accel_ysave_ = nullptr;  // y_{k-1}: what the sweep started from
-  double* accel_rec_ = nullptr;   // pass A's records, 2 doubles per workgroup
-  float* accel_alpha_ = nullptr;  // a_k per sweep boundary
-  void accel_free();
   void accel_extrapolate(int k, float min_value);  // after sweep k (1-based), before sweep k + 1
   void ring_upload(int v, const StackRef& image, const StackRef& weights);  // uploader thread
   void ring_acquire(ViewSlot& s);                                     // main thread, before the view update

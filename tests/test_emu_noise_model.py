@@ -8,6 +8,9 @@ the largest deviation of the float32 formula from it over the five cases (noise_
 2.8e-4); Y exactly the integer sum of the camera counts; M relative 1e-5.  Every test prints what it achieved."""
 import os
 import subprocess
+import sys
+import threading
+import time
 
 import numpy as np
 import pytest
@@ -304,6 +307,140 @@ def test_submit_wait_captures_the_noise_model_at_submit(emu, case):
     assert np.array_equal(psis[0], want[0][0]) and np.array_equal(rows0, want[0][1])
     assert np.array_equal(psis[1], want[1][0]) and np.array_equal(rows1, want[1][1])
     assert not np.array_equal(rows0, rows1)
+
+
+def all_switches(b, on, eps):
+    """convergence statistics, acceleration, total variation, a background and the likelihood: all on, or all off"""
+    b.set_convergence(0 if on else -1)
+    b.set_acceleration(1 if on else 0)
+    b.set_regularization(1 if on else 0, eps)
+    b.set_background([BACKGROUND] if on else None)
+    b.set_likelihood(1 if on else 0)
+
+
+def last_records(b):
+    run, conv = b.last_convergence()
+    return run, conv, b.last_acceleration(), b.last_likelihood()
+
+
+def test_submit_wait_captures_every_switch_by_value(emu, case):
+    cams, views, k1, k2, w, psi0 = case("fixed rows")
+    lam, eps = 0.002, 0.01 * float(psi0.mean())
+    V = len(views)
+    h = holder(views, k1, k2, w, lam=lam)
+    emu.set_pad_mode("none")
+    try:
+        all_switches(emu, True, eps)
+        want = emu.gpu_deconvolve(psi0, h, pad_mode=False)
+        want_rec = last_records(emu)
+        psi = np.ascontiguousarray(psi0.copy())
+        t = emu.deconvolve_submit(psi, h)
+        all_switches(emu, False, eps)  # (what is set now is not what the ticket runs with)
+        emu.deconvolve_wait(t)
+        got_rec = last_records(emu)
+    finally:
+        all_switches(emu, False, eps)
+        emu.set_pad_mode(None)
+    run, conv, alphas, like = want_rec
+    assert run == N_SWEEPS and conv.shape == (N_SWEEPS, 3) and alphas.shape == (N_SWEEPS,) and like.shape == (N_SWEEPS, V, 3)
+    assert alphas[1:-1].max() > 0 and not np.array_equal(want, emu.gpu_deconvolve(psi0, h))  # (the switches were on)
+    assert np.array_equal(psi, want)
+    assert got_rec[0] == run
+    for got, ref in zip(got_rec[1:], want_rec[1:]):
+        assert got.shape == ref.shape and np.array_equal(got, ref)
+
+
+def test_memory_query_beside_a_running_call_sees_the_process_wide_switches(emu, case):
+    cams, views, k1, k2, w, psi0 = case("fixed rows")
+    lam, eps = 0.002, 0.01 * float(psi0.mean())
+    n = 40  # (sweeps enough for the call to outlast the query by far)
+    h = holder(views, k1, k2, w, n=n, lam=lam)
+    emu.set_pad_mode("none")
+    done = {}
+
+    def blocking_call():
+        done["psi"] = emu.gpu_deconvolve(psi0, h, pad_mode=False)
+        done["rec"] = last_records(emu)
+
+    try:
+        off = emu.deconvolve_memory(h, 0)
+        all_switches(emu, True, eps)
+        on = emu.deconvolve_memory(h, 0)
+        before = emu.tv_launch_count()
+        t = threading.Thread(target=blocking_call)
+        t.start()
+        deadline = time.monotonic() + 120
+        while emu.tv_launch_count() == before:  # the first TV pass: the call has captured its switches and is sweeping
+            assert t.is_alive() and time.monotonic() < deadline
+        all_switches(emu, False, eps)
+        beside = emu.deconvolve_memory(h, 0)
+        still_running = t.is_alive()
+        t.join()
+    finally:
+        all_switches(emu, False, eps)
+        emu.set_pad_mode(None)
+    assert on > off and beside == off, (off, on, beside)
+    assert still_running
+    run, conv, alphas, like = done["rec"]  # (the call ran with what it captured)
+    assert run == n and conv.shape == (n, 3) and alphas.shape == (n,) and like.shape == (n, len(views), 3)
+
+
+_ALL_ON_CHILD = r"""
+import os, sys
+import numpy as np
+root, streamed = sys.argv[1], int(sys.argv[2])
+sys.path.insert(0, root); sys.path.insert(0, os.path.join(root, "tests"))
+from libmultiviewnative_amd import native
+from libmultiviewnative_amd.abi import WorkspaceHolder
+import noise_model_reference as R
+emu = native.Binding(native.EMU_SO)
+MB = 1 << 20
+cams, views, k1, k2, w, psi0, _ = R.case_inputs("fixed rows")
+V = len(views)
+lam, eps = 0.002, 0.01 * float(psi0.mean())
+h = WorkspaceHolder(views, k1, k2, w, lam, R.MINV, R.N_SWEEPS)
+emu.set_pad_mode("none")
+switches = [lambda on: emu.set_convergence(0 if on else -1),
+            lambda on: emu.set_acceleration(1 if on else 0),
+            lambda on: emu.set_regularization(1 if on else 0, eps),
+            lambda on: (emu.set_background([R.BACKGROUND] if on else None), emu.set_likelihood(1 if on else 0))]
+off = emu.deconvolve_memory(h, streamed)
+deltas = []
+for sw in switches:  # what each switch adds alone: the figures the tests of the switches pin
+    sw(True)
+    deltas.append(emu.deconvolve_memory(h, streamed) - off)
+    sw(False)
+assert all(d > 0 for d in deltas), deltas
+for sw in switches:
+    sw(True)
+need = emu.deconvolve_memory(h, streamed)
+print("all off %d, all on %d, deltas %r" % (off, need, deltas))
+assert need - off == sum(deltas), (need - off, deltas)
+# the call runs in exactly the memory the model names (rounded up to the MB): an undercount fails an allocation
+os.environ["MVN_EMU_TOTAL_MB"] = str(-(-need // MB))
+emu.set_memory_mode("auto" if streamed == 0 else "stream:%d" % streamed)
+before = emu.stream_counters()
+got = emu.gpu_deconvolve(psi0, h, pad_mode=False)
+err = emu.l.mvn_last_error().decode()
+assert not err, err
+assert np.isfinite(got).all() and not np.array_equal(got, psi0), "the call did not run"
+assert emu.stream_counters()[0] - before[0] == (1 if streamed else 0)
+run, conv = emu.last_convergence()
+assert run == R.N_SWEEPS and conv.shape == (run, 3) and emu.last_acceleration().shape == (run,)
+assert emu.last_likelihood().shape == (run, V, 3)
+print("ok")
+"""
+
+
+@pytest.mark.parametrize("streamed", [0, 1])
+def test_the_memory_model_of_every_switch_at_once_is_what_the_call_allocates(emu, streamed):
+    env = dict(os.environ, OMP_NUM_THREADS="4", **case_inputs("fixed rows")[-1])
+    env.pop("MVN_EMU_TOTAL_MB", None)
+    r = subprocess.run([sys.executable, "-c", _ALL_ON_CHILD, ROOT, str(streamed)], env=env, capture_output=True,
+                       text=True, timeout=600)
+    print(r.stdout[-2000:])
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.stdout[-2000:], r.stderr[-4000:])
+    assert "exhausted" not in r.stderr, r.stderr[-4000:]
 
 
 # ---- 9. the engine API, the refusals, the memory model --------------------------------------------------------------

@@ -11,8 +11,9 @@ import numpy as np
 import pytest
 
 from libmultiviewnative_amd.abi import WorkspaceHolder
-from noise_model_reference import (BACKGROUND, CASES, MINV, N_SWEEPS, PSI_MX, PSI_RMS, case_inputs, case_reference,
-                                   check_statistics, lines_case_inputs, lines_case_reference, nm_call, rel_errors)
+from noise_model_reference import (BACKGROUND, CASES, MINV, N_SWEEPS, PSI_MX, PSI_RMS, Ref, case_inputs, case_reference,
+                                   check_statistics, lines_case_inputs, lines_case_reference, nm_call,
+                                   nm_loop_accelerated, rel_errors)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -118,6 +119,59 @@ def test_line_layout(gpu, monkeypatch):
         assert np.array_equal(again, got) and np.array_equal(rows_again, rows)
     finally:
         gpu.l.mvn_release_cached_engines()
+
+
+def test_combined_with_tv_acceleration_and_convergence(gpu):
+    """the test of this name in tests/test_emu_noise_model.py on the real kernels, and the same values bit for bit
+    through the engine API"""
+    from libmultiviewnative_amd import native
+    cams, views, k1, k2, w, psi0, _ = case_inputs("fixed rows")
+    lam, eps = 0.002, 0.01 * float(psi0.mean())
+    V = len(views)
+    ref_psi, ref_rows = nm_loop_accelerated(psi0, views, k1, k2, w, (BACKGROUND,) * V, MINV, N_SWEEPS, lam, eps)
+    h = WorkspaceHolder(views, k1, k2, w, lam, MINV, N_SWEEPS)
+    gpu.l.mvn_release_cached_engines()
+    gpu.set_regularization(1, eps)
+    gpu.set_acceleration(1)
+    gpu.set_convergence(0)
+    try:
+        got, rows = nm_call(gpu, psi0, h, [BACKGROUND])
+        run, conv = gpu.last_convergence()
+        alphas = gpu.last_acceleration()
+        mx, rms = rel_errors(got, ref_psi)
+        print("TV + acceleration + convergence: psi max %.3g rms %.3g" % (mx, rms))
+        assert mx <= PSI_MX and rms <= PSI_RMS, (mx, rms)
+        assert run == N_SWEEPS and conv.shape == (N_SWEEPS, 3) and rows.shape == (N_SWEEPS, V, 3)
+        check_statistics(rows, Ref(ref_psi, ref_rows[:, :, :3], ref_rows[:, :, 3]), cams, "combined")
+        # a tolerance stop: rows for the sweeps that ran
+        r = conv[:, 0] / conv[:, 2]
+        tol = float(np.sqrt(r[2] * r[3]))  # between the third and the fourth sweep's figure
+        assert r[3] < tol < r[2] and (r[:3] > tol).all()
+        gpu.set_convergence(tol)
+        got_s, rows_s = nm_call(gpu, psi0, h, [BACKGROUND])
+        run_s, _ = gpu.last_convergence()
+        assert run_s == 4 and rows_s.shape == (4, V, 3), (run_s, rows_s.shape)
+        assert np.array_equal(rows_s, rows[:4])
+    finally:
+        gpu.set_regularization(0)
+        gpu.set_acceleration(0)
+        gpu.set_convergence(-1)
+        gpu.l.mvn_release_cached_engines()
+    # the engine API (no padding, like nm_call): the same kernels on the same values
+    e = native.EngineHandle(gpu, psi0.shape, V)
+    try:
+        for v in range(V):
+            e.set_view(v, views[v], w[v], k1[v], k2[v])
+        e.set_psi(psi0)
+        e.set_regularization(1, eps)
+        e.set_noise_model([BACKGROUND] * V, 1)
+        run_e, conv_e, alphas_e = e.iterate_accelerated(N_SWEEPS, lam, MINV, 0.0)
+        rows_e = e.last_likelihood()
+        psi_e = e.get_psi()
+    finally:
+        e.close()
+    assert run_e == run and np.array_equal(psi_e, got)
+    assert np.array_equal(conv_e, conv) and np.array_equal(alphas_e, alphas) and np.array_equal(rows_e, rows)
 
 
 _CHILD = r"""
