@@ -21,7 +21,13 @@
  *    NaN).  mvn_set_pad_mode("zero_exact") (mvn_engine_api.h) or MVN_PAD_MODE=zero_exact keeps
  *    exactly image + kernel - 1 without the guard; "none" selects the reference CPU path's
  *    no_padd instead (cyclic on exactly image_dims_, inc/cpu_convolve.h:22-26), which is the
- *    parity target of the oracle tests;
+ *    parity target of the oracle tests.  The zeros tell the forward model that the specimen is
+ *    black just outside the stack, so within a PSF half-width of every face the estimate comes
+ *    out too bright, more so with every sweep (the reference has the same defect);
+ *    mvn_set_pad_mode("reflect") or MVN_PAD_MODE=reflect keeps the volume, the offset and the
+ *    guard of the default and fills the margins around image, weights and psi with the stack's
+ *    mirror image instead (whole-sample symmetric extension: the reflective boundary condition
+ *    for a symmetric PSF; mvn_engine_api.h states the index rule);
  *  - inplace_gpu_convolution and the legacy convolution entry points are cyclic on exactly the
  *    given dims with the kernel centre on the origin, as in the reference (as_is_padding,
  *    src/multiviewnative.cu:29-30,39-40,58-75);

@@ -106,10 +106,11 @@ MVN_API int mvn_deconvolve_memory_described(struct workspace input, const mvn_ca
 MVN_API int mvn_image_storage_counters(long long out[2]);
 /* Padding policy of inplace_gpu_deconvolve for the calls that follow (process-wide): "zero"
  * (default: the reference GPU entry's zero_padd with FFT-friendly padded extents), "zero_exact"
- * (exactly image + kernel - 1), "none" (the reference CPU path's cyclic no_padd); NULL or ""
- * returns to the environment variable MVN_PAD_MODE / the default.  See multiviewnative.h. */
+ * (exactly image + kernel - 1), "none" (the reference CPU path's cyclic no_padd), "reflect" (the volume, offset
+ * and guard of "zero", the margins around image, weights and psi holding the stack's mirror image instead of zeros);
+ * NULL or "" returns to the environment variable MVN_PAD_MODE / the default.  See multiviewnative.h. */
 MVN_API int mvn_set_pad_mode(const char* mode);
-/* The mode last selected with mvn_set_pad_mode ("zero" | "zero_exact" | "none"), or "" when the
+/* The mode last selected with mvn_set_pad_mode ("zero" | "zero_exact" | "none" | "reflect"), or "" when the
  * environment / default decides -- what a caller that switches the policy for one call restores. */
 MVN_API const char* mvn_get_pad_mode(void);
 /* Memory mode of inplace_gpu_deconvolve / mvn_deconvolve_submit for the calls that follow (process-wide):
@@ -236,6 +237,19 @@ MVN_API int mvn_last_likelihood(int* iterations_run, int* num_views, double* sta
 MVN_API int mvn_tv_factor(int device, const int dims[3], const float* psi, double lambda, double epsilon, float* t);
 MVN_API int mvn_tv_time(int device, const int dims[3], int reps, float* ms);
 MVN_API long mvn_tv_launch_count(void);
+/* Padding policy "reflect".  Volume voxel (z, y, x) of image, weights and psi holds the stack's voxel
+ * (f(z - o0, n0), f(y - o1, n1), f(x - o2, n2)), o the window's offset (kernel - 1) / 2, n the stack's extents and
+ *     f(i, n):  m = i mod 2n (non-negative);  f = m < n ? m : 2n - 1 - m
+ * (whole-sample symmetric extension, numpy.pad's "symmetric"; the row padding of an odd last extent stays zero).  The
+ * margins are filled in place behind whatever placed the stack, one launch per axis that has a margin; nothing else
+ * about the call differs from "zero" (extents, memory, the window of the statistics).  Such a call runs on one device.
+ * mvn_reflect_counters: out[0] = launches of the fill, out[1] = volumes filled, since process start.
+ * mvn_reflect_time (test and bench utility): ms[0] = milliseconds per fill (all its launches) of a resident volume of
+ * extents ext around a window of extents dims at offset off, float32 or (u16 != 0) uint16, `reps` fills between two
+ * stream events; ms[1] = the same for a plain streaming copy of that volume (one read, one write). */
+MVN_API int mvn_reflect_counters(long long out[2]);
+MVN_API int mvn_reflect_time(int device, const int dims[3], const int ext[3], const int off[3], int u16, int reps,
+                             float* ms);
 /* A resident engine keeps, per view slot, the PSF spectra of the last call together with host
  * copies of the kernels they were made from; a call (or mvn_engine_set_view) that brings
  * bytewise identical kernels for a slot re-uses the spectra (the reference's

@@ -329,11 +329,17 @@ static void give_back_engine(int dev, std::unique_ptr<Engine> e) {
 //                           prime factor such as 542 = 2 * 271 then goes the chirp-z route)
 //   MVN_PAD_NONE            the reference CPU path's no_padd: cyclic on exactly image_dims_
 //                           (inc/cpu_convolve.h:22-26) -- the parity target of the oracle tests
+//   MVN_PAD_REFLECT         MVN_PAD_ZERO's volume, offset and guard, but the margins around image,
+//                           weights and psi hold the stack's mirror image instead of zeros
+//                           (whole-sample symmetric extension, mvn_reflect.hpp): the forward model
+//                           no longer sees a black specimen just outside the stack.  One device.
 // Selected by mvn_set_pad_mode() (a JVM host cannot easily change its environment per call),
-// else by the environment variable MVN_PAD_MODE = zero | zero_exact | none (MVN_PAD_GOOD_SIZE=0
+// else by the environment variable MVN_PAD_MODE = zero | zero_exact | none | reflect (MVN_PAD_GOOD_SIZE=0
 // turns "zero" into "zero_exact"), else MVN_PAD_ZERO.
 // ---------------------------------------------------------------------------------------------
-enum { MVN_PAD_UNSET = -1, MVN_PAD_ZERO = 0, MVN_PAD_ZERO_EXACT = 1, MVN_PAD_NONE = 2 };
+enum { MVN_PAD_UNSET = -1, MVN_PAD_ZERO = 0, MVN_PAD_ZERO_EXACT = 1, MVN_PAD_NONE = 2, MVN_PAD_REFLECT = 3 };
+// the policies that grow the padded extents to FFT-friendly sizes and guard the quotient
+static bool pad_grows(int pad_mode) { return pad_mode == MVN_PAD_ZERO || pad_mode == MVN_PAD_REFLECT; }
 static std::atomic<int> g_pad_mode{MVN_PAD_UNSET};
 
 static int parse_pad_mode(const char* m) {
@@ -341,7 +347,8 @@ static int parse_pad_mode(const char* m) {
   if (std::strcmp(m, "zero") == 0) return MVN_PAD_ZERO;
   if (std::strcmp(m, "zero_exact") == 0) return MVN_PAD_ZERO_EXACT;
   if (std::strcmp(m, "none") == 0) return MVN_PAD_NONE;
-  throw std::invalid_argument(std::string("unknown padding mode '") + m + "' (zero | zero_exact | none)");
+  if (std::strcmp(m, "reflect") == 0) return MVN_PAD_REFLECT;
+  throw std::invalid_argument(std::string("unknown padding mode '") + m + "' (zero | zero_exact | none | reflect)");
 }
 
 static int current_pad_mode() {
@@ -571,7 +578,7 @@ static void call_extents(const workspace& input, int pad_mode, int dev, shape_t*
       }
       ext[d] = dims[d] + kmax - 1;
       off[d] = (kmax - 1) / 2;
-      if (pad_mode != MVN_PAD_ZERO) continue;
+      if (!pad_grows(pad_mode)) continue;
       // dim0 is not transformed when every PSF of the call is held in the direct dim0 form (mvn_dim0_direct.hpp):
       // it then keeps the reference's exact image + kernel - 1 (542 planes for a 512-block with 31^3 PSFs, not
       // 576: 6 % less volume in every pass) - provided the rows of a plane keep whole tiles of the fixed
@@ -688,6 +695,7 @@ static void deconvolve_call(const workspace& input, const CallStacks& cs, int de
     if (!devs.empty()) {  // (the second lane belongs to the block pipeline of mvn_deconvolve_submit)
       // the slab drivers know none of the loop's switches, and take dense float32 stacks in host memory only
       const char* why = loop.needs_single_device();
+      if (!why && pad_mode == MVN_PAD_REFLECT) why = "reflect padding";
       bool plain = plain_stack(cs.psi, input.data_[0].image_dims_);
       for (int v = 0; plain && v < V; ++v)
         plain = plain_stack(cs.image[(size_t)v], input.data_[v].image_dims_) &&
@@ -725,7 +733,8 @@ static void deconvolve_call(const workspace& input, const CallStacks& cs, int de
     eng.set_embedding(dims_i, off, scratch);
     // extra zeros beyond the PSF's reach: the blurred estimate is exactly or nearly 0 there and
     // the reference's pointwise math would give 0 * 1/0 = NaN; the one deliberate deviation
-    eng.set_quotient_guard(pad_mode == MVN_PAD_ZERO);
+    eng.set_quotient_guard(pad_grows(pad_mode));
+    eng.set_reflect(pad_mode == MVN_PAD_REFLECT);
     static const bool no_pipeline = [] {
       const char* e = std::getenv("MVN_NO_PIPELINE");
       return e && *e && std::strcmp(e, "0") != 0;
@@ -1160,6 +1169,76 @@ int mvn_tv_time(int device, const int dims[3], int reps, float* ms) {
   });
 }
 
+int mvn_reflect_counters(long long out[2]) {
+  return guarded("mvn_reflect_counters", [&] {
+    if (!out) throw std::invalid_argument("null out");
+    be::reflect_counters(out);
+  });
+}
+
+// ms[0]: the fill of mvn_reflect.hpp (all its launches) on a resident volume of extents ext around a window of extents
+// dims at offset off, float32 or (u16) uint16, per fill over `reps` fills between two stream events; ms[1]: a plain
+// streaming copy of that volume (launch_copy3d on its bytes: one read and one write), likewise
+int mvn_reflect_time(int device, const int dims[3], const int ext[3], const int off[3], int u16, int reps, float* ms) {
+  return guarded("mvn_reflect_time", [&] {
+    if (!dims || !ext || !off || !ms) throw std::invalid_argument("null argument");
+    if (reps < 1) throw std::invalid_argument("reps must be positive");
+    for (int d = 0; d < 3; ++d)
+      if (dims[d] < 1 || off[d] < 0 || (long)off[d] + dims[d] > ext[d])
+        throw std::invalid_argument("the window does not fit the volume");
+    const int dev = pick_device(device);
+    std::lock_guard<std::mutex> lk(device_mutex(dev));
+    be::set_device(dev);
+    const Layout L(ext[0], ext[1], ext[2]);
+    const size_t esz = u16 ? sizeof(uint16_t) : sizeof(float);
+    const size_t bytes = L.real_floats() * esz;
+    float *du = nullptr, *dt = nullptr;
+    be::stream_t s = nullptr;
+    be::event_t a = nullptr, b = nullptr;
+    try {
+      du = (float*)be::dmalloc(bytes);
+      dt = (float*)be::dmalloc(bytes);
+      s = be::stream_create();
+      a = be::event_create();
+      b = be::event_create();
+      std::vector<unsigned char> h(bytes);
+      for (size_t i = 0; i < h.size(); ++i) h[i] = (unsigned char)(i % 251);
+      be::h2d(du, h.data(), bytes, s);
+      ReflectParams p;
+      p.vol = du, p.RP = L.RP, p.D0 = L.d0, p.D1 = L.d1, p.D2 = L.d2;
+      p.n0 = dims[0], p.n1 = dims[1], p.n2 = dims[2];
+      p.o0 = off[0], p.o1 = off[1], p.o2 = off[2];
+      p.axis = 2;
+      // the copy moves the volume's bytes as rows of floats (a uint16 volume: RP / 2 of them, RP is even)
+      const long row = u16 ? L.RP / 2 : L.RP, plane = (long)L.d1 * row;
+      for (int kind = 0; kind < 2; ++kind) {
+        for (int i = -1; i < reps; ++i) {  // (one round to warm up)
+          if (i == 0) be::event_record(a, s);
+          if (kind == 0)
+            be::launch_reflect_fill(p, u16 != 0, s);
+          else
+            be::launch_copy3d(dt, row, plane, du, row, plane, (int)row, L.d1, L.d0, s);
+        }
+        be::event_record(b, s);
+        be::event_sync(b);
+        ms[kind] = be::event_elapsed_ms(a, b) / (float)reps;
+      }
+    } catch (...) {
+      if (a) be::event_destroy(a);
+      if (b) be::event_destroy(b);
+      if (s) be::stream_destroy(s);
+      be::dfree(du);
+      be::dfree(dt);
+      throw;
+    }
+    be::event_destroy(a);
+    be::event_destroy(b);
+    be::stream_destroy(s);
+    be::dfree(du);
+    be::dfree(dt);
+  });
+}
+
 int mvn_set_pad_mode(const char* mode) {
   return guarded("mvn_set_pad_mode", [&] { g_pad_mode.store(parse_pad_mode(mode)); });
 }
@@ -1169,6 +1248,7 @@ const char* mvn_get_pad_mode(void) {
     case MVN_PAD_ZERO: return "zero";
     case MVN_PAD_ZERO_EXACT: return "zero_exact";
     case MVN_PAD_NONE: return "none";
+    case MVN_PAD_REFLECT: return "reflect";
     default: return "";
   }
 }

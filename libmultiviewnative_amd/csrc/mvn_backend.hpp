@@ -16,6 +16,7 @@
 #include "mvn_ingest.hpp"
 #include "mvn_extrapolate.hpp"
 #include "mvn_tv.hpp"
+#include "mvn_reflect.hpp"
 
 namespace mvn {
 namespace be {
@@ -145,6 +146,11 @@ void launch_copy3d(float* dst, long drow, long dplane, const float* src, long sr
 // (dst_u16: a uint16 stack into a uint16 volume, unconverted)
 void launch_ingest3d(const IngestParams& p, bool u16, stream_t s, bool dst_u16 = false);
 void launch_extract3d(const ExtractParams& p, stream_t s);
+// the margins around the window of an embedded stack as its mirror image, in place (mvn_reflect.hpp): one launch per
+// axis that has a margin, in the order 2, 1, 0 (p.axis is set here); u16: a uint16 volume.  reflect_counters: launches
+// and volumes filled since process start
+void launch_reflect_fill(const ReflectParams& p, bool u16, stream_t s);
+void reflect_counters(long long out[2]);
 
 // stand-alone pointwise ops on flat arrays (legacy ABI: compute_quotient / compute_final_values)
 void launch_divide(const float* view, float* inout, size_t n, stream_t s);

@@ -689,6 +689,40 @@ void launch_extract3d(const ExtractParams& p, stream_t) {
     for (int t = 0; t < MVN_INGEST_WG; ++t) mvn_extract_rows(p, blk, t);
 }
 
+static std::atomic<long long> g_reflect_launches{0}, g_reflect_volumes{0};
+void reflect_counters(long long out[2]) {
+  out[0] = g_reflect_launches.load();
+  out[1] = g_reflect_volumes.load();
+}
+
+static void check_reflect(const ReflectParams& p) {
+  const int D[3] = {p.D0, p.D1, p.D2}, n[3] = {p.n0, p.n1, p.n2}, o[3] = {p.o0, p.o1, p.o2};
+  for (int d = 0; d < 3; ++d)
+    if (n[d] < 1 || o[d] < 0 || (long)o[d] + n[d] > D[d] || n[d] > 0x3fffffff)
+      throw std::invalid_argument("mvn: reflect fill: the window does not fit the volume");
+  if (!p.vol || p.RP < p.D2 || (p.RP & 1)) throw std::invalid_argument("mvn: reflect fill: bad volume");
+}
+
+void launch_reflect_fill(const ReflectParams& p0, bool u16, stream_t) {
+  check_reflect(p0);
+  ReflectParams p = p0;
+  for (int axis = 2; axis >= 0; --axis) {
+    p.axis = axis;
+    const long nblocks = mvn_ingest_blocks(mvn_reflect_rows_of(p));
+    if (nblocks < 1) continue;  // (no margin along this axis)
+    ++g_reflect_launches;
+#pragma omp parallel for schedule(static)
+    for (long blk = 0; blk < nblocks; ++blk)
+      for (int t = 0; t < MVN_INGEST_WG; ++t) {
+        if (u16)
+          mvn_reflect_rows<uint16_t>(p, blk, t);
+        else
+          mvn_reflect_rows<float>(p, blk, t);
+      }
+  }
+  ++g_reflect_volumes;
+}
+
 static std::atomic<long> g_tv_launches{0};
 long tv_launch_count() { return g_tv_launches.load(); }
 void launch_tv(const TvParams& p0, stream_t) {

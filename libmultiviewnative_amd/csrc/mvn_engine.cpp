@@ -882,6 +882,7 @@ void Engine::set_embedding(const int dims[3], const int off[3], bool scratch) {
     be::dzero(ring_[r].weights, plan_->main_bytes(), stream_);
   }
   be::stream_sync(stream_);
+  margins_mirrored_ = false;
   be::dfree(embed_scratch_);
   embed_scratch_ = nullptr;
   for (int d = 0; d < 3; ++d) {
@@ -921,8 +922,42 @@ void Engine::image_storage_counters(long long out[2]) {
   out[1] = g_u16_ingests.load();
 }
 
+void Engine::set_reflect(bool on) {
+  be::set_device(device_);
+  if (!on && margins_mirrored_) {  // back to margins of zeros, as set_embedding leaves them
+    be::stream_sync(stream_);
+    for (size_t v = 0; v < views_.size(); ++v) {
+      if (views_[v].image && stream_pos_[v] < 0) be::dzero(views_[v].image, image_bytes(views_[v].image_u16), stream_);
+      if (views_[v].weights && stream_pos_[v] < 0) be::dzero(views_[v].weights, plan_->main_bytes(), stream_);
+    }
+    for (size_t r = 0; r < ring_.size(); ++r) {
+      if (ring_[r].image) be::dzero(ring_[r].image, image_bytes(ring_[r].image_u16), stream_);
+      be::dzero(ring_[r].weights, plan_->main_bytes(), stream_);
+    }
+    be::stream_sync(stream_);
+    margins_mirrored_ = false;
+  }
+  reflect_ = on;
+  if (on && embedded_) margins_mirrored_ = true;
+}
+
 long long Engine::ingest_stack(float* dst, const StackRef& st, float* scratch, bool dst_dirty, be::stream_t s,
                                bool dst_u16) {
+  const long long bytes = place_stack(dst, st, scratch, dst_dirty, s, dst_u16);
+  if (reflect_ && embedded_) {
+    const Layout& L = plan_->L;
+    ReflectParams p;
+    p.vol = dst, p.RP = L.RP, p.D0 = L.d0, p.D1 = L.d1, p.D2 = L.d2;
+    p.n0 = host_dims_[0], p.n1 = host_dims_[1], p.n2 = host_dims_[2];
+    p.o0 = host_off_[0], p.o1 = host_off_[1], p.o2 = host_off_[2];
+    p.axis = 2;
+    be::launch_reflect_fill(p, dst_u16, s);
+  }
+  return bytes;
+}
+
+long long Engine::place_stack(float* dst, const StackRef& st, float* scratch, bool dst_dirty, be::stream_t s,
+                              bool dst_u16) {
   const Layout& L = plan_->L;
   const int* n = host_dims_;
   if (!st.ptr) throw std::invalid_argument("mvn: null stack");

@@ -632,6 +632,12 @@ class Engine {
   StackRef dense(const float* host) const { return StackRef::dense_host(host, host_dims_); }
   // quotient 0 wherever the view is exactly 0 (see EpilogueParams::guard_zero_view)
   void set_quotient_guard(bool on) { quotient_guard_ = on; }
+  // Padding policy "reflect" (mvn_reflect.hpp): every stack placed from now on (set_view / stage_view / stream_view /
+  // ingest_device_view / set_psi) has the margins around its window filled with its mirror image, on the stream that
+  // placed it.  Called after set_embedding.  The copies that place a stack write its window only and rely on margins
+  // that still hold zeros: an engine whose image and weights volumes may hold mirrored margins clears them all (ring
+  // slots included) when it is switched back.
+  void set_reflect(bool on);
   // the PSF form rule on this engine's plan, with the switches read when the engine was built
   FormRule form_rule() const { return FormRule(plan_->L, sw_, plan_->fixed); }
   // will a kernel of these extents be held in the direct dim0 form?
@@ -668,6 +674,10 @@ class Engine {
   // float32 stack would be, by the uint16 -> uint16 ingest pass otherwise
   long long ingest_stack(float* dst, const StackRef& st, float* scratch, bool dst_dirty, be::stream_t s,
                          bool dst_u16 = false);
+  // the placement itself, of ingest_stack: the reflect fill goes behind it
+  long long place_stack(float* dst, const StackRef& st, float* scratch, bool dst_dirty, be::stream_t s, bool dst_u16);
+  bool reflect_ = false;           // set_reflect
+  bool margins_mirrored_ = false;  // some image / weights volume or ring slot may hold mirrored margins
   // image and weights of one view; without an embedding scratch a uint16 image that is converted lands in the weights
   // volume first
   long long ingest_pair(float* image_dst, float* weights_dst, const StackRef& image, const StackRef& weights,

@@ -310,6 +310,12 @@ __global__ __launch_bounds__(MVN_INGEST_WG) void k_extract3d(const ExtractParams
   mvn_extract_rows(p, (long)blockIdx.x, (int)threadIdx.x);
 }
 
+// the margins of an embedded stack as its mirror image, one axis per launch (mvn_reflect.hpp)
+template <typename T>
+__global__ __launch_bounds__(MVN_INGEST_WG) void k_reflect3d(const ReflectParams p) {
+  mvn_reflect_rows<T>(p, (long)blockIdx.x, (int)threadIdx.x);
+}
+
 // vector extrapolation between sweeps (mvn_extrapolate.hpp): two streaming passes and the reduction between them
 template <int W>
 __global__ __launch_bounds__(MVN_ACCEL_WG) void k_accel_a(const AccelParams p) {
@@ -1124,6 +1130,38 @@ void launch_extract3d(const ExtractParams& p, stream_t s) {
   if (nblocks < 1 || nblocks > 0x7fffffffL) throw std::invalid_argument("mvn: grid size out of range");
   hipLaunchKernelGGL(k_extract3d, dim3((unsigned)nblocks), dim3(MVN_INGEST_WG), 0, hs(s), p);
   HIP_CHECK(hipGetLastError());
+}
+
+static std::atomic<long long> g_reflect_launches{0}, g_reflect_volumes{0};
+void reflect_counters(long long out[2]) {
+  out[0] = g_reflect_launches.load();
+  out[1] = g_reflect_volumes.load();
+}
+
+static void check_reflect(const ReflectParams& p) {
+  const int D[3] = {p.D0, p.D1, p.D2}, n[3] = {p.n0, p.n1, p.n2}, o[3] = {p.o0, p.o1, p.o2};
+  for (int d = 0; d < 3; ++d)
+    if (n[d] < 1 || o[d] < 0 || (long)o[d] + n[d] > D[d] || n[d] > 0x3fffffff)
+      throw std::invalid_argument("mvn: reflect fill: the window does not fit the volume");
+  if (!p.vol || p.RP < p.D2 || (p.RP & 1)) throw std::invalid_argument("mvn: reflect fill: bad volume");
+}
+
+void launch_reflect_fill(const ReflectParams& p0, bool u16, stream_t s) {
+  check_reflect(p0);
+  ReflectParams p = p0;
+  for (int axis = 2; axis >= 0; --axis) {
+    p.axis = axis;
+    const long nblocks = mvn_ingest_blocks(mvn_reflect_rows_of(p));
+    if (nblocks < 1) continue;  // (no margin along this axis)
+    if (nblocks > 0x7fffffffL) throw std::invalid_argument("mvn: grid size out of range");
+    ++g_reflect_launches;
+    if (u16)
+      hipLaunchKernelGGL(k_reflect3d<uint16_t>, dim3((unsigned)nblocks), dim3(MVN_INGEST_WG), 0, hs(s), p);
+    else
+      hipLaunchKernelGGL(k_reflect3d<float>, dim3((unsigned)nblocks), dim3(MVN_INGEST_WG), 0, hs(s), p);
+    HIP_CHECK(hipGetLastError());
+  }
+  ++g_reflect_volumes;
 }
 
 static unsigned accel_grid(const AccelParams& p, int W) {

@@ -47,7 +47,7 @@ ENGINE_ABI_SYMBOLS = [
     "mvn_engine_get_psi_described",
     "mvn_set_acceleration", "mvn_get_acceleration", "mvn_last_acceleration", "mvn_engine_iterate_accelerated",
     "mvn_set_regularization", "mvn_get_regularization", "mvn_engine_set_regularization", "mvn_tv_factor",
-    "mvn_tv_time", "mvn_tv_launch_count",
+    "mvn_tv_time", "mvn_tv_launch_count", "mvn_reflect_counters", "mvn_reflect_time",
     "mvn_set_image_storage", "mvn_get_image_storage", "mvn_deconvolve_memory_described", "mvn_image_storage_counters",
     "mvn_set_background", "mvn_get_background", "mvn_set_likelihood", "mvn_get_likelihood", "mvn_last_likelihood",
     "mvn_engine_set_noise_model", "mvn_engine_last_likelihood",
@@ -185,6 +185,9 @@ class Binding:
         l.mvn_last_likelihood.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_int]
         l.mvn_engine_set_noise_model.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int]
         l.mvn_engine_last_likelihood.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_int]
+        l.mvn_reflect_counters.argtypes = [C.POINTER(C.c_longlong)]
+        l.mvn_reflect_time.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,
+                                       C.c_int, C.POINTER(C.c_float)]
         l.mvn_tv_launch_count.restype = C.c_long
         l.mvn_tv_launch_count.argtypes = []
         l.mvn_engine_compute_delta.argtypes = [C.c_void_p, C.c_double, C.c_float]
@@ -241,7 +244,8 @@ class Binding:
         return self.l.mvn_backend_name().decode()
 
     def set_pad_mode(self, mode):
-        """'zero' | 'zero_exact' | 'none' | None (back to MVN_PAD_MODE / the default)."""
+        """'zero' | 'zero_exact' | 'none' | 'reflect' (the volume of 'zero', mirrored margins instead of zeros) | None
+        (back to MVN_PAD_MODE / the default)."""
         self.check(self.l.mvn_set_pad_mode(mode.encode() if mode else None))
 
     def get_pad_mode(self):
@@ -402,11 +406,26 @@ class Binding:
     def tv_launch_count(self):
         return int(self.l.mvn_tv_launch_count())
 
+    def reflect_counters(self):
+        """mvn_reflect_counters: (launches of the reflect fill, volumes filled) since process start."""
+        out = (C.c_longlong * 2)(0, 0)
+        self.check(self.l.mvn_reflect_counters(out))
+        return int(out[0]), int(out[1])
+
+    def reflect_time(self, dims, ext, off, u16=False, reps=10, device=0):
+        """mvn_reflect_time: (ms per reflect fill of a resident volume of extents `ext` around a window of extents `dims`
+        at offset `off`, ms per plain copy of that volume)."""
+        ms = (C.c_float * 2)(0, 0)
+        self.check(self.l.mvn_reflect_time(device, (C.c_int * 3)(*dims), (C.c_int * 3)(*ext), (C.c_int * 3)(*off),
+                                           int(bool(u16)), int(reps), ms))
+        return float(ms[0]), float(ms[1])
+
     # ---- reference ABI, numpy in / numpy out ----------------------------------------------
     def gpu_deconvolve(self, psi, holder, device=0, pad_mode="none"):
         """inplace_gpu_deconvolve on a copy of psi.  `pad_mode` defaults to the CPU path's cyclic
         policy, the one the oracle implements (the library's own default is 'zero', the reference
-        GPU entry's); pass pad_mode=False to leave the process-wide setting alone.  The setting
+        GPU entry's; 'reflect' is that volume with mirrored margins); pass pad_mode=False to leave the process-wide
+        setting alone.  The setting
         found on entry is restored on exit (the switch is process-wide: not for concurrent callers)."""
         out = np.ascontiguousarray(psi, dtype=np.float32).copy()
         before = self.get_pad_mode()
