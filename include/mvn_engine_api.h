@@ -102,6 +102,69 @@ MVN_API int mvn_get_image_storage(int* mode);
  * mvn_deconvolve_memory's figure. */
 MVN_API int mvn_deconvolve_memory_described(struct workspace input, const mvn_call_desc* desc, int device,
                                             int streamed_views, size_t* bytes);
+/* ---- resampled views: the raw stack and a 3 x 4 matrix ----------------------------------------------------------
+ * mvn_deconvolve_resampled is mvn_deconvolve_described for views that are NOT registered yet: image_ of view v is the
+ * raw camera stack, desc->image[v] describes it (dtype, location, strides) over geom[v].src_dims, and geom[v] maps the
+ * block into it.  image_dims_ / weights_dims_ are the block's extents, which are psi's.  A block's position inside a
+ * larger data set is folded into the matrix's fourth column by the caller: the next block of the same data set uses the
+ * same raw pointers and another offset.
+ *
+ * Image.  For block voxel (z, y, x), 0-based integer indices in image_dims_:
+ *   coordinate   c_k = ((M[k][0]*z + M[k][1]*y) + M[k][2]*x) + M[k][3], k = 0, 1, 2, in double, no contraction, every
+ *                operation rounded once
+ *   inside       iff 0 <= c_k <= m_k - 1 for every k, compared in double; a voxel that is not inside gets image 0 and
+ *                weight 0
+ *   cell         i_k = floor(c_k), f_k = (float)(c_k - (double)i_k); neighbour j_k = min(i_k + 1, m_k - 1) (the clamp is
+ *                reached only with f_k == 0: an extent of 1 is no special case)
+ *   samples      S(a, b, c): the raw element widened to float32 (uint16 to float is exact)
+ *   trilinear    in float32, no contraction, lerp(p, q, f) = p + f * (q - p) (one subtract, one multiply, one add):
+ *                a_pq = lerp(S(p, q, i2), S(p, q, j2), f2) for p in {i0, j0}, q in {i1, j1};
+ *                b_p = lerp(a_p,i1, a_p,j1, f1);  v = lerp(b_i0, b_j0, f0)
+ * Blend weight (Fiji's cosine blend), for inside voxels: d_k = min(c_k, (m_k - 1) - c_k) in double, dk = (float)d_k,
+ *   r_k = 0 when dk < border_k; 1 when range_k == 0 or dk >= border_k + range_k; otherwise
+ *   0.5f * (1.0f - cosf(pi_f * ((dk - border_k) / range_k)));  w = (r_0 * r_1) * r_2.
+ * Normalisation over the views, once per call, after every view has been placed, over the stacks' window only, in
+ *   float32: W = ((w_0 + w_1) + ...) + w_{V-1} in view order, then w_v <- W > 0 ? w_v / W : 0, so sum_v w_v <= 1.
+ *   Under "reflect" the mirror fill of computed weights runs behind the normalisation.
+ *
+ * weights_mode 0: the caller's weights stacks (weights_, desc->weights), exactly as in the described call.
+ * weights_mode 1: computed and normalised as above; weights_ and desc->weights are ignored (weights_ may be NULL).
+ * Raw stacks in device memory are read where they lie; a raw stack in host memory (dense or contiguous rows, or one
+ * value) is uploaded as it is into a temporary device buffer for the placement, one view at a time.  The call runs
+ * resident on one device whatever the memory mode and MVN_DEVICES say, and holds its images as float32 whatever
+ * mvn_set_image_storage says (interpolated values are no integers).  Everything behind the placement is the described
+ * call's: padding policy, the loop's switches, caches, statistics.  Errors (< 0, message in mvn_last_error(), psi
+ * untouched) beyond the described call's: a NULL geom, a non-finite matrix entry, a negative or non-finite border or
+ * range, src_dims < 1, a weights_mode other than 0 or 1.
+ * mvn_deconvolve_memory_resampled: mvn_deconvolve_memory_described's figure with float32 images and no streamed views,
+ * plus the bytes of the largest raw stack in host memory (the temporary upload); it allocates nothing.
+ * Out of scope: interpolation other than trilinear; mvn_deconvolve_submit; streamed views; mvn_group_* / mvn_slab_* /
+ * halo mode (mvn_engine_set_view_resampled on an engine with a halo hook is an error); a mix of resampled and plain
+ * views in one call; filling the padded margins with real raw data from beyond the block. */
+typedef struct mvn_view_geometry {
+  int src_dims[3];       /* extents m0, m1, m2 of the raw stack image_ points to */
+  double matrix[12];     /* row-major 3 x 4: raw index c = M * (z, y, x, 1) of block voxel (z, y, x) */
+  float blend_border[3]; /* per raw axis, in raw voxels, >= 0: weight 0 within this distance of a face */
+  float blend_range[3];  /* per raw axis, in raw voxels, >= 0: width of the cosine ramp behind the border */
+} mvn_view_geometry;
+MVN_API int mvn_deconvolve_resampled(void* psi, struct workspace input, const mvn_call_desc* desc,
+                                     const mvn_view_geometry* geom, int weights_mode, int device);
+MVN_API int mvn_deconvolve_memory_resampled(struct workspace input, const mvn_call_desc* desc,
+                                            const mvn_view_geometry* geom, int weights_mode, int device, size_t* bytes);
+/* Test and bench utilities.  mvn_resample_stack: the resample pass alone - the raw stack src (src_desc over
+ * geom->src_dims, NULL = dense float32 in host memory; host or device memory) into two dense float32 HOST arrays of
+ * extents out_dims, the image and the unnormalised weights (either may be NULL).
+ * mvn_resample_time: ms[0] = milliseconds per pass (image and weights written) into resident volumes of extents out_dims
+ * from a resident raw stack of geom->src_dims, uint16 (u16 != 0) or float32, `reps` passes between two stream events;
+ * ms[1] = the same for streaming traffic of the output's size, one volume read and two written (a copy of a volume and
+ * a clear of a second one).
+ * mvn_resample_counters: out[0] = launches of the resample pass, out[1] = launches of the normalisation, since process
+ * start. */
+MVN_API int mvn_resample_stack(int device, const void* src, const mvn_stack_desc* src_desc, const mvn_view_geometry* geom,
+                               const int out_dims[3], float* image_out, float* weights_out);
+MVN_API int mvn_resample_time(int device, int u16, const mvn_view_geometry* geom, const int out_dims[3], int reps,
+                              float* ms);
+MVN_API int mvn_resample_counters(long long out[2]);
 /* out[0] = divide passes launched on a uint16 image, out[1] = ingest passes that wrote a uint16 volume, since process start */
 MVN_API int mvn_image_storage_counters(long long out[2]);
 /* Padding policy of inplace_gpu_deconvolve for the calls that follow (process-wide): "zero"
@@ -317,6 +380,17 @@ MVN_API int mvn_engine_set_view_described(mvn_engine* e, int v, const void* imag
                                           const float* kernel2, const int k2dims[3], void* stream);
 MVN_API int mvn_engine_set_psi_described(mvn_engine* e, const void* psi, const mvn_stack_desc* d, void* stream);
 MVN_API int mvn_engine_get_psi_described(mvn_engine* e, void* psi, const mvn_stack_desc* d);
+/* A resampled view (mvn_view_geometry above): `image` is the RAW stack, image_desc describes it over geom->src_dims
+ * (NULL: dense float32 in host memory); the engine's extents are the block's.  weights: a stack of the block's extents
+ * as in mvn_engine_set_view_described, or NULL - the view's weights are then computed from the geometry,
+ * UNNORMALISED: call mvn_engine_normalize_weights once after the last view has been set (it divides the weights of
+ * every view of the engine by their sum, in view order, and blocks).  The image is held as float32 whatever
+ * mvn_set_image_storage says.  An engine with a halo hook refuses both. */
+MVN_API int mvn_engine_set_view_resampled(mvn_engine* e, int v, const void* image, const mvn_stack_desc* image_desc,
+                                          const mvn_view_geometry* geom, const void* weights,
+                                          const mvn_stack_desc* weights_desc, const float* kernel1, const int k1dims[3],
+                                          const float* kernel2, const int k2dims[3], void* stream);
+MVN_API int mvn_engine_normalize_weights(mvn_engine* e);
 /* enqueue `iterations` sequential (Gauss-Seidel) sweeps over the views */
 MVN_API int mvn_engine_iterate(mvn_engine* e, int iterations, double lambda, float min_value);
 /* resident engine, blocking: stats receives 3 doubles per iteration run ({S_k, M_k, P_k} over the whole volume,

@@ -69,6 +69,32 @@ assert C.sizeof(CallDesc) == 56
 assert (CallDesc.image.offset, CallDesc.weights.offset, CallDesc.stream.offset) == (32, 40, 48)
 
 
+class ViewGeometry(C.Structure):
+    """mvn_view_geometry: a raw stack's extents, the 3 x 4 matrix from block voxel to raw index, and the blend."""
+    _fields_ = [
+        ("src_dims", C.c_int * 3),
+        ("matrix", C.c_double * 12),
+        ("blend_border", C.c_float * 3),
+        ("blend_range", C.c_float * 3),
+    ]
+
+
+assert C.sizeof(ViewGeometry) == 136 and ViewGeometry.matrix.offset == 16 and ViewGeometry.blend_border.offset == 112
+
+
+def view_geometry(src_shape, matrix, border=(0, 0, 0), blend_range=(0, 0, 0)):
+    """A ViewGeometry from a raw stack's shape, a 3 x 4 (or 12-element) matrix, and per-axis border / range."""
+    g = ViewGeometry()
+    m = np.asarray(matrix, dtype=np.float64).reshape(12)
+    for k in range(3):
+        g.src_dims[k] = int(src_shape[k])
+        g.blend_border[k] = float(border[k])
+        g.blend_range[k] = float(blend_range[k])
+    for i in range(12):
+        g.matrix[i] = float(m[i])
+    return g
+
+
 def _is_tensor(a):
     # (torch is never imported here: an object that is not a numpy array and has these is taken for a tensor)
     return not isinstance(a, np.ndarray) and hasattr(a, "data_ptr") and hasattr(a, "stride")

@@ -608,6 +608,10 @@ struct CallStacks {
   bool need_scratch = false; // some stack passes through the host-shaped embedding scratch
   int storage = 0;              // the image storage mode the call captured (mvn_set_image_storage)
   std::vector<char> keep_u16;   // per view: keeps_u16 of its image; empty: none
+  // mvn_deconvolve_resampled: the geometry of every view (image[v].geom points here; empty: no resampled call), and
+  // whether its weights are computed from it (weights[v].ptr is then null) and normalised once all views are placed
+  std::vector<ResampleGeom> geom;
+  bool computed_weights = false;
 };
 
 // a descriptor and its pointer as a StackRef, everything about it checked that can be without touching the memory
@@ -696,6 +700,7 @@ static void deconvolve_call(const workspace& input, const CallStacks& cs, int de
       // the slab drivers know none of the loop's switches, and take dense float32 stacks in host memory only
       const char* why = loop.needs_single_device();
       if (!why && pad_mode == MVN_PAD_REFLECT) why = "reflect padding";
+      if (!why && !cs.geom.empty()) why = "resampled views";
       bool plain = plain_stack(cs.psi, input.data_[0].image_dims_);
       for (int v = 0; plain && v < V; ++v)
         plain = plain_stack(cs.image[(size_t)v], input.data_[v].image_dims_) &&
@@ -746,6 +751,7 @@ static void deconvolve_call(const workspace& input, const CallStacks& cs, int de
         eng.set_view(v, cs.image[(size_t)v], cs.weights[(size_t)v], d.kernel1_, d.kernel1_dims_, d.kernel2_,
                      d.kernel2_dims_);
       }
+      if (cs.computed_weights) eng.normalize_weights();
       eng.set_psi(cs.psi);
       eng.iterate(input.num_iterations_, input.lambda_, input.minValue_, loop, conv);
       eng.sync();
@@ -768,10 +774,12 @@ static void deconvolve_call(const workspace& input, const CallStacks& cs, int de
     std::unique_lock<std::mutex> pcie(upload_mutex(dev));  // handed to the uploader thread's scope below
     eng.wait_for_caller(cs.stream);
     eng.set_psi(cs.psi);
-    // views that are in device memory already: ingested on the compute stream, in view order
+    // views that are in device memory already: ingested on the compute stream, in view order; resampled views too,
+    // wherever their raw stacks are (computed weights need every view in place before the loop's first read)
     for (int v = 0; v < V; ++v)
-      if (cs.image[(size_t)v].device && cs.weights[(size_t)v].device)
+      if ((cs.image[(size_t)v].device && cs.weights[(size_t)v].device) || cs.image[(size_t)v].geom)
         eng.ingest_device_view(v, cs.image[(size_t)v], cs.weights[(size_t)v]);
+    if (cs.computed_weights) eng.normalize_weights();
     lap("upload psi");
     std::exception_ptr up_err;
     std::thread uploader([&] {
@@ -875,6 +883,89 @@ int mvn_deconvolve_described(void* psi, struct workspace input, const mvn_call_d
                                     std::to_string(device));
       if (owner >= 0) device = owner;
     }
+    deconvolve_call(input, dc, device, 0, current_pad_mode(), mode, &t_last_conv);
+  });
+}
+
+// ---- resampled views (mvn_resample.hpp) --------------------------------------------------------------------------
+// a caller's geometry as the kernels take it, refused before anything is touched
+static ResampleGeom checked_geometry(const mvn_view_geometry* g, const std::string& what) {
+  if (!g) throw std::invalid_argument(what + ": null geometry");
+  ResampleGeom r;
+  for (int k = 0; k < 3; ++k) {
+    if (g->src_dims[k] < 1) throw std::invalid_argument(what + ": src_dims must be >= 1");
+    r.m[k] = g->src_dims[k];
+    const float b = g->blend_border[k], w = g->blend_range[k];
+    if (!std::isfinite(b) || !std::isfinite(w) || b < 0.f || w < 0.f)
+      throw std::invalid_argument(what + ": blend border and range must be finite and >= 0");
+    r.border[k] = b, r.range[k] = w;
+  }
+  for (int i = 0; i < 12; ++i) {
+    if (!std::isfinite(g->matrix[i])) throw std::invalid_argument(what + ": non-finite matrix entry");
+    r.M[i] = g->matrix[i];
+  }
+  return r;
+}
+
+// the views of a resampled call with every member check_workspace asks for (computed weights bring no weights_)
+static std::vector<view_data> resampled_views(const workspace& input, int weights_mode) {
+  if (weights_mode != 0 && weights_mode != 1) throw std::invalid_argument("weights_mode must be 0 (the caller's) or 1 (computed)");
+  if (input.num_views_ < 0) throw std::invalid_argument("num_views_ must be >= 0");
+  if (!input.data_) throw std::invalid_argument("null psi or workspace");
+  std::vector<view_data> views(input.data_, input.data_ + input.num_views_);
+  if (weights_mode == 1)
+    for (view_data& d : views) d.weights_ = d.image_;  // (never read: the stacks of the call carry no weights)
+  return views;
+}
+
+int mvn_deconvolve_resampled(void* psi, struct workspace input, const mvn_call_desc* desc, const mvn_view_geometry* geom,
+                             int weights_mode, int device) {
+  return guarded("mvn_deconvolve_resampled", [&] {
+    const LoopOptions mode = current_loop();
+    t_last_conv = LoopResult();
+    if (!geom) throw std::invalid_argument("null geom");
+    std::vector<view_data> views = resampled_views(input, weights_mode);
+    input.data_ = views.data();
+    check_workspace((const imageType*)psi, input);
+    const int V = input.num_views_;
+    if (V == 0) return;
+    const int* dims = input.data_[0].image_dims_;
+    for (int d = 0; d < 3; ++d)
+      if (dims[d] < 1) throw std::invalid_argument("image extents must be >= 1");
+    // everything about descriptors and geometries is settled before any stack is touched
+    CallStacks dc;
+    dc.stream = desc ? desc->stream : nullptr;
+    dc.computed_weights = weights_mode == 1;
+    dc.psi = described_stack(psi, desc ? &desc->psi : nullptr, dims, "psi", false, true);
+    int owner = -1;
+    check_location(dc.psi, "psi", &owner);
+    dc.geom.reserve((size_t)V);
+    for (int v = 0; v < V; ++v) dc.geom.push_back(checked_geometry(geom + v, "geom " + std::to_string(v)));
+    for (int v = 0; v < V; ++v) {
+      const view_data& d = input.data_[v];
+      const std::string n = std::to_string(v);
+      StackRef im = described_stack(d.image_, desc && desc->image ? desc->image + v : nullptr, dc.geom[(size_t)v].m,
+                                    "image " + n, true, false);
+      im.geom = &dc.geom[(size_t)v];
+      dc.image.push_back(im);
+      check_location(dc.image.back(), "image " + n, &owner);
+      if (dc.computed_weights) {
+        dc.weights.push_back(StackRef());
+      } else {
+        dc.weights.push_back(described_stack(d.weights_, desc && desc->weights ? desc->weights + v : nullptr,
+                                             d.image_dims_, "weights " + n, false, false));
+        check_location(dc.weights.back(), "weights " + n, &owner);
+      }
+    }
+    dc.storage = g_image_storage.load();  // (resampled images are float32 volumes: keep_u16 stays empty)
+    dc.need_scratch = through_scratch(dc.psi);
+    for (int v = 0; v < V && !dc.computed_weights; ++v)
+      dc.need_scratch = dc.need_scratch || through_scratch(dc.weights[(size_t)v]);
+    dc.any_device = true;  // resident on one device, as calls with device stacks are
+    if (owner >= 0 && device >= 0 && device != owner)
+      throw std::invalid_argument("the stacks live on device " + std::to_string(owner) + ", not on device " +
+                                  std::to_string(device));
+    if (owner >= 0) device = owner;
     deconvolve_call(input, dc, device, 0, current_pad_mode(), mode, &t_last_conv);
   });
 }
@@ -1239,6 +1330,132 @@ int mvn_reflect_time(int device, const int dims[3], const int ext[3], const int 
   });
 }
 
+int mvn_resample_counters(long long out[2]) {
+  return guarded("mvn_resample_counters", [&] {
+    if (!out) throw std::invalid_argument("null out");
+    be::resample_counters(out);
+  });
+}
+
+// the volumes of a stand-alone resample pass: dense extents dims, the window the whole volume
+static ResampleParams resample_alone(const Layout& L, float* image, float* weights) {
+  ResampleParams p;
+  p.image = image, p.weights = weights, p.RP = L.RP, p.D0 = L.d0, p.D1 = L.d1;
+  p.n0 = L.d0, p.n1 = L.d1, p.n2 = L.d2;
+  p.o0 = p.o1 = p.o2 = 0;
+  return p;
+}
+
+// the pass of mvn_resample.hpp alone, into dense host arrays: a test and bench utility
+int mvn_resample_stack(int device, const void* src, const mvn_stack_desc* src_desc, const mvn_view_geometry* geom,
+                       const int out_dims[3], float* image_out, float* weights_out) {
+  return guarded("mvn_resample_stack", [&] {
+    if (!src || !out_dims) throw std::invalid_argument("null argument");
+    if (out_dims[0] < 1 || out_dims[1] < 1 || out_dims[2] < 1) throw std::invalid_argument("extents must be positive");
+    const ResampleGeom g = checked_geometry(geom, "geom");
+    StackRef st = described_stack(src, src_desc, g.m, "src", true, false);
+    st.geom = &g;
+    int owner = -1;
+    check_location(st, "src", &owner);
+    if (owner >= 0 && device >= 0 && device != owner) throw std::invalid_argument("src lives on another device");
+    const int dev = pick_device(owner >= 0 ? owner : device);
+    std::lock_guard<std::mutex> lk(device_mutex(dev));
+    be::set_device(dev);
+    const Layout L(out_dims[0], out_dims[1], out_dims[2]);
+    const size_t bytes = L.real_floats() * sizeof(float), width = (size_t)L.d2 * sizeof(float),
+                 pitch = (size_t)L.RP * sizeof(float);
+    float *di = nullptr, *dw = nullptr;
+    be::stream_t s = nullptr;
+    try {
+      di = (float*)be::dmalloc(bytes);
+      dw = (float*)be::dmalloc(bytes);
+      s = be::stream_create();
+      Engine::resample_raw(resample_alone(L, di, dw), st, s);
+      if (image_out) be::d2h_2d(image_out, width, di, pitch, width, (size_t)L.rows, s);
+      if (weights_out) be::d2h_2d(weights_out, width, dw, pitch, width, (size_t)L.rows, s);
+      be::stream_sync(s);
+    } catch (...) {
+      if (s) be::stream_destroy(s);
+      be::dfree(di);
+      be::dfree(dw);
+      throw;
+    }
+    be::stream_destroy(s);
+    be::dfree(di);
+    be::dfree(dw);
+  });
+}
+
+// ms[0]: the pass of mvn_resample.hpp from a resident raw stack into resident volumes, per pass over `reps` passes
+// between two stream events; ms[1]: streaming traffic of the output's size, one volume read and two written
+// (launch_copy3d of a volume and a clear of a second one), likewise
+int mvn_resample_time(int device, int u16, const mvn_view_geometry* geom, const int out_dims[3], int reps, float* ms) {
+  return guarded("mvn_resample_time", [&] {
+    if (!out_dims || !ms) throw std::invalid_argument("null argument");
+    if (out_dims[0] < 1 || out_dims[1] < 1 || out_dims[2] < 1 || reps < 1)
+      throw std::invalid_argument("extents and reps must be positive");
+    const ResampleGeom g = checked_geometry(geom, "geom");
+    const int dev = pick_device(device);
+    std::lock_guard<std::mutex> lk(device_mutex(dev));
+    be::set_device(dev);
+    const Layout L(out_dims[0], out_dims[1], out_dims[2]);
+    const size_t bytes = L.real_floats() * sizeof(float);
+    const size_t esz = u16 ? sizeof(uint16_t) : sizeof(float);
+    const size_t raw = (size_t)g.m[0] * (size_t)g.m[1] * (size_t)g.m[2];
+    float *di = nullptr, *dw = nullptr;
+    void* dr = nullptr;
+    be::stream_t s = nullptr;
+    be::event_t a = nullptr, b = nullptr;
+    try {
+      di = (float*)be::dmalloc(bytes);
+      dw = (float*)be::dmalloc(bytes);
+      dr = be::dmalloc(raw * esz);
+      s = be::stream_create();
+      a = be::event_create();
+      b = be::event_create();
+      std::vector<unsigned char> h(raw * esz);
+      if (u16)
+        for (size_t i = 0; i < raw; ++i) ((uint16_t*)h.data())[i] = (uint16_t)(100u + i % 4001u);
+      else
+        for (size_t i = 0; i < raw; ++i) ((float*)h.data())[i] = 100.f + (float)(i % 4001u);
+      be::h2d(dr, h.data(), h.size(), s);
+      be::dzero(di, bytes, s);
+      be::stream_sync(s);
+      ResampleParams p = resample_alone(L, di, dw);
+      p.src = dr, p.s0 = (long long)g.m[1] * g.m[2], p.s1 = g.m[2], p.s2 = 1;
+      p.g = g;
+      for (int kind = 0; kind < 2; ++kind) {
+        for (int i = -1; i < reps; ++i) {  // (one round to warm up)
+          if (i == 0) be::event_record(a, s);
+          if (kind == 0) {
+            be::launch_resample(p, u16 != 0, s);
+          } else {
+            be::launch_copy3d(dw, L.RP, (long)L.d1 * L.RP, di, L.RP, (long)L.d1 * L.RP, (int)L.RP, L.d1, L.d0, s);
+            be::dzero(di, bytes, s);
+          }
+        }
+        be::event_record(b, s);
+        be::event_sync(b);
+        ms[kind] = be::event_elapsed_ms(a, b) / (float)reps;
+      }
+    } catch (...) {
+      if (a) be::event_destroy(a);
+      if (b) be::event_destroy(b);
+      if (s) be::stream_destroy(s);
+      be::dfree(di);
+      be::dfree(dw);
+      be::dfree(dr);
+      throw;
+    }
+    be::event_destroy(a);
+    be::event_destroy(b);
+    be::stream_destroy(s);
+    be::dfree(di);
+    be::dfree(dw);
+    be::dfree(dr);
+  });
+}
+
 int mvn_set_pad_mode(const char* mode) {
   return guarded("mvn_set_pad_mode", [&] { g_pad_mode.store(parse_pad_mode(mode)); });
 }
@@ -1314,6 +1531,27 @@ int mvn_deconvolve_memory_described(struct workspace input, const mvn_call_desc*
                                     size_t* bytes) {
   return guarded("mvn_deconvolve_memory_described",
                  [&] { deconvolve_memory(input, desc, device, streamed_views, bytes); });
+}
+
+int mvn_deconvolve_memory_resampled(struct workspace input, const mvn_call_desc* desc, const mvn_view_geometry* geom,
+                                    int weights_mode, int device, size_t* bytes) {
+  return guarded("mvn_deconvolve_memory_resampled", [&] {
+    if (!geom) throw std::invalid_argument("null geom");
+    std::vector<view_data> views = resampled_views(input, weights_mode);
+    input.data_ = views.data();
+    // (images are float32 volumes: the figure of dense float32 stacks)
+    deconvolve_memory(input, nullptr, device, 0, bytes);
+    size_t upload = 0;  // one raw stack in host memory at a time
+    for (int v = 0; v < input.num_views_; ++v) {
+      const ResampleGeom g = checked_geometry(geom + v, "geom " + std::to_string(v));
+      const mvn_stack_desc* d = desc && desc->image ? desc->image + v : nullptr;
+      if (d && d->location == MVN_DEVICE) continue;
+      const size_t esz = d && d->dtype == MVN_U16 ? sizeof(uint16_t) : sizeof(float);
+      const bool one = d && d->stride[0] == 0 && d->stride[1] == 0 && d->stride[2] == 0;
+      upload = std::max(upload, one ? esz : (size_t)g.m[0] * (size_t)g.m[1] * (size_t)g.m[2] * esz);
+    }
+    *bytes += upload;
+  });
 }
 
 int mvn_set_image_storage(int mode) {
@@ -2078,6 +2316,30 @@ int mvn_engine_set_view_described(mvn_engine* e, int v, const void* image, const
                                   const int k1dims[3], const float* kernel2, const int k2dims[3], void* stream) {
   MVN_ENGINE_CALL("mvn_engine_set_view_described", engine_set_view(E, v, image, image_desc, weights, weights_desc, kernel1,
                                                                    k1dims, kernel2, k2dims, stream, true));
+}
+
+int mvn_engine_set_view_resampled(mvn_engine* e, int v, const void* image, const mvn_stack_desc* image_desc,
+                                  const mvn_view_geometry* geom, const void* weights, const mvn_stack_desc* weights_desc,
+                                  const float* kernel1, const int k1dims[3], const float* kernel2, const int k2dims[3],
+                                  void* stream) {
+  MVN_ENGINE_CALL("mvn_engine_set_view_resampled", {
+    if (!kernel1 || !kernel2 || !k1dims || !k2dims) throw std::invalid_argument("null kernel");
+    if (E.has_halo_hook()) throw std::invalid_argument("resampled views are not for an engine with a halo hook");
+    const ResampleGeom g = checked_geometry(geom, "geom");
+    StackRef im = described_stack(image, image_desc, g.m, "image", true, false);
+    im.geom = &g;
+    const StackRef w = weights ? engine_stack(E, weights, weights_desc, "weights", false, false) : StackRef();
+    int owner = -1;
+    check_location(im, "image", &owner);
+    if (weights) check_location(w, "weights", &owner);
+    if (owner >= 0 && owner != E.device()) throw std::invalid_argument("the stacks live on another device than the engine");
+    E.wait_for_caller(stream);
+    E.set_view(v, im, w, kernel1, k1dims, kernel2, k2dims);
+  });
+}
+
+int mvn_engine_normalize_weights(mvn_engine* e) {
+  MVN_ENGINE_CALL("mvn_engine_normalize_weights", E.normalize_weights());
 }
 
 int mvn_engine_set_psi_described(mvn_engine* e, const void* psi, const mvn_stack_desc* d, void* stream) {

@@ -17,6 +17,7 @@
 #include "mvn_extrapolate.hpp"
 #include "mvn_tv.hpp"
 #include "mvn_reflect.hpp"
+#include "mvn_resample.hpp"
 
 namespace mvn {
 namespace be {
@@ -151,6 +152,12 @@ void launch_extract3d(const ExtractParams& p, stream_t s);
 // and volumes filled since process start
 void launch_reflect_fill(const ReflectParams& p, bool u16, stream_t s);
 void reflect_counters(long long out[2]);
+// a raw view into the image volume and (p.weights) the unnormalised weights volume (mvn_resample.hpp; the raw stack is
+// DEVICE memory here, u16: its element type), and the weights of the V volumes behind the device table p.vols over
+// their sum.  resample_counters: launches of the one and of the other since process start
+void launch_resample(const ResampleParams& p, bool u16, stream_t s);
+void launch_weights_normalize(const NormalizeParams& p, stream_t s);
+void resample_counters(long long out[2]);
 
 // stand-alone pointwise ops on flat arrays (legacy ABI: compute_quotient / compute_final_values)
 void launch_divide(const float* view, float* inout, size_t n, stream_t s);

@@ -723,6 +723,59 @@ void launch_reflect_fill(const ReflectParams& p0, bool u16, stream_t) {
   ++g_reflect_volumes;
 }
 
+static std::atomic<long long> g_resample_launches{0}, g_normalize_launches{0};
+void resample_counters(long long out[2]) {
+  out[0] = g_resample_launches.load();
+  out[1] = g_normalize_launches.load();
+}
+
+static void check_window(const char* what, long RP, int D0, int D1, const int n[3], const int o[3]) {
+  const long D[3] = {D0, D1, RP};
+  for (int d = 0; d < 3; ++d)
+    if (n[d] < 1 || o[d] < 0 || (long)o[d] + n[d] > D[d])
+      throw std::invalid_argument(std::string("mvn: ") + what + ": the window does not fit the volume");
+  if (RP < 2 || (RP & 1)) throw std::invalid_argument(std::string("mvn: ") + what + ": bad volume");
+}
+
+static void check_resample(const ResampleParams& p) {
+  const int n[3] = {p.n0, p.n1, p.n2}, o[3] = {p.o0, p.o1, p.o2};
+  check_window("resample", p.RP, p.D0, p.D1, n, o);
+  if (!p.image || !p.src) throw std::invalid_argument("mvn: resample: null pointer");
+  if (p.s0 < 0 || p.s1 < 0 || p.s2 < 0) throw std::invalid_argument("mvn: resample: negative stride");
+  for (int k = 0; k < 3; ++k)
+    if (p.g.m[k] < 1) throw std::invalid_argument("mvn: resample: raw extents must be >= 1");
+}
+
+static void check_normalize(const NormalizeParams& p) {
+  const int n[3] = {p.n0, p.n1, p.n2}, o[3] = {p.o0, p.o1, p.o2};
+  // (the last plane's rows are all the launch needs of D0)
+  check_window("normalise", p.RP, p.o0 + p.n0, p.D1, n, o);
+  if (!p.vols || p.V < 1) throw std::invalid_argument("mvn: normalise: no volumes");
+}
+
+void launch_resample(const ResampleParams& p, bool u16, stream_t) {
+  check_resample(p);
+  const long nblocks = mvn_resample_blocks(p);
+  ++g_resample_launches;
+#pragma omp parallel for schedule(static)
+  for (long blk = 0; blk < nblocks; ++blk)
+    for (int t = 0; t < MVN_RS_WG; ++t) {
+      if (u16)
+        mvn_resample_tile<uint16_t>(p, blk, t);
+      else
+        mvn_resample_tile<float>(p, blk, t);
+    }
+}
+
+void launch_weights_normalize(const NormalizeParams& p, stream_t) {
+  check_normalize(p);
+  const long nblocks = mvn_normalize_blocks(p);
+  ++g_normalize_launches;
+#pragma omp parallel for schedule(static)
+  for (long blk = 0; blk < nblocks; ++blk)
+    for (int t = 0; t < MVN_INGEST_WG; ++t) mvn_normalize_rows(p, blk, t);
+}
+
 static std::atomic<long> g_tv_launches{0};
 long tv_launch_count() { return g_tv_launches.load(); }
 void launch_tv(const TvParams& p0, stream_t) {

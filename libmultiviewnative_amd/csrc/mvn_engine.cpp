@@ -832,6 +832,7 @@ Engine::~Engine() {
   be::dfree(psi_spec_);
   be::dfree(psi_spec_nyq_);
   be::dfree(embed_scratch_);
+  be::dfree(weights_tab_);
   if (caller_ev_) be::event_destroy(caller_ev_);
   be::dfree(poison_own_);
   be::graph_destroy(sweep_graph_);
@@ -944,16 +945,19 @@ void Engine::set_reflect(bool on) {
 long long Engine::ingest_stack(float* dst, const StackRef& st, float* scratch, bool dst_dirty, be::stream_t s,
                                bool dst_u16) {
   const long long bytes = place_stack(dst, st, scratch, dst_dirty, s, dst_u16);
-  if (reflect_ && embedded_) {
-    const Layout& L = plan_->L;
-    ReflectParams p;
-    p.vol = dst, p.RP = L.RP, p.D0 = L.d0, p.D1 = L.d1, p.D2 = L.d2;
-    p.n0 = host_dims_[0], p.n1 = host_dims_[1], p.n2 = host_dims_[2];
-    p.o0 = host_off_[0], p.o1 = host_off_[1], p.o2 = host_off_[2];
-    p.axis = 2;
-    be::launch_reflect_fill(p, dst_u16, s);
-  }
+  mirror_margins(dst, dst_u16, s);
   return bytes;
+}
+
+void Engine::mirror_margins(float* dst, bool dst_u16, be::stream_t s) {
+  if (!reflect_ || !embedded_) return;
+  const Layout& L = plan_->L;
+  ReflectParams p;
+  p.vol = dst, p.RP = L.RP, p.D0 = L.d0, p.D1 = L.d1, p.D2 = L.d2;
+  p.n0 = host_dims_[0], p.n1 = host_dims_[1], p.n2 = host_dims_[2];
+  p.o0 = host_off_[0], p.o1 = host_off_[1], p.o2 = host_off_[2];
+  p.axis = 2;
+  be::launch_reflect_fill(p, dst_u16, s);
 }
 
 long long Engine::place_stack(float* dst, const StackRef& st, float* scratch, bool dst_dirty, be::stream_t s,
@@ -961,6 +965,7 @@ long long Engine::place_stack(float* dst, const StackRef& st, float* scratch, bo
   const Layout& L = plan_->L;
   const int* n = host_dims_;
   if (!st.ptr) throw std::invalid_argument("mvn: null stack");
+  if (st.geom) throw std::invalid_argument("mvn: only the image of a view can be a raw stack with a geometry");
   if (dst_u16 && (!st.u16 || st.broadcast())) throw std::logic_error("mvn: a uint16 volume takes a uint16 stack");
   for (int d = 0; d < 3; ++d)
     if (st.stride[d] < 0) throw std::invalid_argument("mvn: negative stride");
@@ -1019,6 +1024,10 @@ long long Engine::place_stack(float* dst, const StackRef& st, float* scratch, bo
 long long Engine::ingest_pair(float* image_dst, float* weights_dst, const StackRef& image, const StackRef& weights,
                               be::stream_t s, bool image_u16) {
   if (weights.u16) throw std::invalid_argument("mvn: weights are float32");
+  if (image.geom) {
+    if (image_u16) throw std::logic_error("mvn: a resampled image is a float32 volume");
+    return resample_pair(image_dst, weights_dst, image, weights, s);
+  }
   float* scr = embed_scratch_;
   bool dirty = false;
   if (!image_u16 && !scr && !image.device && !image.broadcast() && image.u16) {
@@ -1030,6 +1039,93 @@ long long Engine::ingest_pair(float* image_dst, float* weights_dst, const StackR
   long long bytes = ingest_stack(image_dst, image, scr, false, s, image_u16);
   bytes += ingest_stack(weights_dst, weights, embed_scratch_, dirty, s);
   return bytes;
+}
+
+long long Engine::resample_pair(float* image_dst, float* weights_dst, const StackRef& image, const StackRef& weights,
+                                be::stream_t s) {
+  const Layout& L = plan_->L;
+  if (halo_fn_) throw std::invalid_argument("mvn: resampled views are not for an engine with a halo hook");
+  ResampleParams p;
+  p.image = image_dst, p.weights = weights.ptr ? nullptr : weights_dst;
+  p.RP = L.RP, p.D0 = L.d0, p.D1 = L.d1;
+  p.n0 = host_dims_[0], p.n1 = host_dims_[1], p.n2 = host_dims_[2];
+  p.o0 = host_off_[0], p.o1 = host_off_[1], p.o2 = host_off_[2];
+  long long bytes = resample_raw(p, image, s);
+  mirror_margins(image_dst, false, s);
+  // (computed weights are mirrored behind their normalisation: normalize_weights)
+  if (weights.ptr) bytes += ingest_stack(weights_dst, weights, embed_scratch_, false, s);
+  return bytes;
+}
+
+long long Engine::resample_raw(ResampleParams p, const StackRef& image, be::stream_t s) {
+  if (!image.ptr || !image.geom) throw std::invalid_argument("mvn: null stack");
+  const ResampleGeom& g = *image.geom;
+  for (int d = 0; d < 3; ++d) {
+    if (image.stride[d] < 0) throw std::invalid_argument("mvn: negative stride");
+    if (g.m[d] < 1) throw std::invalid_argument("mvn: extents of a raw stack must be >= 1");
+  }
+  p.src = image.ptr, p.s0 = image.stride[0], p.s1 = image.stride[1], p.s2 = image.stride[2];
+  p.g = g;
+  void* tmp = nullptr;
+  long long bytes = 0;
+  if (!image.device) {  // the raw stack crosses PCIe as it is, into a dense temporary
+    const size_t esz = image.u16 ? sizeof(uint16_t) : sizeof(float);
+    if (image.broadcast()) {
+      bytes = (long long)esz;
+      tmp = be::dmalloc(esz);
+      be::h2d(tmp, image.ptr, esz, s);
+    } else {
+      check_host_rows(image, g.m);
+      bytes = (long long)g.m[0] * g.m[1] * g.m[2] * (long long)esz;
+      tmp = be::dmalloc((size_t)bytes);
+      const bool dense = (g.m[1] == 1 || image.stride[1] == g.m[2]) &&
+                         (g.m[0] == 1 || image.stride[0] == (long long)g.m[1] * g.m[2]);
+      if (dense)
+        be::h2d(tmp, image.ptr, (size_t)bytes, s);
+      else
+        host_rows_to_device((char*)tmp, (size_t)g.m[2] * esz, (size_t)g.m[1] * g.m[2] * esz, (const char*)image.ptr,
+                            image.stride[0] * (long long)esz, image.stride[1] * (long long)esz, (size_t)g.m[2] * esz,
+                            g.m, s);
+      p.s0 = (long long)g.m[1] * g.m[2], p.s1 = g.m[2], p.s2 = 1;
+    }
+    p.src = tmp;
+  }
+  try {
+    be::launch_resample(p, image.u16, s);
+    if (tmp) be::stream_sync(s);
+  } catch (...) {
+    if (tmp) {
+      try {
+        be::stream_sync(s);
+      } catch (...) {
+      }
+      be::dfree(tmp);
+    }
+    throw;
+  }
+  be::dfree(tmp);
+  return bytes;
+}
+
+void Engine::normalize_weights() {
+  be::set_device(device_);
+  if (halo_fn_) throw std::invalid_argument("mvn: resampled views are not for an engine with a halo hook");
+  const Layout& L = plan_->L;
+  const size_t V = views_.size();
+  weights_tab_host_.assign(V, nullptr);
+  for (size_t v = 0; v < V; ++v) {
+    if (stream_pos_[v] >= 0 || !views_[v].weights) throw std::logic_error("mvn: normalize_weights needs every view resident and placed");
+    weights_tab_host_[v] = views_[v].weights;
+  }
+  if (!weights_tab_) weights_tab_ = (float**)be::dmalloc(V * sizeof(float*));
+  be::h2d(weights_tab_, weights_tab_host_.data(), V * sizeof(float*), stream_);
+  NormalizeParams p;
+  p.vols = weights_tab_, p.V = (int)V, p.RP = L.RP, p.D1 = L.d1;
+  p.n0 = host_dims_[0], p.n1 = host_dims_[1], p.n2 = host_dims_[2];
+  p.o0 = host_off_[0], p.o1 = host_off_[1], p.o2 = host_off_[2];
+  be::launch_weights_normalize(p, stream_);
+  for (size_t v = 0; v < V; ++v) mirror_margins(views_[v].weights, false, stream_);
+  be::stream_sync(stream_);
 }
 
 void Engine::wait_for_caller(void* caller_stream) {
@@ -1494,7 +1590,7 @@ void Engine::set_view(int v, const StackRef& image, const StackRef& weights, con
   if (stream_pos_[(size_t)v] >= 0) throw std::logic_error("mvn: a streamed view is staged by the pipelined call only");
   ViewSlot& s = views_[(size_t)v];
   // (halo mode divides row ranges, whose offsets are in floats: the image stays float32 under a hook)
-  want_u16_[(size_t)v] = image_storage_ == 1 && image.u16 && !image.broadcast() && !halo_fn_;
+  want_u16_[(size_t)v] = image_storage_ == 1 && image.u16 && !image.broadcast() && !halo_fn_ && !image.geom;
   alloc_view(s);
   ingest_pair(s.image, s.weights, image, weights, stream_, s.image_u16);
   be::stream_sync(stream_);  // the sources have been consumed

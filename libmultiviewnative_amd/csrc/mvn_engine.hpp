@@ -433,6 +433,10 @@ struct StackRef {
   bool device = false;  // device memory: the ingest / extract kernels work on it directly
   long long stride[3] = {0, 0, 0};  // in elements; all zero: one value for every voxel (inputs only)
   bool broadcast() const { return stride[0] == 0 && stride[1] == 0 && stride[2] == 0; }
+  // an IMAGE only: the stack is a raw view of extents geom->m, strides over those, and is resampled into the window
+  // through geom->M (mvn_resample.hpp) instead of being copied; the weights of such a view may have a null ptr: they
+  // are then computed from the geometry, unnormalised (Engine::normalize_weights)
+  const ResampleGeom* geom = nullptr;
   static StackRef dense_host(const float* p, const int* dims) {
     StackRef r;
     r.ptr = p;
@@ -485,6 +489,11 @@ class Engine {
   std::vector<char> image_types() const { return want_u16_; }
   // engine API (set_view): 1 = a uint16 image stack that is no broadcast is kept as uint16 unless a halo hook is set
   void set_image_storage(int mode) { image_storage_ = mode; }
+  // The resample pass of mvn_resample.hpp on the raw stack `image` (image.geom set): p brings the destination volumes and
+  // the window, the raw stack's side is filled in here.  A raw stack in host memory (contiguous rows, or one value)
+  // crosses into a temporary device buffer first, which is freed once `s` has passed it (the host waits for that).
+  // Returns the bytes that crossed PCIe.  The current device is the destination's.
+  static long long resample_raw(ResampleParams p, const StackRef& image, be::stream_t s);
   // divide passes launched on a uint16 image, ingest passes that wrote a uint16 volume, since process start
   static void image_storage_counters(long long out[2]);
   // calls that streamed views, streamed view updates, bytes streamed (host -> device), since process start
@@ -501,6 +510,10 @@ class Engine {
                 const float* kernel2, const int* k2dims);
   void set_psi(const StackRef& psi);
   void get_psi(const StackRef& psi);
+  // Computed weights (views set with a geometry and no weights stack) over their sum across ALL views, in view order,
+  // on the window (mvn_resample.hpp); under "reflect" the fill of those weights volumes runs here, behind it.  Once,
+  // after the last view has been placed.  Blocking.
+  void normalize_weights();
   // the caller produced its device stacks on `caller_stream`: the engine's streams wait for what is enqueued there
   // now (an event, no host wait); nullptr: nothing to wait for
   void wait_for_caller(void* caller_stream);
@@ -585,6 +598,7 @@ class Engine {
   // post: fn is called a second time right AFTER the leg has been enqueued, with conv + 2 - where the ranks merge
   // their poison words (a non-finite input met by ONE slab's leg must turn EVERY slab's volume into NaN)
   void set_halo_hook(halo_fn_t fn, void* user, bool drain = true, bool post = false);
+  bool has_halo_hook() const { return halo_fn_ != nullptr; }
   // Tells the engine how many planes at either end of its volume are halo planes (after set_halo_hook): no pass
   // computes them any more - the last-axis and dim1 passes and the leg run on the own planes only (where those
   // start and end on tile boundaries of the last-axis passes; otherwise everything is computed as before).
@@ -676,6 +690,14 @@ class Engine {
                          bool dst_u16 = false);
   // the placement itself, of ingest_stack: the reflect fill goes behind it
   long long place_stack(float* dst, const StackRef& st, float* scratch, bool dst_dirty, be::stream_t s, bool dst_u16);
+  // the reflect fill of ingest_stack, when the policy is on
+  void mirror_margins(float* dst, bool dst_u16, be::stream_t s);
+  // a raw view (image.geom) through the resample pass: a raw stack in host memory crosses into a temporary device
+  // buffer that is freed once the stream has passed it; weights: the caller's, placed as ever, or (null ptr) computed
+  long long resample_pair(float* image_dst, float* weights_dst, const StackRef& image, const StackRef& weights,
+                          be::stream_t s);
+  float** weights_tab_ = nullptr;          // device table of the views' weights volumes (normalize_weights)
+  std::vector<float*> weights_tab_host_;   // ... and what it was filled from
   bool reflect_ = false;           // set_reflect
   bool margins_mirrored_ = false;  // some image / weights volume or ring slot may hold mirrored margins
   // image and weights of one view; without an embedding scratch a uint16 image that is converted lands in the weights

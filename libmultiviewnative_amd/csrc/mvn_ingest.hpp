@@ -9,6 +9,7 @@
 // pass, which converts, follows strides, reads the caller's device memory and depends on no earlier clear.  (In image
 // storage mode 1 a uint16 image keeps its element type: a host stack with contiguous rows into a volume of its own
 // extents is then placed by the copy as well, with 2-byte pitches, and the pass has a uint16 -> uint16 form.)
+// (An image that is a RAW view with a geometry is not copied but resampled into the window: mvn_resample.hpp.)
 //
 //   k_ingest3d<T>   one workgroup per run of MVN_INGEST_ROWS rows of the engine volume (row pitch RP floats, plane
 //                   pitch D1 * RP).  It writes EVERY float of its rows - the converted source inside the embedding

@@ -316,6 +316,17 @@ __global__ __launch_bounds__(MVN_INGEST_WG) void k_reflect3d(const ReflectParams
   mvn_reflect_rows<T>(p, (long)blockIdx.x, (int)threadIdx.x);
 }
 
+// a raw view through its affine transform into the image and the unnormalised weights volume, and the weights of all
+// views over their sum (mvn_resample.hpp)
+template <typename T>
+__global__ __launch_bounds__(MVN_RS_WG) void k_resample3d(const ResampleParams p) {
+  mvn_resample_tile<T>(p, (long)blockIdx.x, (int)threadIdx.x);
+}
+
+__global__ __launch_bounds__(MVN_INGEST_WG) void k_weights_normalize(const NormalizeParams p) {
+  mvn_normalize_rows(p, (long)blockIdx.x, (int)threadIdx.x);
+}
+
 // vector extrapolation between sweeps (mvn_extrapolate.hpp): two streaming passes and the reduction between them
 template <int W>
 __global__ __launch_bounds__(MVN_ACCEL_WG) void k_accel_a(const AccelParams p) {
@@ -1162,6 +1173,57 @@ void launch_reflect_fill(const ReflectParams& p0, bool u16, stream_t s) {
     HIP_CHECK(hipGetLastError());
   }
   ++g_reflect_volumes;
+}
+
+static std::atomic<long long> g_resample_launches{0}, g_normalize_launches{0};
+void resample_counters(long long out[2]) {
+  out[0] = g_resample_launches.load();
+  out[1] = g_normalize_launches.load();
+}
+
+static void check_window(const char* what, long RP, int D0, int D1, const int n[3], const int o[3]) {
+  const long D[3] = {D0, D1, RP};
+  for (int d = 0; d < 3; ++d)
+    if (n[d] < 1 || o[d] < 0 || (long)o[d] + n[d] > D[d])
+      throw std::invalid_argument(std::string("mvn: ") + what + ": the window does not fit the volume");
+  if (RP < 2 || (RP & 1)) throw std::invalid_argument(std::string("mvn: ") + what + ": bad volume");
+}
+
+static void check_resample(const ResampleParams& p) {
+  const int n[3] = {p.n0, p.n1, p.n2}, o[3] = {p.o0, p.o1, p.o2};
+  check_window("resample", p.RP, p.D0, p.D1, n, o);
+  if (!p.image || !p.src) throw std::invalid_argument("mvn: resample: null pointer");
+  if (p.s0 < 0 || p.s1 < 0 || p.s2 < 0) throw std::invalid_argument("mvn: resample: negative stride");
+  for (int k = 0; k < 3; ++k)
+    if (p.g.m[k] < 1) throw std::invalid_argument("mvn: resample: raw extents must be >= 1");
+}
+
+static void check_normalize(const NormalizeParams& p) {
+  const int n[3] = {p.n0, p.n1, p.n2}, o[3] = {p.o0, p.o1, p.o2};
+  // (the last plane's rows are all the launch needs of D0)
+  check_window("normalise", p.RP, p.o0 + p.n0, p.D1, n, o);
+  if (!p.vols || p.V < 1) throw std::invalid_argument("mvn: normalise: no volumes");
+}
+
+void launch_resample(const ResampleParams& p, bool u16, stream_t s) {
+  check_resample(p);
+  const long nblocks = mvn_resample_blocks(p);
+  if (nblocks < 1 || nblocks > 0x7fffffffL) throw std::invalid_argument("mvn: grid size out of range");
+  ++g_resample_launches;
+  if (u16)
+    hipLaunchKernelGGL(k_resample3d<uint16_t>, dim3((unsigned)nblocks), dim3(MVN_RS_WG), 0, hs(s), p);
+  else
+    hipLaunchKernelGGL(k_resample3d<float>, dim3((unsigned)nblocks), dim3(MVN_RS_WG), 0, hs(s), p);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_weights_normalize(const NormalizeParams& p, stream_t s) {
+  check_normalize(p);
+  const long nblocks = mvn_normalize_blocks(p);
+  if (nblocks < 1 || nblocks > 0x7fffffffL) throw std::invalid_argument("mvn: grid size out of range");
+  ++g_normalize_launches;
+  hipLaunchKernelGGL(k_weights_normalize, dim3((unsigned)nblocks), dim3(MVN_INGEST_WG), 0, hs(s), p);
+  HIP_CHECK(hipGetLastError());
 }
 
 static unsigned accel_grid(const AccelParams& p, int W) {

@@ -12,7 +12,8 @@ import os
 
 import numpy as np
 
-from .abi import CallDesc, StackDesc, ViewData, Workspace, c_float_p, c_int_p, describe_stack, fptr, iptr
+from .abi import (CallDesc, StackDesc, ViewData, ViewGeometry, Workspace, c_float_p, c_int_p, describe_stack, fptr, iptr,
+                  view_geometry)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(_HERE, "lib")
@@ -48,6 +49,8 @@ ENGINE_ABI_SYMBOLS = [
     "mvn_set_acceleration", "mvn_get_acceleration", "mvn_last_acceleration", "mvn_engine_iterate_accelerated",
     "mvn_set_regularization", "mvn_get_regularization", "mvn_engine_set_regularization", "mvn_tv_factor",
     "mvn_tv_time", "mvn_tv_launch_count", "mvn_reflect_counters", "mvn_reflect_time",
+    "mvn_deconvolve_resampled", "mvn_deconvolve_memory_resampled", "mvn_engine_set_view_resampled",
+    "mvn_engine_normalize_weights", "mvn_resample_stack", "mvn_resample_time", "mvn_resample_counters",
     "mvn_set_image_storage", "mvn_get_image_storage", "mvn_deconvolve_memory_described", "mvn_image_storage_counters",
     "mvn_set_background", "mvn_get_background", "mvn_set_likelihood", "mvn_get_likelihood", "mvn_last_likelihood",
     "mvn_engine_set_noise_model", "mvn_engine_last_likelihood",
@@ -188,6 +191,17 @@ class Binding:
         l.mvn_reflect_counters.argtypes = [C.POINTER(C.c_longlong)]
         l.mvn_reflect_time.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,
                                        C.c_int, C.POINTER(C.c_float)]
+        vg = C.POINTER(ViewGeometry)
+        l.mvn_deconvolve_resampled.argtypes = [C.c_void_p, Workspace, C.POINTER(CallDesc), vg, C.c_int, C.c_int]
+        l.mvn_deconvolve_memory_resampled.argtypes = [Workspace, C.POINTER(CallDesc), vg, C.c_int, C.c_int,
+                                                      C.POINTER(C.c_size_t)]
+        l.mvn_engine_set_view_resampled.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(StackDesc), vg,
+                                                    C.c_void_p, C.POINTER(StackDesc), c_float_p, i3, c_float_p, i3,
+                                                    C.c_void_p]
+        l.mvn_engine_normalize_weights.argtypes = [C.c_void_p]
+        l.mvn_resample_stack.argtypes = [C.c_int, C.c_void_p, C.POINTER(StackDesc), vg, i3, c_float_p, c_float_p]
+        l.mvn_resample_time.argtypes = [C.c_int, C.c_int, vg, i3, C.c_int, C.POINTER(C.c_float)]
+        l.mvn_resample_counters.argtypes = [C.POINTER(C.c_longlong)]
         l.mvn_tv_launch_count.restype = C.c_long
         l.mvn_tv_launch_count.argtypes = []
         l.mvn_engine_compute_delta.argtypes = [C.c_void_p, C.c_double, C.c_float]
@@ -495,6 +509,94 @@ class Binding:
         return self.describe_call(psi, views, weights, kernels1, kernels2, lambda_, min_value, iterations,
                                   int16_is_uint16).run(device)
 
+    # ---- resampled views (mvn_view_geometry) ----------------------------------------------
+    def resample_counters(self):
+        """mvn_resample_counters: (launches of the resample pass, launches of the normalisation) since process start."""
+        out = (C.c_longlong * 2)(0, 0)
+        self.check(self.l.mvn_resample_counters(out))
+        return int(out[0]), int(out[1])
+
+    def resample_stack(self, src, geom, out_shape, device=-1, int16_is_uint16=False):
+        """mvn_resample_stack: the raw stack `src` (numpy array or torch tensor, float32 or uint16, host or device, as
+        deconvolve_described takes them) through `geom` (abi.view_geometry) into (image, unnormalised weights), two
+        dense float32 arrays of `out_shape`."""
+        ptr, desc, shape, dev = describe_stack(src, int16_is_uint16)
+        if shape != tuple(geom.src_dims):
+            raise ValueError("the raw stack has shape %r, its geometry says %r" % (shape, tuple(geom.src_dims)))
+        if _caller_stream([src]) is not None:  # (the utility takes no stream: the stack must be complete)
+            import torch
+            torch.cuda.current_stream(src.device).synchronize()
+        image, weights = np.empty(out_shape, np.float32), np.empty(out_shape, np.float32)
+        self.check(self.l.mvn_resample_stack(int(dev if dev is not None else device), C.c_void_p(ptr), C.byref(desc),
+                                             C.byref(geom), _dims(out_shape), fptr(image), fptr(weights)))
+        return image, weights
+
+    def resample_time(self, geom, out_shape, u16=True, reps=10, device=0):
+        """mvn_resample_time: (ms per resample pass from a resident raw stack of geom.src_dims into volumes of
+        `out_shape`, ms per streaming copy that reads one and writes two such volumes)."""
+        ms = (C.c_float * 2)(0, 0)
+        self.check(self.l.mvn_resample_time(device, int(bool(u16)), C.byref(geom), _dims(out_shape), int(reps), ms))
+        return float(ms[0]), float(ms[1])
+
+    def resample_call(self, psi, raws, geoms, kernels1, kernels2, lambda_, min_value, iterations, weights=None,
+                      int16_is_uint16=False):
+        """The arguments of mvn_deconvolve_resampled as a ResampledCall (`.run(device)` makes the call, `.memory()` asks
+        mvn_deconvolve_memory_resampled): `raws` are the raw stacks (numpy arrays or torch tensors, float32 or uint16),
+        `geoms` their abi.view_geometry; `weights`: None = computed from the geometries and normalised
+        (weights_mode 1), else one stack of psi's shape per view (weights_mode 0)."""
+        n = len(raws)
+        if not (len(geoms) == n and len(kernels1) == n and len(kernels2) == n and (weights is None or len(weights) == n)):
+            raise ValueError("one geometry and two kernels per view")
+        c = ResampledCall()
+        c.binding, c.psi, c.mode = self, psi, 1 if weights is None else 0
+        c.keep = [[np.ascontiguousarray(k, dtype=np.float32) for k in ks] for ks in (kernels1, kernels2)]
+        k1, k2 = c.keep
+        c.psi_ptr, p_desc, shape, p_dev = describe_stack(psi)
+        c.image, c.weights, c.geom = (StackDesc * n)(), (StackDesc * n)(), (ViewGeometry * n)()
+        data = (ViewData * n)()
+        devices = [p_dev]
+        for v in range(n):
+            i_ptr, c.image[v], i_shape, i_dev = describe_stack(raws[v], int16_is_uint16)
+            if i_shape != tuple(geoms[v].src_dims):
+                raise ValueError("view %d: the raw stack has shape %r, its geometry says %r"
+                                 % (v, i_shape, tuple(geoms[v].src_dims)))
+            c.geom[v] = geoms[v]
+            devices.append(i_dev)
+            d = data[v]
+            if weights is not None:
+                w_ptr, c.weights[v], w_shape, w_dev = describe_stack(weights[v])
+                if w_shape != shape:
+                    raise ValueError("view %d: weights have psi's shape %r" % (v, shape))
+                devices.append(w_dev)
+                d.weights_ = C.cast(C.c_void_p(w_ptr), c_float_p)
+            dims = [np.array(s_, dtype=np.int32) for s_ in (shape, k1[v].shape, k2[v].shape, shape)]
+            c.keep.append(dims)
+            d.image_ = C.cast(C.c_void_p(i_ptr), c_float_p)
+            d.kernel1_, d.kernel2_ = fptr(k1[v]), fptr(k2[v])
+            d.image_dims_, d.kernel1_dims_, d.kernel2_dims_, d.weights_dims_ = [iptr(x) for x in dims]
+        c.keep += [data, list(raws), list(weights or [])]
+        c.ws = Workspace()
+        c.ws.data_ = C.cast(data, C.POINTER(ViewData))
+        c.ws.num_views_, c.ws.lambda_, c.ws.minValue_, c.ws.num_iterations_ = (
+            n, float(lambda_), float(min_value), int(iterations))
+        c.desc = CallDesc()
+        c.desc.psi = p_desc
+        c.desc.image = C.cast(c.image, C.POINTER(StackDesc))
+        if weights is not None:
+            c.desc.weights = C.cast(c.weights, C.POINTER(StackDesc))
+        owners = [x for x in devices if x is not None]
+        c.device = owners[0] if owners else 0
+        return c
+
+    def deconvolve_resampled(self, psi, raws, geoms, kernels1, kernels2, lambda_, min_value, iterations, weights=None,
+                             device=None, int16_is_uint16=False):
+        """mvn_deconvolve_resampled: the deconvolution from RAW views - each a stack as the camera delivered it plus an
+        abi.view_geometry (matrix from block voxel to raw index, blend border and range); the library resamples them
+        into psi's frame on the device and, with weights=None, computes and normalises the blend weights there too.
+        Stacks may be what deconvolve_described takes.  psi is updated in place and returned."""
+        return self.resample_call(psi, raws, geoms, kernels1, kernels2, lambda_, min_value, iterations, weights,
+                                  int16_is_uint16).run(device)
+
     def deconvolve_submit(self, psi, holder, device=0):
         """mvn_deconvolve_submit: starts inplace_gpu_deconvolve on `psi` (C-contiguous float32, updated in
         place by the time deconvolve_wait returns) and returns the ticket.  `psi` and `holder` must be
@@ -633,6 +735,26 @@ class DescribedCall:
         return self.psi
 
 
+class ResampledCall:
+    """One prepared mvn_deconvolve_resampled call (Binding.resample_call); keeps what its pointers refer to alive."""
+
+    def run(self, device=None):
+        """makes the call (blocking); psi is updated in place and returned"""
+        self.desc.stream = _caller_stream([self.psi] + self.keep[-2] + self.keep[-1])
+        b = self.binding
+        b.check(b.l.mvn_deconvolve_resampled(C.c_void_p(self.psi_ptr), self.ws, C.byref(self.desc), self.geom,
+                                             self.mode, int(self.device if device is None else device)))
+        return self.psi
+
+    def memory(self, device=0):
+        """mvn_deconvolve_memory_resampled: bytes of device memory the call needs (nothing is allocated)"""
+        out = C.c_size_t(0)
+        b = self.binding
+        b.check(b.l.mvn_deconvolve_memory_resampled(self.ws, C.byref(self.desc), self.geom, self.mode, int(device),
+                                                    C.byref(out)))
+        return out.value
+
+
 class GroupHandle:
     """One volume as dim0 slabs on several devices of this process (``mvn_group_*``; what MVN_DEVICES runs inside
     ``inplace_gpu_deconvolve``), stacks resident between ``load`` and ``get_psi``."""
@@ -735,6 +857,25 @@ class EngineHandle:
         self.b.check(self.b.l.mvn_engine_set_view_described(
             self.h, v, C.c_void_p(i_ptr), C.byref(i_desc), C.c_void_p(w_ptr), C.byref(w_desc), fptr(k[0]),
             _dims(k[0].shape), fptr(k[1]), _dims(k[1].shape), _caller_stream([image, weights])))
+
+    def set_view_resampled(self, v, raw, geom, kernel1, kernel2, weights=None, int16_is_uint16=False):
+        """mvn_engine_set_view_resampled: the raw stack `raw` through `geom` (abi.view_geometry) into view v.
+        weights=None: computed from the geometry, unnormalised - call normalize_weights() after the last view."""
+        k = [np.ascontiguousarray(x, dtype=np.float32) for x in (kernel1, kernel2)]
+        i_ptr, i_desc, i_shape, _ = describe_stack(raw, int16_is_uint16)
+        assert i_shape == tuple(geom.src_dims)
+        w_ptr, w_desc = None, None
+        if weights is not None:
+            weights = self._stack(weights)
+            w_ptr, w_desc, w_shape, _ = describe_stack(weights)
+            assert w_shape == self.shape
+        self.b.check(self.b.l.mvn_engine_set_view_resampled(
+            self.h, v, C.c_void_p(i_ptr), C.byref(i_desc), C.byref(geom), C.c_void_p(w_ptr),
+            C.byref(w_desc) if w_desc is not None else None, fptr(k[0]), _dims(k[0].shape), fptr(k[1]),
+            _dims(k[1].shape), _caller_stream([raw] + ([weights] if weights is not None else []))))
+
+    def normalize_weights(self):
+        self.b.check(self.b.l.mvn_engine_normalize_weights(self.h))
 
     def set_psi(self, psi):
         psi = self._stack(psi)
