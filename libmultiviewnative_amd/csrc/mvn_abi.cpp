@@ -402,6 +402,72 @@ static shape_t to_shape(const int* d) {
   return s;
 }
 
+// ---- what the test and bench utilities of the ABI share ------------------------------------------
+// milliseconds per call of `body`, which enqueues on `s`: one call to warm up, then `reps` calls between two events
+template <typename F>
+static float time_on_stream(be::stream_t s, int reps, F&& body) {
+  const be::Event a = be::Event::timing(), b = be::Event::timing();
+  body();
+  be::event_record(a.get(), s);
+  for (int i = 0; i < reps; ++i) body();
+  be::event_record(b.get(), s);
+  be::event_sync(b.get());
+  return be::event_elapsed_ms(a.get(), b.get()) / (float)reps;
+}
+
+// non-trivial contents for a timed volume (zeros flatter the clock: guide 5.4 rule 25): an LCG's values in [-0.5, 0.5)
+static std::vector<float> lcg_fill(size_t n) {
+  std::vector<float> host(n);
+  unsigned x = 12345u;
+  for (size_t i = 0; i < n; ++i) {
+    x = x * 1664525u + 1013904223u;
+    host[i] = (float)(x >> 8) * (1.0f / 16777216.0f) - 0.5f;
+  }
+  return host;
+}
+
+// the epilogue of a plain convolution: the result is stored, unscaled
+static EpilogueParams store_epilogue() {
+  EpilogueParams e;
+  std::memset(&e, 0, sizeof(e));
+  e.mode = MVN_EPI_STORE;
+  e.scale = 1.f;
+  return e;
+}
+
+// On the device a spectrum is kept in POSITION order along every axis (digit-reversed, exactly as
+// the decimation-in-frequency passes leave it; the PSF spectra are stored the same way, so the
+// RL loop never permutes anything).  The host-buffer utilities translate to / from the
+// natural FFTW/cuFFT bin order with this pair: bin (k0,k1,k2) lives at (inv0[k0], inv1[k1], inv2[k2]).
+// f(index in the main spectrum, natural index) for every bin, nyq(row of the Nyquist plane, natural index) (even d2)
+template <typename F, typename N>
+static void for_each_bin(const Plan3D& plan, F&& f, N&& nyq) {
+  const Layout& L = plan.L;
+  const std::vector<int>&i0 = plan.ax0.host.inv, &i1 = plan.ax1.host.inv;
+  const std::vector<int>& i2 = plan.ax2.host.inv;  // length L.h; used for even d2 only
+  const size_t nc = (size_t)(L.d2 / 2 + 1);
+  for (int k0 = 0; k0 < L.d0; ++k0)
+    for (int k1 = 0; k1 < L.d1; ++k1) {
+      const size_t row = (size_t)i0[k0] * L.d1 + (size_t)i1[k1], nat = ((size_t)k0 * L.d1 + k1) * nc;
+      for (int k2 = 0; k2 < L.C; ++k2) f(row * L.C + (L.even ? i2[k2] : k2), nat + (size_t)k2);
+      if (L.even) nyq(row, nat + (size_t)L.C);
+    }
+}
+
+static void position_to_natural(const Plan3D& plan, const std::vector<cfloat>& main_h,
+                                const std::vector<cfloat>& nyq_h, cfloat* out) {
+  for_each_bin(
+      plan, [&](size_t pos, size_t nat) { out[nat] = main_h[pos]; },
+      [&](size_t row, size_t nat) { out[nat] = nyq_h[row]; });
+}
+
+static void natural_to_position(const Plan3D& plan, const cfloat* in, std::vector<cfloat>& main_h,
+                                std::vector<cfloat>& nyq_h) {
+  for_each_bin(
+      plan, [&](size_t pos, size_t nat) { main_h[pos] = in[nat]; },
+      [&](size_t row, size_t nat) { nyq_h[row] = in[nat]; });
+}
+
 extern "C" {
 
 const char* mvn_last_error(void) { return g_last_error.c_str(); }
@@ -1183,26 +1249,14 @@ int mvn_tv_factor(int device, const int dims[3], const float* psi, double lambda
     const Layout L(dims[0], dims[1], dims[2]);
     const size_t bytes = L.real_floats() * sizeof(float), width = (size_t)L.d2 * sizeof(float),
                  pitch = (size_t)L.RP * sizeof(float);
-    float *du = nullptr, *dt = nullptr;
-    be::stream_t s = nullptr;
-    try {
-      du = (float*)be::dmalloc(bytes);
-      dt = (float*)be::dmalloc(bytes);
-      s = be::stream_create();
-      be::dzero(du, bytes, s);
-      be::h2d_2d(du, pitch, psi, width, width, (size_t)L.rows, s);
-      be::launch_tv(tv_params(L, du, dt, lambda, epsilon), s);
-      be::d2h_2d(t, width, dt, pitch, width, (size_t)L.rows, s);
-      be::stream_sync(s);
-    } catch (...) {
-      if (s) be::stream_destroy(s);
-      be::dfree(du);
-      be::dfree(dt);
-      throw;
-    }
-    be::stream_destroy(s);
-    be::dfree(du);
-    be::dfree(dt);
+    const be::DeviceBuffer<float> du(bytes), dt(bytes);
+    const be::Stream st = be::Stream::create();
+    const be::stream_t s = st.get();
+    be::dzero(du.get(), bytes, s);
+    be::h2d_2d(du.get(), pitch, psi, width, width, (size_t)L.rows, s);
+    be::launch_tv(tv_params(L, du.get(), dt.get(), lambda, epsilon), s);
+    be::d2h_2d(t, width, dt.get(), pitch, width, (size_t)L.rows, s);
+    be::stream_sync(s);
   });
 }
 
@@ -1217,46 +1271,18 @@ int mvn_tv_time(int device, const int dims[3], int reps, float* ms) {
     be::set_device(dev);
     const Layout L(dims[0], dims[1], dims[2]);
     const size_t bytes = L.real_floats() * sizeof(float);
-    float *du = nullptr, *dt = nullptr;
-    be::stream_t s = nullptr;
-    be::event_t a = nullptr, b = nullptr;
-    try {
-      du = (float*)be::dmalloc(bytes);
-      dt = (float*)be::dmalloc(bytes);
-      s = be::stream_create();
-      a = be::event_create();
-      b = be::event_create();
-      // a ramp with a ripple: finite gradients everywhere
-      std::vector<float> h(L.real_floats());
-      for (size_t i = 0; i < h.size(); ++i) h[i] = 1.f + 0.001f * (float)(i % 977) + 0.01f * (float)(i % 13);
-      be::h2d(du, h.data(), bytes, s);
-      const TvParams p = tv_params(L, du, dt, 0.005, 0.01);
-      const long plane = (long)L.d1 * L.RP;
-      for (int kind = 0; kind < 2; ++kind) {
-        for (int i = -1; i < reps; ++i) {  // (one launch to warm up)
-          if (i == 0) be::event_record(a, s);
-          if (kind == 0)
-            be::launch_tv(p, s);
-          else
-            be::launch_copy3d(dt, L.RP, plane, du, L.RP, plane, L.d2, L.d1, L.d0, s);
-        }
-        be::event_record(b, s);
-        be::event_sync(b);
-        ms[kind] = be::event_elapsed_ms(a, b) / (float)reps;
-      }
-    } catch (...) {
-      if (a) be::event_destroy(a);
-      if (b) be::event_destroy(b);
-      if (s) be::stream_destroy(s);
-      be::dfree(du);
-      be::dfree(dt);
-      throw;
-    }
-    be::event_destroy(a);
-    be::event_destroy(b);
-    be::stream_destroy(s);
-    be::dfree(du);
-    be::dfree(dt);
+    const be::DeviceBuffer<float> du(bytes), dt(bytes);
+    const be::Stream st = be::Stream::create();
+    const be::stream_t s = st.get();
+    // a ramp with a ripple: finite gradients everywhere
+    std::vector<float> h(L.real_floats());
+    for (size_t i = 0; i < h.size(); ++i) h[i] = 1.f + 0.001f * (float)(i % 977) + 0.01f * (float)(i % 13);
+    be::h2d(du.get(), h.data(), bytes, s);
+    const TvParams p = tv_params(L, du.get(), dt.get(), 0.005, 0.01);
+    const long plane = (long)L.d1 * L.RP;
+    ms[0] = time_on_stream(s, reps, [&] { be::launch_tv(p, s); });
+    ms[1] = time_on_stream(
+        s, reps, [&] { be::launch_copy3d(dt.get(), L.RP, plane, du.get(), L.RP, plane, L.d2, L.d1, L.d0, s); });
   });
 }
 
@@ -1283,50 +1309,22 @@ int mvn_reflect_time(int device, const int dims[3], const int ext[3], const int 
     const Layout L(ext[0], ext[1], ext[2]);
     const size_t esz = u16 ? sizeof(uint16_t) : sizeof(float);
     const size_t bytes = L.real_floats() * esz;
-    float *du = nullptr, *dt = nullptr;
-    be::stream_t s = nullptr;
-    be::event_t a = nullptr, b = nullptr;
-    try {
-      du = (float*)be::dmalloc(bytes);
-      dt = (float*)be::dmalloc(bytes);
-      s = be::stream_create();
-      a = be::event_create();
-      b = be::event_create();
-      std::vector<unsigned char> h(bytes);
-      for (size_t i = 0; i < h.size(); ++i) h[i] = (unsigned char)(i % 251);
-      be::h2d(du, h.data(), bytes, s);
-      ReflectParams p;
-      p.vol = du, p.RP = L.RP, p.D0 = L.d0, p.D1 = L.d1, p.D2 = L.d2;
-      p.n0 = dims[0], p.n1 = dims[1], p.n2 = dims[2];
-      p.o0 = off[0], p.o1 = off[1], p.o2 = off[2];
-      p.axis = 2;
-      // the copy moves the volume's bytes as rows of floats (a uint16 volume: RP / 2 of them, RP is even)
-      const long row = u16 ? L.RP / 2 : L.RP, plane = (long)L.d1 * row;
-      for (int kind = 0; kind < 2; ++kind) {
-        for (int i = -1; i < reps; ++i) {  // (one round to warm up)
-          if (i == 0) be::event_record(a, s);
-          if (kind == 0)
-            be::launch_reflect_fill(p, u16 != 0, s);
-          else
-            be::launch_copy3d(dt, row, plane, du, row, plane, (int)row, L.d1, L.d0, s);
-        }
-        be::event_record(b, s);
-        be::event_sync(b);
-        ms[kind] = be::event_elapsed_ms(a, b) / (float)reps;
-      }
-    } catch (...) {
-      if (a) be::event_destroy(a);
-      if (b) be::event_destroy(b);
-      if (s) be::stream_destroy(s);
-      be::dfree(du);
-      be::dfree(dt);
-      throw;
-    }
-    be::event_destroy(a);
-    be::event_destroy(b);
-    be::stream_destroy(s);
-    be::dfree(du);
-    be::dfree(dt);
+    const be::DeviceBuffer<float> du(bytes), dt(bytes);
+    const be::Stream st = be::Stream::create();
+    const be::stream_t s = st.get();
+    std::vector<unsigned char> h(bytes);
+    for (size_t i = 0; i < h.size(); ++i) h[i] = (unsigned char)(i % 251);
+    be::h2d(du.get(), h.data(), bytes, s);
+    ReflectParams p;
+    p.vol = du.get(), p.RP = L.RP, p.D0 = L.d0, p.D1 = L.d1, p.D2 = L.d2;
+    p.n0 = dims[0], p.n1 = dims[1], p.n2 = dims[2];
+    p.o0 = off[0], p.o1 = off[1], p.o2 = off[2];
+    p.axis = 2;
+    // the copy moves the volume's bytes as rows of floats (a uint16 volume: RP / 2 of them, RP is even)
+    const long row = u16 ? L.RP / 2 : L.RP, plane = (long)L.d1 * row;
+    ms[0] = time_on_stream(s, reps, [&] { be::launch_reflect_fill(p, u16 != 0, s); });
+    ms[1] = time_on_stream(
+        s, reps, [&] { be::launch_copy3d(dt.get(), row, plane, du.get(), row, plane, (int)row, L.d1, L.d0, s); });
   });
 }
 
@@ -1364,25 +1362,13 @@ int mvn_resample_stack(int device, const void* src, const mvn_stack_desc* src_de
     const Layout L(out_dims[0], out_dims[1], out_dims[2]);
     const size_t bytes = L.real_floats() * sizeof(float), width = (size_t)L.d2 * sizeof(float),
                  pitch = (size_t)L.RP * sizeof(float);
-    float *di = nullptr, *dw = nullptr;
-    be::stream_t s = nullptr;
-    try {
-      di = (float*)be::dmalloc(bytes);
-      dw = (float*)be::dmalloc(bytes);
-      s = be::stream_create();
-      Engine::resample_raw(resample_alone(L, di, dw), st, s);
-      if (image_out) be::d2h_2d(image_out, width, di, pitch, width, (size_t)L.rows, s);
-      if (weights_out) be::d2h_2d(weights_out, width, dw, pitch, width, (size_t)L.rows, s);
-      be::stream_sync(s);
-    } catch (...) {
-      if (s) be::stream_destroy(s);
-      be::dfree(di);
-      be::dfree(dw);
-      throw;
-    }
-    be::stream_destroy(s);
-    be::dfree(di);
-    be::dfree(dw);
+    const be::DeviceBuffer<float> di(bytes), dw(bytes);
+    const be::Stream stream = be::Stream::create();
+    const be::stream_t s = stream.get();
+    Engine::resample_raw(resample_alone(L, di.get(), dw.get()), st, s);
+    if (image_out) be::d2h_2d(image_out, width, di.get(), pitch, width, (size_t)L.rows, s);
+    if (weights_out) be::d2h_2d(weights_out, width, dw.get(), pitch, width, (size_t)L.rows, s);
+    be::stream_sync(s);
   });
 }
 
@@ -1402,57 +1388,27 @@ int mvn_resample_time(int device, int u16, const mvn_view_geometry* geom, const 
     const size_t bytes = L.real_floats() * sizeof(float);
     const size_t esz = u16 ? sizeof(uint16_t) : sizeof(float);
     const size_t raw = (size_t)g.m[0] * (size_t)g.m[1] * (size_t)g.m[2];
-    float *di = nullptr, *dw = nullptr;
-    void* dr = nullptr;
-    be::stream_t s = nullptr;
-    be::event_t a = nullptr, b = nullptr;
-    try {
-      di = (float*)be::dmalloc(bytes);
-      dw = (float*)be::dmalloc(bytes);
-      dr = be::dmalloc(raw * esz);
-      s = be::stream_create();
-      a = be::event_create();
-      b = be::event_create();
-      std::vector<unsigned char> h(raw * esz);
-      if (u16)
-        for (size_t i = 0; i < raw; ++i) ((uint16_t*)h.data())[i] = (uint16_t)(100u + i % 4001u);
-      else
-        for (size_t i = 0; i < raw; ++i) ((float*)h.data())[i] = 100.f + (float)(i % 4001u);
-      be::h2d(dr, h.data(), h.size(), s);
-      be::dzero(di, bytes, s);
-      be::stream_sync(s);
-      ResampleParams p = resample_alone(L, di, dw);
-      p.src = dr, p.s0 = (long long)g.m[1] * g.m[2], p.s1 = g.m[2], p.s2 = 1;
-      p.g = g;
-      for (int kind = 0; kind < 2; ++kind) {
-        for (int i = -1; i < reps; ++i) {  // (one round to warm up)
-          if (i == 0) be::event_record(a, s);
-          if (kind == 0) {
-            be::launch_resample(p, u16 != 0, s);
-          } else {
-            be::launch_copy3d(dw, L.RP, (long)L.d1 * L.RP, di, L.RP, (long)L.d1 * L.RP, (int)L.RP, L.d1, L.d0, s);
-            be::dzero(di, bytes, s);
-          }
-        }
-        be::event_record(b, s);
-        be::event_sync(b);
-        ms[kind] = be::event_elapsed_ms(a, b) / (float)reps;
-      }
-    } catch (...) {
-      if (a) be::event_destroy(a);
-      if (b) be::event_destroy(b);
-      if (s) be::stream_destroy(s);
-      be::dfree(di);
-      be::dfree(dw);
-      be::dfree(dr);
-      throw;
-    }
-    be::event_destroy(a);
-    be::event_destroy(b);
-    be::stream_destroy(s);
-    be::dfree(di);
-    be::dfree(dw);
-    be::dfree(dr);
+    const be::DeviceBuffer<float> di(bytes), dw(bytes);
+    const be::DeviceBuffer<> dr(raw * esz);
+    const be::Stream st = be::Stream::create();
+    const be::stream_t s = st.get();
+    std::vector<unsigned char> h(raw * esz);
+    if (u16)
+      for (size_t i = 0; i < raw; ++i) ((uint16_t*)h.data())[i] = (uint16_t)(100u + i % 4001u);
+    else
+      for (size_t i = 0; i < raw; ++i) ((float*)h.data())[i] = 100.f + (float)(i % 4001u);
+    be::h2d(dr.get(), h.data(), h.size(), s);
+    be::dzero(di.get(), bytes, s);
+    be::stream_sync(s);
+    ResampleParams p = resample_alone(L, di.get(), dw.get());
+    p.src = dr.get(), p.s0 = (long long)g.m[1] * g.m[2], p.s1 = g.m[2], p.s2 = 1;
+    p.g = g;
+    const long plane = (long)L.d1 * L.RP;
+    ms[0] = time_on_stream(s, reps, [&] { be::launch_resample(p, u16 != 0, s); });
+    ms[1] = time_on_stream(s, reps, [&] {
+      be::launch_copy3d(dw.get(), L.RP, plane, di.get(), L.RP, plane, (int)L.RP, L.d1, L.d0, s);
+      be::dzero(di.get(), bytes, s);
+    });
   });
 }
 
@@ -1592,49 +1548,27 @@ static void convolve_host(float* im, const int* imDim, const float* kernel, cons
   be::set_device(dev);
   std::shared_ptr<Plan3D> plan = PlanStore::get().add(dev, to_shape(imDim));
   const Layout& L = plan->L;
-  be::stream_t s = be::stream_create();
-  float* vol = nullptr;
-  float* spec = nullptr;
-  cfloat *nyq = nullptr, *snyq = nullptr;
-  float* dk = nullptr;
-  auto cleanup = [&] {
-    be::dfree(vol);
-    be::dfree(spec);
-    be::dfree(nyq);
-    be::dfree(snyq);
-    be::dfree(dk);
-    be::stream_destroy(s);
-  };
-  try {
-    vol = (float*)be::dmalloc(plan->main_bytes());
-    spec = (float*)be::dmalloc(plan->main_bytes());
-    if (plan->nyq_bytes()) {
-      nyq = (cfloat*)be::dmalloc(plan->nyq_bytes());
-      snyq = (cfloat*)be::dmalloc(plan->nyq_bytes());
-    }
-    const size_t kb = sizeof(float) * (size_t)kernelDim[0] * kernelDim[1] * kernelDim[2];
-    dk = (float*)be::dmalloc(kb);
-    be::h2d(dk, kernel, kb, s);
-    be::dzero(vol, plan->main_bytes(), s);
-    be::h2d_2d(vol, (size_t)L.RP * 4, im, (size_t)L.d2 * 4, (size_t)L.d2 * 4, L.rows, s);
-    const float scale = (float)(1.0 / (double)L.logical());
-    plan->psf_spectrum(dk, kernelDim, scale, spec, snyq, s);
-    EpilogueParams e;
-    std::memset(&e, 0, sizeof(e));
-    e.mode = MVN_EPI_STORE;
-    e.scale = 1.f;
-    plan->convolve(vol, (cfloat*)vol, nyq, (const cfloat*)spec, snyq, vol, e, s);
-    be::d2h_2d(im, (size_t)L.d2 * 4, vol, (size_t)L.RP * 4, (size_t)L.d2 * 4, L.rows, s);
-    be::stream_sync(s);
-  } catch (...) {
-    try {
-      be::stream_sync(s);
-    } catch (...) {
-    }
-    cleanup();
-    throw;
+  const size_t kb = sizeof(float) * (size_t)kernelDim[0] * kernelDim[1] * kernelDim[2];
+  be::DeviceBuffer<float> vol, spec, dk;
+  be::DeviceBuffer<cfloat> nyq, snyq;
+  const be::Stream st = be::Stream::create();
+  const be::stream_t s = st.get();
+  vol = be::DeviceBuffer<float>(plan->main_bytes());
+  spec = be::DeviceBuffer<float>(plan->main_bytes());
+  if (plan->nyq_bytes()) {
+    nyq = be::DeviceBuffer<cfloat>(plan->nyq_bytes());
+    snyq = be::DeviceBuffer<cfloat>(plan->nyq_bytes());
   }
-  cleanup();
+  dk = be::DeviceBuffer<float>(kb);
+  be::h2d(dk.get(), kernel, kb, s);
+  be::dzero(vol.get(), plan->main_bytes(), s);
+  be::h2d_2d(vol.get(), (size_t)L.RP * 4, im, (size_t)L.d2 * 4, (size_t)L.d2 * 4, L.rows, s);
+  const float scale = (float)(1.0 / (double)L.logical());
+  plan->psf_spectrum(dk.get(), kernelDim, scale, spec.get(), snyq.get(), s);
+  plan->convolve(vol.get(), (cfloat*)vol.get(), nyq.get(), (const cfloat*)spec.get(), snyq.get(), vol.get(),
+                 store_epilogue(), s);
+  be::d2h_2d(im, (size_t)L.d2 * 4, vol.get(), (size_t)L.RP * 4, (size_t)L.d2 * 4, L.rows, s);
+  be::stream_sync(s);
 }
 
 void inplace_gpu_convolution(imageType* im, int* imDim, imageType* kernel, int* kernelDim,
@@ -1652,48 +1586,27 @@ static void core_convolve_on_device(float* d_im, const int* imDim, const float* 
                                     const int* kernelDim, int dev) {
   std::shared_ptr<Plan3D> plan = PlanStore::get().add(dev, to_shape(imDim));
   const Layout& L = plan->L;
-  be::stream_t s = be::stream_create();
-  float *vol = nullptr, *spec = nullptr;
-  cfloat *nyq = nullptr, *snyq = nullptr;
-  auto cleanup = [&] {
-    if (vol != d_im) be::dfree(vol);
-    be::dfree(spec);
-    be::dfree(nyq);
-    be::dfree(snyq);
-    be::stream_destroy(s);
-  };
-  try {
-    spec = (float*)be::dmalloc(plan->main_bytes());
-    if (plan->nyq_bytes()) {
-      nyq = (cfloat*)be::dmalloc(plan->nyq_bytes());
-      snyq = (cfloat*)be::dmalloc(plan->nyq_bytes());
-    }
-    if (L.RP == L.d2) {
-      vol = d_im;  // even d2: the caller's dense volume already is the engine layout
-    } else {
-      vol = (float*)be::dmalloc(plan->main_bytes());
-      be::dzero(vol, plan->main_bytes(), s);
-      be::d2d_2d(vol, (size_t)L.RP * 4, d_im, (size_t)L.d2 * 4, (size_t)L.d2 * 4, L.rows, s);
-    }
-    const float scale = (float)(1.0 / (double)L.logical());
-    plan->psf_spectrum(d_kernel, kernelDim, scale, spec, snyq, s);
-    EpilogueParams e;
-    std::memset(&e, 0, sizeof(e));
-    e.mode = MVN_EPI_STORE;
-    e.scale = 1.f;
-    plan->convolve(vol, (cfloat*)vol, nyq, (const cfloat*)spec, snyq, vol, e, s);
-    if (vol != d_im)
-      be::d2d_2d(d_im, (size_t)L.d2 * 4, vol, (size_t)L.RP * 4, (size_t)L.d2 * 4, L.rows, s);
-    be::stream_sync(s);
-  } catch (...) {
-    try {
-      be::stream_sync(s);
-    } catch (...) {
-    }
-    cleanup();
-    throw;
+  be::DeviceBuffer<float> spec, padded;  // padded: stays empty when the caller's volume is borrowed
+  be::DeviceBuffer<cfloat> nyq, snyq;
+  const be::Stream st = be::Stream::create();
+  const be::stream_t s = st.get();
+  spec = be::DeviceBuffer<float>(plan->main_bytes());
+  if (plan->nyq_bytes()) {
+    nyq = be::DeviceBuffer<cfloat>(plan->nyq_bytes());
+    snyq = be::DeviceBuffer<cfloat>(plan->nyq_bytes());
   }
-  cleanup();
+  float* vol = d_im;  // even d2: the caller's dense volume already is the engine layout
+  if (L.RP != L.d2) {
+    padded = be::DeviceBuffer<float>(plan->main_bytes());
+    vol = padded.get();
+    be::dzero(vol, plan->main_bytes(), s);
+    be::d2d_2d(vol, (size_t)L.RP * 4, d_im, (size_t)L.d2 * 4, (size_t)L.d2 * 4, L.rows, s);
+  }
+  const float scale = (float)(1.0 / (double)L.logical());
+  plan->psf_spectrum(d_kernel, kernelDim, scale, spec.get(), snyq.get(), s);
+  plan->convolve(vol, (cfloat*)vol, nyq.get(), (const cfloat*)spec.get(), snyq.get(), vol, store_epilogue(), s);
+  if (vol != d_im) be::d2d_2d(d_im, (size_t)L.d2 * 4, vol, (size_t)L.RP * 4, (size_t)L.d2 * 4, L.rows, s);
+  be::stream_sync(s);
 }
 
 void convolution3DfftCUDAInPlace_core(imageType* d_im, int* imDim, imageType* d_kernel,
@@ -1723,45 +1636,29 @@ static void iterate_fft_legacy(const char* what, const float* input, const float
     const int dev = pick_device(device);
     std::lock_guard<std::mutex> lk(device_mutex(dev));
     be::set_device(dev);
-    float *d_image = nullptr, *d_initial = nullptr, *d_weights = nullptr, *d_kernel = nullptr;
-    auto cleanup = [&] {
-      be::dfree(d_image);
-      be::dfree(d_initial);
-      be::dfree(d_weights);
-      be::dfree(d_kernel);
-    };
-    try {
-      d_image = (float*)be::dmalloc(n * 4);
-      d_initial = (float*)be::dmalloc(n * 4);
-      d_weights = (float*)be::dmalloc(n * 4);
-      d_kernel = (float*)be::dmalloc(nk * 4);
-      std::vector<float> ones(n, 1.f), tenth(nk, .1f);
-      be::h2d(d_weights, ones.data(), n * 4, nullptr);
-      be::h2d(d_initial, input, n * 4, nullptr);
-      be::h2d(d_image, input, n * 4, nullptr);
-      be::h2d(d_kernel, kernel, nk * 4, nullptr);
-      be::stream_sync(nullptr);
-      int idims[3] = {input_dims[0], input_dims[1], input_dims[2]};
-      int kdims[3] = {kernel_dims[0], kernel_dims[1], kernel_dims[2]};
-      core_convolve_on_device(d_image, idims, d_kernel, kdims, dev);  // psi (*) kernel1
-      be::launch_divide(d_initial, d_image, n, nullptr);              // view / blurred
-      be::h2d(d_kernel, tenth.data(), nk * 4, nullptr);
-      be::stream_sync(nullptr);
-      core_convolve_on_device(d_image, idims, d_kernel, kdims, dev);  // (*) kernel2 -> integral
-      if (tikhonov)
-        be::launch_update_legacy_tikhonov(d_initial, d_image, d_weights, n, (float)lambda,
-                                          min_value, nullptr);
-      else
-        be::launch_update(d_initial, d_image, d_weights, n, 0., min_value, nullptr);
-      std::vector<float> tmp(n);
-      be::d2h(tmp.data(), d_initial, n * 4, nullptr);
-      be::stream_sync(nullptr);
-      std::memcpy(output, tmp.data(), n * 4);
-    } catch (...) {
-      cleanup();
-      throw;
-    }
-    cleanup();
+    const be::DeviceBuffer<float> image(n * 4), initial(n * 4), weights(n * 4), dkernel(nk * 4);
+    float *d_image = image.get(), *d_initial = initial.get(), *d_weights = weights.get(), *d_kernel = dkernel.get();
+    std::vector<float> ones(n, 1.f), tenth(nk, .1f);
+    be::h2d(d_weights, ones.data(), n * 4, nullptr);
+    be::h2d(d_initial, input, n * 4, nullptr);
+    be::h2d(d_image, input, n * 4, nullptr);
+    be::h2d(d_kernel, kernel, nk * 4, nullptr);
+    be::stream_sync(nullptr);
+    int idims[3] = {input_dims[0], input_dims[1], input_dims[2]};
+    int kdims[3] = {kernel_dims[0], kernel_dims[1], kernel_dims[2]};
+    core_convolve_on_device(d_image, idims, d_kernel, kdims, dev);  // psi (*) kernel1
+    be::launch_divide(d_initial, d_image, n, nullptr);              // view / blurred
+    be::h2d(d_kernel, tenth.data(), nk * 4, nullptr);
+    be::stream_sync(nullptr);
+    core_convolve_on_device(d_image, idims, d_kernel, kdims, dev);  // (*) kernel2 -> integral
+    if (tikhonov)
+      be::launch_update_legacy_tikhonov(d_initial, d_image, d_weights, n, (float)lambda, min_value, nullptr);
+    else
+      be::launch_update(d_initial, d_image, d_weights, n, 0., min_value, nullptr);
+    std::vector<float> tmp(n);
+    be::d2h(tmp.data(), d_initial, n * 4, nullptr);
+    be::stream_sync(nullptr);
+    std::memcpy(output, tmp.data(), n * 4);
   });
 }
 
@@ -1788,24 +1685,14 @@ void compute_quotient(imageType* _input, imageType* _output, size_t _size, int _
     std::lock_guard<std::mutex> lk(device_mutex(dev));
     be::set_device(dev);
     const size_t bytes = _size * sizeof(float);
-    float* d_in = (float*)be::dmalloc(bytes);
-    float* d_out = nullptr;
-    try {
-      d_out = (float*)be::dmalloc(bytes);
-      be::h2d(d_in, _input, bytes, nullptr);
-      be::h2d(d_out, _output, bytes, nullptr);
-      be::launch_divide(d_in, d_out, _size, nullptr);
-      std::vector<float> tmp(_size);
-      be::d2h(tmp.data(), d_out, bytes, nullptr);
-      be::stream_sync(nullptr);
-      std::memcpy(_output, tmp.data(), bytes);
-    } catch (...) {
-      be::dfree(d_in);
-      be::dfree(d_out);
-      throw;
-    }
-    be::dfree(d_in);
-    be::dfree(d_out);
+    const be::DeviceBuffer<float> d_in(bytes), d_out(bytes);
+    be::h2d(d_in.get(), _input, bytes, nullptr);
+    be::h2d(d_out.get(), _output, bytes, nullptr);
+    be::launch_divide(d_in.get(), d_out.get(), _size, nullptr);
+    std::vector<float> tmp(_size);
+    be::d2h(tmp.data(), d_out.get(), bytes, nullptr);
+    be::stream_sync(nullptr);
+    std::memcpy(_output, tmp.data(), bytes);
   });
 }
 
@@ -1818,29 +1705,15 @@ void compute_final_values(imageType* _image, imageType* _integral, imageType* _w
     std::lock_guard<std::mutex> lk(device_mutex(dev));
     be::set_device(dev);
     const size_t bytes = _size * sizeof(float);
-    float *d_psi = nullptr, *d_int = nullptr, *d_w = nullptr;
-    auto cleanup = [&] {
-      be::dfree(d_psi);
-      be::dfree(d_int);
-      be::dfree(d_w);
-    };
-    try {
-      d_psi = (float*)be::dmalloc(bytes);
-      d_int = (float*)be::dmalloc(bytes);
-      d_w = (float*)be::dmalloc(bytes);
-      be::h2d(d_psi, _image, bytes, nullptr);
-      be::h2d(d_int, _integral, bytes, nullptr);
-      be::h2d(d_w, _weight, bytes, nullptr);
-      be::launch_update(d_psi, d_int, d_w, _size, _lambda, _minValue, nullptr);
-      std::vector<float> tmp(_size);
-      be::d2h(tmp.data(), d_psi, bytes, nullptr);
-      be::stream_sync(nullptr);
-      std::memcpy(_image, tmp.data(), bytes);
-    } catch (...) {
-      cleanup();
-      throw;
-    }
-    cleanup();
+    const be::DeviceBuffer<float> d_psi(bytes), d_int(bytes), d_w(bytes);
+    be::h2d(d_psi.get(), _image, bytes, nullptr);
+    be::h2d(d_int.get(), _integral, bytes, nullptr);
+    be::h2d(d_w.get(), _weight, bytes, nullptr);
+    be::launch_update(d_psi.get(), d_int.get(), d_w.get(), _size, _lambda, _minValue, nullptr);
+    std::vector<float> tmp(_size);
+    be::d2h(tmp.data(), d_psi.get(), bytes, nullptr);
+    be::stream_sync(nullptr);
+    std::memcpy(_image, tmp.data(), bytes);
   });
 }
 
@@ -1980,61 +1853,52 @@ int mvn_plan_describe(int device, const int dims[3], int out[12]) {
 // ---------------------------------------------------------------------------------------------
 // whole transforms on host buffers
 // ---------------------------------------------------------------------------------------------
+// `batch` zeroed volumes of one shape with their Nyquist planes (even d2), their cached plan and a stream
 struct FftScratch {
   std::shared_ptr<Plan3D> plan;
+  std::vector<be::DeviceBuffer<float>> vol;
+  std::vector<be::DeviceBuffer<cfloat>> nyq;
+  be::Stream stream;  // (behind the buffers: drained and destroyed before they are freed)
   be::stream_t s = nullptr;
-  float* vol = nullptr;
-  cfloat* nyq = nullptr;
-  FftScratch(int dev, const int* dims) {
+  FftScratch(int dev, const int* dims, int batch = 1) {
     be::set_device(dev);
     plan = PlanStore::get().add(dev, to_shape(dims));
-    s = be::stream_create();
-    vol = (float*)be::dmalloc(plan->main_bytes());
-    be::dzero(vol, plan->main_bytes(), s);
-    if (plan->nyq_bytes()) {
-      nyq = (cfloat*)be::dmalloc(plan->nyq_bytes());
-      be::dzero(nyq, plan->nyq_bytes(), s);
+    stream = be::Stream::create();
+    s = stream.get();
+    for (int b = 0; b < batch; ++b) {
+      vol.emplace_back(plan->main_bytes());
+      be::dzero(v(b), plan->main_bytes(), s);
+      nyq.emplace_back();
+      if (plan->nyq_bytes()) {
+        nyq.back() = be::DeviceBuffer<cfloat>(plan->nyq_bytes());
+        be::dzero(n(b), plan->nyq_bytes(), s);
+      }
     }
   }
-  ~FftScratch() {
-    try {
-      be::stream_sync(s);
-    } catch (...) {
-    }
-    be::dfree(vol);
-    be::dfree(nyq);
-    be::stream_destroy(s);
+  float* v(int b = 0) const { return vol[(size_t)b].get(); }
+  cfloat* n(int b = 0) const { return nyq[(size_t)b].get(); }
+  // direction 0: forward; otherwise backward, scaled to give the input back
+  void transform(int b, int direction, Profiler* prof = nullptr) const {
+    if (direction == 0)
+      plan->forward(v(b), n(b), s, prof);
+    else
+      plan->backward(v(b), n(b), 1.0f / (float)plan->L.logical(), s, prof);
   }
 };
 
-// On the device a spectrum is kept in POSITION order along every axis (digit-reversed, exactly as
-// the decimation-in-frequency passes leave it; the PSF spectra are stored the same way, so the
-// RL loop never permutes anything).  These two host-buffer utilities translate to / from the
-// natural FFTW/cuFFT bin order: bin (k0,k1,k2) lives at (inv0[k0], inv1[k1], inv2[k2]).
 int mvn_fft3_r2c(int device, const int dims[3], const float* real, float* spec) {
   return guarded("mvn_fft3_r2c", [&] {
     const int dev = pick_device(device);
     std::lock_guard<std::mutex> lk(device_mutex(dev));
     FftScratch f(dev, dims);
     const Layout& L = f.plan->L;
-    be::h2d_2d(f.vol, (size_t)L.RP * 4, real, (size_t)L.d2 * 4, (size_t)L.d2 * 4, L.rows, f.s);
-    f.plan->forward(f.vol, f.nyq, f.s);
-    const int nc = L.d2 / 2 + 1;
+    be::h2d_2d(f.v(), (size_t)L.RP * 4, real, (size_t)L.d2 * 4, (size_t)L.d2 * 4, L.rows, f.s);
+    f.transform(0, 0);
     std::vector<cfloat> main_h(L.rows * (size_t)L.C), nyq_h(L.nyq_cplx());
-    be::d2h(main_h.data(), f.vol, main_h.size() * sizeof(cfloat), f.s);
-    if (L.even) be::d2h(nyq_h.data(), f.nyq, nyq_h.size() * sizeof(cfloat), f.s);
+    be::d2h(main_h.data(), f.v(), main_h.size() * sizeof(cfloat), f.s);
+    if (L.even) be::d2h(nyq_h.data(), f.n(), nyq_h.size() * sizeof(cfloat), f.s);
     be::stream_sync(f.s);
-    const std::vector<int>& i0 = f.plan->ax0.host.inv;
-    const std::vector<int>& i1 = f.plan->ax1.host.inv;
-    const std::vector<int>& i2 = f.plan->ax2.host.inv;  // length L.h; used for even d2 only
-    cfloat* out = reinterpret_cast<cfloat*>(spec);
-    for (int k0 = 0; k0 < L.d0; ++k0)
-      for (int k1 = 0; k1 < L.d1; ++k1) {
-        const size_t srow = (size_t)i0[k0] * L.d1 + (size_t)i1[k1];
-        cfloat* o = out + ((size_t)k0 * L.d1 + k1) * (size_t)nc;
-        for (int k2 = 0; k2 < L.C; ++k2) o[k2] = main_h[srow * L.C + (L.even ? i2[k2] : k2)];
-        if (L.even) o[L.C] = nyq_h[srow];
-      }
+    position_to_natural(*f.plan, main_h, nyq_h, reinterpret_cast<cfloat*>(spec));
   });
 }
 
@@ -2044,23 +1908,12 @@ int mvn_fft3_c2r(int device, const int dims[3], const float* spec, float* real) 
     std::lock_guard<std::mutex> lk(device_mutex(dev));
     FftScratch f(dev, dims);
     const Layout& L = f.plan->L;
-    const int nc = L.d2 / 2 + 1;
     std::vector<cfloat> main_h(L.rows * (size_t)L.C), nyq_h(L.nyq_cplx());
-    const std::vector<int>& i0 = f.plan->ax0.host.inv;
-    const std::vector<int>& i1 = f.plan->ax1.host.inv;
-    const std::vector<int>& i2 = f.plan->ax2.host.inv;
-    const cfloat* in = reinterpret_cast<const cfloat*>(spec);
-    for (int k0 = 0; k0 < L.d0; ++k0)
-      for (int k1 = 0; k1 < L.d1; ++k1) {
-        const size_t drow = (size_t)i0[k0] * L.d1 + (size_t)i1[k1];
-        const cfloat* o = in + ((size_t)k0 * L.d1 + k1) * (size_t)nc;
-        for (int k2 = 0; k2 < L.C; ++k2) main_h[drow * L.C + (L.even ? i2[k2] : k2)] = o[k2];
-        if (L.even) nyq_h[drow] = o[L.C];
-      }
-    be::h2d(f.vol, main_h.data(), main_h.size() * sizeof(cfloat), f.s);
-    if (L.even) be::h2d(f.nyq, nyq_h.data(), nyq_h.size() * sizeof(cfloat), f.s);
-    f.plan->backward(f.vol, f.nyq, 1.f, f.s);
-    be::d2h_2d(real, (size_t)L.d2 * 4, f.vol, (size_t)L.RP * 4, (size_t)L.d2 * 4, L.rows, f.s);
+    natural_to_position(*f.plan, reinterpret_cast<const cfloat*>(spec), main_h, nyq_h);
+    be::h2d(f.v(), main_h.data(), main_h.size() * sizeof(cfloat), f.s);
+    if (L.even) be::h2d(f.n(), nyq_h.data(), nyq_h.size() * sizeof(cfloat), f.s);
+    f.plan->backward(f.v(), f.n(), 1.f, f.s);
+    be::d2h_2d(real, (size_t)L.d2 * 4, f.v(), (size_t)L.RP * 4, (size_t)L.d2 * 4, L.rows, f.s);
     be::stream_sync(f.s);
   });
 }
@@ -2077,41 +1930,16 @@ int mvn_fft3_profile(int device, const int dims[3], int direction, int reps, flo
     std::lock_guard<std::mutex> lk(device_mutex(dev));
     FftScratch f(dev, dims);
     const Layout& L = f.plan->L;
-    {  // non-trivial contents (zeros flatter the clock: guide 5.4 rule 25)
-      std::vector<float> host(L.real_floats());
-      unsigned x = 12345u;
-      for (size_t i = 0; i < host.size(); ++i) {
-        x = x * 1664525u + 1013904223u;
-        host[i] = (float)(x >> 8) * (1.0f / 16777216.0f) - 0.5f;
-      }
-      be::h2d(f.vol, host.data(), host.size() * 4, f.s);
+    {
+      const std::vector<float> host = lcg_fill(L.real_floats());
+      be::h2d(f.v(), host.data(), host.size() * 4, f.s);
       be::stream_sync(f.s);
     }
-    const float keep = 1.0f / (float)L.logical();
-    auto run = [&] {
-      if (direction == 0)
-        f.plan->forward(f.vol, f.nyq, f.s);
-      else
-        f.plan->backward(f.vol, f.nyq, keep, f.s);
-    };
-    run();  // warm-up
-    be::event_t a = be::event_create(), b = be::event_create();
-    be::event_record(a, f.s);
-    for (int i = 0; i < reps; ++i) run();
-    be::event_record(b, f.s);
-    be::event_sync(b);
-    *ms = be::event_elapsed_ms(a, b) / (float)reps;
-    be::event_destroy(a);
-    be::event_destroy(b);
+    *ms = time_on_stream(f.s, reps, [&] { f.transform(0, direction); });
     if (per_kind_ms) {  // second, event-instrumented round: average launch time per kernel kind
       Profiler prof;
       prof.enabled = true;
-      for (int i = 0; i < reps; ++i) {
-        if (direction == 0)
-          f.plan->forward(f.vol, f.nyq, f.s, &prof);
-        else
-          f.plan->backward(f.vol, f.nyq, keep, f.s, &prof);
-      }
+      for (int i = 0; i < reps; ++i) f.transform(0, direction, &prof);
       be::stream_sync(f.s);
       prof.collect();
       for (int k = 0; k < KK_COUNT; ++k)
@@ -2122,77 +1950,24 @@ int mvn_fft3_profile(int device, const int dims[3], int direction, int reps, flo
 
 // Batched transforms: `batch` stacks of one shape through ONE cached plan, back to back on one
 // stream -- the counterpart of the cufftPlanMany path of bench/bench_gpu_many_nd_fft.cu:403-463.
-namespace {
-struct FftBatch {
-  std::shared_ptr<Plan3D> plan;
-  be::stream_t s = nullptr;
-  std::vector<float*> vol;
-  std::vector<cfloat*> nyq;
-  FftBatch(int dev, const int* dims, int batch) {
-    be::set_device(dev);
-    plan = PlanStore::get().add(dev, to_shape(dims));
-    s = be::stream_create();
-    try {
-      for (int b = 0; b < batch; ++b) {
-        vol.push_back((float*)be::dmalloc(plan->main_bytes()));
-        be::dzero(vol.back(), plan->main_bytes(), s);
-        nyq.push_back(nullptr);
-        if (plan->nyq_bytes()) {
-          nyq.back() = (cfloat*)be::dmalloc(plan->nyq_bytes());
-          be::dzero(nyq.back(), plan->nyq_bytes(), s);
-        }
-      }
-    } catch (...) {
-      release();
-      throw;
-    }
-  }
-  void release() {
-    try {
-      be::stream_sync(s);
-    } catch (...) {
-    }
-    for (float* v : vol) be::dfree(v);
-    for (cfloat* n : nyq) be::dfree(n);
-    vol.clear();
-    nyq.clear();
-    if (s) be::stream_destroy(s);
-    s = nullptr;
-  }
-  ~FftBatch() { release(); }
-};
-}  // namespace
-
 int mvn_fft3_many_r2c(int device, const int dims[3], int batch, const float* real, float* spec) {
   return guarded("mvn_fft3_many_r2c", [&] {
     if (batch < 1 || !real || !spec) throw std::invalid_argument("bad batch or null buffers");
     const int dev = pick_device(device);
     std::lock_guard<std::mutex> lk(device_mutex(dev));
-    FftBatch f(dev, dims, batch);
+    FftScratch f(dev, dims, batch);
     const Layout& L = f.plan->L;
     const size_t nreal = (size_t)L.d0 * L.d1 * L.d2;
-    const int nc = L.d2 / 2 + 1;
-    const size_t nspec = (size_t)L.d0 * L.d1 * nc;
+    const size_t nspec = (size_t)L.d0 * L.d1 * (size_t)(L.d2 / 2 + 1);
     for (int b = 0; b < batch; ++b)
-      be::h2d_2d(f.vol[b], (size_t)L.RP * 4, real + b * nreal, (size_t)L.d2 * 4, (size_t)L.d2 * 4,
-                 L.rows, f.s);
-    for (int b = 0; b < batch; ++b) f.plan->forward(f.vol[b], f.nyq[b], f.s);
+      be::h2d_2d(f.v(b), (size_t)L.RP * 4, real + b * nreal, (size_t)L.d2 * 4, (size_t)L.d2 * 4, L.rows, f.s);
+    for (int b = 0; b < batch; ++b) f.transform(b, 0);
     std::vector<cfloat> main_h(L.rows * (size_t)L.C), nyq_h(L.nyq_cplx());
-    const std::vector<int>& i0 = f.plan->ax0.host.inv;
-    const std::vector<int>& i1 = f.plan->ax1.host.inv;
-    const std::vector<int>& i2 = f.plan->ax2.host.inv;
     for (int b = 0; b < batch; ++b) {
-      be::d2h(main_h.data(), f.vol[b], main_h.size() * sizeof(cfloat), f.s);
-      if (L.even) be::d2h(nyq_h.data(), f.nyq[b], nyq_h.size() * sizeof(cfloat), f.s);
+      be::d2h(main_h.data(), f.v(b), main_h.size() * sizeof(cfloat), f.s);
+      if (L.even) be::d2h(nyq_h.data(), f.n(b), nyq_h.size() * sizeof(cfloat), f.s);
       be::stream_sync(f.s);
-      cfloat* out = reinterpret_cast<cfloat*>(spec) + b * nspec;
-      for (int k0 = 0; k0 < L.d0; ++k0)
-        for (int k1 = 0; k1 < L.d1; ++k1) {
-          const size_t srow = (size_t)i0[k0] * L.d1 + (size_t)i1[k1];
-          cfloat* o = out + ((size_t)k0 * L.d1 + k1) * (size_t)nc;
-          for (int k2 = 0; k2 < L.C; ++k2) o[k2] = main_h[srow * L.C + (L.even ? i2[k2] : k2)];
-          if (L.even) o[L.C] = nyq_h[srow];
-        }
+      position_to_natural(*f.plan, main_h, nyq_h, reinterpret_cast<cfloat*>(spec) + b * nspec);
     }
   });
 }
@@ -2203,36 +1978,15 @@ int mvn_fft3_many_time(int device, const int dims[3], int batch, int direction, 
     if (batch < 1 || reps < 1 || !ms) throw std::invalid_argument("bad batch, reps or null ms");
     const int dev = pick_device(device);
     std::lock_guard<std::mutex> lk(device_mutex(dev));
-    FftBatch f(dev, dims, batch);
-    const Layout& L = f.plan->L;
+    FftScratch f(dev, dims, batch);
     {
-      std::vector<float> host(L.real_floats());
-      unsigned x = 12345u;
-      for (size_t i = 0; i < host.size(); ++i) {
-        x = x * 1664525u + 1013904223u;
-        host[i] = (float)(x >> 8) * (1.0f / 16777216.0f) - 0.5f;
-      }
-      for (int b = 0; b < batch; ++b) be::h2d(f.vol[b], host.data(), host.size() * 4, f.s);
+      const std::vector<float> host = lcg_fill(f.plan->L.real_floats());
+      for (int b = 0; b < batch; ++b) be::h2d(f.v(b), host.data(), host.size() * 4, f.s);
       be::stream_sync(f.s);
     }
-    const float keep = 1.0f / (float)L.logical();
-    auto sweep = [&] {
-      for (int b = 0; b < batch; ++b) {
-        if (direction == 0)
-          f.plan->forward(f.vol[b], f.nyq[b], f.s);
-        else
-          f.plan->backward(f.vol[b], f.nyq[b], keep, f.s);
-      }
-    };
-    sweep();  // warm-up
-    be::event_t a = be::event_create(), b2 = be::event_create();
-    be::event_record(a, f.s);
-    for (int i = 0; i < reps; ++i) sweep();
-    be::event_record(b2, f.s);
-    be::event_sync(b2);
-    *ms = be::event_elapsed_ms(a, b2) / (float)reps;
-    be::event_destroy(a);
-    be::event_destroy(b2);
+    *ms = time_on_stream(f.s, reps, [&] {
+      for (int b = 0; b < batch; ++b) f.transform(b, direction);
+    });
   });
 }
 
@@ -2530,14 +2284,12 @@ int mvn_engine_time_iterate(mvn_engine* e, int iterations, double lambda, float 
                             float* ms) {
   MVN_ENGINE_CALL("mvn_engine_time_iterate", {
     be::set_device(E.device());
-    be::event_t a = be::event_create(), b = be::event_create();
-    be::event_record(a, E.stream());
+    const be::Event a = be::Event::timing(), b = be::Event::timing();
+    be::event_record(a.get(), E.stream());
     E.iterate(iterations, lambda, min_value);
-    be::event_record(b, E.stream());
-    be::event_sync(b);
-    *ms = be::event_elapsed_ms(a, b);
-    be::event_destroy(a);
-    be::event_destroy(b);
+    be::event_record(b.get(), E.stream());
+    be::event_sync(b.get());
+    *ms = be::event_elapsed_ms(a.get(), b.get());
     E.sync();
   });
 }

@@ -9,6 +9,7 @@
 #pragma once
 
 #include <cstddef>
+#include <utility>
 
 #include "mvn_pass_bodies.hpp"
 #include "mvn_dim0_direct.hpp"
@@ -168,6 +169,92 @@ void launch_update(float* psi, const float* integral, const float* weights, size
 void launch_update_legacy_tikhonov(float* image, const float* integral, const float* weights,
                                    size_t n, float lambda_f, float min_value, stream_t s);
 void launch_axpy1(float* psi, const float* delta, size_t n, stream_t s);
+
+// ---- owning handles -----------------------------------------------------------------------
+// A device buffer, a stream and an event that release themselves: move-only, written on the functions above alone,
+// so the product and the emulation share them.  ONE rule of order: a function declares its buffers BEFORE its
+// stream.  Locals and members are destroyed in reverse order, so every way out of the function drains the stream,
+// destroys it and only then frees the buffers the stream's work used.  Work on the null stream needs buffer owners
+// alone (freeing device memory synchronises); a buffer whose work runs on a stream somebody else owns is drained by
+// hand (drain_quietly) before it goes out of scope on an error path.
+
+// wait for `s` on a path that must not throw (destructors, error paths): a failure here has been or will be reported
+// by the call that caused it
+inline void drain_quietly(stream_t s) {
+  try {
+    stream_sync(s);
+  } catch (...) {
+  }
+}
+
+template <typename T = void>
+class DeviceBuffer {
+ public:
+  DeviceBuffer() = default;
+  explicit DeviceBuffer(size_t bytes) : p_(static_cast<T*>(dmalloc(bytes))) {}
+  DeviceBuffer(DeviceBuffer&& o) noexcept : p_(o.release()) {}
+  DeviceBuffer& operator=(DeviceBuffer&& o) noexcept {
+    reset(o.release());
+    return *this;
+  }
+  ~DeviceBuffer() { dfree(p_); }
+  T* get() const { return p_; }
+  T* release() { return std::exchange(p_, nullptr); }
+  void reset(T* p = nullptr) {
+    dfree(p_);
+    p_ = p;
+  }
+
+ private:
+  T* p_ = nullptr;
+};
+
+class Stream {
+ public:
+  Stream() = default;  // empty: holds no stream (not the null stream)
+  static Stream create() { return Stream(stream_create()); }
+  static Stream create_upload() { return Stream(stream_create_upload()); }
+  Stream(Stream&& o) noexcept : s_(std::exchange(o.s_, nullptr)) {}
+  Stream& operator=(Stream&& o) noexcept {
+    reset(std::exchange(o.s_, nullptr));
+    return *this;
+  }
+  ~Stream() { reset(); }
+  stream_t get() const { return s_; }
+  void reset(stream_t s = nullptr) {
+    if (s_) {
+      drain_quietly(s_);
+      stream_destroy(s_);
+    }
+    s_ = s;
+  }
+
+ private:
+  explicit Stream(stream_t s) : s_(s) {}
+  stream_t s_ = nullptr;
+};
+
+class Event {
+ public:
+  Event() = default;
+  static Event timing() { return Event(event_create()); }
+  static Event sync_only() { return Event(event_create_sync()); }
+  Event(Event&& o) noexcept : e_(std::exchange(o.e_, nullptr)) {}
+  Event& operator=(Event&& o) noexcept {
+    reset(std::exchange(o.e_, nullptr));
+    return *this;
+  }
+  ~Event() { reset(); }
+  event_t get() const { return e_; }
+  void reset(event_t e = nullptr) {
+    if (e_) event_destroy(e_);
+    e_ = e;
+  }
+
+ private:
+  explicit Event(event_t e) : e_(e) {}
+  event_t e_ = nullptr;
+};
 
 }  // namespace be
 }  // namespace mvn

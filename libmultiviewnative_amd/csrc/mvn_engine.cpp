@@ -755,7 +755,7 @@ void PlanStore::clear() {
 // ---------------------------------------------------------------------------------------------
 // Engine
 // ---------------------------------------------------------------------------------------------
-Engine::Engine(int device, const shape_t& dims, int num_views) : device_(device) {
+Engine::Engine(int device, const shape_t& dims, int num_views) : Engine(device) {
   // zero views: a rank of a view-sharded run that got none (6 views on 8 GPUs) still keeps a
   // replica of psi and takes part in the all-reduce with a zero correction
   if (num_views < 0) throw std::invalid_argument("mvn: num_views must be >= 0");
@@ -837,17 +837,11 @@ Engine::~Engine() {
   be::dfree(poison_own_);
   be::graph_destroy(sweep_graph_);
   if (!delta_external_) be::dfree(delta_);
-  try {
-    if (side_.s) be::stream_sync(side_.s);
-  } catch (...) {
-  }
+  if (side_.s) be::drain_quietly(side_.s);
   side_.destroy();
-  try {
-    if (upload_stream_) be::stream_sync(upload_stream_);
-  } catch (...) {
-  }
-  for (size_t i = 0; i < stage_scratch_.size(); ++i) be::dfree(stage_scratch_[i]);
-  for (size_t i = 0; i < staged_ev_.size(); ++i) be::event_destroy(staged_ev_[i]);
+  if (upload_stream_) be::drain_quietly(upload_stream_);
+  stage_scratch_.clear();
+  staged_ev_.clear();
   if (upload_stream_) be::stream_destroy(upload_stream_);
   if (stream_) be::stream_destroy(stream_);
 }
@@ -1066,44 +1060,37 @@ long long Engine::resample_raw(ResampleParams p, const StackRef& image, be::stre
   }
   p.src = image.ptr, p.s0 = image.stride[0], p.s1 = image.stride[1], p.s2 = image.stride[2];
   p.g = g;
-  void* tmp = nullptr;
+  be::DeviceBuffer<char> tmp;
   long long bytes = 0;
-  if (!image.device) {  // the raw stack crosses PCIe as it is, into a dense temporary
-    const size_t esz = image.u16 ? sizeof(uint16_t) : sizeof(float);
-    if (image.broadcast()) {
-      bytes = (long long)esz;
-      tmp = be::dmalloc(esz);
-      be::h2d(tmp, image.ptr, esz, s);
-    } else {
-      check_host_rows(image, g.m);
-      bytes = (long long)g.m[0] * g.m[1] * g.m[2] * (long long)esz;
-      tmp = be::dmalloc((size_t)bytes);
-      const bool dense = (g.m[1] == 1 || image.stride[1] == g.m[2]) &&
-                         (g.m[0] == 1 || image.stride[0] == (long long)g.m[1] * g.m[2]);
-      if (dense)
-        be::h2d(tmp, image.ptr, (size_t)bytes, s);
-      else
-        host_rows_to_device((char*)tmp, (size_t)g.m[2] * esz, (size_t)g.m[1] * g.m[2] * esz, (const char*)image.ptr,
-                            image.stride[0] * (long long)esz, image.stride[1] * (long long)esz, (size_t)g.m[2] * esz,
-                            g.m, s);
-      p.s0 = (long long)g.m[1] * g.m[2], p.s1 = g.m[2], p.s2 = 1;
-    }
-    p.src = tmp;
-  }
   try {
-    be::launch_resample(p, image.u16, s);
-    if (tmp) be::stream_sync(s);
-  } catch (...) {
-    if (tmp) {
-      try {
-        be::stream_sync(s);
-      } catch (...) {
+    if (!image.device) {  // the raw stack crosses PCIe as it is, into a dense temporary
+      const size_t esz = image.u16 ? sizeof(uint16_t) : sizeof(float);
+      if (image.broadcast()) {
+        bytes = (long long)esz;
+        tmp = be::DeviceBuffer<char>(esz);
+        be::h2d(tmp.get(), image.ptr, esz, s);
+      } else {
+        check_host_rows(image, g.m);
+        bytes = (long long)g.m[0] * g.m[1] * g.m[2] * (long long)esz;
+        tmp = be::DeviceBuffer<char>((size_t)bytes);
+        const bool dense = (g.m[1] == 1 || image.stride[1] == g.m[2]) &&
+                           (g.m[0] == 1 || image.stride[0] == (long long)g.m[1] * g.m[2]);
+        if (dense)
+          be::h2d(tmp.get(), image.ptr, (size_t)bytes, s);
+        else
+          host_rows_to_device(tmp.get(), (size_t)g.m[2] * esz, (size_t)g.m[1] * g.m[2] * esz, (const char*)image.ptr,
+                              image.stride[0] * (long long)esz, image.stride[1] * (long long)esz, (size_t)g.m[2] * esz,
+                              g.m, s);
+        p.s0 = (long long)g.m[1] * g.m[2], p.s1 = g.m[2], p.s2 = 1;
       }
-      be::dfree(tmp);
+      p.src = tmp.get();
     }
+    be::launch_resample(p, image.u16, s);
+    if (tmp.get()) be::stream_sync(s);
+  } catch (...) {
+    if (tmp.get()) be::drain_quietly(s);  // the caller's stream: what it holds of tmp's is over before tmp goes
     throw;
   }
-  be::dfree(tmp);
   return bytes;
 }
 
@@ -1277,8 +1264,8 @@ void Engine::prepare_psf(ViewSlot& s, int i, const float* d_kernel, const int* k
     if (!staging) throw std::logic_error("mvn: spectrum scratch missing");
     if (!stage_spec_scratch_) {  // the main thread iterates on the work volume meanwhile: own scratch, freed
                                  // with the other staging scratch once the upload stream has drained
-      stage_spec_scratch_ = (float*)be::dmalloc(plan_->main_bytes());
-      stage_scratch_.push_back(stage_spec_scratch_);
+      stage_scratch_.emplace_back(plan_->main_bytes());
+      stage_spec_scratch_ = stage_scratch_.back().get();
     }
     scratch = stage_spec_scratch_;
   }
@@ -1605,8 +1592,9 @@ void Engine::prepare_psfs(ViewSlot& s, const float* kernel1, const int* k1dims, 
   for (int i = 0; i < 2; ++i) {
     if (psf_resident(s, i, ks[i], kd[i])) continue;
     const size_t kb = sizeof(float) * (size_t)kd[i][0] * (size_t)kd[i][1] * (size_t)kd[i][2];
-    float* dk = (float*)be::dmalloc(kb);
-    if (staging) stage_scratch_.push_back(dk);  // freed in finish_staging(), after the stream has drained
+    be::DeviceBuffer<float> own(kb);
+    float* dk = own.get();
+    if (staging) stage_scratch_.push_back(std::move(own));  // freed in finish_staging(), after the stream has drained
     be::h2d(dk, ks[i], kb, st);
     try {
       // nothing else runs on this engine during a blocking set_view: the work volume is the scratch
@@ -1614,17 +1602,11 @@ void Engine::prepare_psfs(ViewSlot& s, const float* kernel1, const int* k1dims, 
       prepare_psf(s, i, dk, kd[i], staging ? nullptr : work_, staging, st);
       // the direct leg's second work volume: allocated here, not inside a sweep (reserve_views has, when staging)
       if (!staging && s.tap_k[i]) ensure_work2();
+      if (!staging) be::stream_sync(st);
     } catch (...) {
-      if (!staging) {
-        be::stream_sync(st);
-        be::dfree(dk);
-      }
+      if (!staging) be::drain_quietly(st);
       s.kcopy[i].clear();  // the resident form is in an unknown state: never a cache hit
       throw;
-    }
-    if (!staging) {
-      be::stream_sync(st);
-      be::dfree(dk);
     }
   }
 }
@@ -1635,9 +1617,9 @@ void Engine::reserve_views(const kernel_list_t& kernels) {
   for (size_t v = 0; v < views_.size(); ++v) alloc_view(views_[v]);
   if (sw_.direct) ensure_work2();  // (not inside the first sweep: the direct dim0 leg is out of place)
   if (!upload_stream_) upload_stream_ = be::stream_create_upload();
-  staged_ev_.resize(views_.size(), nullptr);
+  staged_ev_.resize(views_.size());
   for (size_t v = 0; v < views_.size(); ++v)
-    if (!staged_ev_[v]) staged_ev_[v] = be::event_create_sync();
+    if (!staged_ev_[v].get()) staged_ev_[v] = be::Event::sync_only();
   staged_.assign(views_.size(), 0);
   pre_ingested_.assign(views_.size(), 0);
   {
@@ -1672,7 +1654,7 @@ void Engine::stage_view(int v, const StackRef& image, const StackRef& weights, c
   else if (!pre_ingested_[(size_t)v])
     ingest_pair(s.image, s.weights, image, weights, upload_stream_, s.image_u16);
   prepare_psfs(s, kernel1, k1dims, kernel2, k2dims, true, upload_stream_);
-  be::event_record(staged_ev_[(size_t)v], upload_stream_);
+  be::event_record(staged_ev_[(size_t)v].get(), upload_stream_);
   s.set = true;
   {
     std::lock_guard<std::mutex> lk(stage_mu_);
@@ -1694,7 +1676,6 @@ void Engine::staging_failed() {
 void Engine::finish_staging() {
   be::set_device(device_);
   if (upload_stream_) be::stream_sync(upload_stream_);
-  for (size_t i = 0; i < stage_scratch_.size(); ++i) be::dfree(stage_scratch_[i]);
   stage_scratch_.clear();
   stage_spec_scratch_ = nullptr;
 }
@@ -1706,7 +1687,7 @@ void Engine::wait_staged(int v) {
   stage_cv_.wait(lk, [&] { return staged_[(size_t)v] != 0; });
   if (staged_[(size_t)v] < 0) throw std::runtime_error("mvn: staging of view " + std::to_string(v) + " failed");
   lk.unlock();
-  be::stream_wait_event(stream_, staged_ev_[(size_t)v]);
+  be::stream_wait_event(stream_, staged_ev_[(size_t)v].get());
 }
 
 // ---- out-of-core views ---------------------------------------------------------------------------
@@ -2303,10 +2284,7 @@ int Engine::iterate(int iterations, double lambda, float min_value, const LoopOp
       bool held = false;
       for (int b = 0; b < LoopState::kKept; ++b) held = held || e.loop_.buf[b];
       if (!held) return;
-      try {
-        be::stream_sync(e.stream_);
-      } catch (...) {
-      }
+      be::drain_quietly(e.stream_);
       e.loop_.release(0, LoopState::kKept);
     }
   } scope{*this};
@@ -2872,41 +2850,31 @@ void SlabEngine::set_view(int v, const float* image, const float* weights, const
   std::shared_ptr<Plan3D> full = PlanStore::get().add(device_, dims_);
   const Layout& F = full->L;
   const float scale = (float)(1.0 / (double)F.logical());
-  float* fspec = (float*)be::dmalloc(full->main_bytes());
-  cfloat* fnyq = nullptr;
-  float* dk = nullptr;
+  be::DeviceBuffer<float> fspec(full->main_bytes()), dk;
+  be::DeviceBuffer<cfloat> fnyq;
   try {
-    if (full->nyq_bytes()) fnyq = (cfloat*)be::dmalloc(full->nyq_bytes());
+    if (full->nyq_bytes()) fnyq = be::DeviceBuffer<cfloat>(full->nyq_bytes());
     const float* ks[2] = {kernel1, kernel2};
     const int* kd[2] = {k1dims, k2dims};
     const size_t yb = (size_t)(F.d1 / P_);
     for (int i = 0; i < 2; ++i) {
       const size_t kb = sizeof(float) * (size_t)kd[i][0] * (size_t)kd[i][1] * (size_t)kd[i][2];
-      dk = (float*)be::dmalloc(kb);
-      be::h2d(dk, ks[i], kb, stream_);
-      full->psf_spectrum(dk, kd[i], scale, fspec, fnyq, stream_);
+      dk = be::DeviceBuffer<float>(kb);
+      be::h2d(dk.get(), ks[i], kb, stream_);
+      full->psf_spectrum(dk.get(), kd[i], scale, fspec.get(), fnyq.get(), stream_);
       const size_t wrow = yb * (size_t)F.C * sizeof(cfloat);
-      be::d2d_2d(s.spec[i], wrow, (const cfloat*)fspec + (size_t)rank_ * yb * F.C,
+      be::d2d_2d(s.spec[i], wrow, (const cfloat*)fspec.get() + (size_t)rank_ * yb * F.C,
                  (size_t)F.d1 * F.C * sizeof(cfloat), wrow, (size_t)F.d0, stream_);
-      if (fnyq)
-        be::d2d_2d(s.nyq[i], yb * sizeof(cfloat), fnyq + (size_t)rank_ * yb,
+      if (fnyq.get())
+        be::d2d_2d(s.nyq[i], yb * sizeof(cfloat), fnyq.get() + (size_t)rank_ * yb,
                    (size_t)F.d1 * sizeof(cfloat), yb * sizeof(cfloat), (size_t)F.d0, stream_);
       be::stream_sync(stream_);
-      be::dfree(dk);
-      dk = nullptr;
+      dk.reset();
     }
   } catch (...) {
-    try {
-      be::stream_sync(stream_);
-    } catch (...) {
-    }
-    be::dfree(dk);
-    be::dfree(fspec);
-    be::dfree(fnyq);
+    be::drain_quietly(stream_);  // the engine's stream outlives the three temporaries
     throw;
   }
-  be::dfree(fspec);
-  be::dfree(fnyq);
   s.set = true;
 }
 

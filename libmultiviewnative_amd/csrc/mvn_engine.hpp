@@ -802,18 +802,20 @@ class Engine {
   bool spec_tiled_ = false;
   float* stage_spec_scratch_ = nullptr;  // owned by stage_scratch_
   void wait_staged(int v);
+  // the public constructor delegates to this one, so that ~Engine releases what a construction that fails had made
+  explicit Engine(int device) : device_(device) {}
   int device_;
   std::shared_ptr<Plan3D> plan_;
   be::stream_t stream_ = nullptr;
   SideStream side_;
   // staging pipeline
   be::stream_t upload_stream_ = nullptr;
-  std::vector<be::event_t> staged_ev_;
+  std::vector<be::Event> staged_ev_;
   std::vector<int> staged_;  // per view: 0 pending, 1 enqueued on the upload stream, -1 failed
   bool pipelined_ = false;
   std::mutex stage_mu_;
   std::condition_variable stage_cv_;
-  std::vector<float*> stage_scratch_;
+  std::vector<be::DeviceBuffer<float>> stage_scratch_;
   // out-of-core views (set_residency): per view its position in the sweep's streamed order, or -1 (resident)
   struct RingSlot {
     float* image = nullptr;

@@ -95,11 +95,11 @@ HaloGroup::HaloGroup(const std::vector<int>& devices, const shape_t& ext, int h,
     const shape_t shape = {{s.nz + 2 * h, ext[1], ext[2]}};
     s.eng.reset(new Engine(s.dev, shape, V));
     for (int i = 0; i < 2; ++i) {
-      s.e_fwd[i] = be::event_create_sync();
-      s.e_copy[i][0] = be::event_create_sync();
-      s.e_copy[i][1] = be::event_create_sync();
-      s.e_leg[i] = be::event_create_sync();
-      s.halo_stream[i] = be::stream_create();
+      s.e_fwd[i] = be::Event::sync_only();
+      s.e_copy[i][0] = be::Event::sync_only();
+      s.e_copy[i][1] = be::Event::sync_only();
+      s.e_leg[i] = be::Event::sync_only();
+      s.halo_stream[i] = be::Stream::create();
     }
     s.eng->set_halo_hook(&HaloGroup::hook, &s, /*drain=*/false, /*post=*/true);
     s.eng->set_halo_planes(h, /*split=*/true);
@@ -129,16 +129,12 @@ HaloGroup::~HaloGroup() {
     } catch (...) {
     }
     s.eng.reset();
-    for (int i = 0; i < 2; ++i) {
-      try {
-        if (s.halo_stream[i]) be::stream_sync(s.halo_stream[i]);
-      } catch (...) {
-      }
-      be::stream_destroy(s.halo_stream[i]);
-      be::event_destroy(s.e_fwd[i]);
-      be::event_destroy(s.e_copy[i][0]);
-      be::event_destroy(s.e_copy[i][1]);
-      be::event_destroy(s.e_leg[i]);
+    for (int i = 0; i < 2; ++i) {  // (here, not by the members' destructors: with the handles' own device current)
+      s.halo_stream[i].reset();
+      s.e_fwd[i].reset();
+      s.e_copy[i][0].reset();
+      s.e_copy[i][1].reset();
+      s.e_leg[i].reset();
     }
   }
 }
@@ -178,7 +174,7 @@ void HaloGroup::before_leg(Slab& s, void* spectrum) {
   const int par = (int)(s.convs & 1);
   s.spectrum = spectrum;
   s.spectrum_nyq = s.eng->leg_input_nyq();  // (split layout: the Nyquist plane has halo planes of its own)
-  be::event_record(s.e_fwd[par], s.eng->stream());
+  be::event_record(s.e_fwd[par].get(), s.eng->stream());
   barrier_.wait();
   Slab& lo = slabs_[(size_t)((s.index + P - 1) % P)];
   Slab& up = slabs_[(size_t)((s.index + 1) % P)];
@@ -191,9 +187,9 @@ void HaloGroup::before_leg(Slab& s, void* spectrum) {
   // (two slabs: the one neighbour is both, one link, one stream - a process's streams share 4 hardware queues)
   for (int side = 0; side < 2; ++side) {
     Slab& nb_slab = side == 0 ? lo : up;
-    be::stream_t hs = s.halo_stream[&lo == &up ? 0 : side];
-    be::stream_wait_event(hs, s.e_fwd[par]);  // (my halo planes are free: every earlier reader is behind this event)
-    be::stream_wait_event(hs, nb_slab.e_fwd[par]);
+    be::stream_t hs = s.halo_stream[&lo == &up ? 0 : side].get();
+    be::stream_wait_event(hs, s.e_fwd[par].get());  // (my halo planes are free: every earlier reader is behind this event)
+    be::stream_wait_event(hs, nb_slab.e_fwd[par].get());
     // side 0: planes [0, h) <- the lower neighbour's last h own planes [nz, nz + h) of its extended slab
     // side 1: planes [nz + h, nz + 2 h) <- the upper neighbour's first h own planes [h, 2 h)
     const size_t dst = side == 0 ? 0 : (size_t)(s.nz + h_), src = side == 0 ? (size_t)nb_slab.nz : (size_t)h_;
@@ -202,7 +198,7 @@ void HaloGroup::before_leg(Slab& s, void* spectrum) {
     if (mine_n)
       be::copy_peer(mine_n + dst * nb, s.dev, static_cast<const char*>(nb_slab.spectrum_nyq) + src * nb, nb_slab.dev,
                     (size_t)h_ * nb, hs);
-    be::event_record(s.e_copy[par][side], hs);
+    be::event_record(s.e_copy[par][side].get(), hs);
   }
 }
 
@@ -214,13 +210,13 @@ void HaloGroup::before_boundary(Slab& s) {
   const int P = (int)slabs_.size();
   const int par = (int)(s.convs & 1);
   be::stream_t st = s.eng->stream();
-  be::stream_wait_event(st, s.e_copy[par][0]);
-  be::stream_wait_event(st, s.e_copy[par][1]);
+  be::stream_wait_event(st, s.e_copy[par][0].get());
+  be::stream_wait_event(st, s.e_copy[par][1].get());
   if (s.convs > 0) {
     Slab& lo = slabs_[(size_t)((s.index + P - 1) % P)];
     Slab& up = slabs_[(size_t)((s.index + 1) % P)];
-    be::stream_wait_event(st, lo.e_copy[par ^ 1][1]);  // the lower neighbour's UPPER halo came from my first own planes
-    be::stream_wait_event(st, up.e_copy[par ^ 1][0]);  // the upper neighbour's LOWER halo from my last
+    be::stream_wait_event(st, lo.e_copy[par ^ 1][1].get());  // the lower neighbour's UPPER halo came from my first own planes
+    be::stream_wait_event(st, up.e_copy[par ^ 1][0].get());  // the upper neighbour's LOWER halo from my last
   }
 }
 
@@ -228,10 +224,10 @@ void HaloGroup::before_boundary(Slab& s) {
 void HaloGroup::behind_leg(Slab& s) {
   const int par = (int)(s.convs & 1);
   be::stream_t st = s.eng->stream();
-  be::event_record(s.e_leg[par], st);
+  be::event_record(s.e_leg[par].get(), st);
   barrier_.wait();
   for (size_t r = 0; r < slabs_.size(); ++r)
-    if ((int)r != s.index) be::stream_wait_event(st, slabs_[r].e_leg[par]);
+    if ((int)r != s.index) be::stream_wait_event(st, slabs_[r].e_leg[par].get());
   ++s.convs;
 }
 
@@ -251,7 +247,13 @@ void HaloGroup::on_every_slab(const std::function<void(Slab&)>& body) {
     }
   };
   std::vector<std::thread> threads;
-  for (int r = 1; r < P; ++r) threads.emplace_back(run, r);
+  try {
+    for (int r = 1; r < P; ++r) threads.emplace_back(run, r);
+  } catch (...) {  // a thread could not be started: the ones that run must not wait for it, nor die joinable
+    barrier_.abort();
+    for (size_t i = 0; i < threads.size(); ++i) threads[i].join();
+    throw;
+  }
   run(0);
   for (size_t i = 0; i < threads.size(); ++i) threads[i].join();
   bool failed = false;
@@ -261,8 +263,8 @@ void HaloGroup::on_every_slab(const std::function<void(Slab&)>& body) {
     try {
       be::set_device(slabs_[(size_t)r].dev);
       slabs_[(size_t)r].eng->sync();
-      be::stream_sync(slabs_[(size_t)r].halo_stream[0]);
-      be::stream_sync(slabs_[(size_t)r].halo_stream[1]);
+      be::stream_sync(slabs_[(size_t)r].halo_stream[0].get());
+      be::stream_sync(slabs_[(size_t)r].halo_stream[1].get());
     } catch (...) {
     }
   }
