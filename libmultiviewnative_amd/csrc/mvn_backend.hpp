@@ -171,10 +171,10 @@ void launch_update_legacy_tikhonov(float* image, const float* integral, const fl
 void launch_axpy1(float* psi, const float* delta, size_t n, stream_t s);
 
 // ---- owning handles -----------------------------------------------------------------------
-// A device buffer, a stream and an event that release themselves: move-only, written on the functions above alone,
-// so the product and the emulation share them.  ONE rule of order: a function declares its buffers BEFORE its
-// stream.  Locals and members are destroyed in reverse order, so every way out of the function drains the stream,
-// destroys it and only then frees the buffers the stream's work used.  Work on the null stream needs buffer owners
+// A device buffer, a stream, an event and an instantiated graph that release themselves: move-only, written on the
+// functions above alone, so the product and the emulation share them.  ONE rule of order: buffers are declared BEFORE
+// their stream.  Locals and members are destroyed in reverse order, so every way out of the function, and an engine's
+// destruction, drains the stream, destroys it and only then frees the buffers the stream's work used.  Work on the null stream needs buffer owners
 // alone (freeing device memory synchronises); a buffer whose work runs on a stream somebody else owns is drained by
 // hand (drain_quietly) before it goes out of scope on an error path.
 
@@ -254,6 +254,27 @@ class Event {
  private:
   explicit Event(event_t e) : e_(e) {}
   event_t e_ = nullptr;
+};
+
+// an instantiated graph (capture_end): whoever invalidates it resets it
+class GraphExec {
+ public:
+  GraphExec() = default;
+  explicit GraphExec(graph_exec_t g) : g_(g) {}
+  GraphExec(GraphExec&& o) noexcept : g_(std::exchange(o.g_, nullptr)) {}
+  GraphExec& operator=(GraphExec&& o) noexcept {
+    reset(std::exchange(o.g_, nullptr));
+    return *this;
+  }
+  ~GraphExec() { reset(); }
+  graph_exec_t get() const { return g_; }
+  void reset(graph_exec_t g = nullptr) {
+    if (g_) graph_destroy(g_);
+    g_ = g;
+  }
+
+ private:
+  graph_exec_t g_ = nullptr;
 };
 
 }  // namespace be

@@ -32,13 +32,11 @@ const char* kernel_kind_name(int k) {
 // ---------------------------------------------------------------------------------------------
 // Profiler
 // ---------------------------------------------------------------------------------------------
-be::event_t Profiler::get_event() {
-  if (!pool_.empty()) {
-    be::event_t e = pool_.back();
-    pool_.pop_back();
-    return e;
-  }
-  return be::event_create();
+be::Event Profiler::get_event() {
+  if (pool_.empty()) return be::Event::timing();
+  be::Event e = std::move(pool_.back());
+  pool_.pop_back();
+  return e;
 }
 
 void Profiler::begin(int kind, be::stream_t s) {
@@ -47,22 +45,22 @@ void Profiler::begin(int kind, be::stream_t s) {
   r.kind = kind;
   r.a = get_event();
   r.b = get_event();
-  be::event_record(r.a, s);
-  recs_.push_back(r);
+  be::event_record(r.a.get(), s);
+  recs_.push_back(std::move(r));
 }
 
 void Profiler::end(be::stream_t s) {
   if (!enabled || recs_.empty()) return;
-  be::event_record(recs_.back().b, s);
+  be::event_record(recs_.back().b.get(), s);
 }
 
 void Profiler::collect() {
   for (size_t i = 0; i < recs_.size(); ++i) {
-    be::event_sync(recs_[i].b);
-    total_ms[recs_[i].kind] += be::event_elapsed_ms(recs_[i].a, recs_[i].b);
+    be::event_sync(recs_[i].b.get());
+    total_ms[recs_[i].kind] += be::event_elapsed_ms(recs_[i].a.get(), recs_[i].b.get());
     count[recs_[i].kind] += 1;
-    pool_.push_back(recs_[i].a);
-    pool_.push_back(recs_[i].b);
+    pool_.push_back(std::move(recs_[i].a));
+    pool_.push_back(std::move(recs_[i].b));
   }
   recs_.clear();
 }
@@ -80,7 +78,6 @@ Profiler::~Profiler() {
     collect();
   } catch (...) {
   }
-  for (size_t i = 0; i < pool_.size(); ++i) be::event_destroy(pool_[i]);
 }
 
 struct ProfScope {
@@ -97,31 +94,24 @@ struct ProfScope {
 // ---------------------------------------------------------------------------------------------
 // DevAxis / Plan3D
 // ---------------------------------------------------------------------------------------------
-DevAxis::DevAxis(int n, bool composite) : host(n, composite) {
-  auto upload = [](const void* src, size_t bytes) -> void* {
-    void* d = be::dmalloc(bytes);
-    be::h2d(d, src, bytes, nullptr);
-    return d;
-  };
-  tw = (cfloat*)upload(host.tw.data(), sizeof(cfloat) * host.tw.size());  // nfft entries
-  rev = (int*)upload(host.rev.data(), sizeof(int) * host.rev.size());
-  inv = (int*)upload(host.inv.data(), sizeof(int) * host.inv.size());
-  if (!host.tws.empty()) tws = (cfloat*)upload(host.tws.data(), sizeof(cfloat) * host.tws.size());
-  if (host.bluestein) {
-    chirp = (cfloat*)upload(host.chirp.data(), sizeof(cfloat) * host.chirp.size());
-    bhat = (cfloat*)upload(host.bhat.data(), sizeof(cfloat) * host.bhat.size());
-  }
-  be::stream_sync(nullptr);
-  view = host.view(tw, rev, inv, tws, chirp, bhat);
+template <typename T>
+static be::DeviceBuffer<T> upload(const std::vector<T>& src) {
+  be::DeviceBuffer<T> d(sizeof(T) * src.size());
+  be::h2d(d.get(), src.data(), sizeof(T) * src.size(), nullptr);
+  return d;
 }
 
-DevAxis::~DevAxis() {
-  be::dfree(tw);
-  be::dfree(tws);
-  be::dfree(rev);
-  be::dfree(inv);
-  be::dfree(chirp);
-  be::dfree(bhat);
+DevAxis::DevAxis(int n, bool composite) : host(n, composite) {
+  tw = upload(host.tw);  // nfft entries
+  rev = upload(host.rev);
+  inv = upload(host.inv);
+  if (!host.tws.empty()) tws = upload(host.tws);
+  if (host.bluestein) {
+    chirp = upload(host.chirp);
+    bhat = upload(host.bhat);
+  }
+  be::stream_sync(nullptr);
+  view = host.view(tw.get(), rev.get(), inv.get(), tws.get(), chirp.get(), bhat.get());
 }
 
 static int env_int(const char* name, int dflt) {
@@ -253,8 +243,8 @@ Plan3D::Plan3D(int dev, int d0, int d1, int d2, bool fixed_allowed)
       ax0(d0, ax0_fixed(L, fixed)) {
   // the word an epilogue that follows no direct dim0 leg compares with (EpilogueParams::poison is never null
   // on the device): zero, against the epoch 0xffffffff no leg ever has
-  no_poison = (unsigned*)be::dmalloc(64);
-  be::dzero(no_poison, 64, nullptr);
+  no_poison = be::DeviceBuffer<unsigned>(64);
+  be::dzero(no_poison.get(), 64, nullptr);
   be::stream_sync(nullptr);
   if (L.even) {
     std::vector<cfloat> roots((size_t)L.h / 2 + 1);
@@ -263,8 +253,8 @@ Plan3D::Plan3D(int dev, int d0, int d1, int d2, bool fixed_allowed)
       roots[k].x = (float)std::cos(a);
       roots[k].y = (float)std::sin(a);
     }
-    twr = (cfloat*)be::dmalloc(sizeof(cfloat) * roots.size());
-    be::h2d(twr, roots.data(), sizeof(cfloat) * roots.size(), nullptr);
+    twr = be::DeviceBuffer<cfloat>(sizeof(cfloat) * roots.size());
+    be::h2d(twr.get(), roots.data(), sizeof(cfloat) * roots.size(), nullptr);
     be::stream_sync(nullptr);
   }
   // LDS rows per tile = length of the radix transform (the chirp-z length for bluestein axes)
@@ -303,11 +293,6 @@ Plan3D::Plan3D(int dev, int d0, int d1, int d2, bool fixed_allowed)
   }
 }
 
-Plan3D::~Plan3D() {
-  be::dfree(twr);
-  be::dfree(no_poison);
-}
-
 // a range of rows of a last-axis pass: whole tiles where the kernels need them
 static long rows_in_range(const Plan3D& P, long row0, long nrows) {
   const long all = (long)P.L.rows;
@@ -341,7 +326,7 @@ void Plan3D::rows_r2c(const float* in_real, cfloat* out, cfloat* out_nyq, be::st
   RowsParams p;
   std::memset(&p, 0, sizeof(p));
   p.ax = ax2.view;
-  p.twr = twr;
+  p.twr = twr.get();
   p.d2 = L.d2;
   p.h = L.h;
   p.C = L.C;
@@ -390,7 +375,7 @@ void Plan3D::rows_c2r(const cfloat* in, const cfloat* in_nyq, float* out_real,
   RowsParams p;
   std::memset(&p, 0, sizeof(p));
   p.ax = ax2.view;
-  p.twr = twr;
+  p.twr = twr.get();
   p.d2 = L.d2;
   p.h = L.h;
   p.C = L.C;
@@ -409,7 +394,7 @@ void Plan3D::rows_c2r(const cfloat* in, const cfloat* in_nyq, float* out_real,
   p.out_real = out_real;
   p.epi = epi;
   if (!p.epi.poison) {
-    p.epi.poison = no_poison;
+    p.epi.poison = no_poison.get();
     p.epi.poison_epoch = 0xffffffffu;
   }
   if (st) {
@@ -445,7 +430,7 @@ void Plan3D::rows_c2r_r2c(cfloat* data, cfloat* nyq, const EpilogueParams& epi_a
   RowsParams p;
   std::memset(&p, 0, sizeof(p));
   p.ax = ax2.view;
-  p.twr = twr;
+  p.twr = twr.get();
   p.d2 = L.d2;
   p.h = L.h;
   p.C = L.C;
@@ -459,7 +444,7 @@ void Plan3D::rows_c2r_r2c(cfloat* data, cfloat* nyq, const EpilogueParams& epi_a
   if (lines) lines_args(*this, p, row0, nyq, nullptr, nullptr);
   p.epi = epi;
   if (!p.epi.poison) {
-    p.epi.poison = no_poison;
+    p.epi.poison = no_poison.get();
     p.epi.poison_epoch = 0xffffffffu;
   }
   if (st) {
@@ -545,27 +530,19 @@ static StridedParams make_strided(const DevAxis& ax, const PassGeom& g, cfloat* 
 }
 
 void SideStream::create() {
-  s = be::stream_create();
-  fork = be::event_create_sync();
-  join = be::event_create_sync();
-}
-
-void SideStream::destroy() {
-  if (s) be::stream_destroy(s);
-  be::event_destroy(fork);
-  be::event_destroy(join);
-  s = nullptr;
-  fork = join = nullptr;
+  s = be::Stream::create();
+  fork = be::Event::sync_only();
+  join = be::Event::sync_only();
 }
 
 void SideStream::fork_from(be::stream_t main) {
-  be::event_record(fork, main);
-  be::stream_wait_event(s, fork);
+  be::event_record(fork.get(), main);
+  be::stream_wait_event(s.get(), fork.get());
 }
 
 void SideStream::join_into(be::stream_t main) {
-  be::event_record(join, s);
-  be::stream_wait_event(main, join);
+  be::event_record(join.get(), s.get());
+  be::stream_wait_event(main, join.get());
 }
 
 void Plan3D::axis1(int mode, cfloat* data, cfloat* nyq, be::stream_t s, Profiler* prof,
@@ -658,9 +635,9 @@ void Plan3D::middle_passes(cfloat* work, cfloat* work_nyq, const cfloat* spec,
                            SideStream* side, bool spec_tiled) const {
   be::stream_t sn = s;
   // (where the plane's dim1 transforms ride in the main launches, its dim0 launch runs in line between them)
-  if (side && side->s && L.even && !nyq_rides()) {
+  if (side && side->s.get() && L.even && !nyq_rides()) {
     side->fork_from(s);  // the plane was written by the last-axis pass just enqueued on s
-    sn = side->s;
+    sn = side->s.get();
   }
   axis1(MVN_ST_FWD, work, work_nyq, s, prof, sn);
   axis0(MVN_ST_FWD_MUL_INV, work, work_nyq, spec, spec_nyq, s, prof, sn, nullptr, nullptr, spec_tiled);
@@ -761,17 +738,19 @@ Engine::Engine(int device, const shape_t& dims, int num_views) : Engine(device) 
   if (num_views < 0) throw std::invalid_argument("mvn: num_views must be >= 0");
   be::set_device(device_);
   plan_ = PlanStore::get().add(device_, dims);
-  stream_ = be::stream_create();
+  stream_ = be::Stream::create();
   side_.create();
   const size_t mb = plan_->main_bytes();
-  psi_ = (float*)be::dmalloc(mb);
-  work_ = work_alloc_ = (float*)be::dmalloc(mb);
-  be::dzero(psi_, mb, stream_);
-  be::dzero(work_, mb, stream_);
-  if (plan_->nyq_bytes()) work_nyq_ = (cfloat*)be::dmalloc(plan_->nyq_bytes());
-  poison_own_ = (unsigned*)be::dmalloc(256);  // the words, and at bytes 64 / 128 the tables of the peers' words
-  be::dzero(poison_own_, 256, stream_);
-  poison_ = poison_own_;
+  psi_ = be::DeviceBuffer<float>(mb);
+  work_own_[0] = be::DeviceBuffer<float>(mb);
+  work_ = work_own_[0].get();
+  be::dzero(psi_.get(), mb, stream_.get());
+  be::dzero(work_, mb, stream_.get());
+  if (plan_->nyq_bytes()) work_nyq_own_[0] = be::DeviceBuffer<cfloat>(plan_->nyq_bytes());
+  work_nyq_ = work_nyq_own_[0].get();
+  poison_own_ = be::DeviceBuffer<unsigned>(256);  // the words, and at bytes 64 / 128 the tables of the peers' words
+  be::dzero(poison_own_.get(), 256, stream_.get());
+  poison_ = poison_own_.get();
   views_.resize((size_t)num_views);
   stream_pos_.assign((size_t)num_views, -1);
   want_u16_.assign((size_t)num_views, 0);
@@ -780,7 +759,7 @@ Engine::Engine(int device, const shape_t& dims, int num_views) : Engine(device) 
   d0_stagger_ = env_int("MVN_D0_STAGGER", 64);
   packed_allowed_ = packed_default_ = packed_layout_for(plan_->main_bytes()) && mvn_dim0_packed_possible(dims[0]);
   for (int d = 0; d < 3; ++d) host_dims_[d] = dims[d];
-  be::stream_sync(stream_);
+  be::stream_sync(stream_.get());
 }
 
 // Packed Nyquist layout (mvn_dim0_direct.hpp): MVN_NYQ_PACKED = 1 always / 0 never / unset: for volumes up to
@@ -797,53 +776,9 @@ bool Engine::packed_layout_for(size_t volume_bytes) {
 Engine::~Engine() {
   try {
     be::set_device(device_);
-    if (stream_) be::stream_sync(stream_);
+    if (stream_.get()) be::stream_sync(stream_.get());
   } catch (...) {
   }
-  loop_.release(0, LoopState::N_BUFFERS);
-  for (size_t v = 0; v < views_.size(); ++v) {
-    if (stream_pos_[v] < 0) {  // (a streamed view's pointers are borrowed from the ring during its update)
-      be::dfree(views_[v].image);
-      be::dfree(views_[v].weights);
-    }
-    be::dfree(views_[v].spec1);
-    be::dfree(views_[v].nyq1);
-    be::dfree(views_[v].spec2);
-    be::dfree(views_[v].nyq2);
-    for (int i = 0; i < 2; ++i) {
-      be::dfree(views_[v].taps[i]);
-      be::dfree(views_[v].taps_nyq[i]);
-      be::dfree(views_[v].taps_l[i]);
-    }
-  }
-  be::dfree(taps_scr_);
-  for (size_t r = 0; r < ring_.size(); ++r) {
-    be::dfree(ring_[r].image);
-    be::dfree(ring_[r].weights);
-    if (ring_[r].filled) be::event_destroy(ring_[r].filled);
-    if (ring_[r].freed) be::event_destroy(ring_[r].freed);
-  }
-  be::dfree(psi_);
-  // (work_ and work2_ swap roles at every direct leg: freed by their allocations, not by their roles)
-  be::dfree(work_alloc_);
-  be::dfree(work_nyq_);
-  be::dfree(work2_alloc_);
-  be::dfree(work2_nyq_);
-  be::dfree(psi_spec_);
-  be::dfree(psi_spec_nyq_);
-  be::dfree(embed_scratch_);
-  be::dfree(weights_tab_);
-  if (caller_ev_) be::event_destroy(caller_ev_);
-  be::dfree(poison_own_);
-  be::graph_destroy(sweep_graph_);
-  if (!delta_external_) be::dfree(delta_);
-  if (side_.s) be::drain_quietly(side_.s);
-  side_.destroy();
-  if (upload_stream_) be::drain_quietly(upload_stream_);
-  stage_scratch_.clear();
-  staged_ev_.clear();
-  if (upload_stream_) be::stream_destroy(upload_stream_);
-  if (stream_) be::stream_destroy(stream_);
 }
 
 void Engine::set_embedding(const int dims[3], const int off[3], bool scratch) {
@@ -858,34 +793,32 @@ void Engine::set_embedding(const int dims[3], const int off[3], bool scratch) {
     same = same && host_dims_[d] == dims[d] && host_off_[d] == off[d];
   }
   if (same && embedded_ == !dense) {
-    if (embedded_ && scratch && !embed_scratch_) embed_scratch_ = (float*)be::dmalloc(host_floats() * sizeof(float));
-    if (!scratch && embed_scratch_) {
-      be::stream_sync(stream_);
-      be::dfree(embed_scratch_);
-      embed_scratch_ = nullptr;
+    if (embedded_ && scratch && !embed_scratch_.get()) embed_scratch_ = be::DeviceBuffer<float>(host_floats() * sizeof(float));
+    if (!scratch && embed_scratch_.get()) {
+      be::stream_sync(stream_.get());
+      embed_scratch_.reset();
     }
     return;
   }
-  be::stream_sync(stream_);
+  be::stream_sync(stream_.get());
   // the interior moves: what used to be interior may now be padding and must read zero
   for (size_t v = 0; v < views_.size(); ++v) {
-    if (views_[v].image && stream_pos_[v] < 0) be::dzero(views_[v].image, image_bytes(views_[v].image_u16), stream_);
-    if (views_[v].weights && stream_pos_[v] < 0) be::dzero(views_[v].weights, plan_->main_bytes(), stream_);
+    if (views_[v].image.get()) be::dzero(views_[v].image.get(), image_bytes(views_[v].image_u16), stream_.get());
+    if (views_[v].weights.get()) be::dzero(views_[v].weights.get(), plan_->main_bytes(), stream_.get());
   }
   for (size_t r = 0; r < ring_.size(); ++r) {
-    if (ring_[r].image) be::dzero(ring_[r].image, image_bytes(ring_[r].image_u16), stream_);
-    be::dzero(ring_[r].weights, plan_->main_bytes(), stream_);
+    if (ring_[r].image.get()) be::dzero(ring_[r].image.get(), image_bytes(ring_[r].image_u16), stream_.get());
+    be::dzero(ring_[r].weights.get(), plan_->main_bytes(), stream_.get());
   }
-  be::stream_sync(stream_);
+  be::stream_sync(stream_.get());
   margins_mirrored_ = false;
-  be::dfree(embed_scratch_);
-  embed_scratch_ = nullptr;
+  embed_scratch_.reset();
   for (int d = 0; d < 3; ++d) {
     host_dims_[d] = dims[d];
     host_off_[d] = off[d];
   }
   embedded_ = !dense;
-  if (embedded_ && scratch) embed_scratch_ = (float*)be::dmalloc(host_floats() * sizeof(float));
+  if (embedded_ && scratch) embed_scratch_ = be::DeviceBuffer<float>(host_floats() * sizeof(float));
 }
 
 // ---- stacks in and out (mvn_ingest.hpp) -------------------------------------------------------------
@@ -920,16 +853,16 @@ void Engine::image_storage_counters(long long out[2]) {
 void Engine::set_reflect(bool on) {
   be::set_device(device_);
   if (!on && margins_mirrored_) {  // back to margins of zeros, as set_embedding leaves them
-    be::stream_sync(stream_);
+    be::stream_sync(stream_.get());
     for (size_t v = 0; v < views_.size(); ++v) {
-      if (views_[v].image && stream_pos_[v] < 0) be::dzero(views_[v].image, image_bytes(views_[v].image_u16), stream_);
-      if (views_[v].weights && stream_pos_[v] < 0) be::dzero(views_[v].weights, plan_->main_bytes(), stream_);
+      if (views_[v].image.get()) be::dzero(views_[v].image.get(), image_bytes(views_[v].image_u16), stream_.get());
+      if (views_[v].weights.get()) be::dzero(views_[v].weights.get(), plan_->main_bytes(), stream_.get());
     }
     for (size_t r = 0; r < ring_.size(); ++r) {
-      if (ring_[r].image) be::dzero(ring_[r].image, image_bytes(ring_[r].image_u16), stream_);
-      be::dzero(ring_[r].weights, plan_->main_bytes(), stream_);
+      if (ring_[r].image.get()) be::dzero(ring_[r].image.get(), image_bytes(ring_[r].image_u16), stream_.get());
+      be::dzero(ring_[r].weights.get(), plan_->main_bytes(), stream_.get());
     }
-    be::stream_sync(stream_);
+    be::stream_sync(stream_.get());
     margins_mirrored_ = false;
   }
   reflect_ = on;
@@ -1022,7 +955,7 @@ long long Engine::ingest_pair(float* image_dst, float* weights_dst, const StackR
     if (image_u16) throw std::logic_error("mvn: a resampled image is a float32 volume");
     return resample_pair(image_dst, weights_dst, image, weights, s);
   }
-  float* scr = embed_scratch_;
+  float* scr = embed_scratch_.get();
   bool dirty = false;
   if (!image_u16 && !scr && !image.device && !image.broadcast() && image.u16) {
     // (no embedding, so no scratch: the raw uint16 stack lands in the view's weights volume, which is filled next,
@@ -1031,7 +964,7 @@ long long Engine::ingest_pair(float* image_dst, float* weights_dst, const StackR
     dirty = true;
   }
   long long bytes = ingest_stack(image_dst, image, scr, false, s, image_u16);
-  bytes += ingest_stack(weights_dst, weights, embed_scratch_, dirty, s);
+  bytes += ingest_stack(weights_dst, weights, embed_scratch_.get(), dirty, s);
   return bytes;
 }
 
@@ -1047,7 +980,7 @@ long long Engine::resample_pair(float* image_dst, float* weights_dst, const Stac
   long long bytes = resample_raw(p, image, s);
   mirror_margins(image_dst, false, s);
   // (computed weights are mirrored behind their normalisation: normalize_weights)
-  if (weights.ptr) bytes += ingest_stack(weights_dst, weights, embed_scratch_, false, s);
+  if (weights.ptr) bytes += ingest_stack(weights_dst, weights, embed_scratch_.get(), false, s);
   return bytes;
 }
 
@@ -1101,27 +1034,27 @@ void Engine::normalize_weights() {
   const size_t V = views_.size();
   weights_tab_host_.assign(V, nullptr);
   for (size_t v = 0; v < V; ++v) {
-    if (stream_pos_[v] >= 0 || !views_[v].weights) throw std::logic_error("mvn: normalize_weights needs every view resident and placed");
-    weights_tab_host_[v] = views_[v].weights;
+    if (stream_pos_[v] >= 0 || !views_[v].weights.get()) throw std::logic_error("mvn: normalize_weights needs every view resident and placed");
+    weights_tab_host_[v] = views_[v].weights.get();
   }
-  if (!weights_tab_) weights_tab_ = (float**)be::dmalloc(V * sizeof(float*));
-  be::h2d(weights_tab_, weights_tab_host_.data(), V * sizeof(float*), stream_);
+  if (!weights_tab_.get()) weights_tab_ = be::DeviceBuffer<float*>(V * sizeof(float*));
+  be::h2d(weights_tab_.get(), weights_tab_host_.data(), V * sizeof(float*), stream_.get());
   NormalizeParams p;
-  p.vols = weights_tab_, p.V = (int)V, p.RP = L.RP, p.D1 = L.d1;
+  p.vols = weights_tab_.get(), p.V = (int)V, p.RP = L.RP, p.D1 = L.d1;
   p.n0 = host_dims_[0], p.n1 = host_dims_[1], p.n2 = host_dims_[2];
   p.o0 = host_off_[0], p.o1 = host_off_[1], p.o2 = host_off_[2];
-  be::launch_weights_normalize(p, stream_);
-  for (size_t v = 0; v < V; ++v) mirror_margins(views_[v].weights, false, stream_);
-  be::stream_sync(stream_);
+  be::launch_weights_normalize(p, stream_.get());
+  for (size_t v = 0; v < V; ++v) mirror_margins(views_[v].weights.get(), false, stream_.get());
+  be::stream_sync(stream_.get());
 }
 
 void Engine::wait_for_caller(void* caller_stream) {
   if (!caller_stream) return;
   be::set_device(device_);
-  if (!caller_ev_) caller_ev_ = be::event_create_sync();
-  be::event_record(caller_ev_, (be::stream_t)caller_stream);
-  be::stream_wait_event(stream_, caller_ev_);
-  if (upload_stream_) be::stream_wait_event(upload_stream_, caller_ev_);
+  if (!caller_ev_.get()) caller_ev_ = be::Event::sync_only();
+  be::event_record(caller_ev_.get(), (be::stream_t)caller_stream);
+  be::stream_wait_event(stream_.get(), caller_ev_.get());
+  if (upload_stream_.get()) be::stream_wait_event(upload_stream_.get(), caller_ev_.get());
 }
 
 void Engine::alloc_view(ViewSlot& s) {
@@ -1129,23 +1062,22 @@ void Engine::alloc_view(ViewSlot& s) {
   const size_t v = (size_t)(&s - views_.data());
   if (stream_pos_[v] >= 0) return;  // (streamed views: the ring's slots)
   const bool u16 = want_u16_[v] != 0;
-  if (s.image && s.image_u16 != u16) {  // the slot held the other element type: its image alone is re-allocated
-    be::stream_sync(stream_);
-    be::dfree(s.image);
-    s.image = nullptr;
+  if (s.image.get() && s.image_u16 != u16) {  // the slot held the other element type: its image alone is re-allocated
+    be::stream_sync(stream_.get());
+    s.image.reset();
     ++graph_gen_;
   }
-  const bool new_image = !s.image, new_weights = !s.weights;
+  const bool new_image = !s.image.get(), new_weights = !s.weights.get();
   if (new_image) {
-    s.image = (float*)be::dmalloc(image_bytes(u16));
+    s.image = be::DeviceBuffer<float>(image_bytes(u16));
     s.image_u16 = u16;
   }
-  if (new_weights) s.weights = (float*)be::dmalloc(mb);
+  if (new_weights) s.weights = be::DeviceBuffer<float>(mb);
   // the PSF buffers (3-D spectra or direct-form taps) are allocated by prepare_psf, which knows the form
   if ((new_image || new_weights) && (plan_->L.RP != plan_->L.d2 || embedded_)) {  // odd d2 / embedded stacks: the padding must hold zeros
-    if (new_image) be::dzero(s.image, image_bytes(u16), stream_);
-    if (new_weights) be::dzero(s.weights, mb, stream_);
-    be::stream_sync(stream_);
+    if (new_image) be::dzero(s.image.get(), image_bytes(u16), stream_.get());
+    if (new_weights) be::dzero(s.weights.get(), mb, stream_.get());
+    be::stream_sync(stream_.get());
   }
 }
 
@@ -1210,53 +1142,48 @@ void Engine::prepare_psf(ViewSlot& s, int i, const float* d_kernel, const int* k
     Plan3D* tp = taps_plan(kd);
     if (s.tap_kd[i] != kd) {  // (re)allocate for this depth; the previous arrays may still be read by the stream
       be::stream_sync(st);
-      be::stream_sync(stream_);
-      be::dfree(s.taps[i]);
-      be::dfree(s.taps_nyq[i]);
-      s.taps[i] = nullptr;
-      s.taps_nyq[i] = nullptr;
-      s.taps[i] = (float*)be::dmalloc(tp->main_bytes());
-      if (tp->nyq_bytes()) s.taps_nyq[i] = (cfloat*)be::dmalloc(tp->nyq_bytes());
-      be::dfree(s.taps_l[i]);
-      s.taps_l[i] = nullptr;
+      be::stream_sync(stream_.get());
+      s.tap_kd[i] = 0;  // (none held, should an allocation below fail)
+      s.taps[i].reset();
+      s.taps_nyq[i].reset();
+      s.taps[i] = be::DeviceBuffer<float>(tp->main_bytes());
+      if (tp->nyq_bytes()) s.taps_nyq[i] = be::DeviceBuffer<cfloat>(tp->nyq_bytes());
+      s.taps_l[i].reset();
       s.tap_kd[i] = kd;
     }
     s.taps_l_ok[i] = false;
     s.tap_k[i] = 0;  // not valid until the launches below are enqueued
     // dims 1 and 2 are transformed (un-normalised, both ways), dim0 is not: 1 / (d1 d2)
     const float scale = (float)(1.0 / ((double)L.d1 * (double)L.d2));
-    be::dzero(s.taps[i], tp->main_bytes(), st);
-    be::launch_scatter_psf(d_kernel, kdims[0], kdims[1], kdims[2], s.taps[i], kd, L.d1, L.d2, tp->L.RP, scale, st);
-    tp->rows_r2c(s.taps[i], (cfloat*)s.taps[i], s.taps_nyq[i], st, nullptr);
-    tp->axis1(MVN_ST_FWD, (cfloat*)s.taps[i], s.taps_nyq[i], st, nullptr);
+    be::dzero(s.taps[i].get(), tp->main_bytes(), st);
+    be::launch_scatter_psf(d_kernel, kdims[0], kdims[1], kdims[2], s.taps[i].get(), kd, L.d1, L.d2, tp->L.RP, scale, st);
+    tp->rows_r2c(s.taps[i].get(), (cfloat*)s.taps[i].get(), s.taps_nyq[i].get(), st, nullptr);
+    tp->axis1(MVN_ST_FWD, (cfloat*)s.taps[i].get(), s.taps_nyq[i].get(), st, nullptr);
     if (rule.lines_taps(kdims)) {
       // the same planes for the fused middle pass: line layout, Nyquist bins packed, its own bin order along dim1
       // (wherever the kernel could take the pass: decide_lines() asks whether it is worth it)
-      if (!s.taps_l[i]) s.taps_l[i] = (float*)be::dmalloc(tp->main_bytes());
+      if (!s.taps_l[i].get()) s.taps_l[i] = be::DeviceBuffer<float>(tp->main_bytes());
       if (taps_scr_bytes_ < tp->main_bytes()) {  // one scratch per engine, as large as the deepest tap array
         be::stream_sync(st);
-        be::stream_sync(stream_);
-        be::dfree(taps_scr_);
-        taps_scr_ = nullptr;
+        be::stream_sync(stream_.get());
         taps_scr_bytes_ = 0;
-        taps_scr_ = (float*)be::dmalloc(tp->main_bytes());
+        taps_scr_.reset();
+        taps_scr_ = be::DeviceBuffer<float>(tp->main_bytes());
         taps_scr_bytes_ = tp->main_bytes();
       }
-      be::dzero(taps_scr_, tp->main_bytes(), st);
-      be::launch_scatter_psf(d_kernel, kdims[0], kdims[1], kdims[2], taps_scr_, kd, L.d1, L.d2, tp->L.RP, scale, st);
-      tp->rows_r2c(taps_scr_, (cfloat*)s.taps_l[i], nullptr, st, nullptr, 0, -1, true);
-      tp->taps_to_lines((cfloat*)s.taps_l[i], st);
+      be::dzero(taps_scr_.get(), tp->main_bytes(), st);
+      be::launch_scatter_psf(d_kernel, kdims[0], kdims[1], kdims[2], taps_scr_.get(), kd, L.d1, L.d2, tp->L.RP, scale, st);
+      tp->rows_r2c(taps_scr_.get(), (cfloat*)s.taps_l[i].get(), nullptr, st, nullptr, 0, -1, true);
+      tp->taps_to_lines((cfloat*)s.taps_l[i].get(), st);
       s.taps_l_ok[i] = true;
     }
     s.tap_k[i] = kdims[0];
     return;
   }
   // 3-D spectrum for the fused FFT pass
-  float*& spec = i == 0 ? s.spec1 : s.spec2;
-  cfloat*& nyq = i == 0 ? s.nyq1 : s.nyq2;
-  if (!spec) {
-    spec = (float*)be::dmalloc(plan_->main_bytes());
-    if (plan_->nyq_bytes()) nyq = (cfloat*)be::dmalloc(plan_->nyq_bytes());
+  if (!s.spec[i].get()) {
+    s.spec[i] = be::DeviceBuffer<float>(plan_->main_bytes());
+    if (plan_->nyq_bytes()) s.nyq[i] = be::DeviceBuffer<cfloat>(plan_->nyq_bytes());
   }
   s.tap_k[i] = 0;
   s.taps_l_ok[i] = false;
@@ -1270,13 +1197,15 @@ void Engine::prepare_psf(ViewSlot& s, int i, const float* d_kernel, const int* k
     scratch = stage_spec_scratch_;
   }
   const float scale = (float)(1.0 / (double)L.logical());  // inc/cpu_convolve.h:271-274
-  make_spectrum(d_kernel, kdims, scale, spec, nyq, scratch, st);
+  make_spectrum(d_kernel, kdims, scale, s.spec[i].get(), s.nyq[i].get(), scratch, st);
 }
 
 void Engine::ensure_work2() {
   if (work2_) return;
-  work2_ = work2_alloc_ = (float*)be::dmalloc(plan_->main_bytes());
-  if (plan_->nyq_bytes()) work2_nyq_ = (cfloat*)be::dmalloc(plan_->nyq_bytes());
+  work_own_[1] = be::DeviceBuffer<float>(plan_->main_bytes());
+  if (plan_->nyq_bytes()) work_nyq_own_[1] = be::DeviceBuffer<cfloat>(plan_->nyq_bytes());
+  work2_ = work_own_[1].get();
+  work2_nyq_ = work_nyq_own_[1].get();
 }
 
 // the dim0 leg with the direct form of kernel i: in -> out (never in place).  Packed layout: one launch, the
@@ -1290,7 +1219,7 @@ void Engine::dim0_conv(const ViewSlot& s, int i, const cfloat* in, const cfloat*
   std::memset(&p, 0, sizeof(p));
   p.in = in;
   p.out = out;
-  p.taps = (const cfloat*)s.taps[i];
+  p.taps = (const cfloat*)s.taps[i].get();
   p.d0 = L.d0;
   p.k = s.tap_k[i];
   p.kd = s.tap_kd[i];
@@ -1305,7 +1234,7 @@ void Engine::dim0_conv(const ViewSlot& s, int i, const cfloat* in, const cfloat*
   // non-finite inputs are reported under this leg's epoch (never 0, never a value the word may still hold); the
   // launches of one leg (a slab's interior planes, then those next to its halos) share it
   if (first && ++epoch_ == 0x7fffffffu) {
-    be::dzero(poison_, poison_bytes(), stream_);
+    be::dzero(poison_, poison_bytes(), stream_.get());
     epoch_ = 1;
   }
   armed_epoch_ = epoch_;
@@ -1315,19 +1244,19 @@ void Engine::dim0_conv(const ViewSlot& s, int i, const cfloat* in, const cfloat*
   p.poison_peers = poison_table(epoch_);
   if (packed_) {
     p.packed = 1;
-    p.taps2 = s.taps_nyq[i];
+    p.taps2 = s.taps_nyq[i].get();
     p.inv1 = plan_->ax1.view.inv;
-    ProfScope ps(prof, KK_AXIS0_DIRECT, stream_);
-    be::launch_dim0_direct(p, stream_);
+    ProfScope ps(prof, KK_AXIS0_DIRECT, stream_.get());
+    be::launch_dim0_direct(p, stream_.get());
     return;
   }
   p.in2 = L.even ? in_nyq : nullptr;
   p.out2 = L.even ? out_nyq : nullptr;
-  p.taps2 = L.even ? s.taps_nyq[i] : nullptr;
+  p.taps2 = L.even ? s.taps_nyq[i].get() : nullptr;
   p.plane2 = L.even ? L.d1 : 0;
   p.seg2 = 16;
-  ProfScope ps(prof, KK_AXIS0_DIRECT, stream_);
-  be::launch_dim0_direct(p, stream_);
+  ProfScope ps(prof, KK_AXIS0_DIRECT, stream_.get());
+  be::launch_dim0_direct(p, stream_.get());
 }
 
 void Engine::arm(EpilogueParams& e) {
@@ -1340,42 +1269,41 @@ void Engine::bind_poison(unsigned* external) {
   // (an engine with peers keeps two words of its own, poison_word: a caller-bound word of 4 bytes cannot be one)
   if (external && !poison_peers_.empty()) throw std::logic_error("mvn: bind_poison on an engine with poison peers");
   be::set_device(device_);
-  be::stream_sync(stream_);
-  be::graph_destroy(sweep_graph_);  // a captured sweep holds the word's address
-  sweep_graph_ = nullptr;
-  poison_ = external ? external : poison_own_;
-  be::dzero(poison_own_, sizeof(unsigned), stream_);
-  be::stream_sync(stream_);
+  be::stream_sync(stream_.get());
+  sweep_graph_.reset();  // a captured sweep holds the word's address
+  poison_ = external ? external : poison_own_.get();
+  be::dzero(poison_own_.get(), sizeof(unsigned), stream_.get());
+  be::stream_sync(stream_.get());
 }
 
 unsigned Engine::poison_get() {
   be::set_device(device_);
   unsigned v[2] = {0, 0};
-  be::d2h(v, poison_, poison_bytes(), stream_);
-  be::stream_sync(stream_);
+  be::d2h(v, poison_, poison_bytes(), stream_.get());
+  be::stream_sync(stream_.get());
   return v[0] > v[1] ? v[0] : v[1];  // (with peers: the later report of the two words)
 }
 
 // word = max(word, value): epochs only grow, so the larger one is the later report
 void Engine::poison_merge(unsigned value) {
   if (value > poison_get()) {
-    be::h2d(poison_word(value), &value, sizeof(value), stream_);
-    be::stream_sync(stream_);  // (`value` is a stack variable)
+    be::h2d(poison_word(value), &value, sizeof(value), stream_.get());
+    be::stream_sync(stream_.get());  // (`value` is a stack variable)
   }
 }
 
 void Engine::add_poison_peer(unsigned* word) {
   if (!word) throw std::invalid_argument("mvn: null poison word");
   if ((int)poison_peers_.size() >= MVN_D0_MAX_PEERS) throw std::invalid_argument("mvn: too many poison peers");
-  if (poison_ != poison_own_) throw std::logic_error("mvn: poison peers on an engine with a caller-bound word");
+  if (poison_ != poison_own_.get()) throw std::logic_error("mvn: poison peers on an engine with a caller-bound word");
   be::set_device(device_);
-  be::stream_sync(stream_);
+  be::stream_sync(stream_.get());
   poison_peers_.push_back(word);
   std::vector<unsigned*> odd(poison_peers_);  // the peers' words of the odd epochs (poison_word)
   for (size_t i = 0; i < odd.size(); ++i) ++odd[i];
-  be::h2d(poison_own_ + 16, poison_peers_.data(), poison_peers_.size() * sizeof(unsigned*), stream_);
-  be::h2d(poison_own_ + 32, odd.data(), odd.size() * sizeof(unsigned*), stream_);
-  be::stream_sync(stream_);
+  be::h2d(poison_own_.get() + 16, poison_peers_.data(), poison_peers_.size() * sizeof(unsigned*), stream_.get());
+  be::h2d(poison_own_.get() + 32, odd.data(), odd.size() * sizeof(unsigned*), stream_.get());
+  be::stream_sync(stream_.get());
 }
 
 // every view's two kernels are held in the direct form: the Nyquist bins can ride in the DC column
@@ -1422,12 +1350,12 @@ void Engine::mid_fused_conv(const ViewSlot& s, int i, Profiler* prof, int zbeg, 
   if (!s.taps_l_ok[i] || !s.tap_k[i]) throw std::logic_error("mvn: fused middle pass with a kernel that is not in its form");
   ensure_work2();
   if (++epoch_ == 0x7fffffffu) {
-    be::dzero(poison_, poison_bytes(), stream_);
+    be::dzero(poison_, poison_bytes(), stream_.get());
     epoch_ = 1;
   }
   armed_epoch_ = epoch_;
-  plan_->mid_fused((const cfloat*)work_, (cfloat*)work2_, (const cfloat*)s.taps_l[i], s.tap_k[i], s.tap_kd[i],
-                   poison_word(epoch_), epoch_, stream_, prof, zbeg, zcount, (int)poison_peers_.size(),
+  plan_->mid_fused((const cfloat*)work_, (cfloat*)work2_, (const cfloat*)s.taps_l[i].get(), s.tap_k[i], s.tap_kd[i],
+                   poison_word(epoch_), epoch_, stream_.get(), prof, zbeg, zcount, (int)poison_peers_.size(),
                    poison_table(epoch_));
   std::swap(work_, work2_);
   std::swap(work_nyq_, work2_nyq_);
@@ -1453,7 +1381,7 @@ void Engine::middle(const ViewSlot& s, int i, Profiler* prof, SideStream* side, 
       if (produce && *produce) (*produce)((long)z0 * d1, (long)nz * d1);
     };
     auto call = [&](int what) {
-      if (halo_drain_) be::stream_sync(stream_);
+      if (halo_drain_) be::stream_sync(stream_.get());
       halo_fn_(halo_user_, work_, view, what);
     };
     if (produce && boundary_first()) {
@@ -1470,7 +1398,7 @@ void Engine::middle(const ViewSlot& s, int i, Profiler* prof, SideStream* side, 
     if (halo_post_) call(i + 2);
     return;
   }
-  // One launch chain on stream_ - dim1 forward, direct leg, dim1 inverse, three launches - wherever the Nyquist bins
+  // One launch chain on stream_.get() - dim1 forward, direct leg, dim1 inverse, three launches - wherever the Nyquist bins
   // need no launches of their own: packed into the DC column, or (split layout) riding in the dim1 launches and in
   // the leg's.
   const bool one_chain = packed_ || (s.tap_k[i] != 0 && (!P.L.even || P.nyq_rides()));
@@ -1495,17 +1423,17 @@ void Engine::middle(const ViewSlot& s, int i, Profiler* prof, SideStream* side, 
       // interior and the leg's, not beside the leg's alone
       rows(H, H);
       rows(own, H);
-      P.axis1(MVN_ST_FWD, (cfloat*)work_, wn(), stream_, prof, stream_, H, H);
-      P.axis1(MVN_ST_FWD, (cfloat*)work_, wn(), stream_, nullptr, stream_, own, H);
-      if (halo_drain_) be::stream_sync(stream_);
+      P.axis1(MVN_ST_FWD, (cfloat*)work_, wn(), stream_.get(), prof, stream_.get(), H, H);
+      P.axis1(MVN_ST_FWD, (cfloat*)work_, wn(), stream_.get(), nullptr, stream_.get(), own, H);
+      if (halo_drain_) be::stream_sync(stream_.get());
       halo_fn_(halo_user_, work_, view, i);
       rows(2 * H, own - 2 * H);
-      P.axis1(MVN_ST_FWD, (cfloat*)work_, wn(), stream_, nullptr, stream_, 2 * H, own - 2 * H);
+      P.axis1(MVN_ST_FWD, (cfloat*)work_, wn(), stream_.get(), nullptr, stream_.get(), 2 * H, own - 2 * H);
     } else {
       rows(H, own);
-      P.axis1(MVN_ST_FWD, (cfloat*)work_, wn(), stream_, prof, stream_, H, own);
+      P.axis1(MVN_ST_FWD, (cfloat*)work_, wn(), stream_.get(), prof, stream_.get(), H, own);
       if (halo_fn_) {  // the neighbours' planes arrive in the halo planes of the leg's input
-        if (halo_drain_) be::stream_sync(stream_);
+        if (halo_drain_) be::stream_sync(stream_.get());
         halo_fn_(halo_user_, work_, view, i);
       }
     }
@@ -1516,28 +1444,28 @@ void Engine::middle(const ViewSlot& s, int i, Profiler* prof, SideStream* side, 
     cfloat* out_n = packed_ ? nullptr : work2_nyq_;
     if (H == 0) {
       if (halo_fn_ && halo_split_) {  // (no ranges, e.g. rows that do not end on tile boundaries: one part)
-        if (halo_drain_) be::stream_sync(stream_);
+        if (halo_drain_) be::stream_sync(stream_.get());
         halo_fn_(halo_user_, work_, view, i + 4);
       }
       dim0_conv(s, i, in, in_n, out, out_n, prof);
     } else if (halo_split_ && own > 2 * H) {
       dim0_conv(s, i, in, in_n, out, out_n, prof, 2 * H, own - 2 * H, true);
-      if (halo_drain_) be::stream_sync(stream_);
+      if (halo_drain_) be::stream_sync(stream_.get());
       halo_fn_(halo_user_, work_, view, i + 4);  // the halo planes must be in place behind this call
       dim0_conv(s, i, in, in_n, out, out_n, nullptr, H, H, false);
       dim0_conv(s, i, in, in_n, out, out_n, nullptr, own, H, false);
     } else {
       if (halo_split_) {
-        if (halo_drain_) be::stream_sync(stream_);
+        if (halo_drain_) be::stream_sync(stream_.get());
         halo_fn_(halo_user_, work_, view, i + 4);
       }
       dim0_conv(s, i, in, in_n, out, out_n, prof, H, own, true);
     }
     std::swap(work_, work2_);
     std::swap(work_nyq_, work2_nyq_);
-    P.axis1(MVN_ST_INV, (cfloat*)work_, wn(), stream_, prof, stream_, H, own);
+    P.axis1(MVN_ST_INV, (cfloat*)work_, wn(), stream_.get(), prof, stream_.get(), H, own);
     if (halo_fn_ && halo_post_) {  // the slabs merge their reports of non-finite inputs under the dim1 pass
-      if (halo_drain_) be::stream_sync(stream_);
+      if (halo_drain_) be::stream_sync(stream_.get());
       halo_fn_(halo_user_, work_, view, i + 2);
     }
     return;
@@ -1547,27 +1475,27 @@ void Engine::middle(const ViewSlot& s, int i, Profiler* prof, SideStream* side, 
                            "launches of their own (packed, or riding in the fixed-length dim1 kernels)");
   if (produce && *produce) (*produce)(0, -1);  // (no plane ranges outside halo mode)
   if (!s.tap_k[i]) {
-    P.middle_passes((cfloat*)work_, work_nyq_, (const cfloat*)(i == 0 ? s.spec1 : s.spec2), i == 0 ? s.nyq1 : s.nyq2,
-                    stream_, prof, side, spec_tiled_);
+    P.middle_passes((cfloat*)work_, work_nyq_, (const cfloat*)s.spec[i].get(), s.nyq[i].get(),
+                    stream_.get(), prof, side, spec_tiled_);
     return;
   }
   // The folded dim0 leg needs two fork / join pairs per convolution (17 - 20 us of cross-queue latency each):
   // below 256 MB the Nyquist plane's two dim1 launches cost less in line
   // (256^3 per view update: 0.329 ms with the side stream, 0.312 with the fused FFT pass)
-  const bool use_side = side && side->s && P.L.even && P.main_bytes() > ((size_t)256 << 20) && !P.nyq_rides();
-  be::stream_t sn = use_side ? side->s : stream_;
+  const bool use_side = side && side->s.get() && P.L.even && P.main_bytes() > ((size_t)256 << 20) && !P.nyq_rides();
+  be::stream_t sn = use_side ? side->s.get() : stream_.get();
   // the Nyquist plane's dim1 launches go on the side stream; its dim0 leg rides in the main launch, so the side
   // stream joins before that launch and forks again behind it
-  if (use_side) side->fork_from(stream_);  // the plane was written by the last-axis pass just enqueued on stream_
-  P.axis1(MVN_ST_FWD, (cfloat*)work_, work_nyq_, stream_, prof, sn);
+  if (use_side) side->fork_from(stream_.get());  // the plane was written by the last-axis pass just enqueued on stream_.get()
+  P.axis1(MVN_ST_FWD, (cfloat*)work_, work_nyq_, stream_.get(), prof, sn);
   ensure_work2();
-  if (use_side) side->join_into(stream_);
+  if (use_side) side->join_into(stream_.get());
   dim0_conv(s, i, (const cfloat*)work_, work_nyq_, (cfloat*)work2_, work2_nyq_, prof);
-  if (use_side) side->fork_from(stream_);
+  if (use_side) side->fork_from(stream_.get());
   std::swap(work_, work2_);
   std::swap(work_nyq_, work2_nyq_);
-  P.axis1(MVN_ST_INV, (cfloat*)work_, work_nyq_, stream_, prof, sn);
-  if (use_side) side->join_into(stream_);  // the next last-axis pass on stream_ reads the plane
+  P.axis1(MVN_ST_INV, (cfloat*)work_, work_nyq_, stream_.get(), prof, sn);
+  if (use_side) side->join_into(stream_.get());  // the next last-axis pass on stream_.get() reads the plane
 }
 
 void Engine::set_view(int v, const StackRef& image, const StackRef& weights, const float* kernel1, const int* k1dims,
@@ -1579,9 +1507,9 @@ void Engine::set_view(int v, const StackRef& image, const StackRef& weights, con
   // (halo mode divides row ranges, whose offsets are in floats: the image stays float32 under a hook)
   want_u16_[(size_t)v] = image_storage_ == 1 && image.u16 && !image.broadcast() && !halo_fn_ && !image.geom;
   alloc_view(s);
-  ingest_pair(s.image, s.weights, image, weights, stream_, s.image_u16);
-  be::stream_sync(stream_);  // the sources have been consumed
-  prepare_psfs(s, kernel1, k1dims, kernel2, k2dims, false, stream_);
+  ingest_pair(s.image.get(), s.weights.get(), image, weights, stream_.get(), s.image_u16);
+  be::stream_sync(stream_.get());  // the sources have been consumed
+  prepare_psfs(s, kernel1, k1dims, kernel2, k2dims, false, stream_.get());
   s.set = true;
 }
 
@@ -1616,7 +1544,7 @@ void Engine::reserve_views(const kernel_list_t& kernels) {
   be::set_device(device_);
   for (size_t v = 0; v < views_.size(); ++v) alloc_view(views_[v]);
   if (sw_.direct) ensure_work2();  // (not inside the first sweep: the direct dim0 leg is out of place)
-  if (!upload_stream_) upload_stream_ = be::stream_create_upload();
+  if (!upload_stream_.get()) upload_stream_ = be::Stream::create_upload();
   staged_ev_.resize(views_.size());
   for (size_t v = 0; v < views_.size(); ++v)
     if (!staged_ev_[v].get()) staged_ev_[v] = be::Event::sync_only();
@@ -1640,7 +1568,7 @@ void Engine::ingest_device_view(int v, const StackRef& image, const StackRef& we
   be::set_device(device_);
   ViewSlot& s = views_[(size_t)v];
   if (stream_pos_[(size_t)v] >= 0) throw std::logic_error("mvn: a call with stacks in device memory runs resident");
-  ingest_pair(s.image, s.weights, image, weights, stream_, s.image_u16);
+  ingest_pair(s.image.get(), s.weights.get(), image, weights, stream_.get(), s.image_u16);
   pre_ingested_[(size_t)v] = 1;
 }
 
@@ -1652,9 +1580,9 @@ void Engine::stage_view(int v, const StackRef& image, const StackRef& weights, c
   if (stream_pos_[(size_t)v] >= 0)
     ring_upload(v, image, weights);
   else if (!pre_ingested_[(size_t)v])
-    ingest_pair(s.image, s.weights, image, weights, upload_stream_, s.image_u16);
-  prepare_psfs(s, kernel1, k1dims, kernel2, k2dims, true, upload_stream_);
-  be::event_record(staged_ev_[(size_t)v].get(), upload_stream_);
+    ingest_pair(s.image.get(), s.weights.get(), image, weights, upload_stream_.get(), s.image_u16);
+  prepare_psfs(s, kernel1, k1dims, kernel2, k2dims, true, upload_stream_.get());
+  be::event_record(staged_ev_[(size_t)v].get(), upload_stream_.get());
   s.set = true;
   {
     std::lock_guard<std::mutex> lk(stage_mu_);
@@ -1675,7 +1603,7 @@ void Engine::staging_failed() {
 
 void Engine::finish_staging() {
   be::set_device(device_);
-  if (upload_stream_) be::stream_sync(upload_stream_);
+  if (upload_stream_.get()) be::stream_sync(upload_stream_.get());
   stage_scratch_.clear();
   stage_spec_scratch_ = nullptr;
 }
@@ -1687,7 +1615,7 @@ void Engine::wait_staged(int v) {
   stage_cv_.wait(lk, [&] { return staged_[(size_t)v] != 0; });
   if (staged_[(size_t)v] < 0) throw std::runtime_error("mvn: staging of view " + std::to_string(v) + " failed");
   lk.unlock();
-  be::stream_wait_event(stream_, staged_ev_[(size_t)v].get());
+  be::stream_wait_event(stream_.get(), staged_ev_[(size_t)v].get());
 }
 
 // ---- out-of-core views ---------------------------------------------------------------------------
@@ -1729,36 +1657,33 @@ void Engine::plan_image_types(const std::vector<char>& want) {
   want_u16_ = kept_u16(want, streamed_order_, (int)views_.size());
   if (ring_.empty()) return;
   const bool u16 = want_u16_[(size_t)streamed_order_[0]] != 0;  // (all streamed views, or none)
-  if (ring_[0].image && ring_[0].image_u16 == u16) return;
+  if (ring_[0].image.get() && ring_[0].image_u16 == u16) return;
   alloc_ring_images(u16);
 }
 
 // the ring's image volumes (again): zeroed once, the padded rows and the embedding margins are never written
 void Engine::alloc_ring_images(bool u16) {
-  be::stream_sync(stream_);
+  be::stream_sync(stream_.get());
+  for (RingSlot& r : ring_) r.image.reset();
   for (RingSlot& r : ring_) {
-    be::dfree(r.image);
-    r.image = nullptr;
-  }
-  for (RingSlot& r : ring_) {
-    r.image = (float*)be::dmalloc(image_bytes(u16));
+    r.image = be::DeviceBuffer<float>(image_bytes(u16));
     r.image_u16 = u16;
-    be::dzero(r.image, image_bytes(u16), stream_);
+    be::dzero(r.image.get(), image_bytes(u16), stream_.get());
   }
-  be::stream_sync(stream_);
+  be::stream_sync(stream_.get());
 }
 
 int Engine::u16_views() const {
   int n = 0;
-  for (const ViewSlot& s : views_) n += (s.image && s.image_u16) ? 1 : 0;
+  for (const ViewSlot& s : views_) n += (s.image.get() && s.image_u16) ? 1 : 0;
   return n;
 }
 
-void Engine::divide_epilogue(EpilogueParams& e, const ViewSlot& s) const {
-  e.view = s.image;
+void Engine::divide_epilogue(EpilogueParams& e, const ViewStacks& in) const {
+  e.view = in.image;
   e.mode = MVN_EPI_DIVIDE;
-  if (s.image_u16) {
-    e.view16 = (const unsigned short*)s.image;
+  if (in.image_u16) {
+    e.view16 = (const unsigned short*)in.image;
     e.mode = MVN_EPI_DIVIDE_U16;
     ++g_u16_divides;
   }
@@ -1767,7 +1692,7 @@ void Engine::divide_epilogue(EpilogueParams& e, const ViewSlot& s) const {
 void Engine::set_residency(const std::vector<int>& streamed, int ring) {
   if (!streamed_order_.empty() || !ring_.empty()) throw std::logic_error("mvn: the residency plan is set once");
   for (size_t v = 0; v < views_.size(); ++v)
-    if (views_[v].image) throw std::logic_error("mvn: the residency plan is set before the views are allocated");
+    if (views_[v].image.get()) throw std::logic_error("mvn: the residency plan is set before the views are allocated");
   if (streamed.empty()) {
     if (ring != 0) throw std::invalid_argument("mvn: a ring without streamed views");
     return;
@@ -1785,12 +1710,12 @@ void Engine::set_residency(const std::vector<int>& streamed, int ring) {
   ring_.resize((size_t)ring);
   for (RingSlot& r : ring_) {  // zeroed once: the padded rows and the embedding margins are never written
     // (the image volumes come with the call's image types: plan_image_types)
-    r.weights = (float*)be::dmalloc(mb);
-    be::dzero(r.weights, mb, stream_);
-    r.filled = be::event_create_sync();
-    r.freed = be::event_create_sync();
+    r.weights = be::DeviceBuffer<float>(mb);
+    be::dzero(r.weights.get(), mb, stream_.get());
+    r.filled = be::Event::sync_only();
+    r.freed = be::Event::sync_only();
   }
-  be::stream_sync(stream_);
+  be::stream_sync(stream_.get());
 }
 
 void Engine::ring_upload(int v, const StackRef& image, const StackRef& weights) {
@@ -1805,11 +1730,11 @@ void Engine::ring_upload(int v, const StackRef& image, const StackRef& weights) 
     if (stream_done_) return;  // (the loop stopped early: no later sweep reads this upload)
   }
   RingSlot& r = ring_[(size_t)(k % R)];
-  if (k >= R) be::stream_wait_event(upload_stream_, r.freed);
+  if (k >= R) be::stream_wait_event(upload_stream_.get(), r.freed.get());
   if (image.device || weights.device) throw std::logic_error("mvn: a call with stacks in device memory runs resident");
-  if (!r.image) throw std::logic_error("mvn: the ring has no image volumes (plan_image_types)");
-  g_stream_bytes += ingest_pair(r.image, r.weights, image, weights, upload_stream_, r.image_u16);
-  be::event_record(r.filled, upload_stream_);
+  if (!r.image.get()) throw std::logic_error("mvn: the ring has no image volumes (plan_image_types)");
+  g_stream_bytes += ingest_pair(r.image.get(), r.weights.get(), image, weights, upload_stream_.get(), r.image_u16);
+  be::event_record(r.filled.get(), upload_stream_.get());
   {
     std::lock_guard<std::mutex> lk(stage_mu_);
     ++uploads_;
@@ -1831,7 +1756,7 @@ void Engine::abort_streaming() {
   stage_cv_.notify_all();
 }
 
-void Engine::ring_acquire(ViewSlot& s) {
+ViewStacks Engine::ring_acquire() {
   long k;
   {
     std::unique_lock<std::mutex> lk(stage_mu_);
@@ -1840,18 +1765,15 @@ void Engine::ring_acquire(ViewSlot& s) {
     if (uploads_ <= k) throw std::runtime_error("mvn: upload of a streamed view failed");
   }
   const RingSlot& r = ring_[(size_t)(k % (long)ring_.size())];
-  be::stream_wait_event(stream_, r.filled);
-  s.image = r.image;
-  s.image_u16 = r.image_u16;
-  s.weights = r.weights;
+  be::stream_wait_event(stream_.get(), r.filled.get());
+  return ViewStacks{r.image.get(), r.image_u16, r.weights.get()};
 }
 
 // the view update that reads the pair has been enqueued whole (its last reader is the update pass ending
 // conv_pair): the slot is free behind it
-void Engine::ring_release(ViewSlot& s) {
+void Engine::ring_release() {
   const long k = consumed_;  // (written by this thread only)
-  be::event_record(ring_[(size_t)(k % (long)ring_.size())].freed, stream_);
-  s.image = s.weights = nullptr;
+  be::event_record(ring_[(size_t)(k % (long)ring_.size())].freed.get(), stream_.get());
   ++g_stream_updates;
   {
     std::lock_guard<std::mutex> lk(stage_mu_);
@@ -1892,14 +1814,11 @@ void LoopState::bytes_of(const Layout& L, int V, int iterations, double lambda, 
 
 void LoopState::allocate(const size_t bytes[N_BUFFERS]) {
   for (int b = 0; b < N_BUFFERS; ++b)
-    if (bytes[b] && !buf[b]) buf[b] = be::dmalloc(bytes[b]);
+    if (bytes[b] && !buf[b].get()) buf[b] = be::DeviceBuffer<>(bytes[b]);
 }
 
 void LoopState::release(int first, int last) {
-  for (int b = first; b < last; ++b) {
-    be::dfree(buf[b]);
-    buf[b] = nullptr;
-  }
+  for (int b = first; b < last; ++b) buf[b].reset();
 }
 
 size_t Engine::memory_need(const MemoryQuery& q, const FormRule& rule) {
@@ -1950,7 +1869,7 @@ size_t Engine::memory_need(const MemoryQuery& q, const FormRule& rule) {
   size_t loop[LoopState::N_BUFFERS];  // what the switches of the loop add (Engine::iterate)
   LoopState::bytes_of(L, V, q.iterations, q.lambda, q.loop, loop);
   for (size_t b : loop) add(b, 1);
-  // (psi_spec_ and delta_ belong to the simultaneous steps of the view-sharded drivers: never allocated here)
+  // (psi_spec_.get() and delta_ belong to the simultaneous steps of the view-sharded drivers: never allocated here)
   return total;
 }
 
@@ -1958,8 +1877,8 @@ void Engine::set_psi(const StackRef& st) {
   if (st.u16) throw std::invalid_argument("mvn: psi is float32");
   be::set_device(device_);
   psi_spec_valid_ = false;
-  ingest_stack(psi_, st, embed_scratch_, embedded_, stream_);  // (the loop has written the margins of an embedded psi)
-  be::stream_sync(stream_);
+  ingest_stack(psi_.get(), st, embed_scratch_.get(), embedded_, stream_.get());  // (the loop has written the margins of an embedded psi)
+  be::stream_sync(stream_.get());
 }
 
 void Engine::get_psi(const StackRef& st) {
@@ -1970,42 +1889,42 @@ void Engine::get_psi(const StackRef& st) {
   for (int d = 0; d < 3; ++d)
     if (n[d] > 1 && st.stride[d] <= 0) throw std::invalid_argument("mvn: psi needs positive strides");
   ExtractParams e;
-  e.src = psi_, e.RP = L.RP, e.D1 = L.d1;
+  e.src = psi_.get(), e.RP = L.RP, e.D1 = L.d1;
   e.n0 = n[0], e.n1 = n[1], e.n2 = n[2];
   e.o0 = host_off_[0], e.o1 = host_off_[1], e.o2 = host_off_[2];
   if (st.device) {  // straight into the caller's memory
     e.dst = (float*)st.ptr, e.s0 = st.stride[0], e.s1 = st.stride[1], e.s2 = st.stride[2];
-    be::launch_extract3d(e, stream_);
-    be::stream_sync(stream_);
+    be::launch_extract3d(e, stream_.get());
+    be::stream_sync(stream_.get());
     return;
   }
   check_host_rows(st, n);
-  if (embedded_ && !embed_scratch_) throw std::logic_error("mvn: no scratch for a host stack");
+  if (embedded_ && !embed_scratch_.get()) throw std::logic_error("mvn: no scratch for a host stack");
   const bool dense = (n[1] == 1 || st.stride[1] == n[2]) && (n[0] == 1 || st.stride[0] == (long long)n[1] * n[2]);
-  const char* src = (const char*)psi_;
+  const char* src = (const char*)psi_.get();
   size_t srow = (size_t)L.RP * sizeof(float), splane = (size_t)L.d1 * srow;
   if (embedded_) {  // the window into the scratch first: a strided device copy for dense rows, the extract pass else
     if (dense) {
-      be::launch_copy3d(embed_scratch_, n[2], (long)n[1] * n[2],
-                        psi_ + ((size_t)host_off_[0] * L.d1 + host_off_[1]) * L.RP + host_off_[2], L.RP,
-                        (long)L.d1 * L.RP, n[2], n[1], n[0], stream_);
+      be::launch_copy3d(embed_scratch_.get(), n[2], (long)n[1] * n[2],
+                        psi_.get() + ((size_t)host_off_[0] * L.d1 + host_off_[1]) * L.RP + host_off_[2], L.RP,
+                        (long)L.d1 * L.RP, n[2], n[1], n[0], stream_.get());
     } else {
-      e.dst = embed_scratch_, e.s0 = (long long)n[1] * n[2], e.s1 = n[2], e.s2 = 1;
-      be::launch_extract3d(e, stream_);
+      e.dst = embed_scratch_.get(), e.s0 = (long long)n[1] * n[2], e.s1 = n[2], e.s2 = 1;
+      be::launch_extract3d(e, stream_.get());
     }
-    src = (const char*)embed_scratch_;
+    src = (const char*)embed_scratch_.get();
     srow = (size_t)n[2] * sizeof(float), splane = (size_t)n[1] * srow;
   }
   const size_t width = (size_t)n[2] * sizeof(float);
   if (dense && srow == width)
-    be::d2h((void*)st.ptr, src, host_floats() * sizeof(float), stream_);
+    be::d2h((void*)st.ptr, src, host_floats() * sizeof(float), stream_.get());
   else if (dense)
-    be::d2h_2d((void*)st.ptr, width, src, srow, width, L.rows, stream_);
+    be::d2h_2d((void*)st.ptr, width, src, srow, width, L.rows, stream_.get());
   else
     for (int z = 0; z < n[0]; ++z)
       be::d2h_2d((char*)st.ptr + (long long)z * st.stride[0] * 4, n[1] == 1 ? width : (size_t)st.stride[1] * 4,
-                 src + z * splane, srow, width, (size_t)n[1], stream_);
-  be::stream_sync(stream_);
+                 src + z * splane, srow, width, (size_t)n[1], stream_.get());
+  be::stream_sync(stream_.get());
 }
 
 // one (view, iteration): the reference's steps 1-4, src/gpu_deconvolve_methods.cuh:491-532.
@@ -2013,7 +1932,7 @@ void Engine::get_psi(const StackRef& st) {
 // With a fixed-length plan the two last-axis passes that meet between the convolutions
 // (c2r + divide, then r2c) run as ONE kernel, and so do the update pass and the forward
 // last-axis pass of the NEXT (view, iteration) when `feed_next` is set: 8 full passes instead of 10.
-void Engine::conv_pair(int v, double lambda, float min_value, int final_mode, int accumulate,
+void Engine::conv_pair(int v, const ViewStacks& in, double lambda, float min_value, int final_mode, int accumulate,
                        bool feed_next) {
   const ViewSlot& s = views_[(size_t)v];
   if (!s.set) throw std::runtime_error("mvn: view " + std::to_string(v) + " was never set");
@@ -2026,7 +1945,7 @@ void Engine::conv_pair(int v, double lambda, float min_value, int final_mode, in
   EpilogueParams e1;
   std::memset(&e1, 0, sizeof(e1));
   e1.scale = 1.f;  // 1/N already lives in the PSF spectrum
-  divide_epilogue(e1, s);
+  divide_epilogue(e1, in);
   e1.guard_zero_view = quotient_guard_ ? 1 : 0;
   // noise model: the same pass with the view's background in the forward model and the statistics of the window
   const bool nm = nm_records().on() && final_mode == MVN_EPI_UPDATE;
@@ -2045,15 +1964,15 @@ void Engine::conv_pair(int v, double lambda, float min_value, int final_mode, in
   // multiplies the integral there; lambda is the TV weight and the Tikhonov branch stays off
   const bool tv = tv_volume() && final_mode == MVN_EPI_UPDATE;
   if (tv) {
-    ProfScope ps(prof, KK_TV, stream_);
-    be::launch_tv(tv_params(P.L, psi_, tv_volume(), lambda, loop_.o.epsilon), stream_);
+    ProfScope ps(prof, KK_TV, stream_.get());
+    be::launch_tv(tv_params(P.L, psi_.get(), tv_volume(), lambda, loop_.o.epsilon), stream_.get());
     e2.mode = stats ? MVN_EPI_UPDATE_STATS_TV : MVN_EPI_UPDATE_TV;
     e2.tv = tv_volume();
     lambda = 0.;
   }
   e2.scale = 1.f;
-  e2.psi = psi_;
-  e2.weights = s.weights;
+  e2.psi = psi_.get();
+  e2.weights = in.weights;
   e2.delta = delta_;
   e2.accumulate = accumulate;
   e2.lambda = lambda;
@@ -2072,13 +1991,13 @@ void Engine::conv_pair(int v, double lambda, float min_value, int final_mode, in
   // (work_ / work_nyq_ are read when a producer is BUILT: the direct dim0 leg swaps the two work volumes, and a
   // producer runs before the next leg.)
   const Plan3D* Pp = plan_.get();
-  be::stream_t st = stream_;
+  be::stream_t st = stream_.get();
   RowsProducer p1;
   if (pending_rows_) {  // the previous view update's fused update + forward pass, deferred (boundary-first order)
     p1 = std::move(pending_rows_);
     pending_rows_ = nullptr;
   } else if (!work_has_psi_spectrum_) {
-    const float* psi = psi_;
+    const float* psi = psi_.get();
     cfloat* w = (cfloat*)work_;
     cfloat* wnq = wn();
     const bool ln = lines_;
@@ -2123,7 +2042,7 @@ void Engine::conv_pair(int v, double lambda, float min_value, int final_mode, in
       upd(r0, nr);
     work_has_psi_spectrum_ = true;
   } else {
-    P.rows_c2r((const cfloat*)work_, lines_ ? nullptr : wn(), psi_, e2, stream_, prof, r0, nr, lines_,
+    P.rows_c2r((const cfloat*)work_, lines_ ? nullptr : wn(), psi_.get(), e2, stream_.get(), prof, r0, nr, lines_,
                stats ? &st2 : nullptr);
   }
 }
@@ -2239,11 +2158,10 @@ void Engine::end_streaming() {
 
 void Engine::tv_free() {
   if (!tv_volume()) return;
-  be::stream_sync(stream_);  // (a pass that reads it may still be in flight)
+  be::stream_sync(stream_.get());  // (a pass that reads it may still be in flight)
   // a captured sweep of a TV call holds the volume's address (the pass's store target and the update's operand):
   // it goes with the volume, as in bind_poison, and the key below holds the address as well
-  be::graph_destroy(sweep_graph_);
-  sweep_graph_ = nullptr;
+  sweep_graph_.reset();
   loop_.release(LoopState::TV, LoopState::TV + 1);
 }
 
@@ -2252,7 +2170,7 @@ void Engine::accel_extrapolate(int k, float min_value) {
   const Layout& L = plan_->L;
   AccelParams p;
   std::memset(&p, 0, sizeof(p));
-  p.psi = psi_, p.ysave = loop_.at<float>(LoopState::Y_SAVE), p.g = loop_.at<float>(LoopState::G_PREV);
+  p.psi = psi_.get(), p.ysave = loop_.at<float>(LoopState::Y_SAVE), p.g = loop_.at<float>(LoopState::G_PREV);
   p.xprev = loop_.at<float>(LoopState::X_PREV);
   p.n = (long)L.real_floats();
   p.RP = L.RP, p.d2 = L.d2;
@@ -2261,9 +2179,9 @@ void Engine::accel_extrapolate(int k, float min_value) {
   float* const alpha = loop_.at<float>(LoopState::ALPHA) + (k - 1);
   p.alpha = alpha;
   p.min_value = min_value;
-  be::launch_accel_a(p, stream_);
-  be::launch_accel_reduce(p.rec, LoopState::accel_records(L), alpha, stream_);
-  be::launch_accel_b(p, stream_);
+  be::launch_accel_a(p, stream_.get());
+  be::launch_accel_reduce(p.rec, LoopState::accel_records(L), alpha, stream_.get());
+  be::launch_accel_b(p, stream_.get());
 }
 
 int Engine::iterate(int iterations, double lambda, float min_value, const LoopOptions& o, LoopResult* result) {
@@ -2282,9 +2200,9 @@ int Engine::iterate(int iterations, double lambda, float min_value, const LoopOp
     Engine& e;
     ~CallScope() {
       bool held = false;
-      for (int b = 0; b < LoopState::kKept; ++b) held = held || e.loop_.buf[b];
+      for (int b = 0; b < LoopState::kKept; ++b) held = held || e.loop_.buf[b].get();
       if (!held) return;
-      be::drain_quietly(e.stream_);
+      be::drain_quietly(e.stream_.get());
       e.loop_.release(0, LoopState::kKept);
     }
   } scope{*this};
@@ -2315,7 +2233,7 @@ int Engine::iterate_sweeps(int iterations, double lambda, float min_value) {
                    !nm.on();  // (a captured sweep would bake in the backgrounds and the records' addresses)
   std::vector<double>& rows = last_.rows;  // {S, M, P} of the sweeps run
   int ran = 0;
-  if (accel) be::d2d(loop_.buf[LoopState::Y_SAVE], psi_, plan_->main_bytes(), stream_);  // y_0
+  if (accel) be::d2d(loop_.buf[LoopState::Y_SAVE].get(), psi_.get(), plan_->main_bytes(), stream_.get());  // y_0
   for (int it = 0; it < iterations; ++it) {
     if (use_graph && it == 1) {  // every view has been staged by now: its PSF forms are known
       int swaps = 0;
@@ -2323,31 +2241,30 @@ int Engine::iterate_sweeps(int iterations, double lambda, float min_value) {
       use_graph = swaps % 2 == 0;
     }
     if (use_graph && it >= 1 && it < iterations - 1) {
-      if (sweep_graph_ && (graph_lambda_ != lambda || graph_min_ != min_value ||
+      if (sweep_graph_.get() && (graph_lambda_ != lambda || graph_min_ != min_value ||
                            graph_guard_ != quotient_guard_ || graph_captured_gen_ != graph_gen_ ||
                            graph_reg_kind_ != o.reg_kind || graph_reg_eps_ != o.epsilon ||
                            graph_tv_ != tv_volume() ||
                            graph_work_ != work_)) {
-        be::graph_destroy(sweep_graph_);
-        sweep_graph_ = nullptr;
+        sweep_graph_.reset();
       }
-      if (sweep_graph_) g_u16_divides += u16_views();  // (a replay; the capture below counts through conv_pair)
-      if (!sweep_graph_) {
+      if (sweep_graph_.get()) g_u16_divides += u16_views();  // (a replay; the capture below counts through conv_pair)
+      if (!sweep_graph_.get()) {
         // all views were used by sweep 0, so none is still being staged
         const float* work_at_capture = work_;
-        be::capture_begin(stream_);
+        be::capture_begin(stream_.get());
         try {
           // (a replay reports under the epochs of the capture: the word must not still hold one of them)
-          be::dzero(poison_, poison_bytes(), stream_);
-          for (int v = 0; v < V; ++v) conv_pair(v, lambda, min_value, MVN_EPI_UPDATE, 0, true);
+          be::dzero(poison_, poison_bytes(), stream_.get());
+          for (int v = 0; v < V; ++v) conv_pair(v, views_[(size_t)v].stacks(), lambda, min_value, MVN_EPI_UPDATE, 0, true);
         } catch (...) {
           try {
-            be::graph_destroy(be::capture_end(stream_));
+            be::GraphExec(be::capture_end(stream_.get()));
           } catch (...) {
           }
           throw;
         }
-        sweep_graph_ = be::capture_end(stream_);
+        sweep_graph_.reset(be::capture_end(stream_.get()));
         graph_lambda_ = lambda;
         graph_reg_kind_ = o.reg_kind;
         graph_reg_eps_ = o.epsilon;
@@ -2357,31 +2274,31 @@ int Engine::iterate_sweeps(int iterations, double lambda, float min_value) {
         graph_captured_gen_ = graph_gen_;
         graph_work_ = work_at_capture;  // (the two work volumes swap roles at every direct leg)
       }
-      be::graph_launch(sweep_graph_, stream_);
+      be::graph_launch(sweep_graph_.get(), stream_.get());
       continue;
     }
     for (int v = 0; v < V; ++v) {
       if (pipelined_ && it == 0) wait_staged(v);  // the uploader thread may still be busy with v
       const bool last = (it == iterations - 1) && (v == V - 1);
       const bool streamed = stream_pos_[(size_t)v] >= 0;
-      if (streamed) ring_acquire(views_[(size_t)v]);
+      const ViewStacks in = streamed ? ring_acquire() : views_[(size_t)v].stacks();
       // (acceleration: psi changes between the sweeps, so the last view update leaves no spectrum of it behind
       // and the next sweep starts from rows_r2c of the new psi, as the first sweep of a call does.  Not after
       // sweep 1: y_1 = x_1, psi stays, and so does the fused pass - 2 iterations are the plain loop's launches.
       // The fused pass has written all of psi when pass A reads it: pending_rows_ is only ever set under
       // boundary_first(), which needs a halo hook, and an engine with one refuses acceleration)
-      conv_pair(v, lambda, min_value, MVN_EPI_UPDATE, 0, !last && !(accel && v == V - 1 && it >= 1));
-      if (streamed) ring_release(views_[(size_t)v]);
+      conv_pair(v, in, lambda, min_value, MVN_EPI_UPDATE, 0, !last && !(accel && v == V - 1 && it >= 1));
+      if (streamed) ring_release();
     }
     ran = it + 1;
-    if (nm.on()) be::launch_nm_reduce(nm.rec, nm.count, V, nm.cap, nm.out + 3 * (size_t)V * (size_t)it, stream_);
+    if (nm.on()) be::launch_nm_reduce(nm.rec, nm.count, V, nm.cap, nm.out + 3 * (size_t)V * (size_t)it, stream_.get());
     if (st.on()) {
-      be::launch_convergence_reduce(st.rec, st.count, V, st.cap, st.out + 3 * (size_t)it, stream_);
+      be::launch_convergence_reduce(st.rec, st.count, V, st.cap, st.out + 3 * (size_t)it, stream_.get());
       if (tolerance > 0.) {
         // (no sweep is enqueued ahead: after a stop psi is the estimate of the sweeps run)
         double r[3];
-        be::d2h(r, st.out + 3 * (size_t)it, sizeof(r), stream_);
-        be::stream_sync(stream_);
+        be::d2h(r, st.out + 3 * (size_t)it, sizeof(r), stream_.get());
+        be::stream_sync(stream_.get());
         rows.insert(rows.end(), r, r + 3);
         if (r[0] / r[2] <= tolerance) break;  // (NaN never stops the loop)
       }
@@ -2393,20 +2310,20 @@ int Engine::iterate_sweeps(int iterations, double lambda, float min_value) {
   work_has_psi_spectrum_ = false;
   if (st.on() && tolerance == 0. && ran > 0) {
     rows.resize(3 * (size_t)ran);
-    be::d2h(rows.data(), st.out, rows.size() * sizeof(double), stream_);
-    be::stream_sync(stream_);
+    be::d2h(rows.data(), st.out, rows.size() * sizeof(double), stream_.get());
+    be::stream_sync(stream_.get());
   }
   if (nm.on() && ran > 0) {  // {D, Y, M} per (sweep, view) of the sweeps run
     last_.like.resize(3 * (size_t)V * (size_t)ran);
-    be::d2h(last_.like.data(), nm.out, last_.like.size() * sizeof(double), stream_);
-    be::stream_sync(stream_);
+    be::d2h(last_.like.data(), nm.out, last_.like.size() * sizeof(double), stream_.get());
+    be::stream_sync(stream_.get());
   }
   if (accel) {  // a_1 .. a_ran; the last sweep run was not followed by an extrapolation
     last_.alphas.assign((size_t)ran, 0.);
     if (ran > 1) {
       std::vector<float> a((size_t)ran - 1);
-      be::d2h(a.data(), loop_.buf[LoopState::ALPHA], a.size() * sizeof(float), stream_);
-      be::stream_sync(stream_);
+      be::d2h(a.data(), loop_.buf[LoopState::ALPHA].get(), a.size() * sizeof(float), stream_.get());
+      be::stream_sync(stream_.get());
       for (size_t k = 0; k < a.size(); ++k) last_.alphas[k] = (double)a[k];
     }
   }
@@ -2416,8 +2333,9 @@ int Engine::iterate_sweeps(int iterations, double lambda, float min_value) {
 float* Engine::delta_ptr() {
   if (!delta_) {
     be::set_device(device_);
-    delta_ = (float*)be::dmalloc(plan_->main_bytes());
-    be::dzero(delta_, plan_->main_bytes(), stream_);
+    delta_own_ = be::DeviceBuffer<float>(plan_->main_bytes());
+    delta_ = delta_own_.get();
+    be::dzero(delta_, plan_->main_bytes(), stream_.get());
   }
   return delta_;
 }
@@ -2471,23 +2389,22 @@ void Engine::copy_planes(void* spectrum, int plane0, int nplanes, void* buffer, 
   const size_t n = (size_t)nplanes * pb;
   if (host_buffer) {
     if (to_buffer)
-      be::d2h(buffer, p, n, stream_);
+      be::d2h(buffer, p, n, stream_.get());
     else
-      be::h2d(p, buffer, n, stream_);
+      be::h2d(p, buffer, n, stream_.get());
   } else if (to_buffer) {
-    be::d2d(buffer, p, n, stream_);
+    be::d2d(buffer, p, n, stream_.get());
   } else {
-    be::d2d(p, buffer, n, stream_);
+    be::d2d(p, buffer, n, stream_.get());
   }
-  if (wait) be::stream_sync(stream_);
+  if (wait) be::stream_sync(stream_.get());
 }
 
 void Engine::bind_delta(float* external) {
   be::set_device(device_);
-  be::stream_sync(stream_);
-  if (!delta_external_) be::dfree(delta_);
+  be::stream_sync(stream_.get());
+  delta_own_.reset();
   delta_ = external;
-  delta_external_ = external != nullptr;
 }
 
 // Simultaneous (Jacobi) step.  psi is not touched while the local views are swept, so its
@@ -2550,21 +2467,21 @@ void Engine::compute_delta_head(double lambda, float min_value) {
   // event pairs around every launch cost ~3 % of a sweep: sample like iterate() does
   const int every = prof_.sample_every > 0 ? prof_.sample_every : 1;
   Profiler* prof = (prof_.enabled && (pair_counter_++ % every) == 0) ? &prof_ : nullptr;
-  if (!psi_spec_) {
-    psi_spec_ = (float*)be::dmalloc(P.main_bytes());
-    if (P.nyq_bytes()) psi_spec_nyq_ = (cfloat*)be::dmalloc(P.nyq_bytes());
+  if (!psi_spec_.get()) {
+    psi_spec_ = be::DeviceBuffer<float>(P.main_bytes());
+    if (P.nyq_bytes()) psi_spec_nyq_ = be::DeviceBuffer<cfloat>(P.nyq_bytes());
     psi_spec_valid_ = false;
   }
   const bool fuse = P.can_fuse_rows();
-  const bool use_side = side_.s && P.L.even && P.main_bytes() > kSideMinBytes && !packed_ && !P.nyq_rides();
-  be::stream_t sn = use_side ? side_.s : stream_;
+  const bool use_side = side_.s.get() && P.L.even && P.main_bytes() > kSideMinBytes && !packed_ && !P.nyq_rides();
+  be::stream_t sn = use_side ? side_.s.get() : stream_.get();
   if (!psi_spec_valid_) {  // else: left there chunk by chunk by apply_delta_chunk(.., feed_next)
     if (lines_) {  // line layout: the fused middle pass transforms along dim1 itself
-      P.rows_r2c(psi_, (cfloat*)psi_spec_, nullptr, stream_, prof, 0, -1, true);
+      P.rows_r2c(psi_.get(), (cfloat*)psi_spec_.get(), nullptr, stream_.get(), prof, 0, -1, true);
     } else {
-      P.rows_r2c(psi_, (cfloat*)psi_spec_, pn(), stream_, prof);
-      if (use_side) side_.fork_from(stream_);
-      P.axis1(MVN_ST_FWD, (cfloat*)psi_spec_, pn(), stream_, prof, sn);
+      P.rows_r2c(psi_.get(), (cfloat*)psi_spec_.get(), pn(), stream_.get(), prof);
+      if (use_side) side_.fork_from(stream_.get());
+      P.axis1(MVN_ST_FWD, (cfloat*)psi_spec_.get(), pn(), stream_.get(), prof, sn);
     }
     psi_spec_lines_ = lines_;
   }
@@ -2576,14 +2493,14 @@ void Engine::compute_delta_head(double lambda, float min_value) {
     EpilogueParams e1;
     std::memset(&e1, 0, sizeof(e1));
     e1.scale = 1.f;
-    divide_epilogue(e1, s);
+    divide_epilogue(e1, s.stacks());
     e1.guard_zero_view = quotient_guard_ ? 1 : 0;
     EpilogueParams e2;
     std::memset(&e2, 0, sizeof(e2));
     e2.mode = MVN_EPI_DELTA;
     e2.scale = 1.f;
-    e2.psi = psi_;
-    e2.weights = s.weights;
+    e2.psi = psi_.get();
+    e2.weights = s.weights.get();
     e2.delta = delta_;
     e2.accumulate = v == 0 ? 0 : 1;
     e2.lambda = lambda;
@@ -2593,18 +2510,18 @@ void Engine::compute_delta_head(double lambda, float min_value) {
       // line layout: psi's last-axis spectrum -> ONE middle pass -> fused divide -> ONE middle pass -> correction
       if (!s.taps_l_ok[0] || !s.tap_k[0]) throw std::logic_error("mvn: fused middle pass with a kernel that is not in its form");
       if (++epoch_ == 0x7fffffffu) {
-        be::dzero(poison_, poison_bytes(), stream_);
+        be::dzero(poison_, poison_bytes(), stream_.get());
         epoch_ = 1;
       }
       armed_epoch_ = epoch_;
-      P.mid_fused((const cfloat*)psi_spec_, (cfloat*)work_, (const cfloat*)s.taps_l[0], s.tap_k[0], s.tap_kd[0],
-                  poison_word(epoch_), epoch_, stream_, prof);
+      P.mid_fused((const cfloat*)psi_spec_.get(), (cfloat*)work_, (const cfloat*)s.taps_l[0].get(), s.tap_k[0], s.tap_kd[0],
+                  poison_word(epoch_), epoch_, stream_.get(), prof);
       arm(e1);
-      P.rows_c2r_r2c((cfloat*)work_, nullptr, e1, stream_, prof, 0, -1, true);
+      P.rows_c2r_r2c((cfloat*)work_, nullptr, e1, stream_.get(), prof, 0, -1, true);
       mid_fused_conv(s, 1, prof);
       arm(e2);
       if (v + 1 < V) {
-        P.rows_c2r((const cfloat*)work_, nullptr, psi_, e2, stream_, prof, 0, -1, true);
+        P.rows_c2r((const cfloat*)work_, nullptr, psi_.get(), e2, stream_.get(), prof, 0, -1, true);
       } else {
         tail_epi_ = e2;
         tail_prof_ = prof;
@@ -2617,27 +2534,27 @@ void Engine::compute_delta_head(double lambda, float min_value) {
     // chunk-fed spectrum of psi was written on the main stream)
     if (s.tap_k[0]) {
       // (the shared spectrum of psi may still be in the making on the side stream: v == 0)
-      if (use_side && v == 0) side_.join_into(stream_);
-      dim0_conv(s, 0, (const cfloat*)psi_spec_, pn(), (cfloat*)work_, wn(), prof);
-      if (use_side) side_.fork_from(stream_);
+      if (use_side && v == 0) side_.join_into(stream_.get());
+      dim0_conv(s, 0, (const cfloat*)psi_spec_.get(), pn(), (cfloat*)work_, wn(), prof);
+      if (use_side) side_.fork_from(stream_.get());
     } else {
-      if (use_side) side_.fork_from(stream_);
-      P.axis0(MVN_ST_FWD_MUL_INV, (cfloat*)work_, wn(), (const cfloat*)s.spec1, s.nyq1, stream_, prof, sn,
-              (const cfloat*)psi_spec_, pn(), spec_tiled_);
+      if (use_side) side_.fork_from(stream_.get());
+      P.axis0(MVN_ST_FWD_MUL_INV, (cfloat*)work_, wn(), (const cfloat*)s.spec[0].get(), s.nyq[0].get(), stream_.get(), prof, sn,
+              (const cfloat*)psi_spec_.get(), pn(), spec_tiled_);
     }
-    P.axis1(MVN_ST_INV, (cfloat*)work_, wn(), stream_, prof, sn);
-    if (use_side) side_.join_into(stream_);
+    P.axis1(MVN_ST_INV, (cfloat*)work_, wn(), stream_.get(), prof, sn);
+    if (use_side) side_.join_into(stream_.get());
     arm(e1);
     if (fuse) {
-      P.rows_c2r_r2c((cfloat*)work_, wn(), e1, stream_, prof);
+      P.rows_c2r_r2c((cfloat*)work_, wn(), e1, stream_.get(), prof);
     } else {
-      P.rows_c2r((const cfloat*)work_, wn(), work_, e1, stream_, prof);
-      P.rows_r2c(work_, (cfloat*)work_, wn(), stream_, prof);
+      P.rows_c2r((const cfloat*)work_, wn(), work_, e1, stream_.get(), prof);
+      P.rows_r2c(work_, (cfloat*)work_, wn(), stream_.get(), prof);
     }
     middle(s, 1, prof, use_side ? &side_ : nullptr);
     arm(e2);
     if (v + 1 < V) {
-      P.rows_c2r((const cfloat*)work_, wn(), psi_, e2, stream_, prof);
+      P.rows_c2r((const cfloat*)work_, wn(), psi_.get(), e2, stream_.get(), prof);
     } else {  // the last view's final pass is launched chunk by chunk (compute_delta_chunk)
       tail_epi_ = e2;
       tail_prof_ = prof;
@@ -2654,11 +2571,11 @@ void Engine::compute_delta_chunk(int c, int n) {
   if (views_.empty()) {
     size_t off = 0, cnt = 0;
     delta_chunk_range(c, n, &off, &cnt);
-    be::dzero(delta_ptr() + off, cnt * sizeof(float), stream_);
+    be::dzero(delta_ptr() + off, cnt * sizeof(float), stream_.get());
     return;
   }
   if (!tail_pending_) throw std::logic_error("mvn: compute_delta_chunk without compute_delta_head");
-  plan_->rows_c2r((const cfloat*)work_, lines_ ? nullptr : wn(), psi_, tail_epi_, stream_, c == 0 ? tail_prof_ : nullptr,
+  plan_->rows_c2r((const cfloat*)work_, lines_ ? nullptr : wn(), psi_.get(), tail_epi_, stream_.get(), c == 0 ? tail_prof_ : nullptr,
                   (long)z0 * L.d1, (long)nz * L.d1, lines_);
   if (c == n - 1) tail_pending_ = false;
 }
@@ -2676,18 +2593,18 @@ void Engine::apply_delta_chunk(int c, int n, bool feed_next) {
     fed_n_ = n;
     fed_ = 0;
   }
-  be::launch_axpy1(psi_ + off, delta_ptr() + off, cnt, stream_);
+  be::launch_axpy1(psi_.get() + off, delta_ptr() + off, cnt, stream_.get());
   if (feed_next && !views_.empty()) {
-    if (!psi_spec_) {
-      psi_spec_ = (float*)be::dmalloc(P.main_bytes());
-      if (P.nyq_bytes()) psi_spec_nyq_ = (cfloat*)be::dmalloc(P.nyq_bytes());
+    if (!psi_spec_.get()) {
+      psi_spec_ = be::DeviceBuffer<float>(P.main_bytes());
+      if (P.nyq_bytes()) psi_spec_nyq_ = be::DeviceBuffer<cfloat>(P.nyq_bytes());
     }
     if (lines_) {  // (the layout of the step this correction belongs to; the next head checks it against its own)
-      P.rows_r2c(psi_, (cfloat*)psi_spec_, nullptr, stream_, nullptr, (long)z0 * P.L.d1, (long)nz * P.L.d1, true);
+      P.rows_r2c(psi_.get(), (cfloat*)psi_spec_.get(), nullptr, stream_.get(), nullptr, (long)z0 * P.L.d1, (long)nz * P.L.d1, true);
     } else {
-      P.rows_r2c(psi_, (cfloat*)psi_spec_, pn(), stream_, nullptr, (long)z0 * P.L.d1,
+      P.rows_r2c(psi_.get(), (cfloat*)psi_spec_.get(), pn(), stream_.get(), nullptr, (long)z0 * P.L.d1,
                  (long)nz * P.L.d1);
-      P.axis1(MVN_ST_FWD, (cfloat*)psi_spec_, pn(), stream_, nullptr, stream_, z0, nz);
+      P.axis1(MVN_ST_FWD, (cfloat*)psi_spec_.get(), pn(), stream_.get(), nullptr, stream_.get(), z0, nz);
     }
     psi_spec_lines_ = lines_;
     if (++fed_ == n) {  // every plane of the spectrum belongs to the new psi
@@ -2702,12 +2619,12 @@ void Engine::apply_delta_chunk(int c, int n, bool feed_next) {
 void Engine::apply_delta() {
   be::set_device(device_);
   psi_spec_valid_ = false;
-  be::launch_axpy1(psi_, delta_ptr(), plan_->L.real_floats(), stream_);
+  be::launch_axpy1(psi_.get(), delta_ptr(), plan_->L.real_floats(), stream_.get());
 }
 
 void Engine::sync() {
   be::set_device(device_);
-  be::stream_sync(stream_);
+  be::stream_sync(stream_.get());
   prof_.collect();
 }
 
@@ -2726,54 +2643,38 @@ SlabEngine::SlabEngine(int device, const shape_t& dims, int nranks, int rank, in
   shape_t b = {{dims[0], dims[1] / nranks, dims[2]}};
   planA_ = PlanStore::get().add(device_, a);
   planB_ = PlanStore::get().add(device_, b);
-  stream_ = be::stream_create();
+  stream_ = be::Stream::create();
   const size_t mb = planA_->main_bytes(), nb = planA_->nyq_bytes();
-  psi_ = (float*)be::dmalloc(mb);
-  work_ = (float*)be::dmalloc(mb);
-  own_a_ = (float*)be::dmalloc(mb);
-  own_b_ = (float*)be::dmalloc(mb);
-  be::dzero(psi_, mb, stream_);
-  be::dzero(work_, mb, stream_);
+  psi_ = be::DeviceBuffer<float>(mb);
+  work_ = be::DeviceBuffer<float>(mb);
+  own_a_ = be::DeviceBuffer<float>(mb);
+  own_b_ = be::DeviceBuffer<float>(mb);
+  be::dzero(psi_.get(), mb, stream_.get());
+  be::dzero(work_.get(), mb, stream_.get());
   if (nb) {
-    work_nyq_ = (cfloat*)be::dmalloc(nb);
-    own_an_ = (cfloat*)be::dmalloc(nb);
-    own_bn_ = (cfloat*)be::dmalloc(nb);
+    work_nyq_ = be::DeviceBuffer<cfloat>(nb);
+    own_an_ = be::DeviceBuffer<cfloat>(nb);
+    own_bn_ = be::DeviceBuffer<cfloat>(nb);
   }
-  a_main_ = own_a_;
-  b_main_ = own_b_;
-  a_nyq_ = own_an_;
-  b_nyq_ = own_bn_;
+  a_main_ = own_a_.get();
+  b_main_ = own_b_.get();
+  a_nyq_ = own_an_.get();
+  b_nyq_ = own_bn_.get();
   views_.resize((size_t)num_views);
-  be::stream_sync(stream_);
+  be::stream_sync(stream_.get());
 }
 
 SlabEngine::~SlabEngine() {
   try {
     be::set_device(device_);
-    if (stream_) be::stream_sync(stream_);
+    if (stream_.get()) be::stream_sync(stream_.get());
   } catch (...) {
   }
-  for (size_t v = 0; v < views_.size(); ++v) {
-    be::dfree(views_[v].image);
-    be::dfree(views_[v].weights);
-    for (int i = 0; i < 2; ++i) {
-      be::dfree(views_[v].spec[i]);
-      be::dfree(views_[v].nyq[i]);
-    }
-  }
-  be::dfree(psi_);
-  be::dfree(work_);
-  be::dfree(work_nyq_);
-  be::dfree(own_a_);
-  be::dfree(own_b_);
-  be::dfree(own_an_);
-  be::dfree(own_bn_);
-  if (stream_) be::stream_destroy(stream_);
 }
 
 void SlabEngine::sync() {
   be::set_device(device_);
-  be::stream_sync(stream_);
+  be::stream_sync(stream_.get());
 }
 
 void SlabEngine::bind_buffers(float* a_main, float* b_main, float* a_nyq, float* b_nyq) {
@@ -2788,38 +2689,36 @@ void SlabEngine::bind_buffers(float* a_main, float* b_main, float* a_nyq, float*
     b_main_ = b_main;
     a_nyq_ = (cfloat*)a_nyq;
     b_nyq_ = (cfloat*)b_nyq;
-    external_ = true;
   } else {
-    a_main_ = own_a_;
-    b_main_ = own_b_;
-    a_nyq_ = own_an_;
-    b_nyq_ = own_bn_;
-    external_ = false;
+    a_main_ = own_a_.get();
+    b_main_ = own_b_.get();
+    a_nyq_ = own_an_.get();
+    b_nyq_ = own_bn_.get();
   }
 }
 
 void SlabEngine::upload_slab(float* dst, const float* host) {
   const Layout& L = planA_->L;
   if (L.RP == L.d2)
-    be::h2d(dst, host, L.logical() * sizeof(float), stream_);
+    be::h2d(dst, host, L.logical() * sizeof(float), stream_.get());
   else
     be::h2d_2d(dst, (size_t)L.RP * sizeof(float), host, (size_t)L.d2 * sizeof(float),
-               (size_t)L.d2 * sizeof(float), L.rows, stream_);
+               (size_t)L.d2 * sizeof(float), L.rows, stream_.get());
 }
 
 void SlabEngine::set_psi(const float* host) {
   be::set_device(device_);
-  if (planA_->L.RP != planA_->L.d2) be::dzero(psi_, planA_->main_bytes(), stream_);
-  upload_slab(psi_, host);
-  be::stream_sync(stream_);
+  if (planA_->L.RP != planA_->L.d2) be::dzero(psi_.get(), planA_->main_bytes(), stream_.get());
+  upload_slab(psi_.get(), host);
+  be::stream_sync(stream_.get());
   work_has_psi_spectrum_ = false;
 }
 
 void SlabEngine::get_psi(float* host) {
   be::set_device(device_);
   const Layout& L = planA_->L;
-  be::d2h_2d(host, (size_t)L.d2 * 4, psi_, (size_t)L.RP * 4, (size_t)L.d2 * 4, L.rows, stream_);
-  be::stream_sync(stream_);
+  be::d2h_2d(host, (size_t)L.d2 * 4, psi_.get(), (size_t)L.RP * 4, (size_t)L.d2 * 4, L.rows, stream_.get());
+  be::stream_sync(stream_.get());
 }
 
 void SlabEngine::set_view(int v, const float* image, const float* weights, const float* kernel1,
@@ -2829,20 +2728,20 @@ void SlabEngine::set_view(int v, const float* image, const float* weights, const
   SlabView& s = views_[(size_t)v];
   const size_t mb = planA_->main_bytes();
   const size_t nbT = planB_->nyq_bytes();
-  if (!s.image) {
-    s.image = (float*)be::dmalloc(mb);
-    s.weights = (float*)be::dmalloc(mb);
+  if (!s.image.get()) {
+    s.image = be::DeviceBuffer<float>(mb);
+    s.weights = be::DeviceBuffer<float>(mb);
     for (int i = 0; i < 2; ++i) {
-      s.spec[i] = (float*)be::dmalloc(planB_->main_bytes());
-      if (nbT) s.nyq[i] = (cfloat*)be::dmalloc(nbT);
+      s.spec[i] = be::DeviceBuffer<float>(planB_->main_bytes());
+      if (nbT) s.nyq[i] = be::DeviceBuffer<cfloat>(nbT);
     }
     if (planA_->L.RP != planA_->L.d2) {
-      be::dzero(s.image, mb, stream_);
-      be::dzero(s.weights, mb, stream_);
+      be::dzero(s.image.get(), mb, stream_.get());
+      be::dzero(s.weights.get(), mb, stream_.get());
     }
   }
-  upload_slab(s.image, image);
-  upload_slab(s.weights, weights);
+  upload_slab(s.image.get(), image);
+  upload_slab(s.weights.get(), weights);
   // PSF spectra: the whole 3-D spectrum is formed locally (three passes on a temporary full
   // volume) and this rank's dim1 block cut out of it -- position order along dim1 is the same in
   // the full and in the decomposed transform, so the block is what a decomposed forward
@@ -2860,19 +2759,19 @@ void SlabEngine::set_view(int v, const float* image, const float* weights, const
     for (int i = 0; i < 2; ++i) {
       const size_t kb = sizeof(float) * (size_t)kd[i][0] * (size_t)kd[i][1] * (size_t)kd[i][2];
       dk = be::DeviceBuffer<float>(kb);
-      be::h2d(dk.get(), ks[i], kb, stream_);
-      full->psf_spectrum(dk.get(), kd[i], scale, fspec.get(), fnyq.get(), stream_);
+      be::h2d(dk.get(), ks[i], kb, stream_.get());
+      full->psf_spectrum(dk.get(), kd[i], scale, fspec.get(), fnyq.get(), stream_.get());
       const size_t wrow = yb * (size_t)F.C * sizeof(cfloat);
-      be::d2d_2d(s.spec[i], wrow, (const cfloat*)fspec.get() + (size_t)rank_ * yb * F.C,
-                 (size_t)F.d1 * F.C * sizeof(cfloat), wrow, (size_t)F.d0, stream_);
+      be::d2d_2d(s.spec[i].get(), wrow, (const cfloat*)fspec.get() + (size_t)rank_ * yb * F.C,
+                 (size_t)F.d1 * F.C * sizeof(cfloat), wrow, (size_t)F.d0, stream_.get());
       if (fnyq.get())
-        be::d2d_2d(s.nyq[i], yb * sizeof(cfloat), fnyq.get() + (size_t)rank_ * yb,
-                   (size_t)F.d1 * sizeof(cfloat), yb * sizeof(cfloat), (size_t)F.d0, stream_);
-      be::stream_sync(stream_);
+        be::d2d_2d(s.nyq[i].get(), yb * sizeof(cfloat), fnyq.get() + (size_t)rank_ * yb,
+                   (size_t)F.d1 * sizeof(cfloat), yb * sizeof(cfloat), (size_t)F.d0, stream_.get());
+      be::stream_sync(stream_.get());
       dk.reset();
     }
   } catch (...) {
-    be::drain_quietly(stream_);  // the engine's stream outlives the three temporaries
+    be::drain_quietly(stream_.get());  // the engine's stream outlives the three temporaries
     throw;
   }
   s.set = true;
@@ -2888,29 +2787,29 @@ void SlabEngine::step_pack(int v, int conv) {
   if (!views_.at((size_t)v).set) throw std::runtime_error("mvn: view " + std::to_string(v) + " was never set");
   const Plan3D& A = *planA_;
   const Layout& L = A.L;
-  cfloat* W = (cfloat*)work_;
+  cfloat* W = (cfloat*)work_.get();
   if (conv == 0) {
-    if (!work_has_psi_spectrum_) A.rows_r2c(psi_, W, work_nyq_, stream_);
+    if (!work_has_psi_spectrum_) A.rows_r2c(psi_.get(), W, work_nyq_.get(), stream_.get());
     work_has_psi_spectrum_ = false;
   }
-  A.axis1(MVN_ST_FWD, W, work_nyq_, stream_);
+  A.axis1(MVN_ST_FWD, W, work_nyq_.get(), stream_.get());
   const size_t yb = (size_t)(L.d1 / P_);
   const size_t wrow = yb * (size_t)L.C * sizeof(cfloat);
   const size_t blk = (size_t)L.d0 * yb * L.C;  // cfloats per destination rank
   for (int j = 0; j < P_; ++j) {
     be::d2d_2d((cfloat*)a_main_ + (size_t)j * blk, wrow, W + (size_t)j * yb * L.C,
-               (size_t)L.d1 * L.C * sizeof(cfloat), wrow, (size_t)L.d0, stream_);
-    if (work_nyq_)
-      be::d2d_2d(a_nyq_ + (size_t)j * L.d0 * yb, yb * sizeof(cfloat), work_nyq_ + (size_t)j * yb,
-                 (size_t)L.d1 * sizeof(cfloat), yb * sizeof(cfloat), (size_t)L.d0, stream_);
+               (size_t)L.d1 * L.C * sizeof(cfloat), wrow, (size_t)L.d0, stream_.get());
+    if (work_nyq_.get())
+      be::d2d_2d(a_nyq_ + (size_t)j * L.d0 * yb, yb * sizeof(cfloat), work_nyq_.get() + (size_t)j * yb,
+                 (size_t)L.d1 * sizeof(cfloat), yb * sizeof(cfloat), (size_t)L.d0, stream_.get());
   }
 }
 
 void SlabEngine::step_mid(int v, int conv) {
   be::set_device(device_);
   const SlabView& s = views_.at((size_t)v);
-  planB_->axis0(MVN_ST_FWD_MUL_INV, (cfloat*)b_main_, b_nyq_, (const cfloat*)s.spec[conv],
-                s.nyq[conv], stream_);
+  planB_->axis0(MVN_ST_FWD_MUL_INV, (cfloat*)b_main_, b_nyq_, (const cfloat*)s.spec[conv].get(),
+                s.nyq[conv].get(), stream_.get());
 }
 
 void SlabEngine::step_unpack(int v, int conv, double lambda, float min_value, bool feed_next) {
@@ -2918,43 +2817,43 @@ void SlabEngine::step_unpack(int v, int conv, double lambda, float min_value, bo
   const SlabView& s = views_.at((size_t)v);
   const Plan3D& A = *planA_;
   const Layout& L = A.L;
-  cfloat* W = (cfloat*)work_;
+  cfloat* W = (cfloat*)work_.get();
   const size_t yb = (size_t)(L.d1 / P_);
   const size_t wrow = yb * (size_t)L.C * sizeof(cfloat);
   const size_t blk = (size_t)L.d0 * yb * L.C;
   for (int j = 0; j < P_; ++j) {
     be::d2d_2d(W + (size_t)j * yb * L.C, (size_t)L.d1 * L.C * sizeof(cfloat),
-               (const cfloat*)a_main_ + (size_t)j * blk, wrow, wrow, (size_t)L.d0, stream_);
-    if (work_nyq_)
-      be::d2d_2d(work_nyq_ + (size_t)j * yb, (size_t)L.d1 * sizeof(cfloat),
+               (const cfloat*)a_main_ + (size_t)j * blk, wrow, wrow, (size_t)L.d0, stream_.get());
+    if (work_nyq_.get())
+      be::d2d_2d(work_nyq_.get() + (size_t)j * yb, (size_t)L.d1 * sizeof(cfloat),
                  a_nyq_ + (size_t)j * L.d0 * yb, yb * sizeof(cfloat), yb * sizeof(cfloat),
-                 (size_t)L.d0, stream_);
+                 (size_t)L.d0, stream_.get());
   }
-  A.axis1(MVN_ST_INV, W, work_nyq_, stream_);
+  A.axis1(MVN_ST_INV, W, work_nyq_.get(), stream_.get());
   EpilogueParams e;
   std::memset(&e, 0, sizeof(e));
   e.scale = 1.f;  // 1/N lives in the PSF spectra
   if (conv == 0) {
     e.mode = MVN_EPI_DIVIDE;
-    e.view = s.image;
+    e.view = s.image.get();
     if (A.can_fuse_rows()) {
-      A.rows_c2r_r2c(W, work_nyq_, e, stream_);
+      A.rows_c2r_r2c(W, work_nyq_.get(), e, stream_.get());
     } else {
-      A.rows_c2r(W, work_nyq_, work_, e, stream_);
-      A.rows_r2c(work_, W, work_nyq_, stream_);
+      A.rows_c2r(W, work_nyq_.get(), work_.get(), e, stream_.get());
+      A.rows_r2c(work_.get(), W, work_nyq_.get(), stream_.get());
     }
   } else {
     e.mode = MVN_EPI_UPDATE;
-    e.psi = psi_;
-    e.weights = s.weights;
+    e.psi = psi_.get();
+    e.weights = s.weights.get();
     e.lambda = lambda;
     e.lambda_inv = lambda > 0 ? (float)(1.f / lambda) : 0.f;
     e.min_value = min_value;
     if (A.can_fuse_rows() && feed_next) {
-      A.rows_c2r_r2c(W, work_nyq_, e, stream_);
+      A.rows_c2r_r2c(W, work_nyq_.get(), e, stream_.get());
       work_has_psi_spectrum_ = true;
     } else {
-      A.rows_c2r(W, work_nyq_, psi_, e, stream_);
+      A.rows_c2r(W, work_nyq_.get(), psi_.get(), e, stream_.get());
     }
   }
 }

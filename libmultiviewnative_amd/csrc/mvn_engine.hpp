@@ -59,26 +59,19 @@ class Profiler {
  private:
   struct Rec {
     int kind;
-    be::event_t a, b;
+    be::Event a, b;
   };
   std::vector<Rec> recs_;
-  std::vector<be::event_t> pool_;
-  be::event_t get_event();
+  std::vector<be::Event> pool_;
+  be::Event get_event();
 };
 
 struct DevAxis {
   AxisPlanHost host;
-  cfloat* tw = nullptr;
-  cfloat* tws = nullptr;
-  cfloat* chirp = nullptr;  // bluestein axes only
-  cfloat* bhat = nullptr;
-  int* rev = nullptr;
-  int* inv = nullptr;
-  AxisPlan view;
+  be::DeviceBuffer<cfloat> tw, tws, chirp, bhat;  // (chirp, bhat: bluestein axes only)
+  be::DeviceBuffer<int> rev, inv;
+  AxisPlan view;  // the tables above, as the kernels take them
   explicit DevAxis(int n, bool composite = false);
-  ~DevAxis();
-  DevAxis(const DevAxis&) = delete;
-  DevAxis& operator=(const DevAxis&) = delete;
 };
 
 struct PassGeom {
@@ -147,10 +140,9 @@ struct FormRule {
 
 // a second stream plus the two events used to fork it from / join it to the main stream
 struct SideStream {
-  be::stream_t s = nullptr;
-  be::event_t fork = nullptr, join = nullptr;
+  be::Event fork, join;
+  be::Stream s;
   void create();
-  void destroy();
   // side stream waits for everything enqueued on `main` so far / `main` waits for the side stream
   void fork_from(be::stream_t main);
   void join_into(be::stream_t main);
@@ -162,8 +154,8 @@ class Plan3D {
   const Layout L;
   const bool fixed;  // built with the fixed-length kernels allowed (FormSwitches::fixed)
   DevAxis ax2, ax1, ax0;
-  cfloat* twr = nullptr;  // d2-th roots of unity (even d2)
-  unsigned* no_poison = nullptr;  // a zero word: what EpilogueParams::poison points to after an FFT dim0 leg
+  be::DeviceBuffer<cfloat> twr;  // d2-th roots of unity (even d2)
+  be::DeviceBuffer<unsigned> no_poison;  // a zero word: what EpilogueParams::poison points to after an FFT dim0 leg
   PassGeom g_rows, g_ax1, g_ax0, g_nyq1, g_nyq0, g_nyq1_line;
   // compile-time specialised kernels (mvn_fixed.hpp) are used where the shape allows
   bool fx_rows = false, fx_ax1 = false, fx_ax0 = false;
@@ -173,7 +165,6 @@ class Plan3D {
   PassGeom gx_rows, gx_ax1, gx_ax0;
 
   Plan3D(int device, int d0, int d1, int d2, bool fixed);
-  ~Plan3D();
 
   size_t main_bytes() const { return L.real_floats() * sizeof(float); }
   size_t nyq_bytes() const { return L.nyq_cplx() * sizeof(cfloat); }
@@ -270,29 +261,37 @@ class PlanStore {
   std::map<std::array<int, 4>, std::shared_ptr<Plan3D>> plans_;
 };
 
+// The stacks a view update reads, not owned: a resident view's own volumes (ViewSlot::stacks), or the ring slot the
+// pair of a streamed view has landed in (Engine::ring_acquire).
+struct ViewStacks {
+  float* image;  // image_u16: a uint16 volume (the same element grid at 2 bytes per voxel) behind this pointer
+  bool image_u16;
+  float* weights;
+};
+
 struct ViewSlot {
-  float* image = nullptr;   // image_u16: a uint16 volume (the same element grid at 2 bytes per voxel) behind this pointer
+  // image and weights of a RESIDENT view; a streamed view never holds any (its stacks pass through the ring)
+  be::DeviceBuffer<float> image;
   bool image_u16 = false;
-  float* weights = nullptr;
-  float* spec1 = nullptr;  // main array of the kernel1 spectrum (pre-scaled by 1/N)
-  cfloat* nyq1 = nullptr;
-  float* spec2 = nullptr;
-  cfloat* nyq2 = nullptr;
+  be::DeviceBuffer<float> weights;
+  ViewStacks stacks() const { return ViewStacks{image.get(), image_u16, weights.get()}; }
+  be::DeviceBuffer<float> spec[2];  // main array of the spectrum of kernel i (pre-scaled by 1/N)
+  be::DeviceBuffer<cfloat> nyq[2];
   bool set = false;
-  // host copies of the kernels whose spectra spec1 / spec2 currently hold: a later call that
+  // host copies of the kernels whose spectra spec[0] / spec[1] currently hold: a later call that
   // brings the same PSF for this slot (Fiji's block-after-block calls do) skips the preparation
   std::vector<float> kcopy[2];
   int kdims[2][3] = {{0, 0, 0}, {0, 0, 0}};
   // direct dim0 form of kernel i (mvn_dim0_direct.hpp): its planes after the last-axis and dim1
   // transforms, [tap_kd][d1][C] (+ Nyquist [tap_kd][d1]), pre-scaled by 1 / (d1 d2).  tap_k = PSF planes
   // when this form is what the slot holds for kernel i, 0 when the 3-D spectrum (spec / nyq) is.
-  float* taps[2] = {nullptr, nullptr};
-  cfloat* taps_nyq[2] = {nullptr, nullptr};
+  be::DeviceBuffer<float> taps[2];
+  be::DeviceBuffer<cfloat> taps_nyq[2];
   int tap_k[2] = {0, 0};
   int tap_kd[2] = {0, 0};
   // the same PSF planes for the fused middle pass (mvn_mid_fused.hpp): [tap_kd][C][d1], Nyquist bins packed, bins
   // along dim1 in that pass's own order.  taps_l_ok: valid for the kernel tap_k / tap_kd describe.
-  float* taps_l[2] = {nullptr, nullptr};
+  be::DeviceBuffer<float> taps_l[2];
   bool taps_l_ok[2] = {false, false};
 };
 
@@ -376,7 +375,7 @@ struct LoopState {
     N_BUFFERS,
     kKept = TV
   };
-  void* buf[N_BUFFERS] = {};
+  be::DeviceBuffer<> buf[N_BUFFERS];
   LoopOptions o;  // of the running iterate()
   static void bytes_of(const Layout& L, int V, int iterations, double lambda, const LoopOptions& o,
                        size_t bytes[N_BUFFERS]);
@@ -385,7 +384,7 @@ struct LoopState {
   // workgroups of the extrapolation's pass A (mvn_extrapolate.hpp): a function of the extents only
   static long accel_records(const Layout& L) { return mvn_accel_blocks((long)L.real_floats(), L.RP == L.d2 ? 4 : 2); }
   template <typename T>
-  T* at(Buffer b) const { return (T*)buf[b]; }
+  T* at(Buffer b) const { return (T*)buf[b].get(); }
   RecordSet records(Buffer first, const Layout& L) const {
     RecordSet r;
     r.rec = at<double>(first), r.count = at<unsigned>((Buffer)(first + 1)), r.out = at<double>((Buffer)(first + 2));
@@ -455,7 +454,7 @@ class Engine {
   int device() const { return device_; }
   const Layout& layout() const { return plan_->L; }
   int num_views() const { return (int)views_.size(); }
-  be::stream_t stream() const { return stream_; }
+  be::stream_t stream() const { return stream_.get(); }
   Profiler& profiler() { return prof_; }
 
   // Out-of-core calls: the views listed keep their image and weights stacks in host memory; every view update of
@@ -633,7 +632,7 @@ class Engine {
   void set_poison_epoch(unsigned e) { epoch_ = e; }
   void copy_planes(void* spectrum, int plane0, int nplanes, void* buffer, bool to_buffer, bool host_buffer = false,
                    bool wait = true);
-  float* psi_ptr() { return psi_; }
+  float* psi_ptr() { return psi_.get(); }
   size_t volume_floats() const { return plan_->L.real_floats(); }
   // Host stacks of extents `dims` live at offset `off` inside the engine's (larger) volume, the
   // rest of which holds zeros: set_view / stage_view / set_psi embed, get_psi crops (the
@@ -679,7 +678,7 @@ class Engine {
  private:
   // true when slot spectrum i already belongs to this kernel; otherwise records the kernel
   bool psf_resident(ViewSlot& s, int i, const float* kernel, const int* kdims);
-  void conv_pair(int v, double lambda, float min_value, int final_mode, int accumulate,
+  void conv_pair(int v, const ViewStacks& in, double lambda, float min_value, int final_mode, int accumulate,
                  bool feed_next);
   // one stack into volume `dst` on stream s; `scratch`: where a host stack that needs converting or embedding
   // lands first; dst_dirty: dst has been used as such a scratch since its padding was cleared.  Returns the bytes
@@ -696,8 +695,7 @@ class Engine {
   // buffer that is freed once the stream has passed it; weights: the caller's, placed as ever, or (null ptr) computed
   long long resample_pair(float* image_dst, float* weights_dst, const StackRef& image, const StackRef& weights,
                           be::stream_t s);
-  float** weights_tab_ = nullptr;          // device table of the views' weights volumes (normalize_weights)
-  std::vector<float*> weights_tab_host_;   // ... and what it was filled from
+  std::vector<float*> weights_tab_host_;  // what weights_tab_ was filled from
   bool reflect_ = false;           // set_reflect
   bool margins_mirrored_ = false;  // some image / weights volume or ring slot may hold mirrored margins
   // image and weights of one view; without an embedding scratch a uint16 image that is converted lands in the weights
@@ -708,8 +706,8 @@ class Engine {
   int image_storage_ = 0;
   size_t image_bytes(bool u16) const { return u16 ? plan_->main_bytes() / 2 : plan_->main_bytes(); }
   void alloc_ring_images(bool u16);
-  // the DIVIDE epilogue of view slot s: MVN_EPI_DIVIDE, or MVN_EPI_DIVIDE_U16 on a uint16 volume (counted)
-  void divide_epilogue(EpilogueParams& e, const ViewSlot& s) const;
+  // the DIVIDE epilogue on the image of `in`: MVN_EPI_DIVIDE, or MVN_EPI_DIVIDE_U16 on a uint16 volume (counted)
+  void divide_epilogue(EpilogueParams& e, const ViewStacks& in) const;
   int u16_views() const;
   // Both kernels of slot s on stream st, each unless the slot holds it already (psf_resident): device copy of the
   // kernel, then prepare_psf.  Blocking (set_view): the work volume is the scratch and each copy is freed once the
@@ -717,14 +715,12 @@ class Engine {
   void prepare_psfs(ViewSlot& s, const float* kernel1, const int* k1dims, const float* kernel2, const int* k2dims,
                     bool staging, be::stream_t st);
   std::vector<char> pre_ingested_;  // per view: ingest_device_view has taken its stacks
-  be::event_t caller_ev_ = nullptr;
   bool embedded_ = false;
   int host_dims_[3] = {0, 0, 0}, host_off_[3] = {0, 0, 0};
-  float* embed_scratch_ = nullptr;  // one dense host-shaped stack: H2D lands here, a strided device copy embeds it
   size_t host_floats() const { return (size_t)host_dims_[0] * host_dims_[1] * host_dims_[2]; }
  public:
   // floats of the embedding scratch this engine holds now (0: none) - what the memory planner prices it by
-  size_t scratch_floats() const { return embed_scratch_ ? host_floats() : 0; }
+  size_t scratch_floats() const { return embed_scratch_.get() ? host_floats() : 0; }
  private:
   void alloc_view(ViewSlot& s);
   // PSF spectrum of slot array `spec` from a device-resident kernel: forward transform, then (where
@@ -738,10 +734,7 @@ class Engine {
   void prepare_psf(ViewSlot& s, int i, const float* d_kernel, const int* kdims, float* scratch, bool staging,
                    be::stream_t st);
   Plan3D* taps_plan(int kd);
-  // scattered PSF planes the last-axis pass of the fused-pass taps reads (it cannot run in place into the line
-  // layout): one buffer per engine, read only by prepare_psf's launches on the stream that prepares
-  float* taps_scr_ = nullptr;
-  size_t taps_scr_bytes_ = 0;
+  size_t taps_scr_bytes_ = 0;  // of taps_scr_
   // dim1 forward -> dim0 leg (direct or fused FFT) -> dim1 inverse on the work volume, with kernel i of s
   // `produce` (optional): the last-axis pass that produces this convolution's input, as a function of a row range
   // (row0, nrows; nrows < 0 = all): launched by middle() - in one piece, or boundary planes first (halo mode)
@@ -760,7 +753,7 @@ class Engine {
   bool all_direct() const;
   void decide_layout();
   cfloat* wn() const { return packed_ ? nullptr : work_nyq_; }
-  cfloat* pn() const { return packed_ ? nullptr : psi_spec_nyq_; }
+  cfloat* pn() const { return packed_ ? nullptr : psi_spec_nyq_.get(); }
   bool packed_ = false, packed_hint_ = false, packed_allowed_ = true;
   bool packed_default_ = true;  // packed_allowed_ as the constructor decided it (a removed halo hook restores it)
   // the loops run their convolutions as last-axis pass -> fused middle pass -> last-axis pass on the line layout
@@ -776,8 +769,7 @@ class Engine {
   int layout_override_ = -1;
   int halo_planes_ = 0;
   bool halo_ranged() const;
-  unsigned* poison_ = nullptr;      // the word in use: poison_own_, or caller-owned memory (bind_poison)
-  unsigned* poison_own_ = nullptr;  // 256 bytes: [0] / [1] the engine's own words, bytes 64 / 128: tables of the peers'
+  unsigned* poison_ = nullptr;  // the word in use: poison_own_'s first, or caller-owned memory (bind_poison)
   std::vector<unsigned*> poison_peers_;
   // The word a leg of `epoch` reports to (and the last-axis pass that ends its convolution reads), and the table of
   // the peers' words it reports to as well.  With peers (the slabs of one volume, mvn_multi.cpp) the words alternate
@@ -785,8 +777,8 @@ class Engine {
   // to read the current epoch (boundary-first order: the interior planes of that pass run after the exchange has
   // begun), so it must not overwrite that word; a leg two epochs on follows the peers' next leg, and with it their
   // last-axis pass (HaloGroup::behind_leg).
-  unsigned* poison_word(unsigned epoch) const { return poison_peers_.empty() ? poison_ : poison_own_ + (epoch & 1u); }
-  unsigned* const* poison_table(unsigned epoch) const { return (unsigned* const*)(poison_own_ + 16 + 16 * (epoch & 1u)); }
+  unsigned* poison_word(unsigned epoch) const { return poison_peers_.empty() ? poison_ : poison_own_.get() + (epoch & 1u); }
+  unsigned* const* poison_table(unsigned epoch) const { return (unsigned* const*)(poison_own_.get() + 16 + 16 * (epoch & 1u)); }
   size_t poison_bytes() const { return (poison_peers_.empty() ? 1 : 2) * sizeof(unsigned); }
   unsigned epoch_ = 0;        // direct dim0 legs enqueued so far = the epoch of the latest
   unsigned armed_epoch_ = 0;  // != 0: the convolution in flight ran a direct leg with this epoch
@@ -794,39 +786,27 @@ class Engine {
   void arm(EpilogueParams& e);
   FormSwitches sw_;
   int d0_stagger_ = 0;
-  std::map<int, std::unique_ptr<Plan3D>> taps_plans_;  // (kd, d1, d2) plans of the tap arrays, private to the engine
-  // second work volume: the direct dim0 leg is out of place, work_ and work2_ swap roles after it
-  float* work2_ = nullptr;
-  cfloat* work2_nyq_ = nullptr;
-  float *work_alloc_ = nullptr, *work2_alloc_ = nullptr;  // what the two work volumes were allocated as
   bool spec_tiled_ = false;
   float* stage_spec_scratch_ = nullptr;  // owned by stage_scratch_
   void wait_staged(int v);
-  // the public constructor delegates to this one, so that ~Engine releases what a construction that fails had made
+  // the public constructor delegates to this one, so that ~Engine runs - and drains - when a construction fails half-way
   explicit Engine(int device) : device_(device) {}
   int device_;
-  std::shared_ptr<Plan3D> plan_;
-  be::stream_t stream_ = nullptr;
-  SideStream side_;
   // staging pipeline
-  be::stream_t upload_stream_ = nullptr;
-  std::vector<be::Event> staged_ev_;
   std::vector<int> staged_;  // per view: 0 pending, 1 enqueued on the upload stream, -1 failed
   bool pipelined_ = false;
   std::mutex stage_mu_;
   std::condition_variable stage_cv_;
-  std::vector<be::DeviceBuffer<float>> stage_scratch_;
   // out-of-core views (set_residency): per view its position in the sweep's streamed order, or -1 (resident)
   struct RingSlot {
-    float* image = nullptr;
+    be::DeviceBuffer<float> image;
     bool image_u16 = false;  // the image is a uint16 volume (every streamed view of the call is held as uint16)
-    float* weights = nullptr;
-    be::event_t filled = nullptr;  // upload stream: the pair has landed
-    be::event_t freed = nullptr;   // compute stream: the last pass that reads the pair has been enqueued before it
+    be::DeviceBuffer<float> weights;
+    be::Event filled;  // upload stream: the pair has landed
+    be::Event freed;   // compute stream: the last pass that reads the pair has been enqueued before it
   };
   std::vector<int> stream_pos_;
   std::vector<int> streamed_order_;
-  std::vector<RingSlot> ring_;
   // uploads enqueued / streamed view updates enqueued in this call (under stage_mu_), upload order == use order
   long uploads_ = 0, consumed_ = 0;
   bool stream_abort_ = false;
@@ -839,11 +819,10 @@ class Engine {
   // the switches of the loop: the options the engine holds, the device state of the running iterate() (a buffer that
   // is held = its switch is on), and what the last one reported
   LoopOptions held_;
-  LoopState loop_;
   LoopResult last_;
   RecordSet stat_records() const { return loop_.records(LoopState::STAT_REC, plan_->L); }
   RecordSet nm_records() const { return loop_.records(LoopState::NM_REC, plan_->L); }
-  bool accel_running() const { return loop_.buf[LoopState::X_PREV] != nullptr; }
+  bool accel_running() const { return loop_.buf[LoopState::X_PREV].get() != nullptr; }
   float* tv_volume() const { return loop_.at<float>(LoopState::TV); }
   // the records of view v's pass and the window they cover: the stacks inside the padded volume, or all of it
   MvnStatsParams params_for(const RecordSet& r, int v) const;
@@ -851,16 +830,8 @@ class Engine {
   void tv_free();
   void accel_extrapolate(int k, float min_value);  // after sweep k (1-based), before sweep k + 1
   void ring_upload(int v, const StackRef& image, const StackRef& weights);  // uploader thread
-  void ring_acquire(ViewSlot& s);                                     // main thread, before the view update
-  void ring_release(ViewSlot& s);                                     // main thread, after it
-  float* psi_ = nullptr;
-  float* work_ = nullptr;
-  cfloat* work_nyq_ = nullptr;
-  float* delta_ = nullptr;
-  bool delta_external_ = false;
-  // simultaneous mode: psi after the forward last-axis and dim1 passes, shared by all local views
-  float* psi_spec_ = nullptr;
-  cfloat* psi_spec_nyq_ = nullptr;
+  ViewStacks ring_acquire();  // main thread, before the view update: the slot its pair has landed in
+  void ring_release();        // main thread, after it
   bool work_has_psi_spectrum_ = false;  // work_ holds the last-axis transform of the current psi
   bool psi_spec_valid_ = false;         // psi_spec_ holds the last-axis + dim1 transform of the current psi
   // chunked simultaneous step: the last local view's final pass, parked by compute_delta_head
@@ -873,7 +844,6 @@ class Engine {
   long pair_counter_ = 0;
   // one steady-state sweep over all views captured as a graph (small, launch-bound volumes);
   // valid for the parameters it was captured with, buffers never move during an engine's life
-  be::graph_exec_t sweep_graph_ = nullptr;
   double graph_lambda_ = 0;
   int graph_reg_kind_ = 0;  // the regulariser the sweep was captured with
   double graph_reg_eps_ = 0;
@@ -884,8 +854,43 @@ class Engine {
   // (taps or 3-D spectrum), depth and the Nyquist layout
   unsigned long graph_gen_ = 0, graph_captured_gen_ = 0;
   const float* graph_work_ = nullptr;  // which of the two work volumes was current when the sweep was captured
+  // ---- the device state ---------------------------------------------------------------------------------------
+  // The members below own what the engine holds on the device, and their ORDER carries the rule of mvn_backend.hpp:
+  // buffers, events and the graph first, the streams last - side, upload, then compute -, so that destruction drains
+  // and destroys the compute stream, the upload stream and the side stream, in that order, before the first buffer
+  // goes.  A plain pointer beside an owner is a ROLE, not an allocation: it is never freed.
+  std::shared_ptr<Plan3D> plan_;
+  std::map<int, std::unique_ptr<Plan3D>> taps_plans_;  // (kd, d1, d2) plans of the tap arrays, private to the engine
+  be::DeviceBuffer<float> psi_;
+  // The two work volumes and their Nyquist planes.  The direct dim0 leg is out of place: work_ and work2_ (roles)
+  // swap at every such leg; the second pair is allocated at first need (ensure_work2).
+  be::DeviceBuffer<float> work_own_[2];
+  be::DeviceBuffer<cfloat> work_nyq_own_[2];
+  float *work_ = nullptr, *work2_ = nullptr;
+  cfloat *work_nyq_ = nullptr, *work2_nyq_ = nullptr;
+  // simultaneous mode: psi after the forward last-axis and dim1 passes, shared by all local views; the correction -
+  // delta_ is the buffer in use (role): delta_own_, or caller-owned memory (bind_delta)
+  be::DeviceBuffer<float> psi_spec_;
+  be::DeviceBuffer<cfloat> psi_spec_nyq_;
+  be::DeviceBuffer<float> delta_own_;
+  float* delta_ = nullptr;
+  be::DeviceBuffer<float> embed_scratch_;  // one dense host-shaped stack: H2D lands here, a strided device copy embeds it
+  be::DeviceBuffer<float*> weights_tab_;   // device table of the views' weights volumes (normalize_weights)
+  // scattered PSF planes the last-axis pass of the fused-pass taps reads (it cannot run in place into the line
+  // layout): one buffer per engine, read only by prepare_psf's launches on the stream that prepares
+  be::DeviceBuffer<float> taps_scr_;
+  be::DeviceBuffer<unsigned> poison_own_;  // 256 bytes: [0] / [1] the engine's own words, bytes 64 / 128: tables of the peers'
+  LoopState loop_;
   std::vector<ViewSlot> views_;
+  std::vector<RingSlot> ring_;
+  std::vector<be::DeviceBuffer<float>> stage_scratch_;
+  std::vector<be::Event> staged_ev_;
+  be::Event caller_ev_;
+  be::GraphExec sweep_graph_;
   Profiler prof_;
+  SideStream side_;
+  be::Stream upload_stream_;
+  be::Stream stream_;
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -936,31 +941,28 @@ class SlabEngine {
   void step_mid(int v, int conv);
   void step_unpack(int v, int conv, double lambda, float min_value, bool feed_next);
   void sync();
-  be::stream_t stream() const { return stream_; }
+  be::stream_t stream() const { return stream_.get(); }
 
  private:
   void upload_slab(float* dst, const float* host);
   int device_, P_, rank_;
   shape_t dims_;
-  std::shared_ptr<Plan3D> planA_, planB_;
-  be::stream_t stream_ = nullptr;
-  float* psi_ = nullptr;
-  float* work_ = nullptr;
-  cfloat* work_nyq_ = nullptr;
-  float *a_main_ = nullptr, *b_main_ = nullptr;
-  cfloat *a_nyq_ = nullptr, *b_nyq_ = nullptr;
-  bool external_ = false;
-  float *own_a_ = nullptr, *own_b_ = nullptr;
-  cfloat *own_an_ = nullptr, *own_bn_ = nullptr;
   bool work_has_psi_spectrum_ = false;
   struct SlabView {
-    float* image = nullptr;
-    float* weights = nullptr;
-    float* spec[2] = {nullptr, nullptr};   // transposed slabs [d0][d1/P][C]
-    cfloat* nyq[2] = {nullptr, nullptr};   // [d0][d1/P]
+    be::DeviceBuffer<float> image, weights;
+    be::DeviceBuffer<float> spec[2];   // transposed slabs [d0][d1/P][C]
+    be::DeviceBuffer<cfloat> nyq[2];   // [d0][d1/P]
     bool set = false;
   };
+  // the device state, buffers before the stream (Engine); a_* / b_* are the exchange buffers in use (roles): own_*,
+  // or caller-owned memory (bind_buffers)
+  std::shared_ptr<Plan3D> planA_, planB_;
+  be::DeviceBuffer<float> psi_, work_, own_a_, own_b_;
+  be::DeviceBuffer<cfloat> work_nyq_, own_an_, own_bn_;
+  float *a_main_ = nullptr, *b_main_ = nullptr;
+  cfloat *a_nyq_ = nullptr, *b_nyq_ = nullptr;
   std::vector<SlabView> views_;
+  be::Stream stream_;
 };
 
 }  // namespace mvn

@@ -337,6 +337,16 @@ def test_engine_simultaneous_mode(emu, shape, leg):
     eng.close()
 
 
+def test_psf_buffers_replaced_on_a_live_engine_equal_fresh_engines(emu, monkeypatch):
+    """tests/psf_replace_case.py: taps of 16 planes -> 32 planes -> 3-D spectrum -> taps again on ONE engine, psi after
+    every stage bit for bit that of a fresh engine given only that stage's kernels (tests/test_gpu_scoped.py runs the
+    same body on the device)."""
+    import psf_replace_case
+    monkeypatch.delenv("MVN_DIM0_DIRECT_MIN_ITEMS", raising=False)
+    monkeypatch.delenv("MVN_DIM0_DIRECT_MIN_PLANE", raising=False)
+    psf_replace_case.run(emu)
+
+
 def test_pointwise_entry_points(emu):
     rng = np.random.default_rng(0)
     n = 1000

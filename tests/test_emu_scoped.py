@@ -4,7 +4,9 @@ MVN_EMU_TOTAL_MB (read at every allocation).  For every test and legacy utility 
 it at a small shape S and keep the result; cap the device at what that call needs, rounded up to the MB; run it eight
 times at a shape B of about twice the volume, whose first allocation fits and a later one does not - each call must
 fail, naming exhausted device memory; then the call at S again under the same cap - it must succeed and give the kept
-result bit for bit.  One leaked buffer of one failed call and it cannot.
+result bit for bit.  One leaked buffer of one failed call and it cannot.  The same recipe for the engines' resident
+state, held in the same owners (csrc/mvn_engine.hpp): an engine and a slab engine that cannot be built, set_view on a
+live engine, a streamed call.
 
 Each case runs in a process of its own, so that the count starts at zero: no plan, engine or garbage of another test.
 tools/scoped_standalone.cpp runs the same error paths, the group constructor's among them, under AddressSanitizer with
@@ -52,8 +54,72 @@ def void_call(where, f):
         raise native.MvnError(err)
     return out
 
+# ---- the engines' resident state (csrc/mvn_engine.hpp): every buffer, stream and event a member that owns it ----
+def engine_create(s):  # Engine::Engine: psi, the work volume, its Nyquist plane, the poison words
+    e = emu.engine(s, 0)
+    try:
+        e.set_psi(data[s])
+        return e.get_psi()
+    finally:
+        e.close()
+
+def with_engine_uncapped(s, views):
+    cap = os.environ.pop("MVN_EMU_TOTAL_MB", None)
+    try:
+        return emu.engine(s, views)
+    finally:
+        if cap is not None:
+            os.environ["MVN_EMU_TOTAL_MB"] = cap
+
+def live_set_view(s):
+    # the engine itself is built with no cap; the views are then set under it: alloc_view (image, weights), and per
+    # kernel prepare_psfs' device copy and prepare_psf's 3-D spectrum with its Nyquist plane (the suite's pin of the
+    # direct dim0 leg, tests/conftest.py, holds in this process: no taps at these sizes, no second work volume)
+    e = with_engine_uncapped(s, 2)
+    try:
+        for v in range(2):
+            e.set_view(v, data[s] + v, np.full(s, 0.5, np.float32), kernel, kernel)
+        e.set_psi(data[s])
+        e.iterate(1, 0.006, 1e-4)
+        return e.get_psi()
+    finally:
+        e.close()
+
+def streamed_ring(s):
+    # inplace_gpu_deconvolve, 2 views of which 1 streams through a ring of 2 slots, cyclic policy (the engine has the
+    # extents of the stacks)
+    from libmultiviewnative_amd.abi import WorkspaceHolder
+    h = WorkspaceHolder([data[s], data[s] + 1], [kernel] * 2, [kernel] * 2, [np.full(s, 0.5, np.float32)] * 2, 0.006, 1e-4, 2)
+    emu.set_pad_mode("none")
+    emu.set_memory_mode("stream:1")
+    before = emu.stream_counters()
+    try:
+        out = void_call("inplace_gpu_deconvolve", lambda: emu.gpu_deconvolve(data[s], h, pad_mode=False))
+        assert [b - a for a, b in zip(before, emu.stream_counters())][:2] == [1, 2], "the call streamed no view"
+        return out
+    finally:
+        emu.set_memory_mode(None)
+
+def slab_create(s):  # SlabEngine::SlabEngine, rank 0 of 2: psi, work, own_a_, own_b_, then the three Nyquist planes
+    e = emu.slab_engine(s, 2, 0, 1)
+    try:
+        e.set_psi(data[s][:s[0] // 2])
+        return e.get_psi()
+    finally:
+        e.close()
+
+half = lambda s: (s[0] // 2, s[1], s[2])
+ENGINE = lambda s: [vol(s), vol(s), nyq(s), 256]
+VIEW = lambda s: [vol(s), vol(s)] + [kernel.nbytes, vol(s), nyq(s)] * 2
+# stream:1 of 2 views: the engine, the ring's two weights volumes (set_residency) and two image volumes
+# (alloc_ring_images), the resident view's pair and the second work volume (reserve_views), then per kernel its device
+# copy and 3-D spectrum, and the staging thread's re-tiling scratch
+RING = lambda s: ENGINE(s) + [vol(s)] * 2 + [vol(s)] * 2 + [vol(s)] * 2 + [vol(s), nyq(s)] + \
+    [kernel.nbytes, vol(s), nyq(s)] * 4 + [vol(s)]
+
 # name -> (the call at a shape, the device allocations of that call in order, timed: the result is a time, plans: the
-# call goes through the plan store)
+# call goes through the plan store[, fits: this many leading allocations at B fit under the cap and the next one does
+# not[, the refusal's words]])
 CASES = {
     "mvn_tv_factor": (lambda s: emu.tv_factor(data[s], 0.005, 0.01), lambda s: [vol(s)] * 2, False, False),
     "mvn_tv_time": (lambda s: emu.tv_time(s, reps=1), lambda s: [vol(s)] * 2, True, False),
@@ -73,20 +139,36 @@ CASES = {
     "mvn_fft3_many_r2c": (lambda s: emu.rfft3_many(np.stack([data[s], data[s] * 2, data[s] + 1])),
                           lambda s: [vol(s), nyq(s)] * 3, False, True),
     "mvn_fft3_many_time": (lambda s: emu.fft3_many_time(s, 3, reps=1), lambda s: [vol(s), nyq(s)] * 3, True, True),
+    # psi fits, the work volume does not
+    "mvn_engine_create": (engine_create, ENGINE, False, True, 1),
+    # view 0 gets its image, weights and first spectrum; the second spectrum's main array does not fit
+    "mvn_engine_set_view": (live_set_view, lambda s: ENGINE(s) + VIEW(s) * 2, False, True, 10),
+    # The planner (plan_engine, csrc/mvn_abi.cpp) prices the call by Engine::memory_need against the same total before
+    # anything is allocated, and that model is exact (tests/test_emu_streamed_views.py): under ANY cap a streamed call
+    # either fits whole or is refused there, in the reference's words - no cap makes alloc_ring_images, or any other
+    # allocation of the call, fail.  What the case does check: the engine the call at S left in the cache - ring slots,
+    # their events, the upload stream - is dropped by the refused calls, and everything it held is free again.
+    "streamed_ring": (streamed_ring, RING, False, True, None, "memory constraints"),
+    # own_a_ fits, own_b_ does not
+    "mvn_slab_create": (slab_create, lambda s: [vol(half(s))] * 4 + [nyq(half(s))] * 3, False, True, 3),
 }
-call, allocations, timed, plans = CASES[name]
+call, allocations, timed, plans = CASES[name][:4]
+fits = CASES[name][4] if len(CASES[name]) > 4 else None
+refusal = CASES[name][5] if len(CASES[name]) > 5 else "device memory exhausted"
 emu.check(emu.l.mvn_release_cached_engines())
 kept = call(S)  # (uncapped; the plan's small device tables stay in the store and are counted from here on)
 cap = -(-sum(allocations(S)) // MB)
 # the tables of the plans of S and B (a few KB each) must fit beside the call at S, and beside the first allocation at B
 TABLES = 24 << 10 if plans else 0
 assert sum(allocations(S)) + TABLES <= cap * MB and allocations(B)[0] + TABLES <= cap * MB < sum(allocations(B)), name
+if fits:
+    assert sum(allocations(B)[:fits]) + TABLES <= cap * MB < sum(allocations(B)[:fits + 1]), name
 os.environ["MVN_EMU_TOTAL_MB"] = str(cap)
 for i in range(8):
     try:
         call(B)
     except native.MvnError as e:
-        assert "device memory exhausted" in str(e), (name, i, str(e))
+        assert refusal in str(e), (name, i, str(e))
     else:
         raise AssertionError("%s: call %d at %r succeeded under a cap of %d MB" % (name, i, B, cap))
 again = call(S)
@@ -99,7 +181,8 @@ print("ok")
 
 CASES = ["mvn_tv_factor", "mvn_tv_time", "mvn_reflect_time", "mvn_resample_stack", "mvn_resample_time",
          "inplace_gpu_convolution", "iterate_fft_plain", "compute_quotient", "compute_final_values", "mvn_fft3_r2c",
-         "mvn_fft3_many_r2c", "mvn_fft3_many_time"]
+         "mvn_fft3_many_r2c", "mvn_fft3_many_time", "mvn_engine_create", "mvn_engine_set_view", "streamed_ring",
+         "mvn_slab_create"]
 
 
 @pytest.fixture(scope="module")

@@ -1,7 +1,7 @@
 """The two utilities of the ABI that no other device test calls, on the MI355X: mvn_tv_time (the shared timing helper
 on real events) and mvn_fft3_many_r2c (the shared position-order -> natural-order helper, pinned against the
-single-transform path that the oracle tests pin).  Error paths are not provoked on the device: tests/test_emu_scoped.py
-drives them on the emulation."""
+single-transform path that the oracle tests pin), and an engine whose PSF buffers are replaced while it lives.  Error
+paths are not provoked on the device: tests/test_emu_scoped.py drives them on the emulation."""
 import math
 import os
 
@@ -34,3 +34,12 @@ def test_batched_r2c_equals_the_single_transform(gpu, shape):
     many = gpu.rfft3_many(stacks)
     for b in range(2):
         assert many[b].tobytes() == gpu.rfft3(stacks[b]).tobytes(), (shape, b)
+
+
+def test_psf_buffers_replaced_on_a_live_engine_equal_fresh_engines(gpu, monkeypatch):
+    """tests/psf_replace_case.py, the body tests/test_emu_engine.py runs on the emulation: taps of 16 planes -> 32 planes
+    -> 3-D spectrum -> taps again on ONE engine, psi after every stage bit for bit that of a fresh engine."""
+    import psf_replace_case
+    monkeypatch.delenv("MVN_DIM0_DIRECT_MIN_ITEMS", raising=False)
+    monkeypatch.delenv("MVN_DIM0_DIRECT_MIN_PLANE", raising=False)
+    psf_replace_case.run(gpu)

@@ -8,6 +8,10 @@
 //       its engine, eight events, two streams - is released by the constructor's unwinding
 //   (c) mvn_fft3_profile with the per-kind times (the profiler's event pool)
 //   (d) one group that works: create, load, one sweep, destroy
+//   (e) the engines' resident state, once each: an engine whose work volume does not fit, set_view on a live engine
+//       whose PSF buffers do not fit, a streamed call (ring of two slots) and then one the planner refuses - the cached
+//       engine with its ring goes -, a slab engine whose second exchange buffer does not fit
+//   (f) a plan whose construction fails among the tables of its first axis
 // Built with -fsanitize=address,undefined against the emulation built the same way (csrc/Makefile, target
 // scoped-asan); exits non-zero on a failure, and LeakSanitizer reports at exit what was not released.
 #include <cmath>
@@ -35,13 +39,14 @@ static void cap_mb(int mb) {
 
 // the call must fail under the cap, with the emulation's message; `rc`: its return code, or for a void entry point 1
 // after a message of another call's was put into mvn_last_error
-static int must_exhaust(const char* name, int mb, const std::function<int()>& call) {
+static int must_exhaust(const char* name, int mb, const std::function<int()>& call,
+                        const char* words = "device memory exhausted") {
   mvn_set_pad_mode("no such mode");  // (fails: mvn_last_error is this call's until the next failure)
   cap_mb(mb);
   const int rc = call();
   cap_mb(0);
   const std::string err = mvn_last_error();
-  if (rc == 0 || err.rfind(name, 0) != 0 || err.find("device memory exhausted") == std::string::npos) return bad(name);
+  if (rc == 0 || err.rfind(name, 0) != 0 || err.find(words) == std::string::npos) return bad(name);
   std::printf("%s: refused\n", name);
   return 0;
 }
@@ -133,6 +138,64 @@ int main() {
     if (got == psi) fails += bad("the group's sweep changed nothing");
     if (mvn_group_destroy(g) < 0) fails += bad("mvn_group_destroy");
     if (!fails) std::printf("group: swept\n");
+  }
+
+  // ---- (e): shapes and caps of tests/test_emu_scoped.py, under the product's defaults (3 x 3 x 3 kernels are held in
+  // the direct form: taps of 16 planes and a second work volume)
+  {
+    mvn_engine* e = nullptr;
+    fails += must_exhaust("mvn_engine_create", 3, [&] { return mvn_engine_create(0, B, 0, &e); });  // psi fits
+    if (e) fails += bad("an engine came back from the refused call");
+    // the engine of 4 MB is built with no cap; under 9 MB view 0 gets its image, weights and taps, not the second work
+    // volume
+    if (mvn_engine_create(0, B, 2, &e) < 0) fails += bad("mvn_engine_create");
+    fails += must_exhaust("mvn_engine_set_view", 9, [&] {
+      int rc = 0;
+      for (int v = 0; v < 2 && rc == 0; ++v)
+        rc = mvn_engine_set_view(e, v, a.data(), c.data(), kernel.data(), K, kernel.data(), K);
+      return rc;
+    });
+    if (mvn_engine_destroy(e) < 0) fails += bad("mvn_engine_destroy");
+    // a call of two views at 64^3, one of them streamed; then the same at B under what that took: the planner refuses
+    // it before anything is allocated (no cap reaches an allocation of a streamed call: the planner's figure is
+    // exact), and drops the cached engine with its ring
+    int S[3] = {64, 64, 64};
+    const size_t sn = (size_t)S[0] * S[1] * S[2];
+    view_data v[2];
+    std::memset(v, 0, sizeof v);
+    for (int i = 0; i < 2; ++i) {
+      v[i].image_ = a.data() + i * sn, v[i].weights_ = c.data(), v[i].kernel1_ = v[i].kernel2_ = kernel.data();
+      v[i].image_dims_ = v[i].weights_dims_ = S, v[i].kernel1_dims_ = v[i].kernel2_dims_ = K;
+    }
+    workspace ws;
+    std::memset(&ws, 0, sizeof ws);
+    ws.data_ = v, ws.num_views_ = 2, ws.lambda_ = 0.006, ws.minValue_ = 1e-4f, ws.num_iterations_ = 2;
+    std::vector<float> psi(b.begin(), b.begin() + sn);
+    if (mvn_set_pad_mode("none") < 0 || mvn_set_memory_mode("stream:1") < 0) fails += bad("the streamed call's modes");
+    mvn_set_pad_mode("no such mode");
+    inplace_gpu_deconvolve(psi.data(), ws, 0);
+    if (std::string(mvn_last_error()).rfind("mvn_set_pad_mode", 0) != 0 || !std::isfinite(psi[0]) || psi[0] == b[0])
+      fails += bad("a streamed call");
+    for (int i = 0; i < 2; ++i) v[i].image_ = a.data() + i * n, v[i].image_dims_ = v[i].weights_dims_ = B;
+    fails += must_exhaust("inplace_gpu_deconvolve", 15, [&] { return inplace_gpu_deconvolve(out.data(), ws, 0), 1; },
+                          "memory constraints");
+    if (mvn_set_memory_mode(nullptr) < 0 || mvn_set_pad_mode("zero") < 0) fails += bad("the modes' defaults");
+    mvn_slab* slab = nullptr;
+    fails += must_exhaust("mvn_slab_create", 3, [&] { return mvn_slab_create(0, B, 2, 0, 1, &slab); });  // own_a_ fits
+    if (slab) fails += bad("a slab engine came back from the refused call");
+  }
+
+  // ---- (f): an engine of 72 x 80 x 64 on device 1 takes all but about 140 KB of a cap of 3 MB (two volumes of 1440
+  // KB, a Nyquist plane of 45 KB, its plan's tables).  The last axis of 2 x 2 x 20480 has a twiddle table of 80 KB and
+  // two index tables of 40 KB: the first two fit, the third does not, and the plan gives them back.
+  {
+    int E[3] = {72, 80, 64}, T[3] = {2, 2, 20480};
+    mvn_engine* occupy = nullptr;
+    cap_mb(3);
+    if (mvn_engine_create(1, E, 0, &occupy) < 0) fails += bad("the engine that occupies device 1");
+    fails += must_exhaust("mvn_plan_store_add", 3, [&] { return mvn_plan_store_add(1, T); });
+    if (mvn_plan_store_has_key(1, T) != 0) fails += bad("the plan that could not be built is in the store");
+    if (mvn_engine_destroy(occupy) < 0) fails += bad("mvn_engine_destroy");
   }
 
   if (mvn_release_cached_engines() < 0 || mvn_plan_store_clear() < 0) fails += bad("the clean-up");
