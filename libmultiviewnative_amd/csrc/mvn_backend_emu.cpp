@@ -27,17 +27,6 @@
 namespace mvn {
 namespace be {
 
-#define MVN_DISPATCH_T(T_, CALL)                                   \
-  switch (T_) {                                                    \
-    case 16: { constexpr int TT = 16; CALL; } break;               \
-    case 8: { constexpr int TT = 8; CALL; } break;                 \
-    case 4: { constexpr int TT = 4; CALL; } break;                 \
-    case 2: { constexpr int TT = 2; CALL; } break;                 \
-    case 1: { constexpr int TT = 1; CALL; } break;                 \
-    default: throw std::invalid_argument("mvn: unsupported tile width"); \
-  }
-
-
 const char* backend_name() { return "host-emulation (test only)"; }
 
 // MVN_EMU_DEVICES=n pretends to have n devices (tests of the per-device engine cache and locking);
@@ -160,11 +149,7 @@ void graph_destroy(graph_exec_t) {}
 // one-sweep launch would have, so that the sweep loop and its ragged tail are exercised
 // same knobs as the HIP backend, but read at every launch and with every pass enabled by default
 // (the emulation exists to test them)
-static bool emu_wave_rows(const RowsParams& p, int kind_bit) {
-  const char* m = std::getenv("MVN_WAVE_ROWS_MASK");
-  const int mask = m && *m ? std::atoi(m) : 31;
-  return (mask & kind_bit) && p.fixed && !p.lines && p.h == WrCfg::H && p.C == WrCfg::H;
-}
+static bool emu_wave_rows(const RowsParams& p, int kind_bit) { return wr_rows_enabled(p, wr_rows_mask(31), kind_bit); }
 
 template <int MODE, int EPI>
 static void emu_wave_rows_run(const RowsParams& p) {
@@ -181,27 +166,6 @@ static void emu_wave_rows_run(const RowsParams& p) {
   }
 }
 
-template <int MODE>
-static void emu_wave_rows_mode(const RowsParams& p) {
-  switch (p.epi.mode) {
-    case MVN_EPI_DIVIDE: emu_wave_rows_run<MODE, MVN_EPI_DIVIDE>(p); break;
-    case MVN_EPI_DIVIDE_U16: emu_wave_rows_run<MODE, MVN_EPI_DIVIDE_U16>(p); break;
-    case MVN_EPI_DIVIDE_NM: emu_wave_rows_run<MODE, MVN_EPI_DIVIDE_NM>(p); break;
-    case MVN_EPI_DIVIDE_NM_U16: emu_wave_rows_run<MODE, MVN_EPI_DIVIDE_NM_U16>(p); break;
-    case MVN_EPI_UPDATE: emu_wave_rows_run<MODE, MVN_EPI_UPDATE>(p); break;
-    case MVN_EPI_UPDATE_STATS: emu_wave_rows_run<MODE, MVN_EPI_UPDATE_STATS>(p); break;
-    case MVN_EPI_UPDATE_TV: emu_wave_rows_run<MODE, MVN_EPI_UPDATE_TV>(p); break;
-    case MVN_EPI_UPDATE_STATS_TV: emu_wave_rows_run<MODE, MVN_EPI_UPDATE_STATS_TV>(p); break;
-    case MVN_EPI_DELTA:
-      if (MODE == MVN_WR_C2R) {
-        emu_wave_rows_run<MVN_WR_C2R, MVN_EPI_DELTA>(p);
-        break;
-      }
-      throw std::invalid_argument("mvn: DELTA epilogue only in the plain c2r pass");
-    default: emu_wave_rows_run<MODE, MVN_EPI_STORE>(p); break;
-  }
-}
-
 // fixed-length kernels: every phase is run for all thread ids in turn (real thread mapping)
 // "grid" of a fixed last-axis launch: one workgroup per tile, or for the walking configurations
 // about a third as many, so that the tile loop is exercised
@@ -210,54 +174,85 @@ static long emu_rows_grid(long ntiles) {
   return FxRowsCfg<H>::WALK && ntiles > 2 ? (ntiles + 2) / 3 : ntiles;
 }
 
-// line-layout forms of the fixed last-axis kernels (H = 256), KIND 0 r2c, 1 c2r, 2 fused
-static void emu_rows_lines(const RowsParams& p, long ntiles, int kind) {
-  constexpr int H = 256;
-  typedef FxCtx<FxRowsRegs<H>, FxRowsCfg<H>::NT> Ctx;
-  typedef FxCtx<FxRowsStatRegs<H>, FxRowsCfg<H>::NT> SCtx;  // (MVN_EPI_UPDATE_STATS)
-  typedef FxCtx<FxRowsNmRegs<H>, FxRowsCfg<H>::NT> NCtx;    // (MVN_EPI_DIVIDE_NM)
-  if (!fx_rows_lines_ok<H>() || !p.fixed || p.h != H || p.C != H || !p.nyq_packed || p.lines_d1 < 1 ||
-      p.lines_d1 % FxRowsCfg<H>::T || p.row_base % FxRowsCfg<H>::T || p.rows != ntiles * FxRowsCfg<H>::T)
-    throw std::invalid_argument("mvn: line-layout last-axis pass outside its range");
+// `grid` workgroups of a fixed last-axis launch (KIND: MvnPassKind), one register context per host thread
+template <int H, int KIND, int EPI, bool LINES>
+static void emu_rows_fixed_run(const RowsParams& p, long grid) {
+  typedef FxCtx<FxRowsRegsFor<H, EPI>, FxRowsCfg<H>::NT> Ctx;
 #pragma omp parallel
   {
     std::vector<char> lds(sizeof(cfloat) * FxRowsCfg<H>::lds_cfloats + 64);
     std::unique_ptr<Ctx> ctx(new Ctx());
-    std::unique_ptr<SCtx> sctx(new SCtx());
-    std::unique_ptr<NCtx> nctx(new NCtx());
+#pragma omp for schedule(static)
+    for (long t = 0; t < grid; ++t) fx_rows_workgroup<H, KIND, EPI, LINES>(p, t, grid, (cfloat*)lds.data(), *ctx);
+  }
+}
+
+// the tiles of a run-time-radix launch, one "thread" per workgroup
+template <int KIND, int T, int FORM>
+static void emu_rows_generic_run(const RowsParams& p, bool even, long ntiles, size_t lds_bytes) {
+#pragma omp parallel
+  {
+    std::vector<char> lds(lds_bytes + 64);
 #pragma omp for schedule(static)
     for (long t = 0; t < ntiles; ++t) {
       cfloat* l = (cfloat*)lds.data();
-      if (kind == 0) {
-        fx_rows_run<H, 0, MVN_EPI_STORE, Ctx, true>(p, t, ntiles, l, *ctx);
-      } else if (kind == 1) {
-        switch (p.epi.mode) {
-          case MVN_EPI_DIVIDE: fx_rows_run<H, 1, MVN_EPI_DIVIDE, Ctx, true>(p, t, ntiles, l, *ctx); break;
-          case MVN_EPI_DIVIDE_U16: fx_rows_run<H, 1, MVN_EPI_DIVIDE_U16, Ctx, true>(p, t, ntiles, l, *ctx); break;
-          case MVN_EPI_DIVIDE_NM: fx_rows_run_nm<H, 1, MVN_EPI_DIVIDE_NM, NCtx, true>(p, t, ntiles, l, *nctx); break;
-          case MVN_EPI_DIVIDE_NM_U16: fx_rows_run_nm<H, 1, MVN_EPI_DIVIDE_NM_U16, NCtx, true>(p, t, ntiles, l, *nctx); break;
-          case MVN_EPI_UPDATE: fx_rows_run<H, 1, MVN_EPI_UPDATE, Ctx, true>(p, t, ntiles, l, *ctx); break;
-          case MVN_EPI_UPDATE_STATS: fx_rows_run_stats<H, 1, SCtx, true>(p, t, ntiles, l, *sctx); break;
-          case MVN_EPI_UPDATE_TV: fx_rows_run<H, 1, MVN_EPI_UPDATE_TV, Ctx, true>(p, t, ntiles, l, *ctx); break;
-          case MVN_EPI_UPDATE_STATS_TV: fx_rows_run_stats<H, 1, SCtx, true, MVN_EPI_UPDATE_STATS_TV>(p, t, ntiles, l, *sctx); break;
-          case MVN_EPI_DELTA: fx_rows_run<H, 1, MVN_EPI_DELTA, Ctx, true>(p, t, ntiles, l, *ctx); break;
-          default: fx_rows_run<H, 1, MVN_EPI_STORE, Ctx, true>(p, t, ntiles, l, *ctx); break;
-        }
+      if constexpr (KIND == MVN_PASS_R2C) {
+        if (even)
+          rows_r2c_even_body<T>(p, t, 0, 1, l);
+        else
+          rows_r2c_odd_body<T>(p, t, 0, 1, l);
+      } else if constexpr (KIND == MVN_PASS_C2R) {
+        if (even)
+          rows_c2r_even_body<T, false, FORM>(p, t, 0, 1, l);
+        else
+          rows_c2r_odd_body<T, FORM>(p, t, 0, 1, l);
       } else {
-        switch (p.epi.mode) {
-          case MVN_EPI_DIVIDE: fx_rows_run<H, 2, MVN_EPI_DIVIDE, Ctx, true>(p, t, ntiles, l, *ctx); break;
-          case MVN_EPI_DIVIDE_U16: fx_rows_run<H, 2, MVN_EPI_DIVIDE_U16, Ctx, true>(p, t, ntiles, l, *ctx); break;
-          case MVN_EPI_DIVIDE_NM: fx_rows_run_nm<H, 2, MVN_EPI_DIVIDE_NM, NCtx, true>(p, t, ntiles, l, *nctx); break;
-          case MVN_EPI_DIVIDE_NM_U16: fx_rows_run_nm<H, 2, MVN_EPI_DIVIDE_NM_U16, NCtx, true>(p, t, ntiles, l, *nctx); break;
-          case MVN_EPI_UPDATE: fx_rows_run<H, 2, MVN_EPI_UPDATE, Ctx, true>(p, t, ntiles, l, *ctx); break;
-          case MVN_EPI_UPDATE_STATS: fx_rows_run_stats<H, 2, SCtx, true>(p, t, ntiles, l, *sctx); break;
-          case MVN_EPI_UPDATE_TV: fx_rows_run<H, 2, MVN_EPI_UPDATE_TV, Ctx, true>(p, t, ntiles, l, *ctx); break;
-          case MVN_EPI_UPDATE_STATS_TV: fx_rows_run_stats<H, 2, SCtx, true, MVN_EPI_UPDATE_STATS_TV>(p, t, ntiles, l, *sctx); break;
-          default: fx_rows_run<H, 2, MVN_EPI_STORE, Ctx, true>(p, t, ntiles, l, *ctx); break;
-        }
+        rows_c2r_even_body<T, true, FORM>(p, t, 0, 1, l);  // (even extents only: Plan3D::rows_c2r_r2c)
       }
     }
   }
+}
+
+// The three last-axis passes, as in the product: the families in their order - line layout, wave rows, fixed length,
+// run-time radix - each behind the one dispatch of the launch's mode (mvn_pass_bodies.hpp)
+template <int KIND>
+static void emu_rows(const RowsParams& p0, bool even, long ntiles, size_t lds_bytes) {
+  RowsParams p = p0;
+  if (KIND != MVN_PASS_R2C) mvn_arm_poison(p.epi);  // (the device kernels do this at their entry)
+  const int mode = p.epi.mode;
+  if (p.lines) {  // (H = 256: d2 = 512)
+    fx_rows_lines_check(p, ntiles);
+    return mvn_epi_dispatch<KIND>(mode, [&](auto epi) { emu_rows_fixed_run<256, KIND, decltype(epi)::value, true>(p, ntiles); });
+  }
+  if (emu_wave_rows(p, mvn_wave_rows_kind_bit(KIND, mode)))
+    return mvn_epi_dispatch<KIND>(mode, [&](auto epi) { emu_wave_rows_run<KIND, decltype(epi)::value>(p); });
+  if (p.fixed) {
+    switch (p.h) {
+#define X(H)                                                                                     \
+  case H:                                                                                        \
+    return mvn_epi_dispatch<KIND>(mode, [&](auto epi) {                                          \
+      emu_rows_fixed_run<H, KIND, decltype(epi)::value, false>(p, emu_rows_grid<H>(ntiles));     \
+    });
+      MVN_FIXED_ROWS_LENGTHS(X)
+#undef X
+      default: throw std::invalid_argument("mvn: no fixed kernel");
+    }
+  }
+  mvn_epi_dispatch<KIND, true>(mode, [&](auto form) {
+    mvn_dispatch_tile_width(p.T, [&](auto t) {
+      emu_rows_generic_run<KIND, decltype(t)::value, decltype(form)::value>(p, even, ntiles, lds_bytes);
+    });
+  });
+}
+
+void launch_rows_r2c(const RowsParams& p, bool even, long ntiles, int, size_t lds_bytes, stream_t) {
+  emu_rows<MVN_PASS_R2C>(p, even, ntiles, lds_bytes);
+}
+void launch_rows_c2r(const RowsParams& p, bool even, long ntiles, int, size_t lds_bytes, stream_t) {
+  emu_rows<MVN_PASS_C2R>(p, even, ntiles, lds_bytes);
+}
+void launch_rows_c2r_r2c(const RowsParams& p, long ntiles, int, size_t lds_bytes, stream_t) {
+  emu_rows<MVN_PASS_C2R_R2C>(p, true, ntiles, lds_bytes);
 }
 
 static std::atomic<long> g_mid_fused_launches{0};
@@ -276,7 +271,6 @@ static void emu_mid_fused(const MidFusedParams& p) {
     for (long b = 0; b < blocks; ++b) mf_body<K>(p, b, lds.data(), *ctx);
   }
 }
-#define MVN_MF_TAP_COUNTS(X) X(1) X(3) X(5) X(7) X(9) X(11) X(13) X(15) X(17) X(19) X(21) X(23) X(25) X(27) X(29) X(31)
 void launch_mid_fused(const MidFusedParams& p, stream_t) {
   mf_check(p);
   if (p.mode == MF_TAPS) {
@@ -297,110 +291,6 @@ void launch_mid_fused(const MidFusedParams& p, stream_t) {
     MVN_MF_TAP_COUNTS(X)
 #undef X
     default: throw std::invalid_argument("mvn: no fused middle pass for this tap count");
-  }
-}
-
-template <int H>
-static void emu_rows_fused(const RowsParams& p, long ntiles) {
-  typedef FxCtx<FxRowsRegs<H>, FxRowsCfg<H>::NT> Ctx;
-  typedef FxCtx<FxRowsStatRegs<H>, FxRowsCfg<H>::NT> SCtx;  // (MVN_EPI_UPDATE_STATS)
-  typedef FxCtx<FxRowsNmRegs<H>, FxRowsCfg<H>::NT> NCtx;    // (MVN_EPI_DIVIDE_NM)
-  const long grid = emu_rows_grid<H>(ntiles);
-#pragma omp parallel
-  {
-    std::vector<char> lds(sizeof(cfloat) * FxRowsCfg<H>::lds_cfloats + 64);
-    std::unique_ptr<Ctx> ctx(new Ctx());
-    std::unique_ptr<SCtx> sctx(new SCtx());
-    std::unique_ptr<NCtx> nctx(new NCtx());
-#pragma omp for schedule(static)
-    for (long t = 0; t < grid; ++t) {
-      cfloat* l = (cfloat*)lds.data();
-      switch (p.epi.mode) {
-        case MVN_EPI_DIVIDE: fx_rows_run<H, 2, MVN_EPI_DIVIDE>(p, t, grid, l, *ctx); break;
-        case MVN_EPI_DIVIDE_U16: fx_rows_run<H, 2, MVN_EPI_DIVIDE_U16>(p, t, grid, l, *ctx); break;
-        case MVN_EPI_DIVIDE_NM: fx_rows_run_nm<H, 2, MVN_EPI_DIVIDE_NM, NCtx>(p, t, grid, l, *nctx); break;
-        case MVN_EPI_DIVIDE_NM_U16: fx_rows_run_nm<H, 2, MVN_EPI_DIVIDE_NM_U16, NCtx>(p, t, grid, l, *nctx); break;
-        case MVN_EPI_UPDATE: fx_rows_run<H, 2, MVN_EPI_UPDATE>(p, t, grid, l, *ctx); break;
-        case MVN_EPI_UPDATE_STATS: fx_rows_run_stats<H, 2, SCtx>(p, t, grid, l, *sctx); break;
-        case MVN_EPI_UPDATE_TV: fx_rows_run<H, 2, MVN_EPI_UPDATE_TV>(p, t, grid, l, *ctx); break;
-        case MVN_EPI_UPDATE_STATS_TV: fx_rows_run_stats<H, 2, SCtx, false, MVN_EPI_UPDATE_STATS_TV>(p, t, grid, l, *sctx); break;
-        default: fx_rows_run<H, 2, MVN_EPI_STORE>(p, t, grid, l, *ctx); break;
-      }
-    }
-  }
-}
-
-void launch_rows_c2r_r2c(const RowsParams& p0, long ntiles, int, size_t lds_bytes, stream_t) {
-  RowsParams p = p0;
-  mvn_arm_poison(p.epi);  // (the device kernels do this at their entry)
-  if (p.lines) return emu_rows_lines(p, ntiles, 2);
-  if (emu_wave_rows(p, mvn_epi_divides(p.epi.mode) ? 4 : 8)) return emu_wave_rows_mode<MVN_WR_C2R_R2C>(p);
-  if (!p.fixed) {  // run-time-radix form of the fused pass (any even d2)
-#pragma omp parallel
-    {
-      std::vector<char> lds(lds_bytes + 64);
-#pragma omp for schedule(static)
-      for (long t = 0; t < ntiles; ++t) {
-        cfloat* l = (cfloat*)lds.data();
-        if (p.epi.mode == MVN_EPI_UPDATE_STATS) {
-          MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, true, true>(p, t, 0, 1, l)));
-        } else if (p.epi.mode == MVN_EPI_UPDATE_STATS_TV) {
-          MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, true, true, false, true>(p, t, 0, 1, l)));
-        } else if (p.epi.mode == MVN_EPI_UPDATE_TV) {
-          MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, true, false, false, true>(p, t, 0, 1, l)));
-        } else if (p.epi.mode == MVN_EPI_DIVIDE_NM) {
-          MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, true, false, false, false, true>(p, t, 0, 1, l)));
-        } else if (p.epi.mode == MVN_EPI_DIVIDE_NM_U16) {
-          MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, true, false, true, false, true>(p, t, 0, 1, l)));
-        } else if (p.epi.mode == MVN_EPI_DIVIDE_U16) {
-          MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, true, false, true>(p, t, 0, 1, l)));
-        } else {
-          MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, true>(p, t, 0, 1, l)));
-        }
-      }
-    }
-    return;
-  }
-  switch (p.h) {
-#define X(H) case H: emu_rows_fused<H>(p, ntiles); return;
-    MVN_FIXED_ROWS_LENGTHS(X)
-#undef X
-    default: throw std::invalid_argument("mvn: no fixed kernel");
-  }
-}
-
-template <int H>
-static void emu_rows_fixed(const RowsParams& p, long ntiles, bool r2c) {
-  typedef FxCtx<FxRowsRegs<H>, FxRowsCfg<H>::NT> Ctx;
-  typedef FxCtx<FxRowsStatRegs<H>, FxRowsCfg<H>::NT> SCtx;  // (MVN_EPI_UPDATE_STATS)
-  typedef FxCtx<FxRowsNmRegs<H>, FxRowsCfg<H>::NT> NCtx;    // (MVN_EPI_DIVIDE_NM)
-  const long grid = emu_rows_grid<H>(ntiles);
-#pragma omp parallel
-  {
-    std::vector<char> lds(sizeof(cfloat) * FxRowsCfg<H>::lds_cfloats + 64);
-    std::unique_ptr<Ctx> ctx(new Ctx());
-    std::unique_ptr<SCtx> sctx(new SCtx());
-    std::unique_ptr<NCtx> nctx(new NCtx());
-#pragma omp for schedule(static)
-    for (long t = 0; t < grid; ++t) {
-      cfloat* l = (cfloat*)lds.data();
-      if (r2c)
-        fx_rows_run<H, 0, MVN_EPI_STORE>(p, t, grid, l, *ctx);
-      else {
-        switch (p.epi.mode) {
-          case MVN_EPI_DIVIDE: fx_rows_run<H, 1, MVN_EPI_DIVIDE>(p, t, grid, l, *ctx); break;
-          case MVN_EPI_DIVIDE_U16: fx_rows_run<H, 1, MVN_EPI_DIVIDE_U16>(p, t, grid, l, *ctx); break;
-          case MVN_EPI_DIVIDE_NM: fx_rows_run_nm<H, 1, MVN_EPI_DIVIDE_NM, NCtx>(p, t, grid, l, *nctx); break;
-          case MVN_EPI_DIVIDE_NM_U16: fx_rows_run_nm<H, 1, MVN_EPI_DIVIDE_NM_U16, NCtx>(p, t, grid, l, *nctx); break;
-          case MVN_EPI_UPDATE: fx_rows_run<H, 1, MVN_EPI_UPDATE>(p, t, grid, l, *ctx); break;
-          case MVN_EPI_UPDATE_STATS: fx_rows_run_stats<H, 1, SCtx>(p, t, grid, l, *sctx); break;
-          case MVN_EPI_UPDATE_TV: fx_rows_run<H, 1, MVN_EPI_UPDATE_TV>(p, t, grid, l, *ctx); break;
-          case MVN_EPI_UPDATE_STATS_TV: fx_rows_run_stats<H, 1, SCtx, false, MVN_EPI_UPDATE_STATS_TV>(p, t, grid, l, *sctx); break;
-          case MVN_EPI_DELTA: fx_rows_run<H, 1, MVN_EPI_DELTA>(p, t, grid, l, *ctx); break;
-          default: fx_rows_run<H, 1, MVN_EPI_STORE>(p, t, grid, l, *ctx); break;
-        }
-      }
-    }
   }
 }
 
@@ -427,16 +317,11 @@ long split_launch_count() { return g_split_launches.load(); }
 
 template <int N>
 static bool emu_try_split(int mode, const StridedParams& p, long nblocks) {
+  StridedParams q;
+  if (!fx_split_retile<N>(mode, p, nblocks, q)) return false;
   if constexpr (FxSplitCfg<N>::USE) {
     typedef FxSplitCfg<N> C;
-    if (mode == MVN_ST_FWD_MUL_INV || p.cstride != 1 || p.ncols % C::T != 0 || p.tiles_per_outer < 1)
-      return false;
-    StridedParams q = p;
-    const long outer = nblocks / p.tiles_per_outer;
-    q.tiles_per_outer = p.ncols / C::T;
-    q.T = q.TP = C::T;
-    const long nb = outer * q.tiles_per_outer;
-    q.nblocks = nb;
+    const long nb = q.nblocks;
     ++g_split_launches;
     const long grid = nb > 1 ? (nb + 1) / 2 : 1;
     typedef FxCtx<FxSplitRegs<N>, C::NT> Ctx;
@@ -452,11 +337,8 @@ static bool emu_try_split(int mode, const StridedParams& p, long nblocks) {
           fx_strided_split_body<N, MVN_ST_INV>(q, b, nb, grid, (cfloat*)lds.data(), *ctx);
       }
     }
-    return true;
-  } else {
-    (void)mode; (void)p; (void)nblocks;
-    return false;
   }
+  return true;
 }
 
 template <int N>
@@ -467,105 +349,12 @@ static void emu_strided_fixed(int mode, const StridedParams& p, long nblocks) {
   if (mode == MVN_ST_FWD_MUL_INV) emu_strided_fixed_mode<N, MVN_ST_FWD_MUL_INV>(p, nblocks);
 }
 
-static bool emu_rows_fixed_dispatch(const RowsParams& p, long ntiles, bool r2c) {
-  switch (p.h) {
-#define X(H) case H: emu_rows_fixed<H>(p, ntiles, r2c); return true;
-    MVN_FIXED_ROWS_LENGTHS(X)
-#undef X
-    default: return false;
-  }
-}
-
 static bool emu_strided_fixed_dispatch(int mode, const StridedParams& p, long nblocks) {
   switch (p.ax.n) {
 #define X(N) case N: emu_strided_fixed<N>(mode, p, nblocks); return true;
     MVN_FIXED_STRIDED_LENGTHS(X)
 #undef X
     default: return false;
-  }
-}
-
-void launch_rows_r2c(const RowsParams& p, bool even, long ntiles, int, size_t lds_bytes,
-                     stream_t) {
-  if (p.lines) return emu_rows_lines(p, ntiles, 0);
-  if (emu_wave_rows(p, 1)) return emu_wave_rows_run<MVN_WR_R2C, MVN_EPI_STORE>(p);
-  if (p.fixed) {
-    if (!emu_rows_fixed_dispatch(p, ntiles, true)) throw std::invalid_argument("mvn: no fixed kernel");
-    return;
-  }
-#pragma omp parallel
-  {
-    std::vector<char> lds(lds_bytes + 64);
-#pragma omp for schedule(static)
-    for (long t = 0; t < ntiles; ++t) {
-      cfloat* l = (cfloat*)lds.data();
-      if (even) {
-        MVN_DISPATCH_T(p.T, rows_r2c_even_body<TT>(p, t, 0, 1, l));
-      } else {
-        MVN_DISPATCH_T(p.T, rows_r2c_odd_body<TT>(p, t, 0, 1, l));
-      }
-    }
-  }
-}
-
-void launch_rows_c2r(const RowsParams& p0, bool even, long ntiles, int, size_t lds_bytes,
-                     stream_t) {
-  RowsParams p = p0;
-  mvn_arm_poison(p.epi);
-  if (p.lines) return emu_rows_lines(p, ntiles, 1);
-  if (emu_wave_rows(p, p.epi.mode == MVN_EPI_DELTA ? 16 : 2)) return emu_wave_rows_mode<MVN_WR_C2R>(p);
-  if (p.fixed) {
-    if (!emu_rows_fixed_dispatch(p, ntiles, false)) throw std::invalid_argument("mvn: no fixed kernel");
-    return;
-  }
-#pragma omp parallel
-  {
-    std::vector<char> lds(lds_bytes + 64);
-#pragma omp for schedule(static)
-    for (long t = 0; t < ntiles; ++t) {
-      cfloat* l = (cfloat*)lds.data();
-      if (p.epi.mode == MVN_EPI_UPDATE_STATS) {
-        if (even) {
-          MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, false, true>(p, t, 0, 1, l)));
-        } else {
-          MVN_DISPATCH_T(p.T, (rows_c2r_odd_body<TT, true>(p, t, 0, 1, l)));
-        }
-      } else if (p.epi.mode == MVN_EPI_UPDATE_STATS_TV) {
-        if (even) {
-          MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, false, true, false, true>(p, t, 0, 1, l)));
-        } else {
-          MVN_DISPATCH_T(p.T, (rows_c2r_odd_body<TT, true, false, true>(p, t, 0, 1, l)));
-        }
-      } else if (p.epi.mode == MVN_EPI_UPDATE_TV) {
-        if (even) {
-          MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, false, false, false, true>(p, t, 0, 1, l)));
-        } else {
-          MVN_DISPATCH_T(p.T, (rows_c2r_odd_body<TT, false, false, true>(p, t, 0, 1, l)));
-        }
-      } else if (p.epi.mode == MVN_EPI_DIVIDE_NM) {
-        if (even) {
-          MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, false, false, false, false, true>(p, t, 0, 1, l)));
-        } else {
-          MVN_DISPATCH_T(p.T, (rows_c2r_odd_body<TT, false, false, false, true>(p, t, 0, 1, l)));
-        }
-      } else if (p.epi.mode == MVN_EPI_DIVIDE_NM_U16) {
-        if (even) {
-          MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, false, false, true, false, true>(p, t, 0, 1, l)));
-        } else {
-          MVN_DISPATCH_T(p.T, (rows_c2r_odd_body<TT, false, true, false, true>(p, t, 0, 1, l)));
-        }
-      } else if (p.epi.mode == MVN_EPI_DIVIDE_U16) {
-        if (even) {
-          MVN_DISPATCH_T(p.T, (rows_c2r_even_body<TT, false, false, true>(p, t, 0, 1, l)));
-        } else {
-          MVN_DISPATCH_T(p.T, (rows_c2r_odd_body<TT, false, true>(p, t, 0, 1, l)));
-        }
-      } else if (even) {
-        MVN_DISPATCH_T(p.T, rows_c2r_even_body<TT>(p, t, 0, 1, l));
-      } else {
-        MVN_DISPATCH_T(p.T, rows_c2r_odd_body<TT>(p, t, 0, 1, l));
-      }
-    }
   }
 }
 
@@ -582,8 +371,7 @@ void launch_nm_reduce(const double* rec, const unsigned* counts, int nviews, lon
 
 void launch_strided(int mode, const StridedParams& p, long nblocks, int, size_t lds_bytes,
                     stream_t, const StridedParams* rider, size_t rider_lds) {
-  if (rider && (!p.fixed || mode == MVN_ST_FWD_MUL_INV || rider->T != 1 || rider->fixed || rider_lds > 160 * 1024))
-    throw std::invalid_argument("mvn: Nyquist lines ride only in the plain fixed-length strided passes, one per workgroup");
+  mvn_strided_rider_check(mode, p, rider, rider_lds);
   if (p.fixed) {
     if (!emu_strided_fixed_dispatch(mode, p, nblocks)) throw std::invalid_argument("mvn: no fixed kernel");
     if (rider) {  // the workgroups behind the walkers: one line each
@@ -603,28 +391,25 @@ void launch_strided(int mode, const StridedParams& p, long nblocks, int, size_t 
     }
     return;
   }
+  mvn_dispatch_tile_width(p.T, [&](auto tt) {
+    constexpr int T = decltype(tt)::value;
 #pragma omp parallel
-  {
-    std::vector<char> lds(lds_bytes + 64);
+    {
+      std::vector<char> lds(lds_bytes + 64);
 #pragma omp for schedule(static)
-    for (long b = 0; b < nblocks; ++b) {
-      cfloat* l = (cfloat*)lds.data();
-      if (mode == MVN_ST_FWD) { MVN_DISPATCH_T(p.T, (strided_body<MVN_ST_FWD, TT, true>(p, b, 0, 1, l))); }
-      if (mode == MVN_ST_INV) { MVN_DISPATCH_T(p.T, (strided_body<MVN_ST_INV, TT, true>(p, b, 0, 1, l))); }
-      if (mode == MVN_ST_FWD_MUL_INV) { MVN_DISPATCH_T(p.T, (strided_body<MVN_ST_FWD_MUL_INV, TT, true>(p, b, 0, 1, l))); }
+      for (long b = 0; b < nblocks; ++b) {
+        cfloat* l = (cfloat*)lds.data();
+        if (mode == MVN_ST_FWD) strided_body<MVN_ST_FWD, T, true>(p, b, 0, 1, l);
+        if (mode == MVN_ST_INV) strided_body<MVN_ST_INV, T, true>(p, b, 0, 1, l);
+        if (mode == MVN_ST_FWD_MUL_INV) strided_body<MVN_ST_FWD_MUL_INV, T, true>(p, b, 0, 1, l);
+      }
     }
-  }
+  });
 }
 
 void launch_dim0_direct(const Dim0DirectParams& p, stream_t) {
-  if (!mvn_dim0_direct_possible(p.k, p.d0) || p.kd < p.k + 1 || p.h != p.k / 2 || p.plane < 0 || p.plane + p.plane2 < 1 || (p.plane > 0 && p.in == p.out) ||
-      p.plane2 < 0 || (p.plane2 > 0 && (!p.in2 || !p.out2 || !p.taps2 || p.in2 == p.out2)))
-    throw std::invalid_argument("mvn: direct dim0 convolution called outside its range");
+  mvn_dim0_check(p);
   if (p.packed) {
-    if (!p.inv1 || !p.taps2 || (long)p.C * p.d1 != p.plane)
-      throw std::invalid_argument("mvn: packed direct dim0 convolution needs the dim1 tables and the Nyquist taps");
-    if (mvn_dim0_dc_lds_bytes(p.d0, p.k) > 64 * 1024)  // the device launch's limit
-      throw std::invalid_argument("mvn: dim0 too long for the packed DC column");
 #pragma omp parallel
     {
       std::vector<cfloat> lds(2 * (size_t)p.d0 + 2 * (size_t)p.k);
@@ -695,16 +480,8 @@ void reflect_counters(long long out[2]) {
   out[1] = g_reflect_volumes.load();
 }
 
-static void check_reflect(const ReflectParams& p) {
-  const int D[3] = {p.D0, p.D1, p.D2}, n[3] = {p.n0, p.n1, p.n2}, o[3] = {p.o0, p.o1, p.o2};
-  for (int d = 0; d < 3; ++d)
-    if (n[d] < 1 || o[d] < 0 || (long)o[d] + n[d] > D[d] || n[d] > 0x3fffffff)
-      throw std::invalid_argument("mvn: reflect fill: the window does not fit the volume");
-  if (!p.vol || p.RP < p.D2 || (p.RP & 1)) throw std::invalid_argument("mvn: reflect fill: bad volume");
-}
-
 void launch_reflect_fill(const ReflectParams& p0, bool u16, stream_t) {
-  check_reflect(p0);
+  mvn_reflect_check(p0);
   ReflectParams p = p0;
   for (int axis = 2; axis >= 0; --axis) {
     p.axis = axis;
@@ -729,32 +506,8 @@ void resample_counters(long long out[2]) {
   out[1] = g_normalize_launches.load();
 }
 
-static void check_window(const char* what, long RP, int D0, int D1, const int n[3], const int o[3]) {
-  const long D[3] = {D0, D1, RP};
-  for (int d = 0; d < 3; ++d)
-    if (n[d] < 1 || o[d] < 0 || (long)o[d] + n[d] > D[d])
-      throw std::invalid_argument(std::string("mvn: ") + what + ": the window does not fit the volume");
-  if (RP < 2 || (RP & 1)) throw std::invalid_argument(std::string("mvn: ") + what + ": bad volume");
-}
-
-static void check_resample(const ResampleParams& p) {
-  const int n[3] = {p.n0, p.n1, p.n2}, o[3] = {p.o0, p.o1, p.o2};
-  check_window("resample", p.RP, p.D0, p.D1, n, o);
-  if (!p.image || !p.src) throw std::invalid_argument("mvn: resample: null pointer");
-  if (p.s0 < 0 || p.s1 < 0 || p.s2 < 0) throw std::invalid_argument("mvn: resample: negative stride");
-  for (int k = 0; k < 3; ++k)
-    if (p.g.m[k] < 1) throw std::invalid_argument("mvn: resample: raw extents must be >= 1");
-}
-
-static void check_normalize(const NormalizeParams& p) {
-  const int n[3] = {p.n0, p.n1, p.n2}, o[3] = {p.o0, p.o1, p.o2};
-  // (the last plane's rows are all the launch needs of D0)
-  check_window("normalise", p.RP, p.o0 + p.n0, p.D1, n, o);
-  if (!p.vols || p.V < 1) throw std::invalid_argument("mvn: normalise: no volumes");
-}
-
 void launch_resample(const ResampleParams& p, bool u16, stream_t) {
-  check_resample(p);
+  mvn_resample_check(p);
   const long nblocks = mvn_resample_blocks(p);
   ++g_resample_launches;
 #pragma omp parallel for schedule(static)
@@ -768,7 +521,7 @@ void launch_resample(const ResampleParams& p, bool u16, stream_t) {
 }
 
 void launch_weights_normalize(const NormalizeParams& p, stream_t) {
-  check_normalize(p);
+  mvn_normalize_check(p);
   const long nblocks = mvn_normalize_blocks(p);
   ++g_normalize_launches;
 #pragma omp parallel for schedule(static)

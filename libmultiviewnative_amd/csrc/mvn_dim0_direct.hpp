@@ -23,6 +23,8 @@
 //   x_j = in[z + h - j] (j = -PF .. K-1) sits in slot (j + PF - u) mod (K + PF) at unrolled step u.
 #pragma once
 
+#include <stdexcept>
+
 #include "mvn_fft_core.hpp"
 
 #define MVN_D0_MAX_PEERS 7  // further slabs of one volume a launch reports non-finite inputs to
@@ -158,6 +160,21 @@ inline int mvn_dim0_pairs(int d1) { return d1 / 2 + 1; }
 // 64 KB of dynamic LDS, 4062 planes at 33 taps.  Longer volumes keep the separate Nyquist plane.
 inline size_t mvn_dim0_dc_lds_bytes(int d0, int k) { return sizeof(cfloat) * (2 * (size_t)d0 + 2 * (size_t)k); }
 inline bool mvn_dim0_packed_possible(int d0) { return mvn_dim0_dc_lds_bytes(d0, MVN_D0_MAX_TAPS) <= 64 * 1024; }
+
+// what a launch of the leg must hold, in both backends
+inline void mvn_dim0_check(const Dim0DirectParams& p) {
+  if (!mvn_dim0_direct_possible(p.k, p.d0) || p.kd < p.k + 1 || p.h != p.k / 2 || p.plane < 0 || p.plane + p.plane2 < 1 ||
+      (p.plane > 0 && p.in == p.out) || p.plane2 < 0 ||
+      (p.plane2 > 0 && (!p.in2 || !p.out2 || !p.taps2 || p.in2 == p.out2)))
+    throw std::invalid_argument("mvn: direct dim0 convolution called outside its range");
+  if (p.plane + p.plane2 >= (1L << 28)) throw std::invalid_argument("mvn: plane too large for the direct dim0 leg");
+  if (p.packed) {
+    if (!p.inv1 || !p.taps2 || p.C < 1 || p.d1 < 1 || (long)p.C * p.d1 != p.plane)
+      throw std::invalid_argument("mvn: packed direct dim0 convolution needs the dim1 tables and the Nyquist taps");
+    if (mvn_dim0_dc_lds_bytes(p.d0, p.k) > 64 * 1024)  // (the dynamic LDS of a DC-pair workgroup)
+      throw std::invalid_argument("mvn: dim0 too long for the packed DC column");
+  }
+}
 
 // One pair per workgroup, two phases around a workgroup barrier.  lds: 2 * d0 + 2 * k cfloats.
 MVN_HD void mvn_dim0_dc_load(const Dim0DirectParams& P, int pair, cfloat* lds, int tid, int nthreads) {

@@ -807,6 +807,21 @@ struct FxSplitCfg {
   static_assert(!USE || sizeof(cfloat) * lds_cfloats <= 160 * 1024, "window does not fit the LDS");
 };
 
+// Long lines: a plain strided launch planned for the 8-column kernel (p, nblocks) re-tiled into FxSplitCfg<N>::T
+// columns for the split-window body (q, q.nblocks) when the columns divide; false: not this body.
+template <int N>
+inline bool fx_split_retile(int mode, const StridedParams& p, long nblocks, StridedParams& q) {
+  typedef FxSplitCfg<N> C;
+  if (!C::USE || mode == MVN_ST_FWD_MUL_INV || p.cstride != 1 || p.ncols % C::T != 0 || p.tiles_per_outer < 1)
+    return false;
+  q = p;
+  const long outer = nblocks / p.tiles_per_outer;
+  q.tiles_per_outer = p.ncols / C::T;
+  q.T = q.TP = C::T;
+  q.nblocks = outer * q.tiles_per_outer;
+  return true;
+}
+
 template <int N>
 struct FxSplitRegs {
   qfloat a[8 * FxSplitCfg<N>::IT0];  // the whole tile: rows j2 + k M0 of IT0 work items
@@ -1598,26 +1613,6 @@ constexpr bool fx_rows_lines_ok() {
   return H == 256 && !FxRowsCfg<H>::WALK && FxRowsCfg<H>::T == 16 && FxRowsCfg<H>::EXACT;
 }
 
-template <int H, int KIND, int EPI, typename Ctx, bool LINES = false>
-MVN_HD void fx_rows_run(const RowsParams& P, long block, long nblocks, cfloat* lds, Ctx& ctx) {
-  if constexpr (LINES) {
-    fx_rows_tile<H, KIND, EPI, Ctx, true>(P, block, lds, ctx);
-    return;
-  }
-  typedef FxRowsCfg<H> C;
-  if constexpr (C::WALK) {
-    constexpr int NT_ = C::NT;
-    (void)NT_;
-    cfloat* tws = lds + C::TILE;
-    cfloat* twr = tws + fx_twsize(H);
-    MVN_PHASE(ctx, (fx_rows_tables<H>(P, tws, twr, tid)));
-    const long ntiles = P.rows / C::T;
-    for (long tile = block; tile < ntiles; tile += nblocks) fx_rows_tile<H, KIND, EPI>(P, tile, lds, ctx);
-  } else {
-    fx_rows_tile<H, KIND, EPI>(P, block, lds, ctx);
-  }
-}
-
 // workgroup end of an UPDATE_STATS launch of the phase-structured kernels: the lanes' accumulators (in their
 // register sets) reduced in a fixed order through the LDS, one record per workgroup
 template <int NT, typename Ctx>
@@ -1631,18 +1626,6 @@ MVN_HD void fx_stat_flush(const MvnStatsParams& s, long block, long nblocks, cfl
     MVN_PHASE(ctx, (mvn_stat_tree_step(l, NT, h, tid)));
   }
   MVN_PHASE_NOSYNC(ctx, (tid == 0 ? mvn_stat_record(s, l, NT, block, nblocks) : (void)0));
-}
-
-// the MVN_EPI_UPDATE_STATS (or MVN_EPI_UPDATE_STATS_TV) workgroup: accumulators zeroed, fx_rows_run, one record
-template <int H, int KIND, typename Ctx, bool LINES = false, int EPI = MVN_EPI_UPDATE_STATS>
-MVN_HD void fx_rows_run_stats(const RowsParams& P, long block, long nblocks, cfloat* lds, Ctx& ctx) {
-  static_assert(mvn_stat_lds_bytes(FxRowsCfg<H>::NT) <= (long)sizeof(cfloat) * FxRowsCfg<H>::lds_cfloats,
-                "statistics scratch exceeds the LDS");
-  constexpr int NT_ = FxRowsCfg<H>::NT;
-  (void)NT_;
-  MVN_PHASE_NOSYNC(ctx, (mvn_stat_init(r.st)));
-  fx_rows_run<H, KIND, EPI, Ctx, LINES>(P, block, nblocks, lds, ctx);
-  fx_stat_flush<FxRowsCfg<H>::NT>(P.st, block, nblocks, lds, ctx);
 }
 
 // the same for the noise-model divide forms: the lanes' {D, Y, M} accumulators, one record per workgroup
@@ -1659,14 +1642,49 @@ MVN_HD void fx_nm_flush(const MvnStatsParams& s, long block, long nblocks, cfloa
   MVN_PHASE_NOSYNC(ctx, (tid == 0 ? mvn_nm_record(s, l, NT, block, nblocks) : (void)0));
 }
 
-template <int H, int KIND, int EPI, typename Ctx, bool LINES = false>
-MVN_HD void fx_rows_run_nm(const RowsParams& P, long block, long nblocks, cfloat* lds, Ctx& ctx) {
-  static_assert(mvn_epi_nm(EPI), "a noise-model divide epilogue");
-  static_assert(mvn_nm_lds_bytes(FxRowsCfg<H>::NT) <= (long)sizeof(cfloat) * FxRowsCfg<H>::lds_cfloats,
+// The one entry to a workgroup of the fixed last-axis kernels, for both backends (KIND: MvnPassKind): its single tile,
+// or (FxRowsCfg<H>::WALK) the tables once and then tiles block, block + nblocks, ...  The register set follows from the
+// mode (FxRowsRegsFor).  The forms that keep statistics zero their accumulators, run the tiles and reduce the
+// accumulators into one record per workgroup.
+// TILES_ONLY is this function's own: no caller sets it.  The statistics forms run their tiles through a second
+// instance of the entry, one inlining level below the plain forms' tiles.  The level matters to the compiler: with the
+// tiles in a helper that every form calls, 37 of the plain kernels come out 4 - 24 bytes longer or shorter (another
+// division multiplier, scalar loads in another place); with the tiles inline for every form, the statistics kernels do.
+template <int H, int KIND, int EPI, bool LINES = false, bool TILES_ONLY = false>
+MVN_HD void fx_rows_workgroup(const RowsParams& P, long block, long nblocks, cfloat* lds,
+                              FxCtx<FxRowsRegsFor<H, EPI>, FxRowsCfg<H>::NT>& ctx) {
+  typedef FxRowsCfg<H> C;
+  typedef FxCtx<FxRowsRegsFor<H, EPI>, C::NT> Ctx;
+  static_assert(mvn_epi_allowed(KIND, EPI), "a mode the pass takes");
+  static_assert(mvn_epi_extra_lds_bytes(EPI, C::NT) <= (long)sizeof(cfloat) * C::lds_cfloats,
                 "statistics scratch exceeds the LDS");
-  constexpr int NT_ = FxRowsCfg<H>::NT;
+  constexpr int NT_ = C::NT;
   (void)NT_;
-  MVN_PHASE_NOSYNC(ctx, (mvn_nm_init(r.nm)));
-  fx_rows_run<H, KIND, EPI, Ctx, LINES>(P, block, nblocks, lds, ctx);
-  fx_nm_flush<FxRowsCfg<H>::NT>(P.st, block, nblocks, lds, ctx);
+  if constexpr (!TILES_ONLY && mvn_epi_stats(EPI)) {
+    MVN_PHASE_NOSYNC(ctx, (mvn_stat_init(r.st)));
+    fx_rows_workgroup<H, KIND, EPI, LINES, true>(P, block, nblocks, lds, ctx);
+    fx_stat_flush<C::NT>(P.st, block, nblocks, lds, ctx);
+  } else if constexpr (!TILES_ONLY && mvn_epi_nm(EPI)) {
+    MVN_PHASE_NOSYNC(ctx, (mvn_nm_init(r.nm)));
+    fx_rows_workgroup<H, KIND, EPI, LINES, true>(P, block, nblocks, lds, ctx);
+    fx_nm_flush<C::NT>(P.st, block, nblocks, lds, ctx);
+  } else if constexpr (LINES) {
+    fx_rows_tile<H, KIND, EPI, Ctx, true>(P, block, lds, ctx);
+  } else if constexpr (C::WALK) {
+    cfloat* tws = lds + C::TILE;
+    cfloat* twr = tws + fx_twsize(H);
+    MVN_PHASE(ctx, (fx_rows_tables<H>(P, tws, twr, tid)));
+    const long ntiles = P.rows / C::T;
+    for (long tile = block; tile < ntiles; tile += nblocks) fx_rows_tile<H, KIND, EPI>(P, tile, lds, ctx);
+  } else {
+    fx_rows_tile<H, KIND, EPI>(P, block, lds, ctx);
+  }
+}
+
+// a line-layout launch (H = 256: d2 = 512) of `ntiles` workgroups
+inline void fx_rows_lines_check(const RowsParams& p, long ntiles) {
+  constexpr int H = 256;
+  if (!fx_rows_lines_ok<H>() || !p.fixed || p.h != H || p.C != H || !p.nyq_packed || p.lines_d1 < 1 ||
+      p.lines_d1 % FxRowsCfg<H>::T || p.row_base % FxRowsCfg<H>::T || p.rows != ntiles * FxRowsCfg<H>::T)
+    throw std::invalid_argument("mvn: line-layout last-axis pass outside its range");
 }

@@ -53,87 +53,27 @@ __global__ void __launch_bounds__(512) k_rows_r2c(const RowsParams p) {
     rows_r2c_odd_body<T>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
 }
 
-template <bool EVEN, int T>
+// FORM: the form of the launch's mode in the run-time-radix bodies (mvn_epi_generic_form)
+template <bool EVEN, int T, int FORM>
 __global__ void __launch_bounds__(512) k_rows_c2r(const RowsParams p) {
   extern __shared__ __attribute__((aligned(16))) char mvn_smem[];
   if (EVEN)
-    rows_c2r_even_body<T>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
+    rows_c2r_even_body<T, false, FORM>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
   else
-    rows_c2r_odd_body<T>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
+    rows_c2r_odd_body<T, FORM>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
 }
-// the same with the update epilogue that also keeps the convergence statistics (MVN_EPI_UPDATE_STATS)
-template <bool EVEN, int T>
-__global__ void __launch_bounds__(512) k_rows_c2r_stats(const RowsParams p) {
+// run-time-radix form of the fused c2r + pointwise + r2c pass (any even d2)
+template <int T, int FORM>
+__global__ void __launch_bounds__(512) k_rows_c2r_r2c(const RowsParams p) {
   extern __shared__ __attribute__((aligned(16))) char mvn_smem[];
-  if (EVEN)
-    rows_c2r_even_body<T, false, true>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
-  else
-    rows_c2r_odd_body<T, true>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
+  rows_c2r_even_body<T, true, FORM>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
 }
 
-// the divide epilogue on a view held as uint16 (MVN_EPI_DIVIDE_U16), plain and fused
-template <bool EVEN, int T>
-__global__ void __launch_bounds__(512) k_rows_c2r_u16(const RowsParams p) {
-  extern __shared__ __attribute__((aligned(16))) char mvn_smem[];
-  if (EVEN)
-    rows_c2r_even_body<T, false, false, true>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
-  else
-    rows_c2r_odd_body<T, false, true>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
-}
-template <int T>
-__global__ void __launch_bounds__(512) k_rows_c2r_r2c_u16(const RowsParams p) {
-  extern __shared__ __attribute__((aligned(16))) char mvn_smem[];
-  rows_c2r_even_body<T, true, false, true>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
-}
-
-// the update epilogue on the integral times the total-variation factor (MVN_EPI_UPDATE_TV, MVN_EPI_UPDATE_STATS_TV),
-// plain and fused
-template <bool EVEN, int T, bool STATS>
-__global__ void __launch_bounds__(512) k_rows_c2r_tv(const RowsParams p) {
-  extern __shared__ __attribute__((aligned(16))) char mvn_smem[];
-  if (EVEN)
-    rows_c2r_even_body<T, false, STATS, false, true>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
-  else
-    rows_c2r_odd_body<T, STATS, false, true>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
-}
-template <int T, bool STATS>
-__global__ void __launch_bounds__(512) k_rows_c2r_r2c_tv(const RowsParams p) {
-  extern __shared__ __attribute__((aligned(16))) char mvn_smem[];
-  rows_c2r_even_body<T, true, STATS, false, true>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
-}
-
-// the noise-model divide epilogue (MVN_EPI_DIVIDE_NM, MVN_EPI_DIVIDE_NM_U16), plain and fused
-template <bool EVEN, int T, bool U16>
-__global__ void __launch_bounds__(512) k_rows_c2r_nm(const RowsParams p) {
-  extern __shared__ __attribute__((aligned(16))) char mvn_smem[];
-  if (EVEN)
-    rows_c2r_even_body<T, false, false, U16, false, true>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
-  else
-    rows_c2r_odd_body<T, false, U16, false, true>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
-}
-template <int T, bool U16>
-__global__ void __launch_bounds__(512) k_rows_c2r_r2c_nm(const RowsParams p) {
-  extern __shared__ __attribute__((aligned(16))) char mvn_smem[];
-  rows_c2r_even_body<T, true, false, U16, false, true>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
-}
 // once per sweep with the noise model on: workgroup v sums the records of view v's divide pass -> out + 3 v = {D, Y, M}
 __global__ void __launch_bounds__(256) k_nm_reduce(const double* rec, const unsigned* counts, long cap, double* out) {
   __shared__ double lds[3 * 256];
   const long v = (long)blockIdx.x;
   mvn_nm_reduce_body(rec + 3 * v * cap, counts + v, cap, out + 3 * v, lds, (int)threadIdx.x, (int)blockDim.x);
-}
-
-// NYQ only tags the launches that work on the Nyquist plane, so that profilers list them apart
-// run-time-radix form of the fused c2r + pointwise + r2c pass (any even d2)
-template <int T>
-__global__ void __launch_bounds__(512) k_rows_c2r_r2c(const RowsParams p) {
-  extern __shared__ __attribute__((aligned(16))) char mvn_smem[];
-  rows_c2r_even_body<T, true>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
-}
-template <int T>
-__global__ void __launch_bounds__(512) k_rows_c2r_r2c_stats(const RowsParams p) {
-  extern __shared__ __attribute__((aligned(16))) char mvn_smem[];
-  rows_c2r_even_body<T, true, true>(p, (long)blockIdx.x, (int)threadIdx.x, (int)blockDim.x, (cfloat*)mvn_smem);
 }
 
 // once per sweep with statistics on: the records of the sweep's view updates -> {S, M, P} (mvn_pass_bodies.hpp)
@@ -143,6 +83,7 @@ __global__ void __launch_bounds__(256) k_convergence_reduce(const double* rec, c
   mvn_convergence_reduce_body(rec, counts, nviews, cap, out, lds, (int)threadIdx.x, (int)blockDim.x);
 }
 
+// NYQ only tags the launches that work on the Nyquist plane, so that profilers list them apart
 template <int MODE, int T, bool NYQ>
 __global__ void __launch_bounds__(512) k_strided(const StridedParams p) {
   extern __shared__ __attribute__((aligned(16))) char mvn_smem[];
@@ -154,10 +95,9 @@ __global__ void __launch_bounds__(512) k_strided(const StridedParams p) {
 template <int H, bool LINES = false>
 __global__ void __launch_bounds__(FxRowsCfg<H>::NT) kx_rows_r2c(const RowsParams p) {
   extern __shared__ __attribute__((aligned(16))) char mvn_smem[];
-  typedef FxCtx<FxRowsRegs<H>, FxRowsCfg<H>::NT> Ctx;
-  Ctx ctx;
+  FxCtx<FxRowsRegsFor<H, MVN_EPI_STORE>, FxRowsCfg<H>::NT> ctx;
   ctx.tid = (int)threadIdx.x;
-  fx_rows_run<H, 0, MVN_EPI_STORE, Ctx, LINES>(p, (long)blockIdx.x, (long)gridDim.x, (cfloat*)mvn_smem, ctx);
+  fx_rows_workgroup<H, MVN_PASS_R2C, MVN_EPI_STORE, LINES>(p, (long)blockIdx.x, (long)gridDim.x, (cfloat*)mvn_smem, ctx);
 }
 
 template <int H, int EPI, bool LINES = false>
@@ -165,15 +105,9 @@ __global__ void __launch_bounds__(FxRowsCfg<H>::NT) kx_rows_c2r(const RowsParams
   extern __shared__ __attribute__((aligned(16))) char mvn_smem[];
   RowsParams p = p0;
   mvn_arm_poison(p.epi);
-  typedef FxCtx<FxRowsRegsFor<H, EPI>, FxRowsCfg<H>::NT> Ctx;
-  Ctx ctx;
+  FxCtx<FxRowsRegsFor<H, EPI>, FxRowsCfg<H>::NT> ctx;
   ctx.tid = (int)threadIdx.x;
-  if constexpr (mvn_epi_base(EPI) == MVN_EPI_UPDATE_STATS)
-    fx_rows_run_stats<H, 1, Ctx, LINES, EPI>(p, (long)blockIdx.x, (long)gridDim.x, (cfloat*)mvn_smem, ctx);
-  else if constexpr (mvn_epi_nm(EPI))
-    fx_rows_run_nm<H, 1, EPI, Ctx, LINES>(p, (long)blockIdx.x, (long)gridDim.x, (cfloat*)mvn_smem, ctx);
-  else
-    fx_rows_run<H, 1, EPI, Ctx, LINES>(p, (long)blockIdx.x, (long)gridDim.x, (cfloat*)mvn_smem, ctx);
+  fx_rows_workgroup<H, MVN_PASS_C2R, EPI, LINES>(p, (long)blockIdx.x, (long)gridDim.x, (cfloat*)mvn_smem, ctx);
 }
 
 // (The divide form needs 93 VGPRs, just above the 84 that would let three 512-thread workgroups
@@ -183,15 +117,9 @@ __global__ void __launch_bounds__(FxRowsCfg<H>::NT) kx_rows_c2r_r2c(const RowsPa
   extern __shared__ __attribute__((aligned(16))) char mvn_smem[];
   RowsParams p = p0;
   mvn_arm_poison(p.epi);
-  typedef FxCtx<FxRowsRegsFor<H, EPI>, FxRowsCfg<H>::NT> Ctx;
-  Ctx ctx;
+  FxCtx<FxRowsRegsFor<H, EPI>, FxRowsCfg<H>::NT> ctx;
   ctx.tid = (int)threadIdx.x;
-  if constexpr (mvn_epi_base(EPI) == MVN_EPI_UPDATE_STATS)
-    fx_rows_run_stats<H, 2, Ctx, LINES, EPI>(p, (long)blockIdx.x, (long)gridDim.x, (cfloat*)mvn_smem, ctx);
-  else if constexpr (mvn_epi_nm(EPI))
-    fx_rows_run_nm<H, 2, EPI, Ctx, LINES>(p, (long)blockIdx.x, (long)gridDim.x, (cfloat*)mvn_smem, ctx);
-  else
-    fx_rows_run<H, 2, EPI, Ctx, LINES>(p, (long)blockIdx.x, (long)gridDim.x, (cfloat*)mvn_smem, ctx);
+  fx_rows_workgroup<H, MVN_PASS_C2R_R2C, EPI, LINES>(p, (long)blockIdx.x, (long)gridDim.x, (cfloat*)mvn_smem, ctx);
 }
 
 // the fused middle pass (mvn_mid_fused.hpp): one column (piece) per workgroup
@@ -690,11 +618,8 @@ static void launch_walking(K kernel, StridedParams p, long nblocks, int nthreads
 // update 2 % (0.485 -> 0.475 ms); the plain r2c / c2r passes, which the tiled kernels already run
 // at the streaming ceiling, lose 3-8 % and stay tiled.
 static bool wave_rows_enabled(const RowsParams& p, int kind_bit) {
-  static const int mask = [] {
-    const char* e = std::getenv("MVN_WAVE_ROWS_MASK");
-    return e && *e ? std::atoi(e) : 28;
-  }();
-  return (mask & kind_bit) && p.fixed && !p.lines && p.h == WrCfg::H && p.C == WrCfg::H;
+  static const int mask = wr_rows_mask(28);
+  return wr_rows_enabled(p, mask, kind_bit);
 }
 
 // `mult` workgroups per resident slot: short-lived workgroups that the dispatcher keeps feeding in
@@ -704,7 +629,7 @@ static bool wave_rows_enabled(const RowsParams& p, int kind_bit) {
 // per workgroup.  Measured at 512^3 (`tools/ab_bench.sh` (removed; see git history before this
 // change)): fused divide 0.336 -> 0.312 ms at 16 per slot, fused update 0.535 -> 0.498 ms at 32.
 template <typename K>
-static void launch_wave_rows(K kernel, const RowsParams& p, stream_t s, long mult = 16) {
+static void launch_wave_rows(K kernel, const RowsParams& p, stream_t s, long mult) {
   const size_t lds = sizeof(cfloat) * (size_t)WrCfg::lds_cfloats;
   const long pairs = (p.rows + 1) / 2;
   long grid = (pairs + WrCfg::WAVES - 1) / WrCfg::WAVES;
@@ -729,243 +654,81 @@ static void launch_rows_fixed(K kernel, const RowsParams& p, long nblocks, int n
   launch_pass(kernel, p, nblocks, nthreads, lds_bytes, s);
 }
 
-#define MVN_DISPATCH_T(T_, KERNEL_EXPR)                                        \
-  switch (T_) {                                                                \
-    case 16: { constexpr int TT = 16; launch_pass(KERNEL_EXPR, p, nblocks, nthreads, lds_bytes, s); } break; \
-    case 8: { constexpr int TT = 8; launch_pass(KERNEL_EXPR, p, nblocks, nthreads, lds_bytes, s); } break;   \
-    case 4: { constexpr int TT = 4; launch_pass(KERNEL_EXPR, p, nblocks, nthreads, lds_bytes, s); } break;   \
-    case 2: { constexpr int TT = 2; launch_pass(KERNEL_EXPR, p, nblocks, nthreads, lds_bytes, s); } break;   \
-    case 1: { constexpr int TT = 1; launch_pass(KERNEL_EXPR, p, nblocks, nthreads, lds_bytes, s); } break;   \
-    default: throw std::invalid_argument("mvn: unsupported tile width");       \
-  }
-
 static void check_aligned16(const void* p, const char* what) {
   if (((size_t)p) & 15) throw std::invalid_argument(std::string("mvn: fixed kernels need 16-byte aligned ") + what);
 }
 
-// line-layout forms of the fixed last-axis kernels (H = 256: d2 = 512)
-static void check_lines(const RowsParams& p, long nblocks) {
-  constexpr int H = 256;
-  if (!fx_rows_lines_ok<H>() || !p.fixed || p.h != H || p.C != H || !p.nyq_packed || p.lines_d1 < 1 ||
-      p.lines_d1 % FxRowsCfg<H>::T || p.row_base % FxRowsCfg<H>::T || p.rows != nblocks * FxRowsCfg<H>::T)
-    throw std::invalid_argument("mvn: line-layout last-axis pass outside its range");
+// the kernel of a last-axis pass (KIND: MvnPassKind) - of a fixed length, or of the run-time-radix bodies
+typedef void (*rows_kernel_t)(const RowsParams);
+template <int KIND, int H, int EPI, bool LINES>
+static rows_kernel_t fixed_rows_kernel() {
+  if constexpr (KIND == MVN_PASS_R2C)
+    return kx_rows_r2c<H, LINES>;
+  else if constexpr (KIND == MVN_PASS_C2R)
+    return kx_rows_c2r<H, EPI, LINES>;
+  else
+    return kx_rows_c2r_r2c<H, EPI, LINES>;
+}
+template <int KIND, int T, int FORM>
+static rows_kernel_t generic_rows_kernel(bool even) {
+  if constexpr (KIND == MVN_PASS_R2C)
+    return even ? k_rows_r2c<true, T> : k_rows_r2c<false, T>;
+  else if constexpr (KIND == MVN_PASS_C2R)
+    return even ? k_rows_c2r<true, T, FORM> : k_rows_c2r<false, T, FORM>;
+  else
+    return k_rows_c2r_r2c<T, FORM>;  // (even extents only: Plan3D::rows_c2r_r2c)
+}
+
+// The three last-axis passes: the families in their order - line layout, wave rows, fixed length, run-time radix -
+// each behind the one dispatch of the launch's mode (mvn_pass_bodies.hpp), which refuses a mode the pass does not take.
+template <int KIND>
+static void launch_rows(const RowsParams& p, bool even, long nblocks, int nthreads, size_t lds_bytes, stream_t s) {
+  check_launch(nblocks, nthreads, lds_bytes);
+  const int mode = p.epi.mode;
+  if (p.lines) {  // (H = 256: d2 = 512)
+    fx_rows_lines_check(p, nblocks);
+    return mvn_epi_dispatch<KIND>(mode, [&](auto epi) {
+      launch_pass(fixed_rows_kernel<KIND, 256, decltype(epi)::value, true>(), p, nblocks, nthreads, lds_bytes, s);
+    });
+  }
+  if (p.fixed) {
+    check_aligned16(KIND == MVN_PASS_R2C ? (const void*)p.in_real : p.in_cplx, "input");
+    check_aligned16(KIND == MVN_PASS_C2R ? (const void*)p.out_real : p.out_cplx, "output");
+    if (wave_rows_enabled(p, mvn_wave_rows_kind_bit(KIND, mode)))
+      return mvn_epi_dispatch<KIND>(mode, [&](auto epi) {
+        launch_wave_rows(kw_rows<KIND, decltype(epi)::value>, p, s, mvn_wave_rows_per_slot(KIND, mode));
+      });
+    switch (p.h) {
+#define X(H)                                                                                                     \
+  case H:                                                                                                        \
+    return mvn_epi_dispatch<KIND>(mode, [&](auto epi) {                                                          \
+      launch_rows_fixed<FxRowsCfg<H>::WALK>(fixed_rows_kernel<KIND, H, decltype(epi)::value, false>(), p, nblocks, \
+                                            nthreads, lds_bytes, s);                                             \
+    });
+      MVN_FIXED_ROWS_LENGTHS(X)
+#undef X
+      default: throw std::invalid_argument("mvn: no fixed rows kernel for this length");
+    }
+  }
+  mvn_epi_dispatch<KIND, true>(mode, [&](auto form) {
+    mvn_dispatch_tile_width(p.T, [&](auto t) {
+      launch_pass(generic_rows_kernel<KIND, decltype(t)::value, decltype(form)::value>(even), p, nblocks, nthreads,
+                  std::max(lds_bytes, (size_t)mvn_epi_extra_lds_bytes(mode, nthreads)), s);
+    });
+  });
 }
 
 void launch_rows_r2c(const RowsParams& p, bool even, long nblocks, int nthreads, size_t lds_bytes,
                      stream_t s) {
-  check_launch(nblocks, nthreads, lds_bytes);
-  if (p.lines) {
-    check_lines(p, nblocks);
-    return launch_pass(kx_rows_r2c<256, true>, p, nblocks, nthreads, lds_bytes, s);
-  }
-  if (p.fixed) {
-    check_aligned16(p.in_real, "input");
-    check_aligned16(p.out_cplx, "output");
-    if (wave_rows_enabled(p, 1)) return launch_wave_rows(kw_rows<MVN_WR_R2C, MVN_EPI_STORE>, p, s);
-    switch (p.h) {
-#define X(H) case H: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_r2c<H>, p, nblocks, nthreads, lds_bytes, s); return;
-      MVN_FIXED_ROWS_LENGTHS(X)
-#undef X
-      default: throw std::invalid_argument("mvn: no fixed rows kernel for this length");
-    }
-  }
-  if (even) {
-    MVN_DISPATCH_T(p.T, (k_rows_r2c<true, TT>));
-  } else {
-    MVN_DISPATCH_T(p.T, (k_rows_r2c<false, TT>));
-  }
+  launch_rows<MVN_PASS_R2C>(p, even, nblocks, nthreads, lds_bytes, s);
 }
-
 void launch_rows_c2r(const RowsParams& p, bool even, long nblocks, int nthreads, size_t lds_bytes,
                      stream_t s) {
-  check_launch(nblocks, nthreads, lds_bytes);
-  if (p.lines) {
-    check_lines(p, nblocks);
-    switch (p.epi.mode) {
-      case MVN_EPI_DIVIDE: return launch_pass(kx_rows_c2r<256, MVN_EPI_DIVIDE, true>, p, nblocks, nthreads, lds_bytes, s);
-      case MVN_EPI_DIVIDE_U16: return launch_pass(kx_rows_c2r<256, MVN_EPI_DIVIDE_U16, true>, p, nblocks, nthreads, lds_bytes, s);
-      case MVN_EPI_DIVIDE_NM: return launch_pass(kx_rows_c2r<256, MVN_EPI_DIVIDE_NM, true>, p, nblocks, nthreads, lds_bytes, s);
-      case MVN_EPI_DIVIDE_NM_U16: return launch_pass(kx_rows_c2r<256, MVN_EPI_DIVIDE_NM_U16, true>, p, nblocks, nthreads, lds_bytes, s);
-      case MVN_EPI_UPDATE: return launch_pass(kx_rows_c2r<256, MVN_EPI_UPDATE, true>, p, nblocks, nthreads, lds_bytes, s);
-      case MVN_EPI_UPDATE_STATS: return launch_pass(kx_rows_c2r<256, MVN_EPI_UPDATE_STATS, true>, p, nblocks, nthreads, lds_bytes, s);
-      case MVN_EPI_UPDATE_TV: return launch_pass(kx_rows_c2r<256, MVN_EPI_UPDATE_TV, true>, p, nblocks, nthreads, lds_bytes, s);
-      case MVN_EPI_UPDATE_STATS_TV: return launch_pass(kx_rows_c2r<256, MVN_EPI_UPDATE_STATS_TV, true>, p, nblocks, nthreads, lds_bytes, s);
-      case MVN_EPI_DELTA: return launch_pass(kx_rows_c2r<256, MVN_EPI_DELTA, true>, p, nblocks, nthreads, lds_bytes, s);
-      default: return launch_pass(kx_rows_c2r<256, MVN_EPI_STORE, true>, p, nblocks, nthreads, lds_bytes, s);
-    }
-  }
-  if (p.fixed) {
-    check_aligned16(p.in_cplx, "input");
-    check_aligned16(p.out_real, "output");
-    if (wave_rows_enabled(p, p.epi.mode == MVN_EPI_DELTA ? 16 : 2)) {
-      switch (p.epi.mode) {
-        case MVN_EPI_DIVIDE: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_DIVIDE>, p, s);
-        case MVN_EPI_DIVIDE_U16: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_DIVIDE_U16>, p, s);
-        case MVN_EPI_DIVIDE_NM: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_DIVIDE_NM>, p, s);
-        case MVN_EPI_DIVIDE_NM_U16: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_DIVIDE_NM_U16>, p, s);
-        case MVN_EPI_UPDATE: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_UPDATE>, p, s);
-        case MVN_EPI_UPDATE_STATS: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_UPDATE_STATS>, p, s);
-        case MVN_EPI_UPDATE_TV: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_UPDATE_TV>, p, s);
-        case MVN_EPI_UPDATE_STATS_TV: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_UPDATE_STATS_TV>, p, s);
-        case MVN_EPI_DELTA: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_DELTA>, p, s);
-        default: return launch_wave_rows(kw_rows<MVN_WR_C2R, MVN_EPI_STORE>, p, s);
-      }
-    }
-    switch (p.h) {
-#define X(H)                                                                                  \
-  case H:                                                                                     \
-    switch (p.epi.mode) {                                                                     \
-      case MVN_EPI_DIVIDE: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_DIVIDE>, p, nblocks, nthreads, lds_bytes, s); break; \
-      case MVN_EPI_DIVIDE_U16: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_DIVIDE_U16>, p, nblocks, nthreads, lds_bytes, s); break; \
-      case MVN_EPI_DIVIDE_NM: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_DIVIDE_NM>, p, nblocks, nthreads, lds_bytes, s); break; \
-      case MVN_EPI_DIVIDE_NM_U16: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_DIVIDE_NM_U16>, p, nblocks, nthreads, lds_bytes, s); break; \
-      case MVN_EPI_UPDATE: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_UPDATE>, p, nblocks, nthreads, lds_bytes, s); break; \
-      case MVN_EPI_UPDATE_STATS: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_UPDATE_STATS>, p, nblocks, nthreads, lds_bytes, s); break; \
-      case MVN_EPI_UPDATE_TV: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_UPDATE_TV>, p, nblocks, nthreads, lds_bytes, s); break; \
-      case MVN_EPI_UPDATE_STATS_TV: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_UPDATE_STATS_TV>, p, nblocks, nthreads, lds_bytes, s); break; \
-      case MVN_EPI_DELTA: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_DELTA>, p, nblocks, nthreads, lds_bytes, s); break;   \
-      default: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r<H, MVN_EPI_STORE>, p, nblocks, nthreads, lds_bytes, s); break;             \
-    }                                                                                         \
-    return;
-      MVN_FIXED_ROWS_LENGTHS(X)
-#undef X
-      default: throw std::invalid_argument("mvn: no fixed rows kernel for this length");
-    }
-  }
-  if (p.epi.mode == MVN_EPI_UPDATE_STATS) {
-    lds_bytes = std::max(lds_bytes, (size_t)mvn_stat_lds_bytes(nthreads));
-    if (even) {
-      MVN_DISPATCH_T(p.T, (k_rows_c2r_stats<true, TT>));
-    } else {
-      MVN_DISPATCH_T(p.T, (k_rows_c2r_stats<false, TT>));
-    }
-    return;
-  }
-  if (mvn_epi_tv(p.epi.mode)) {
-    const bool stats = p.epi.mode == MVN_EPI_UPDATE_STATS_TV;
-    if (stats) lds_bytes = std::max(lds_bytes, (size_t)mvn_stat_lds_bytes(nthreads));
-    if (even && stats) {
-      MVN_DISPATCH_T(p.T, (k_rows_c2r_tv<true, TT, true>));
-    } else if (even) {
-      MVN_DISPATCH_T(p.T, (k_rows_c2r_tv<true, TT, false>));
-    } else if (stats) {
-      MVN_DISPATCH_T(p.T, (k_rows_c2r_tv<false, TT, true>));
-    } else {
-      MVN_DISPATCH_T(p.T, (k_rows_c2r_tv<false, TT, false>));
-    }
-    return;
-  }
-  if (mvn_epi_nm(p.epi.mode)) {
-    lds_bytes = std::max(lds_bytes, (size_t)mvn_nm_lds_bytes(nthreads));
-    const bool u16 = p.epi.mode == MVN_EPI_DIVIDE_NM_U16;
-    if (even && u16) {
-      MVN_DISPATCH_T(p.T, (k_rows_c2r_nm<true, TT, true>));
-    } else if (even) {
-      MVN_DISPATCH_T(p.T, (k_rows_c2r_nm<true, TT, false>));
-    } else if (u16) {
-      MVN_DISPATCH_T(p.T, (k_rows_c2r_nm<false, TT, true>));
-    } else {
-      MVN_DISPATCH_T(p.T, (k_rows_c2r_nm<false, TT, false>));
-    }
-    return;
-  }
-  if (p.epi.mode == MVN_EPI_DIVIDE_U16) {
-    if (even) {
-      MVN_DISPATCH_T(p.T, (k_rows_c2r_u16<true, TT>));
-    } else {
-      MVN_DISPATCH_T(p.T, (k_rows_c2r_u16<false, TT>));
-    }
-    return;
-  }
-  if (even) {
-    MVN_DISPATCH_T(p.T, (k_rows_c2r<true, TT>));
-  } else {
-    MVN_DISPATCH_T(p.T, (k_rows_c2r<false, TT>));
-  }
+  launch_rows<MVN_PASS_C2R>(p, even, nblocks, nthreads, lds_bytes, s);
 }
-
 void launch_rows_c2r_r2c(const RowsParams& p, long nblocks, int nthreads, size_t lds_bytes,
                          stream_t s) {
-  check_launch(nblocks, nthreads, lds_bytes);
-  if (p.lines) {
-    check_lines(p, nblocks);
-    switch (p.epi.mode) {
-      case MVN_EPI_DIVIDE: return launch_pass(kx_rows_c2r_r2c<256, MVN_EPI_DIVIDE, true>, p, nblocks, nthreads, lds_bytes, s);
-      case MVN_EPI_DIVIDE_U16: return launch_pass(kx_rows_c2r_r2c<256, MVN_EPI_DIVIDE_U16, true>, p, nblocks, nthreads, lds_bytes, s);
-      case MVN_EPI_DIVIDE_NM: return launch_pass(kx_rows_c2r_r2c<256, MVN_EPI_DIVIDE_NM, true>, p, nblocks, nthreads, lds_bytes, s);
-      case MVN_EPI_DIVIDE_NM_U16: return launch_pass(kx_rows_c2r_r2c<256, MVN_EPI_DIVIDE_NM_U16, true>, p, nblocks, nthreads, lds_bytes, s);
-      case MVN_EPI_UPDATE: return launch_pass(kx_rows_c2r_r2c<256, MVN_EPI_UPDATE, true>, p, nblocks, nthreads, lds_bytes, s);
-      case MVN_EPI_UPDATE_STATS: return launch_pass(kx_rows_c2r_r2c<256, MVN_EPI_UPDATE_STATS, true>, p, nblocks, nthreads, lds_bytes, s);
-      case MVN_EPI_UPDATE_TV: return launch_pass(kx_rows_c2r_r2c<256, MVN_EPI_UPDATE_TV, true>, p, nblocks, nthreads, lds_bytes, s);
-      case MVN_EPI_UPDATE_STATS_TV: return launch_pass(kx_rows_c2r_r2c<256, MVN_EPI_UPDATE_STATS_TV, true>, p, nblocks, nthreads, lds_bytes, s);
-      default: return launch_pass(kx_rows_c2r_r2c<256, MVN_EPI_STORE, true>, p, nblocks, nthreads, lds_bytes, s);
-    }
-  }
-  if (!p.fixed) {
-    if (p.epi.mode == MVN_EPI_UPDATE_STATS) {
-      lds_bytes = std::max(lds_bytes, (size_t)mvn_stat_lds_bytes(nthreads));
-      MVN_DISPATCH_T(p.T, (k_rows_c2r_r2c_stats<TT>));
-      return;
-    }
-    if (p.epi.mode == MVN_EPI_UPDATE_STATS_TV) {
-      lds_bytes = std::max(lds_bytes, (size_t)mvn_stat_lds_bytes(nthreads));
-      MVN_DISPATCH_T(p.T, (k_rows_c2r_r2c_tv<TT, true>));
-      return;
-    }
-    if (p.epi.mode == MVN_EPI_UPDATE_TV) {
-      MVN_DISPATCH_T(p.T, (k_rows_c2r_r2c_tv<TT, false>));
-      return;
-    }
-    if (mvn_epi_nm(p.epi.mode)) {
-      lds_bytes = std::max(lds_bytes, (size_t)mvn_nm_lds_bytes(nthreads));
-      if (p.epi.mode == MVN_EPI_DIVIDE_NM_U16) {
-        MVN_DISPATCH_T(p.T, (k_rows_c2r_r2c_nm<TT, true>));
-      } else {
-        MVN_DISPATCH_T(p.T, (k_rows_c2r_r2c_nm<TT, false>));
-      }
-      return;
-    }
-    if (p.epi.mode == MVN_EPI_DIVIDE_U16) {
-      MVN_DISPATCH_T(p.T, (k_rows_c2r_r2c_u16<TT>));
-      return;
-    }
-    MVN_DISPATCH_T(p.T, (k_rows_c2r_r2c<TT>));
-    return;
-  }
-  check_aligned16(p.in_cplx, "input");
-  check_aligned16(p.out_cplx, "output");
-  if (wave_rows_enabled(p, mvn_epi_divides(p.epi.mode) ? 4 : 8)) {
-    switch (p.epi.mode) {
-      case MVN_EPI_DIVIDE: return launch_wave_rows(kw_rows<MVN_WR_C2R_R2C, MVN_EPI_DIVIDE>, p, s);
-      case MVN_EPI_DIVIDE_U16: return launch_wave_rows(kw_rows<MVN_WR_C2R_R2C, MVN_EPI_DIVIDE_U16>, p, s);
-      case MVN_EPI_DIVIDE_NM: return launch_wave_rows(kw_rows<MVN_WR_C2R_R2C, MVN_EPI_DIVIDE_NM>, p, s);
-      case MVN_EPI_DIVIDE_NM_U16: return launch_wave_rows(kw_rows<MVN_WR_C2R_R2C, MVN_EPI_DIVIDE_NM_U16>, p, s);
-      case MVN_EPI_UPDATE: return launch_wave_rows(kw_rows<MVN_WR_C2R_R2C, MVN_EPI_UPDATE>, p, s, 32);
-      case MVN_EPI_UPDATE_STATS: return launch_wave_rows(kw_rows<MVN_WR_C2R_R2C, MVN_EPI_UPDATE_STATS>, p, s, 32);
-      case MVN_EPI_UPDATE_TV: return launch_wave_rows(kw_rows<MVN_WR_C2R_R2C, MVN_EPI_UPDATE_TV>, p, s, 32);
-      case MVN_EPI_UPDATE_STATS_TV: return launch_wave_rows(kw_rows<MVN_WR_C2R_R2C, MVN_EPI_UPDATE_STATS_TV>, p, s, 32);
-      default: return launch_wave_rows(kw_rows<MVN_WR_C2R_R2C, MVN_EPI_STORE>, p, s);
-    }
-  }
-  switch (p.h) {
-#define X(H)                                                                                  \
-  case H:                                                                                     \
-    switch (p.epi.mode) {                                                                     \
-      case MVN_EPI_DIVIDE: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r_r2c<H, MVN_EPI_DIVIDE>, p, nblocks, nthreads, lds_bytes, s); break; \
-      case MVN_EPI_DIVIDE_U16: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r_r2c<H, MVN_EPI_DIVIDE_U16>, p, nblocks, nthreads, lds_bytes, s); break; \
-      case MVN_EPI_DIVIDE_NM: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r_r2c<H, MVN_EPI_DIVIDE_NM>, p, nblocks, nthreads, lds_bytes, s); break; \
-      case MVN_EPI_DIVIDE_NM_U16: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r_r2c<H, MVN_EPI_DIVIDE_NM_U16>, p, nblocks, nthreads, lds_bytes, s); break; \
-      case MVN_EPI_UPDATE: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r_r2c<H, MVN_EPI_UPDATE>, p, nblocks, nthreads, lds_bytes, s); break; \
-      case MVN_EPI_UPDATE_STATS: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r_r2c<H, MVN_EPI_UPDATE_STATS>, p, nblocks, nthreads, lds_bytes, s); break; \
-      case MVN_EPI_UPDATE_TV: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r_r2c<H, MVN_EPI_UPDATE_TV>, p, nblocks, nthreads, lds_bytes, s); break; \
-      case MVN_EPI_UPDATE_STATS_TV: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r_r2c<H, MVN_EPI_UPDATE_STATS_TV>, p, nblocks, nthreads, lds_bytes, s); break; \
-      default: launch_rows_fixed<FxRowsCfg<H>::WALK>(kx_rows_c2r_r2c<H, MVN_EPI_STORE>, p, nblocks, nthreads, lds_bytes, s); break;             \
-    }                                                                                         \
-    return;
-    MVN_FIXED_ROWS_LENGTHS(X)
-#undef X
-    default: throw std::invalid_argument("mvn: no fixed rows kernel for this length");
-  }
+  launch_rows<MVN_PASS_C2R_R2C>(p, true, nblocks, nthreads, lds_bytes, s);
 }
 
 void launch_convergence_reduce(const double* rec, const unsigned* counts, int nviews, long cap, double* out,
@@ -984,38 +747,38 @@ long split_launch_count() { return g_split_launches.load(); }
 static std::atomic<long> g_mid_fused_launches{0};
 long mid_fused_launch_count() { return g_mid_fused_launches.load(); }
 
-// long lines: 16-column tiles through the split-window body when the columns divide (the plan's
-// geometry is for the 8-column kernel)
+// long lines: 16-column tiles through the split-window body when the columns divide (fx_split_retile)
 template <int N>
 static bool try_launch_split(int mode, const StridedParams& p, long nblocks, stream_t s, const StridedParams* rider,
                              size_t rider_lds) {
+  StridedParams q;
+  if (!fx_split_retile<N>(mode, p, nblocks, q)) return false;
   if constexpr (FxSplitCfg<N>::USE) {
     typedef FxSplitCfg<N> C;
-    if (mode == MVN_ST_FWD_MUL_INV || p.cstride != 1 || p.ncols % C::T != 0 || p.tiles_per_outer < 1)
-      return false;
-    StridedParams q = p;
-    const long outer = nblocks / p.tiles_per_outer;
-    q.tiles_per_outer = p.ncols / C::T;
-    q.T = q.TP = C::T;
-    const long nb = outer * q.tiles_per_outer;
     const size_t lds = sizeof(cfloat) * (size_t)C::lds_cfloats;
     ++g_split_launches;
     if (mode == MVN_ST_FWD)
-      launch_walking(kx_strided_split<N, MVN_ST_FWD>, q, nb, C::NT, lds, s, true, rider, rider_lds);
+      launch_walking(kx_strided_split<N, MVN_ST_FWD>, q, q.nblocks, C::NT, lds, s, true, rider, rider_lds);
     else
-      launch_walking(kx_strided_split<N, MVN_ST_INV>, q, nb, C::NT, lds, s, true, rider, rider_lds);
-    return true;
-  } else {
-    (void)mode; (void)p; (void)nblocks; (void)s; (void)rider; (void)rider_lds;
-    return false;
+      launch_walking(kx_strided_split<N, MVN_ST_INV>, q, q.nblocks, C::NT, lds, s, true, rider, rider_lds);
+  }
+  return true;
+}
+
+template <int T, bool NYQ>
+static auto strided_kernel(int mode) -> void (*)(const StridedParams) {
+  switch (mode) {
+    case MVN_ST_FWD: return k_strided<MVN_ST_FWD, T, NYQ>;
+    case MVN_ST_INV: return k_strided<MVN_ST_INV, T, NYQ>;
+    case MVN_ST_FWD_MUL_INV: return k_strided<MVN_ST_FWD_MUL_INV, T, NYQ>;
+    default: throw std::invalid_argument("mvn: unknown strided mode");
   }
 }
 
 void launch_strided(int mode, const StridedParams& p, long nblocks, int nthreads,
                     size_t lds_bytes, stream_t s, const StridedParams* rider, size_t rider_lds) {
   check_launch(nblocks, nthreads, lds_bytes);
-  if (rider && (!p.fixed || mode == MVN_ST_FWD_MUL_INV || rider->T != 1 || rider->fixed || rider_lds > 160 * 1024))
-    throw std::invalid_argument("mvn: Nyquist lines ride only in the plain fixed-length strided passes, one per workgroup");
+  mvn_strided_rider_check(mode, p, rider, rider_lds);
   if (p.fixed) {
     check_aligned16(p.data, "data");
     if (mode == MVN_ST_FWD_MUL_INV) check_aligned16(p.spec, "spectrum");
@@ -1032,38 +795,21 @@ void launch_strided(int mode, const StridedParams& p, long nblocks, int nthreads
       default: throw std::invalid_argument("mvn: no fixed strided kernel for this length");
     }
   }
-  if (p.is_nyq) {
-    switch (mode) {
-      case MVN_ST_FWD: MVN_DISPATCH_T(p.T, (k_strided<MVN_ST_FWD, TT, true>)); break;
-      case MVN_ST_INV: MVN_DISPATCH_T(p.T, (k_strided<MVN_ST_INV, TT, true>)); break;
-      case MVN_ST_FWD_MUL_INV: MVN_DISPATCH_T(p.T, (k_strided<MVN_ST_FWD_MUL_INV, TT, true>)); break;
-      default: throw std::invalid_argument("mvn: unknown strided mode");
-    }
-    return;
-  }
-  switch (mode) {
-    case MVN_ST_FWD: MVN_DISPATCH_T(p.T, (k_strided<MVN_ST_FWD, TT, false>)); break;
-    case MVN_ST_INV: MVN_DISPATCH_T(p.T, (k_strided<MVN_ST_INV, TT, false>)); break;
-    case MVN_ST_FWD_MUL_INV: MVN_DISPATCH_T(p.T, (k_strided<MVN_ST_FWD_MUL_INV, TT, false>)); break;
-    default: throw std::invalid_argument("mvn: unknown strided mode");
-  }
+  mvn_dispatch_tile_width(p.T, [&](auto t) {
+    constexpr int T = decltype(t)::value;
+    launch_pass(p.is_nyq ? strided_kernel<T, true>(mode) : strided_kernel<T, false>(mode), p, nblocks, nthreads, lds_bytes, s);
+  });
 }
 
 void launch_dim0_direct(const Dim0DirectParams& p, stream_t s) {
-  if (!mvn_dim0_direct_possible(p.k, p.d0) || p.kd < p.k + 1 || p.h != p.k / 2 || p.plane < 0 || p.plane + p.plane2 < 1 || (p.plane > 0 && p.in == p.out) ||
-      p.plane2 < 0 || (p.plane2 > 0 && (!p.in2 || !p.out2 || !p.taps2 || p.in2 == p.out2)))
-    throw std::invalid_argument("mvn: direct dim0 convolution called outside its range");
+  mvn_dim0_check(p);
   if (p.plane > 0) check_aligned16(p.in, "input");  // (8-byte accesses; the volumes are 16-byte aligned anyway)
-  if (p.plane + p.plane2 >= (1L << 28)) throw std::invalid_argument("mvn: plane too large for the direct dim0 leg");
   const long main_blocks = mvn_dim0_blocks(p).blocks;
   long nblocks = main_blocks;
   size_t lds = 0;
   if (p.packed) {
-    if (!p.inv1 || !p.taps2 || p.C < 1 || p.d1 < 1 || (long)p.C * p.d1 != p.plane)
-      throw std::invalid_argument("mvn: packed direct dim0 convolution needs the dim1 tables and the Nyquist taps");
     nblocks += mvn_dim0_pairs(p.d1);
     lds = mvn_dim0_dc_lds_bytes(p.d0, p.k);
-    if (lds > 64 * 1024) throw std::invalid_argument("mvn: dim0 too long for the packed DC column");
   }
   if (nblocks > 0x7fffffffL) throw std::invalid_argument("mvn: grid size out of range");
   switch (mvn_dim0_taps_template(p.k)) {
@@ -1075,9 +821,6 @@ void launch_dim0_direct(const Dim0DirectParams& p, stream_t s) {
   HIP_CHECK(hipGetLastError());
 }
 
-// the fused middle pass: instantiated for odd tap counts up to 31 (33 taps would need 40 window slots: beyond the
-// registers of two waves per SIMD)
-#define MVN_MF_TAP_COUNTS(X) X(1) X(3) X(5) X(7) X(9) X(11) X(13) X(15) X(17) X(19) X(21) X(23) X(25) X(27) X(29) X(31)
 void launch_mid_fused(const MidFusedParams& p, stream_t s) {
   mf_check(p);
   const long nblocks = mf_blocks(p);
@@ -1149,16 +892,8 @@ void reflect_counters(long long out[2]) {
   out[1] = g_reflect_volumes.load();
 }
 
-static void check_reflect(const ReflectParams& p) {
-  const int D[3] = {p.D0, p.D1, p.D2}, n[3] = {p.n0, p.n1, p.n2}, o[3] = {p.o0, p.o1, p.o2};
-  for (int d = 0; d < 3; ++d)
-    if (n[d] < 1 || o[d] < 0 || (long)o[d] + n[d] > D[d] || n[d] > 0x3fffffff)
-      throw std::invalid_argument("mvn: reflect fill: the window does not fit the volume");
-  if (!p.vol || p.RP < p.D2 || (p.RP & 1)) throw std::invalid_argument("mvn: reflect fill: bad volume");
-}
-
 void launch_reflect_fill(const ReflectParams& p0, bool u16, stream_t s) {
-  check_reflect(p0);
+  mvn_reflect_check(p0);
   ReflectParams p = p0;
   for (int axis = 2; axis >= 0; --axis) {
     p.axis = axis;
@@ -1181,32 +916,8 @@ void resample_counters(long long out[2]) {
   out[1] = g_normalize_launches.load();
 }
 
-static void check_window(const char* what, long RP, int D0, int D1, const int n[3], const int o[3]) {
-  const long D[3] = {D0, D1, RP};
-  for (int d = 0; d < 3; ++d)
-    if (n[d] < 1 || o[d] < 0 || (long)o[d] + n[d] > D[d])
-      throw std::invalid_argument(std::string("mvn: ") + what + ": the window does not fit the volume");
-  if (RP < 2 || (RP & 1)) throw std::invalid_argument(std::string("mvn: ") + what + ": bad volume");
-}
-
-static void check_resample(const ResampleParams& p) {
-  const int n[3] = {p.n0, p.n1, p.n2}, o[3] = {p.o0, p.o1, p.o2};
-  check_window("resample", p.RP, p.D0, p.D1, n, o);
-  if (!p.image || !p.src) throw std::invalid_argument("mvn: resample: null pointer");
-  if (p.s0 < 0 || p.s1 < 0 || p.s2 < 0) throw std::invalid_argument("mvn: resample: negative stride");
-  for (int k = 0; k < 3; ++k)
-    if (p.g.m[k] < 1) throw std::invalid_argument("mvn: resample: raw extents must be >= 1");
-}
-
-static void check_normalize(const NormalizeParams& p) {
-  const int n[3] = {p.n0, p.n1, p.n2}, o[3] = {p.o0, p.o1, p.o2};
-  // (the last plane's rows are all the launch needs of D0)
-  check_window("normalise", p.RP, p.o0 + p.n0, p.D1, n, o);
-  if (!p.vols || p.V < 1) throw std::invalid_argument("mvn: normalise: no volumes");
-}
-
 void launch_resample(const ResampleParams& p, bool u16, stream_t s) {
-  check_resample(p);
+  mvn_resample_check(p);
   const long nblocks = mvn_resample_blocks(p);
   if (nblocks < 1 || nblocks > 0x7fffffffL) throw std::invalid_argument("mvn: grid size out of range");
   ++g_resample_launches;
@@ -1218,7 +929,7 @@ void launch_resample(const ResampleParams& p, bool u16, stream_t s) {
 }
 
 void launch_weights_normalize(const NormalizeParams& p, stream_t s) {
-  check_normalize(p);
+  mvn_normalize_check(p);
   const long nblocks = mvn_normalize_blocks(p);
   if (nblocks < 1 || nblocks > 0x7fffffffL) throw std::invalid_argument("mvn: grid size out of range");
   ++g_normalize_launches;

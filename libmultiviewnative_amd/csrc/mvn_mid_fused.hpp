@@ -131,6 +131,10 @@ MVN_HD int mf_tap_plane(const MidFusedParams& P, int j) {
   return p < 0 ? p + P.kd : p;
 }
 
+// instantiated for odd tap counts up to 31 (33 taps would need 40 window slots: beyond the registers of two waves per
+// SIMD)
+#define MVN_MF_TAP_COUNTS(X) X(1) X(3) X(5) X(7) X(9) X(11) X(13) X(15) X(17) X(19) X(21) X(23) X(25) X(27) X(29) X(31)
+
 inline void mf_check(const MidFusedParams& P) {
   const bool taps_mode = P.mode == MF_TAPS;
   if (!P.in || !P.out || !P.tw || P.d0 < 1 || P.H < 1 || (long)P.d0 * P.H * MF_N1 >= (1L << 31) * 4 || P.seg < 0)

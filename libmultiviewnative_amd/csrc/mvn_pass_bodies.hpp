@@ -16,6 +16,10 @@
 
 #include <math.h>
 
+#include <stdexcept>
+#include <string>
+#include <type_traits>
+
 #include "mvn_fft_core.hpp"
 
 // The RL pointwise math mirrors the reference's rounding step by step: no FMA contraction there
@@ -39,9 +43,12 @@ enum MvnEpilogue {
   MVN_EPI_UPDATE_STATS_TV = 7,  // UPDATE_TV, plus the convergence statistics
   // noise model (camera background + per-sweep likelihood): the quotient against m = x*scale + background, plus the
   // statistics {D, Y, M} of the window (MvnStatsParams, MvnNmAcc)
-  MVN_EPI_DIVIDE_NM = 8,     // view as float32
-  MVN_EPI_DIVIDE_NM_U16 = 9  // view as uint16 (EpilogueParams::view16)
+  MVN_EPI_DIVIDE_NM = 8,      // view as float32
+  MVN_EPI_DIVIDE_NM_U16 = 9,  // view as uint16 (EpilogueParams::view16)
+  MVN_EPI_COUNT               // (not a mode: one past the last)
 };
+// A new mode is added HERE, in the predicates below (mvn_epi_allowed is the one table of which pass takes which
+// mode) and in the bodies - nowhere else: both backends reach the bodies through mvn_epi_dispatch.
 
 // the epilogues that read psi and the weights
 constexpr bool mvn_epi_reads_psi(int epi) {
@@ -59,6 +66,72 @@ constexpr int mvn_epi_math(int epi) { return epi == MVN_EPI_DIVIDE_U16 ? (int)MV
 constexpr bool mvn_epi_nm(int epi) { return epi == MVN_EPI_DIVIDE_NM || epi == MVN_EPI_DIVIDE_NM_U16; }
 constexpr bool mvn_epi_u16(int epi) { return epi == MVN_EPI_DIVIDE_U16 || epi == MVN_EPI_DIVIDE_NM_U16; }
 constexpr bool mvn_epi_divides(int epi) { return epi == MVN_EPI_DIVIDE || mvn_epi_u16(epi) || mvn_epi_nm(epi); }
+// the epilogues that keep statistics of the window: the convergence statistics, the noise model's (above)
+constexpr bool mvn_epi_stats(int epi) { return mvn_epi_base(epi) == MVN_EPI_UPDATE_STATS; }
+// The run-time-radix bodies (rows_c2r_even_body / rows_c2r_odd_body) are one form for the four modes they tell apart
+// at run time, by EpilogueParams::mode, and a form of its own for every other mode.
+constexpr int mvn_epi_generic_form(int epi) {
+  return (epi == MVN_EPI_DIVIDE || epi == MVN_EPI_UPDATE || epi == MVN_EPI_DELTA) ? (int)MVN_EPI_STORE : epi;
+}
+
+// the last-axis passes (the values of KIND in mvn_fixed.hpp and of MvnWaveRowsMode) and the modes each of them takes:
+// r2c has no epilogue (its launches leave the mode at STORE), DELTA accumulates into a volume and is never fused
+enum MvnPassKind { MVN_PASS_R2C = 0, MVN_PASS_C2R = 1, MVN_PASS_C2R_R2C = 2 };
+constexpr bool mvn_epi_allowed(int kind, int epi) {
+  return epi >= 0 && epi < MVN_EPI_COUNT &&
+         (kind == MVN_PASS_R2C ? epi == MVN_EPI_STORE : kind == MVN_PASS_C2R ? true : kind == MVN_PASS_C2R_R2C && epi != MVN_EPI_DELTA);
+}
+
+// ---- launch side (host only): from the run-time mode of a launch to a compile-time constant -------------------------
+// mvn_epi_dispatch<KIND>(mode, f) calls f(std::integral_constant<int, EPI>{}) for the mode of the launch - GENERIC:
+// for its form in the run-time-radix bodies - and throws for a mode the pass does not take.  f is instantiated for the
+// modes of KIND only, so a backend compiles exactly the kernels its passes can launch.
+template <int KIND, bool GENERIC, int EPI, typename F>
+inline void mvn_epi_dispatch_from(int mode, F& f) {
+  if constexpr (EPI < MVN_EPI_COUNT) {
+    if constexpr (mvn_epi_allowed(KIND, EPI)) {
+      if (mode == EPI) return f(std::integral_constant<int, GENERIC ? mvn_epi_generic_form(EPI) : EPI>{});
+    }
+    mvn_epi_dispatch_from<KIND, GENERIC, EPI + 1>(mode, f);
+  } else {
+    static const char* const pass[] = {"r2c", "c2r", "fused c2r + r2c"};
+    throw std::invalid_argument("mvn: epilogue mode " + std::to_string(mode) + " in a " + pass[KIND] + " last-axis pass");
+  }
+}
+template <int KIND, bool GENERIC = false, typename F>
+inline void mvn_epi_dispatch(int mode, F&& f) {
+  static_assert(KIND >= MVN_PASS_R2C && KIND <= MVN_PASS_C2R_R2C, "a last-axis pass");
+  mvn_epi_dispatch_from<KIND, GENERIC, 0>(mode, f);
+}
+
+// the tile width of the run-time-radix kernels
+template <typename F>
+inline void mvn_dispatch_tile_width(int T, F&& f) {
+  switch (T) {
+    case 16: return f(std::integral_constant<int, 16>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 1: return f(std::integral_constant<int, 1>{});
+    default: throw std::invalid_argument("mvn: unsupported tile width");
+  }
+}
+
+// scratch of the lane reduction of the convergence statistics: n doubles (sum), n doubles (mass), n floats (max);
+// of the noise model's: 3 n doubles
+MVN_HD constexpr long mvn_stat_lds_bytes(int nthreads) { return 20L * nthreads; }
+MVN_HD constexpr long mvn_nm_lds_bytes(int nthreads) { return 24L * nthreads; }
+// the LDS a launch of the run-time-radix kernels needs for its mode's reduction (at least: the tile may be larger;
+// the fixed and wave-row kernels reduce inside the LDS they have)
+constexpr long mvn_epi_extra_lds_bytes(int epi, int nthreads) {
+  return mvn_epi_stats(epi) ? mvn_stat_lds_bytes(nthreads) : mvn_epi_nm(epi) ? mvn_nm_lds_bytes(nthreads) : 0;
+}
+// wave-row launches (mvn_wave_rows.hpp): workgroups per resident slot - 32 where the fused pass also reads psi and
+// the weights, 16 otherwise - and the bit of MVN_WAVE_ROWS_MASK that enables the launch
+constexpr long mvn_wave_rows_per_slot(int kind, int epi) { return kind == MVN_PASS_C2R_R2C && mvn_epi_reads_psi(epi) ? 32 : 16; }
+constexpr int mvn_wave_rows_kind_bit(int kind, int epi) {
+  return kind == MVN_PASS_R2C ? 1 : kind == MVN_PASS_C2R ? (epi == MVN_EPI_DELTA ? 16 : 2) : (mvn_epi_divides(epi) ? 4 : 8);
+}
 
 struct EpilogueParams {
   int mode;
@@ -369,9 +442,6 @@ MVN_HD void mvn_update_stats(const EpilogueParams& e, long i, float x, MvnStatAc
   mvn_stat_add(acc, in, last, y, x);
 }
 
-// scratch of the lane reduction: n doubles (sum), n doubles (mass), n floats (max)
-MVN_HD constexpr long mvn_stat_lds_bytes(int nthreads) { return 20L * nthreads; }
-
 // lanes [tid] of the scratch after a barrier: a tree over the next power of two, pairs (t, t + h) in a fixed order
 MVN_HD void mvn_stat_tree_step(char* lds, int n, int h, int tid) {
   double* ls = reinterpret_cast<double*>(lds);
@@ -499,9 +569,6 @@ MVN_HD cfloat mvn_nm_pair(const EpilogueParams& e, cfloat z, cfloat a, MvnNmAcc&
   const float q1 = mvn_nm_one(e, a.y, x1, acc, row_in && c + 1u < s.n2);
   return cmake(q0, q1);
 }
-
-// scratch of the lane reduction: 3 n doubles
-MVN_HD constexpr long mvn_nm_lds_bytes(int nthreads) { return 24L * nthreads; }
 
 MVN_HD void mvn_nm_put(char* lds, int n, int tid, const MvnNmAcc& a) {
   double* l = reinterpret_cast<double*>(lds);
@@ -728,13 +795,16 @@ MVN_HD void rows_r2c_even_body(const RowsParams& P, long tile, int tid, int nthr
 // O = (X[k] - conj X[h-k]) exp(+2 pi i k/d2); z = IFFT_h(Z); x[2j] = Re z[j], x[2j+1] = Im z[j]
 // KEEP = true is the fused pass: the epilogue results stay in LDS and run straight through the
 // forward half (rows_r2c_even_tail), writing the half-spectrum of the result over the input.
-// STATS = true: the UPDATE epilogue with the convergence statistics (P.epi.mode is then MVN_EPI_UPDATE_STATS).
-// U16 = true: the DIVIDE epilogue on a uint16 view (P.epi.mode is then MVN_EPI_DIVIDE_U16).
-// TV = true: the UPDATE epilogue (with STATS or without) on the integral times the total-variation factor (P.epi.mode
-// is then MVN_EPI_UPDATE_TV / MVN_EPI_UPDATE_STATS_TV); the factor is loaded at its use.
-// NM = true: the noise-model divide (P.epi.mode is then MVN_EPI_DIVIDE_NM, or MVN_EPI_DIVIDE_NM_U16 with U16).
-template <int T, bool KEEP = false, bool STATS = false, bool U16 = false, bool TV = false, bool NM = false>
+// EPI is the form of the launch's mode (mvn_epi_generic_form): MVN_EPI_STORE for the four modes told apart at run time
+// by P.epi.mode, else P.epi.mode itself, from which follow
+// STATS: the UPDATE epilogue with the convergence statistics;
+// U16: the DIVIDE epilogue on a uint16 view;
+// TV: the UPDATE epilogue (with STATS or without) on the integral times the total-variation factor, loaded at its use;
+// NM: the noise-model divide (on a uint16 view with U16).
+template <int T, bool KEEP = false, int EPI = MVN_EPI_STORE>
 MVN_HD void rows_c2r_even_body(const RowsParams& P, long tile, int tid, int nthreads, cfloat* lds) {
+  static_assert(mvn_epi_generic_form(EPI) == EPI, "a form of the run-time-radix bodies");
+  constexpr bool STATS = mvn_epi_stats(EPI), U16 = mvn_epi_u16(EPI), TV = mvn_epi_tv(EPI), NM = mvn_epi_nm(EPI);
   // (a copy of the epilogue's few fields, not of P: the run-time radix tables in P are indexed dynamically and a
   // private copy of the whole struct would live in scratch memory)
   EpilogueParams epi = P.epi;
@@ -900,8 +970,10 @@ MVN_HD void rows_r2c_odd_body(const RowsParams& P, long tile, int tid, int nthre
   }
 }
 
-template <int T, bool STATS = false, bool U16 = false, bool TV = false, bool NM = false>
+template <int T, int EPI = MVN_EPI_STORE>
 MVN_HD void rows_c2r_odd_body(const RowsParams& P, long tile, int tid, int nthreads, cfloat* lds) {
+  static_assert(mvn_epi_generic_form(EPI) == EPI, "a form of the run-time-radix bodies");
+  constexpr bool STATS = mvn_epi_stats(EPI), U16 = mvn_epi_u16(EPI), TV = mvn_epi_tv(EPI), NM = mvn_epi_nm(EPI);
   // (a copy of the epilogue's few fields, not of P: the run-time radix tables in P are indexed dynamically and a
   // private copy of the whole struct would live in scratch memory)
   EpilogueParams epi = P.epi;
@@ -996,6 +1068,13 @@ struct StridedParams {
   int fixed;    // 1: launch the compile-time specialised kernel for this length (mvn_fixed.hpp)
   long nblocks; // fixed kernels: tiles of the launch (a workgroup walks over several of them)
 };
+
+// The lines of the Nyquist plane may ride behind the walking workgroups of a plain fixed-length launch, one line per
+// workgroup through the run-time-radix body (`rider`, null: none)
+inline void mvn_strided_rider_check(int mode, const StridedParams& p, const StridedParams* rider, size_t rider_lds) {
+  if (rider && (!p.fixed || mode == MVN_ST_FWD_MUL_INV || rider->T != 1 || rider->fixed || rider_lds > 160 * 1024))
+    throw std::invalid_argument("mvn: Nyquist lines ride only in the plain fixed-length strided passes, one per workgroup");
+}
 
 // Loads are issued in batches of U per thread BEFORE any of them is consumed, so a tile's HBM
 // latency is paid once, not once per element.  When the whole tile is a single batch

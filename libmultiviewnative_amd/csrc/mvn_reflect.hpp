@@ -34,6 +34,8 @@
 
 #include <stdint.h>
 
+#include <stdexcept>
+
 #include "mvn_ingest.hpp"
 
 struct ReflectParams {
@@ -44,6 +46,14 @@ struct ReflectParams {
   int o0, o1, o2;  // the window's offset inside the volume
   int axis;        // which of the three launches
 };
+
+inline void mvn_reflect_check(const ReflectParams& p) {
+  const int D[3] = {p.D0, p.D1, p.D2}, n[3] = {p.n0, p.n1, p.n2}, o[3] = {p.o0, p.o1, p.o2};
+  for (int d = 0; d < 3; ++d)
+    if (n[d] < 1 || o[d] < 0 || (long)o[d] + n[d] > D[d] || n[d] > 0x3fffffff)
+      throw std::invalid_argument("mvn: reflect fill: the window does not fit the volume");
+  if (!p.vol || p.RP < p.D2 || (p.RP & 1)) throw std::invalid_argument("mvn: reflect fill: bad volume");
+}
 
 // index of the stack's element that volume index o + i mirrors
 MVN_HD int mvn_reflect_index(int i, int n) {

@@ -33,6 +33,9 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <stdexcept>
+#include <string>
+
 #include "mvn_ingest.hpp"
 
 #define MVN_RS_WG 256  // work items of a workgroup
@@ -69,6 +72,29 @@ struct NormalizeParams {
   int n0, n1, n2;
   int o0, o1, o2;
 };
+
+// the window [o, o + n) of a launch inside a volume of D0 x D1 rows of RP elements
+inline void mvn_window_check(const char* what, long RP, int D0, int D1, const int n[3], const int o[3]) {
+  const long D[3] = {D0, D1, RP};
+  for (int d = 0; d < 3; ++d)
+    if (n[d] < 1 || o[d] < 0 || (long)o[d] + n[d] > D[d])
+      throw std::invalid_argument(std::string("mvn: ") + what + ": the window does not fit the volume");
+  if (RP < 2 || (RP & 1)) throw std::invalid_argument(std::string("mvn: ") + what + ": bad volume");
+}
+inline void mvn_resample_check(const ResampleParams& p) {
+  const int n[3] = {p.n0, p.n1, p.n2}, o[3] = {p.o0, p.o1, p.o2};
+  mvn_window_check("resample", p.RP, p.D0, p.D1, n, o);
+  if (!p.image || !p.src) throw std::invalid_argument("mvn: resample: null pointer");
+  if (p.s0 < 0 || p.s1 < 0 || p.s2 < 0) throw std::invalid_argument("mvn: resample: negative stride");
+  for (int k = 0; k < 3; ++k)
+    if (p.g.m[k] < 1) throw std::invalid_argument("mvn: resample: raw extents must be >= 1");
+}
+inline void mvn_normalize_check(const NormalizeParams& p) {
+  const int n[3] = {p.n0, p.n1, p.n2}, o[3] = {p.o0, p.o1, p.o2};
+  // (the last plane's rows are all the launch needs of D0)
+  mvn_window_check("normalise", p.RP, p.o0 + p.n0, p.D1, n, o);
+  if (!p.vols || p.V < 1) throw std::invalid_argument("mvn: normalise: no volumes");
+}
 
 MVN_HD long mvn_resample_blocks(const ResampleParams& p) {
   const long bz = (p.D0 + MVN_RS_TZ - 1) / MVN_RS_TZ, by = (p.D1 + MVN_RS_TY - 1) / MVN_RS_TY,

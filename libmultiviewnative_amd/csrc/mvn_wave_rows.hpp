@@ -28,6 +28,8 @@
 // The plain r2c pass is C' (real rows in), D, E; the plain c2r pass A, B, C'' (epilogue stores).
 #pragma once
 
+#include <cstdlib>
+
 #include "mvn_fixed.hpp"
 
 struct WrCfg {
@@ -43,7 +45,18 @@ struct WrCfg {
                 "wave-row kernels are written for 256 = 8 * 8 * 4");
 };
 
-enum MvnWaveRowsMode { MVN_WR_R2C = 0, MVN_WR_C2R = 1, MVN_WR_C2R_R2C = 2 };
+enum MvnWaveRowsMode { MVN_WR_R2C = 0, MVN_WR_C2R = 1, MVN_WR_C2R_R2C = 2 };  // (= MvnPassKind)
+
+// MVN_WAVE_ROWS_MASK selects the passes that use these kernels (mvn_wave_rows_kind_bit: 1 plain r2c, 2 plain c2r,
+// 4 fused divide, 8 fused update / store, 16 c2r with the DELTA epilogue of the sharded step): the mask, or a
+// backend's default, and whether a launch with that bit goes here
+inline int wr_rows_mask(int default_mask) {
+  const char* e = std::getenv("MVN_WAVE_ROWS_MASK");
+  return e && *e ? std::atoi(e) : default_mask;
+}
+inline bool wr_rows_enabled(const RowsParams& p, int mask, int kind_bit) {
+  return (mask & kind_bit) && p.fixed && !p.lines && p.h == WrCfg::H && p.C == WrCfg::H;
+}
 
 // LDS index of position p of a row: 4 spare entries after every 32 positions.  Phases B - D then
 // touch 64 different banks with every half-wave access (lanes = neighbouring positions, blocks of

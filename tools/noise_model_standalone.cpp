@@ -89,12 +89,13 @@ struct HostRows {
     if (KEEP) p.out_cplx = data, p.out_nyq = nyq;
     constexpr int EPI = NM ? (U16 ? MVN_EPI_DIVIDE_NM_U16 : MVN_EPI_DIVIDE_NM) : MVN_EPI_STORE;
     if (wave) return wave_run<KEEP ? MVN_WR_C2R_R2C : MVN_WR_C2R, EPI>(p);
+    constexpr int FORM = NM ? EPI : U16 ? (int)MVN_EPI_DIVIDE_U16 : (int)MVN_EPI_STORE;  // (of the run-time-radix bodies)
     std::vector<cfloat> lds((size_t)lds_cfloats());
     for (long t = 0; t < (p.rows + T - 1) / T; ++t) {
       if (L.even)
-        rows_c2r_even_body<T, KEEP, false, U16, false, NM>(p, t, 0, 1, lds.data());
+        rows_c2r_even_body<T, KEEP, FORM>(p, t, 0, 1, lds.data());
       else
-        rows_c2r_odd_body<T, false, U16, false, NM>(p, t, 0, 1, lds.data());
+        rows_c2r_odd_body<T, FORM>(p, t, 0, 1, lds.data());
     }
   }
 };
