@@ -33,6 +33,16 @@
 // pair's LDS requests and its arithmetic (mf_body).  The window is indexed with compile-time register numbers: KW = K
 // rounded up to a multiple of 8 slots, the filter code exists KW / 8 times per line (batch i uses variant i mod KW / 8),
 // selected by a workgroup-uniform branch.
+//
+// The ends of a walk are code of their own (a launch had ~50 us outside its steady state, 12 % at 512 planes):
+//     prologue   passes -1 .. P - 1, P = (K - 1) / 8 whole batches that only fill the window: forward stages of the wave's
+//                line back to back, the loads of the batch after next, the window fill with compile-time slots - no
+//                transform back, no filter.  The first thing a workgroup requests is batch 0; the K taps follow in
+//                P + 1 groups, one behind each pass's line loads, so no wait for a line includes a tap (vector-memory
+//                loads return in order) and none is used before the loop.  The DC column's partner taps likewise.
+//     loop       batches P .. nb - 1 with the pipeline above; batch P is the only one with fill lines left in it (the
+//                first (K - 1) mod 8), and those take the fill form, not the whole filter
+//     tail       the last batch is transformed back and stored
 #pragma once
 
 #include <stdexcept>
@@ -162,16 +172,36 @@ MVN_HD void mf_fetch(const MidFusedParams& P, MfRegs<K>& r, int c, int z0, int b
   for (int m = 0; m < 8; ++m) r.xr[m] = src[64 * m];
 }
 
+// The ends of a walk.  The first K - 1 steps only fill the window: MF_P whole batches of them, and with the pass in
+// front of batch 0 that makes MF_P + 1 passes before the loop of mf_body - its prologue.  The K taps are requested in
+// MF_P + 1 groups, group G behind the line loads of prologue pass G - 1 (mf_load_taps): vector-memory loads return in
+// order, so the wait for the next lines never includes a tap, and no tap is used before the loop.
+constexpr int mf_fill_batches(int K) { return (K - 1) / MF_LINES; }
+constexpr int mf_tap_group(int K) { return (K + mf_fill_batches(K)) / (mf_fill_batches(K) + 1); }  // taps per group
+constexpr int mf_tap_lo(int K, int G) { return G * mf_tap_group(K) < K ? G * mf_tap_group(K) : K; }
+
 template <int K>
 MVN_HD void mf_setup(const MidFusedParams& P, MfRegs<K>& r, int c, int z0, int nsteps, int tid) {
+  mf_fetch<K>(P, r, c, z0, 0, nsteps, tid);  // first: the forward transform of batch 0 waits for nothing else
   r.bad = cmake(0.f, 0.f);
   r.dcmode = MF_DC_NONE;
   r.qm = r.cpar = 0;
 #pragma unroll
-  for (int j = 0; j < K; ++j) r.tap[j] = j < P.k ? P.taps[((long)mf_tap_plane(P, j) * P.H + c) * MF_N1 + tid] : cmake(0.f, 0.f);
-#pragma unroll
   for (int s = 0; s < mf_slots(K); ++s) r.w[s] = cmake(0.f, 0.f);
-  mf_fetch<K>(P, r, c, z0, 0, nsteps, tid);
+}
+template <int K, int G>
+MVN_HD void mf_load_taps(const MidFusedParams& P, MfRegs<K>& r, int c, int tid) {
+#pragma unroll
+  for (int j = mf_tap_lo(K, G); j < mf_tap_lo(K, G + 1); ++j)
+    r.tap[j] = j < P.k ? P.taps[((long)mf_tap_plane(P, j) * P.H + c) * MF_N1 + tid] : cmake(0.f, 0.f);
+}
+// before the loop: every tap has arrived (device: the loop's own waits then never name a load of the prologue)
+template <int K>
+MVN_HD void mf_taps_arrived(MfRegs<K>& r) {
+#if defined(__HIPCC__) && !defined(MVN_HOST_EMU)
+#pragma unroll
+  for (int j = 0; j < K; ++j) asm volatile("" : "+v"(r.tap[j]));
+#endif
 }
 
 // twiddle products of the transforms here: two packed instructions each (the scalar form of cmul is four; the LDS-
@@ -450,12 +480,27 @@ MVN_HD void mf_setup_dc(const MidFusedParams& P, MfRegs<K>& r, int tid) {
     const int l = tid & 63, g = (l >> 3) + 8 * (l & 7);
     r.cpar = g == 0 ? 64 : 8 * ((64 - g) & 7) + ((64 - g) >> 3);
   }
+}
+// The taps of the DC column: the partner bins of tap group G are requested behind the group itself, into the window
+// slots of batch MF_P - the eight slots no prologue pass fills (a group is at most eight taps) -, and split a pass
+// later (mf_split_taps_dc), when the loads of that pass are the only ones behind them.
+template <int K, int G>
+MVN_HD void mf_load_taps_dc(const MidFusedParams& P, MfRegs<K>& r, int tid) {
+  constexpr int S0 = MF_LINES * mf_fill_batches(K), J0 = mf_tap_lo(K, G);
+  static_assert(mf_tap_group(K) <= mf_slots(K) - S0, "a tap group's partner bins fit the window slots the prologue leaves alone");
   const cfloat* tp = P.taps + r.qm;
 #pragma unroll
-  for (int j = 0; j < K; ++j) {
-    const cfloat a = r.tap[j], b = j < P.k ? tp[(long)mf_tap_plane(P, j) * P.H * MF_N1] : cmake(0.f, 0.f);
+  for (int j = J0; j < mf_tap_lo(K, G + 1); ++j)
+    r.w[S0 + j - J0] = j < P.k ? tp[(long)mf_tap_plane(P, j) * P.H * MF_N1] : cmake(0.f, 0.f);
+}
+template <int K, int G>
+MVN_HD void mf_split_taps_dc(MfRegs<K>& r) {
+  constexpr int S0 = MF_LINES * mf_fill_batches(K), J0 = mf_tap_lo(K, G);
+#pragma unroll
+  for (int j = J0; j < mf_tap_lo(K, G + 1); ++j) {
+    const cfloat a = r.tap[j], b = r.w[S0 + j - J0];
     // bins 1 .. 255 filter X0 with T0[f]; bins 257 .. 511 filter XH[-f] with TH[-f] (the pair seen from the other side)
-    r.tap[j] = f == fm ? a : (f < MF_N1 / 2 ? mf_herm0(a, b) : mf_hermh(b, a));
+    r.tap[j] = r.dcmode == MF_DC_SELF ? a : (r.dcmode == MF_DC_LOW ? mf_herm0(a, b) : mf_hermh(b, a));
   }
 }
 
@@ -537,18 +582,25 @@ template <int K, int C>
 MVN_HD void mf_fread_ahead(MfRegs<K>& r, const cfloat* in, bool dc, int tid) {
   if (C + 1 < MF_LINES) mf_fread<K>(r, in, C + 1, dc, tid);
 }
+// The loop of mf_body starts at batch MF_P, the only one in it that can hold fill lines: its first (K - 1) mod 8 ones
+// (`mixed`: this is that batch; the variant and the lines are compile-time constants, so FILL is known per line).
 template <int K, int C, int U>
-MVN_HD void mf_fline_dispatch(MfRegs<K>& r, const cfloat* in, cfloat* out, int u, bool fill, bool dc, int tid) {
+MVN_HD void mf_fline_dispatch(MfRegs<K>& r, const cfloat* in, cfloat* out, int u, bool mixed, bool dc, int tid) {
+  constexpr int NU = mf_slots(K) / 8;
   if (u == U) {
-    if (fill)
-      mf_filter_line<K, U, C, true>(r, in, out, dc, tid);
-    else
+    if constexpr (U == mf_fill_batches(K) % NU && C < (K - 1) % MF_LINES) {
+      if (mixed)
+        mf_filter_line<K, U, C, true>(r, in, out, dc, tid);
+      else
+        mf_filter_line<K, U, C, false>(r, in, out, dc, tid);
+    } else {
       mf_filter_line<K, U, C, false>(r, in, out, dc, tid);
+    }
     return;
   }
-  if constexpr (U + 1 < mf_slots(K) / 8) mf_fline_dispatch<K, C, U + 1>(r, in, out, u, fill, dc, tid);
+  if constexpr (U + 1 < NU) mf_fline_dispatch<K, C, U + 1>(r, in, out, u, mixed, dc, tid);
 }
-// (a FILL batch tracks nothing: the planes it reads are tracked by the piece that outputs them.  A step that
+// (a FILL line tracks nothing: the plane it reads is tracked by the piece that outputs it.  A step that
 // outputs tracks its newest input in[z + h]: over the pieces of a column every plane exactly once.)
 
 // the first stage of the transform back reads the wave's line of filter outputs; in the DC column it reads the
@@ -583,14 +635,49 @@ MVN_HD void mf_report(const MidFusedParams& P, const MfRegs<K>& r) {
   }
 }
 
+// Prologue pass I (I = -1 .. MF_P - 1; the passes I .. MF_P - 1 follow by recursion): the wave's line of batch I + 1
+// goes through the three forward stages back to back, the line of batch I + 2 and tap group I + 1 are requested, the
+// eight lines of batch I fill their window slots; one workgroup barrier.  Nothing is transformed back, nothing stored.
+// Every index is a compile-time constant.  In the DC column the previous tap group is split first.
+template <int K, int I, typename Ctx>
+MVN_HD void mf_prologue(const MidFusedParams& P, cfloat* lds, const cfloat* twl, Ctx& ctx, int c, int z0, int nsteps, bool dc) {
+  constexpr int NT_ = MF_NT, U = I < 0 ? 0 : I % (mf_slots(K) / 8);
+  (void)NT_;
+  const cfloat* fin = lds + (I & 1) * MF_BUF;
+  cfloat* fwd = lds + ((I + 1) & 1) * MF_BUF;
+  (void)fin;
+  if constexpr (I >= 0) {
+    if (dc) {
+      MVN_PHASE_NOSYNC(ctx, (mf_split_taps_dc<K, I>(r)));
+    }
+    MF_WPHASE(ctx, (mf_fread<K>(r, fin, 0, dc, tid)));
+  }
+  MF_WPHASE(ctx, (mf_fwd0<K>(r, fwd, tid), mf_fetch<K>(P, r, c, z0, I + 2, nsteps, tid), mf_load_taps<K, I + 1>(P, r, c, tid)));
+  if (dc) {
+    MVN_PHASE_NOSYNC(ctx, (mf_load_taps_dc<K, I + 1>(P, r, tid)));
+  }
+  MF_WPHASE(ctx, (mf_fwd1_r2<K>(r, fwd, tid)));
+  MF_WPHASE(ctx, (mf_fwd1_c2<K>(r, twl, tid), mf_fwd1_b2<K>(r, fwd, tid)));
+  MF_WPHASE(ctx, (mf_fwd2_r2<K>(r, fwd, tid)));
+  MF_WPHASE(ctx, (dftR<8, -1>(r.t2), mf_fwd2_b2<K>(r, fwd, tid)));
+  if constexpr (I >= 0) {
+#define MF_FILL(C) MF_WPHASE(ctx, (mf_fread_ahead<K, C>(r, fin, dc, tid), mf_filter_line<K, U, C, true>(r, fin, nullptr, dc, tid)));
+    MF_FILL(0) MF_FILL(1) MF_FILL(2) MF_FILL(3) MF_FILL(4) MF_FILL(5) MF_FILL(6) MF_FILL(7)
+#undef MF_FILL
+  }
+  MF_WPHASE(ctx, (mf_tw0_ahead<K>(r, twl, tid)));
+  MVN_PHASE(ctx, (void)0);
+  if constexpr (I + 1 < mf_fill_batches(K)) mf_prologue<K, I + 1>(P, lds, twl, ctx, c, z0, nsteps, dc);
+}
+
 template <int K, typename Ctx>
 MVN_HD void mf_body(const MidFusedParams& P, long block, cfloat* lds, Ctx& ctx) {
-  constexpr int NT_ = MF_NT;
+  constexpr int NT_ = MF_NT, MF_P = mf_fill_batches(K);
   (void)NT_;
   int c, z0, nout;
   mf_job(P, block, c, z0, nout);
   const int nsteps = nout + K - 1;
-  const int nb = (nsteps + MF_LINES - 1) / MF_LINES;
+  const int nb = (nsteps + MF_LINES - 1) / MF_LINES;  // > MF_P: a walk has at least K steps
   const bool dc = P.packed && c == 0;
   cfloat* twl = lds + 4 * MF_BUF;
   MVN_PHASE_NOSYNC(ctx, (mf_setup<K>(P, r, c, z0, nsteps, tid), mf_build_twiddles(P, twl, tid)));
@@ -599,6 +686,12 @@ MVN_HD void mf_body(const MidFusedParams& P, long block, cfloat* lds, Ctx& ctx) 
   }
   MVN_PHASE(ctx, (void)0);
   MVN_PHASE_NOSYNC(ctx, (mf_tw0_ahead<K>(r, twl, tid)));
+  mf_prologue<K, -1>(P, lds, twl, ctx, c, z0, nsteps, dc);
+  // behind the last barrier of the prologue: the DC column's last tap group - only that workgroup pays for it
+  if (dc) {
+    MVN_PHASE_NOSYNC(ctx, (mf_split_taps_dc<K, MF_P>(r)));
+  }
+  MVN_PHASE_NOSYNC(ctx, (mf_taps_arrived<K>(r)));
   // Four line buffers: the forward transforms of batch i + 1 go to FW[(i + 1) & 1], the filter step of batch i reads
   // FW[i & 1] and writes OU[i & 1], the transforms back of batch i - 1 read OU[(i - 1) & 1].  A wave's forward and
   // backward transform of an iteration are then independent of each other (two lines, two register sets): their
@@ -613,25 +706,36 @@ MVN_HD void mf_body(const MidFusedParams& P, long block, cfloat* lds, Ctx& ctx) 
 #define MF_PRIO_RESET() __builtin_amdgcn_s_setprio(0);
 #define MF_PRIO_RAISE_YOUNG() \
   if (wave_young != 0) __builtin_amdgcn_s_setprio(2);
+#define MF_OPAQUE(x) asm volatile("" : "+s"(x))
 #else
 #define MF_PRIO_RESET()
 #define MF_PRIO_RAISE_YOUNG()
+#define MF_OPAQUE(x) (void)0
 #endif
-  for (int i = -1; i <= nb; ++i) {
+  // (Device: the loop's first batch and the flag every filter line is tested behind are opaque to the compiler, and so
+  // is the thread id behind the loop (MVN_TILE_LOOP_TOP).  The loop then keeps the blocks it had when it ran from pass -1
+  // to pass nb - each filter line a block of its own behind a uniform test - and no address of the tail is parked in a
+  // register across it: with the bounds and the flag known, the same loop took 6 more registers at every tap count
+  // (profiles/mid_fused_ends.md).)
+  int i0 = MF_P, F = 1;
+  MF_OPAQUE(i0);
+  MF_OPAQUE(F);
+  for (int i = i0; i < nb; ++i) {
     const cfloat* fin = lds + (i & 1) * MF_BUF;
     cfloat* fout = lds + (2 + (i & 1)) * MF_BUF;
     cfloat* fwd = lds + ((i + 1) & 1) * MF_BUF;
     cfloat* inv = lds + (2 + ((i + 1) & 1)) * MF_BUF;
-    // The transform stages run in EVERY pass of the loop - in the two passes at either end on lines nobody wrote (their
-    // results go nowhere: mf_store_line_c and mf_fetch test the line's number themselves).  Behind a test each stage's
-    // LDS reads were followed, inside the test's block, by a wait and copies into the registers the next block
-    // expects: the latency the lines of the filter step were dealt out to cover was paid on the spot.
-    const bool F = i >= 0 && i < nb;
-    const bool fill = i * MF_LINES + MF_LINES - 1 < K - 1;
-    const int u = F ? i % (mf_slots(K) / 8) : 0;
+    // Both transforms run in EVERY pass of the loop - in the first one the transform back works on lines nobody wrote,
+    // in the last one the forward transform does (their results go nowhere: mf_store_line_c and mf_fetch test the
+    // line's number themselves).  Behind a test each stage's LDS reads were followed, inside the test's block, by a
+    // wait and copies into the registers the next block expects: the latency the lines of the filter step were dealt
+    // out to cover was paid on the spot.  The passes that need only one of the two are outside the loop: mf_prologue
+    // in front of it, the tail behind it.
+    const bool mixed = i == MF_P;
+    const int u = i % (mf_slots(K) / 8);
 #define MF_FLINE(C)                                                                \
   if (F) {                                                                         \
-    MF_WPHASE(ctx, (mf_fread_ahead<K, C>(r, fin, dc, tid), mf_fline_dispatch<K, C, 0>(r, fin, fout, u, fill, dc, tid)));  \
+    MF_WPHASE(ctx, (mf_fread_ahead<K, C>(r, fin, dc, tid), mf_fline_dispatch<K, C, 0>(r, fin, fout, u, mixed, dc, tid)));  \
   }
     MF_PRIO_RESET()
     // stage A: first stage back (reads the line) | first forward stage (reads the registers loaded ahead)
@@ -669,6 +773,21 @@ MVN_HD void mf_body(const MidFusedParams& P, long block, cfloat* lds, Ctx& ctx) 
   }
 #undef MF_PRIO_RESET
 #undef MF_PRIO_RAISE_YOUNG
+#undef MF_OPAQUE
+  // the tail: the last batch is transformed back and stored, nothing else
+  MVN_TILE_LOOP_TOP(ctx);
+  {
+    cfloat* inv = lds + (2 + ((nb + 1) & 1)) * MF_BUF;
+    MF_WPHASE(ctx, (mf_inv2_r<K>(r, inv, tid)));
+    if (dc) {
+      MF_WPHASE(ctx, (mf_inv2_fix_dc<K>(r, inv, tid)));
+    }
+    MF_WPHASE(ctx, (dftR<8, +1>(r.t), mf_inv2_b<K>(r, inv, tid)));
+    MF_WPHASE(ctx, (mf_inv1_r<K>(r, inv, tid)));
+    MF_WPHASE(ctx, (mf_inv1_c<K>(r, twl, tid), mf_inv1_b<K>(r, inv, tid)));
+    MF_WPHASE(ctx, (mf_inv0_r<K>(r, inv, tid)));
+    MF_WPHASE(ctx, (mf_store_line_c<K>(P, r, twl, c, z0, nout, nb - 1, tid)));
+  }
   MVN_PHASE_NOSYNC(ctx, (mf_report<K>(P, r)));
 }
 
