@@ -165,6 +165,62 @@ MVN_API int mvn_resample_stack(int device, const void* src, const mvn_stack_desc
 MVN_API int mvn_resample_time(int device, int u16, const mvn_view_geometry* geom, const int out_dims[3], int reps,
                               float* ms);
 MVN_API int mvn_resample_counters(long long out[2]);
+/* ---- fusion: the weighted average of the registered views -------------------------------------------------------
+ * mvn_fuse_resampled writes F = sum_v w_v I_v / sum_v w_v of num_views RAW views into `out`, a block of extents
+ * out_dims.  raw[v] is the raw stack of view v, raw_desc[v] describes it over geom[v].src_dims and geom[v] maps the block
+ * into it, all as in mvn_deconvolve_resampled; raw_desc == NULL means dense float32 in host memory for every view.
+ *
+ * Arithmetic (normative).  For an output voxel take the views in view order; (s_v, w_v) are the trilinear sample and
+ * the UNNORMALISED blend weight exactly as mvn_view_geometry defines them above, both 0 when the voxel is not inside
+ * view v.  Everything is float32, every operation is rounded once, nothing is contracted into a fused multiply-add:
+ *   t_v = w_v * s_v
+ *   N   = ((t_0 + t_1) + ...) + t_{V-1}        (starts from t_0 itself, not from 0 + t_0)
+ *   W   = ((w_0 + w_1) + ...) + w_{V-1}
+ *   F   = W > 0 ? N / W : fill                 (correctly rounded divide)
+ * A uint16 output stores F >= 65535 ? 65535 : F > 0 ? rintf(F) : 0 - ties round to even, a NaN becomes 0 - and the
+ * same rule applies to `fill`.
+ *
+ * `out` is MVN_F32 or MVN_U16, in host or device memory, with the strides rules of psi in mvn_deconvolve_described
+ * (out_desc == NULL: dense float32 in host memory).  An output in device memory is written where it lies, whatever its
+ * (positive, non-overlapping) strides - with stores of 4 elements where rows are contiguous and base and pitches are
+ * multiples of 4 elements -, and only its own elements are written: a window of a larger array keeps its surroundings.
+ * An output in host memory (contiguous rows) is written into a dense device volume first and copied out.  Raw stacks in
+ * device memory are read where they lie; raw stacks in host memory are uploaded into temporaries, all num_views at
+ * once.  One kernel reads all views per output voxel; no image and no weights volume is written on the way.
+ * The call blocks.  `stream`, the device choice and its checks are those of the described call.  Errors (< 0, message
+ * in mvn_last_error(), `out` untouched) are those of the resampled call, plus num_views < 1 and a non-finite fill.
+ * mvn_fuse_memory_resampled: the bytes that call would allocate on the device, allocating nothing: 176 bytes per view
+ * (the table of the views' records), plus the dense output volume when `out` is in host memory, plus the sum of the raw
+ * stacks in host memory (one element for a stack of strides {0, 0, 0}).  An all-device call costs the table alone.
+ * mvn_fuse_time: ms[0] = milliseconds per fusion from num_views resident raw stacks of geom[v].src_dims (uint16 when
+ * u16 != 0, else float32) into a resident float32 volume of extents out_dims, `reps` passes between two stream events
+ * behind one pass that warms up (mvn_fuse_counters' out[0] moves by reps + 1); ms[1] = the same for num_views launches
+ * of the resample pass on the same stacks and geometries, each writing an image and a weights volume - the route a
+ * fusion took before this entry point, without its combining pass; ms[2] = a plain copy of one volume.
+ * mvn_fuse_counters: out[0] = launches of the fusion from raw stacks, out[1] = launches of the fusion of an engine's
+ * volumes (psi start, mvn_engine_fuse_psi), since process start. */
+MVN_API int mvn_fuse_resampled(void* out, const mvn_stack_desc* out_desc, const int out_dims[3], int num_views,
+                               const void* const* raw, const mvn_stack_desc* raw_desc,
+                               const mvn_view_geometry* geom, float fill, void* stream, int device);
+MVN_API int mvn_fuse_memory_resampled(const mvn_stack_desc* out_desc, const int out_dims[3], int num_views,
+                                      const mvn_stack_desc* raw_desc, const mvn_view_geometry* geom,
+                                      int device, size_t* bytes);
+MVN_API int mvn_fuse_time(int device, int u16, int num_views, const mvn_view_geometry* geom,
+                          const int out_dims[3], int reps, float* ms);
+MVN_API int mvn_fuse_counters(long long out[2]);
+/* Where mvn_deconvolve_resampled starts from (process-wide, captured at the start of that call; no other entry point
+ * honours it):
+ * 0 (default) the caller's psi - launches and bits as without this switch;
+ * 1 psi is OUTPUT only (its pointer and descriptor must still be valid; what it holds is never read): after every view
+ *   has been placed and before the weights are normalised, one pass fills psi's window with the F above, s_v and w_v
+ *   read from the engine's image volumes and its weights volumes as they stand then - under weights_mode 1 the
+ *   unnormalised computed blend weights, so psi starts from exactly mvn_fuse_resampled's float32 result; under
+ *   weights_mode 0 the caller's weights.  The margins then follow the padding policy as if that stack had been handed
+ *   in: zeros, or the mirror image under "reflect".  No extra volume is held: mvn_deconvolve_memory_resampled is
+ *   unchanged.  A call of 0 iterations returns psi unchanged in either mode.
+ * A mode other than 0 or 1, or a non-finite fill, is an error. */
+MVN_API int mvn_set_psi_start(int mode, float fill);
+MVN_API int mvn_get_psi_start(int* mode, float* fill);
 /* out[0] = divide passes launched on a uint16 image, out[1] = ingest passes that wrote a uint16 volume, since process start */
 MVN_API int mvn_image_storage_counters(long long out[2]);
 /* Padding policy of inplace_gpu_deconvolve for the calls that follow (process-wide): "zero"
@@ -391,6 +447,11 @@ MVN_API int mvn_engine_set_view_resampled(mvn_engine* e, int v, const void* imag
                                           const mvn_stack_desc* weights_desc, const float* kernel1, const int k1dims[3],
                                           const float* kernel2, const int k2dims[3], void* stream);
 MVN_API int mvn_engine_normalize_weights(mvn_engine* e);
+/* psi <- the fusion F of mvn_fuse_resampled (above) of the views as the engine holds them: s_v from its image volumes,
+ * w_v from its weights volumes as they stand (before mvn_engine_normalize_weights: the unnormalised computed weights),
+ * `fill` where no weight is positive; margins as mvn_engine_set_psi leaves them.  Blocking.  Refused - psi is left as it
+ * was - by an engine with a halo hook, with streamed views, or with a uint16 image volume, and for a non-finite fill. */
+MVN_API int mvn_engine_fuse_psi(mvn_engine* e, float fill);
 /* enqueue `iterations` sequential (Gauss-Seidel) sweeps over the views */
 MVN_API int mvn_engine_iterate(mvn_engine* e, int iterations, double lambda, float min_value);
 /* resident engine, blocking: stats receives 3 doubles per iteration run ({S_k, M_k, P_k} over the whole volume,

@@ -174,6 +174,11 @@ static std::atomic<int> g_image_storage{0};
 // per view: a described call in storage mode `mode` wants this image kept as uint16
 static bool keeps_u16(const StackRef& image, int mode) { return mode == 1 && image.u16 && !image.broadcast(); }
 
+// ---- psi start (mvn_set_psi_start): captured at the start of mvn_deconvolve_resampled ----
+static std::mutex g_psi_start_mu;
+static int g_psi_start_mode = 0;
+static float g_psi_start_fill = 0.f;
+
 static MemoryQuery memory_query(const shape_t& ext, const workspace& input, const LoopOptions& loop,
                                 size_t embed_floats, const std::vector<char>& keep_u16) {
   MemoryQuery q;
@@ -678,6 +683,9 @@ struct CallStacks {
   // whether its weights are computed from it (weights[v].ptr is then null) and normalised once all views are placed
   std::vector<ResampleGeom> geom;
   bool computed_weights = false;
+  // mvn_set_psi_start as the call captured it: 1 = psi is output only, the loop starts from the fusion of the views
+  int psi_start = 0;
+  float psi_fill = 0.f;
 };
 
 // a descriptor and its pointer as a StackRef, everything about it checked that can be without touching the memory
@@ -817,8 +825,9 @@ static void deconvolve_call(const workspace& input, const CallStacks& cs, int de
         eng.set_view(v, cs.image[(size_t)v], cs.weights[(size_t)v], d.kernel1_, d.kernel1_dims_, d.kernel2_,
                      d.kernel2_dims_);
       }
+      if (cs.psi_start == 1) eng.fuse_psi(cs.psi_fill);  // (from the weights as they stand: before their normalisation)
       if (cs.computed_weights) eng.normalize_weights();
-      eng.set_psi(cs.psi);
+      if (cs.psi_start != 1) eng.set_psi(cs.psi);
       eng.iterate(input.num_iterations_, input.lambda_, input.minValue_, loop, conv);
       eng.sync();
       eng.get_psi(cs.psi);
@@ -839,12 +848,13 @@ static void deconvolve_call(const workspace& input, const CallStacks& cs, int de
     lap("allocate view buffers");
     std::unique_lock<std::mutex> pcie(upload_mutex(dev));  // handed to the uploader thread's scope below
     eng.wait_for_caller(cs.stream);
-    eng.set_psi(cs.psi);
+    if (cs.psi_start != 1) eng.set_psi(cs.psi);
     // views that are in device memory already: ingested on the compute stream, in view order; resampled views too,
     // wherever their raw stacks are (computed weights need every view in place before the loop's first read)
     for (int v = 0; v < V; ++v)
       if ((cs.image[(size_t)v].device && cs.weights[(size_t)v].device) || cs.image[(size_t)v].geom)
         eng.ingest_device_view(v, cs.image[(size_t)v], cs.weights[(size_t)v]);
+    if (cs.psi_start == 1) eng.fuse_psi(cs.psi_fill);  // (every view of a resampled call is in place here)
     if (cs.computed_weights) eng.normalize_weights();
     lap("upload psi");
     std::exception_ptr up_err;
@@ -1002,6 +1012,10 @@ int mvn_deconvolve_resampled(void* psi, struct workspace input, const mvn_call_d
     CallStacks dc;
     dc.stream = desc ? desc->stream : nullptr;
     dc.computed_weights = weights_mode == 1;
+    {
+      std::lock_guard<std::mutex> lk(g_psi_start_mu);
+      dc.psi_start = g_psi_start_mode, dc.psi_fill = g_psi_start_fill;
+    }
     dc.psi = described_stack(psi, desc ? &desc->psi : nullptr, dims, "psi", false, true);
     int owner = -1;
     check_location(dc.psi, "psi", &owner);
@@ -1409,6 +1423,225 @@ int mvn_resample_time(int device, int u16, const mvn_view_geometry* geom, const 
       be::launch_copy3d(dw.get(), L.RP, plane, di.get(), L.RP, plane, (int)L.RP, L.d1, L.d0, s);
       be::dzero(di.get(), bytes, s);
     });
+  });
+}
+
+// ---- fusion (mvn_fuse.hpp) ---------------------------------------------------------------------------------------
+int mvn_fuse_counters(long long out[2]) {
+  return guarded("mvn_fuse_counters", [&] {
+    if (!out) throw std::invalid_argument("null out");
+    be::fuse_counters(out);
+  });
+}
+
+int mvn_set_psi_start(int mode, float fill) {
+  return guarded("mvn_set_psi_start", [&] {
+    if (mode != 0 && mode != 1)
+      throw std::invalid_argument("psi start mode must be 0 (the caller's psi) or 1 (the fusion of the views)");
+    if (!std::isfinite(fill)) throw std::invalid_argument("fill must be finite");
+    std::lock_guard<std::mutex> lk(g_psi_start_mu);
+    g_psi_start_mode = mode, g_psi_start_fill = fill;
+  });
+}
+
+int mvn_get_psi_start(int* mode, float* fill) {
+  return guarded("mvn_get_psi_start", [&] {
+    if (!mode || !fill) throw std::invalid_argument("null argument");
+    std::lock_guard<std::mutex> lk(g_psi_start_mu);
+    *mode = g_psi_start_mode, *fill = g_psi_start_fill;
+  });
+}
+
+// what a fusion call is made of, everything checked that can be without its pointers (raw == NULL: a memory query)
+extern "C++" {
+namespace {
+struct FuseCall {
+  int dims[3];
+  StackRef out;
+  std::vector<ResampleGeom> geom;
+  std::vector<StackRef> raw;
+  size_t out_bytes = 0;  // the dense device volume of an output in host memory
+  size_t raw_bytes = 0;  // the uploads of the raw stacks in host memory, all V at once
+  size_t table_bytes = 0;
+  size_t bytes() const { return out_bytes + raw_bytes + table_bytes; }
+};
+}  // namespace
+static FuseCall fuse_call(const void* out, const mvn_stack_desc* out_desc, const int* out_dims, int num_views,
+                          const void* const* raw, const mvn_stack_desc* raw_desc, const mvn_view_geometry* geom,
+                          float fill, bool pointers) {
+  static const int placeholder = 0;  // (a memory query brings no pointers: nothing is read through this one)
+  if (!out_dims) throw std::invalid_argument("null out_dims");
+  if (num_views < 1) throw std::invalid_argument("num_views must be >= 1");
+  if (!geom) throw std::invalid_argument("null geom");
+  if (pointers && !raw) throw std::invalid_argument("null raw");
+  if (!std::isfinite(fill)) throw std::invalid_argument("fill must be finite");
+  FuseCall c;
+  for (int d = 0; d < 3; ++d) {
+    if (out_dims[d] < 1) throw std::invalid_argument("extents must be positive");
+    c.dims[d] = out_dims[d];
+  }
+  c.out = described_stack(pointers ? out : &placeholder, out_desc, c.dims, "out", true, true);
+  const size_t voxels = (size_t)c.dims[0] * (size_t)c.dims[1] * (size_t)c.dims[2];
+  if (!c.out.device) {
+    if ((c.dims[2] > 1 && c.out.stride[2] != 1) || (c.dims[1] > 1 && c.out.stride[1] < c.dims[2]))
+      throw std::invalid_argument("out: a stack in host memory needs contiguous rows that do not overlap");
+    c.out_bytes = voxels * (c.out.u16 ? sizeof(uint16_t) : sizeof(float));
+  }
+  c.table_bytes = (size_t)num_views * sizeof(FuseView);
+  c.geom.reserve((size_t)num_views);
+  for (int v = 0; v < num_views; ++v) c.geom.push_back(checked_geometry(geom + v, "geom " + std::to_string(v)));
+  for (int v = 0; v < num_views; ++v) {
+    const ResampleGeom& g = c.geom[(size_t)v];
+    StackRef r = described_stack(pointers ? raw[v] : &placeholder, raw_desc ? raw_desc + v : nullptr, g.m,
+                                 "raw " + std::to_string(v), true, false);
+    r.geom = &g;
+    Engine::check_raw_host(r, g.m);
+    if (!r.device) {
+      const size_t esz = r.u16 ? sizeof(uint16_t) : sizeof(float);
+      c.raw_bytes += r.broadcast() ? esz : (size_t)g.m[0] * (size_t)g.m[1] * (size_t)g.m[2] * esz;
+    }
+    c.raw.push_back(r);
+  }
+  return c;
+}
+}  // extern "C++"
+
+int mvn_fuse_memory_resampled(const mvn_stack_desc* out_desc, const int out_dims[3], int num_views,
+                              const mvn_stack_desc* raw_desc, const mvn_view_geometry* geom, int device, size_t* bytes) {
+  return guarded("mvn_fuse_memory_resampled", [&] {
+    if (!bytes) throw std::invalid_argument("null bytes");
+    *bytes = 0;
+    (void)device;
+    *bytes = fuse_call(nullptr, out_desc, out_dims, num_views, nullptr, raw_desc, geom, 0.f, false).bytes();
+  });
+}
+
+int mvn_fuse_resampled(void* out, const mvn_stack_desc* out_desc, const int out_dims[3], int num_views,
+                       const void* const* raw, const mvn_stack_desc* raw_desc, const mvn_view_geometry* geom, float fill,
+                       void* stream, int device) {
+  return guarded("mvn_fuse_resampled", [&] {
+    const FuseCall c = fuse_call(out, out_desc, out_dims, num_views, raw, raw_desc, geom, fill, true);
+    const int V = num_views;
+    int owner = -1;
+    check_location(c.out, "out", &owner);
+    for (int v = 0; v < V; ++v) check_location(c.raw[(size_t)v], "raw " + std::to_string(v), &owner);
+    if (owner >= 0 && device >= 0 && device != owner)
+      throw std::invalid_argument("the stacks live on device " + std::to_string(owner) + ", not on device " +
+                                  std::to_string(device));
+    const int dev = pick_device(owner >= 0 ? owner : device);
+    std::lock_guard<std::mutex> lk(device_mutex(dev));
+    be::set_device(dev);
+    const int* n = c.dims;
+    const size_t esz = c.out.u16 ? sizeof(uint16_t) : sizeof(float);
+    std::vector<be::DeviceBuffer<char>> uploads((size_t)V);
+    be::DeviceBuffer<char> dout;
+    if (c.out_bytes) dout = be::DeviceBuffer<char>(c.out_bytes);
+    const be::DeviceBuffer<FuseView> table(c.table_bytes);
+    std::vector<FuseView> records((size_t)V);
+    const be::Event caller = be::Event::sync_only();
+    const be::Stream own = be::Stream::create();
+    const be::stream_t s = own.get();
+    if (stream) {  // the caller's device stacks are complete behind what its stream holds now
+      be::event_record(caller.get(), (be::stream_t)stream);
+      be::stream_wait_event(s, caller.get());
+    }
+    for (int v = 0; v < V; ++v) {
+      StackRef r = c.raw[(size_t)v];
+      if (!r.device) Engine::upload_raw(c.raw[(size_t)v], c.geom[(size_t)v].m, uploads[(size_t)v], &r, s);
+      FuseView& f = records[(size_t)v];
+      std::memset(&f, 0, sizeof(f));
+      f.src = r.ptr, f.s0 = r.stride[0], f.s1 = r.stride[1], f.s2 = r.stride[2];
+      f.u16 = r.u16 ? 1 : 0;
+      f.g = c.geom[(size_t)v];
+    }
+    be::h2d(table.get(), records.data(), c.table_bytes, s);
+    FuseParams p;
+    p.out_u16 = c.out.u16 ? 1 : 0;
+    p.n0 = n[0], p.n1 = n[1], p.n2 = n[2];
+    p.views = table.get(), p.V = V, p.fill = fill;
+    if (c.out.device) {  // written where it lies
+      p.out = (void*)c.out.ptr, p.q0 = c.out.stride[0], p.q1 = c.out.stride[1], p.q2 = c.out.stride[2];
+    } else {
+      p.out = dout.get(), p.q0 = (long long)n[1] * n[2], p.q1 = n[2], p.q2 = 1;
+    }
+    for (int d = 0; d < 3; ++d)  // (an extent of 1 makes no use of its stride)
+      if (n[d] == 1) (d == 0 ? p.q0 : d == 1 ? p.q1 : p.q2) = 1;
+    be::launch_fuse_resampled(p, s);
+    if (!c.out.device) {
+      const size_t width = (size_t)n[2] * esz;
+      const size_t pitch = n[1] == 1 ? width : (size_t)c.out.stride[1] * esz;
+      for (int z = 0; z < n[0]; ++z)
+        be::d2h_2d((char*)out + (long long)z * c.out.stride[0] * (long long)esz, pitch,
+                   dout.get() + (size_t)z * n[1] * width, width, width, (size_t)n[1], s);
+    }
+    be::stream_sync(s);
+  });
+}
+
+// ms[0]: the fusion from V resident raw stacks of geom[v].src_dims (uint16, or float32) into a resident float32 volume
+// of extents out_dims, per pass over `reps` passes between two stream events (one more pass warms up: the from-raw
+// counter moves by reps + 1); ms[1]: V launches of the resample pass on the same stacks and geometries, image and
+// weights volumes written, likewise; ms[2]: a plain copy of one volume
+int mvn_fuse_time(int device, int u16, int num_views, const mvn_view_geometry* geom, const int out_dims[3], int reps,
+                  float* ms) {
+  return guarded("mvn_fuse_time", [&] {
+    if (!out_dims || !ms || !geom) throw std::invalid_argument("null argument");
+    if (out_dims[0] < 1 || out_dims[1] < 1 || out_dims[2] < 1 || reps < 1 || num_views < 1)
+      throw std::invalid_argument("extents, reps and num_views must be positive");
+    const int V = num_views;
+    std::vector<ResampleGeom> g;
+    for (int v = 0; v < V; ++v) g.push_back(checked_geometry(geom + v, "geom " + std::to_string(v)));
+    const int dev = pick_device(device);
+    std::lock_guard<std::mutex> lk(device_mutex(dev));
+    be::set_device(dev);
+    const Layout L(out_dims[0], out_dims[1], out_dims[2]);
+    const size_t bytes = L.real_floats() * sizeof(float);
+    const size_t esz = u16 ? sizeof(uint16_t) : sizeof(float);
+    const be::DeviceBuffer<float> di(bytes), dw(bytes);
+    std::vector<be::DeviceBuffer<>> dr;
+    const be::DeviceBuffer<FuseView> table((size_t)V * sizeof(FuseView));
+    std::vector<FuseView> records((size_t)V);
+    std::vector<unsigned char> h;
+    for (int v = 0; v < V; ++v) dr.emplace_back((size_t)g[(size_t)v].m[0] * g[(size_t)v].m[1] * g[(size_t)v].m[2] * esz);
+    const be::Stream st = be::Stream::create();
+    const be::stream_t s = st.get();
+    for (int v = 0; v < V; ++v) {
+      const int* m = g[(size_t)v].m;
+      const size_t raw = (size_t)m[0] * (size_t)m[1] * (size_t)m[2];
+      h.resize(raw * esz);
+      if (u16)
+        for (size_t i = 0; i < raw; ++i) ((uint16_t*)h.data())[i] = (uint16_t)(100u + (i + 977u * (unsigned)v) % 4001u);
+      else
+        for (size_t i = 0; i < raw; ++i) ((float*)h.data())[i] = 100.f + (float)((i + 977u * (unsigned)v) % 4001u);
+      be::h2d(dr[(size_t)v].get(), h.data(), h.size(), s);
+      be::stream_sync(s);  // (h is filled again)
+      FuseView& f = records[(size_t)v];
+      std::memset(&f, 0, sizeof(f));
+      f.src = dr[(size_t)v].get(), f.s0 = (long long)m[1] * m[2], f.s1 = m[2], f.s2 = 1;
+      f.u16 = u16 ? 1 : 0;
+      f.g = g[(size_t)v];
+    }
+    be::h2d(table.get(), records.data(), records.size() * sizeof(FuseView), s);
+    be::dzero(di.get(), bytes, s);
+    be::dzero(dw.get(), bytes, s);
+    be::stream_sync(s);
+    FuseParams p;
+    p.out = di.get(), p.out_u16 = 0, p.q0 = (long long)L.d1 * L.RP, p.q1 = L.RP, p.q2 = 1;
+    p.n0 = L.d0, p.n1 = L.d1, p.n2 = L.d2;
+    p.views = table.get(), p.V = V, p.fill = 0.f;
+    ms[0] = time_on_stream(s, reps, [&] { be::launch_fuse_resampled(p, s); });
+    ms[1] = time_on_stream(s, reps, [&] {
+      for (int v = 0; v < V; ++v) {
+        ResampleParams r = resample_alone(L, di.get(), dw.get());
+        const FuseView& f = records[(size_t)v];
+        r.src = f.src, r.s0 = f.s0, r.s1 = f.s1, r.s2 = f.s2;
+        r.g = f.g;
+        be::launch_resample(r, u16 != 0, s);
+      }
+    });
+    const long plane = (long)L.d1 * L.RP;
+    ms[2] = time_on_stream(
+        s, reps, [&] { be::launch_copy3d(dw.get(), L.RP, plane, di.get(), L.RP, plane, (int)L.RP, L.d1, L.d0, s); });
   });
 }
 
@@ -2095,6 +2328,8 @@ int mvn_engine_set_view_resampled(mvn_engine* e, int v, const void* image, const
 int mvn_engine_normalize_weights(mvn_engine* e) {
   MVN_ENGINE_CALL("mvn_engine_normalize_weights", E.normalize_weights());
 }
+
+int mvn_engine_fuse_psi(mvn_engine* e, float fill) { MVN_ENGINE_CALL("mvn_engine_fuse_psi", E.fuse_psi(fill)); }
 
 int mvn_engine_set_psi_described(mvn_engine* e, const void* psi, const mvn_stack_desc* d, void* stream) {
   MVN_ENGINE_CALL("mvn_engine_set_psi_described", {

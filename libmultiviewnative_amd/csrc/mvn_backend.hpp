@@ -19,6 +19,7 @@
 #include "mvn_tv.hpp"
 #include "mvn_reflect.hpp"
 #include "mvn_resample.hpp"
+#include "mvn_fuse.hpp"
 
 namespace mvn {
 namespace be {
@@ -159,6 +160,12 @@ void reflect_counters(long long out[2]);
 void launch_resample(const ResampleParams& p, bool u16, stream_t s);
 void launch_weights_normalize(const NormalizeParams& p, stream_t s);
 void resample_counters(long long out[2]);
+// fusion (mvn_fuse.hpp): the weighted average of the V raw views behind the device table p.views into p.out, and of an
+// engine's V image and V weights volumes behind the device table p.vols into the window of p.psi.  fuse_counters:
+// launches of the one and of the other since process start
+void launch_fuse_resampled(const FuseParams& p, stream_t s);
+void launch_fuse_volumes(const FuseVolumesParams& p, stream_t s);
+void fuse_counters(long long out[2]);
 
 // stand-alone pointwise ops on flat arrays (legacy ABI: compute_quotient / compute_final_values)
 void launch_divide(const float* view, float* inout, size_t n, stream_t s);

@@ -529,6 +529,30 @@ void launch_weights_normalize(const NormalizeParams& p, stream_t) {
     for (int t = 0; t < MVN_INGEST_WG; ++t) mvn_normalize_rows(p, blk, t);
 }
 
+static std::atomic<long long> g_fuse_raw_launches{0}, g_fuse_volumes_launches{0};
+void fuse_counters(long long out[2]) {
+  out[0] = g_fuse_raw_launches.load();
+  out[1] = g_fuse_volumes_launches.load();
+}
+
+void launch_fuse_resampled(const FuseParams& p, stream_t) {
+  mvn_fuse_check(p);
+  const long nblocks = mvn_fuse_blocks(p);
+  ++g_fuse_raw_launches;
+#pragma omp parallel for schedule(static)
+  for (long blk = 0; blk < nblocks; ++blk)
+    for (int t = 0; t < MVN_RS_WG; ++t) mvn_fuse_tile(p, blk, t);
+}
+
+void launch_fuse_volumes(const FuseVolumesParams& p, stream_t) {
+  mvn_fuse_volumes_check(p);
+  const long nblocks = mvn_fuse_volumes_blocks(p);
+  ++g_fuse_volumes_launches;
+#pragma omp parallel for schedule(static)
+  for (long blk = 0; blk < nblocks; ++blk)
+    for (int t = 0; t < MVN_INGEST_WG; ++t) mvn_fuse_rows(p, blk, t);
+}
+
 static std::atomic<long> g_tv_launches{0};
 long tv_launch_count() { return g_tv_launches.load(); }
 void launch_tv(const TvParams& p0, stream_t) {

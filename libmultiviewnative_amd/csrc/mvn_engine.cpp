@@ -984,6 +984,36 @@ long long Engine::resample_pair(float* image_dst, float* weights_dst, const Stac
   return bytes;
 }
 
+void Engine::check_raw_host(const StackRef& image, const int* m) {
+  if (!image.device && !image.broadcast()) check_host_rows(image, m);
+}
+
+long long Engine::upload_raw(const StackRef& image, const int* m, be::DeviceBuffer<char>& tmp, StackRef* there,
+                             be::stream_t s) {
+  const size_t esz = image.u16 ? sizeof(uint16_t) : sizeof(float);
+  *there = image;
+  there->device = true;
+  long long bytes;
+  if (image.broadcast()) {
+    bytes = (long long)esz;
+    tmp = be::DeviceBuffer<char>(esz);
+    be::h2d(tmp.get(), image.ptr, esz, s);
+  } else {
+    check_host_rows(image, m);
+    bytes = (long long)m[0] * m[1] * m[2] * (long long)esz;
+    tmp = be::DeviceBuffer<char>((size_t)bytes);
+    const bool dense = (m[1] == 1 || image.stride[1] == m[2]) && (m[0] == 1 || image.stride[0] == (long long)m[1] * m[2]);
+    if (dense)
+      be::h2d(tmp.get(), image.ptr, (size_t)bytes, s);
+    else
+      host_rows_to_device(tmp.get(), (size_t)m[2] * esz, (size_t)m[1] * m[2] * esz, (const char*)image.ptr,
+                          image.stride[0] * (long long)esz, image.stride[1] * (long long)esz, (size_t)m[2] * esz, m, s);
+    there->stride[0] = (long long)m[1] * m[2], there->stride[1] = m[2], there->stride[2] = 1;
+  }
+  there->ptr = tmp.get();
+  return bytes;
+}
+
 long long Engine::resample_raw(ResampleParams p, const StackRef& image, be::stream_t s) {
   if (!image.ptr || !image.geom) throw std::invalid_argument("mvn: null stack");
   const ResampleGeom& g = *image.geom;
@@ -997,26 +1027,9 @@ long long Engine::resample_raw(ResampleParams p, const StackRef& image, be::stre
   long long bytes = 0;
   try {
     if (!image.device) {  // the raw stack crosses PCIe as it is, into a dense temporary
-      const size_t esz = image.u16 ? sizeof(uint16_t) : sizeof(float);
-      if (image.broadcast()) {
-        bytes = (long long)esz;
-        tmp = be::DeviceBuffer<char>(esz);
-        be::h2d(tmp.get(), image.ptr, esz, s);
-      } else {
-        check_host_rows(image, g.m);
-        bytes = (long long)g.m[0] * g.m[1] * g.m[2] * (long long)esz;
-        tmp = be::DeviceBuffer<char>((size_t)bytes);
-        const bool dense = (g.m[1] == 1 || image.stride[1] == g.m[2]) &&
-                           (g.m[0] == 1 || image.stride[0] == (long long)g.m[1] * g.m[2]);
-        if (dense)
-          be::h2d(tmp.get(), image.ptr, (size_t)bytes, s);
-        else
-          host_rows_to_device(tmp.get(), (size_t)g.m[2] * esz, (size_t)g.m[1] * g.m[2] * esz, (const char*)image.ptr,
-                              image.stride[0] * (long long)esz, image.stride[1] * (long long)esz, (size_t)g.m[2] * esz,
-                              g.m, s);
-        p.s0 = (long long)g.m[1] * g.m[2], p.s1 = g.m[2], p.s2 = 1;
-      }
-      p.src = tmp.get();
+      StackRef there;
+      bytes = upload_raw(image, g.m, tmp, &there, s);
+      p.src = there.ptr, p.s0 = there.stride[0], p.s1 = there.stride[1], p.s2 = there.stride[2];
     }
     be::launch_resample(p, image.u16, s);
     if (tmp.get()) be::stream_sync(s);
@@ -1045,6 +1058,36 @@ void Engine::normalize_weights() {
   p.o0 = host_off_[0], p.o1 = host_off_[1], p.o2 = host_off_[2];
   be::launch_weights_normalize(p, stream_.get());
   for (size_t v = 0; v < V; ++v) mirror_margins(views_[v].weights.get(), false, stream_.get());
+  be::stream_sync(stream_.get());
+}
+
+void Engine::fuse_psi(float fill) {
+  be::set_device(device_);
+  if (halo_fn_) throw std::invalid_argument("mvn: fusion into psi is not for an engine with a halo hook");
+  if (!streamed_order_.empty()) throw std::invalid_argument("mvn: fusion into psi needs every view resident");
+  if (!std::isfinite(fill)) throw std::invalid_argument("mvn: fill must be finite");
+  const Layout& L = plan_->L;
+  const size_t V = views_.size();
+  if (V < 1) throw std::invalid_argument("mvn: fusion into psi needs a view");
+  fuse_tab_host_.assign(2 * V, nullptr);
+  for (size_t v = 0; v < V; ++v) {
+    if (!views_[v].image.get() || !views_[v].weights.get()) throw std::invalid_argument("mvn: fusion into psi needs every view placed");
+    if (views_[v].image_u16) throw std::invalid_argument("mvn: fusion into psi is not for an engine that holds a uint16 image volume");
+    fuse_tab_host_[v] = views_[v].image.get();
+    fuse_tab_host_[V + v] = views_[v].weights.get();
+  }
+  if (!fuse_tab_.get()) fuse_tab_ = be::DeviceBuffer<const float*>(2 * V * sizeof(float*));
+  be::h2d(fuse_tab_.get(), fuse_tab_host_.data(), 2 * V * sizeof(float*), stream_.get());
+  psi_spec_valid_ = false;
+  // (the loop has written the margins of an embedded psi; the row padding of an odd last extent reads zero)
+  if (embedded_ || L.RP != L.d2) be::dzero(psi_.get(), plan_->main_bytes(), stream_.get());
+  FuseVolumesParams p;
+  p.psi = psi_.get(), p.vols = fuse_tab_.get(), p.V = (int)V, p.RP = L.RP, p.D1 = L.d1;
+  p.n0 = host_dims_[0], p.n1 = host_dims_[1], p.n2 = host_dims_[2];
+  p.o0 = host_off_[0], p.o1 = host_off_[1], p.o2 = host_off_[2];
+  p.fill = fill;
+  be::launch_fuse_volumes(p, stream_.get());
+  mirror_margins(psi_.get(), false, stream_.get());
   be::stream_sync(stream_.get());
 }
 

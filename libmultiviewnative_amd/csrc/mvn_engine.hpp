@@ -493,6 +493,12 @@ class Engine {
   // crosses into a temporary device buffer first, which is freed once `s` has passed it (the host waits for that).
   // Returns the bytes that crossed PCIe.  The current device is the destination's.
   static long long resample_raw(ResampleParams p, const StackRef& image, be::stream_t s);
+  // Its upload alone: a raw stack in HOST memory of extents m (contiguous rows, or one value) as it is into the
+  // temporary `tmp`, allocated here and assigned before anything is enqueued on s; *there describes it in device
+  // memory.  Returns the bytes that crossed.  check_raw_host: what it refuses, with nothing touched.
+  static long long upload_raw(const StackRef& image, const int* m, be::DeviceBuffer<char>& tmp, StackRef* there,
+                              be::stream_t s);
+  static void check_raw_host(const StackRef& image, const int* m);
   // divide passes launched on a uint16 image, ingest passes that wrote a uint16 volume, since process start
   static void image_storage_counters(long long out[2]);
   // calls that streamed views, streamed view updates, bytes streamed (host -> device), since process start
@@ -513,6 +519,11 @@ class Engine {
   // on the window (mvn_resample.hpp); under "reflect" the fill of those weights volumes runs here, behind it.  Once,
   // after the last view has been placed.  Blocking.
   void normalize_weights();
+  // psi <- the fusion of the views as they stand (mvn_fuse.hpp, k_fuse_volumes): over the window, from the V image and
+  // the V weights volumes - unnormalised computed weights when it runs before normalize_weights -, `fill` where no
+  // weight is positive; the margins then are what set_psi leaves (zeros, or the mirror image under "reflect").
+  // Refused with a halo hook, streamed views or a uint16 image volume; psi is then left as it was.  Blocking.
+  void fuse_psi(float fill);
   // the caller produced its device stacks on `caller_stream`: the engine's streams wait for what is enqueued there
   // now (an event, no host wait); nullptr: nothing to wait for
   void wait_for_caller(void* caller_stream);
@@ -696,6 +707,8 @@ class Engine {
   long long resample_pair(float* image_dst, float* weights_dst, const StackRef& image, const StackRef& weights,
                           be::stream_t s);
   std::vector<float*> weights_tab_host_;  // what weights_tab_ was filled from
+  be::DeviceBuffer<const float*> fuse_tab_;  // fuse_psi: V image volumes, then V weights volumes
+  std::vector<const float*> fuse_tab_host_;
   bool reflect_ = false;           // set_reflect
   bool margins_mirrored_ = false;  // some image / weights volume or ring slot may hold mirrored margins
   // image and weights of one view; without an embedding scratch a uint16 image that is converted lands in the weights

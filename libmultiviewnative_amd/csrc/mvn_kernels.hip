@@ -255,6 +255,15 @@ __global__ __launch_bounds__(MVN_INGEST_WG) void k_weights_normalize(const Norma
   mvn_normalize_rows(p, (long)blockIdx.x, (int)threadIdx.x);
 }
 
+// fusion (mvn_fuse.hpp): the weighted average of the views, from their raw stacks and from an engine's volumes
+__global__ __launch_bounds__(MVN_RS_WG) void k_fuse_resampled(const FuseParams p) {
+  mvn_fuse_tile(p, (long)blockIdx.x, (int)threadIdx.x);
+}
+
+__global__ __launch_bounds__(MVN_INGEST_WG) void k_fuse_volumes(const FuseVolumesParams p) {
+  mvn_fuse_rows(p, (long)blockIdx.x, (int)threadIdx.x);
+}
+
 // vector extrapolation between sweeps (mvn_extrapolate.hpp): two streaming passes and the reduction between them
 template <int W>
 __global__ __launch_bounds__(MVN_ACCEL_WG) void k_accel_a(const AccelParams p) {
@@ -934,6 +943,30 @@ void launch_weights_normalize(const NormalizeParams& p, stream_t s) {
   if (nblocks < 1 || nblocks > 0x7fffffffL) throw std::invalid_argument("mvn: grid size out of range");
   ++g_normalize_launches;
   hipLaunchKernelGGL(k_weights_normalize, dim3((unsigned)nblocks), dim3(MVN_INGEST_WG), 0, hs(s), p);
+  HIP_CHECK(hipGetLastError());
+}
+
+static std::atomic<long long> g_fuse_raw_launches{0}, g_fuse_volumes_launches{0};
+void fuse_counters(long long out[2]) {
+  out[0] = g_fuse_raw_launches.load();
+  out[1] = g_fuse_volumes_launches.load();
+}
+
+void launch_fuse_resampled(const FuseParams& p, stream_t s) {
+  mvn_fuse_check(p);
+  const long nblocks = mvn_fuse_blocks(p);
+  if (nblocks < 1 || nblocks > 0x7fffffffL) throw std::invalid_argument("mvn: grid size out of range");
+  ++g_fuse_raw_launches;
+  hipLaunchKernelGGL(k_fuse_resampled, dim3((unsigned)nblocks), dim3(MVN_RS_WG), 0, hs(s), p);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_fuse_volumes(const FuseVolumesParams& p, stream_t s) {
+  mvn_fuse_volumes_check(p);
+  const long nblocks = mvn_fuse_volumes_blocks(p);
+  if (nblocks < 1 || nblocks > 0x7fffffffL) throw std::invalid_argument("mvn: grid size out of range");
+  ++g_fuse_volumes_launches;
+  hipLaunchKernelGGL(k_fuse_volumes, dim3((unsigned)nblocks), dim3(MVN_INGEST_WG), 0, hs(s), p);
   HIP_CHECK(hipGetLastError());
 }
 

@@ -54,6 +54,8 @@ ENGINE_ABI_SYMBOLS = [
     "mvn_set_image_storage", "mvn_get_image_storage", "mvn_deconvolve_memory_described", "mvn_image_storage_counters",
     "mvn_set_background", "mvn_get_background", "mvn_set_likelihood", "mvn_get_likelihood", "mvn_last_likelihood",
     "mvn_engine_set_noise_model", "mvn_engine_last_likelihood",
+    "mvn_fuse_resampled", "mvn_fuse_memory_resampled", "mvn_fuse_time", "mvn_fuse_counters", "mvn_set_psi_start",
+    "mvn_get_psi_start", "mvn_engine_fuse_psi",
 ]
 
 
@@ -202,6 +204,15 @@ class Binding:
         l.mvn_resample_stack.argtypes = [C.c_int, C.c_void_p, C.POINTER(StackDesc), vg, i3, c_float_p, c_float_p]
         l.mvn_resample_time.argtypes = [C.c_int, C.c_int, vg, i3, C.c_int, C.POINTER(C.c_float)]
         l.mvn_resample_counters.argtypes = [C.POINTER(C.c_longlong)]
+        l.mvn_fuse_resampled.argtypes = [C.c_void_p, C.POINTER(StackDesc), i3, C.c_int, C.POINTER(C.c_void_p),
+                                         C.POINTER(StackDesc), vg, C.c_float, C.c_void_p, C.c_int]
+        l.mvn_fuse_memory_resampled.argtypes = [C.POINTER(StackDesc), i3, C.c_int, C.POINTER(StackDesc), vg, C.c_int,
+                                                C.POINTER(C.c_size_t)]
+        l.mvn_fuse_time.argtypes = [C.c_int, C.c_int, C.c_int, vg, i3, C.c_int, C.POINTER(C.c_float)]
+        l.mvn_fuse_counters.argtypes = [C.POINTER(C.c_longlong)]
+        l.mvn_set_psi_start.argtypes = [C.c_int, C.c_float]
+        l.mvn_get_psi_start.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_float)]
+        l.mvn_engine_fuse_psi.argtypes = [C.c_void_p, C.c_float]
         l.mvn_tv_launch_count.restype = C.c_long
         l.mvn_tv_launch_count.argtypes = []
         l.mvn_engine_compute_delta.argtypes = [C.c_void_p, C.c_double, C.c_float]
@@ -537,6 +548,70 @@ class Binding:
         ms = (C.c_float * 2)(0, 0)
         self.check(self.l.mvn_resample_time(device, int(bool(u16)), C.byref(geom), _dims(out_shape), int(reps), ms))
         return float(ms[0]), float(ms[1])
+
+    # ---- fusion (mvn_fuse_resampled) -------------------------------------------------------
+    def fuse_counters(self):
+        """mvn_fuse_counters: (launches of the fusion from raw stacks, launches of the fusion of an engine's volumes)
+        since process start."""
+        out = (C.c_longlong * 2)(0, 0)
+        self.check(self.l.mvn_fuse_counters(out))
+        return int(out[0]), int(out[1])
+
+    def _fuse_args(self, out, raws, geoms, int16_is_uint16):
+        n = len(raws)
+        if len(geoms) != n:
+            raise ValueError("one geometry per raw stack")
+        o_ptr, o_desc, shape, o_dev = describe_stack(out, int16_is_uint16)
+        descs, garr, ptrs = (StackDesc * max(n, 1))(), (ViewGeometry * max(n, 1))(), (C.c_void_p * max(n, 1))()
+        devices = [o_dev]
+        for v in range(n):
+            ptr, descs[v], r_shape, r_dev = describe_stack(raws[v], int16_is_uint16)
+            if r_shape != tuple(geoms[v].src_dims):
+                raise ValueError("view %d: the raw stack has shape %r, its geometry says %r"
+                                 % (v, r_shape, tuple(geoms[v].src_dims)))
+            ptrs[v], garr[v] = ptr, geoms[v]
+            devices.append(r_dev)
+        owners = [x for x in devices if x is not None]
+        return o_ptr, o_desc, shape, n, ptrs, descs, garr, (owners[0] if owners else None)
+
+    def fuse_resampled(self, out, raws, geoms, fill=0.0, device=None, int16_is_uint16=False):
+        """mvn_fuse_resampled: the weighted average of the RAW views `raws` (numpy arrays or torch tensors, float32 or
+        uint16, host or device, as deconvolve_resampled takes them) through `geoms` (abi.view_geometry), with Fiji's
+        cosine blend weights, written into `out` (float32 or uint16, numpy array or torch tensor of the block's shape,
+        any window of a larger array with positive strides; host memory needs contiguous rows); `fill` where no view
+        contributes.  Returns `out`."""
+        o_ptr, o_desc, shape, n, ptrs, descs, garr, owner = self._fuse_args(out, raws, geoms, int16_is_uint16)
+        stream = _caller_stream([out] + list(raws))
+        dev = device if device is not None else (owner if owner is not None else 0)
+        self.check(self.l.mvn_fuse_resampled(C.c_void_p(o_ptr), C.byref(o_desc), _dims(shape), n, ptrs, descs, garr,
+                                             float(fill), C.c_void_p(stream), int(dev)))
+        return out
+
+    def fuse_memory(self, out, raws, geoms, device=0, int16_is_uint16=False):
+        """mvn_fuse_memory_resampled: the bytes fuse_resampled would allocate on the device for these objects."""
+        o_ptr, o_desc, shape, n, ptrs, descs, garr, owner = self._fuse_args(out, raws, geoms, int16_is_uint16)
+        need = C.c_size_t(0)
+        self.check(self.l.mvn_fuse_memory_resampled(C.byref(o_desc), _dims(shape), n, descs, garr, int(device),
+                                                    C.byref(need)))
+        return need.value
+
+    def fuse_time(self, geoms, out_shape, u16=True, reps=10, device=0):
+        """mvn_fuse_time: (ms per fusion from len(geoms) resident raw stacks into a resident float32 volume of
+        `out_shape`, ms for one resample pass per view on the same stacks, ms per plain copy of one volume)."""
+        garr = (ViewGeometry * len(geoms))(*geoms)
+        ms = (C.c_float * 3)(0, 0, 0)
+        self.check(self.l.mvn_fuse_time(device, int(bool(u16)), len(geoms), garr, _dims(out_shape), int(reps), ms))
+        return float(ms[0]), float(ms[1]), float(ms[2])
+
+    def set_psi_start(self, mode, fill=0.0):
+        """Process-wide start of mvn_deconvolve_resampled: 0 the caller's psi (default), 1 the fusion of the views,
+        `fill` where no view contributes (mvn_engine_api.h)."""
+        self.check(self.l.mvn_set_psi_start(int(mode), float(fill)))
+
+    def get_psi_start(self):
+        mode, fill = C.c_int(0), C.c_float(0)
+        self.check(self.l.mvn_get_psi_start(C.byref(mode), C.byref(fill)))
+        return mode.value, fill.value
 
     def resample_call(self, psi, raws, geoms, kernels1, kernels2, lambda_, min_value, iterations, weights=None,
                       int16_is_uint16=False):
@@ -876,6 +951,11 @@ class EngineHandle:
 
     def normalize_weights(self):
         self.b.check(self.b.l.mvn_engine_normalize_weights(self.h))
+
+    def fuse_psi(self, fill=0.0):
+        """mvn_engine_fuse_psi: psi <- the fusion of the views as they stand (image and weights volumes), `fill` where
+        no weight is positive."""
+        self.b.check(self.b.l.mvn_engine_fuse_psi(self.h, float(fill)))
 
     def set_psi(self, psi):
         psi = self._stack(psi)
