@@ -140,7 +140,8 @@ MVN_API int mvn_deconvolve_memory_described(struct workspace input, const mvn_ca
  * plus the bytes of the largest raw stack in host memory (the temporary upload); it allocates nothing.
  * Out of scope: interpolation other than trilinear; mvn_deconvolve_submit; streamed views; mvn_group_* / mvn_slab_* /
  * halo mode (mvn_engine_set_view_resampled on an engine with a halo hook is an error); a mix of resampled and plain
- * views in one call; filling the padded margins with real raw data from beyond the block. */
+ * views in one call; filling the padded margins with real raw data from beyond the block.  Kernels arrive transformed
+ * into the block's frame unless mvn_set_kernel_derivation (below) says that they are raw PSFs. */
 typedef struct mvn_view_geometry {
   int src_dims[3];       /* extents m0, m1, m2 of the raw stack image_ points to */
   double matrix[12];     /* row-major 3 x 4: raw index c = M * (z, y, x, 1) of block voxel (z, y, x) */
@@ -221,6 +222,83 @@ MVN_API int mvn_fuse_counters(long long out[2]);
  * A mode other than 0 or 1, or a non-finite fill, is an error. */
 MVN_API int mvn_set_psi_start(int mode, float fill);
 MVN_API int mvn_get_psi_start(int* mode, float* fill);
+/* ---- derived kernels: kernel1 and kernel2 of every view from its raw PSF and its matrix ------------------------------
+ * What a caller has is the PSF extracted from beads in the raw view's own voxel grid, and the matrix it hands in anyway.
+ * mvn_derive_kernels makes of them, on the device, what a deconvolution takes: kernel1_v, the PSF transformed into the
+ * block's frame and normalised, and kernel2_v, the compound kernel of the iteration scheme of Preibisch et al. 2014
+ * ("Independent", "Efficient Bayesian", "Optimization I", "Optimization II" in Multiview Reconstruction).
+ *
+ * Inputs per view v of V: a raw PSF p_v, dense float32 in HOST memory, of ODD extents r_v, centre cr = (r - 1) / 2; and
+ * optionally the view's mvn_view_geometry, of which only the linear part A (matrix[4k + 0..2]) is read - the fourth
+ * column, src_dims and the blend fields are ignored.  geom == NULL: the PSFs are in the block's frame already.
+ *
+ * Extents.  All derived kernels of a call share one odd extent triple K, h = (K - 1) / 2.  The caller may give K
+ * (out_dims: odd, every entry in 1..257).  out_dims == NULL: K = mvn_psf_extents':
+ *   with a geometry, per view B = A^-1 in double as adjugate over determinant (a zero or non-finite determinant is an
+ *   error), s_k = (|B[k][0]| cr_0 + |B[k][1]| cr_1) + |B[k][2]| cr_2, h_k(v) = ceil(s_k - 1e-6), K_k = 2 max_v h_k(v) + 1
+ *   (a K_k above 257 is an error); without one, K_k = max_v r_v[k].
+ * Step 1, transform.  q_v is what mvn_resample_stack returns as image for the raw stack p_v (float32) with src_dims =
+ *   r_v, matrix [A | t], border and range 0 and out_dims = K, where t_k = cr_k - ((A[k][0] h_0 + A[k][1] h_1) +
+ *   A[k][2] h_2), formed in double on the host, every operation rounded once: the coordinate, inside, floor and lerp
+ *   rules of mvn_view_geometry apply unchanged, voxels outside the raw PSF are 0.  Without a geometry q_v is p_v copied
+ *   centred into K (an axis with K_k < r_v[k] keeps the central K_k elements).
+ * Step 2, normalise.  S = sum q_v in double, in any order; kernel1_v[i] = (float)((double)q_v[i] / S).  S <= 0 or
+ *   non-finite is an error ("a kernel without mass").
+ * Step 3, kernel2.  Index kernels by the offset d from the centre, P_v = kernel1_v; a value outside an array's extents
+ *   is 0; flip(P)(d) = P(-d).  The correlation primitive is
+ *     corr(a, b)(d) = sum over t of (double)a(-t) * (double)b(d - t)
+ *   with t over a's offsets in raster order (t_0 outermost, ascending), terms whose d - t lies outside b skipped, the sum
+ *   started from +0.0 and held in double (the product of two widened floats is exact in double: contraction into a fused
+ *   multiply-add cannot change a bit), the result rounded to float32 once.
+ *     MVN_PSF_INDEPENDENT         kernel2_v = flip(P_v), bit for bit, no second normalisation - for every V
+ *     MVN_PSF_EFFICIENT_BAYESIAN  A_w = corr(flip(P_w), flip(P_w)) on extents 2K - 1, held as float32 (the full
+ *                                 autocorrelation of P_w; once per view); C_vw = corr(P_v, A_w) on extents K;
+ *                                 T = flip(P_v); for w != v in view order T = T * C_vw (float32, rounded once);
+ *                                 kernel2_v = T normalised as in step 2
+ *     MVN_PSF_OPTIMIZATION_I      the same with C_vw = corr(P_v, P_w) on extents K; no autocorrelation
+ *     MVN_PSF_OPTIMIZATION_II     T = flip(P_v) multiplied by flip(P_v) another V - 1 times (float32, no powf), normalised
+ *   With V == 1 the product of the last three types is empty: kernel2 is flip(P_0) normalised once more.
+ *
+ * mvn_psf_extents: K by the rule above (raw_dims: 3 ints per view).  mvn_derive_kernels: kernel1[v] and kernel2[v] are
+ * dense float32 HOST arrays of extents K (out_dims, or NULL = mvn_psf_extents'); either table may be NULL.  The call
+ * blocks, checks everything before it touches anything, and writes the outputs last: errors (< 0, message in
+ * mvn_last_error(), outputs untouched) are even or < 1 raw extents, a non-finite PSF value, a singular or non-finite
+ * linear part, an unknown type, bad out_dims, num_views < 1, a null pointer, and a kernel without mass.
+ * Device memory while it runs, all freed before it returns: the raw PSFs, one padded volume of extents K (rows of
+ * K_2 + 1), 2 V prod K floats (kernel1, kernel2), V (V - 1) prod K floats (the C_vw, types 1 and 2 only) and
+ * V prod (2K - 1) floats (the A_w, type 1 only), plus 64 bytes per correlation and 2048 + 8 bytes per kernel for the sums.
+ * The correlations cost prod K multiply-adds per output voxel and are done one output voxel per work item: meant for
+ * PSFs of tens of voxels per axis.
+ *
+ * mvn_set_kernel_derivation (process-wide; captured at the start of mvn_deconvolve_resampled, and read by
+ * mvn_deconvolve_memory_resampled; no other entry point honours it): mode 0 (default) - kernels are handed in, launches
+ * and bits as without this switch; mode 1 - kernel1_ / kernel1_dims_ of each view are the RAW PSF and its extents,
+ * kernel2_ / kernel2_dims_ are ignored and may be NULL, and the call derives both kernels of `type` with geom's linear
+ * parts and K = mvn_psf_extents' on its device before it looks up an engine, then continues exactly as if the derived
+ * arrays of extents K had been handed in: padding extents, the dim0 form rule, the PSF cache, the uploader thread.
+ * mvn_deconvolve_memory_resampled then prices the call with K (it reads dims and matrices only).  The derivation's errors
+ * are the call's: psi stays untouched.  A mode other than 0 or 1, or an unknown type, is an error.
+ * The derivation cache: process-wide, ONE entry - the last derivation, whichever of the two routes made it.  Its key is
+ * the type, V, K, every raw PSF's extents and bytes and every linear part; a hit launches nothing, and the PSF cache
+ * then sees identical kernel bytes and re-uses the spectra: the block-after-block case, where only the matrices' fourth
+ * columns change.
+ * mvn_derive_counters: out[0] = launches of the correlation kernel, out[1] = derivations computed, out[2] = derivations
+ * re-used from the cache, since process start.
+ * mvn_derive_time (test and bench utility): ms[0] = milliseconds per derivation of `type` for num_views resident PSFs
+ * of extents dims (odd; no geometry, K = dims) holding random positive values - all its device work, `reps` derivations
+ * between two stream events behind one that warms up; ms[1] = the same for its correlation launches alone (0 for the
+ * types that have none).  It bypasses the derivation cache and moves out[0] only.
+ * Out of scope: extracting PSFs from beads; the engine API (mvn_engine_set_view_resampled keeps taking kernels: call
+ * mvn_derive_kernels first); every entry point other than the two resampled ones; raw PSFs in device memory. */
+enum { MVN_PSF_INDEPENDENT = 0, MVN_PSF_EFFICIENT_BAYESIAN = 1, MVN_PSF_OPTIMIZATION_I = 2, MVN_PSF_OPTIMIZATION_II = 3 };
+MVN_API int mvn_psf_extents(int num_views, const int* raw_dims, const mvn_view_geometry* geom, int out_dims[3]);
+MVN_API int mvn_derive_kernels(int device, int num_views, const float* const* raw_psf, const int* raw_dims,
+                               const mvn_view_geometry* geom, int type, const int out_dims[3],
+                               float* const* kernel1, float* const* kernel2);
+MVN_API int mvn_set_kernel_derivation(int mode, int type);
+MVN_API int mvn_get_kernel_derivation(int* mode, int* type);
+MVN_API int mvn_derive_counters(long long out[3]);
+MVN_API int mvn_derive_time(int device, int num_views, const int dims[3], int type, int reps, float* ms);
 /* out[0] = divide passes launched on a uint16 image, out[1] = ingest passes that wrote a uint16 volume, since process start */
 MVN_API int mvn_image_storage_counters(long long out[2]);
 /* Padding policy of inplace_gpu_deconvolve for the calls that follow (process-wide): "zero"

@@ -473,6 +473,363 @@ static void natural_to_position(const Plan3D& plan, const cfloat* in, std::vecto
       [&](size_t row, size_t nat) { nyq_h[row] = in[nat]; });
 }
 
+// ---- derived kernels (mvn_psf.hpp; the arithmetic is stated at mvn_derive_kernels in include/mvn_engine_api.h) --------
+namespace {
+
+// B = A^-1 of the linear part of a row-major 3 x 4 matrix, in double, as adjugate over determinant
+void psf_inverse(const double* M, const std::string& what, double B[9]) {
+  double a[3][3];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      a[i][j] = M[4 * i + j];
+      if (!std::isfinite(a[i][j])) throw std::invalid_argument(what + ": non-finite linear part");
+    }
+  double adj[3][3];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      const int r0 = (j + 1) % 3, r1 = (j + 2) % 3, c0 = (i + 1) % 3, c1 = (i + 2) % 3;
+      adj[i][j] = a[r0][c0] * a[r1][c1] - a[r0][c1] * a[r1][c0];  // cofactor (j, i): cyclic indices carry the sign
+    }
+  const double det = a[0][0] * adj[0][0] + a[0][1] * adj[1][0] + a[0][2] * adj[2][0];
+  if (!std::isfinite(det) || det == 0.) throw std::invalid_argument(what + ": singular linear part");
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      B[3 * i + j] = adj[i][j] / det;
+      if (!std::isfinite(B[3 * i + j])) throw std::invalid_argument(what + ": singular linear part");
+    }
+}
+
+void psf_check_raw_dims(int V, const int* raw_dims) {
+  if (V < 1) throw std::invalid_argument("num_views must be >= 1");
+  if (!raw_dims) throw std::invalid_argument("null raw_dims");
+  for (int i = 0; i < 3 * V; ++i)
+    if (raw_dims[i] < 1 || !(raw_dims[i] & 1))
+      throw std::invalid_argument("raw PSF " + std::to_string(i / 3) + ": extents must be odd and >= 1");
+}
+
+// K of mvn_psf_extents
+void psf_extents(int V, const int* raw_dims, const mvn_view_geometry* geom, int K[3]) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  psf_check_raw_dims(V, raw_dims);
+  int best[3] = {0, 0, 0};
+  for (int v = 0; v < V; ++v) {
+    const int* r = raw_dims + 3 * v;
+    if (!geom) {
+      for (int k = 0; k < 3; ++k) best[k] = std::max(best[k], r[k]);
+      continue;
+    }
+    double B[9];
+    psf_inverse(geom[v].matrix, "geom " + std::to_string(v), B);
+    const double cr[3] = {(double)((r[0] - 1) / 2), (double)((r[1] - 1) / 2), (double)((r[2] - 1) / 2)};
+    for (int k = 0; k < 3; ++k) {
+      const double p0 = std::fabs(B[3 * k]) * cr[0], p1 = std::fabs(B[3 * k + 1]) * cr[1], p2 = std::fabs(B[3 * k + 2]) * cr[2];
+      const double s01 = p0 + p1;
+      const double s = s01 + p2;
+      const double h = std::ceil(s - 1e-6);
+      if (!(h <= (double)(MVN_PSF_MAX / 2)))
+        throw std::invalid_argument("the transformed PSF of view " + std::to_string(v) + " exceeds " +
+                                    std::to_string(MVN_PSF_MAX) + " voxels along an axis");
+      best[k] = std::max(best[k], 2 * (int)(h > 0. ? h : 0.) + 1);
+    }
+  }
+  for (int k = 0; k < 3; ++k) {
+    if (best[k] > MVN_PSF_MAX)
+      throw std::invalid_argument("kernel extents above " + std::to_string(MVN_PSF_MAX));
+    K[k] = best[k];
+  }
+}
+
+// a derivation, everything checked that the host can check
+struct PsfRequest {
+  int V = 0, type = 0;
+  int K[3] = {1, 1, 1};
+  bool has_geom = false;
+  std::vector<int> r;             // 3 per view
+  std::vector<double> M;          // 12 per view: [A | t] (has_geom)
+  std::vector<const float*> raw;  // host memory
+  size_t n() const { return (size_t)K[0] * (size_t)K[1] * (size_t)K[2]; }
+  size_t nA() const { return (size_t)(2 * K[0] - 1) * (size_t)(2 * K[1] - 1) * (size_t)(2 * K[2] - 1); }
+  bool correlates() const { return V > 1 && (type == PSF_EFFICIENT_BAYESIAN || type == PSF_OPTIMIZATION_I); }
+};
+
+void psf_check_type(int type) {
+  if (type < PSF_INDEPENDENT || type > PSF_OPTIMIZATION_II)
+    throw std::invalid_argument("kernel type must be 0 (independent), 1 (efficient Bayesian), 2 (optimization I) or "
+                                "3 (optimization II)");
+}
+
+PsfRequest psf_request(int V, const float* const* raw_psf, const int* raw_dims, const mvn_view_geometry* geom, int type,
+                       const int* out_dims) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  PsfRequest q;
+  psf_check_raw_dims(V, raw_dims);
+  psf_check_type(type);
+  if (!raw_psf) throw std::invalid_argument("null raw_psf");
+  q.V = V, q.type = type, q.has_geom = geom != nullptr;
+  q.r.assign(raw_dims, raw_dims + 3 * V);
+  if (out_dims) {
+    for (int k = 0; k < 3; ++k) {
+      if (out_dims[k] < 1 || out_dims[k] > MVN_PSF_MAX || !(out_dims[k] & 1))
+        throw std::invalid_argument("out_dims must be odd and between 1 and " + std::to_string(MVN_PSF_MAX));
+      q.K[k] = out_dims[k];
+    }
+    if (geom)
+      for (int v = 0; v < V; ++v) {
+        double B[9];
+        psf_inverse(geom[v].matrix, "geom " + std::to_string(v), B);
+      }
+  } else {
+    psf_extents(V, raw_dims, geom, q.K);
+  }
+  for (int v = 0; v < V; ++v) {
+    const float* p = raw_psf[v];
+    if (!p) throw std::invalid_argument("raw PSF " + std::to_string(v) + ": null pointer");
+    const int* r = raw_dims + 3 * v;
+    const size_t count = (size_t)r[0] * (size_t)r[1] * (size_t)r[2];
+    for (size_t i = 0; i < count; ++i)
+      if (!std::isfinite(p[i])) throw std::invalid_argument("raw PSF " + std::to_string(v) + ": non-finite value");
+    q.raw.push_back(p);
+    if (!geom) continue;
+    // t_k = cr_k - ((A[k][0] h_0 + A[k][1] h_1) + A[k][2] h_2): the centre of K lands on the centre of the raw PSF
+    const double* A = geom[v].matrix;
+    for (int k = 0; k < 3; ++k) {
+      const double h0 = (double)((q.K[0] - 1) / 2), h1 = (double)((q.K[1] - 1) / 2), h2 = (double)((q.K[2] - 1) / 2);
+      const double a = A[4 * k] * h0;
+      const double b = A[4 * k + 1] * h1;
+      const double ab = a + b;
+      const double c = A[4 * k + 2] * h2;
+      const double abc = ab + c;
+      const double t = (double)((r[k] - 1) / 2) - abc;
+      for (int j = 0; j < 3; ++j) q.M.push_back(A[4 * k + j]);
+      q.M.push_back(t);
+    }
+  }
+  return q;
+}
+
+// the device side of one derivation: buffers, job tables, and the launches in stream order
+class PsfDerivation {
+ public:
+  PsfDerivation(const PsfRequest& q, be::stream_t s) : q_(q), L_(q.K[0], q.K[1], q.K[2]), n_(q.n()), nA_(q.nA()) {
+    const size_t V = (size_t)q.V;
+    size_t raw_floats = 0;
+    for (size_t v = 0; v < V; ++v) {
+      raw_off_.push_back(raw_floats);
+      raw_floats += (size_t)q.r[3 * v] * (size_t)q.r[3 * v + 1] * (size_t)q.r[3 * v + 2];
+    }
+    raw_ = be::DeviceBuffer<float>(raw_floats * sizeof(float));
+    if (q.has_geom) rs_ = be::DeviceBuffer<float>(L_.real_floats() * sizeof(float));
+    k1_ = be::DeviceBuffer<float>(V * n_ * sizeof(float));
+    k2_ = be::DeviceBuffer<float>(V * n_ * sizeof(float));
+    partial_ = be::DeviceBuffer<double>(V * MVN_PSF_WG * sizeof(double));
+    sums_ = be::DeviceBuffer<double>(2 * V * sizeof(double));
+    for (size_t v = 0; v < V; ++v)
+      be::h2d(raw_.get() + raw_off_[v], q.raw[v],
+              (size_t)q.r[3 * v] * (size_t)q.r[3 * v + 1] * (size_t)q.r[3 * v + 2] * sizeof(float), s);
+    if (!q.correlates()) return;
+    const int* K = q.K;
+    const int K2[3] = {2 * K[0] - 1, 2 * K[1] - 1, 2 * K[2] - 1};
+    c_ = be::DeviceBuffer<float>(V * (V - 1) * n_ * sizeof(float));
+    std::vector<PsfJob> ja, jc;
+    if (q.type == PSF_EFFICIENT_BAYESIAN) {
+      a_ = be::DeviceBuffer<float>(V * nA_ * sizeof(float));
+      for (size_t w = 0; w < V; ++w)  // A_w = corr(flip(P_w), flip(P_w)): k2_ holds the flipped kernels then
+        ja.push_back(job(k2_.get() + w * n_, K, k2_.get() + w * n_, K, a_.get() + w * nA_, K2));
+    }
+    for (size_t v = 0; v < V; ++v)
+      for (size_t w = 0; w < V; ++w) {
+        if (w == v) continue;
+        float* out = c_.get() + (v * (V - 1) + (w < v ? w : w - 1)) * n_;
+        if (q.type == PSF_EFFICIENT_BAYESIAN)
+          jc.push_back(job(k1_.get() + v * n_, K, a_.get() + w * nA_, K2, out, K));
+        else
+          jc.push_back(job(k1_.get() + v * n_, K, k1_.get() + w * n_, K, out, K));
+      }
+    jobs_ = be::DeviceBuffer<PsfJob>((ja.size() + jc.size()) * sizeof(PsfJob));
+    if (!ja.empty()) be::h2d(jobs_.get(), ja.data(), ja.size() * sizeof(PsfJob), s);
+    be::h2d(jobs_.get() + ja.size(), jc.data(), jc.size() * sizeof(PsfJob), s);
+    be::stream_sync(s);  // (the tables are locals)
+    n_ja_ = (int)ja.size(), n_jc_ = (int)jc.size();
+  }
+
+  // the correlation launches alone (the buffers hold what the passes before them left)
+  void correlations(be::stream_t s) const {
+    if (!q_.correlates()) return;
+    PsfCorrParams p;
+    if (n_ja_) {
+      p.jobs = jobs_.get(), p.njobs = n_ja_, p.blocks_per_job = (int)mvn_psf_blocks((long)nA_);
+      be::launch_psf_correlate(p, s);
+    }
+    p.jobs = jobs_.get() + n_ja_, p.njobs = n_jc_, p.blocks_per_job = (int)mvn_psf_blocks((long)n_);
+    be::launch_psf_correlate(p, s);
+  }
+
+  // every launch of the derivation
+  void enqueue(be::stream_t s) const {
+    const int V = q_.V;
+    const int* K = q_.K;
+    const long krow = K[2], kplane = (long)K[1] * K[2];
+    if (!q_.has_geom) be::dzero(k1_.get(), (size_t)V * n_ * sizeof(float), s);
+    for (int v = 0; v < V; ++v) {
+      const int* r = &q_.r[3 * (size_t)v];
+      const float* raw = raw_.get() + raw_off_[(size_t)v];
+      float* dst = k1_.get() + (size_t)v * n_;
+      if (q_.has_geom) {  // step 1: the resample pass on a volume of extents K, then its rows without their padding
+        ResampleParams p;
+        std::memset(&p, 0, sizeof(p));
+        p.image = rs_.get(), p.weights = nullptr, p.RP = L_.RP, p.D0 = L_.d0, p.D1 = L_.d1;
+        p.n0 = L_.d0, p.n1 = L_.d1, p.n2 = L_.d2;
+        p.src = raw, p.s0 = (long long)r[1] * r[2], p.s1 = r[2], p.s2 = 1;
+        for (int k = 0; k < 3; ++k) p.g.m[k] = r[k];
+        for (int i = 0; i < 12; ++i) p.g.M[i] = q_.M[12 * (size_t)v + (size_t)i];
+        be::launch_resample(p, false, s);
+        be::launch_copy3d(dst, krow, kplane, rs_.get(), L_.RP, (long)L_.d1 * L_.RP, K[2], K[1], K[0], s);
+      } else {  // the centred copy: per axis the whole raw PSF, or its central K elements
+        int len[3];
+        long so = 0, d_o = 0;
+        const long sst[3] = {(long)r[1] * r[2], r[2], 1}, dst_st[3] = {kplane, krow, 1};
+        for (int k = 0; k < 3; ++k) {
+          const int cr = (r[k] - 1) / 2, h = (K[k] - 1) / 2;
+          len[k] = std::min(r[k], K[k]);
+          if (K[k] >= r[k])
+            d_o += (long)(h - cr) * dst_st[k];
+          else
+            so += (long)(cr - h) * sst[k];
+        }
+        be::launch_copy3d(dst + d_o, krow, kplane, raw + so, sst[1], sst[0], len[2], len[1], len[0], s);
+      }
+    }
+    PsfNormParams nm;  // step 2
+    nm.src = k1_.get(), nm.dst = k1_.get(), nm.partial = partial_.get(), nm.sums = sums_.get(), nm.n = (long)n_, nm.count = V;
+    be::launch_psf_normalize(nm, s);
+    PsfPointParams pt;  // step 3
+    pt.P = k1_.get(), pt.C = c_.get(), pt.T = k2_.get(), pt.n = (long)n_, pt.V = V, pt.type = PSF_INDEPENDENT;
+    if (q_.correlates()) {
+      if (q_.type == PSF_EFFICIENT_BAYESIAN) be::launch_psf_pointwise(pt, s);  // the flipped kernels the A_w are made of
+      correlations(s);
+    }
+    pt.type = q_.type;
+    be::launch_psf_pointwise(pt, s);
+    if (q_.type == PSF_INDEPENDENT) return;
+    nm.src = k2_.get(), nm.dst = k2_.get(), nm.sums = sums_.get() + V;
+    be::launch_psf_normalize(nm, s);
+  }
+
+  // the sums checked, then the kernels into host memory (either may be null); blocks
+  void download(std::vector<std::vector<float>>* k1, std::vector<std::vector<float>>* k2, be::stream_t s) const {
+    const size_t V = (size_t)q_.V;
+    std::vector<double> sums(2 * V, 1.0);
+    be::d2h(sums.data(), sums_.get(), (q_.type == PSF_INDEPENDENT ? V : 2 * V) * sizeof(double), s);
+    be::stream_sync(s);
+    for (size_t i = 0; i < 2 * V; ++i)
+      if (!std::isfinite(sums[i]) || !(sums[i] > 0.))
+        throw std::invalid_argument(std::string("a kernel without mass: ") + (i < V ? "kernel1" : "kernel2") +
+                                    " of view " + std::to_string(i % V) + " sums to " + std::to_string(sums[i]));
+    for (size_t v = 0; v < V; ++v) {
+      if (k1) be::d2h((*k1)[v].data(), k1_.get() + v * n_, n_ * sizeof(float), s);
+      if (k2) be::d2h((*k2)[v].data(), k2_.get() + v * n_, n_ * sizeof(float), s);
+    }
+    be::stream_sync(s);
+  }
+
+ private:
+  static PsfJob job(const float* a, const int* ea, const float* b, const int* eb, float* out, const int* eo) {
+    PsfJob j;
+    std::memset(&j, 0, sizeof(j));
+    j.a = a, j.b = b, j.out = out;
+    for (int k = 0; k < 3; ++k) j.ea[k] = ea[k], j.eb[k] = eb[k], j.eo[k] = eo[k];
+    mvn_psf_job_check(j);
+    return j;
+  }
+
+  const PsfRequest& q_;
+  const Layout L_;
+  const size_t n_, nA_;
+  std::vector<size_t> raw_off_;
+  be::DeviceBuffer<float> raw_, rs_, k1_, k2_, c_, a_;
+  be::DeviceBuffer<double> partial_, sums_;
+  be::DeviceBuffer<PsfJob> jobs_;
+  int n_ja_ = 0, n_jc_ = 0;
+};
+
+// what a derivation leaves: the kernels of every view, in host memory
+struct PsfKernels {
+  int K[3];
+  std::vector<std::vector<float>> k1, k2;
+};
+
+// the derivation cache: ONE entry, the last derivation of the process
+struct PsfCacheEntry {
+  int type = -1, V = 0;
+  bool has_geom = false;
+  std::vector<int> r;
+  std::vector<double> A;  // 9 per view
+  std::vector<std::vector<float>> raw;
+  std::shared_ptr<const PsfKernels> out;
+};
+std::mutex g_psf_cache_mu;
+PsfCacheEntry g_psf_cache;
+std::atomic<long long> g_psf_computed{0}, g_psf_reused{0};
+
+std::vector<double> psf_linear_parts(const PsfRequest& q) {
+  std::vector<double> A;
+  for (size_t v = 0; q.has_geom && v < (size_t)q.V; ++v)
+    for (int k = 0; k < 3; ++k)
+      for (int j = 0; j < 3; ++j) A.push_back(q.M[12 * v + 4 * (size_t)k + (size_t)j]);
+  return A;
+}
+
+bool psf_cache_hit(const PsfCacheEntry& e, const PsfRequest& q, const std::vector<double>& A) {
+  if (!e.out || e.type != q.type || e.V != q.V || e.has_geom != q.has_geom || e.r != q.r) return false;
+  if (std::memcmp(e.out->K, q.K, sizeof(q.K)) != 0) return false;
+  if (A.size() != e.A.size() || (!A.empty() && std::memcmp(A.data(), e.A.data(), A.size() * sizeof(double)) != 0)) return false;
+  for (size_t v = 0; v < (size_t)q.V; ++v)
+    if (std::memcmp(e.raw[v].data(), q.raw[v], e.raw[v].size() * sizeof(float)) != 0) return false;
+  return true;
+}
+
+// the kernels of a request: from the cache, or derived on `dev` (>= 0) and left there
+std::shared_ptr<const PsfKernels> psf_derive(const PsfRequest& q, int dev) {
+  std::lock_guard<std::mutex> cache_lk(g_psf_cache_mu);
+  const std::vector<double> A = psf_linear_parts(q);
+  if (psf_cache_hit(g_psf_cache, q, A)) {
+    ++g_psf_reused;
+    return g_psf_cache.out;
+  }
+  auto out = std::make_shared<PsfKernels>();
+  std::memcpy(out->K, q.K, sizeof(q.K));
+  out->k1.assign((size_t)q.V, std::vector<float>(q.n()));
+  out->k2.assign((size_t)q.V, std::vector<float>(q.n()));
+  {
+    std::lock_guard<std::mutex> lk(device_mutex(dev));
+    be::set_device(dev);
+    const be::Stream stream = be::Stream::create();
+    const PsfDerivation d(q, stream.get());
+    d.enqueue(stream.get());
+    d.download(&out->k1, &out->k2, stream.get());
+  }
+  ++g_psf_computed;
+  PsfCacheEntry e;
+  e.type = q.type, e.V = q.V, e.has_geom = q.has_geom, e.r = q.r, e.A = A;
+  for (size_t v = 0; v < (size_t)q.V; ++v) {
+    const size_t count = (size_t)q.r[3 * v] * (size_t)q.r[3 * v + 1] * (size_t)q.r[3 * v + 2];
+    e.raw.emplace_back(q.raw[v], q.raw[v] + count);
+  }
+  e.out = out;
+  g_psf_cache = std::move(e);
+  return out;
+}
+
+// mvn_set_kernel_derivation
+std::mutex g_derivation_mu;
+int g_derivation_mode = 0, g_derivation_type = 0;
+
+}  // namespace
+
 extern "C" {
 
 const char* mvn_last_error(void) { return g_last_error.c_str(); }
@@ -994,6 +1351,23 @@ static std::vector<view_data> resampled_views(const workspace& input, int weight
   return views;
 }
 
+// mvn_set_kernel_derivation as a resampled call captures it
+static void captured_derivation(int* mode, int* type) {
+  std::lock_guard<std::mutex> lk(g_derivation_mu);
+  *mode = g_derivation_mode, *type = g_derivation_type;
+}
+
+// Derivation mode 1: kernel1_ / kernel1_dims_ of the views are raw PSFs.  Their extents into `raw_dims`, and the members
+// the mode ignores (kernel2_, kernel2_dims_) made whatever check_workspace wants to see.
+static void raw_psf_views(std::vector<view_data>& views, std::vector<int>* raw_dims) {
+  for (size_t v = 0; v < views.size(); ++v) {
+    view_data& d = views[v];
+    if (!d.kernel1_ || !d.kernel1_dims_) throw std::invalid_argument("view " + std::to_string(v) + " has null members");
+    raw_dims->insert(raw_dims->end(), d.kernel1_dims_, d.kernel1_dims_ + 3);
+    d.kernel2_ = d.kernel1_, d.kernel2_dims_ = d.kernel1_dims_;
+  }
+}
+
 int mvn_deconvolve_resampled(void* psi, struct workspace input, const mvn_call_desc* desc, const mvn_view_geometry* geom,
                              int weights_mode, int device) {
   return guarded("mvn_deconvolve_resampled", [&] {
@@ -1002,6 +1376,10 @@ int mvn_deconvolve_resampled(void* psi, struct workspace input, const mvn_call_d
     if (!geom) throw std::invalid_argument("null geom");
     std::vector<view_data> views = resampled_views(input, weights_mode);
     input.data_ = views.data();
+    int derive = 0, derive_type = 0;
+    captured_derivation(&derive, &derive_type);
+    std::vector<int> raw_psf_dims;
+    if (derive) raw_psf_views(views, &raw_psf_dims);
     check_workspace((const imageType*)psi, input);
     const int V = input.num_views_;
     if (V == 0) return;
@@ -1046,6 +1424,23 @@ int mvn_deconvolve_resampled(void* psi, struct workspace input, const mvn_call_d
       throw std::invalid_argument("the stacks live on device " + std::to_string(owner) + ", not on device " +
                                   std::to_string(device));
     if (owner >= 0) device = owner;
+    // Derivation mode 1: both kernels of every view from its raw PSF and its linear part, on the call's device, before
+    // an engine is looked up; from here on the call is the one that brings the derived arrays
+    std::shared_ptr<const PsfKernels> derived;
+    int derived_dims[3];
+    if (derive) {
+      std::vector<const float*> raw_psf;
+      for (const view_data& d : views) raw_psf.push_back(d.kernel1_);
+      const PsfRequest q = psf_request(V, raw_psf.data(), raw_psf_dims.data(), geom, derive_type, nullptr);
+      device = pick_device(device);
+      derived = psf_derive(q, device);
+      std::memcpy(derived_dims, q.K, sizeof(q.K));
+      for (size_t v = 0; v < (size_t)V; ++v) {
+        views[v].kernel1_ = const_cast<float*>(derived->k1[v].data());
+        views[v].kernel2_ = const_cast<float*>(derived->k2[v].data());
+        views[v].kernel1_dims_ = views[v].kernel2_dims_ = derived_dims;
+      }
+    }
     deconvolve_call(input, dc, device, 0, current_pad_mode(), mode, &t_last_conv);
   });
 }
@@ -1452,6 +1847,94 @@ int mvn_get_psi_start(int* mode, float* fill) {
   });
 }
 
+// ---- derived kernels (mvn_psf.hpp) ---------------------------------------------------------------------------------
+int mvn_psf_extents(int num_views, const int* raw_dims, const mvn_view_geometry* geom, int out_dims[3]) {
+  return guarded("mvn_psf_extents", [&] {
+    if (!out_dims) throw std::invalid_argument("null out_dims");
+    int K[3];
+    psf_extents(num_views, raw_dims, geom, K);
+    for (int k = 0; k < 3; ++k) out_dims[k] = K[k];
+  });
+}
+
+int mvn_derive_kernels(int device, int num_views, const float* const* raw_psf, const int* raw_dims,
+                       const mvn_view_geometry* geom, int type, const int out_dims[3], float* const* kernel1,
+                       float* const* kernel2) {
+  return guarded("mvn_derive_kernels", [&] {
+    const PsfRequest q = psf_request(num_views, raw_psf, raw_dims, geom, type, out_dims);
+    for (int v = 0; v < num_views; ++v)
+      if ((kernel1 && !kernel1[v]) || (kernel2 && !kernel2[v]))
+        throw std::invalid_argument("null output for view " + std::to_string(v));
+    const std::shared_ptr<const PsfKernels> k = psf_derive(q, pick_device(device));
+    for (size_t v = 0; v < (size_t)num_views; ++v) {
+      if (kernel1) std::memcpy(kernel1[v], k->k1[v].data(), q.n() * sizeof(float));
+      if (kernel2) std::memcpy(kernel2[v], k->k2[v].data(), q.n() * sizeof(float));
+    }
+  });
+}
+
+int mvn_set_kernel_derivation(int mode, int type) {
+  return guarded("mvn_set_kernel_derivation", [&] {
+    if (mode != 0 && mode != 1)
+      throw std::invalid_argument("kernel derivation mode must be 0 (kernels handed in) or 1 (derived from raw PSFs)");
+    psf_check_type(type);
+    std::lock_guard<std::mutex> lk(g_derivation_mu);
+    g_derivation_mode = mode, g_derivation_type = type;
+  });
+}
+
+int mvn_get_kernel_derivation(int* mode, int* type) {
+  return guarded("mvn_get_kernel_derivation", [&] {
+    if (!mode || !type) throw std::invalid_argument("null argument");
+    std::lock_guard<std::mutex> lk(g_derivation_mu);
+    *mode = g_derivation_mode, *type = g_derivation_type;
+  });
+}
+
+int mvn_derive_counters(long long out[3]) {
+  return guarded("mvn_derive_counters", [&] {
+    if (!out) throw std::invalid_argument("null out");
+    out[0] = be::psf_correlate_launches(), out[1] = g_psf_computed.load(), out[2] = g_psf_reused.load();
+  });
+}
+
+// ms[0]: every launch of a derivation of `type` for num_views resident PSFs of extents dims (no geometry: K = dims), per
+// derivation over `reps` derivations between two stream events behind one that warms up; ms[1]: its correlation launches
+// alone, likewise (0: the type has none)
+int mvn_derive_time(int device, int num_views, const int dims[3], int type, int reps, float* ms) {
+  return guarded("mvn_derive_time", [&] {
+    if (!dims || !ms) throw std::invalid_argument("null argument");
+    if (reps < 1 || num_views < 1) throw std::invalid_argument("reps and num_views must be positive");
+    std::vector<int> r;
+    for (int v = 0; v < num_views; ++v) r.insert(r.end(), dims, dims + 3);
+    psf_check_raw_dims(num_views, r.data());
+    for (int k = 0; k < 3; ++k)
+      if (dims[k] > MVN_PSF_MAX) throw std::invalid_argument("extents above " + std::to_string(MVN_PSF_MAX));
+    const size_t n = (size_t)dims[0] * (size_t)dims[1] * (size_t)dims[2];
+    std::vector<std::vector<float>> host;
+    std::vector<const float*> ptrs;
+    for (int v = 0; v < num_views; ++v) {  // random positives, peaked like a PSF: u^6 of an LCG's values
+      host.push_back(lcg_fill(n));
+      for (float& x : host.back()) {
+        const float u = x + 0.5f + 1.0f / 1024.0f;
+        x = (u * u) * (u * u) * (u * u);
+        x += 1e-3f * (float)v;
+      }
+      ptrs.push_back(host.back().data());
+    }
+    const PsfRequest q = psf_request(num_views, ptrs.data(), r.data(), nullptr, type, nullptr);
+    const int dev = pick_device(device);
+    std::lock_guard<std::mutex> lk(device_mutex(dev));
+    be::set_device(dev);
+    const be::Stream stream = be::Stream::create();
+    const be::stream_t s = stream.get();
+    const PsfDerivation d(q, s);
+    ms[0] = time_on_stream(s, reps, [&] { d.enqueue(s); });
+    ms[1] = q.correlates() ? time_on_stream(s, reps, [&] { d.correlations(s); }) : 0.f;
+    d.download(nullptr, nullptr, s);  // (drains the stream; the sums say that the passes ran on sound values)
+  });
+}
+
 // what a fusion call is made of, everything checked that can be without its pointers (raw == NULL: a memory query)
 extern "C++" {
 namespace {
@@ -1728,6 +2211,17 @@ int mvn_deconvolve_memory_resampled(struct workspace input, const mvn_call_desc*
     if (!geom) throw std::invalid_argument("null geom");
     std::vector<view_data> views = resampled_views(input, weights_mode);
     input.data_ = views.data();
+    int derive = 0, derive_type = 0, derived_dims[3];
+    captured_derivation(&derive, &derive_type);
+    if (derive) {  // the call is priced with the derived kernels' extents: dims and matrices are all that is read
+      std::vector<int> raw_psf_dims;
+      for (size_t v = 0; v < views.size(); ++v) {
+        if (!views[v].kernel1_dims_) throw std::invalid_argument("view " + std::to_string(v) + " has null dims");
+        raw_psf_dims.insert(raw_psf_dims.end(), views[v].kernel1_dims_, views[v].kernel1_dims_ + 3);
+      }
+      psf_extents(input.num_views_, raw_psf_dims.data(), geom, derived_dims);
+      for (view_data& d : views) d.kernel1_dims_ = d.kernel2_dims_ = derived_dims;
+    }
     // (images are float32 volumes: the figure of dense float32 stacks)
     deconvolve_memory(input, nullptr, device, 0, bytes);
     size_t upload = 0;  // one raw stack in host memory at a time

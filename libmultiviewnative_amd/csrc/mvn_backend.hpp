@@ -20,6 +20,7 @@
 #include "mvn_reflect.hpp"
 #include "mvn_resample.hpp"
 #include "mvn_fuse.hpp"
+#include "mvn_psf.hpp"
 
 namespace mvn {
 namespace be {
@@ -166,6 +167,14 @@ void resample_counters(long long out[2]);
 void launch_fuse_resampled(const FuseParams& p, stream_t s);
 void launch_fuse_volumes(const FuseVolumesParams& p, stream_t s);
 void fuse_counters(long long out[2]);
+// a view's kernels from its raw PSF (mvn_psf.hpp): p.count arrays over their sums (both steps), flip and running product
+// of all V views, and ALL the correlations of a stage behind the device table p.jobs (the table is read on the host
+// for its checks by the caller, mvn_psf_job_check, before it is uploaded).  psf_correlate_launches: launches of the
+// last one since process start
+void launch_psf_normalize(const PsfNormParams& p, stream_t s);
+void launch_psf_pointwise(const PsfPointParams& p, stream_t s);
+void launch_psf_correlate(const PsfCorrParams& p, stream_t s);
+long long psf_correlate_launches();
 
 // stand-alone pointwise ops on flat arrays (legacy ABI: compute_quotient / compute_final_values)
 void launch_divide(const float* view, float* inout, size_t n, stream_t s);

@@ -553,6 +553,37 @@ void launch_fuse_volumes(const FuseVolumesParams& p, stream_t) {
     for (int t = 0; t < MVN_INGEST_WG; ++t) mvn_fuse_rows(p, blk, t);
 }
 
+static std::atomic<long long> g_psf_correlate_launches{0};
+long long psf_correlate_launches() { return g_psf_correlate_launches.load(); }
+
+void launch_psf_normalize(const PsfNormParams& p, stream_t) {
+  mvn_psf_norm_check(p);
+#pragma omp parallel for schedule(static)
+  for (long blk = 0; blk < (long)p.count; ++blk)
+    for (int t = 0; t < MVN_PSF_WG; ++t) mvn_psf_sum_item(p, blk, t);
+  const long nblocks = p.count * mvn_psf_blocks(p.n);
+#pragma omp parallel for schedule(static)
+  for (long blk = 0; blk < nblocks; ++blk)
+    for (int t = 0; t < MVN_PSF_WG; ++t) mvn_psf_scale_item(p, blk, t);
+}
+
+void launch_psf_pointwise(const PsfPointParams& p, stream_t) {
+  mvn_psf_point_check(p);
+  const long nblocks = p.V * mvn_psf_blocks(p.n);
+#pragma omp parallel for schedule(static)
+  for (long blk = 0; blk < nblocks; ++blk)
+    for (int t = 0; t < MVN_PSF_WG; ++t) mvn_psf_pointwise_item(p, blk, t);
+}
+
+void launch_psf_correlate(const PsfCorrParams& p, stream_t) {
+  mvn_psf_corr_check(p);
+  ++g_psf_correlate_launches;
+  const long nblocks = (long)p.njobs * p.blocks_per_job;
+#pragma omp parallel for schedule(static)
+  for (long blk = 0; blk < nblocks; ++blk)
+    for (int t = 0; t < MVN_PSF_WG; ++t) mvn_psf_correlate_item(p, blk, t);
+}
+
 static std::atomic<long> g_tv_launches{0};
 long tv_launch_count() { return g_tv_launches.load(); }
 void launch_tv(const TvParams& p0, stream_t) {

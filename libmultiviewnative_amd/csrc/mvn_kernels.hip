@@ -264,6 +264,24 @@ __global__ __launch_bounds__(MVN_INGEST_WG) void k_fuse_volumes(const FuseVolume
   mvn_fuse_rows(p, (long)blockIdx.x, (int)threadIdx.x);
 }
 
+// a view's kernels from its raw PSF (mvn_psf.hpp): normalisation in two steps, flip and running product, and the
+// correlations of a stage, all of its jobs in one launch
+__global__ __launch_bounds__(MVN_PSF_WG) void k_psf_sum(const PsfNormParams p) {
+  mvn_psf_sum_item(p, (long)blockIdx.x, (int)threadIdx.x);
+}
+
+__global__ __launch_bounds__(MVN_PSF_WG) void k_psf_scale(const PsfNormParams p) {
+  mvn_psf_scale_item(p, (long)blockIdx.x, (int)threadIdx.x);
+}
+
+__global__ __launch_bounds__(MVN_PSF_WG) void k_psf_pointwise(const PsfPointParams p) {
+  mvn_psf_pointwise_item(p, (long)blockIdx.x, (int)threadIdx.x);
+}
+
+__global__ __launch_bounds__(MVN_PSF_WG) void k_psf_correlate(const PsfCorrParams p) {
+  mvn_psf_correlate_item(p, (long)blockIdx.x, (int)threadIdx.x);
+}
+
 // vector extrapolation between sweeps (mvn_extrapolate.hpp): two streaming passes and the reduction between them
 template <int W>
 __global__ __launch_bounds__(MVN_ACCEL_WG) void k_accel_a(const AccelParams p) {
@@ -967,6 +985,35 @@ void launch_fuse_volumes(const FuseVolumesParams& p, stream_t s) {
   if (nblocks < 1 || nblocks > 0x7fffffffL) throw std::invalid_argument("mvn: grid size out of range");
   ++g_fuse_volumes_launches;
   hipLaunchKernelGGL(k_fuse_volumes, dim3((unsigned)nblocks), dim3(MVN_INGEST_WG), 0, hs(s), p);
+  HIP_CHECK(hipGetLastError());
+}
+
+static std::atomic<long long> g_psf_correlate_launches{0};
+long long psf_correlate_launches() { return g_psf_correlate_launches.load(); }
+
+static unsigned psf_grid(long nblocks) {
+  if (nblocks < 1 || nblocks > 0x7fffffffL) throw std::invalid_argument("mvn: grid size out of range");
+  return (unsigned)nblocks;
+}
+
+void launch_psf_normalize(const PsfNormParams& p, stream_t s) {
+  mvn_psf_norm_check(p);
+  hipLaunchKernelGGL(k_psf_sum, dim3(psf_grid(p.count)), dim3(MVN_PSF_WG), 0, hs(s), p);
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_psf_scale, dim3(psf_grid(p.count * mvn_psf_blocks(p.n))), dim3(MVN_PSF_WG), 0, hs(s), p);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_psf_pointwise(const PsfPointParams& p, stream_t s) {
+  mvn_psf_point_check(p);
+  hipLaunchKernelGGL(k_psf_pointwise, dim3(psf_grid(p.V * mvn_psf_blocks(p.n))), dim3(MVN_PSF_WG), 0, hs(s), p);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_psf_correlate(const PsfCorrParams& p, stream_t s) {
+  mvn_psf_corr_check(p);
+  ++g_psf_correlate_launches;
+  hipLaunchKernelGGL(k_psf_correlate, dim3(psf_grid((long)p.njobs * p.blocks_per_job)), dim3(MVN_PSF_WG), 0, hs(s), p);
   HIP_CHECK(hipGetLastError());
 }
 

@@ -56,7 +56,10 @@ ENGINE_ABI_SYMBOLS = [
     "mvn_engine_set_noise_model", "mvn_engine_last_likelihood",
     "mvn_fuse_resampled", "mvn_fuse_memory_resampled", "mvn_fuse_time", "mvn_fuse_counters", "mvn_set_psi_start",
     "mvn_get_psi_start", "mvn_engine_fuse_psi",
+    "mvn_psf_extents", "mvn_derive_kernels", "mvn_set_kernel_derivation", "mvn_get_kernel_derivation",
+    "mvn_derive_counters", "mvn_derive_time",
 ]
+PSF_TYPES = {"independent": 0, "efficient_bayesian": 1, "optimization_1": 2, "optimization_2": 3}
 
 
 def _caller_stream(tensors):
@@ -213,6 +216,13 @@ class Binding:
         l.mvn_set_psi_start.argtypes = [C.c_int, C.c_float]
         l.mvn_get_psi_start.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_float)]
         l.mvn_engine_fuse_psi.argtypes = [C.c_void_p, C.c_float]
+        fpp = C.POINTER(c_float_p)
+        l.mvn_psf_extents.argtypes = [C.c_int, i3, vg, i3]
+        l.mvn_derive_kernels.argtypes = [C.c_int, C.c_int, fpp, i3, vg, C.c_int, i3, fpp, fpp]
+        l.mvn_set_kernel_derivation.argtypes = [C.c_int, C.c_int]
+        l.mvn_get_kernel_derivation.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        l.mvn_derive_counters.argtypes = [C.POINTER(C.c_longlong)]
+        l.mvn_derive_time.argtypes = [C.c_int, C.c_int, i3, C.c_int, C.c_int, C.POINTER(C.c_float)]
         l.mvn_tv_launch_count.restype = C.c_long
         l.mvn_tv_launch_count.argtypes = []
         l.mvn_engine_compute_delta.argtypes = [C.c_void_p, C.c_double, C.c_float]
@@ -613,18 +623,80 @@ class Binding:
         self.check(self.l.mvn_get_psi_start(C.byref(mode), C.byref(fill)))
         return mode.value, fill.value
 
+    # ---- derived kernels (mvn_derive_kernels) ----------------------------------------------
+    @staticmethod
+    def _psf_type(type_):
+        return PSF_TYPES[type_] if isinstance(type_, str) else int(type_)
+
+    @staticmethod
+    def _psf_args(raw_dims, geoms):
+        n = len(raw_dims)
+        if geoms is not None and len(geoms) != n:
+            raise ValueError("one geometry per raw PSF")
+        dims = (C.c_int * (3 * max(n, 1)))(*[int(x) for r in raw_dims for x in r])
+        garr = (ViewGeometry * max(n, 1))(*geoms) if geoms is not None else None
+        return n, dims, garr
+
+    def psf_extents(self, raw_dims, geoms=None):
+        """mvn_psf_extents: the common odd extents K of the kernels derived from raw PSFs of extents `raw_dims` (one
+        triple per view) under `geoms` (abi.view_geometry per view, only the linear part of the matrix is read; None:
+        the PSFs are in the block's frame)."""
+        n, dims, garr = self._psf_args(raw_dims, geoms)
+        out = (C.c_int * 3)(0, 0, 0)
+        self.check(self.l.mvn_psf_extents(n, dims, garr, out))
+        return tuple(out)
+
+    def derive_kernels(self, raw_psfs, geoms=None, type_="efficient_bayesian", out_dims=None, device=-1):
+        """mvn_derive_kernels: (kernels1, kernels2), two lists of dense float32 arrays of the common extents K, from the
+        raw PSFs (float32 arrays of odd extents) and the views' geometries; `type_` is a key of PSF_TYPES or its
+        number."""
+        raws = [np.ascontiguousarray(p, dtype=np.float32) for p in raw_psfs]
+        n, dims, garr = self._psf_args([p.shape for p in raws], geoms)
+        K = tuple(int(k) for k in out_dims) if out_dims is not None else self.psf_extents([p.shape for p in raws], geoms)
+        k1 = [np.full(K, np.nan, np.float32) for _ in raws]
+        k2 = [np.full(K, np.nan, np.float32) for _ in raws]
+        tab = lambda arrs: (c_float_p * max(n, 1))(*[fptr(a) for a in arrs])
+        self.check(self.l.mvn_derive_kernels(int(device), n, tab(raws), dims, garr, self._psf_type(type_),
+                                             _dims(K) if out_dims is not None else None, tab(k1), tab(k2)))
+        return k1, k2
+
+    def set_kernel_derivation(self, mode, type_="efficient_bayesian"):
+        """Process-wide: 1 makes mvn_deconvolve_resampled take RAW PSFs as kernel1_ and derive both kernels of `type_`
+        on the device; 0 (default) takes kernels as handed in (mvn_engine_api.h)."""
+        self.check(self.l.mvn_set_kernel_derivation(int(mode), self._psf_type(type_)))
+
+    def get_kernel_derivation(self):
+        mode, type_ = C.c_int(0), C.c_int(0)
+        self.check(self.l.mvn_get_kernel_derivation(C.byref(mode), C.byref(type_)))
+        return mode.value, type_.value
+
+    def derive_counters(self):
+        """mvn_derive_counters: (launches of the correlation kernel, derivations computed, derivations re-used)."""
+        out = (C.c_longlong * 3)(0, 0, 0)
+        self.check(self.l.mvn_derive_counters(out))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def derive_time(self, num_views, dims, type_="efficient_bayesian", reps=3, device=0):
+        """mvn_derive_time: (ms per derivation of num_views resident PSFs of extents `dims`, ms of its correlation
+        launches alone)."""
+        ms = (C.c_float * 2)(0, 0)
+        self.check(self.l.mvn_derive_time(int(device), int(num_views), _dims(dims), self._psf_type(type_), int(reps), ms))
+        return float(ms[0]), float(ms[1])
+
     def resample_call(self, psi, raws, geoms, kernels1, kernels2, lambda_, min_value, iterations, weights=None,
                       int16_is_uint16=False):
         """The arguments of mvn_deconvolve_resampled as a ResampledCall (`.run(device)` makes the call, `.memory()` asks
         mvn_deconvolve_memory_resampled): `raws` are the raw stacks (numpy arrays or torch tensors, float32 or uint16),
         `geoms` their abi.view_geometry; `weights`: None = computed from the geometries and normalised
-        (weights_mode 1), else one stack of psi's shape per view (weights_mode 0)."""
+        (weights_mode 1), else one stack of psi's shape per view (weights_mode 0).  kernels2=None leaves kernel2_ and
+        kernel2_dims_ NULL: for calls under set_kernel_derivation(1), where kernels1 are the raw PSFs."""
         n = len(raws)
-        if not (len(geoms) == n and len(kernels1) == n and len(kernels2) == n and (weights is None or len(weights) == n)):
+        if not (len(geoms) == n and len(kernels1) == n and (kernels2 is None or len(kernels2) == n)
+                and (weights is None or len(weights) == n)):
             raise ValueError("one geometry and two kernels per view")
         c = ResampledCall()
         c.binding, c.psi, c.mode = self, psi, 1 if weights is None else 0
-        c.keep = [[np.ascontiguousarray(k, dtype=np.float32) for k in ks] for ks in (kernels1, kernels2)]
+        c.keep = [[np.ascontiguousarray(k, dtype=np.float32) for k in ks] for ks in (kernels1, kernels2 or [])]
         k1, k2 = c.keep
         c.psi_ptr, p_desc, shape, p_dev = describe_stack(psi)
         c.image, c.weights, c.geom = (StackDesc * n)(), (StackDesc * n)(), (ViewGeometry * n)()
@@ -644,11 +716,13 @@ class Binding:
                     raise ValueError("view %d: weights have psi's shape %r" % (v, shape))
                 devices.append(w_dev)
                 d.weights_ = C.cast(C.c_void_p(w_ptr), c_float_p)
-            dims = [np.array(s_, dtype=np.int32) for s_ in (shape, k1[v].shape, k2[v].shape, shape)]
+            dims = [np.array(s_, dtype=np.int32) for s_ in (shape, k1[v].shape, k2[v].shape if k2 else (), shape)]
             c.keep.append(dims)
             d.image_ = C.cast(C.c_void_p(i_ptr), c_float_p)
-            d.kernel1_, d.kernel2_ = fptr(k1[v]), fptr(k2[v])
-            d.image_dims_, d.kernel1_dims_, d.kernel2_dims_, d.weights_dims_ = [iptr(x) for x in dims]
+            d.kernel1_ = fptr(k1[v])
+            d.image_dims_, d.kernel1_dims_, d.weights_dims_ = iptr(dims[0]), iptr(dims[1]), iptr(dims[3])
+            if k2:
+                d.kernel2_, d.kernel2_dims_ = fptr(k2[v]), iptr(dims[2])
         c.keep += [data, list(raws), list(weights or [])]
         c.ws = Workspace()
         c.ws.data_ = C.cast(data, C.POINTER(ViewData))
