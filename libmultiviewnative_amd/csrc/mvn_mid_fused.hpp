@@ -31,8 +31,8 @@
 //     ONE workgroup barrier
 // The two transforms of a wave are independent and run as stage pairs; the filter's lines are dealt out between a
 // pair's LDS requests and its arithmetic (mf_body).  The window is indexed with compile-time register numbers: KW = K
-// rounded up to a multiple of 8 slots, the filter code exists KW / 8 times per line (batch i uses variant i mod KW / 8),
-// selected by a workgroup-uniform branch.
+// rounded up to a multiple of 8 slots, the filter code exists KW / 8 times per line (batch i uses variant i mod KW / 8:
+// its window phase), and the steady state's loop is unrolled over the KW / 8 phases - no variant is selected at run time.
 //
 // The ends of a walk are code of their own (a launch had ~50 us outside its steady state, 12 % at 512 planes):
 //     prologue   passes -1 .. P - 1, P = (K - 1) / 8 whole batches that only fill the window: forward stages of the wave's
@@ -40,8 +40,10 @@
 //                transform back, no filter.  The first thing a workgroup requests is batch 0; the K taps follow in
 //                P + 1 groups, one behind each pass's line loads, so no wait for a line includes a tap (vector-memory
 //                loads return in order) and none is used before the loop.  The DC column's partner taps likewise.
-//     loop       batches P .. nb - 1 with the pipeline above; batch P is the only one with fill lines left in it (the
-//                first (K - 1) mod 8), and those take the fill form, not the whole filter
+//     mixed      batch P with the pipeline above, peeled: the only one with fill lines left in it (the first
+//                (K - 1) mod 8), and those take the fill form, not the whole filter.  Its phase is P = KW / 8 - 1
+//     loop       batches P + 1 .. nb - 1 with the pipeline above, starting in phase 0, KW / 8 batches per turn, one loop
+//                exit behind each batch
 //     tail       the last batch is transformed back and stored
 #pragma once
 
@@ -63,8 +65,10 @@
   }                                                                 \
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront", "local");   \
   __builtin_amdgcn_wave_barrier();
+#define MF_KEEP_IN_BLOCK(v) asm volatile("" : "+v"(v))  // not speculated, not turned into a select: stays behind its test
 #else
 #define MF_WPHASE(ctx, ...) MVN_PHASE(ctx, __VA_ARGS__)
+#define MF_KEEP_IN_BLOCK(v) (void)0
 #endif
 
 #define MF_N1 512         // line length (dim1 extent)
@@ -115,6 +119,7 @@ struct MfRegs {
   // the line's variant (see MF_FLINE in mf_body)
   cfloat xn[2], xp[2];
   int dcmode, qm, cpar;  // packed DC column (see below): the bin's kind, its partner bin, the lane's partner offset
+  int zin, zstep;        // the plane of the wave's next line to load and its step from batch to batch (mf_fetch); wave-uniform
 };
 
 inline long mf_pieces(const MidFusedParams& P) { return (P.seg > 0 && P.zcount <= 0) ? (P.d0 + P.seg - 1) / P.seg : 1; }
@@ -162,12 +167,22 @@ MVN_HD int mf_in_plane(const MidFusedParams& P, int z0, int n) {
   return z < 0 ? z + P.d0 : z;
 }
 
+// The wave's line of batch `batch`.  The batches are fetched in order, 0, 1, 2, ... (mf_setup, the prologue's passes, the
+// steady state), so the line's plane mf_in_plane(8 batch + wave) is carried as a counter that wraps by compare and
+// subtract (mf_fetch_start; device: in scalar registers, the wave's number being uniform) - not a division per batch.
 template <int K>
-MVN_HD void mf_fetch(const MidFusedParams& P, MfRegs<K>& r, int c, int z0, int batch, int nsteps, int tid) {
-  const int wv = tid >> 6, l = tid & 63;
+MVN_HD void mf_fetch_start(const MidFusedParams& P, MfRegs<K>& r, int z0, int tid) {
+  r.zin = mf_in_plane(P, z0, mvn_uniform(tid >> 6));
+  r.zstep = MF_LINES % P.d0;  // < d0: one subtraction wraps
+}
+template <int K>
+MVN_HD void mf_fetch(const MidFusedParams& P, MfRegs<K>& r, int c, int batch, int nsteps, int tid) {
+  const int wv = mvn_uniform(tid >> 6), l = tid & 63;
   const int n = batch * MF_LINES + wv;
+  const int z = r.zin;  // the plane of step n (mf_in_plane)
+  r.zin = z + r.zstep >= P.d0 ? z + r.zstep - P.d0 : z + r.zstep;
   if (n >= nsteps) return;
-  const cfloat* src = P.in + ((long)mf_in_plane(P, z0, n) * P.H + c) * MF_N1 + l;
+  const cfloat* src = P.in + ((long)z * P.H + c) * MF_N1 + l;
 #pragma unroll
   for (int m = 0; m < 8; ++m) r.xr[m] = src[64 * m];
 }
@@ -182,7 +197,8 @@ constexpr int mf_tap_lo(int K, int G) { return G * mf_tap_group(K) < K ? G * mf_
 
 template <int K>
 MVN_HD void mf_setup(const MidFusedParams& P, MfRegs<K>& r, int c, int z0, int nsteps, int tid) {
-  mf_fetch<K>(P, r, c, z0, 0, nsteps, tid);  // first: the forward transform of batch 0 waits for nothing else
+  mf_fetch_start<K>(P, r, z0, tid);
+  mf_fetch<K>(P, r, c, 0, nsteps, tid);  // first: the forward transform of batch 0 waits for nothing else
   r.bad = cmake(0.f, 0.f);
   r.dcmode = MF_DC_NONE;
   r.qm = r.cpar = 0;
@@ -439,7 +455,8 @@ MVN_HD void mf_store_line(const MidFusedParams& P, MfRegs<K>& r, const cfloat* b
 template <int K>
 MVN_HD void mf_store_line_c(const MidFusedParams& P, MfRegs<K>& r, const cfloat* twl, int c, int z0, int nout, int batch,
                             int tid) {
-  const int m = batch * MF_LINES + (tid >> 6) - (K - 1);
+  // (the wave's number is uniform: the line's plane and its wrap are scalar arithmetic on the device)
+  const int m = batch * MF_LINES + mvn_uniform(tid >> 6) - (K - 1);
   if (m < 0 || m >= nout) return;
   int z = z0 + m;
   z = z >= P.d0 ? z - P.d0 : z;
@@ -575,30 +592,22 @@ MVN_HD void mf_filter_line(MfRegs<K>& r, const cfloat* in, cfloat* out, bool dc,
   r.w[S] = x;
   r.bad = mvn_dim0_track(r.bad, x);
   cfloat o = cadd_i<+1>(s1, s2);
-  if (dc) o = r.dcmode == MF_DC_SELF ? cmake(s1.x, s2.y) : o;
+  if (dc) {
+    // (only column 0 pays for the select: the empty statement keeps it inside the uniform test's block)
+    o = r.dcmode == MF_DC_SELF ? cmake(s1.x, s2.y) : o;
+    MF_KEEP_IN_BLOCK(o);
+  }
   out[C * MF_PITCH + tid] = o;
 }
 template <int K, int C>
 MVN_HD void mf_fread_ahead(MfRegs<K>& r, const cfloat* in, bool dc, int tid) {
   if (C + 1 < MF_LINES) mf_fread<K>(r, in, C + 1, dc, tid);
 }
-// The loop of mf_body starts at batch MF_P, the only one in it that can hold fill lines: its first (K - 1) mod 8 ones
-// (`mixed`: this is that batch; the variant and the lines are compile-time constants, so FILL is known per line).
-template <int K, int C, int U>
-MVN_HD void mf_fline_dispatch(MfRegs<K>& r, const cfloat* in, cfloat* out, int u, bool mixed, bool dc, int tid) {
-  constexpr int NU = mf_slots(K) / 8;
-  if (u == U) {
-    if constexpr (U == mf_fill_batches(K) % NU && C < (K - 1) % MF_LINES) {
-      if (mixed)
-        mf_filter_line<K, U, C, true>(r, in, out, dc, tid);
-      else
-        mf_filter_line<K, U, C, false>(r, in, out, dc, tid);
-    } else {
-      mf_filter_line<K, U, C, false>(r, in, out, dc, tid);
-    }
-    return;
-  }
-  if constexpr (U + 1 < NU) mf_fline_dispatch<K, C, U + 1>(r, in, out, u, mixed, dc, tid);
+// Line C of a batch whose window phase U is a compile-time constant.  MIXED: batch MF_P, the only one behind the
+// prologue that can hold fill lines - its first (K - 1) mod 8 ones -, so FILL is known per line.
+template <int K, int U, int C, bool MIXED>
+MVN_HD void mf_fline(MfRegs<K>& r, const cfloat* in, cfloat* out, bool dc, int tid) {
+  mf_filter_line<K, U, C, MIXED && C < (K - 1) % MF_LINES>(r, in, out, dc, tid);
 }
 // (a FILL line tracks nothing: the plane it reads is tracked by the piece that outputs it.  A step that
 // outputs tracks its newest input in[z + h]: over the pieces of a column every plane exactly once.)
@@ -652,7 +661,7 @@ MVN_HD void mf_prologue(const MidFusedParams& P, cfloat* lds, const cfloat* twl,
     }
     MF_WPHASE(ctx, (mf_fread<K>(r, fin, 0, dc, tid)));
   }
-  MF_WPHASE(ctx, (mf_fwd0<K>(r, fwd, tid), mf_fetch<K>(P, r, c, z0, I + 2, nsteps, tid), mf_load_taps<K, I + 1>(P, r, c, tid)));
+  MF_WPHASE(ctx, (mf_fwd0<K>(r, fwd, tid), mf_fetch<K>(P, r, c, I + 2, nsteps, tid), mf_load_taps<K, I + 1>(P, r, c, tid)));
   if (dc) {
     MVN_PHASE_NOSYNC(ctx, (mf_load_taps_dc<K, I + 1>(P, r, tid)));
   }
@@ -670,9 +679,98 @@ MVN_HD void mf_prologue(const MidFusedParams& P, cfloat* lds, const cfloat* twl,
   if constexpr (I + 1 < mf_fill_batches(K)) mf_prologue<K, I + 1>(P, lds, twl, ctx, c, z0, nsteps, dc);
 }
 
+#if defined(__HIPCC__) && !defined(MVN_HOST_EMU)
+#define MF_PRIO_RESET() __builtin_amdgcn_s_setprio(0);
+#define MF_PRIO_RAISE_YOUNG() \
+  if (wave_young != 0) __builtin_amdgcn_s_setprio(2);
+#define MF_OPAQUE(x) asm volatile("" : "+s"(x))
+#else
+#define MF_PRIO_RESET()
+#define MF_PRIO_RAISE_YOUNG()
+#define MF_OPAQUE(x) (void)0
+#endif
+
+// Batch i of the steady state (MF_P <= i < nb), window phase U = i mod KW / 8 a compile-time constant: the pipeline of
+// the header on four line buffers - the forward transforms of batch i + 1 go to FW[(i + 1) & 1], the filter step of batch
+// i reads FW[i & 1] and writes OU[i & 1], the transforms back of batch i - 1 read OU[(i - 1) & 1].  A wave's forward and
+// backward transform of a batch are then independent of each other (two lines, two register sets): their
+// stages run in pairs (A, B, C), the LDS reads of a pair are requested together, and the lines of the filter step
+// - arithmetic on other buffers - are dealt out between a pair's requests and its arithmetic.
+// Orders that were tried and lost (profiles/r04_mid_fused.md): the filter step as one block in front of / behind the
+// transforms (+3 .. +18 %, and the loop that selects the order per wave spills), the forward transform one stage
+// behind the transform back (+8 %: a fourth stage in the batch's chain), the two halves of the CU's waves a third
+// of a batch out of step (+6 %), a stepped schedule read from a per-wave table (290 spills).
+// F: an always-true flag the compiler cannot see through (mf_body); every filter line is a block of its own behind it.
+template <int K, int U, bool MIXED, typename Ctx>
+MVN_HD void mf_batch(const MidFusedParams& P, cfloat* lds, const cfloat* twl, Ctx& ctx, int c, int z0, int nout, int nsteps,
+                     int i, bool dc, int F, int wave_young) {
+  constexpr int NT_ = MF_NT;
+  (void)NT_;
+  (void)wave_young;
+  const cfloat* fin = lds + (i & 1) * MF_BUF;
+  cfloat* fout = lds + (2 + (i & 1)) * MF_BUF;
+  cfloat* fwd = lds + ((i + 1) & 1) * MF_BUF;
+  cfloat* inv = lds + (2 + ((i + 1) & 1)) * MF_BUF;
+  // Both transforms run in EVERY batch - in batch MF_P the transform back works on lines nobody wrote, in the last one
+  // the forward transform does (their results go nowhere: mf_store_line_c and mf_fetch test the line's number
+  // themselves).  Behind a test each stage's LDS reads were followed, inside the test's block, by a wait and copies
+  // into the registers the next block expects: the latency the lines of the filter step were dealt out to cover was
+  // paid on the spot.  The passes that need only one of the two are outside: mf_prologue in front, the tail behind.
+#define MF_FLINE(C)                                                                                                      \
+  if (F) {                                                                                                               \
+    MF_WPHASE(ctx, (mf_fread_ahead<K, C>(r, fin, dc, tid), mf_fline<K, U, C, MIXED>(r, fin, fout, dc, tid)));            \
+  }
+  MF_PRIO_RESET()
+  // stage A: first stage back (reads the line) | first forward stage (reads the registers loaded ahead)
+  if (F) {
+    MF_WPHASE(ctx, (mf_fread<K>(r, fin, 0, dc, tid)));
+  }
+  MF_WPHASE(ctx, (mf_inv2_r<K>(r, inv, tid)));
+  if (dc) {
+    MF_WPHASE(ctx, (mf_inv2_fix_dc<K>(r, inv, tid)));
+  }
+  MF_WPHASE(ctx, (mf_fwd0<K>(r, fwd, tid), mf_fetch<K>(P, r, c, i + 2, nsteps, tid)));
+  MF_FLINE(0)
+  MF_WPHASE(ctx, (dftR<8, +1>(r.t), mf_inv2_b<K>(r, inv, tid)));
+  // stage B
+  MF_WPHASE(ctx, (mf_inv1_r<K>(r, inv, tid)));
+  MF_WPHASE(ctx, (mf_fwd1_r2<K>(r, fwd, tid)));
+  MF_FLINE(1)
+  MF_FLINE(2)
+  MF_PRIO_RAISE_YOUNG()
+  MF_WPHASE(ctx, (mf_inv1_c<K>(r, twl, tid), mf_inv1_b<K>(r, inv, tid)));
+  MF_WPHASE(ctx, (mf_fwd1_c2<K>(r, twl, tid), mf_fwd1_b2<K>(r, fwd, tid)));
+  // stage C
+  MF_WPHASE(ctx, (mf_inv0_r<K>(r, inv, tid)));
+  MF_WPHASE(ctx, (mf_fwd2_r2<K>(r, fwd, tid)));
+  MF_FLINE(3)
+  MF_FLINE(4)
+  MF_WPHASE(ctx, (mf_store_line_c<K>(P, r, twl, c, z0, nout, i - 1, tid)));
+  MF_WPHASE(ctx, (dftR<8, -1>(r.t2), mf_fwd2_b2<K>(r, fwd, tid)));
+  MF_FLINE(5)
+  MF_FLINE(6)
+  MF_FLINE(7)
+#undef MF_FLINE
+  MF_WPHASE(ctx, (mf_tw0_ahead<K>(r, twl, tid)));
+  MVN_PHASE(ctx, (void)0);
+}
+// One turn of the steady state's loop: the batches of phases U .. KW / 8 - 1, one loop exit behind each.  True: the walk
+// is at its end.
+template <int K, int U, typename Ctx>
+MVN_HD bool mf_turn(const MidFusedParams& P, cfloat* lds, const cfloat* twl, Ctx& ctx, int c, int z0, int nout, int nsteps,
+                    int& i, int nb, bool dc, int F, int wave_young) {
+  mf_batch<K, U, false>(P, lds, twl, ctx, c, z0, nout, nsteps, i, dc, F, wave_young);
+  if (++i >= nb) return true;
+  if constexpr (U + 1 < mf_slots(K) / 8)
+    return mf_turn<K, U + 1>(P, lds, twl, ctx, c, z0, nout, nsteps, i, nb, dc, F, wave_young);
+  else
+    return false;
+}
+
 template <int K, typename Ctx>
 MVN_HD void mf_body(const MidFusedParams& P, long block, cfloat* lds, Ctx& ctx) {
-  constexpr int NT_ = MF_NT, MF_P = mf_fill_batches(K);
+  constexpr int NT_ = MF_NT, MF_P = mf_fill_batches(K), NU = mf_slots(K) / 8;
+  static_assert(MF_P + 1 == NU, "the batch behind the mixed one is in window phase 0");
   (void)NT_;
   int c, z0, nout;
   mf_job(P, block, c, z0, nout);
@@ -692,88 +790,25 @@ MVN_HD void mf_body(const MidFusedParams& P, long block, cfloat* lds, Ctx& ctx) 
     MVN_PHASE_NOSYNC(ctx, (mf_split_taps_dc<K, MF_P>(r)));
   }
   MVN_PHASE_NOSYNC(ctx, (mf_taps_arrived<K>(r)));
-  // Four line buffers: the forward transforms of batch i + 1 go to FW[(i + 1) & 1], the filter step of batch i reads
-  // FW[i & 1] and writes OU[i & 1], the transforms back of batch i - 1 read OU[(i - 1) & 1].  A wave's forward and
-  // backward transform of an iteration are then independent of each other (two lines, two register sets): their
-  // stages run in pairs (A, B, C), the LDS reads of a pair are requested together, and the lines of the filter step
-  // - arithmetic on other buffers - are dealt out between a pair's requests and its arithmetic.
-  // Orders that were tried and lost (profiles/r04_mid_fused.md): the filter step as one block in front of / behind the
-  // transforms (+3 .. +18 %, and the loop that selects the order per wave spills), the forward transform one stage
-  // behind the transform back (+8 %: a fourth stage in the batch's chain), the two halves of the CU's waves a third
-  // of a batch out of step (+6 %), a stepped schedule read from a per-wave table (290 spills).
 #if defined(__HIPCC__) && !defined(MVN_HOST_EMU)
   const int wave_young = mvn_uniform((ctx.tid >> 8) & 1);
-#define MF_PRIO_RESET() __builtin_amdgcn_s_setprio(0);
-#define MF_PRIO_RAISE_YOUNG() \
-  if (wave_young != 0) __builtin_amdgcn_s_setprio(2);
-#define MF_OPAQUE(x) asm volatile("" : "+s"(x))
 #else
-#define MF_PRIO_RESET()
-#define MF_PRIO_RAISE_YOUNG()
-#define MF_OPAQUE(x) (void)0
+  const int wave_young = 0;
 #endif
-  // (Device: the loop's first batch and the flag every filter line is tested behind are opaque to the compiler, and so
-  // is the thread id behind the loop (MVN_TILE_LOOP_TOP).  The loop then keeps the blocks it had when it ran from pass -1
-  // to pass nb - each filter line a block of its own behind a uniform test - and no address of the tail is parked in a
-  // register across it: with the bounds and the flag known, the same loop took 6 more registers at every tap count
-  // (profiles/mid_fused_ends.md).)
-  int i0 = MF_P, F = 1;
-  MF_OPAQUE(i0);
+  // The steady state (mf_batch): the mixed batch MF_P, in window phase MF_P = KW / 8 - 1, then a loop over the batches
+  // MF_P + 1 .. nb - 1 that is unrolled over the KW / 8 phases, starting in phase 0: every filter line's window slots are
+  // compile-time register numbers without a run-time selection of the variant.
+  // (Device: the flag every filter line is tested behind is opaque to the compiler, and so is the thread id behind the
+  // loop (MVN_TILE_LOOP_TOP).  Each filter line stays a block of its own behind a uniform test, and no address of the
+  // tail is parked in a register across the loop: with the flag known, the loop took 6 more registers at every tap
+  // count (profiles/mid_fused_ends.md).)
+  int F = 1;
   MF_OPAQUE(F);
-  for (int i = i0; i < nb; ++i) {
-    const cfloat* fin = lds + (i & 1) * MF_BUF;
-    cfloat* fout = lds + (2 + (i & 1)) * MF_BUF;
-    cfloat* fwd = lds + ((i + 1) & 1) * MF_BUF;
-    cfloat* inv = lds + (2 + ((i + 1) & 1)) * MF_BUF;
-    // Both transforms run in EVERY pass of the loop - in the first one the transform back works on lines nobody wrote,
-    // in the last one the forward transform does (their results go nowhere: mf_store_line_c and mf_fetch test the
-    // line's number themselves).  Behind a test each stage's LDS reads were followed, inside the test's block, by a
-    // wait and copies into the registers the next block expects: the latency the lines of the filter step were dealt
-    // out to cover was paid on the spot.  The passes that need only one of the two are outside the loop: mf_prologue
-    // in front of it, the tail behind it.
-    const bool mixed = i == MF_P;
-    const int u = i % (mf_slots(K) / 8);
-#define MF_FLINE(C)                                                                \
-  if (F) {                                                                         \
-    MF_WPHASE(ctx, (mf_fread_ahead<K, C>(r, fin, dc, tid), mf_fline_dispatch<K, C, 0>(r, fin, fout, u, mixed, dc, tid)));  \
-  }
-    MF_PRIO_RESET()
-    // stage A: first stage back (reads the line) | first forward stage (reads the registers loaded ahead)
-    if (F) {
-      MF_WPHASE(ctx, (mf_fread<K>(r, fin, 0, dc, tid)));
+  int i = MF_P;
+  mf_batch<K, MF_P % NU, true>(P, lds, twl, ctx, c, z0, nout, nsteps, i, dc, F, wave_young);
+  if (++i < nb)
+    while (!mf_turn<K, 0>(P, lds, twl, ctx, c, z0, nout, nsteps, i, nb, dc, F, wave_young)) {
     }
-    MF_WPHASE(ctx, (mf_inv2_r<K>(r, inv, tid)));
-    if (dc) {
-      MF_WPHASE(ctx, (mf_inv2_fix_dc<K>(r, inv, tid)));
-    }
-    MF_WPHASE(ctx, (mf_fwd0<K>(r, fwd, tid), mf_fetch<K>(P, r, c, z0, i + 2, nsteps, tid)));
-    MF_FLINE(0)
-    MF_WPHASE(ctx, (dftR<8, +1>(r.t), mf_inv2_b<K>(r, inv, tid)));
-    // stage B
-    MF_WPHASE(ctx, (mf_inv1_r<K>(r, inv, tid)));
-    MF_WPHASE(ctx, (mf_fwd1_r2<K>(r, fwd, tid)));
-    MF_FLINE(1)
-    MF_FLINE(2)
-    MF_PRIO_RAISE_YOUNG()
-    MF_WPHASE(ctx, (mf_inv1_c<K>(r, twl, tid), mf_inv1_b<K>(r, inv, tid)));
-    MF_WPHASE(ctx, (mf_fwd1_c2<K>(r, twl, tid), mf_fwd1_b2<K>(r, fwd, tid)));
-    // stage C
-    MF_WPHASE(ctx, (mf_inv0_r<K>(r, inv, tid)));
-    MF_WPHASE(ctx, (mf_fwd2_r2<K>(r, fwd, tid)));
-    MF_FLINE(3)
-    MF_FLINE(4)
-    MF_WPHASE(ctx, (mf_store_line_c<K>(P, r, twl, c, z0, nout, i - 1, tid)));
-    MF_WPHASE(ctx, (dftR<8, -1>(r.t2), mf_fwd2_b2<K>(r, fwd, tid)));
-    MF_FLINE(5)
-    MF_FLINE(6)
-    MF_FLINE(7)
-#undef MF_FLINE
-    MF_WPHASE(ctx, (mf_tw0_ahead<K>(r, twl, tid)));
-    MVN_PHASE(ctx, (void)0);
-  }
-#undef MF_PRIO_RESET
-#undef MF_PRIO_RAISE_YOUNG
-#undef MF_OPAQUE
   // the tail: the last batch is transformed back and stored, nothing else
   MVN_TILE_LOOP_TOP(ctx);
   {
@@ -790,6 +825,9 @@ MVN_HD void mf_body(const MidFusedParams& P, long block, cfloat* lds, Ctx& ctx) 
   }
   MVN_PHASE_NOSYNC(ctx, (mf_report<K>(P, r)));
 }
+#undef MF_PRIO_RESET
+#undef MF_PRIO_RAISE_YOUNG
+#undef MF_OPAQUE
 
 // PSF preparation: lines [z][c][.] of a small stack (the PSF's planes after the last-axis pass) -> forward
 // transform along dim1, bins stored in the order the filter keeps them.  One batch of 8 planes of one column per
