@@ -199,6 +199,14 @@ template <int K>
 MVN_HD void mf_setup(const MidFusedParams& P, MfRegs<K>& r, int c, int z0, int nsteps, int tid) {
   mf_fetch_start<K>(P, r, z0, tid);
   mf_fetch<K>(P, r, c, 0, nsteps, tid);  // first: the forward transform of batch 0 waits for nothing else
+  // A walk of fewer than 8 steps (one tap on 5 .. 7 planes, a short last piece): the waves beyond it fetch nothing, ever,
+  // yet their line of batch 0 is transformed and TRACKED like every line (mf_fline) - whatever the registers held would
+  // flood the volume with NaN if it happened to be a non-finite pattern.  (In later batches such a wave still holds the
+  // last line it did fetch: tracked before.)
+  if (mvn_uniform(tid >> 6) >= nsteps) {
+#pragma unroll
+    for (int m = 0; m < 8; ++m) r.xr[m] = cmake(0.f, 0.f);
+  }
   r.bad = cmake(0.f, 0.f);
   r.dcmode = MF_DC_NONE;
   r.qm = r.cpar = 0;

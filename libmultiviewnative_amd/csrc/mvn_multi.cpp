@@ -284,6 +284,11 @@ void HaloGroup::load(const imageType* psi, const workspace& input, const shape_t
                      bool quotient_guard) {
   const int P = (int)slabs_.size();
   if (input.num_views_ != V_) throw std::invalid_argument("mvn: view count of the group");
+  // a PSF with more planes than the volume: a slab with its halos may be deep enough for it, the volume is not -
+  // rejected as one engine rejects it (Engine::prepare_psf), before anything is loaded: the caller's psi stays untouched
+  for (int v = 0; v < V_; ++v)
+    if (input.data_[v].kernel1_dims_[0] > ext_[0] || input.data_[v].kernel2_dims_[0] > ext_[0])
+      throw std::invalid_argument("mvn: kernel extent must be in [1, image extent]");
   for (int r = 0; r < P; ++r) {
     Slab& s = slabs_[(size_t)r];
     // the host planes this slab holds: [lo, hi) of the volume = [ha, hb) of the host stacks

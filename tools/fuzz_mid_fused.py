@@ -1,6 +1,10 @@
 """Every tap-count template of the fused middle pass (PSF depths 1 .. 31 along dim0) on random plane counts, through the
-blocking ABI call and the resident engine's slab range, against the CPU oracle.   python tools/fuzz_mid_fused.py [seed]
-(on the GPU box; MVN_MID_FUSED=2 forces the line layout for shallow volumes too)"""
+blocking ABI call, against the CPU oracle.   python tools/fuzz_mid_fused.py [seed] [--gaussian]
+(on the GPU box; MVN_MID_FUSED=2 forces the line layout for shallow volumes too)
+
+PSFs and images come from tests/flat_psf_cases.py: every PSF coefficient of the same order, white images - a lost or
+misplaced tap moves the result by about 1e-2.  --gaussian: the Gaussian PSFs and smooth blobs of ref_fixtures.py instead
+(their outer taps are below anything the 1e-5 bound sees)."""
 import os
 import sys
 
@@ -13,10 +17,13 @@ import numpy as np  # noqa: E402
 from libmultiviewnative_amd import native  # noqa: E402
 from libmultiviewnative_amd.abi import WorkspaceHolder  # noqa: E402
 from oracle import binding as orc  # noqa: E402
+from flat_psf_cases import flat_inputs  # noqa: E402
 from ref_fixtures import realistic_views  # noqa: E402
 
+args = [a for a in sys.argv[1:] if not a.startswith("--")]
+gaussian = "--gaussian" in sys.argv[1:]
 lib = native.lib()
-rng = np.random.default_rng(int(sys.argv[1]) if len(sys.argv) > 1 else 0)
+rng = np.random.default_rng(int(args[0]) if args else 0)
 worst = 0.0
 bad = 0
 for k0 in range(1, 32):
@@ -25,7 +32,11 @@ for k0 in range(1, 32):
     ks = (k0, int(rng.choice([1, 3, 5])), int(rng.choice([1, 3, 4])))
     lam = float(rng.choice([0.0, 0.006]))
     its = int(rng.integers(1, 3))
-    _, views, k1, k2, w, psi0 = realistic_views(shape, 2, ks, seed=int(rng.integers(1 << 30)))
+    seed = int(rng.integers(1 << 30))
+    if gaussian:
+        _, views, k1, k2, w, psi0 = realistic_views(shape, 2, ks, seed=seed)
+    else:
+        views, k1, k2, w, psi0 = flat_inputs(shape, ks, 2, seed)
     h = WorkspaceHolder(views, k1, k2, w, lam, 1e-4, its)
     c0 = lib.l.mvn_mid_fused_launch_count()
     got = lib.gpu_deconvolve(psi0, h)
