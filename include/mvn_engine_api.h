@@ -288,8 +288,9 @@ MVN_API int mvn_get_psi_start(int* mode, float* fill);
  * of extents dims (odd; no geometry, K = dims) holding random positive values - all its device work, `reps` derivations
  * between two stream events behind one that warms up; ms[1] = the same for its correlation launches alone (0 for the
  * types that have none).  It bypasses the derivation cache and moves out[0] only.
- * Out of scope: extracting PSFs from beads; the engine API (mvn_engine_set_view_resampled keeps taking kernels: call
- * mvn_derive_kernels first); every entry point other than the two resampled ones; raw PSFs in device memory. */
+ * Out of scope: the engine API (mvn_engine_set_view_resampled keeps taking kernels: call mvn_derive_kernels first);
+ * every entry point other than the two resampled ones; raw PSFs in device memory.  The raw PSF itself comes from the
+ * view's beads through mvn_extract_psf (below). */
 enum { MVN_PSF_INDEPENDENT = 0, MVN_PSF_EFFICIENT_BAYESIAN = 1, MVN_PSF_OPTIMIZATION_I = 2, MVN_PSF_OPTIMIZATION_II = 3 };
 MVN_API int mvn_psf_extents(int num_views, const int* raw_dims, const mvn_view_geometry* geom, int out_dims[3]);
 MVN_API int mvn_derive_kernels(int device, int num_views, const float* const* raw_psf, const int* raw_dims,
@@ -299,6 +300,79 @@ MVN_API int mvn_set_kernel_derivation(int mode, int type);
 MVN_API int mvn_get_kernel_derivation(int* mode, int* type);
 MVN_API int mvn_derive_counters(long long out[3]);
 MVN_API int mvn_derive_time(int device, int num_views, const int dims[3], int type, int reps, float* ms);
+/* ---- bead PSFs: a view's raw PSF from the beads in its raw stack -----------------------------------------------------
+ * What a light-sheet caller has is the raw stack of each view and a list of sub-voxel bead positions in it, from the
+ * interest points the views were registered with.  mvn_extract_psf averages, on the device, the interpolated
+ * neighbourhoods of those beads: the result is exactly what mvn_derive_kernels takes as raw_psf[v].  One call takes ONE
+ * view; a caller loops over its views.
+ *
+ * Inputs.  `raw` and raw_desc describe the raw stack over src_dims = m exactly as in mvn_resample_stack: uint16 or
+ * float32, host or device memory, the stride rules of an input stack, raw_desc == NULL = dense float32 in host memory;
+ * a stack in device memory is read where it lies, a stack in host memory is uploaded as it is into a temporary.
+ * `beads` is num_beads x 3 doubles (z, y, x) in HOST memory, as raw indices.  psf_dims = r, every entry odd and in
+ * 1..129, h = (r - 1) / 2.  psf_out is a dense float32 HOST array of extents r; scores_out receives num_beads doubles
+ * in HOST memory, or is NULL.  `stream`, the device choice and its checks are those of the described call.
+ *
+ * Arithmetic (normative).  Every float32 operation is rounded once, nothing is contracted into a fused multiply-add.
+ *   bead      for bead b at position p: B_k = floor(p_k), f_k = (float)(p_k - (double)B_k), formed once per bead - the
+ *             window is a pure translation, so they are the same for every voxel of it
+ *   sample    for PSF voxel j = (j0, j1, j2) the cell's low index along axis k is i_k = B_k + (j_k - h_k), its high index
+ *             i_k + 1; both go through mir(i, n), the mirror without repeating the edge sample (numpy.pad's "reflect"):
+ *             mir = 0 for n == 1, otherwise q = i mod (2n - 2) taken non-negative and mir = q < n ? q : 2n - 2 - q -
+ *             which holds for windows wider than the stack (several reflections).  S is the raw element widened to
+ *             float32, and s_b(j) is mvn_view_geometry's trilinear rule on those eight samples: lerp(p, q, f) =
+ *             p + f * (q - p) along raw axis 2, then 1, then 0
+ *   sum       beads in the order given, in groups of MVN_BEADS_GROUP: P_g(j) = ((+0.0 + (double)s_{32g}(j)) +
+ *             (double)s_{32g+1}(j)) + ... in double; T(j) = ((P_0 + P_1) + ...) + P_{G-1}, started from P_0 itself;
+ *             psf(j) = (float)(T(j) / (double)num_beads)
+ *   The result is the mean window: one bead at integer coordinates returns its neighbourhood bit for bit.
+ *   MVN_BEADS_REMOVE_MIN   mn = the minimum of psf over j (exact in any order); psf(j) <- psf(j) - mn in float32: the
+ *             smallest value becomes 0, what a camera's offset leaves under the PSF is removed
+ *   scores    (scores_out != NULL) against psf BEFORE the minimum is removed: per bead the sums sum s, sum s^2, sum P,
+ *             sum P^2 and sum sP over the window, P = psf widened to double, in double and in any order (a product of
+ *             two widened floats is exact in double); n = prod r;
+ *             score_b = (sum sP - sum s sum P / n) / sqrt((sum s^2 - (sum s)^2 / n) (sum P^2 - (sum P)^2 / n)),
+ *             and 0 where that denominator is not positive and finite.  Pearson's correlation of one bead with the
+ *             mean, in [-1, 1]: a caller drops merged beads and debris by it and extracts again.
+ *
+ * The call blocks, checks everything before it touches anything and writes the outputs last: errors (< 0, message in
+ * mvn_last_error(), psf_out and scores_out untouched) are those of mvn_resample_stack for the stack and its descriptor
+ * (src_dims above 2^30 - 1 as well), num_beads < 1, a null pointer, even psf_dims or psf_dims out of range, an unknown
+ * flag bit, a bead position that is not finite or lies outside 0 <= p_k <= m_k - 1 (the message names the bead's
+ * index), and a result with a non-finite element ("a non-finite PSF": a non-finite raw sample is the caller's mistake
+ * and must not reach the kernel derivation quietly).
+ *
+ * mvn_extract_memory: the device bytes that call allocates, allocating nothing; it reads only raw_desc, the dims and
+ * the counts.  With G = ceil(num_beads / MVN_BEADS_GROUP) and n = prod r:
+ *   32 num_beads            the bead records
+ *   8 G n                   the G partial volumes in double
+ *   4 n + 1028              the result, 256 partial minima and the non-finite flag
+ *   (10240 + 8) num_beads   want_scores != 0 only: 256 records of five double sums per bead, and the scores
+ *   the raw stack when it is in host memory: one element for strides {0, 0, 0}, m0 m1 m2 elements (the rows as they
+ *   are uploaded) otherwise.
+ * mvn_extract_counters, since process start: out[0] = launches of the gather, out[1] = launches of the score pass,
+ * out[2] = extractions completed (mvn_extract_psf calls that returned 0).  An extraction is one launch of the gather
+ * and, with scores_out, one of the score pass.
+ * mvn_extract_time (test and bench utility): ms[0] = milliseconds per extraction - all its device work, no scores,
+ * flags 0 - from a resident raw stack of src_dims (uint16 when u16 != 0, else float32; every src_dims[k] >=
+ * psf_dims[k] + 2) with num_beads beads at reproducible sub-voxel positions at least h + 1 from every face, `reps`
+ * extractions between two stream events behind one that warms up (out[0] moves by reps + 1, out[2] does not move);
+ * ms[1] = the same for the route a caller had until now: num_beads launches of the resample pass (image only) on the
+ * same stack and positions, each writing one volume of extents r through the identity plus the bead's offset, nothing
+ * summed; ms[2] = a plain copy of num_beads x prod r floats.
+ * Out of scope: detecting the beads; several views in one call; interpolation other than trilinear; bead lists or the
+ * result in device memory; a mode of mvn_set_kernel_derivation that takes bead lists - the extraction happens once per
+ * data set, not once per block, and the derivation cache already makes block after block free. */
+enum { MVN_BEADS_REMOVE_MIN = 1 }; /* flags */
+#define MVN_BEADS_GROUP 32         /* beads per partial sum: part of the arithmetic */
+MVN_API int mvn_extract_psf(int device, const void* raw, const mvn_stack_desc* raw_desc, const int src_dims[3],
+                            const double* beads, int num_beads, const int psf_dims[3], int flags, float* psf_out,
+                            double* scores_out, void* stream);
+MVN_API int mvn_extract_memory(const mvn_stack_desc* raw_desc, const int src_dims[3], int num_beads,
+                               const int psf_dims[3], int want_scores, int device, size_t* bytes);
+MVN_API int mvn_extract_counters(long long out[3]);
+MVN_API int mvn_extract_time(int device, int u16, const int src_dims[3], int num_beads, const int psf_dims[3], int reps,
+                             float* ms);
 /* out[0] = divide passes launched on a uint16 image, out[1] = ingest passes that wrote a uint16 volume, since process start */
 MVN_API int mvn_image_storage_counters(long long out[2]);
 /* Padding policy of inplace_gpu_deconvolve for the calls that follow (process-wide): "zero"

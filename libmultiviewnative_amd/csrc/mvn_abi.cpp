@@ -1935,6 +1935,252 @@ int mvn_derive_time(int device, int num_views, const int dims[3], int type, int 
   });
 }
 
+// ---- bead PSFs (mvn_beads.hpp; the arithmetic is stated at mvn_extract_psf in include/mvn_engine_api.h) ---------------
+extern "C++" {
+namespace {
+static_assert(MVN_BEADS_GROUP == MVN_BEADS_PER_GROUP, "the group size of the header is the passes'");
+
+// an extraction, everything checked that can be without touching the stack (pointers == false: a memory query, which
+// brings neither the stack nor the beads)
+struct BeadRequest {
+  int m[3] = {1, 1, 1}, r[3] = {1, 1, 1};
+  int nbeads = 0, flags = 0;
+  bool want_scores = false;
+  StackRef raw;
+  std::vector<BeadRec> recs;
+  size_t raw_bytes = 0;  // the upload of a stack in host memory
+  size_t n() const { return (size_t)r[0] * (size_t)r[1] * (size_t)r[2]; }
+  size_t groups() const { return (size_t)mvn_beads_groups(nbeads); }
+  size_t record_bytes() const { return (size_t)nbeads * sizeof(BeadRec); }
+  size_t partial_bytes() const { return groups() * n() * sizeof(double); }
+  size_t result_bytes() const { return n() * sizeof(float) + (MVN_BEADS_WG + 1) * sizeof(float); }
+  size_t score_bytes() const {
+    return want_scores ? (size_t)nbeads * (MVN_BEADS_WG * MVN_BEADS_SUMS + 1) * sizeof(double) : 0;
+  }
+  size_t bytes() const { return record_bytes() + partial_bytes() + result_bytes() + score_bytes() + raw_bytes; }
+};
+
+BeadRequest bead_request(const void* raw, const mvn_stack_desc* raw_desc, const int* src_dims, const double* beads,
+                         int num_beads, const int* psf_dims, int flags, bool want_scores, bool pointers) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  static const int placeholder = 0;  // (a memory query brings no pointers: nothing is read through this one)
+  if (!src_dims || !psf_dims) throw std::invalid_argument("null dims");
+  if (pointers && !beads) throw std::invalid_argument("null beads");
+  BeadRequest q;
+  for (int k = 0; k < 3; ++k) {
+    if (src_dims[k] < 1 || src_dims[k] > 0x3fffffff) throw std::invalid_argument("src_dims must be in 1..2^30 - 1");
+    if (psf_dims[k] < 1 || psf_dims[k] > MVN_BEADS_MAX || !(psf_dims[k] & 1))
+      throw std::invalid_argument("psf_dims must be odd and between 1 and " + std::to_string(MVN_BEADS_MAX));
+    q.m[k] = src_dims[k], q.r[k] = psf_dims[k];
+  }
+  if (num_beads < 1) throw std::invalid_argument("num_beads must be >= 1");
+  if (flags & ~(int)MVN_BEADS_REMOVE_MIN) throw std::invalid_argument("unknown flag bits " + std::to_string(flags));
+  q.nbeads = num_beads, q.flags = flags, q.want_scores = want_scores;
+  q.raw = described_stack(pointers ? raw : &placeholder, raw_desc, q.m, "raw", true, false);
+  Engine::check_raw_host(q.raw, q.m);
+  if (!q.raw.device) {
+    const size_t esz = q.raw.u16 ? sizeof(uint16_t) : sizeof(float);
+    q.raw_bytes = q.raw.broadcast() ? esz : (size_t)q.m[0] * (size_t)q.m[1] * (size_t)q.m[2] * esz;
+  }
+  if (!pointers) return q;
+  q.recs.resize((size_t)num_beads);
+  for (int b = 0; b < num_beads; ++b) {
+    BeadRec& rec = q.recs[(size_t)b];
+    std::memset(&rec, 0, sizeof(rec));
+    rec.interior = 1;
+    for (int k = 0; k < 3; ++k) {
+      const double p = beads[3 * (size_t)b + (size_t)k];
+      if (!std::isfinite(p)) throw std::invalid_argument("bead " + std::to_string(b) + ": non-finite position");
+      if (!(p >= 0. && p <= (double)(q.m[k] - 1)))
+        throw std::invalid_argument("bead " + std::to_string(b) + ": position outside the raw stack");
+      const int B = (int)p;  // floor: p >= 0
+      const int h = (q.r[k] - 1) / 2;
+      rec.B[k] = B;
+      rec.f[k] = (float)(p - (double)B);
+      if (B - h < 0 || (long long)B + h + 1 > (long long)q.m[k] - 1) rec.interior = 0;
+    }
+  }
+  return q;
+}
+
+// the device side of one extraction: buffers, the bead table, and the launches in stream order
+class BeadExtraction {
+ public:
+  // raw: the stack where the passes read it, in device memory (the caller's, or its temporary upload)
+  BeadExtraction(const BeadRequest& q, const StackRef& raw, be::stream_t s)
+      : q_(q),
+        table_(q.record_bytes()),
+        partial_(q.partial_bytes()),
+        psf_(q.result_bytes()),
+        records_(q.score_bytes() ? q.score_bytes() : sizeof(double)) {
+    std::memset(&p_, 0, sizeof(p_));
+    p_.src = raw.ptr, p_.s0 = raw.stride[0], p_.s1 = raw.stride[1], p_.s2 = raw.stride[2];
+    for (int k = 0; k < 3; ++k) p_.m[k] = q.m[k], p_.r[k] = q.r[k];
+    p_.beads = table_.get(), p_.nbeads = q.nbeads;
+    p_.partial = partial_.get(), p_.psf = psf_.get();
+    p_.minima = psf_.get() + q.n();
+    p_.flag = (unsigned*)(psf_.get() + q.n() + MVN_BEADS_WG);
+    if (q.want_scores) {
+      p_.records = records_.get();
+      p_.scores = records_.get() + (size_t)q.nbeads * MVN_BEADS_WG * MVN_BEADS_SUMS;
+    }
+    u16_ = raw.u16;
+    mvn_beads_check(p_);
+    be::h2d(table_.get(), q.recs.data(), q.record_bytes(), s);
+  }
+
+  // every launch of the extraction; scores are taken against the mean BEFORE its minimum is removed
+  void enqueue(be::stream_t s) const {
+    be::dzero(p_.flag, sizeof(unsigned), s);
+    be::launch_beads_gather(p_, u16_, s);
+    be::launch_beads_reduce(p_, s);
+    if (q_.want_scores) be::launch_beads_score(p_, u16_, s);
+    if (q_.flags & MVN_BEADS_REMOVE_MIN) be::launch_beads_remove_min(p_, s);
+  }
+
+  // the flag checked, then the results into host memory (either may be null); blocks
+  void download(float* psf, double* scores, be::stream_t s) const {
+    unsigned flag = 0;
+    std::vector<float> h_psf(psf ? q_.n() : 0);
+    std::vector<double> h_scores(scores && q_.want_scores ? (size_t)q_.nbeads : 0);
+    be::d2h(&flag, p_.flag, sizeof(flag), s);
+    if (!h_psf.empty()) be::d2h(h_psf.data(), p_.psf, h_psf.size() * sizeof(float), s);
+    if (!h_scores.empty()) be::d2h(h_scores.data(), p_.scores, h_scores.size() * sizeof(double), s);
+    be::stream_sync(s);
+    if (flag) throw std::invalid_argument("a non-finite PSF (a non-finite sample under a bead, or a mean beyond float32)");
+    if (!h_psf.empty()) std::memcpy(psf, h_psf.data(), h_psf.size() * sizeof(float));
+    if (!h_scores.empty()) std::memcpy(scores, h_scores.data(), h_scores.size() * sizeof(double));
+  }
+
+ private:
+  const BeadRequest& q_;
+  BeadsParams p_;
+  bool u16_ = false;
+  be::DeviceBuffer<BeadRec> table_;
+  be::DeviceBuffer<double> partial_;
+  be::DeviceBuffer<float> psf_;  // the result, MVN_BEADS_WG minima and the flag word behind it
+  be::DeviceBuffer<double> records_;
+};
+
+std::atomic<long long> g_extractions{0};
+}  // namespace
+}  // extern "C++"
+
+int mvn_extract_psf(int device, const void* raw, const mvn_stack_desc* raw_desc, const int src_dims[3],
+                    const double* beads, int num_beads, const int psf_dims[3], int flags, float* psf_out,
+                    double* scores_out, void* stream) {
+  return guarded("mvn_extract_psf", [&] {
+    if (!psf_out) throw std::invalid_argument("null psf_out");
+    const BeadRequest q = bead_request(raw, raw_desc, src_dims, beads, num_beads, psf_dims, flags, scores_out != nullptr, true);
+    int owner = -1;
+    check_location(q.raw, "raw", &owner);
+    if (owner >= 0 && device >= 0 && device != owner) throw std::invalid_argument("raw lives on another device");
+    const int dev = pick_device(owner >= 0 ? owner : device);
+    std::lock_guard<std::mutex> lk(device_mutex(dev));
+    be::set_device(dev);
+    be::DeviceBuffer<char> upload;
+    const be::Event caller = be::Event::sync_only();
+    const be::Stream own = be::Stream::create();
+    const be::stream_t s = own.get();
+    if (stream) {  // the caller's device stack is complete behind what its stream holds now
+      be::event_record(caller.get(), (be::stream_t)stream);
+      be::stream_wait_event(s, caller.get());
+    }
+    StackRef there = q.raw;
+    if (!q.raw.device) Engine::upload_raw(q.raw, q.m, upload, &there, s);
+    const BeadExtraction x(q, there, s);
+    x.enqueue(s);
+    x.download(psf_out, scores_out, s);
+    ++g_extractions;
+  });
+}
+
+int mvn_extract_memory(const mvn_stack_desc* raw_desc, const int src_dims[3], int num_beads, const int psf_dims[3],
+                       int want_scores, int device, size_t* bytes) {
+  return guarded("mvn_extract_memory", [&] {
+    if (!bytes) throw std::invalid_argument("null bytes");
+    *bytes = 0;
+    (void)device;
+    *bytes = bead_request(nullptr, raw_desc, src_dims, nullptr, num_beads, psf_dims, 0, want_scores != 0, false).bytes();
+  });
+}
+
+int mvn_extract_counters(long long out[3]) {
+  return guarded("mvn_extract_counters", [&] {
+    if (!out) throw std::invalid_argument("null out");
+    be::beads_counters(out);
+    out[2] = g_extractions.load();
+  });
+}
+
+// ms[0]: every launch of an extraction (no scores, flags 0) of num_beads beads from a resident raw stack of src_dims,
+// per extraction over `reps` extractions between two stream events behind one that warms up; ms[1]: num_beads launches
+// of the resample pass on the same stack, image only, each into one volume of extents psf_dims through the identity
+// plus the bead's offset, nothing summed, likewise; ms[2]: a plain copy of num_beads x prod psf_dims floats
+int mvn_extract_time(int device, int u16, const int src_dims[3], int num_beads, const int psf_dims[3], int reps,
+                     float* ms) {
+  return guarded("mvn_extract_time", [&] {
+    if (!src_dims || !psf_dims || !ms) throw std::invalid_argument("null argument");
+    if (reps < 1 || num_beads < 1) throw std::invalid_argument("reps and num_beads must be positive");
+    for (int k = 0; k < 3; ++k)
+      if (psf_dims[k] >= 1 && src_dims[k] < psf_dims[k] + 2)
+        throw std::invalid_argument("src_dims must be at least psf_dims + 2: the beads keep h + 1 from every face");
+    // reproducible sub-voxel positions, at least h + 1 from every face: an LCG's values in [h + 1, m - 2 - h]
+    std::vector<double> pos(3 * (size_t)num_beads);
+    unsigned x = 2463534242u;
+    for (size_t i = 0; i < pos.size(); ++i) {
+      x = x * 1664525u + 1013904223u;
+      const int k = (int)(i % 3);
+      const double lo = (double)((psf_dims[k] - 1) / 2 + 1), hi = (double)(src_dims[k] - 1) - lo;
+      pos[i] = lo + (hi - lo) * ((double)(x >> 8) * (1.0 / 16777216.0));
+    }
+    const int dev = pick_device(device);
+    std::lock_guard<std::mutex> lk(device_mutex(dev));
+    be::set_device(dev);
+    const size_t esz = u16 ? sizeof(uint16_t) : sizeof(float);
+    const size_t raw = (size_t)src_dims[0] * (size_t)src_dims[1] * (size_t)src_dims[2];
+    const be::DeviceBuffer<> dr(raw * esz);
+    mvn_stack_desc desc;
+    desc.dtype = u16 ? MVN_U16 : MVN_F32, desc.location = MVN_DEVICE;
+    desc.stride[0] = (long long)src_dims[1] * src_dims[2], desc.stride[1] = src_dims[2], desc.stride[2] = 1;
+    const BeadRequest q = bead_request(dr.get(), &desc, src_dims, pos.data(), num_beads, psf_dims, 0, false, true);
+    const Layout L(q.r[0], q.r[1], q.r[2]);
+    const size_t n = q.n();
+    const be::DeviceBuffer<float> di(L.real_floats() * sizeof(float));
+    const be::DeviceBuffer<float> ca((size_t)num_beads * n * sizeof(float)), cb((size_t)num_beads * n * sizeof(float));
+    const be::Stream st = be::Stream::create();
+    const be::stream_t s = st.get();
+    std::vector<unsigned char> h(raw * esz);
+    if (u16)
+      for (size_t i = 0; i < raw; ++i) ((uint16_t*)h.data())[i] = (uint16_t)(100u + i % 4001u);
+    else
+      for (size_t i = 0; i < raw; ++i) ((float*)h.data())[i] = 100.f + (float)(i % 4001u);
+    be::h2d(dr.get(), h.data(), h.size(), s);
+    const std::vector<float> row = lcg_fill(n);
+    for (int b = 0; b < num_beads; ++b) be::h2d(ca.get() + (size_t)b * n, row.data(), n * sizeof(float), s);
+    be::stream_sync(s);
+    const BeadExtraction ex(q, q.raw, s);
+    ms[0] = time_on_stream(s, reps, [&] { ex.enqueue(s); });
+    ex.download(nullptr, nullptr, s);  // (drains the stream; the flag says that the passes ran on sound values)
+    ResampleParams rp = resample_alone(L, di.get(), nullptr);
+    std::memset(&rp.g, 0, sizeof(rp.g));
+    rp.src = dr.get(), rp.s0 = desc.stride[0], rp.s1 = desc.stride[1], rp.s2 = 1;
+    for (int k = 0; k < 3; ++k) rp.g.m[k] = q.m[k], rp.g.M[4 * k + k] = 1.0;
+    ms[1] = time_on_stream(s, reps, [&] {
+      for (int b = 0; b < num_beads; ++b) {
+        for (int k = 0; k < 3; ++k) rp.g.M[4 * k + 3] = pos[3 * (size_t)b + (size_t)k] - (double)((q.r[k] - 1) / 2);
+        be::launch_resample(rp, u16 != 0, s);
+      }
+    });
+    const long width = (long)n;
+    ms[2] = time_on_stream(s, reps, [&] {
+      be::launch_copy3d(cb.get(), width, width * num_beads, ca.get(), width, width * num_beads, (int)n, num_beads, 1, s);
+    });
+  });
+}
+
 // what a fusion call is made of, everything checked that can be without its pointers (raw == NULL: a memory query)
 extern "C++" {
 namespace {

@@ -21,6 +21,7 @@
 #include "mvn_resample.hpp"
 #include "mvn_fuse.hpp"
 #include "mvn_psf.hpp"
+#include "mvn_beads.hpp"
 
 namespace mvn {
 namespace be {
@@ -175,6 +176,15 @@ void launch_psf_normalize(const PsfNormParams& p, stream_t s);
 void launch_psf_pointwise(const PsfPointParams& p, stream_t s);
 void launch_psf_correlate(const PsfCorrParams& p, stream_t s);
 long long psf_correlate_launches();
+// a view's PSF from its beads (mvn_beads.hpp; the raw stack is DEVICE memory here, u16: its element type): the gather
+// into p.partial; the sum over the groups and the mean into p.psf (p.flag is cleared by the caller); the minimum taken
+// off p.psf (both steps); and the scores of all beads against p.psf (both steps).  beads_counters: launches of the
+// gather and of the score pass since process start
+void launch_beads_gather(const BeadsParams& p, bool u16, stream_t s);
+void launch_beads_reduce(const BeadsParams& p, stream_t s);
+void launch_beads_remove_min(const BeadsParams& p, stream_t s);
+void launch_beads_score(const BeadsParams& p, bool u16, stream_t s);
+void beads_counters(long long out[2]);
 
 // stand-alone pointwise ops on flat arrays (legacy ABI: compute_quotient / compute_final_values)
 void launch_divide(const float* view, float* inout, size_t n, stream_t s);

@@ -584,6 +584,60 @@ void launch_psf_correlate(const PsfCorrParams& p, stream_t) {
     for (int t = 0; t < MVN_PSF_WG; ++t) mvn_psf_correlate_item(p, blk, t);
 }
 
+static std::atomic<long long> g_beads_gather_launches{0}, g_beads_score_launches{0};
+void beads_counters(long long out[2]) {
+  out[0] = g_beads_gather_launches.load();
+  out[1] = g_beads_score_launches.load();
+}
+
+void launch_beads_gather(const BeadsParams& p, bool u16, stream_t) {
+  mvn_beads_check(p);
+  const long nblocks = (long)mvn_beads_groups(p.nbeads) * mvn_beads_tiles(p);
+  ++g_beads_gather_launches;
+#pragma omp parallel for schedule(static)
+  for (long blk = 0; blk < nblocks; ++blk)
+    for (int t = 0; t < MVN_BEADS_WG; ++t) {
+      if (u16)
+        mvn_beads_gather_item<uint16_t>(p, blk, t);
+      else
+        mvn_beads_gather_item<float>(p, blk, t);
+    }
+}
+
+void launch_beads_reduce(const BeadsParams& p, stream_t) {
+  mvn_beads_check(p);
+  const long nblocks = mvn_beads_tiles(p);
+  for (long blk = 0; blk < nblocks; ++blk)
+    for (int t = 0; t < MVN_BEADS_WG; ++t) mvn_beads_reduce_item(p, blk, t);
+}
+
+void launch_beads_remove_min(const BeadsParams& p, stream_t) {
+  mvn_beads_check(p);
+  if (!p.minima) throw std::invalid_argument("mvn: beads: null pointer");
+  for (int t = 0; t < MVN_BEADS_WG; ++t) mvn_beads_min_item(p, t);
+  const long nblocks = mvn_beads_tiles(p);
+#pragma omp parallel for schedule(static)
+  for (long blk = 0; blk < nblocks; ++blk)
+    for (int t = 0; t < MVN_BEADS_WG; ++t) mvn_beads_sub_item(p, blk, t);
+}
+
+void launch_beads_score(const BeadsParams& p, bool u16, stream_t) {
+  mvn_beads_check(p);
+  if (!p.records || !p.scores) throw std::invalid_argument("mvn: beads: null pointer");
+  ++g_beads_score_launches;
+#pragma omp parallel for schedule(static)
+  for (long blk = 0; blk < (long)p.nbeads; ++blk)
+    for (int t = 0; t < MVN_BEADS_WG; ++t) {
+      if (u16)
+        mvn_beads_score_item<uint16_t>(p, blk, t);
+      else
+        mvn_beads_score_item<float>(p, blk, t);
+    }
+  const long folds = ((long)p.nbeads + MVN_BEADS_WG - 1) / MVN_BEADS_WG;
+  for (long blk = 0; blk < folds; ++blk)
+    for (int t = 0; t < MVN_BEADS_WG; ++t) mvn_beads_score_fold_item(p, blk, t);
+}
+
 static std::atomic<long> g_tv_launches{0};
 long tv_launch_count() { return g_tv_launches.load(); }
 void launch_tv(const TvParams& p0, stream_t) {

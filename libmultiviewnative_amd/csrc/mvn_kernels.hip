@@ -282,6 +282,34 @@ __global__ __launch_bounds__(MVN_PSF_WG) void k_psf_correlate(const PsfCorrParam
   mvn_psf_correlate_item(p, (long)blockIdx.x, (int)threadIdx.x);
 }
 
+// a view's PSF from its beads (mvn_beads.hpp): the gather, the sum over the groups, the minimum in two steps, and the
+// scores in two steps
+template <typename T>
+__global__ __launch_bounds__(MVN_BEADS_WG) void k_beads_gather(const BeadsParams p) {
+  mvn_beads_gather_item<T>(p, (long)blockIdx.x, (int)threadIdx.x);
+}
+
+__global__ __launch_bounds__(MVN_BEADS_WG) void k_beads_reduce(const BeadsParams p) {
+  mvn_beads_reduce_item(p, (long)blockIdx.x, (int)threadIdx.x);
+}
+
+__global__ __launch_bounds__(MVN_BEADS_WG) void k_beads_min(const BeadsParams p) {
+  mvn_beads_min_item(p, (int)threadIdx.x);
+}
+
+__global__ __launch_bounds__(MVN_BEADS_WG) void k_beads_sub(const BeadsParams p) {
+  mvn_beads_sub_item(p, (long)blockIdx.x, (int)threadIdx.x);
+}
+
+template <typename T>
+__global__ __launch_bounds__(MVN_BEADS_WG) void k_beads_score(const BeadsParams p) {
+  mvn_beads_score_item<T>(p, (long)blockIdx.x, (int)threadIdx.x);
+}
+
+__global__ __launch_bounds__(MVN_BEADS_WG) void k_beads_score_fold(const BeadsParams p) {
+  mvn_beads_score_fold_item(p, (long)blockIdx.x, (int)threadIdx.x);
+}
+
 // vector extrapolation between sweeps (mvn_extrapolate.hpp): two streaming passes and the reduction between them
 template <int W>
 __global__ __launch_bounds__(MVN_ACCEL_WG) void k_accel_a(const AccelParams p) {
@@ -1014,6 +1042,52 @@ void launch_psf_correlate(const PsfCorrParams& p, stream_t s) {
   mvn_psf_corr_check(p);
   ++g_psf_correlate_launches;
   hipLaunchKernelGGL(k_psf_correlate, dim3(psf_grid((long)p.njobs * p.blocks_per_job)), dim3(MVN_PSF_WG), 0, hs(s), p);
+  HIP_CHECK(hipGetLastError());
+}
+
+static std::atomic<long long> g_beads_gather_launches{0}, g_beads_score_launches{0};
+void beads_counters(long long out[2]) {
+  out[0] = g_beads_gather_launches.load();
+  out[1] = g_beads_score_launches.load();
+}
+
+void launch_beads_gather(const BeadsParams& p, bool u16, stream_t s) {
+  mvn_beads_check(p);
+  const unsigned grid = psf_grid((long)mvn_beads_groups(p.nbeads) * mvn_beads_tiles(p));
+  ++g_beads_gather_launches;
+  if (u16)
+    hipLaunchKernelGGL(k_beads_gather<uint16_t>, dim3(grid), dim3(MVN_BEADS_WG), 0, hs(s), p);
+  else
+    hipLaunchKernelGGL(k_beads_gather<float>, dim3(grid), dim3(MVN_BEADS_WG), 0, hs(s), p);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_beads_reduce(const BeadsParams& p, stream_t s) {
+  mvn_beads_check(p);
+  hipLaunchKernelGGL(k_beads_reduce, dim3(psf_grid(mvn_beads_tiles(p))), dim3(MVN_BEADS_WG), 0, hs(s), p);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_beads_remove_min(const BeadsParams& p, stream_t s) {
+  mvn_beads_check(p);
+  if (!p.minima) throw std::invalid_argument("mvn: beads: null pointer");
+  hipLaunchKernelGGL(k_beads_min, dim3(1), dim3(MVN_BEADS_WG), 0, hs(s), p);
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_beads_sub, dim3(psf_grid(mvn_beads_tiles(p))), dim3(MVN_BEADS_WG), 0, hs(s), p);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_beads_score(const BeadsParams& p, bool u16, stream_t s) {
+  mvn_beads_check(p);
+  if (!p.records || !p.scores) throw std::invalid_argument("mvn: beads: null pointer");
+  ++g_beads_score_launches;
+  if (u16)
+    hipLaunchKernelGGL(k_beads_score<uint16_t>, dim3(psf_grid(p.nbeads)), dim3(MVN_BEADS_WG), 0, hs(s), p);
+  else
+    hipLaunchKernelGGL(k_beads_score<float>, dim3(psf_grid(p.nbeads)), dim3(MVN_BEADS_WG), 0, hs(s), p);
+  HIP_CHECK(hipGetLastError());
+  const long folds = ((long)p.nbeads + MVN_BEADS_WG - 1) / MVN_BEADS_WG;
+  hipLaunchKernelGGL(k_beads_score_fold, dim3(psf_grid(folds)), dim3(MVN_BEADS_WG), 0, hs(s), p);
   HIP_CHECK(hipGetLastError());
 }
 

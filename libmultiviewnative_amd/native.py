@@ -12,8 +12,8 @@ import os
 
 import numpy as np
 
-from .abi import (CallDesc, StackDesc, ViewData, ViewGeometry, Workspace, c_float_p, c_int_p, describe_stack, fptr, iptr,
-                  view_geometry)
+from .abi import (MVN_DEVICE, CallDesc, StackDesc, ViewData, ViewGeometry, Workspace, c_float_p, c_int_p, describe_stack,
+                  fptr, iptr, view_geometry)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(_HERE, "lib")
@@ -58,7 +58,10 @@ ENGINE_ABI_SYMBOLS = [
     "mvn_get_psi_start", "mvn_engine_fuse_psi",
     "mvn_psf_extents", "mvn_derive_kernels", "mvn_set_kernel_derivation", "mvn_get_kernel_derivation",
     "mvn_derive_counters", "mvn_derive_time",
+    "mvn_extract_psf", "mvn_extract_memory", "mvn_extract_counters", "mvn_extract_time",
 ]
+BEADS_REMOVE_MIN = 1  # MVN_BEADS_REMOVE_MIN
+BEADS_GROUP = 32      # MVN_BEADS_GROUP
 PSF_TYPES = {"independent": 0, "efficient_bayesian": 1, "optimization_1": 2, "optimization_2": 3}
 
 
@@ -223,6 +226,11 @@ class Binding:
         l.mvn_get_kernel_derivation.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
         l.mvn_derive_counters.argtypes = [C.POINTER(C.c_longlong)]
         l.mvn_derive_time.argtypes = [C.c_int, C.c_int, i3, C.c_int, C.c_int, C.POINTER(C.c_float)]
+        l.mvn_extract_psf.argtypes = [C.c_int, C.c_void_p, C.POINTER(StackDesc), i3, C.POINTER(C.c_double), C.c_int, i3,
+                                      C.c_int, c_float_p, C.POINTER(C.c_double), C.c_void_p]
+        l.mvn_extract_memory.argtypes = [C.POINTER(StackDesc), i3, C.c_int, i3, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
+        l.mvn_extract_counters.argtypes = [C.POINTER(C.c_longlong)]
+        l.mvn_extract_time.argtypes = [C.c_int, C.c_int, i3, C.c_int, i3, C.c_int, C.POINTER(C.c_float)]
         l.mvn_tv_launch_count.restype = C.c_long
         l.mvn_tv_launch_count.argtypes = []
         l.mvn_engine_compute_delta.argtypes = [C.c_void_p, C.c_double, C.c_float]
@@ -682,6 +690,55 @@ class Binding:
         ms = (C.c_float * 2)(0, 0)
         self.check(self.l.mvn_derive_time(int(device), int(num_views), _dims(dims), self._psf_type(type_), int(reps), ms))
         return float(ms[0]), float(ms[1])
+
+    # ---- bead PSFs (mvn_extract_psf) --------------------------------------------------------
+    def extract_psf(self, raw, beads, psf_shape, remove_min=False, scores=False, device=None, int16_is_uint16=False,
+                    as_device=False):
+        """mvn_extract_psf: the mean of the trilinear windows of extents `psf_shape` (odd) around the `beads` (an
+        (N, 3) array of (z, y, x) positions, raw indices) of ONE view's raw stack `raw` (numpy array or torch tensor,
+        float32 or uint16, host or device, as deconvolve_resampled takes them).  Returns the PSF as a dense float32
+        array - what derive_kernels takes as a raw PSF - or (psf, scores) with scores=True: Pearson's correlation of
+        every bead's window with the mean.  remove_min: the smallest value of the result becomes 0.  as_device: describe
+        a host array as device memory (the emulation's pointers may be called either)."""
+        ptr, desc, shape, dev = describe_stack(raw, int16_is_uint16)
+        if as_device:
+            desc.location = MVN_DEVICE
+        pos = np.ascontiguousarray(beads, dtype=np.float64).reshape(-1, 3)
+        psf = np.full(tuple(int(x) for x in psf_shape), np.nan, np.float32)
+        sc = np.full(len(pos), np.nan, np.float64) if scores else None
+        stream = _caller_stream([raw])
+        self.check(self.l.mvn_extract_psf(int(device if device is not None else (dev if dev is not None else -1)),
+                                          C.c_void_p(ptr), C.byref(desc), _dims(shape),
+                                          pos.ctypes.data_as(C.POINTER(C.c_double)), len(pos), _dims(psf_shape),
+                                          BEADS_REMOVE_MIN if remove_min else 0, fptr(psf),
+                                          sc.ctypes.data_as(C.POINTER(C.c_double)) if scores else None,
+                                          C.c_void_p(stream)))
+        return (psf, sc) if scores else psf
+
+    def extract_memory(self, raw, num_beads, psf_shape, scores=False, device=0, int16_is_uint16=False,
+                       as_device=False):
+        """mvn_extract_memory: the bytes extract_psf would allocate on the device for this stack and these counts."""
+        ptr, desc, shape, dev = describe_stack(raw, int16_is_uint16)
+        if as_device:
+            desc.location = MVN_DEVICE
+        need = C.c_size_t(0)
+        self.check(self.l.mvn_extract_memory(C.byref(desc), _dims(shape), int(num_beads), _dims(psf_shape),
+                                             int(bool(scores)), int(device), C.byref(need)))
+        return need.value
+
+    def extract_counters(self):
+        """mvn_extract_counters: (launches of the gather, launches of the score pass, extractions completed)."""
+        out = (C.c_longlong * 3)(0, 0, 0)
+        self.check(self.l.mvn_extract_counters(out))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def extract_time(self, src_shape, num_beads, psf_shape, u16=True, reps=3, device=0):
+        """mvn_extract_time: (ms per extraction of num_beads beads from a resident raw stack, ms for one resample pass
+        per bead on the same stack and positions, ms per plain copy of num_beads windows)."""
+        ms = (C.c_float * 3)(0, 0, 0)
+        self.check(self.l.mvn_extract_time(int(device), int(bool(u16)), _dims(src_shape), int(num_beads),
+                                           _dims(psf_shape), int(reps), ms))
+        return float(ms[0]), float(ms[1]), float(ms[2])
 
     def resample_call(self, psi, raws, geoms, kernels1, kernels2, lambda_, min_value, iterations, weights=None,
                       int16_is_uint16=False):
