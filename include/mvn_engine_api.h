@@ -360,7 +360,8 @@ MVN_API int mvn_derive_time(int device, int num_views, const int dims[3], int ty
  * ms[1] = the same for the route a caller had until now: num_beads launches of the resample pass (image only) on the
  * same stack and positions, each writing one volume of extents r through the identity plus the bead's offset, nothing
  * summed; ms[2] = a plain copy of num_beads x prod r floats.
- * Out of scope: detecting the beads; several views in one call; interpolation other than trilinear; bead lists or the
+ * The bead positions themselves come from the same raw stack through mvn_detect_beads (below).
+ * Out of scope: several views in one call; interpolation other than trilinear; bead lists or the
  * result in device memory; a mode of mvn_set_kernel_derivation that takes bead lists - the extraction happens once per
  * data set, not once per block, and the derivation cache already makes block after block free. */
 enum { MVN_BEADS_REMOVE_MIN = 1 }; /* flags */
@@ -373,6 +374,90 @@ MVN_API int mvn_extract_memory(const mvn_stack_desc* raw_desc, const int src_dim
 MVN_API int mvn_extract_counters(long long out[3]);
 MVN_API int mvn_extract_time(int device, int u16, const int src_dims[3], int num_beads, const int psf_dims[3], int reps,
                              float* ms);
+/* ---- bead detection: a view's beads from its raw stack ----------------------------------------------------------------
+ * mvn_detect_beads finds, on the device, the beads of ONE view's raw stack: the strict extrema of a difference of two
+ * Gaussian blurs above a threshold, each with a quadratic sub-voxel fit.  Its positions are what mvn_extract_psf takes
+ * as `beads`, so the chain is raw stack -> mvn_detect_beads -> mvn_extract_psf -> mvn_derive_kernels ->
+ * mvn_deconvolve_resampled.
+ *
+ * Inputs.  `raw`, raw_desc, src_dims = m, `stream`, the device choice and their checks are exactly mvn_extract_psf's:
+ * uint16 or float32, host or device memory, the stride rules of an input stack, raw_desc == NULL = dense float32 in
+ * host memory; a stack in device memory is read where it lies, a stack in host memory is uploaded as it is into a
+ * temporary.  prm: sigma1 and sigma2 per raw axis in raw voxels (finite, 0 <= sigma <= 10), a finite threshold, flags.
+ * Outputs are HOST memory: *num_found; positions_out, capacity x 3 doubles (z, y, x) as raw indices - the layout of
+ * mvn_extract_psf's `beads`; values_out, capacity floats, or NULL; voxels_out, capacity x 3 ints, or NULL.
+ *
+ * Arithmetic (normative).  Every float32 and double operation is rounded once, nothing is contracted into a fused
+ * multiply-add.
+ *   taps      for a sigma s, on the host in double: R = ceil(3 s); g_i = exp(-(double)(i i) / ((2 s) s)) for i = -R..R;
+ *             S = ((g_{-R} + g_{-R+1}) + ...) + g_R, started from g_{-R} itself; w_i = (float)(g_i / S).  s = 0 gives
+ *             R = 0 and w = {1}.  R <= MVN_DETECT_MAX_RADIUS.  mvn_detect_taps returns exactly these taps: taps[j] =
+ *             w_{j-R} for j = 0..2R, *radius = R (an error, nothing written, when capacity < 2R + 1 or sigma is refused)
+ *   blur      along axis k of a float32 volume u: v(x) = ((w_{-R} u(mir(x-R)) + w_{-R+1} u(mir(x-R+1))) + ...) +
+ *             w_R u(mir(x+R)) - taps in ascending order, the sum started from the first product, everything float32;
+ *             mir is mvn_extract_psf's mirror (numpy.pad's "reflect", any number of reflections, 0 for an extent of 1)
+ *   volumes   L_a = the raw element widened to float32, blurred with sigma_a along axis 2, then axis 1, then axis 0
+ *             (a = 1, 2); D = L_1 - L_2 in float32; E = D, or -D under MVN_DETECT_MINIMA
+ *   candidate voxel c with 1 <= c_k <= m_k - 2 for every k, E(c) > threshold, and E(c) > E(n) for all 26 neighbours n:
+ *             the comparisons are strict, so a plateau yields nothing and a NaN neighbour disqualifies.  A stack with
+ *             an extent below 3 has no candidates, and that is no error (*num_found = 0, return value 0)
+ *   order     candidates are returned in ascending raster index (c_0 m_1 + c_1) m_2 + c_2, whatever the schedule
+ *   fit       in double on E widened, e_k the unit step along k, P = E(c + e_k), M = E(c - e_k):
+ *             g_k = (P - M) / 2;  H_kk = (P + M) - 2 E(c);
+ *             H_kl = ((E(c+e_k+e_l) - E(c+e_k-e_l)) - (E(c-e_k+e_l) - E(c-e_k-e_l))) / 4  (k < l; H is symmetric);
+ *             the cofactors, each a difference of two products:
+ *               C00 = H11 H22 - H12 H12   C01 = H02 H12 - H01 H22   C02 = H01 H12 - H02 H11
+ *               C11 = H00 H22 - H02 H02   C12 = H01 H02 - H00 H12   C22 = H00 H11 - H01 H01
+ *             the determinant along row 0: det = (H00 C00 + H01 C01) + H02 C02;
+ *             n_0 = (C00 g_0 + C01 g_1) + C02 g_2,  n_1 = (C01 g_0 + C11 g_1) + C12 g_2,
+ *             n_2 = (C02 g_0 + C12 g_1) + C22 g_2;  o_k = (-n_k) / det, that is o = -(adj(H) g) / det H.
+ *             If det is zero or not finite, or any o_k is not finite, or any |o_k| > 1, then o = (0, 0, 0)
+ *   result    position p_k = (double)c_k + o_k; value E(c); voxel c
+ *
+ * Capacity and errors.  The call blocks, checks everything before it touches anything and writes the outputs last.
+ * *num_found is the number of candidates; if it exceeds `capacity` the call fails, writes *num_found ONLY, and the
+ * message states the count (a caller calls again with that capacity).  Every other error returns < 0 with its message
+ * in mvn_last_error() and leaves every output, *num_found included, untouched: mvn_extract_psf's errors for the stack
+ * and its descriptor; a NULL raw, src_dims, prm, num_found or positions_out; a sigma that is negative, non-finite or
+ * above 10; a non-finite threshold; an unknown flag bit; capacity < 1.
+ *
+ * mvn_detect_dog (test utility): D alone, dense float32 of extents m into HOST memory; three blur launches, no
+ * extremum pass, no detection counted; prm's threshold and flags are checked and otherwise unused.
+ * mvn_detect_memory: the device bytes mvn_detect_beads allocates, allocating nothing; it reads only raw_desc, the dims
+ * and the capacity.  With n = m0 m1 m2:
+ *   16 n               four float32 volumes: the blurs along axis 2 and along axis 1 of both sigmas; D reuses the first
+ *   1536               the tap table: 2 blurs x 3 axes x 64 floats
+ *   8 + 48 capacity    the candidate count; per candidate its raster index (8), position (24), value (4), voxel (12)
+ *   the raw stack when it is in host memory: one element for strides {0, 0, 0}, n elements otherwise.
+ * mvn_detect_counters, since process start: out[0] = launches of the blur passes (three per detection: one per axis),
+ * out[1] = launches of the extremum pass (one per detection), out[2] = detections completed (mvn_detect_beads calls
+ * that returned 0).  A stack with an extent below 3 completes a detection without a launch.
+ * mvn_detect_time (test and bench utility): on a resident stack of src_dims (uint16 when u16 != 0, else float32) of
+ * reproducible non-trivial values, `reps` repetitions between two stream events behind one that warms up: ms[0] = all
+ * device work of a detection - the three blur passes, the extremum pass and the fit of the candidates a first run found
+ * (at most 2^20; the list is not sorted here); ms[1] = the three blur passes alone; ms[2] = a plain copy of one float32
+ * volume of src_dims.  out[0] moves by 3 + 6 (reps + 1), out[1] by 1 + (reps + 1), out[2] does not move.
+ * Out of scope: a scale-space search over several sigmas; an iterative re-localisation that moves to a neighbouring
+ * voxel; intensity normalisation of the raw stack; several views in one call; outputs in device memory; matching the
+ * detections across views; a mode of mvn_set_kernel_derivation that detects by itself. */
+enum { MVN_DETECT_MINIMA = 1 }; /* flags */
+#define MVN_DETECT_MAX_RADIUS 30
+typedef struct mvn_detect_params {
+  double sigma1[3], sigma2[3]; /* per raw axis, in raw voxels, finite, 0 <= sigma <= 10 */
+  float threshold;             /* finite */
+  int flags;
+} mvn_detect_params;
+MVN_API int mvn_detect_beads(int device, const void* raw, const mvn_stack_desc* raw_desc, const int src_dims[3],
+                             const mvn_detect_params* prm, int capacity, int* num_found, double* positions_out,
+                             float* values_out, int* voxels_out, void* stream);
+MVN_API int mvn_detect_taps(double sigma, float* taps, int capacity, int* radius);
+MVN_API int mvn_detect_dog(int device, const void* raw, const mvn_stack_desc* raw_desc, const int src_dims[3],
+                           const mvn_detect_params* prm, float* dog_out);
+MVN_API int mvn_detect_memory(const mvn_stack_desc* raw_desc, const int src_dims[3], int capacity, int device,
+                              size_t* bytes);
+MVN_API int mvn_detect_counters(long long out[3]);
+MVN_API int mvn_detect_time(int device, int u16, const int src_dims[3], const mvn_detect_params* prm, int reps,
+                            float* ms);
 /* out[0] = divide passes launched on a uint16 image, out[1] = ingest passes that wrote a uint16 volume, since process start */
 MVN_API int mvn_image_storage_counters(long long out[2]);
 /* Padding policy of inplace_gpu_deconvolve for the calls that follow (process-wide): "zero"

@@ -95,6 +95,30 @@ def view_geometry(src_shape, matrix, border=(0, 0, 0), blend_range=(0, 0, 0)):
     return g
 
 
+class DetectParams(C.Structure):
+    """mvn_detect_params: the two sigmas per raw axis, the threshold and the flags of mvn_detect_beads."""
+    _fields_ = [
+        ("sigma1", C.c_double * 3),
+        ("sigma2", C.c_double * 3),
+        ("threshold", C.c_float),
+        ("flags", C.c_int),
+    ]
+
+
+assert C.sizeof(DetectParams) == 56 and DetectParams.threshold.offset == 48 and DetectParams.flags.offset == 52
+
+
+def detect_params(sigma1, sigma2, threshold, flags=0):
+    """A DetectParams from one sigma or three per set (z, y, x)."""
+    p = DetectParams()
+    s1 = np.broadcast_to(np.asarray(sigma1, np.float64), (3,))
+    s2 = np.broadcast_to(np.asarray(sigma2, np.float64), (3,))
+    for k in range(3):
+        p.sigma1[k], p.sigma2[k] = float(s1[k]), float(s2[k])
+    p.threshold, p.flags = float(threshold), int(flags)
+    return p
+
+
 def _is_tensor(a):
     # (torch is never imported here: an object that is not a numpy array and has these is taken for a tensor)
     return not isinstance(a, np.ndarray) and hasattr(a, "data_ptr") and hasattr(a, "stride")

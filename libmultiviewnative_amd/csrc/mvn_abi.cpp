@@ -2181,6 +2181,315 @@ int mvn_extract_time(int device, int u16, const int src_dims[3], int num_beads, 
   });
 }
 
+// ---- bead detection (mvn_detect.hpp; the arithmetic is stated at mvn_detect_beads in include/mvn_engine_api.h) ---------
+extern "C++" {
+namespace {
+static_assert(MVN_DETECT_MAX_RADIUS == MVN_DETECT_RMAX, "the largest radius of the header is the passes'");
+static_assert(2 * MVN_DETECT_RMAX + 1 <= MVN_DETECT_TAPS, "a tap vector fits its place in the table");
+
+// a detection, everything checked that can be without touching the stack (pointers == false: a memory query, which
+// brings neither the stack nor the parameters)
+struct DetectRequest {
+  int m[3] = {1, 1, 1};
+  int R[2][3] = {{0, 0, 0}, {0, 0, 0}};
+  float threshold = 0.f;
+  int flags = 0;
+  long long capacity = 1;
+  StackRef raw;
+  std::vector<float> table;  // MVN_DETECT_TABLE floats
+  size_t raw_bytes = 0;      // the upload of a stack in host memory
+  size_t n() const { return (size_t)m[0] * (size_t)m[1] * (size_t)m[2]; }
+  size_t volume_bytes() const { return n() * sizeof(float); }
+  size_t table_bytes() const { return MVN_DETECT_TABLE * sizeof(float); }
+  size_t list_bytes() const { return (size_t)capacity * sizeof(long long); }
+  size_t result_bytes() const { return (size_t)capacity * (3 * sizeof(double) + sizeof(float) + 3 * sizeof(int)); }
+  size_t bytes() const {
+    return 4 * volume_bytes() + table_bytes() + sizeof(unsigned long long) + list_bytes() + result_bytes() + raw_bytes;
+  }
+  bool too_thin() const { return m[0] < 3 || m[1] < 3 || m[2] < 3; }  // no voxel has 26 neighbours
+};
+
+DetectRequest detect_request(const void* raw, const mvn_stack_desc* raw_desc, const int* src_dims,
+                             const mvn_detect_params* prm, long long capacity, bool pointers) {
+  static const int placeholder = 0;  // (a memory query brings no pointers: nothing is read through this one)
+  if (!src_dims) throw std::invalid_argument("null dims");
+  if (pointers && !prm) throw std::invalid_argument("null prm");
+  DetectRequest q;
+  for (int k = 0; k < 3; ++k) {
+    if (src_dims[k] < 1 || src_dims[k] > 0x3fffffff) throw std::invalid_argument("src_dims must be in 1..2^30 - 1");
+    q.m[k] = src_dims[k];
+  }
+  if (capacity < 1) throw std::invalid_argument("capacity must be >= 1");
+  q.capacity = capacity;
+  q.raw = described_stack(pointers ? raw : &placeholder, raw_desc, q.m, "raw", true, false);
+  Engine::check_raw_host(q.raw, q.m);
+  if (!q.raw.device) {
+    const size_t esz = q.raw.u16 ? sizeof(uint16_t) : sizeof(float);
+    q.raw_bytes = q.raw.broadcast() ? esz : q.n() * esz;
+  }
+  if (!pointers) return q;
+  if (!std::isfinite(prm->threshold)) throw std::invalid_argument("a non-finite threshold");
+  if (prm->flags & ~(int)MVN_DETECT_MINIMA) throw std::invalid_argument("unknown flag bits " + std::to_string(prm->flags));
+  q.threshold = prm->threshold, q.flags = prm->flags;
+  q.table.assign(MVN_DETECT_TABLE, 0.f);
+  for (int a = 0; a < 2; ++a)
+    for (int k = 0; k < 3; ++k) {
+      const double sigma = a == 0 ? prm->sigma1[k] : prm->sigma2[k];
+      if (!(sigma >= 0.0 && sigma <= 10.0))
+        throw std::invalid_argument("sigma" + std::to_string(a + 1) + "[" + std::to_string(k) +
+                                    "] must be finite and in 0..10");
+      q.R[a][k] = mvn_detect_make_taps(sigma, q.table.data() + (size_t)(a * 3 + k) * MVN_DETECT_TAPS);
+    }
+  return q;
+}
+
+// the device side of one detection: buffers, the tap table, and the launches in stream order
+class Detection {
+ public:
+  // raw: the stack where the passes read it, in device memory (the caller's, or its temporary upload)
+  Detection(const DetectRequest& q, const StackRef& raw, be::stream_t s)
+      : q_(q),
+        volumes_(4 * q.volume_bytes()),
+        table_(q.table_bytes()),
+        count_(sizeof(unsigned long long)),
+        list_(q.list_bytes()),
+        results_(q.result_bytes()) {
+    std::memset(&p_, 0, sizeof(p_));
+    p_.src = raw.ptr, p_.s0 = raw.stride[0], p_.s1 = raw.stride[1], p_.s2 = raw.stride[2];
+    for (int k = 0; k < 3; ++k) p_.m[k] = q.m[k], p_.R[0][k] = q.R[0][k], p_.R[1][k] = q.R[1][k];
+    p_.taps = table_.get();
+    p_.a[0] = volumes_.get(), p_.a[1] = volumes_.get() + q.n();
+    p_.b[0] = volumes_.get() + 2 * q.n(), p_.b[1] = volumes_.get() + 3 * q.n();
+    p_.threshold = q.threshold, p_.minima = (q.flags & MVN_DETECT_MINIMA) ? 1 : 0;
+    p_.count = count_.get(), p_.list = list_.get(), p_.list_cap = q.capacity;
+    p_.pos = (double*)results_.get();  // positions, then voxels, then values: every block aligned to its type
+    p_.vox = (int*)(p_.pos + 3 * (size_t)q.capacity);
+    p_.val = (float*)(p_.vox + 3 * (size_t)q.capacity);
+    u16_ = raw.u16;
+    mvn_detect_check_blur(p_);
+    be::h2d(table_.get(), q.table.data(), q.table_bytes(), s);
+  }
+
+  void blur(be::stream_t s) const { be::launch_detect_blur(p_, u16_, s); }
+  void extrema(be::stream_t s) const {
+    be::dzero(p_.count, sizeof(unsigned long long), s);
+    be::launch_detect_extrema(p_, s);
+  }
+  // the candidates the extremum pass counted (it may be above the capacity: the list then holds some of them); blocks
+  unsigned long long found(be::stream_t s) const {
+    unsigned long long c = 0;
+    be::d2h(&c, p_.count, sizeof(c), s);
+    be::stream_sync(s);
+    return c;
+  }
+  // the list in ascending raster order, whatever order the workgroups appended in; blocks
+  void sort(long long nfound, be::stream_t s) const {
+    std::vector<long long> h((size_t)nfound);
+    be::d2h(h.data(), p_.list, h.size() * sizeof(long long), s);
+    be::stream_sync(s);
+    std::sort(h.begin(), h.end());
+    be::h2d(p_.list, h.data(), h.size() * sizeof(long long), s);
+    be::stream_sync(s);  // (h leaves scope)
+  }
+  void refine(long long nfound, be::stream_t s) const {
+    DetectParams p = p_;
+    p.nfound = nfound;
+    be::launch_detect_refine(p, s);
+  }
+  // the results of nfound candidates into host vectors; blocks
+  void download(long long nfound, std::vector<double>* pos, std::vector<float>* val, std::vector<int>* vox,
+                be::stream_t s) const {
+    pos->resize(3 * (size_t)nfound), val->resize((size_t)nfound), vox->resize(3 * (size_t)nfound);
+    be::d2h(pos->data(), p_.pos, pos->size() * sizeof(double), s);
+    be::d2h(val->data(), p_.val, val->size() * sizeof(float), s);
+    be::d2h(vox->data(), p_.vox, vox->size() * sizeof(int), s);
+    be::stream_sync(s);
+  }
+  const float* dog() const { return p_.a[0]; }
+
+ private:
+  const DetectRequest& q_;
+  DetectParams p_;
+  bool u16_ = false;
+  be::DeviceBuffer<float> volumes_;  // a[0], a[1], b[0], b[1]; D is a[0]
+  be::DeviceBuffer<float> table_;
+  be::DeviceBuffer<unsigned long long> count_;
+  be::DeviceBuffer<long long> list_;
+  be::DeviceBuffer<char> results_;
+};
+
+// the device and the stream of a call on one described raw stack, as mvn_extract_psf picks them; `body` runs with the
+// stack where the passes read it
+template <typename F>
+void on_raw_stack(int device, const StackRef& raw, const int* m, void* stream, F&& body) {
+  int owner = -1;
+  check_location(raw, "raw", &owner);
+  if (owner >= 0 && device >= 0 && device != owner) throw std::invalid_argument("raw lives on another device");
+  const int dev = pick_device(owner >= 0 ? owner : device);
+  std::lock_guard<std::mutex> lk(device_mutex(dev));
+  be::set_device(dev);
+  be::DeviceBuffer<char> upload;
+  const be::Event caller = be::Event::sync_only();
+  const be::Stream own = be::Stream::create();
+  const be::stream_t s = own.get();
+  if (stream) {  // the caller's device stack is complete behind what its stream holds now
+    be::event_record(caller.get(), (be::stream_t)stream);
+    be::stream_wait_event(s, caller.get());
+  }
+  StackRef there = raw;
+  if (!raw.device) Engine::upload_raw(raw, m, upload, &there, s);
+  body(there, s);
+}
+
+std::atomic<long long> g_detections{0};
+}  // namespace
+}  // extern "C++"
+
+int mvn_detect_beads(int device, const void* raw, const mvn_stack_desc* raw_desc, const int src_dims[3],
+                     const mvn_detect_params* prm, int capacity, int* num_found, double* positions_out,
+                     float* values_out, int* voxels_out, void* stream) {
+  return guarded("mvn_detect_beads", [&] {
+    if (!num_found || !positions_out) throw std::invalid_argument("null num_found or positions_out");
+    const DetectRequest q = detect_request(raw, raw_desc, src_dims, prm, capacity, true);
+    if (q.too_thin()) {  // (the location is still checked: a wrong descriptor is an error at any extents)
+      int owner = -1;
+      check_location(q.raw, "raw", &owner);
+      *num_found = 0;
+      ++g_detections;
+      return;
+    }
+    on_raw_stack(device, q.raw, q.m, stream, [&](const StackRef& there, be::stream_t s) {
+      const Detection d(q, there, s);
+      d.blur(s);
+      d.extrema(s);
+      const unsigned long long found = d.found(s);
+      if (found > (unsigned long long)q.capacity) {
+        *num_found = found > 0x7fffffffull ? 0x7fffffff : (int)found;
+        throw std::invalid_argument(std::to_string(found) + " candidates exceed the capacity of " +
+                                    std::to_string(q.capacity));
+      }
+      std::vector<double> pos;
+      std::vector<float> val;
+      std::vector<int> vox;
+      if (found > 0) {
+        d.sort((long long)found, s);
+        d.refine((long long)found, s);
+        d.download((long long)found, &pos, &val, &vox, s);
+      }
+      *num_found = (int)found;
+      if (found > 0) {
+        std::memcpy(positions_out, pos.data(), pos.size() * sizeof(double));
+        if (values_out) std::memcpy(values_out, val.data(), val.size() * sizeof(float));
+        if (voxels_out) std::memcpy(voxels_out, vox.data(), vox.size() * sizeof(int));
+      }
+      ++g_detections;
+    });
+  });
+}
+
+int mvn_detect_taps(double sigma, float* taps, int capacity, int* radius) {
+  return guarded("mvn_detect_taps", [&] {
+    if (!taps || !radius) throw std::invalid_argument("null argument");
+    float w[2 * MVN_DETECT_RMAX + 1];
+    const int R = mvn_detect_make_taps(sigma, w);
+    if (capacity < 2 * R + 1)
+      throw std::invalid_argument("capacity " + std::to_string(capacity) + " is below the " + std::to_string(2 * R + 1) +
+                                  " taps of this sigma");
+    std::memcpy(taps, w, (size_t)(2 * R + 1) * sizeof(float));
+    *radius = R;
+  });
+}
+
+int mvn_detect_dog(int device, const void* raw, const mvn_stack_desc* raw_desc, const int src_dims[3],
+                   const mvn_detect_params* prm, float* dog_out) {
+  return guarded("mvn_detect_dog", [&] {
+    if (!dog_out) throw std::invalid_argument("null dog_out");
+    const DetectRequest q = detect_request(raw, raw_desc, src_dims, prm, 1, true);
+    on_raw_stack(device, q.raw, q.m, nullptr, [&](const StackRef& there, be::stream_t s) {
+      const Detection d(q, there, s);
+      d.blur(s);
+      std::vector<float> h(q.n());
+      be::d2h(h.data(), d.dog(), h.size() * sizeof(float), s);
+      be::stream_sync(s);
+      std::memcpy(dog_out, h.data(), h.size() * sizeof(float));
+    });
+  });
+}
+
+int mvn_detect_memory(const mvn_stack_desc* raw_desc, const int src_dims[3], int capacity, int device, size_t* bytes) {
+  return guarded("mvn_detect_memory", [&] {
+    if (!bytes) throw std::invalid_argument("null bytes");
+    *bytes = 0;
+    (void)device;
+    *bytes = detect_request(nullptr, raw_desc, src_dims, nullptr, capacity, false).bytes();
+  });
+}
+
+int mvn_detect_counters(long long out[3]) {
+  return guarded("mvn_detect_counters", [&] {
+    if (!out) throw std::invalid_argument("null out");
+    be::detect_counters(out);
+    out[2] = g_detections.load();
+  });
+}
+
+// ms[0]: the blur passes, the extremum pass and the fit of the candidates a first run found (at most 2^20, unsorted),
+// per repetition over `reps` repetitions between two stream events behind one that warms up; ms[1]: the blur passes
+// alone, likewise; ms[2]: a plain copy of one float32 volume of src_dims
+int mvn_detect_time(int device, int u16, const int src_dims[3], const mvn_detect_params* prm, int reps, float* ms) {
+  return guarded("mvn_detect_time", [&] {
+    if (!src_dims || !prm || !ms) throw std::invalid_argument("null argument");
+    if (reps < 1) throw std::invalid_argument("reps must be positive");
+    const int dev = pick_device(device);
+    std::lock_guard<std::mutex> lk(device_mutex(dev));
+    be::set_device(dev);
+    for (int k = 0; k < 3; ++k)
+      if (src_dims[k] < 1 || src_dims[k] > 0x3fffffff) throw std::invalid_argument("src_dims must be in 1..2^30 - 1");
+    const size_t esz = u16 ? sizeof(uint16_t) : sizeof(float);
+    const size_t n = (size_t)src_dims[0] * (size_t)src_dims[1] * (size_t)src_dims[2];
+    const be::DeviceBuffer<> dr(n * esz);
+    mvn_stack_desc desc;
+    desc.dtype = u16 ? MVN_U16 : MVN_F32, desc.location = MVN_DEVICE;
+    desc.stride[0] = (long long)src_dims[1] * src_dims[2], desc.stride[1] = src_dims[2], desc.stride[2] = 1;
+    const DetectRequest q = detect_request(dr.get(), &desc, src_dims, prm, 1 << 20, true);
+    const be::DeviceBuffer<float> cb(n * sizeof(float));
+    const be::Stream st = be::Stream::create();
+    const be::stream_t s = st.get();
+    {  // an LCG's values: 100 .. 4195 with no period the tiles share
+      std::vector<unsigned char> h(n * esz);
+      unsigned x = 2463534242u;
+      for (size_t i = 0; i < n; ++i) {
+        x = x * 1664525u + 1013904223u;
+        if (u16)
+          ((uint16_t*)h.data())[i] = (uint16_t)(100u + (x >> 20));
+        else
+          ((float*)h.data())[i] = 100.f + (float)(x >> 20);
+      }
+      be::h2d(dr.get(), h.data(), h.size(), s);
+      be::stream_sync(s);
+    }
+    const Detection d(q, q.raw, s);
+    d.blur(s);
+    unsigned long long found = 0;
+    if (!q.too_thin()) {
+      d.extrema(s);
+      found = d.found(s);
+      if (found > (unsigned long long)q.capacity) found = (unsigned long long)q.capacity;
+    }
+    ms[0] = time_on_stream(s, reps, [&] {
+      d.blur(s);
+      if (!q.too_thin()) d.extrema(s);
+      if (found > 0) d.refine((long long)found, s);
+    });
+    ms[1] = time_on_stream(s, reps, [&] { d.blur(s); });
+    be::stream_sync(s);
+    const long row = src_dims[2], plane = (long)src_dims[1] * src_dims[2];
+    ms[2] = time_on_stream(s, reps, [&] {
+      be::launch_copy3d(cb.get(), row, plane, d.dog(), row, plane, src_dims[2], src_dims[1], src_dims[0], s);
+    });
+  });
+}
+
 // what a fusion call is made of, everything checked that can be without its pointers (raw == NULL: a memory query)
 extern "C++" {
 namespace {

@@ -22,6 +22,7 @@
 #include "mvn_fuse.hpp"
 #include "mvn_psf.hpp"
 #include "mvn_beads.hpp"
+#include "mvn_detect.hpp"
 
 namespace mvn {
 namespace be {
@@ -185,6 +186,14 @@ void launch_beads_reduce(const BeadsParams& p, stream_t s);
 void launch_beads_remove_min(const BeadsParams& p, stream_t s);
 void launch_beads_score(const BeadsParams& p, bool u16, stream_t s);
 void beads_counters(long long out[2]);
+// a view's beads from its raw stack (mvn_detect.hpp; the raw stack is DEVICE memory here, u16: its element type): the
+// three blur passes - axis 2 from the raw stack into p.a, axis 1 into p.b, axis 0 into D = p.a[0] -; the extremum pass
+// over D, which appends to p.list behind p.count (cleared by the caller); and the fit of the p.nfound candidates of
+// the sorted list.  detect_counters: launches of the blur passes and of the extremum pass since process start
+void launch_detect_blur(const DetectParams& p, bool u16, stream_t s);
+void launch_detect_extrema(const DetectParams& p, stream_t s);
+void launch_detect_refine(const DetectParams& p, stream_t s);
+void detect_counters(long long out[2]);
 
 // stand-alone pointwise ops on flat arrays (legacy ABI: compute_quotient / compute_final_values)
 void launch_divide(const float* view, float* inout, size_t n, stream_t s);

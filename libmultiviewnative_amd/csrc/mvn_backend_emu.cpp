@@ -638,6 +638,36 @@ void launch_beads_score(const BeadsParams& p, bool u16, stream_t) {
     for (int t = 0; t < MVN_BEADS_WG; ++t) mvn_beads_score_fold_item(p, blk, t);
 }
 
+static std::atomic<long long> g_detect_blur_launches{0}, g_detect_extrema_launches{0};
+void detect_counters(long long out[2]) {
+  out[0] = g_detect_blur_launches.load();
+  out[1] = g_detect_extrema_launches.load();
+}
+
+void launch_detect_blur(const DetectParams& p, bool u16, stream_t) {
+  mvn_detect_check_blur(p);
+  g_detect_blur_launches += 3;
+  if (u16)
+    mvn_detect_rows_host<uint16_t>(p);
+  else
+    mvn_detect_rows_host<float>(p);
+  mvn_detect_lines_host<1>(p);
+  mvn_detect_lines_host<0>(p);
+}
+
+void launch_detect_extrema(const DetectParams& p, stream_t) {
+  mvn_detect_check_list(p);
+  ++g_detect_extrema_launches;
+  mvn_detect_extrema_host(p);
+}
+
+void launch_detect_refine(const DetectParams& p, stream_t) {
+  mvn_detect_check_list(p);
+  if (p.nfound < 1 || p.nfound > p.list_cap || !p.pos || !p.val || !p.vox)
+    throw std::invalid_argument("mvn: detect: nothing to refine");
+  mvn_detect_refine_host(p);
+}
+
 static std::atomic<long> g_tv_launches{0};
 long tv_launch_count() { return g_tv_launches.load(); }
 void launch_tv(const TvParams& p0, stream_t) {

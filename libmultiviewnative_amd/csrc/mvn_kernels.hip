@@ -310,6 +310,29 @@ __global__ __launch_bounds__(MVN_BEADS_WG) void k_beads_score_fold(const BeadsPa
   mvn_beads_score_fold_item(p, (long)blockIdx.x, (int)threadIdx.x);
 }
 
+// a view's beads from its raw stack (mvn_detect.hpp): the blur along axis 2 from the raw stack, along axis 1 and axis 0
+// (which writes D), the extrema of D, and the fit of the sorted candidates
+template <typename T>
+__global__ __launch_bounds__(MVN_DETECT_WG) void k_detect_rows(const DetectParams p) {
+  __shared__ float lds[MVN_DETECT_ROWS_LDS];
+  mvn_detect_rows_body<T>(p, (long)blockIdx.x, lds, (int)threadIdx.x, MVN_DETECT_WG);
+}
+
+template <int AXIS>
+__global__ __launch_bounds__(MVN_DETECT_WG) void k_detect_lines(const DetectParams p) {
+  __shared__ float lds[MVN_DETECT_LINES_LDS];
+  mvn_detect_lines_body<AXIS, 1>(p, (long)blockIdx.x, lds, (int)threadIdx.x, MVN_DETECT_WG);
+}
+
+__global__ __launch_bounds__(MVN_DETECT_WG) void k_detect_extrema(const DetectParams p) {
+  __shared__ float lds[MVN_DETECT_EXTREMA_LDS];
+  mvn_detect_extrema_body(p, (long)blockIdx.x, lds, (int)threadIdx.x, MVN_DETECT_WG);
+}
+
+__global__ __launch_bounds__(MVN_DETECT_WG) void k_detect_refine(const DetectParams p) {
+  mvn_detect_refine_item(p, (long)blockIdx.x, (int)threadIdx.x);
+}
+
 // vector extrapolation between sweeps (mvn_extrapolate.hpp): two streaming passes and the reduction between them
 template <int W>
 __global__ __launch_bounds__(MVN_ACCEL_WG) void k_accel_a(const AccelParams p) {
@@ -1088,6 +1111,44 @@ void launch_beads_score(const BeadsParams& p, bool u16, stream_t s) {
   HIP_CHECK(hipGetLastError());
   const long folds = ((long)p.nbeads + MVN_BEADS_WG - 1) / MVN_BEADS_WG;
   hipLaunchKernelGGL(k_beads_score_fold, dim3(psf_grid(folds)), dim3(MVN_BEADS_WG), 0, hs(s), p);
+  HIP_CHECK(hipGetLastError());
+}
+
+static std::atomic<long long> g_detect_blur_launches{0}, g_detect_extrema_launches{0};
+void detect_counters(long long out[2]) {
+  out[0] = g_detect_blur_launches.load();
+  out[1] = g_detect_extrema_launches.load();
+}
+
+void launch_detect_blur(const DetectParams& p, bool u16, stream_t s) {
+  mvn_detect_check_blur(p);
+  const unsigned rows = psf_grid(mvn_detect_rows_blocks(p));
+  const unsigned cols = psf_grid(mvn_detect_lines_blocks(p, 1)), planes = psf_grid(mvn_detect_lines_blocks(p, 0));
+  g_detect_blur_launches += 3;
+  if (u16)
+    hipLaunchKernelGGL(k_detect_rows<uint16_t>, dim3(rows), dim3(MVN_DETECT_WG), 0, hs(s), p);
+  else
+    hipLaunchKernelGGL(k_detect_rows<float>, dim3(rows), dim3(MVN_DETECT_WG), 0, hs(s), p);
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_detect_lines<1>, dim3(cols), dim3(MVN_DETECT_WG), 0, hs(s), p);
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_detect_lines<0>, dim3(planes), dim3(MVN_DETECT_WG), 0, hs(s), p);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_detect_extrema(const DetectParams& p, stream_t s) {
+  mvn_detect_check_list(p);
+  ++g_detect_extrema_launches;
+  hipLaunchKernelGGL(k_detect_extrema, dim3(psf_grid(mvn_detect_extrema_blocks(p))), dim3(MVN_DETECT_WG), 0, hs(s), p);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_detect_refine(const DetectParams& p, stream_t s) {
+  mvn_detect_check_list(p);
+  if (p.nfound < 1 || p.nfound > p.list_cap || !p.pos || !p.val || !p.vox)
+    throw std::invalid_argument("mvn: detect: nothing to refine");
+  hipLaunchKernelGGL(k_detect_refine, dim3(psf_grid(mvn_detect_ceil((long)p.nfound, MVN_DETECT_WG))),
+                     dim3(MVN_DETECT_WG), 0, hs(s), p);
   HIP_CHECK(hipGetLastError());
 }
 

@@ -12,8 +12,8 @@ import os
 
 import numpy as np
 
-from .abi import (MVN_DEVICE, CallDesc, StackDesc, ViewData, ViewGeometry, Workspace, c_float_p, c_int_p, describe_stack,
-                  fptr, iptr, view_geometry)
+from .abi import (MVN_DEVICE, CallDesc, DetectParams, StackDesc, ViewData, ViewGeometry, Workspace, c_float_p, c_int_p,
+                  describe_stack, detect_params, fptr, iptr, view_geometry)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(_HERE, "lib")
@@ -59,7 +59,11 @@ ENGINE_ABI_SYMBOLS = [
     "mvn_psf_extents", "mvn_derive_kernels", "mvn_set_kernel_derivation", "mvn_get_kernel_derivation",
     "mvn_derive_counters", "mvn_derive_time",
     "mvn_extract_psf", "mvn_extract_memory", "mvn_extract_counters", "mvn_extract_time",
+    "mvn_detect_beads", "mvn_detect_taps", "mvn_detect_dog", "mvn_detect_memory", "mvn_detect_counters",
+    "mvn_detect_time",
 ]
+DETECT_MINIMA = 1       # MVN_DETECT_MINIMA
+DETECT_MAX_RADIUS = 30  # MVN_DETECT_MAX_RADIUS
 BEADS_REMOVE_MIN = 1  # MVN_BEADS_REMOVE_MIN
 BEADS_GROUP = 32      # MVN_BEADS_GROUP
 PSF_TYPES = {"independent": 0, "efficient_bayesian": 1, "optimization_1": 2, "optimization_2": 3}
@@ -231,6 +235,14 @@ class Binding:
         l.mvn_extract_memory.argtypes = [C.POINTER(StackDesc), i3, C.c_int, i3, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
         l.mvn_extract_counters.argtypes = [C.POINTER(C.c_longlong)]
         l.mvn_extract_time.argtypes = [C.c_int, C.c_int, i3, C.c_int, i3, C.c_int, C.POINTER(C.c_float)]
+        l.mvn_detect_beads.argtypes = [C.c_int, C.c_void_p, C.POINTER(StackDesc), i3, C.POINTER(DetectParams), C.c_int,
+                                       C.POINTER(C.c_int), C.POINTER(C.c_double), c_float_p, C.POINTER(C.c_int),
+                                       C.c_void_p]
+        l.mvn_detect_taps.argtypes = [C.c_double, c_float_p, C.c_int, C.POINTER(C.c_int)]
+        l.mvn_detect_dog.argtypes = [C.c_int, C.c_void_p, C.POINTER(StackDesc), i3, C.POINTER(DetectParams), c_float_p]
+        l.mvn_detect_memory.argtypes = [C.POINTER(StackDesc), i3, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
+        l.mvn_detect_counters.argtypes = [C.POINTER(C.c_longlong)]
+        l.mvn_detect_time.argtypes = [C.c_int, C.c_int, i3, C.POINTER(DetectParams), C.c_int, C.POINTER(C.c_float)]
         l.mvn_tv_launch_count.restype = C.c_long
         l.mvn_tv_launch_count.argtypes = []
         l.mvn_engine_compute_delta.argtypes = [C.c_void_p, C.c_double, C.c_float]
@@ -738,6 +750,70 @@ class Binding:
         ms = (C.c_float * 3)(0, 0, 0)
         self.check(self.l.mvn_extract_time(int(device), int(bool(u16)), _dims(src_shape), int(num_beads),
                                            _dims(psf_shape), int(reps), ms))
+        return float(ms[0]), float(ms[1]), float(ms[2])
+
+    # ---- bead detection (mvn_detect_beads) --------------------------------------------------
+    def detect_beads(self, raw, sigma1, sigma2, threshold, minima=False, capacity=4096, device=None,
+                     int16_is_uint16=False, as_device=False):
+        """mvn_detect_beads: the beads of ONE view's raw stack `raw` (numpy array or torch tensor, float32 or uint16,
+        host or device) - the strict 26-neighbour maxima (minima=True: minima) above `threshold` of the difference of
+        its Gaussian blurs with sigma1 and sigma2 (one value or (z, y, x), raw voxels), in raster order, each with a
+        quadratic sub-voxel fit.  Returns (positions (N, 3) float64 as extract_psf takes them, values (N,) float32,
+        voxels (N, 3) int32).  More than `capacity` candidates raise MvnError; the message states their number."""
+        ptr, desc, shape, dev = describe_stack(raw, int16_is_uint16)
+        if as_device:
+            desc.location = MVN_DEVICE
+        prm = detect_params(sigma1, sigma2, threshold, DETECT_MINIMA if minima else 0)
+        n = C.c_int(-1)
+        pos = np.full((int(capacity), 3), np.nan, np.float64)
+        val = np.full(int(capacity), np.nan, np.float32)
+        vox = np.full((int(capacity), 3), -1, np.int32)
+        stream = _caller_stream([raw])
+        self.check(self.l.mvn_detect_beads(int(device if device is not None else (dev if dev is not None else -1)),
+                                           C.c_void_p(ptr), C.byref(desc), _dims(shape), C.byref(prm), int(capacity),
+                                           C.byref(n), pos.ctypes.data_as(C.POINTER(C.c_double)), fptr(val), iptr(vox),
+                                           C.c_void_p(stream)))
+        return pos[:n.value].copy(), val[:n.value].copy(), vox[:n.value].copy()
+
+    def detect_taps(self, sigma):
+        """mvn_detect_taps: the 2 R + 1 float32 taps of one sigma, R = ceil(3 sigma)."""
+        taps = np.zeros(2 * DETECT_MAX_RADIUS + 1, np.float32)
+        r = C.c_int(-1)
+        self.check(self.l.mvn_detect_taps(float(sigma), fptr(taps), len(taps), C.byref(r)))
+        return taps[:2 * r.value + 1].copy()
+
+    def detect_dog(self, raw, sigma1, sigma2, device=None, int16_is_uint16=False, as_device=False):
+        """mvn_detect_dog (test utility): the difference of the two blurs as a dense float32 array."""
+        ptr, desc, shape, dev = describe_stack(raw, int16_is_uint16)
+        if as_device:
+            desc.location = MVN_DEVICE
+        prm = detect_params(sigma1, sigma2, 0.0)
+        out = np.full(shape, np.nan, np.float32)
+        self.check(self.l.mvn_detect_dog(int(device if device is not None else (dev if dev is not None else -1)),
+                                         C.c_void_p(ptr), C.byref(desc), _dims(shape), C.byref(prm), fptr(out)))
+        return out
+
+    def detect_memory(self, raw, capacity, device=0, int16_is_uint16=False, as_device=False):
+        """mvn_detect_memory: the bytes detect_beads would allocate on the device for this stack and capacity."""
+        ptr, desc, shape, dev = describe_stack(raw, int16_is_uint16)
+        if as_device:
+            desc.location = MVN_DEVICE
+        need = C.c_size_t(0)
+        self.check(self.l.mvn_detect_memory(C.byref(desc), _dims(shape), int(capacity), int(device), C.byref(need)))
+        return need.value
+
+    def detect_counters(self):
+        """mvn_detect_counters: (launches of the blur passes, launches of the extremum pass, detections completed)."""
+        out = (C.c_longlong * 3)(0, 0, 0)
+        self.check(self.l.mvn_detect_counters(out))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def detect_time(self, src_shape, sigma1, sigma2, threshold, u16=True, reps=3, device=0):
+        """mvn_detect_time: (ms per detection on a resident stack - all its device work, ms for its blur passes alone,
+        ms per plain copy of one float32 volume)."""
+        ms = (C.c_float * 3)(0, 0, 0)
+        prm = detect_params(sigma1, sigma2, threshold)
+        self.check(self.l.mvn_detect_time(int(device), int(bool(u16)), _dims(src_shape), C.byref(prm), int(reps), ms))
         return float(ms[0]), float(ms[1]), float(ms[2])
 
     def resample_call(self, psi, raws, geoms, kernels1, kernels2, lambda_, min_value, iterations, weights=None,
