@@ -438,8 +438,8 @@ MVN_API int mvn_extract_time(int device, int u16, const int src_dims[3], int num
  * (at most 2^20; the list is not sorted here); ms[1] = the three blur passes alone; ms[2] = a plain copy of one float32
  * volume of src_dims.  out[0] moves by 3 + 6 (reps + 1), out[1] by 1 + (reps + 1), out[2] does not move.
  * Out of scope: a scale-space search over several sigmas; an iterative re-localisation that moves to a neighbouring
- * voxel; intensity normalisation of the raw stack; several views in one call; outputs in device memory; matching the
- * detections across views; a mode of mvn_set_kernel_derivation that detects by itself. */
+ * voxel; intensity normalisation of the raw stack; several views in one call; outputs in device memory; a mode of
+ * mvn_set_kernel_derivation that detects by itself.  Matching the detections across views is mvn_register_beads. */
 enum { MVN_DETECT_MINIMA = 1 }; /* flags */
 #define MVN_DETECT_MAX_RADIUS 30
 typedef struct mvn_detect_params {
@@ -458,6 +458,122 @@ MVN_API int mvn_detect_memory(const mvn_stack_desc* raw_desc, const int src_dims
 MVN_API int mvn_detect_counters(long long out[3]);
 MVN_API int mvn_detect_time(int device, int u16, const int src_dims[3], const mvn_detect_params* prm, int reps,
                             float* ms);
+/* ---- bead registration: the matrix between two views from their beads ------------------------------------------------------
+ * mvn_register_beads takes the beads of two views, A and B, as mvn_detect_beads returns them, and finds on the device
+ * the affine matrix that maps an index of A to an index of B: geometric-descriptor matching of the two sets, RANSAC
+ * over affine models of four pairs, and a least-squares refit.  It produces the one input of the chain that no other
+ * call does, so the chain is raw stacks -> mvn_detect_beads -> mvn_register_beads -> mvn_view_geometry ->
+ * mvn_extract_psf -> mvn_derive_kernels -> mvn_deconvolve_resampled.
+ *
+ * Inputs.  `a` and `b`: num_a x 3 and num_b x 3 doubles (z, y, x) in HOST memory, the layout of mvn_detect_beads'
+ * positions_out; both counts in 5 .. MVN_REGISTER_MAX_BEADS; every coordinate finite.  prm: see the struct.
+ * Outputs, HOST memory.  matrix_out: row-major 3 x 4, M, with b ~ M (a; 1).  With the block frame set to A's frame
+ * shifted by the block origin o (block voxel x <-> index x + o of A), B's mvn_view_geometry matrix is M composed with
+ * that shift - (L | L o + t) for M = (L | t) - and A's own matrix is the shift alone, (I | o).  *num_candidates: the
+ * candidates of step 4.  *num_inliers: the inliers of the result.  pairs_out: NULL, or room for min(num_a, num_b) x 2
+ * ints, receives the inlier pairs (i, j) in ascending i.  errors_out: NULL, or 2 doubles, the mean and the maximum
+ * residual of the inliers in voxels of B.
+ * No model is no error: the call returns 0, writes *num_candidates, sets *num_inliers = 0 and leaves the matrix, the
+ * pairs and the errors untouched.
+ *
+ * Arithmetic (normative).  Every float32 and double operation is rounded once, nothing is contracted into a fused
+ * multiply-add.
+ *   1 prior       under MVN_REGISTER_PRIOR, T = prm->prior, on the host in double: a'_ik = ((T_k0 z + T_k1 y) + T_k2 x) +
+ *                 T_k3 for a_i = (z, y, x); otherwise a' = a.  Steps 2 and 3 of A use a'; steps 5 to 7 use a
+ *   2 neighbours  within one set (a', or b): D(i, j) = (dz dz + dy dy) + dx dx in double with d = p_j - p_i.  The
+ *                 MVN_REGISTER_NEIGHBOURS = 4 nearest j != i (the index is excluded, not a zero distance), ordered by
+ *                 (D, j) ascending: n_0 .. n_3.  mvn_register_neighbours returns them
+ *   3 descriptors four per bead, of the neighbour triples (0,1,2), (0,1,3), (0,2,3), (1,2,3) in that order; each is the 9
+ *                 values (float)(p_n - p_i), neighbour-major, z y x inside a neighbour: translation invariant.  Rotation
+ *                 is the prior's job
+ *   4 match       dist(u, v) = ((e_0 e_0 + e_1 e_1) + ...) + e_8 e_8 with e = u - v, in float32, started from the first
+ *                 product; d(i, j) = the minimum over the 16 descriptor pairs of bead i of A and bead j of B (a NaN is
+ *                 never a minimum).  For each i: j1 = the j of least d, the lower j on a tie, d1 = that distance; d2 =
+ *                 the least d over j != j1.  i is a candidate iff d1 * ratio < d2, a float32 product and a strict
+ *                 comparison: a lattice (d1 = d2 = 0) yields none.  A j claimed by more than one such i drops all of its
+ *                 candidates.  Candidates (i, j1) are kept in ascending i; nC is their number.  nC < 4: no model.
+ *                 mvn_register_candidates returns them with (d1, d2) per pair
+ *   5 samples     mix(z): z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31, on
+ *                 64-bit wrap-around arithmetic.  Draw q of hypothesis h over a range of size n:
+ *                 u = mix(seed + 0x9E3779B97F4A7C15 * (16 h + q + 1)), r = ((u >> 32) * n) >> 32.  Hypothesis h takes
+ *                 four distinct candidates by draws q = 0..3 over ranges nC - q; after each draw the earlier picks are
+ *                 walked in ascending order and r is incremented for every pick <= r.  mvn_register_sample returns them
+ *   6 hypothesis  in double; the four samples are (a_m, b_m), m = 0..3.  E has the columns a_1 - a_0, a_2 - a_0, a_3 - a_0
+ *                 (E_kc = a_(c+1)k - a_0k) and F likewise from b.  The cofactors of E, each a difference of two products:
+ *                   C00 = E11 E22 - E12 E21   C01 = E12 E20 - E10 E22   C02 = E10 E21 - E11 E20
+ *                   C10 = E02 E21 - E01 E22   C11 = E00 E22 - E02 E20   C12 = E01 E20 - E00 E21
+ *                   C20 = E01 E12 - E02 E11   C21 = E02 E10 - E00 E12   C22 = E00 E11 - E01 E10
+ *                 det = (E00 C00 + E01 C01) + E02 C02;  L = (F adj E) / det:
+ *                 L_kj = ((F_k0 C_j0 + F_k1 C_j1) + F_k2 C_j2) / det;
+ *                 t_k = b_0k - ((L_k0 a_00 + L_k1 a_01) + L_k2 a_02).
+ *                 The hypothesis scores 0 if det is zero or not finite or any entry of L or t is not finite; otherwise
+ *                 its score is the number of candidates (a, b) with (r_0 r_0 + r_1 r_1) + r_2 r_2 <= max_error *
+ *                 max_error, r_k = (((L_k0 a_0 + L_k1 a_1) + L_k2 a_2) + t_k) - b_k.  The best hypothesis has the
+ *                 highest score, the lowest h on a tie; a best score < min_inliers: no model
+ *   7 refit       on the host in double.  I_0 = the best hypothesis' inliers.  For r = 1 .. MVN_REGISTER_REFITS = 10, over
+ *                 I_(r-1) in ascending candidate order: the centroids c_a, c_b (each coordinate summed from the first
+ *                 element, then divided by the count); S_aa_kl = the sum of (a_k - c_ak)(a_l - c_al) and S_ba_kl = the
+ *                 sum of (b_k - c_bk)(a_l - c_al), each started from the first product; L = (S_ba adj S_aa) / det S_aa
+ *                 in the cofactor form of step 6 (E = S_aa, F = S_ba); t_k = c_bk - ((L_k0 c_a0 + L_k1 c_a1) + L_k2 c_a2).
+ *                 A det that is zero or not finite, or a non-finite entry: no model.  I_r = the inliers of step 6's
+ *                 rule under this model; |I_r| < min_inliers: no model; stop when I_r == I_(r-1).  The result is the last
+ *                 model, M = (L | t), and the last I_r; the errors are the mean (summed in order from the first, then
+ *                 divided by the count) and the maximum of sqrt of the inliers' squared residuals under that model
+ *
+ * Errors.  The call blocks, checks everything before it touches anything and writes the outputs last.  Every error
+ * returns < 0 with its message in mvn_last_error() and leaves every output untouched: a NULL a, b, prm, matrix_out,
+ * num_candidates or num_inliers; a count out of range; a non-finite coordinate, or a non-finite prior entry under the
+ * flag; a ratio that is not finite or below 1; a max_error that is not finite or not positive; hypotheses outside
+ * 1 .. MVN_REGISTER_MAX_HYPOTHESES; min_inliers < 4; an unknown flag bit; a bad device.  `stream` is accepted for
+ * symmetry with the other calls; the inputs are host memory, so nothing is waited for.
+ *
+ * mvn_register_neighbours (test utility): step 2 on one set p of n points, idx_out n x 4 ints.
+ * mvn_register_candidates (test utility): steps 1 to 4; *num candidates into pairs_out, min(num_a, num_b) x 2 ints,
+ * and d_out, min(num_a, num_b) x 2 floats (d1, d2); it reads prm's prior, flags and ratio and checks all of prm.
+ * mvn_register_sample: the sample of step 5, host only; n >= 4, 0 <= h < MVN_REGISTER_MAX_HYPOTHESES.
+ * mvn_register_memory: the device bytes mvn_register_beads allocates, allocating nothing.  With n = num_a + num_b,
+ * tiles = ceil(num_b / 64), c = min(tiles, ceil(1024 / ceil(num_a / 256))), chunk = 64 ceil(tiles / c) beads of B and
+ * chunks = ceil(num_b / chunk):
+ *   184 n                     per bead its position (24), neighbours (16) and descriptors (144)
+ *   12 num_a (chunks + 1)     (d1, j1, d2) per bead of A and chunk, and folded
+ *   48 min(num_a, num_b)      the candidate records (a, b)
+ *   8                         the best (score, h)
+ * `hypotheses` is checked and does not enter: a hypothesis lives in registers.
+ * mvn_register_counters, since process start: out[0] = launches of the match pass, out[1] = launches of the RANSAC
+ * pass, out[2] = registrations completed (mvn_register_beads calls that returned 0, no model included).  A call with
+ * nC < 4 launches no RANSAC pass.
+ * mvn_register_time (test and bench utility): on reproducible synthetic sets (num_a points in a box, B = the first
+ * num_b of them under a small affine map, cyclically when num_b > num_a), `reps` repetitions between two stream events
+ * behind one that warms up: ms[0] = the neighbour and descriptor pass of both sets; ms[1] = the match pass and its
+ * fold; ms[2] = the RANSAC pass of `hypotheses` hypotheses over min(num_a, num_b) candidate records (pair i with i).
+ * out[0] and out[1] move by reps + 1 each, out[2] does not move.
+ * Out of scope: a global optimisation over more than two views; rotation-invariant descriptors; rigid or
+ * translation-only models; bead lists in device memory; a mode of the resampled call that registers by itself;
+ * anisotropy calibration (the caller composes it into the prior). */
+enum { MVN_REGISTER_PRIOR = 1 }; /* flags */
+#define MVN_REGISTER_NEIGHBOURS 4 /* part of the arithmetic */
+#define MVN_REGISTER_REFITS 10    /* part of the arithmetic */
+#define MVN_REGISTER_MAX_BEADS 65536
+#define MVN_REGISTER_MAX_HYPOTHESES (1 << 24)
+typedef struct mvn_register_params {
+  double prior[12];        /* row-major 3 x 4, read only under MVN_REGISTER_PRIOR */
+  double max_error;        /* inlier bound, in voxels of B; finite, > 0 */
+  float ratio;             /* finite, >= 1 */
+  int hypotheses;          /* 1 .. MVN_REGISTER_MAX_HYPOTHESES */
+  int min_inliers;         /* >= 4 */
+  int flags;
+  unsigned long long seed;
+} mvn_register_params;
+MVN_API int mvn_register_beads(int device, const double* a, int num_a, const double* b, int num_b,
+                               const mvn_register_params* prm, double matrix_out[12], int* num_candidates,
+                               int* num_inliers, int* pairs_out, double* errors_out, void* stream);
+MVN_API int mvn_register_neighbours(int device, const double* p, int n, int* idx_out);
+MVN_API int mvn_register_candidates(int device, const double* a, int num_a, const double* b, int num_b,
+                                    const mvn_register_params* prm, int* num, int* pairs_out, float* d_out);
+MVN_API int mvn_register_sample(unsigned long long seed, int h, int n, int out[4]);
+MVN_API int mvn_register_memory(int num_a, int num_b, int hypotheses, size_t* bytes);
+MVN_API int mvn_register_counters(long long out[3]);
+MVN_API int mvn_register_time(int device, int num_a, int num_b, int hypotheses, int reps, float* ms);
 /* out[0] = divide passes launched on a uint16 image, out[1] = ingest passes that wrote a uint16 volume, since process start */
 MVN_API int mvn_image_storage_counters(long long out[2]);
 /* Padding policy of inplace_gpu_deconvolve for the calls that follow (process-wide): "zero"

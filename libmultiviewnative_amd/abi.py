@@ -119,6 +119,36 @@ def detect_params(sigma1, sigma2, threshold, flags=0):
     return p
 
 
+class RegisterParams(C.Structure):
+    """mvn_register_params: the prior, the inlier bound, the ratio, the hypotheses, the flags and the seed of
+    mvn_register_beads."""
+    _fields_ = [
+        ("prior", C.c_double * 12),
+        ("max_error", C.c_double),
+        ("ratio", C.c_float),
+        ("hypotheses", C.c_int),
+        ("min_inliers", C.c_int),
+        ("flags", C.c_int),
+        ("seed", C.c_ulonglong),
+    ]
+
+
+assert C.sizeof(RegisterParams) == 128 and RegisterParams.ratio.offset == 104 and RegisterParams.seed.offset == 120
+
+
+def register_params(max_error, ratio=3.0, hypotheses=1000, min_inliers=4, prior=None, seed=0, flags=None):
+    """A RegisterParams; a `prior` (3 x 4 or 12 elements) sets MVN_REGISTER_PRIOR unless `flags` is given."""
+    p = RegisterParams()
+    if prior is not None:
+        m = np.asarray(prior, dtype=np.float64).reshape(12)
+        for i in range(12):
+            p.prior[i] = float(m[i])
+    p.max_error, p.ratio, p.hypotheses, p.min_inliers = float(max_error), float(ratio), int(hypotheses), int(min_inliers)
+    p.flags = int(flags) if flags is not None else (1 if prior is not None else 0)
+    p.seed = int(seed)
+    return p
+
+
 def _is_tensor(a):
     # (torch is never imported here: an object that is not a numpy array and has these is taken for a tensor)
     return not isinstance(a, np.ndarray) and hasattr(a, "data_ptr") and hasattr(a, "stride")

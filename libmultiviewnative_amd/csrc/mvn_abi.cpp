@@ -2490,6 +2490,427 @@ int mvn_detect_time(int device, int u16, const int src_dims[3], const mvn_detect
   });
 }
 
+// ---- bead registration (mvn_register.hpp; the arithmetic is stated at mvn_register_beads in include/mvn_engine_api.h) ----
+extern "C++" {
+namespace {
+static_assert(MVN_REGISTER_NEIGHBOURS == MVN_REG_NN, "the neighbours of the header are the passes'");
+static_assert(MVN_REGISTER_MAX_BEADS == MVN_REG_MAX_BEADS, "the largest set of the header is the passes'");
+static_assert(MVN_REGISTER_MAX_HYPOTHESES == MVN_REG_MAX_HYPOTHESES, "the hypotheses of the header are the passes'");
+
+void register_check_count(int n, const char* name) {
+  if (n < MVN_REG_NN + 1 || n > MVN_REGISTER_MAX_BEADS)
+    throw std::invalid_argument(std::string(name) + " must be in 5.." + std::to_string(MVN_REGISTER_MAX_BEADS));
+}
+
+void register_check_points(const double* p, int n, const char* name) {
+  if (!p) throw std::invalid_argument(std::string("null ") + name);
+  register_check_count(n, (std::string("num_") + name).c_str());
+  for (size_t i = 0; i < 3 * (size_t)n; ++i)
+    if (!std::isfinite(p[i])) throw std::invalid_argument(std::string("a non-finite coordinate in ") + name);
+}
+
+void register_check_params(const mvn_register_params* prm) {
+  if (!prm) throw std::invalid_argument("null prm");
+  if (prm->flags & ~(int)MVN_REGISTER_PRIOR) throw std::invalid_argument("unknown flag bits " + std::to_string(prm->flags));
+  if (prm->flags & MVN_REGISTER_PRIOR)
+    for (int k = 0; k < 12; ++k)
+      if (!std::isfinite(prm->prior[k])) throw std::invalid_argument("a non-finite prior entry");
+  if (!(std::isfinite(prm->max_error) && prm->max_error > 0.0)) throw std::invalid_argument("max_error must be finite and > 0");
+  if (!(std::isfinite(prm->ratio) && prm->ratio >= 1.0f)) throw std::invalid_argument("ratio must be finite and >= 1");
+  if (prm->hypotheses < 1 || prm->hypotheses > MVN_REGISTER_MAX_HYPOTHESES)
+    throw std::invalid_argument("hypotheses must be in 1.." + std::to_string(MVN_REGISTER_MAX_HYPOTHESES));
+  if (prm->min_inliers < 4) throw std::invalid_argument("min_inliers must be >= 4");
+}
+
+// step 1: a' = T (a; 1) under the flag
+std::vector<double> register_prior(const double* a, int n, const mvn_register_params* prm) {
+  MVN_FP_EXACT
+  std::vector<double> out(a, a + 3 * (size_t)n);
+  if (!(prm->flags & MVN_REGISTER_PRIOR)) return out;
+  const double* T = prm->prior;
+  for (int i = 0; i < n; ++i) {
+    const double z = a[3 * (size_t)i], y = a[3 * (size_t)i + 1], x = a[3 * (size_t)i + 2];
+    for (int k = 0; k < 3; ++k) out[3 * (size_t)i + k] = ((T[4 * k] * z + T[4 * k + 1] * y) + T[4 * k + 2] * x) + T[4 * k + 3];
+  }
+  return out;
+}
+
+struct RegisterSizes {
+  int na, nb, chunk, chunks, cap;
+  RegisterSizes(int num_a, int num_b)
+      : na(num_a), nb(num_b), chunk(mvn_reg_chunk(num_a, num_b)), chunks(mvn_reg_chunks(num_b, chunk)),
+        cap(num_a < num_b ? num_a : num_b) {}
+  size_t n() const { return (size_t)na + (size_t)nb; }
+  size_t points_bytes() const { return n() * 3 * sizeof(double); }
+  size_t nn_bytes() const { return n() * MVN_REG_NN * sizeof(int); }
+  size_t desc_bytes() const { return n() * MVN_REG_DESC * sizeof(float); }
+  size_t match_bytes() const { return (size_t)na * ((size_t)chunks + 1) * (2 * sizeof(float) + sizeof(int)); }
+  size_t cand_bytes() const { return (size_t)cap * 6 * sizeof(double); }
+  size_t bytes() const {
+    return points_bytes() + nn_bytes() + desc_bytes() + match_bytes() + cand_bytes() + sizeof(unsigned long long);
+  }
+};
+
+struct RegisterCandidate {
+  int i, j;
+  float d1, d2;
+};
+
+// the device side of one registration: buffers and the launches in stream order.  A's points are a' (step 1)
+class Registration {
+ public:
+  Registration(int na, int nb)
+      : z_(na, nb),
+        points_(z_.points_bytes()),
+        nn_(z_.nn_bytes()),
+        desc_(z_.desc_bytes()),
+        match_(z_.match_bytes()),
+        cand_(z_.cand_bytes()),
+        best_(sizeof(unsigned long long)) {}
+
+  void upload(const double* a_prior, const double* b, be::stream_t s) const {
+    be::h2d(points_.get(), a_prior, (size_t)z_.na * 3 * sizeof(double), s);
+    be::h2d(points_.get() + 3 * (size_t)z_.na, b, (size_t)z_.nb * 3 * sizeof(double), s);
+  }
+  // steps 2 and 3 of set 0 (A) or 1 (B)
+  void neighbours(int set, be::stream_t s) const {
+    const size_t at = set ? (size_t)z_.na : 0;
+    RegParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.pts = points_.get() + 3 * at, p.n = set ? z_.nb : z_.na;
+    p.nn = nn_.get() + MVN_REG_NN * at, p.desc = desc_.get() + MVN_REG_DESC * at;
+    be::launch_register_neighbours(p, s);
+  }
+  void match(be::stream_t s) const { be::launch_register_match(match_params(), s); }
+  void download_neighbours(int set, int* out, be::stream_t s) const {
+    const size_t at = set ? (size_t)z_.na : 0;
+    be::d2h(out, nn_.get() + MVN_REG_NN * at, (size_t)(set ? z_.nb : z_.na) * MVN_REG_NN * sizeof(int), s);
+    be::stream_sync(s);
+  }
+  // step 4 behind the match pass: the ratio test and the uniqueness filter, on the host; blocks
+  std::vector<RegisterCandidate> candidates(float ratio, be::stream_t s) const {
+    MVN_FP_EXACT
+    const size_t na = (size_t)z_.na;
+    std::vector<float> d1(na), d2(na);
+    std::vector<int> j1(na);
+    const RegParams p = match_params();
+    be::d2h(d1.data(), p.d1, na * sizeof(float), s);
+    be::d2h(j1.data(), p.j1, na * sizeof(int), s);
+    be::d2h(d2.data(), p.d2, na * sizeof(float), s);
+    be::stream_sync(s);
+    std::vector<int> claims((size_t)z_.nb, 0);
+    std::vector<char> passes(na, 0);
+    for (size_t i = 0; i < na; ++i) {
+      const float scaled = d1[i] * ratio;
+      if (!(scaled < d2[i])) continue;
+      if (j1[i] < 0 || j1[i] >= z_.nb) throw std::runtime_error("mvn: register: a match outside B");
+      passes[i] = 1;
+      ++claims[(size_t)j1[i]];
+    }
+    std::vector<RegisterCandidate> out;
+    for (size_t i = 0; i < na; ++i)
+      if (passes[i] && claims[(size_t)j1[i]] == 1) out.push_back(RegisterCandidate{(int)i, j1[i], d1[i], d2[i]});
+    return out;
+  }
+  // step 6 over `nc` records of (a, b); returns the best key; blocks
+  unsigned long long ransac(const double* records, int nc, int hyps, unsigned long long seed, double maxerr2,
+                            be::stream_t s) const {
+    upload_records(records, nc, s);
+    launch_ransac(nc, hyps, seed, maxerr2, s);
+    unsigned long long key = 0;
+    be::d2h(&key, best_.get(), sizeof(key), s);
+    be::stream_sync(s);
+    return key;
+  }
+  void launch_ransac(int nc, int hyps, unsigned long long seed, double maxerr2, be::stream_t s) const {
+    if (nc > z_.cap) throw std::invalid_argument("mvn: register: more candidates than beads");
+    RegParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.cand = cand_.get(), p.nc = nc, p.hyps = hyps, p.seed = seed, p.maxerr2 = maxerr2, p.best = best_.get();
+    be::dzero(best_.get(), sizeof(unsigned long long), s);
+    be::launch_register_ransac(p, s);
+  }
+  void upload_records(const double* records, int nc, be::stream_t s) const {
+    be::h2d(cand_.get(), records, (size_t)nc * 6 * sizeof(double), s);
+  }
+  const RegisterSizes& sizes() const { return z_; }
+
+ private:
+  // the match pass and its fold: the chunks' records, then the folded ones, for each of d1, j1, d2
+  RegParams match_params() const {
+    RegParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.da = desc_.get(), p.db = desc_.get() + MVN_REG_DESC * (size_t)z_.na;
+    p.na = z_.na, p.nb = z_.nb, p.chunk = z_.chunk;
+    const size_t part = (size_t)z_.na * (size_t)z_.chunks;
+    p.pd1 = match_.get(), p.d1 = p.pd1 + part;
+    p.pj1 = (int*)(p.d1 + z_.na), p.j1 = p.pj1 + part;
+    p.pd2 = (float*)(p.j1 + z_.na), p.d2 = p.pd2 + part;
+    return p;
+  }
+
+  RegisterSizes z_;
+  be::DeviceBuffer<double> points_;  // a', then b
+  be::DeviceBuffer<int> nn_;
+  be::DeviceBuffer<float> desc_;
+  be::DeviceBuffer<float> match_;
+  be::DeviceBuffer<double> cand_;
+  be::DeviceBuffer<unsigned long long> best_;
+};
+
+// the candidates of step 4 as records (a, b) on the ORIGINAL a
+std::vector<double> register_records(const std::vector<RegisterCandidate>& c, const double* a, const double* b) {
+  std::vector<double> r(6 * c.size());
+  for (size_t m = 0; m < c.size(); ++m)
+    for (int k = 0; k < 3; ++k) {
+      r[6 * m + k] = a[3 * (size_t)c[m].i + k];
+      r[6 * m + 3 + k] = b[3 * (size_t)c[m].j + k];
+    }
+  return r;
+}
+
+std::vector<int> register_inliers(const std::vector<double>& rec, const double L[9], const double t[3], double maxerr2) {
+  std::vector<int> in;
+  for (size_t m = 0; m < rec.size() / 6; ++m)
+    if (mvn_reg_residual2(L, t, &rec[6 * m], &rec[6 * m + 3]) <= maxerr2) in.push_back((int)m);
+  return in;
+}
+
+// step 7 on the inliers `in` of the best hypothesis; false: no model
+bool register_refit(const std::vector<double>& rec, std::vector<int>& in, int min_inliers, double maxerr2, double L[9],
+                    double t[3]) {
+  MVN_FP_EXACT
+  for (int r = 1; r <= MVN_REGISTER_REFITS; ++r) {
+    double ca[3], cb[3];
+    for (int k = 0; k < 3; ++k) {
+      double sa = rec[6 * (size_t)in[0] + k], sb = rec[6 * (size_t)in[0] + 3 + k];
+      for (size_t m = 1; m < in.size(); ++m) sa = sa + rec[6 * (size_t)in[m] + k], sb = sb + rec[6 * (size_t)in[m] + 3 + k];
+      ca[k] = sa / (double)in.size(), cb[k] = sb / (double)in.size();
+    }
+    double Saa[9], Sba[9];
+    for (int k = 0; k < 3; ++k)
+      for (int l = 0; l < 3; ++l) {
+        double saa = 0.0, sba = 0.0;
+        for (size_t m = 0; m < in.size(); ++m) {
+          const double* q = &rec[6 * (size_t)in[m]];
+          const double al = q[l] - ca[l];
+          const double paa = (q[k] - ca[k]) * al, pba = (q[3 + k] - cb[k]) * al;
+          saa = m == 0 ? paa : saa + paa;
+          sba = m == 0 ? pba : sba + pba;
+        }
+        Saa[3 * k + l] = saa, Sba[3 * k + l] = sba;
+      }
+    if (!mvn_reg_solve(Saa, Sba, L) || !mvn_reg_offset(L, ca, cb, t)) return false;
+    std::vector<int> next = register_inliers(rec, L, t, maxerr2);
+    if ((int)next.size() < min_inliers) return false;
+    const bool same = next == in;
+    in.swap(next);
+    if (same) break;
+  }
+  return true;
+}
+
+// `body` with the device of a call on host lists picked, locked and current
+template <typename F>
+void on_register_device(int device, F&& body) {
+  const int dev = pick_device(device);
+  std::lock_guard<std::mutex> lk(device_mutex(dev));
+  be::set_device(dev);
+  body();
+}
+
+std::atomic<long long> g_registrations{0};
+}  // namespace
+}  // extern "C++"
+
+int mvn_register_beads(int device, const double* a, int num_a, const double* b, int num_b,
+                       const mvn_register_params* prm, double matrix_out[12], int* num_candidates, int* num_inliers,
+                       int* pairs_out, double* errors_out, void* stream) {
+  return guarded("mvn_register_beads", [&] {
+    MVN_FP_EXACT
+    (void)stream;  // (the lists are host memory: there is nothing to wait for)
+    if (!matrix_out || !num_candidates || !num_inliers) throw std::invalid_argument("null matrix_out, num_candidates or num_inliers");
+    register_check_points(a, num_a, "a");
+    register_check_points(b, num_b, "b");
+    register_check_params(prm);
+    on_register_device(device, [&] {
+      const std::vector<double> ap = register_prior(a, num_a, prm);
+      std::vector<RegisterCandidate> cand;
+      std::vector<double> rec;
+      std::vector<int> in;
+      double L[9], t[3];
+      bool model = false;
+      const double maxerr2 = prm->max_error * prm->max_error;
+      {
+        const Registration reg(num_a, num_b);
+        const be::Stream own = be::Stream::create();
+        const be::stream_t s = own.get();
+        reg.upload(ap.data(), b, s);
+        reg.neighbours(0, s);
+        reg.neighbours(1, s);
+        reg.match(s);
+        cand = reg.candidates(prm->ratio, s);
+        if (cand.size() >= 4) {
+          rec = register_records(cand, a, b);
+          const unsigned long long key = reg.ransac(rec.data(), (int)cand.size(), prm->hypotheses, prm->seed, maxerr2, s);
+          const int score = mvn_reg_key_score(key);
+          if (score >= prm->min_inliers) {
+            if (!mvn_reg_hypothesis(rec.data(), (int)cand.size(), prm->seed, mvn_reg_key_h(key), L, t))
+              throw std::runtime_error("mvn: register: the best hypothesis has no model on the host");
+            in = register_inliers(rec, L, t, maxerr2);
+            if ((int)in.size() != score) throw std::runtime_error("mvn: register: the host and the device disagree on a score");
+            model = register_refit(rec, in, prm->min_inliers, maxerr2, L, t);
+          }
+        }
+      }
+      *num_candidates = (int)cand.size();
+      if (!model) {
+        *num_inliers = 0;
+        ++g_registrations;
+        return;
+      }
+      double sum = 0.0, worst = 0.0;
+      for (size_t m = 0; m < in.size(); ++m) {
+        const double e = std::sqrt(mvn_reg_residual2(L, t, &rec[6 * (size_t)in[m]], &rec[6 * (size_t)in[m] + 3]));
+        sum = m == 0 ? e : sum + e;
+        worst = e > worst ? e : worst;
+      }
+      for (int k = 0; k < 3; ++k) {
+        for (int l = 0; l < 3; ++l) matrix_out[4 * k + l] = L[3 * k + l];
+        matrix_out[4 * k + 3] = t[k];
+      }
+      *num_inliers = (int)in.size();
+      if (pairs_out)
+        for (size_t m = 0; m < in.size(); ++m) pairs_out[2 * m] = cand[(size_t)in[m]].i, pairs_out[2 * m + 1] = cand[(size_t)in[m]].j;
+      if (errors_out) errors_out[0] = sum / (double)in.size(), errors_out[1] = worst;
+      ++g_registrations;
+    });
+  });
+}
+
+int mvn_register_neighbours(int device, const double* p, int n, int* idx_out) {
+  return guarded("mvn_register_neighbours", [&] {
+    if (!idx_out) throw std::invalid_argument("null idx_out");
+    register_check_points(p, n, "p");
+    on_register_device(device, [&] {
+      std::vector<int> h((size_t)n * MVN_REG_NN);
+      {
+        const Registration reg(n, n);
+        const be::Stream own = be::Stream::create();
+        const be::stream_t s = own.get();
+        reg.upload(p, p, s);
+        reg.neighbours(0, s);
+        reg.download_neighbours(0, h.data(), s);
+      }
+      std::memcpy(idx_out, h.data(), h.size() * sizeof(int));
+    });
+  });
+}
+
+int mvn_register_candidates(int device, const double* a, int num_a, const double* b, int num_b,
+                            const mvn_register_params* prm, int* num, int* pairs_out, float* d_out) {
+  return guarded("mvn_register_candidates", [&] {
+    if (!num || !pairs_out || !d_out) throw std::invalid_argument("null num, pairs_out or d_out");
+    register_check_points(a, num_a, "a");
+    register_check_points(b, num_b, "b");
+    register_check_params(prm);
+    on_register_device(device, [&] {
+      const std::vector<double> ap = register_prior(a, num_a, prm);
+      std::vector<RegisterCandidate> cand;
+      {
+        const Registration reg(num_a, num_b);
+        const be::Stream own = be::Stream::create();
+        const be::stream_t s = own.get();
+        reg.upload(ap.data(), b, s);
+        reg.neighbours(0, s);
+        reg.neighbours(1, s);
+        reg.match(s);
+        cand = reg.candidates(prm->ratio, s);
+      }
+      *num = (int)cand.size();
+      for (size_t m = 0; m < cand.size(); ++m) {
+        pairs_out[2 * m] = cand[m].i, pairs_out[2 * m + 1] = cand[m].j;
+        d_out[2 * m] = cand[m].d1, d_out[2 * m + 1] = cand[m].d2;
+      }
+    });
+  });
+}
+
+int mvn_register_sample(unsigned long long seed, int h, int n, int out[4]) {
+  return guarded("mvn_register_sample", [&] {
+    if (!out) throw std::invalid_argument("null out");
+    if (n < 4) throw std::invalid_argument("n must be >= 4");
+    if (h < 0 || h >= MVN_REGISTER_MAX_HYPOTHESES) throw std::invalid_argument("h out of range");
+    int s[4];
+    mvn_reg_sample(seed, (unsigned)h, n, s);
+    std::memcpy(out, s, sizeof(s));
+  });
+}
+
+int mvn_register_memory(int num_a, int num_b, int hypotheses, size_t* bytes) {
+  return guarded("mvn_register_memory", [&] {
+    if (!bytes) throw std::invalid_argument("null bytes");
+    register_check_count(num_a, "num_a");
+    register_check_count(num_b, "num_b");
+    if (hypotheses < 1 || hypotheses > MVN_REGISTER_MAX_HYPOTHESES)
+      throw std::invalid_argument("hypotheses must be in 1.." + std::to_string(MVN_REGISTER_MAX_HYPOTHESES));
+    *bytes = RegisterSizes(num_a, num_b).bytes();
+  });
+}
+
+int mvn_register_counters(long long out[3]) {
+  return guarded("mvn_register_counters", [&] {
+    if (!out) throw std::invalid_argument("null out");
+    be::register_counters(out);
+    out[2] = g_registrations.load();
+  });
+}
+
+// ms[0]: the neighbour and descriptor pass of both sets; ms[1]: the match pass and its fold; ms[2]: the RANSAC pass over
+// min(num_a, num_b) records (pair i with i); each per repetition over `reps` repetitions behind one that warms up
+int mvn_register_time(int device, int num_a, int num_b, int hypotheses, int reps, float* ms) {
+  return guarded("mvn_register_time", [&] {
+    if (!ms) throw std::invalid_argument("null ms");
+    if (reps < 1) throw std::invalid_argument("reps must be positive");
+    register_check_count(num_a, "num_a");
+    register_check_count(num_b, "num_b");
+    if (hypotheses < 1 || hypotheses > MVN_REGISTER_MAX_HYPOTHESES)
+      throw std::invalid_argument("hypotheses must be in 1.." + std::to_string(MVN_REGISTER_MAX_HYPOTHESES));
+    on_register_device(device, [&] {
+      // an LCG's points in a box of 100 x 1000 x 1000; B: the same under a small affine map
+      std::vector<double> a(3 * (size_t)num_a), b(3 * (size_t)num_b);
+      unsigned x = 2463534242u;
+      for (size_t i = 0; i < a.size(); ++i) {
+        x = x * 1664525u + 1013904223u;
+        a[i] = (double)(x >> 8) * (1.0 / 16777216.0) * (i % 3 == 0 ? 100.0 : 1000.0);
+      }
+      for (int j = 0; j < num_b; ++j) {
+        const double* q = &a[3 * (size_t)(j % num_a)];
+        b[3 * (size_t)j] = 1.01 * q[0] + 0.02 * q[1] + 1.5;
+        b[3 * (size_t)j + 1] = 0.99 * q[1] - 0.02 * q[0] - 2.0;
+        b[3 * (size_t)j + 2] = 1.005 * q[2] + 3.0;
+      }
+      const Registration reg(num_a, num_b);
+      const int nc = reg.sizes().cap;
+      std::vector<double> rec(6 * (size_t)nc);
+      for (int m = 0; m < nc; ++m)
+        for (int k = 0; k < 3; ++k) rec[6 * (size_t)m + k] = a[3 * (size_t)m + k], rec[6 * (size_t)m + 3 + k] = b[3 * (size_t)m + k];
+      const be::Stream own = be::Stream::create();
+      const be::stream_t s = own.get();
+      reg.upload(a.data(), b.data(), s);
+      reg.upload_records(rec.data(), nc, s);
+      be::stream_sync(s);
+      ms[0] = time_on_stream(s, reps, [&] {
+        reg.neighbours(0, s);
+        reg.neighbours(1, s);
+      });
+      ms[1] = time_on_stream(s, reps, [&] { reg.match(s); });
+      ms[2] = time_on_stream(s, reps, [&] { reg.launch_ransac(nc, hypotheses, 1ull, 0.25, s); });
+      be::stream_sync(s);
+    });
+  });
+}
+
 // what a fusion call is made of, everything checked that can be without its pointers (raw == NULL: a memory query)
 extern "C++" {
 namespace {

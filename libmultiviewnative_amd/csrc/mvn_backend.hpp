@@ -23,6 +23,7 @@
 #include "mvn_psf.hpp"
 #include "mvn_beads.hpp"
 #include "mvn_detect.hpp"
+#include "mvn_register.hpp"
 
 namespace mvn {
 namespace be {
@@ -194,6 +195,14 @@ void launch_detect_blur(const DetectParams& p, bool u16, stream_t s);
 void launch_detect_extrema(const DetectParams& p, stream_t s);
 void launch_detect_refine(const DetectParams& p, stream_t s);
 void detect_counters(long long out[2]);
+// two views' beads into the matrix between them (mvn_register.hpp): the neighbours and the descriptors of the set p.pts;
+// the match pass over (tiles of A) x (chunks of B) and its fold, one after the other; and the RANSAC pass, which folds
+// its best key into *p.best (cleared by the caller).  register_counters: launches of the match pass and of the RANSAC
+// pass since process start
+void launch_register_neighbours(const RegParams& p, stream_t s);
+void launch_register_match(const RegParams& p, stream_t s);
+void launch_register_ransac(const RegParams& p, stream_t s);
+void register_counters(long long out[2]);
 
 // stand-alone pointwise ops on flat arrays (legacy ABI: compute_quotient / compute_final_values)
 void launch_divide(const float* view, float* inout, size_t n, stream_t s);

@@ -668,6 +668,29 @@ void launch_detect_refine(const DetectParams& p, stream_t) {
   mvn_detect_refine_host(p);
 }
 
+static std::atomic<long long> g_register_match_launches{0}, g_register_ransac_launches{0};
+void register_counters(long long out[2]) {
+  out[0] = g_register_match_launches.load();
+  out[1] = g_register_ransac_launches.load();
+}
+
+void launch_register_neighbours(const RegParams& p, stream_t) {
+  mvn_reg_check_neighbours(p);
+  mvn_reg_neighbours_host(p);
+}
+
+void launch_register_match(const RegParams& p, stream_t) {
+  mvn_reg_check_match(p);
+  ++g_register_match_launches;
+  mvn_reg_match_host(p);
+}
+
+void launch_register_ransac(const RegParams& p, stream_t) {
+  mvn_reg_check_ransac(p);
+  ++g_register_ransac_launches;
+  mvn_reg_ransac_host(p);
+}
+
 static std::atomic<long> g_tv_launches{0};
 long tv_launch_count() { return g_tv_launches.load(); }
 void launch_tv(const TvParams& p0, stream_t) {

@@ -333,6 +333,28 @@ __global__ __launch_bounds__(MVN_DETECT_WG) void k_detect_refine(const DetectPar
   mvn_detect_refine_item(p, (long)blockIdx.x, (int)threadIdx.x);
 }
 
+// two views' beads into the matrix between them (mvn_register.hpp): brute-force scans, the scanned set broadcast from
+// the LDS
+__global__ __launch_bounds__(MVN_REG_WG) void k_reg_neighbours(const RegParams p) {
+  __shared__ double lds[3 * MVN_REG_NTILE];
+  mvn_reg_neighbours_body<1>(p, (long)blockIdx.x, lds, (int)threadIdx.x, MVN_REG_WG);
+}
+
+__global__ __launch_bounds__(MVN_REG_WG) void k_reg_match(const RegParams p) {
+  __shared__ float lds[MVN_REG_MTILE * MVN_REG_DESC];
+  mvn_reg_match_body<1>(p, (long)blockIdx.x, lds, (int)threadIdx.x, MVN_REG_WG);
+}
+
+__global__ __launch_bounds__(MVN_REG_WG) void k_reg_match_fold(const RegParams p) {
+  mvn_reg_fold_item(p, (long)blockIdx.x, (int)threadIdx.x);
+}
+
+__global__ __launch_bounds__(MVN_REG_WG) void k_reg_ransac(const RegParams p) {
+  __shared__ double lds[6 * MVN_REG_RTILE];
+  __shared__ unsigned long long keys[MVN_REG_WG];
+  mvn_reg_ransac_body<1>(p, (long)blockIdx.x, lds, keys, (int)threadIdx.x, MVN_REG_WG);
+}
+
 // vector extrapolation between sweeps (mvn_extrapolate.hpp): two streaming passes and the reduction between them
 template <int W>
 __global__ __launch_bounds__(MVN_ACCEL_WG) void k_accel_a(const AccelParams p) {
@@ -1149,6 +1171,34 @@ void launch_detect_refine(const DetectParams& p, stream_t s) {
     throw std::invalid_argument("mvn: detect: nothing to refine");
   hipLaunchKernelGGL(k_detect_refine, dim3(psf_grid(mvn_detect_ceil((long)p.nfound, MVN_DETECT_WG))),
                      dim3(MVN_DETECT_WG), 0, hs(s), p);
+  HIP_CHECK(hipGetLastError());
+}
+
+static std::atomic<long long> g_register_match_launches{0}, g_register_ransac_launches{0};
+void register_counters(long long out[2]) {
+  out[0] = g_register_match_launches.load();
+  out[1] = g_register_ransac_launches.load();
+}
+
+void launch_register_neighbours(const RegParams& p, stream_t s) {
+  mvn_reg_check_neighbours(p);
+  hipLaunchKernelGGL(k_reg_neighbours, dim3(psf_grid(mvn_reg_neighbours_blocks(p))), dim3(MVN_REG_WG), 0, hs(s), p);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_register_match(const RegParams& p, stream_t s) {
+  mvn_reg_check_match(p);
+  ++g_register_match_launches;
+  hipLaunchKernelGGL(k_reg_match, dim3(psf_grid(mvn_reg_match_blocks(p))), dim3(MVN_REG_WG), 0, hs(s), p);
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_reg_match_fold, dim3(psf_grid(mvn_reg_fold_blocks(p))), dim3(MVN_REG_WG), 0, hs(s), p);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_register_ransac(const RegParams& p, stream_t s) {
+  mvn_reg_check_ransac(p);
+  ++g_register_ransac_launches;
+  hipLaunchKernelGGL(k_reg_ransac, dim3(psf_grid(mvn_reg_ransac_blocks(p))), dim3(MVN_REG_WG), 0, hs(s), p);
   HIP_CHECK(hipGetLastError());
 }
 

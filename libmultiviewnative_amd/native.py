@@ -12,8 +12,8 @@ import os
 
 import numpy as np
 
-from .abi import (MVN_DEVICE, CallDesc, DetectParams, StackDesc, ViewData, ViewGeometry, Workspace, c_float_p, c_int_p,
-                  describe_stack, detect_params, fptr, iptr, view_geometry)
+from .abi import (MVN_DEVICE, CallDesc, DetectParams, RegisterParams, StackDesc, ViewData, ViewGeometry, Workspace,
+                  c_float_p, c_int_p, describe_stack, detect_params, fptr, iptr, register_params, view_geometry)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(_HERE, "lib")
@@ -61,7 +61,14 @@ ENGINE_ABI_SYMBOLS = [
     "mvn_extract_psf", "mvn_extract_memory", "mvn_extract_counters", "mvn_extract_time",
     "mvn_detect_beads", "mvn_detect_taps", "mvn_detect_dog", "mvn_detect_memory", "mvn_detect_counters",
     "mvn_detect_time",
+    "mvn_register_beads", "mvn_register_neighbours", "mvn_register_candidates", "mvn_register_sample",
+    "mvn_register_memory", "mvn_register_counters", "mvn_register_time",
 ]
+REGISTER_PRIOR = 1                     # MVN_REGISTER_PRIOR
+REGISTER_NEIGHBOURS = 4                # MVN_REGISTER_NEIGHBOURS
+REGISTER_REFITS = 10                   # MVN_REGISTER_REFITS
+REGISTER_MAX_BEADS = 65536             # MVN_REGISTER_MAX_BEADS
+REGISTER_MAX_HYPOTHESES = 1 << 24      # MVN_REGISTER_MAX_HYPOTHESES
 DETECT_MINIMA = 1       # MVN_DETECT_MINIMA
 DETECT_MAX_RADIUS = 30  # MVN_DETECT_MAX_RADIUS
 BEADS_REMOVE_MIN = 1  # MVN_BEADS_REMOVE_MIN
@@ -243,6 +250,16 @@ class Binding:
         l.mvn_detect_memory.argtypes = [C.POINTER(StackDesc), i3, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
         l.mvn_detect_counters.argtypes = [C.POINTER(C.c_longlong)]
         l.mvn_detect_time.argtypes = [C.c_int, C.c_int, i3, C.POINTER(DetectParams), C.c_int, C.POINTER(C.c_float)]
+        d_p = C.POINTER(C.c_double)
+        l.mvn_register_beads.argtypes = [C.c_int, d_p, C.c_int, d_p, C.c_int, C.POINTER(RegisterParams), d_p,
+                                         C.POINTER(C.c_int), C.POINTER(C.c_int), c_int_p, d_p, C.c_void_p]
+        l.mvn_register_neighbours.argtypes = [C.c_int, d_p, C.c_int, c_int_p]
+        l.mvn_register_candidates.argtypes = [C.c_int, d_p, C.c_int, d_p, C.c_int, C.POINTER(RegisterParams),
+                                              C.POINTER(C.c_int), c_int_p, c_float_p]
+        l.mvn_register_sample.argtypes = [C.c_ulonglong, C.c_int, C.c_int, c_int_p]
+        l.mvn_register_memory.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
+        l.mvn_register_counters.argtypes = [C.POINTER(C.c_longlong)]
+        l.mvn_register_time.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
         l.mvn_tv_launch_count.restype = C.c_long
         l.mvn_tv_launch_count.argtypes = []
         l.mvn_engine_compute_delta.argtypes = [C.c_void_p, C.c_double, C.c_float]
@@ -814,6 +831,80 @@ class Binding:
         ms = (C.c_float * 3)(0, 0, 0)
         prm = detect_params(sigma1, sigma2, threshold)
         self.check(self.l.mvn_detect_time(int(device), int(bool(u16)), _dims(src_shape), C.byref(prm), int(reps), ms))
+        return float(ms[0]), float(ms[1]), float(ms[2])
+
+    # ---- bead registration (mvn_register_beads) ----------------------------------------------
+    @staticmethod
+    def _beads(p):
+        p = np.ascontiguousarray(p, dtype=np.float64)
+        if p.ndim != 2 or p.shape[1] != 3:
+            raise ValueError("bead lists are (N, 3)")
+        return p
+
+    def register_beads(self, a, b, max_error, ratio=3.0, hypotheses=1000, min_inliers=4, prior=None, seed=0, device=-1,
+                       with_candidates=False):
+        """mvn_register_beads: the affine matrix from the beads `a` of one view to the beads `b` of another ((N, 3)
+        float64, z y x, as detect_beads returns them) - descriptor matching, RANSAC, a least-squares refit.  `prior`: a
+        3 x 4 matrix applied to `a` for the descriptors (the stage rotation).  Returns (matrix (3, 4) float64 with
+        b ~ matrix (a; 1), pairs (K, 2) int32 of inliers in ascending i, errors (mean, max) float64); without a model
+        (None, an empty pairs array, None).  with_candidates=True appends the number of candidates."""
+        a, b = self._beads(a), self._beads(b)
+        prm = register_params(max_error, ratio, hypotheses, min_inliers, prior, seed)
+        d_p = C.POINTER(C.c_double)
+        m = np.full(12, np.nan, np.float64)
+        pairs = np.full((max(1, min(len(a), len(b))), 2), -1, np.int32)
+        err = np.full(2, np.nan, np.float64)
+        nc, ni = C.c_int(-1), C.c_int(-1)
+        self.check(self.l.mvn_register_beads(int(device), a.ctypes.data_as(d_p), len(a), b.ctypes.data_as(d_p), len(b),
+                                             C.byref(prm), m.ctypes.data_as(d_p), C.byref(nc), C.byref(ni), iptr(pairs),
+                                             err.ctypes.data_as(d_p), None))
+        if ni.value > 0:
+            out = (m.reshape(3, 4), pairs[:ni.value].copy(), err)
+        else:
+            out = (None, pairs[:0].copy(), None)
+        return out + (nc.value,) if with_candidates else out
+
+    def register_neighbours(self, p, device=-1):
+        """mvn_register_neighbours (test utility): each point's 4 nearest others by (distance, index), (N, 4) int32."""
+        p = self._beads(p)
+        idx = np.full((len(p), 4), -1, np.int32)
+        self.check(self.l.mvn_register_neighbours(int(device), p.ctypes.data_as(C.POINTER(C.c_double)), len(p), iptr(idx)))
+        return idx
+
+    def register_candidates(self, a, b, ratio=3.0, prior=None, device=-1):
+        """mvn_register_candidates (test utility): (pairs (K, 2) int32, distances (K, 2) float32 of d1 and d2)."""
+        a, b = self._beads(a), self._beads(b)
+        prm = register_params(1.0, ratio, 1, 4, prior, 0)
+        d_p = C.POINTER(C.c_double)
+        cap = max(1, min(len(a), len(b)))
+        pairs, d = np.full((cap, 2), -1, np.int32), np.full((cap, 2), np.nan, np.float32)
+        n = C.c_int(-1)
+        self.check(self.l.mvn_register_candidates(int(device), a.ctypes.data_as(d_p), len(a), b.ctypes.data_as(d_p), len(b),
+                                                  C.byref(prm), C.byref(n), iptr(pairs), fptr(d)))
+        return pairs[:n.value].copy(), d[:n.value].copy()
+
+    def register_sample(self, seed, h, n):
+        """mvn_register_sample: the four candidate indices of hypothesis h over n candidates."""
+        out = np.full(4, -1, np.int32)
+        self.check(self.l.mvn_register_sample(int(seed), int(h), int(n), iptr(out)))
+        return out
+
+    def register_memory(self, num_a, num_b, hypotheses=1000):
+        """mvn_register_memory: the bytes register_beads would allocate on the device."""
+        need = C.c_size_t(0)
+        self.check(self.l.mvn_register_memory(int(num_a), int(num_b), int(hypotheses), C.byref(need)))
+        return need.value
+
+    def register_counters(self):
+        """mvn_register_counters: (launches of the match pass, launches of the RANSAC pass, registrations completed)."""
+        out = (C.c_longlong * 3)(0, 0, 0)
+        self.check(self.l.mvn_register_counters(out))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def register_time(self, num_a, num_b, hypotheses, reps=3, device=0):
+        """mvn_register_time: ms of (the neighbour and descriptor pass of both sets, the match pass, the RANSAC pass)."""
+        ms = (C.c_float * 3)(0, 0, 0)
+        self.check(self.l.mvn_register_time(int(device), int(num_a), int(num_b), int(hypotheses), int(reps), ms))
         return float(ms[0]), float(ms[1]), float(ms[2])
 
     def resample_call(self, psi, raws, geoms, kernels1, kernels2, lambda_, min_value, iterations, weights=None,
